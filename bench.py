@@ -61,7 +61,49 @@ def parse():
     ap.add_argument("--no-modes", action="store_true", help="skip the `modes` block (mixed / parity throughput + logits deviation beside the bf16 headline)")
     ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` block (BASELINE.json configs[2..4] beside the headline)")
     ap.add_argument("--workload-steps", type=int, default=30, help="timed steps of each entry of the `workloads` block (5 warm-up steps, 4 rotating batches)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, head outputs, a fixed sample of the "
+                         "updated parameters and of their gradient) as DIR/<name>.npy, float32/float64, at most 64 MB (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE = 1 << 21          # parameter / gradient entries sampled (the flagship model has 31.7 M)
+
+
+def dump_outputs(ts, out_dir):
+    """What the timed path handed back in its last step, as float32 / float64 .npy files: the total loss and every per-layer loss,
+    the head outputs of the forward, and - the model itself being too large to dump whole - the same seeded sample of entries of the
+    updated parameters and of the step's gradient (`param_sample_index`: positions in the concatenation of the parameters, in
+    model.parameters() order).  Inputs, weights and the sample are functions of the command line alone, so two builds run with the
+    same arguments can be compared file by file."""
+    import re
+    torch.cuda.synchronize()
+    arrays = {"loss": ts.loss.detach().float().cpu().numpy()}
+    for k, v in ts._losses.items():
+        arrays["losses_" + re.sub(r"\W", "_", k)] = v.detach().float().cpu().numpy()
+    for k, v in ts._outs.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().float().cpu().numpy()
+    numels = np.array([p.numel() for p in ts.params], dtype=np.int64)
+    starts = np.cumsum(numels) - numels
+    total = int(numels.sum())
+    pos = np.sort(np.random.default_rng(0).choice(total, size=min(DUMP_SAMPLE, total), replace=False))
+    which = np.searchsorted(starts, pos, side="right") - 1
+    flat = torch.from_numpy(np.asarray(ts.offsets, dtype=np.int64)[which] + (pos - starts[which])).to(ts.flat_grad.device)
+    arrays["param_sample_index"] = pos.astype(np.float64)            # exact: every position is below 2**53
+    arrays["params_sample"] = ts.flat_param[flat].cpu().numpy()
+    arrays["grads_sample"] = ts.flat_grad[flat].cpu().numpy()
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, f"--dump-outputs: {nbytes} bytes exceed the {DUMP_MAX_BYTES} byte budget"
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {nbytes / 1e6:.1f} MB -> {out_dir}", file=sys.stderr, flush=True)
 
 
 def make_batch(rank, B, npts, dev, index=0, cfg=None):
@@ -326,6 +368,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     dt_local = dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ts, args.dump_outputs)           # before the instrumented steps below train the model any further
     comm = ts.comm_exposed_ms() if use_dist else None
     ts.comm_diag = False
     if not args.no_graph:

@@ -677,8 +677,7 @@ typedef struct u3d_declayer_dims {
   int32_t dtype;        /* U3D_BF16: bf16 activations / weights / slots, v_mfma_f32_16x16x32_bf16 (throughput mode);
                            U3D_F32: f32 everywhere, exact v_mfma_f32_16x16x4_f32 (parity mode) - the SAME kernels, instantiated on the
                            element type; every `void*` operand / slot below then holds f32 and xc may alias x */
-  int32_t dvalue_bf16;  /* backward, U3D_BF16 only: 1 = dvalue is a bf16 [rows][256] accumulator (packed bf16 atomics: two channels per
-                           atomic, no f32 volume to zero and to cast afterwards); 0 = f32 [rows][256] */
+  int32_t reserved;     /* 0 */
 } u3d_declayer_dims;
 /* forward-save slots (row matrices [m, cols]); u3d_decoder_layer_slots fills byte offsets (U3D_DS_COUNT + 1 entries, last = total) */
 enum {
@@ -710,12 +709,20 @@ int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_d
                               const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
                               float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, u3d_stream s);
 /* Gradients in: dx_out f32 [m,256] (NULL = zero), dreg f32 [m,code], dcls f32 [m,ncls], diou f32 [m].
- * Out: dx f32 [m,256] (w.r.t. the layer input x), dvalue f32 rows (ACCUMULATED with atomics: caller zero-fills once per step),
- * dref f32 [m,3] (only when need_dref), and the gradient workspace `grad` (dY slots for the caller's weight-gradient pass). */
+ * Out: dx f32 [m,256] (w.r.t. the layer input x), vrec: the value-gradient records (u3d_value_records_bytes(m) bytes: d(sample) f32
+ * [m][256], trilinear corner cells int32 [m][8] (-1 = outside the volume), corner weights f32 [m][8]) that u3d_value_scatter adds into
+ * the volume gradient, dref f32 [m,3] (only when need_dref), and the gradient workspace `grad` (dY slots for the weight-gradient pass). */
 int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
                               const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
                               const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                              void* dvalue, float* dref, void* grad, int64_t grad_bytes, u3d_stream s);
+                              void* vrec, float* dref, void* grad, int64_t grad_bytes, u3d_stream s);
+int64_t u3d_value_records_bytes(int32_t m);
+/* Adds the records of one u3d_decoder_layer_bwd call into dvalue [n_cells][256] (f32, or bf16 when dvalue_bf16): per cell the sum over
+ * its (row, corner) entries in ascending entry order, in f32, added once - bitwise reproducible.  work: u3d_value_scatter_workspace
+ * bytes of scratch (no contents required; initialised by the call, on stream s). */
+int64_t u3d_value_scatter_workspace(int32_t n_cells);
+int32_t u3d_value_scatter(const void* records, int32_t m, int32_t n_cells, void* dvalue, int32_t dvalue_bf16, void* work,
+                          int64_t work_bytes, u3d_stream s);
 /* Self-attention over groups on its own (the middle launch of the layer): q,k rows of qk [m,512] (q | k), v [m,256], 8 heads x 32;
  * o bf16 [m,256], lse f32 [m,8].  Backward: dqk [m,512], dv [m,256] bf16. */
 int32_t u3d_mha_fwd(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng, void* o,

@@ -1,7 +1,8 @@
 """ORACLE (test infrastructure).  Generates tests/golden/*.npz by running the REFERENCE's own files
-(/root/reference/projects/mmdet3d_plugin/..., loaded in place through oracle/refshim.py) on seeded inputs with
-name-seeded weights (oracle/weights.py).  Run in the build container only:  python -m oracle.make_golden
-Only inputs/outputs (data) are stored; no reference source travels.
+(<reference>/projects/mmdet3d_plugin/..., loaded in place through oracle/refshim.py) on seeded inputs with
+name-seeded weights (oracle/weights.py), and tests/golden/shipped_configs.txt from its configuration files.  Runs only where a
+reference tree is present (U3D_REFERENCE):  python -m oracle.make_golden [--check]
+Only inputs/outputs and configuration values (data) are stored; no reference source travels.
 """
 import os
 import sys
@@ -359,9 +360,39 @@ def gen_detector_glue(nd):
     print("detector_glue ok", tuple(y4.shape))
 
 
-def main():
-    if not rs.available():
-        sys.exit("reference tree not available: goldens can only be generated in the build container")
+# the sections of a shipped configuration the tests read (tests/test_plugin_cpu.py, test_schedule_cpu.py, test_configs_gpu.py)
+SHIPPED_KEYS = ("plugin", "plugin_dir", "dist_params", "model", "train_pipeline", "test_pipeline", "optimizer", "optimizer_config",
+                "lr_config", "momentum_config", "runner")
+
+
+def _plain(obj):
+    """ConfigDict -> dict, recursively (lists / tuples keep their type)."""
+    if isinstance(obj, dict):
+        return {k: _plain(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_plain(v) for v in obj)
+    return obj
+
+
+def gen_shipped_configs():
+    """The six shipped configurations (projects/configs/uni3detr/uni3detr_*.py) as uni3detr_amd.registry.Config.fromfile resolves
+    them (`_base_` files served from uni3detr_amd/configs/_base_/): per file its `_base_` list and the SHIPPED_KEYS sections, as one
+    Python literal (tuples stay tuples: the plugin checks e.g. `order` and `operation_order` against tuples), read with ast.literal_eval."""
+    import glob
+    import pprint
+    from uni3detr_amd.registry import Config, _exec_file
+    out = {}
+    for f in sorted(glob.glob(os.path.join(rs.REF_ROOT, "projects", "configs", "uni3detr", "uni3detr_*.py"))):
+        cfg = Config.fromfile(f)
+        bases = _exec_file(f).get("_base_", [])
+        out[os.path.basename(f)[len("uni3detr_"):-3]] = dict(bases=[bases] if isinstance(bases, str) else list(bases),
+                                                              config=_plain({k: cfg[k] for k in SHIPPED_KEYS if k in cfg}))
+    with open(os.path.join(OUT, "shipped_configs.txt"), "w") as fh:
+        fh.write(pprint.pformat(out, width=130, sort_dicts=True) + "\n")
+    print("shipped_configs:", sorted(out))
+
+
+def generate():
     os.makedirs(OUT, exist_ok=True)
     ns = rs.load_hot_path()
     gen_small(ns)
@@ -374,6 +405,48 @@ def main():
     gen_dense_stack(nd)
     gen_encoder_wiring(nd)
     gen_detector_glue(nd)
+    gen_shipped_configs()
+
+
+def check():
+    """Regenerate every fixture into a scratch directory and compare it with the committed one: arrays bit for bit (names and dtypes
+    included), the configuration file byte for byte.  Returns the list of differences."""
+    import tempfile
+    global OUT
+    golden, bad = OUT, []
+    with tempfile.TemporaryDirectory() as tmp:
+        OUT = tmp
+        try:
+            generate()
+        finally:
+            OUT = golden
+        names = sorted(os.listdir(golden))
+        if names != sorted(os.listdir(tmp)):
+            bad.append(f"fixture set differs: {names} vs {sorted(os.listdir(tmp))}")
+        for name in names:
+            p, q = os.path.join(golden, name), os.path.join(tmp, name)
+            if not os.path.exists(q):
+                continue
+            if name.endswith(".npz"):
+                a, b = np.load(p, allow_pickle=False), np.load(q, allow_pickle=False)
+                if sorted(a.files) != sorted(b.files):
+                    bad.append(f"{name}: arrays {sorted(a.files)} vs {sorted(b.files)}")
+                bad += [f"{name}:{k}" for k in a.files if k in b.files and not (a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]))]
+            elif open(p, "rb").read() != open(q, "rb").read():
+                bad.append(name)
+    return bad
+
+
+def main():
+    """python -m oracle.make_golden          regenerate tests/golden/ from the reference tree
+       python -m oracle.make_golden --check  regenerate into a scratch directory and compare with the committed fixtures"""
+    if not rs.available():
+        sys.exit(f"reference tree not available at {rs.REF_ROOT} (set U3D_REFERENCE): goldens can only be generated from it")
+    if "--check" in sys.argv[1:]:
+        bad = check()
+        print("golden check:", "every fixture regenerates bit-identically" if not bad else f"{len(bad)} difference(s): {bad}")
+        sys.exit(1 if bad else 0)
+    generate()
 
 
 if __name__ == "__main__":

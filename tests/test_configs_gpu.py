@@ -1,8 +1,10 @@
-"""GPU: the other shipped configurations (BASELINE.json configs[2..4]) build from the reference config files when present
-(else from restated key numbers), run one training step on scaled synthetic clouds and produce finite losses and gradients.
+"""GPU: the other shipped configurations (BASELINE.json configs[2..4]) build from the shipped config files' values
+(tests/golden/shipped_configs.txt, as Config.fromfile resolves them), run one training step on scaled synthetic clouds and produce
+finite losses and gradients.
 nuScenes (BASELINE configs[4]: 2 scenes, 2700 training queries, code size 10) trains too: the reference's own target line slices to 7
 columns and cannot feed its 10-column L1, so the step follows the commented-out upstream `[..., :9]` semantics
 with zero velocities for 7-column GT (plugin/head.py gt_dim; oracle/model.py loss_single makes the same choice and pins it)."""
+import ast
 import os
 
 import numpy as np
@@ -11,20 +13,15 @@ import torch
 
 import projects.mmdet3d_plugin  # noqa: F401
 from uni3detr_amd.plugin.structures import Boxes3D
-from uni3detr_amd.registry import Config, build_model
+from uni3detr_amd.registry import build_model, to_config
 from uni3detr_amd.synth import room_scene
 
 pytestmark = pytest.mark.gpu
-REF_CFG = "/root/reference/projects/configs/uni3detr"
+SHIPPED = os.path.join(os.path.dirname(__file__), "golden", "shipped_configs.txt")
 
 
 def _cfg(name):
-    import copy
-    from uni3detr_amd.configs import variants
-    p = os.path.join(REF_CFG, f"uni3detr_{name}.py")
-    if os.path.exists(p):
-        return Config.fromfile(p).model
-    return copy.deepcopy(getattr(variants, name))
+    return to_config(ast.literal_eval(open(SHIPPED).read())[name]["config"]["model"])
 
 
 def _scene(i, n, rng_range, nfeat):

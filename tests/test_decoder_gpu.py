@@ -367,11 +367,10 @@ def test_head_bf16_fused_path_matches_layerwise_path(cuda):
 
 @pytest.mark.parametrize("spread", [1.0, 0.02], ids=["spread", "clustered"])
 def test_packed_bf16_volume_gradient_scatter_vs_f32_accumulator(cuda, spread):
-    """the OPT-IN packed-bf16 scatter (fused_decoder.PK_SCATTER) accumulates the value-volume gradient of all 3 layers x 3
-    query groups in ONE bf16 buffer through global_atomic_pk_add_bf16.  Every add rounds to 8 mantissa bits, so the error grows with
-    the contributions per cell: measured against the f32 accumulator (the default: rounded once) 0.7 % with the queries spread over the
-    volume, 9.4 % with all 600 FPS queries of a scene inside a 2 % cube (hundreds of contributions per cell) - which is why the f32
-    accumulator is the default.  Gates: spread <= 1 %, clustered <= 15 % (a bound on the documented drift, not an endorsement)."""
+    """the OPT-IN bf16 accumulator (fused_decoder.PK_SCATTER) collects the value-volume gradient of all 3 layers in ONE bf16
+    buffer; each layer's per-cell sum (f32, fixed order: native.value_scatter) is rounded to 8 mantissa bits as it is added.  Measured
+    against the f32 accumulator (the default) with the queries spread over the volume and with all 600 FPS queries of a scene inside a
+    2 % cube.  Gates: spread <= 1 %, clustered <= 15 %."""
     from uni3detr_amd.plugin import fused_decoder as fdm
     head = make_head(cuda, 11)
     for m in head.modules():
@@ -591,3 +590,59 @@ def test_uncovered_decoder_call_raises_instead_of_running_vendor_kernels(cuda):
     with pytest.raises(RuntimeError, match="no vendor-kernel"):
         with torch.autocast("cuda", dtype=torch.float16):
             head(feats, None, fps)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+def test_value_scatter_sums_each_cell_in_a_fixed_order(cuda, dt):
+    """native.value_scatter against a float64 index_add of the same records: out-of-volume corners (-1) skipped, cells with more
+    entries than the kernel's id list (one cell takes 300) summed too, and the result bitwise the same on every call."""
+    g = torch.Generator(device="cpu").manual_seed(17)
+    m, cells = 2000, 5000
+    ds = torch.randn(m, 256, generator=g)
+    cell = torch.randint(0, cells, (m, 8), generator=g, dtype=torch.int32)
+    cell[torch.rand(m, 8, generator=g) < 0.1] = -1
+    cell[:300, 0] = 7                                           # a crowded cell: beyond the per-cell id list
+    cell[300:310, :] = 11                                       # one row hitting the same cell with all eight corners
+    w = torch.rand(m, 8, generator=g)
+    rec = torch.cat([ds.reshape(-1).view(torch.uint8), cell.reshape(-1).view(torch.uint8), w.reshape(-1).view(torch.uint8)]).to(cuda)
+    assert rec.numel() == nv.lib().u3d_value_records_bytes(m)
+    ref = torch.zeros(cells, 256, dtype=torch.float64)
+    ok = cell.reshape(-1) >= 0
+    rows = torch.arange(m).repeat_interleave(8)[ok]
+    ref.index_add_(0, cell.reshape(-1)[ok].long(), ds.double()[rows] * w.reshape(-1)[ok].double()[:, None])
+    outs = []
+    for _ in range(3):
+        dv = torch.zeros(cells, 256, dtype=dt, device=cuda)
+        nv.value_scatter(rec, m, dv)
+        outs.append(dv)
+    assert all(torch.equal(o, outs[0]) for o in outs[1:])
+    got = outs[0].double().cpu()
+    tol = 1e-5 if dt == torch.float32 else 8e-3                 # one f32 sum per cell; bf16: rounded once on the way in
+    assert float((got - ref).abs().max()) <= tol * float(ref.abs().max())
+    assert bool((got[ref.abs().sum(1) == 0] == 0).all())
+
+
+@pytest.mark.parametrize("spread", [1.0, 0.02], ids=["spread", "clustered"])
+def test_value_volume_gradient_is_bitwise_reproducible(cuda, spread):
+    """The gradient w.r.t. the sampled feature volume - the one the neck, backbone and encoder backward start from - is the same bit for
+    bit on every run of the same step (queries spread over the volume, and clustered so that cells collect hundreds of contributions)."""
+    head = make_head(cuda, 11)
+    for mod in head.modules():
+        if isinstance(mod, torch.nn.Dropout):
+            mod.p = 0.0
+        if hasattr(mod, "attn_drop"):
+            mod.attn_drop = 0.0
+    g = torch.Generator(device="cpu").manual_seed(5)
+    feats = torch.randn(2, 256, 15, 40, 40, generator=g).clamp_min(0).to(cuda).to(memory_format=torch.channels_last_3d)
+    fps = (0.5 + (torch.rand(2, 600, 3, generator=g) - 0.5) * spread).to(cuda)
+    grads = []
+    for _ in range(3):
+        f = feats.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            outs = head(f, None, fps)
+        tot = sum((v.float() ** 2).sum() * w for v, w in zip((outs["all_cls_scores"], outs["all_bbox_preds"], outs["all_iou_preds"]), (1.0, 0.1, 1.0)))
+        head.zero_grad(set_to_none=True)
+        tot.backward()
+        grads.append(f.grad.clone())
+    assert float(grads[0].abs().sum()) > 0
+    assert all(torch.equal(x, grads[0]) for x in grads[1:])

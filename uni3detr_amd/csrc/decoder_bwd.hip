@@ -151,8 +151,11 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
                                                              const unsigned long long* __restrict__ rng, DcSave<E> S, DcGrad<E> Gd,
                                                              const float* __restrict__ dx_out, const float* __restrict__ dreg,
                                                              const float* __restrict__ dcls, const float* __restrict__ diou,
-                                                             void* __restrict__ dvalue_v, float* __restrict__ dref) {
-  float* const dvalue = (float*)dvalue_v;
+                                                             void* __restrict__ vrec, float* __restrict__ dref) {
+  // value-gradient records (u3d_value_records_bytes): d(sample) f32 [m][256], corner cells int32 [m][8], corner weights f32 [m][8]
+  float* const rec_ds = (float*)vrec;
+  int* const rec_cell = (int*)(rec_ds + (size_t)dm.m * DC_C);
+  float* const rec_w = (float*)(rec_cell + (size_t)dm.m * 8);
   typedef typename E::T T;
   typedef typename E::V4 V4;
   typedef DcLds<E> L;
@@ -429,42 +432,28 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
       float dsc[4];                                                  // the same d(sample) values, channel j*64 + lane
 #pragma unroll
       for (int j = 0; j < 4; ++j) dsc[j] = E::round(G[row * DC_TS + j * 64 + lane] * gate);
-      float dsp[2][2];                                               // ... and as channel pairs (j*128 + 2*lane, + 1) for the packed bf16 atomics
-#pragma unroll
-      for (int j = 0; j < 2; ++j) { dsp[j][0] = E::round(G[row * DC_TS + j * 128 + 2 * lane] * gate); dsp[j][1] = E::round(G[row * DC_TS + j * 128 + 2 * lane + 1] * gate); }
       DcCorners tc;
       dc_corners<E>(misc + row * DC_MISC_LD, min(gr, M - 1) / dm.qps, dm.dz, dm.dy, dm.dx, tc);
+      if (ok) {
+        // the trilinear scatter itself is u3d_value_scatter's: this row's d(sample) and its eight (cell, weight) pairs go to the
+        // records, and the volume gradient is summed per cell in a fixed order there (atomics here made it run-to-run different)
+        float* rds = rec_ds + (size_t)gr * DC_C + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rds[j * 64] = dsc[j];
+        if (lane == 0) {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) { rec_cell[(size_t)gr * 8 + c] = tc.row[c]; rec_w[(size_t)gr * 8 + c] = tc.w[c]; }
+        }
+      }
       float gx = 0.f, gy = 0.f, gz = 0.f;
 #ifndef DC_ABL_NOGATHER
-      if (ok) {
+      if (ok && dm.need_dref) {
 #pragma unroll
         for (int c = 0; c < 8; ++c)
           if (tc.row[c] >= 0) {
-            // lane l adds channels l, l + 64, l + 128, l + 192: one atomic instruction then covers 64 CONSECUTIVE floats (two cache
-            // lines) - with the MFMA-side mapping (channels 4l .. 4l+3) each of the four instructions touched all eight lines of
-            // the row, and the L2 atomic unit works a line at a time (125 of this kernel's 316 us were these atomics)
-            if (E::DT == U3D_BF16 && dm.dvalue_bf16) {
-              // bf16 accumulator: lane l adds the channel PAIRS (2l, 2l+1) and (128 + 2l, 128 + 2l + 1) - global_atomic_pk_add_bf16,
-              // 64 lanes x 4 B = 256 consecutive bytes per instruction, two instructions per corner instead of four, and the volume
-              // gradient needs neither a 196 MB f32 zero-fill nor a cast pass (a cell collects a handful of contributions at most)
-              typedef short s16x2 __attribute__((ext_vector_type(2)));
-              typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-              u16* dvp = (u16*)dvalue_v + (size_t)tc.row[c] * DC_C + 2 * lane;
-#pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                const bf16x2_t pv = {(__bf16)(tc.w[c] * dsp[j][0]), (__bf16)(tc.w[c] * dsp[j][1])};
-                __builtin_amdgcn_global_atomic_fadd_v2bf16((s16x2 __attribute__((address_space(1)))*)(dvp + j * 128), __builtin_bit_cast(s16x2, pv));
-              }
-            } else {
-              float* dvr = dvalue + (size_t)tc.row[c] * DC_C + lane;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) atomicAdd(dvr + j * 64, tc.w[c] * dsc[j]);
-            }
-            if (dm.need_dref) {
-              const f32x4 val = E::unpack4(*(const V4*)(value + (size_t)tc.row[c] * DC_C + lane * 4));
-              const float dot = val[0] * ds[0] + val[1] * ds[1] + val[2] * ds[2] + val[3] * ds[3];
-              gx += tc.dwx[c] * dot; gy += tc.dwy[c] * dot; gz += tc.dwz[c] * dot;
-            }
+            const f32x4 val = E::unpack4(*(const V4*)(value + (size_t)tc.row[c] * DC_C + lane * 4));
+            const float dot = val[0] * ds[0] + val[1] * ds[1] + val[2] * ds[2] + val[3] * ds[3];
+            gx += tc.dwx[c] * dot; gy += tc.dwy[c] * dot; gz += tc.dwz[c] * dot;
           }
       }
 #endif
@@ -871,10 +860,116 @@ extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d
   int32_t rc = dcb_check(p, d);
   if (rc != U3D_OK) return rc;
   U3D_REQUIRE(ref && value && save && dreg && dcls && diou && dx && dvalue && grad, U3D_ERR_ARG);
-  U3D_REQUIRE(!d->dvalue_bf16 || d->dtype == U3D_BF16, U3D_ERR_ARG);
+  U3D_REQUIRE(d->reserved == 0, U3D_ERR_ARG);
   U3D_REQUIRE(!d->need_dref || dref, U3D_ERR_ARG);
   U3D_REQUIRE((d->p_attn == 0.f && d->p_drop == 0.f) || rng, U3D_ERR_ARG);
   if (d->dtype == U3D_BF16)
     return dcb_layer_bwd<EB>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
   return dcb_layer_bwd<EF>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// u3d_value_scatter: the trilinear scatter of the layer's d(sample) rows into the value-volume gradient, in a fixed order.
+// k_vs_register lists every (row, corner) entry e = row * 8 + corner under its cell with integer atomics only (count, the smallest
+// entry as the cell's owner, up to VS_K entry ids); k_vs_reduce: the owner's wave sorts the cell's ids and sums w * d(sample) in
+// ascending entry order in f32 and adds the sum to the accumulator once (the only writer of that cell).  A cell with more than VS_K
+// entries is summed by scanning all entries in order instead.  The workspace is the caller's, initialised by every call.
+// ---------------------------------------------------------------------------------------------------------------------------
+#define VS_K 64
+#define VS_NONE 0x7fffffff
+
+__global__ void k_vs_init(int* __restrict__ cnt, int* __restrict__ owner, int n_cells) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_cells) { cnt[i] = 0; owner[i] = VS_NONE; }
+}
+
+__global__ void k_vs_register(const int* __restrict__ cell, int n_entries, int n_cells, int* __restrict__ cnt, int* __restrict__ owner,
+                              int* __restrict__ list) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_entries) return;
+  const int c = cell[e];
+  if (c < 0 || c >= n_cells) return;
+  atomicMin(&owner[c], e);
+  const int slot = atomicAdd(&cnt[c], 1);
+  if (slot < VS_K) list[(size_t)c * VS_K + slot] = e;
+}
+
+__device__ __forceinline__ unsigned short vs_bf16_rne(float f) {
+  const unsigned int u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);     // NaN stays a (quiet) NaN
+  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+__device__ __forceinline__ void vs_add_entry(const float* __restrict__ ds, const float* __restrict__ w, int id, int lane, float* acc) {
+  const float wt = w[id];
+  const float* src = ds + (size_t)(id >> 3) * 256 + lane;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] += wt * src[j * 64];
+}
+
+// one wave per entry (4 per 256-thread block); lane l owns channels l, l + 64, l + 128, l + 192
+__global__ __launch_bounds__(256) void k_vs_reduce(const float* __restrict__ ds, const int* __restrict__ cell, const float* __restrict__ w,
+                                                   int n_entries, int n_cells, int* __restrict__ cnt, int* __restrict__ owner,
+                                                   const int* __restrict__ list, void* __restrict__ dvalue, int dvalue_bf16) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int e = blockIdx.x * 4 + wave;
+  if (e >= n_entries) return;
+  const int c = cell[e];
+  if (c < 0 || c >= n_cells || owner[c] != e) return;            // wave-uniform
+  const int n = cnt[c];
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if (n <= VS_K) {                                                 // VS_K == 64: one listed id per lane
+    const int mine = lane < n ? list[(size_t)c * VS_K + lane] : VS_NONE;
+    int rank = 0;                                                  // ids are distinct: the rank is the sorted position
+    for (int k = 0; k < n; ++k) rank += __shfl(mine, k) < mine;
+    for (int k = 0; k < n; ++k)
+      vs_add_entry(ds, w, __shfl(mine, __builtin_ctzll(__ballot(lane < n && rank == k))), lane, acc);   // the k-th smallest id
+  } else {
+    for (int base = 0; base < n_entries; base += 256) {            // all entries in order; four loads in flight per lane
+      int cc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) cc[q] = base + q * 64 + lane < n_entries ? cell[base + q * 64 + lane] : -1;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        unsigned long long m = __ballot(cc[q] == c);
+        while (m) {
+          vs_add_entry(ds, w, base + q * 64 + __builtin_ctzll(m), lane, acc);
+          m &= m - 1;
+        }
+      }
+    }
+  }
+  if (dvalue_bf16) {
+    unsigned short* dst = (unsigned short*)dvalue + (size_t)c * 256 + lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[j * 64] = vs_bf16_rne(__uint_as_float((unsigned int)dst[j * 64] << 16) + acc[j]);
+  } else {
+    float* dst = (float*)dvalue + (size_t)c * 256 + lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[j * 64] += acc[j];
+  }
+}
+
+extern "C" int64_t u3d_value_records_bytes(int32_t m) { return m < 0 ? 0 : (int64_t)m * (256 * 4 + 8 * 4 + 8 * 4); }
+
+extern "C" int64_t u3d_value_scatter_workspace(int32_t n_cells) { return n_cells < 0 ? 0 : (int64_t)n_cells * (2 + VS_K) * 4; }
+
+extern "C" int32_t u3d_value_scatter(const void* records, int32_t m, int32_t n_cells, void* dvalue, int32_t dvalue_bf16, void* work,
+                                     int64_t work_bytes, u3d_stream s) {
+  U3D_REQUIRE(records && dvalue && work && m > 0 && n_cells > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(work_bytes >= u3d_value_scatter_workspace(n_cells), U3D_ERR_WORKSPACE);
+  U3D_REQUIRE((int64_t)m * 8 < (1ll << 31), U3D_ERR_UNSUPPORTED);
+  const float* ds = (const float*)records;
+  const int* cell = (const int*)(ds + (size_t)m * 256);
+  const float* w = (const float*)(cell + (size_t)m * 8);
+  int* cnt = (int*)work;
+  int* owner = cnt + n_cells;
+  int* list = owner + n_cells;
+  const int n_entries = m * 8;
+  hipLaunchKernelGGL(k_vs_init, dim3((n_cells + 255) / 256), dim3(256), 0, s, cnt, owner, n_cells);
+  hipLaunchKernelGGL(k_vs_register, dim3((n_entries + 255) / 256), dim3(256), 0, s, cell, n_entries, n_cells, cnt, owner, list);
+  hipLaunchKernelGGL(k_vs_reduce, dim3((n_entries + 3) / 4), dim3(256), 0, s, ds, cell, w, n_entries, n_cells, cnt, owner,
+                     (const int*)list, dvalue, dvalue_bf16);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
 }

@@ -43,7 +43,7 @@ class DecLayerParams(C.Structure):
 class DecLayerDims(C.Structure):
     """u3d_declayer_dims."""
     _fields_ = [(n, C.c_int32) for n in ("m", "nq", "qps", "batch", "dz", "dy", "dx", "ncls", "code", "has_qs", "need_dref", "layer")] + \
-               [("p_attn", C.c_float), ("p_drop", C.c_float), ("ln_eps", C.c_float), ("dtype", C.c_int32), ("dvalue_bf16", C.c_int32)]
+               [("p_attn", C.c_float), ("p_drop", C.c_float), ("ln_eps", C.c_float), ("dtype", C.c_int32), ("reserved", C.c_int32)]
 
 
 class WPackDesc(C.Structure):
@@ -197,6 +197,9 @@ _SIGS = {
     "u3d_mha_bwd_dt": (_I, [_P, _P, _P, _P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _I, _P]),
     "u3d_dropout_mask": (_I, [_P, _I, _I, _L, C.c_float, _I, _P, _P]),
     "u3d_scatter_rows": (_I, [_P, _P, _I, _I, _P, _P]),
+    "u3d_value_records_bytes": (_L, [_I]),
+    "u3d_value_scatter_workspace": (_L, [_I]),
+    "u3d_value_scatter": (_I, [_P, _I, _I, _P, _I, _P, _L, _P]),
 }
 
 
@@ -1662,17 +1665,30 @@ def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save):
 
 
 def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad):
-    """dvalue: f32 [rows, 256] accumulator, or (bf16 kernels only) a bf16 one - packed bf16 atomics, see u3d_declayer_dims.dvalue_bf16."""
+    """dvalue: f32 [rows, 256] accumulator, or (bf16 kernels only) a bf16 one: the layer's value-volume gradient is ADDED to it, summed
+    per cell in a fixed order (value_scatter: bitwise reproducible)."""
     m = dims.m
-    dims.dvalue_bf16 = 1 if dvalue.dtype == torch.bfloat16 else 0
+    dims.reserved = 0
     assert dvalue.dtype == torch.float32 or dims.dtype == DT_BF16
+    rec = torch.empty(int(lib().u3d_value_records_bytes(m)), dtype=torch.uint8, device=ref.device)
     mp = decoder_rows(m, torch.bfloat16 if dims.dtype == DT_BF16 else torch.float32)
     dx = torch.empty((mp, 256), dtype=torch.float32, device=ref.device)
     dref = torch.empty((mp, 3), dtype=torch.float32, device=ref.device) if dims.need_dref else None
     _check(lib().u3d_decoder_layer_bwd(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
                                        _ptr(xc_out), _ptr(save), _ptr(dx_out), _ptr(dreg), _ptr(dcls), _ptr(diou), _ptr(dx),
-                                       _ptr(dvalue), _ptr(dref), _ptr(grad), grad.numel(), _stream()), "decoder_layer_bwd")
+                                       _ptr(rec), _ptr(dref), _ptr(grad), grad.numel(), _stream()), "decoder_layer_bwd")
+    value_scatter(rec, m, dvalue)
     return dx[:m], (None if dref is None else dref[:m])
+
+
+def value_scatter(records, m, dvalue):
+    """Adds one decoder layer's value-gradient records (u3d_decoder_layer_bwd) into dvalue [cells, 256] (f32 or bf16), per cell in a
+    fixed order.  The per-cell bookkeeping is scratch of this call (stream-ordered allocation, initialised by the kernel)."""
+    assert dvalue.is_contiguous() and dvalue.shape[1] == 256 and dvalue.dtype in (torch.float32, torch.bfloat16)
+    n = dvalue.shape[0]
+    work = torch.empty(int(lib().u3d_value_scatter_workspace(n)), dtype=torch.uint8, device=dvalue.device)
+    _check(lib().u3d_value_scatter(_ptr(records), m, n, _ptr(dvalue), int(dvalue.dtype == torch.bfloat16), _ptr(work), work.numel(),
+                                   _stream()), "value_scatter")
 
 
 def mha_fwd(qk, v, nq, p_attn=0.0, layer=0, rng=None):

@@ -21,10 +21,9 @@ from torch import nn
 from .. import native as nv
 
 ENABLED = True         # test-only module attribute: the GPU tests set it False to run the layer-by-layer formulation next to the fused one
-# trilinear scatter of the value-volume gradient with global_atomic_pk_add_bf16 into a bf16 accumulator (two channels per atomic, no f32
-# volume to zero and cast: -0.07 ms per step).  OPT-IN: every add rounds to 8 mantissa bits, and all 3 layers x 3 query groups land in one
-# buffer - with queries clustered on objects a cell collects hundreds of contributions and the result drifts 9 % from the f32
-# accumulator (tests/test_decoder_gpu.py::test_packed_bf16_volume_gradient_scatter_vs_f32_accumulator; 0.7 % with spread queries).
+# value-volume gradient accumulated over the decoder layers in a bf16 buffer instead of an f32 one (no f32 volume to zero and cast).
+# OPT-IN: each layer's per-cell sum is rounded to 8 mantissa bits as it is added
+# (tests/test_decoder_gpu.py::test_packed_bf16_volume_gradient_scatter_vs_f32_accumulator).
 SHARED_DEFER = True     # test-only module attribute: shared linears' gradients summed by the deferred flush (False: autograd adds them)
 PK_SCATTER = os.environ.get("U3D_PK_SCATTER", "0") == "1"
 POISON = os.environ.get("U3D_DEC_POISON", "0") == "1"      # debugging: NaN-fill the workspaces (read-before-write shows up as NaN)
@@ -289,8 +288,8 @@ class FusedLayerFn(torch.autograd.Function):
         dreg, dcls, diou = z(dreg, (M, sp.code)), z(dcls, (M, sp.ncls)), z(diou, (M,))
         dx_out = None if dx_out is None else dx_out.contiguous().float()
         want_dv = ctx.needs_input_grad[3]
-        # bf16 kernels: the volume gradient accumulates in bf16 through packed atomics (two channels per atomic; no f32 volume to zero and
-        # cast).  A cell collects a handful of contributions at most, each already rounded to bf16 on the way into the conv backward.
+        # each layer's volume gradient is summed per cell in a fixed order and added once (native.value_scatter); with PK_SCATTER and
+        # bf16 kernels the accumulator over the layers is bf16 (no f32 volume to zero and cast), else f32
         acc_dt = torch.bfloat16 if (PK_SCATTER and rows.dtype == torch.bfloat16) else torch.float32
         if accum is not None:
             if accum.buf is None:
