@@ -619,6 +619,33 @@ int32_t u3d_box_merge(const float* boxes, const int32_t* labels, int32_t n, floa
                       int64_t workspace_bytes, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Indoor 3-D detection evaluation: per-class AP ('area' mode) and recall at 3-D IoU thresholds (ref:
+ * projects/mmdet3d_plugin/core/indoor_eval.py eval_det_cls :58-140 and average_precision :7-55, as called by indoor_eval_ov :168-303;
+ * the reference loops over every detection in Python).  Detections and GT are concatenated over scenes: det_off / gt_off int32 [n_scene+1]
+ * (CSR), boxes f32 [.,7] bottom-centre (x, y, z, dx, dy, dz, yaw), labels int32 in [0, num_classes), scores finite f32.
+ * u3d_eval_iou_argmax: per detection, over the GT of its scene and class (rotated 3-D IoU of mmdet3d's DepthInstance3DBoxes.overlaps):
+ *   iou_max f32 [n_det] (-inf without such GT) and jmax int32 [n_det] (global GT index of the FIRST maximal IoU, -1 without), and
+ *   sort_key int64 [n_det] = (label << 32) | descending-orderable score bits.  The caller sorts the keys STABLY (perm int64 [n_det]):
+ *   ties keep (scene, position in the scene).  n_det == 0 (n_scene == 0 included) is a no-op.
+ * u3d_eval_segments: seg int32 [2*num_classes] = [lo, hi) of each class in the sorted keys; npos int32 [num_classes] = GT per class.
+ * u3d_eval_first_hit: first int32 [n_thr][n_gt] = lowest rank r (position in perm) with iou_max > thr[t] and jmax == GT (0x7f7f7f7f if
+ *   none); thr f32 [n_thr] on the device.  u3d_eval_tp: tp uint8 [n_thr][n_det] in rank order = the reference's greedy TP flags.
+ * u3d_eval_ap: ap f32 [n_thr][num_classes] (float64 sum rounded to float32), rec f64 [n_thr][num_classes] (final recall); NaN for a
+ *   class that is predicted but has no GT; prec_ws f64 [n_thr][n_gt] workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t u3d_eval_iou_argmax(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const int32_t* det_off,
+                            const float* gt_boxes, const int32_t* gt_labels, const int32_t* gt_off, int32_t n_scene, int32_t n_det,
+                            float* iou_max, int32_t* jmax, int64_t* sort_key, u3d_stream s);
+int32_t u3d_eval_segments(const int64_t* sorted_key, int32_t n_det, const int32_t* gt_labels, int32_t n_gt, int32_t num_classes,
+                          int32_t* seg, int32_t* npos, u3d_stream s);
+int32_t u3d_eval_first_hit(const int64_t* perm, int32_t n_det, const float* iou_max, const int32_t* jmax, const float* thr, int32_t n_thr,
+                           int32_t n_gt, int32_t* first, u3d_stream s);
+int32_t u3d_eval_tp(const int64_t* perm, int32_t n_det, const float* iou_max, const int32_t* jmax, const float* thr, int32_t n_thr,
+                    int32_t n_gt, const int32_t* first, uint8_t* tp, u3d_stream s);
+int32_t u3d_eval_ap(const uint8_t* tp, int32_t n_det, const int32_t* seg, const int32_t* npos, int32_t num_classes, int32_t n_thr,
+                    int32_t n_gt, double* prec_ws, float* ap, double* rec, u3d_stream s);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused decoder layer (bf16 MFMA, f32 accumulation / residual stream / LayerNorm statistics / softmax statistics).
  * One call = one Uni3DETRTransformerDecoder layer over ALL query groups of all scenes, plus everything the decoder loop and the head
  * hang on that layer's state (ref: models/utils/uni3detr_transformer.py:145-212 decoder loop, :33-65 sine embedding, :271-360

@@ -183,6 +183,11 @@ _SIGS = {
     "u3d_soft_nms": (_I, [_P, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
     "u3d_box_merge_workspace": (_L, [_I]),
     "u3d_box_merge": (_I, [_P, _P, _I, C.c_float, _P, _P, _P, _L, _P]),
+    "u3d_eval_iou_argmax": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "u3d_eval_segments": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
+    "u3d_eval_first_hit": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "u3d_eval_tp": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "u3d_eval_ap": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "u3d_decoder_layer_slots": (_I, [_I, _I, _I, _P, _P]),
     "u3d_decoder_layer_blocks": (_I, [_I]),
     "u3d_decoder_layer_fwd": (_I, [C.POINTER(DecLayerParams), C.POINTER(DecLayerDims)] + [_P] * 11 + [_L, _P]),
@@ -1307,6 +1312,39 @@ def box_merge(boxes_sorted, labels_sorted, thr):
     _check(lib().u3d_box_merge(_ptr(boxes_sorted.contiguous().float()), _ptr(labels_sorted.contiguous().int()), n, float(thr), _ptr(merged),
                                _ptr(keep), _ptr(ws), ws.numel(), _stream()), "box_merge")
     return merged, keep.bool()
+
+
+def eval_iou_argmax(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off):
+    """Per detection: best same-scene, same-class GT -> (iou_max f32 [N] (-inf: none), jmax int32 [N] (-1: none), sort key int64 [N])."""
+    n, dev = det_boxes.shape[0], det_off.device
+    iou = torch.empty((n,), dtype=torch.float32, device=dev)
+    jmax = torch.empty((n,), dtype=torch.int32, device=dev)
+    key = torch.empty((n,), dtype=torch.int64, device=dev)
+    _check(lib().u3d_eval_iou_argmax(_ptr(det_boxes), _ptr(det_scores), _ptr(det_labels), _ptr(det_off), _ptr(gt_boxes), _ptr(gt_labels),
+                                     _ptr(gt_off), det_off.numel() - 1, n, _ptr(iou), _ptr(jmax), _ptr(key), _stream()), "eval_iou_argmax")
+    return iou, jmax, key
+
+
+def eval_indoor(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, num_classes, thr):
+    """Indoor AP / recall on the device (u3d_eval_*).  Boxes f32 [.,7] bottom-centre, labels int32, offsets int32 [S+1], thr f32 [T]
+    (device).  -> dict of device tensors: iou_max, jmax, perm (rank -> detection), seg [C,2], npos [C], tp uint8 [T,N] (rank order),
+    ap f32 [T,C], rec f64 [T,C].  No host synchronisation."""
+    n, g, t = det_boxes.shape[0], gt_boxes.shape[0], thr.numel()
+    dev = det_off.device
+    iou, jmax, key = eval_iou_argmax(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off)
+    key_s, perm = torch.sort(key, stable=True)                 # stable: ties keep (scene, position in the scene)
+    seg = torch.empty((num_classes, 2), dtype=torch.int32, device=dev)
+    npos = torch.empty((num_classes,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_eval_segments(_ptr(key_s), n, _ptr(gt_labels), g, num_classes, _ptr(seg), _ptr(npos), _stream()), "eval_segments")
+    first = torch.empty((t, g), dtype=torch.int32, device=dev)
+    tp = torch.empty((t, n), dtype=torch.uint8, device=dev)
+    _check(lib().u3d_eval_first_hit(_ptr(perm), n, _ptr(iou), _ptr(jmax), _ptr(thr), t, g, _ptr(first), _stream()), "eval_first_hit")
+    _check(lib().u3d_eval_tp(_ptr(perm), n, _ptr(iou), _ptr(jmax), _ptr(thr), t, g, _ptr(first), _ptr(tp), _stream()), "eval_tp")
+    prec = torch.empty((t, g), dtype=torch.float64, device=dev)
+    ap = torch.empty((t, num_classes), dtype=torch.float32, device=dev)
+    rec = torch.empty((t, num_classes), dtype=torch.float64, device=dev)
+    _check(lib().u3d_eval_ap(_ptr(tp), n, _ptr(seg), _ptr(npos), num_classes, t, g, _ptr(prec), _ptr(ap), _ptr(rec), _stream()), "eval_ap")
+    return dict(iou_max=iou, jmax=jmax, perm=perm, seg=seg, npos=npos, tp=tp, ap=ap, rec=rec)
 
 
 def count_tensor(n, device):

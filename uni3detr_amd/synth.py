@@ -58,3 +58,37 @@ def uniform_scene(scene_id, n_points=20000, pc_range=SUNRGBD_RANGE, seed_base=43
     p = lo + rng.random((n_points, 3)) * (hi - lo)
     h = p[:, 2:3] - p[:, 2].min()
     return np.concatenate([p, h], 1).astype(np.float32)
+
+
+def eval_scenes(n_scenes, n_det, num_classes, seed=0, max_gt=12, pc_range=SUNRGBD_RANGE, tp_frac=0.3, dup=3):
+    """Seeded detection-evaluation sets: per scene (gt f32 [m,7] gravity-centre, gt labels i64 [m], det boxes f32 [n,7] bottom-centre,
+    det scores f32 [n], det labels i64 [n]).  GT are room_scene-like boxes; detections are jittered copies of the GT (up to `dup` per GT,
+    some with a wrong class) filling tp_frac of the list, the rest random boxes with random classes; n_det per scene (an int, or a
+    [n_scenes] array)."""
+    rng = np.random.default_rng(seed)
+    x0, y0, z0, x1, y1, z1 = pc_range
+    out = []
+    for s in range(n_scenes):
+        nd = int(n_det[s]) if np.ndim(n_det) else int(n_det)
+        m = int(rng.integers(0, max_gt + 1))
+        dims = rng.uniform(0.3, 2.0, (m, 3))
+        ctr = np.stack([rng.uniform(x0 + 0.5, x1 - 0.5, m), rng.uniform(y0 + 0.5, y1 - 0.5, m), z0 + dims[:, 2] / 2 + rng.uniform(0, 0.3, m)], 1)
+        gt = np.concatenate([ctr, dims, rng.uniform(-np.pi, np.pi, (m, 1))], 1).astype(np.float32)
+        gl = rng.integers(0, num_classes, m)
+        k = min(nd, int(round(tp_frac * nd)), m * dup) if m else 0
+        src = rng.integers(0, m, k) if m else np.zeros(0, np.int64)
+        near = gt[src].astype(np.float64)
+        near[:, 2] -= near[:, 5] / 2
+        near[:, :3] += rng.normal(0, 0.12, (k, 3)) * near[:, 3:6]
+        near[:, 3:6] *= rng.uniform(0.75, 1.25, (k, 3))
+        near[:, 6] += rng.normal(0, 0.15, k)
+        nl = np.where(rng.uniform(size=k) < 0.9, gl[src], rng.integers(0, num_classes, k))
+        r = nd - k
+        rd = rng.uniform(0.2, 2.0, (r, 3))
+        rand = np.concatenate([rng.uniform((x0, y0, z0), (x1, y1, z1 - 0.5), (r, 3)), rd, rng.uniform(-np.pi, np.pi, (r, 1))], 1)
+        db = np.concatenate([near, rand]).astype(np.float32)
+        dl = np.concatenate([nl, rng.integers(0, num_classes, r)]).astype(np.int64)
+        ds = np.concatenate([rng.uniform(0.3, 1.0, k), rng.uniform(0.0, 0.7, r)]).astype(np.float32)
+        p = rng.permutation(nd)
+        out.append((gt, gl.astype(np.int64), db[p], ds[p], dl[p]))
+    return out
