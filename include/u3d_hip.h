@@ -815,6 +815,45 @@ int32_t u3d_point_sample(const float* points, const int32_t* scene_off, const in
 int32_t u3d_boxes_range_filter(float* boxes, int32_t* labels, const int32_t* gt_off, int32_t batch, int32_t box_dim,
                                const float* bev_range4, int32_t* count, u3d_stream s);
 
+/* GT-paste (mmdet3d ObjectSample / the plugin's UnifiedObjectSample, ref: projects/mmdet3d_plugin/datasets/pipelines/dbsampler.py,
+ * transform_3d.py:591-786) and ObjectNoise (global_rot_range = 0) on a packed batch: uni3detr_amd/csrc/objaug.hip.  The random draws
+ * stay with the caller (uni3detr_amd/datapath.py).  Boxes are bottom-centre (x, y, z, dx, dy, dz, yaw [, vx, vy]), box_dim 7 or 9.
+ * count / gt_count / n_live / g_live (nullable where noted) give the live rows at the front of every scene's segment. */
+/* stats [2*batch + batch*ncls] = live points per scene | live GT rows per scene | GT rows per (scene, label in [0, ncls)); ncls <= 64 */
+int32_t u3d_objaug_stats(const int32_t* scene_off, const int32_t* count, const int32_t* gt_off, const int32_t* gt_count,
+                         const int32_t* labels, int32_t batch, int32_t ncls, int32_t* stats, u3d_stream s);
+/* candidates (database rows cand_ids, scene b = cand_off[b] .. cand_off[b+1], classes contiguous and labelled by cand_grp): BEV
+ * collision against the scene's live GT and each other, then sample_class_v2's greedy rule -> acc[k] = 1 accepted / 0 rejected.
+ * Every scene holds at most 32 * words <= 1024 candidates; hit_ws int32 [K], cc_ws uint32 [K * words]. */
+int32_t u3d_objaug_accept(const float* gt, const int32_t* gt_off, const int32_t* g_live, int32_t box_dim, const float* db_boxes,
+                          const int32_t* cand_ids, const int32_t* cand_off, const int32_t* cand_grp, int32_t batch, int32_t words,
+                          int32_t* hit_ws, uint32_t* cc_ws, int32_t* acc, u3d_stream s);
+/* points of scene b (first n_live[b] rows, n_live nullable) vs the boxes of scene b (box_live nullable, box_active nullable int32 per
+ * box row): first[row] = scene-local index of the lowest box that holds the point strictly inside all six faces, -1 none;
+ * bits (nullable) [rows][words] one bit per (point, box); tile_free (nullable) [batch][tiles] = points of each 256-row tile inside
+ * no box.  tiles = ceil(max live points / 256). */
+int32_t u3d_points_in_boxes(const float* points, const int32_t* scene_off, const int32_t* n_live, int32_t batch, int32_t feat,
+                            int32_t tiles, const float* boxes, const int32_t* box_off, const int32_t* box_live, const int32_t* box_active,
+                            int32_t box_dim, int32_t words, int32_t* first, uint32_t* bits, int32_t* tile_free, u3d_stream s);
+/* the paste after u3d_points_in_boxes(box_active = acc): out_points / out_scene_off get, per scene, the accepted candidates' database
+ * points translated by their box (candidate order) and the kept scene points (scene order) - sampled first when sampled_first
+ * (mmdet3d ObjectSample), after them otherwise (UnifiedObjectSample); out_boxes / out_labels / out_gt_off (out_boxes nullable) the
+ * live GT rows followed by the accepted boxes.  Rows past out_scene_off[batch] / out_gt_off[batch] are untouched.  Workspaces:
+ * tile_base_ws int32 [batch * tiles], cand_base_ws / cand_row_ws int32 [n_cand]. */
+int32_t u3d_objaug_paste(const float* points, const int32_t* scene_off, const int32_t* n_live, int32_t feat, const int32_t* first,
+                         const int32_t* tile_free, int32_t tiles, const float* gt, const int32_t* labels, const int32_t* gt_off,
+                         const int32_t* g_live, int32_t box_dim, const float* db_points, const int32_t* db_obj_off, const float* db_boxes,
+                         const int32_t* db_labels, const int32_t* cand_ids, const int32_t* cand_off, const int32_t* acc, int32_t n_cand,
+                         int32_t max_obj_points, int32_t batch, int32_t sampled_first, int32_t* tile_base_ws, int32_t* cand_base_ws,
+                         int32_t* cand_row_ws, float* out_points, int32_t* out_scene_off, float* out_boxes, int32_t* out_labels,
+                         int32_t* out_gt_off, u3d_stream s);
+/* ObjectNoise in place: per scene (at most 1024 live boxes), box by box in index order, the lowest try j of loc [rows][num_try][3] /
+ * rot [rows][num_try] whose moved BEV rectangle collides with no other box's current one (chosen[row] = j, -1 = none: the box stays);
+ * then every point moves with the lowest-index original box holding it.  first_ws int32 [point rows], sel_ws f32 [box rows * 8]. */
+int32_t u3d_object_noise(float* points, const int32_t* scene_off, const int32_t* n_live, int32_t batch, int32_t feat, int32_t tiles,
+                         float* boxes, const int32_t* gt_off, const int32_t* g_live, int32_t box_dim, int32_t num_try, const float* loc,
+                         const float* rot, int32_t* first_ws, float* sel_ws, int32_t* chosen, u3d_stream s);
+
 #ifdef __cplusplus
 }
 #endif

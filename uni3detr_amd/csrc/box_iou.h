@@ -63,3 +63,50 @@ __device__ static float pp_iou3d(const float* p, const float* q) {
   float v1 = p[3] * p[4] * p[5], v2 = q[3] * q[4] * q[5];
   return ov / fmaxf(v1 + v2 - ov, 1e-8f);
 }
+
+// ---- rectangle corners and the upstream BEV collision test (GT-paste / ObjectNoise, objaug.hip) ----
+// Corner order of mmdet3d's box2d_to_corner_jit (recalled): (-.5,-.5), (-.5,.5), (.5,.5), (.5,-.5) times (dx, dy), rotated
+// counter-clockwise by yaw, plus the centre - a clockwise list for dx, dy > 0.
+__device__ static void bx_corners(float cx, float cy, float dx, float dy, float yaw, Q2* c) {
+  const float cs = cosf(yaw), sn = sinf(yaw);
+  const float sx[4] = {-0.5f, -0.5f, 0.5f, 0.5f}, sy[4] = {-0.5f, 0.5f, 0.5f, -0.5f};
+  for (int i = 0; i < 4; ++i) {
+    const float x = sx[i] * dx, y = sy[i] * dy;
+    c[i] = Q2{x * cs - y * sn + cx, x * sn + y * cs + cy};
+  }
+}
+// mmdet3d data_augment_utils.box_collision_test (recalled, clockwise=True) for one pair: the standup boxes overlap and either two
+// edges cross or one rectangle holds all four corners of the other.
+__device__ static bool bx_collide(const Q2* a, const Q2* b) {
+  float ax0 = a[0].x, ax1 = a[0].x, ay0 = a[0].y, ay1 = a[0].y, bx0 = b[0].x, bx1 = b[0].x, by0 = b[0].y, by1 = b[0].y;
+  for (int i = 1; i < 4; ++i) {
+    ax0 = fminf(ax0, a[i].x); ax1 = fmaxf(ax1, a[i].x); ay0 = fminf(ay0, a[i].y); ay1 = fmaxf(ay1, a[i].y);
+    bx0 = fminf(bx0, b[i].x); bx1 = fmaxf(bx1, b[i].x); by0 = fminf(by0, b[i].y); by1 = fmaxf(by1, b[i].y);
+  }
+  if (!(fminf(ax1, bx1) - fmaxf(ax0, bx0) > 0.f) || !(fminf(ay1, by1) - fmaxf(ay0, by0) > 0.f)) return false;
+  for (int k = 0; k < 4; ++k) {
+    const Q2 A = a[k], B = a[(k + 1) & 3];
+    for (int l = 0; l < 4; ++l) {
+      const Q2 C = b[l], D = b[(l + 1) & 3];
+      const bool acd = (D.y - A.y) * (C.x - A.x) > (C.y - A.y) * (D.x - A.x);
+      const bool bcd = (D.y - B.y) * (C.x - B.x) > (C.y - B.y) * (D.x - B.x);
+      if (acd != bcd) {
+        const bool abc = (C.y - A.y) * (B.x - A.x) > (B.y - A.y) * (C.x - A.x);
+        const bool abd = (D.y - A.y) * (B.x - A.x) > (B.y - A.y) * (D.x - A.x);
+        if (abc != abd) return true;
+      }
+    }
+  }
+  for (int pass = 0; pass < 2; ++pass) {           // pass 0: a holds every corner of b; pass 1: the other way round
+    const Q2* o = pass ? b : a;
+    const Q2* q = pass ? a : b;
+    bool holds = true;
+    for (int l = 0; l < 4 && holds; ++l)
+      for (int k = 0; k < 4; ++k) {
+        const float vx = o[(k + 1) & 3].x - o[k].x, vy = o[(k + 1) & 3].y - o[k].y;
+        if (vy * (o[k].x - q[l].x) - vx * (o[k].y - q[l].y) >= 0.f) { holds = false; break; }
+      }
+    if (holds) return true;
+  }
+  return false;
+}

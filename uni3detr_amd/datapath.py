@@ -18,6 +18,7 @@ from . import native as nv
 from .registry import Registry
 
 PIPELINES = Registry("pipeline")
+OBJECT_AUG = Registry("object_aug")          # opt-in entries: built only when DevicePipeline is given what they need
 DEPTH, LIDAR = 0, 1
 
 
@@ -212,6 +213,151 @@ class MultiScaleFlipAug3D:
         return self.inner(batch)
 
 
+@OBJECT_AUG.register_module()
+class ObjectSample:
+    """ref: mmdet3d ObjectSample (recalled) with the plugin's UnifiedDataBaseSampler (projects/mmdet3d_plugin/datasets/pipelines/
+    dbsampler.py: sample_all, sample_class_v2).  Per scene, in scene order, the host reads the scene's per-class GT count (one small
+    device-to-host copy for the whole batch), computes sampled_num = round(rate * (max - count)) per class in sample_groups order and
+    draws that many database rows from the class's BatchSampler; the draws go into batch["db_sampled"] (a list per scene of
+    (rows, group index) arrays) and are replayed when already present.  The device then runs the collision test and sample_class_v2's
+    greedy accept, removes the scene points inside an accepted box and pastes the accepted objects (points translated by their box,
+    boxes and labels after the existing GT).  The sampled points go BEFORE the kept scene points (mmdet3d); UnifiedObjectSample puts
+    them after (transform_3d.py:668).  The output is exactly packed: new scene_off / gt_off / gt_labels_3d, no count / gt_count (rows
+    past scene_off[-1] / gt_off[-1] are spare capacity).  batch["db_accepted"]: int32 [K] device flags of the candidates."""
+    sampled_first = True
+
+    def __init__(self, db_sampler, sample_2d=False, gt_database=None, **kwargs):
+        if sample_2d:
+            raise NotImplementedError("ObjectSample: sample_2d (image pasting) is not supported on the device")
+        if gt_database is None:
+            raise ValueError("ObjectSample needs a GTDatabase (DevicePipeline(..., gt_database=...))")
+        classes = db_sampler.get("classes")
+        if classes is not None and list(classes) != list(gt_database.classes):
+            raise ValueError(f"GTDatabase classes {gt_database.classes} differ from db_sampler.classes {list(classes)}")
+        self.db = gt_database
+        self.rate = float(db_sampler.get("rate", 1.0))
+        self.groups = [(name, int(num)) for name, num in db_sampler["sample_groups"].items()]
+        self.cat = {n: i for i, n in enumerate(gt_database.classes)}
+
+    def draw(self, hist):
+        """one scene's candidates: (database rows, group index) in sample_groups order (UnifiedDataBaseSampler.sample_all)."""
+        rows, grp = [], []
+        for gi, (name, mx) in enumerate(self.groups):
+            n = int(np.round(self.rate * int(mx - int(hist[self.cat[name]]))).astype(np.int64))
+            if n > 0 and len(self.db.rows.get(name, ())):
+                r = self.db.sample(name, n)
+                rows.append(r)
+                grp.append(np.full(len(r), gi, np.int64))
+        return (np.concatenate(rows) if rows else np.zeros(0, np.int64), np.concatenate(grp) if grp else np.zeros(0, np.int64))
+
+    def __call__(self, batch):
+        db, dev = self.db, batch["points"].device
+        if batch.get("gt_labels_3d") is None:
+            raise KeyError("ObjectSample needs gt_labels_3d in the batch")
+        lab = batch["gt_labels_3d"] = batch["gt_labels_3d"].to(torch.int32).contiguous()
+        gt, go, so = batch["gt_bboxes_3d"], batch["gt_off"], batch["scene_off"]
+        if gt.shape[1] != db.box_dim or batch["points"].shape[1] != db.feat:
+            raise ValueError(f"GTDatabase holds [{db.feat}]-feature points / [{db.box_dim}]-column boxes, the batch "
+                             f"[{batch['points'].shape[1]}] / [{gt.shape[1]}]")
+        B, C = so.numel() - 1, len(db.classes)
+        stats = nv.objaug_stats(so, batch.get("count"), go, batch.get("gt_count"), lab, C)
+        st = stats.cpu().numpy()                          # the one device-to-host copy
+        n_live, g_live, hist = st[:B], st[B:2 * B], st[2 * B:].reshape(B, C)
+        if "db_sampled" not in batch:
+            batch["db_sampled"] = [self.draw(hist[b]) for b in range(B)]
+        rows = [np.asarray(r, np.int64) for r, _ in batch["db_sampled"]]
+        grps = [np.asarray(g, np.int64) for _, g in batch["db_sampled"]]
+        ks = [len(r) for r in rows]
+        if max(ks) > nv.OA_CAP:
+            raise ValueError(f"ObjectSample: {max(ks)} candidates in one scene, at most {nv.OA_CAP}")
+        ids_h = np.concatenate(rows).astype(np.int32)
+        K = len(ids_h)
+        sizes = db.obj_off_host[ids_h + 1] - db.obj_off_host[ids_h] if K else np.zeros(0, np.int64)
+        stats_n, stats_g = stats[:B], stats[B:2 * B]
+        if K:
+            ids = torch.from_numpy(ids_h).to(dev)
+            coff = torch.tensor(np.concatenate([[0], np.cumsum(ks)]).astype(np.int32), device=dev)
+            cgrp = torch.from_numpy(np.concatenate(grps).astype(np.int32)).to(dev)
+            acc = nv.objaug_accept(gt, go, stats_g, db.boxes, ids, coff, cgrp, max(ks))
+        else:
+            ids = coff = acc = torch.zeros((0,), dtype=torch.int32, device=dev)
+        pts, so2, boxes, labels, go2 = nv.objaug_paste(
+            batch["points"], so, stats_n, int(n_live.max(initial=0)), gt, lab, go, stats_g, nv._nz(db.points), db.obj_off, nv._nz(db.boxes),
+            nv._nz(db.labels), ids, coff, acc, int(sizes.max(initial=0)), int(n_live.sum() + sizes.sum()), int(g_live.sum()) + K,
+            self.sampled_first)
+        batch.update(points=pts, scene_off=so2, gt_bboxes_3d=boxes, gt_off=go2, gt_labels_3d=labels, db_accepted=acc)
+        batch.pop("count", None)
+        batch.pop("gt_count", None)
+        return batch
+
+
+@OBJECT_AUG.register_module()
+class UnifiedObjectSample(ObjectSample):
+    """ref: transform_3d.py:591-786 - the sampled points go AFTER the kept scene points (:668)."""
+    sampled_first = False
+
+    def __init__(self, db_sampler, sample_2d=False, sample_method="depth", modify_points=False, gt_database=None, **kwargs):
+        super().__init__(db_sampler, sample_2d, gt_database)
+
+
+@OBJECT_AUG.register_module()
+class ObjectNoise:
+    """ref: mmdet3d ObjectNoise -> noise_per_object_v3_ (recalled) with global_rot_range = 0 (noise_per_box).  Per scene, in scene
+    order, the host draws loc ~ N(0, translation_std) [G, num_try, 3], rot ~ U(rot_range) [G, num_try] and the (unused, zero-width)
+    global rotation draw upstream makes as well, so the host RNG stream stays the reference's; the draws go into batch["object_noise"]
+    (replayed when present).  The device takes, box by box, the lowest collision-free try, moves every point with the lowest-index
+    original box holding it and adds loc / rot to the box; batch["object_noise_try"] = chosen try per box row (-1 = none)."""
+
+    def __init__(self, translation_std=(0.25, 0.25, 0.25), global_rot_range=(0.0, 0.0), rot_range=(-0.15707963267, 0.15707963267),
+                 num_try=100, **kwargs):
+        if not isinstance(global_rot_range, (list, tuple, np.ndarray)):
+            global_rot_range = [-global_rot_range, global_rot_range]
+        if abs(global_rot_range[0] - global_rot_range[1]) >= 1e-3:
+            raise NotImplementedError("ObjectNoise: global_rot_range != 0 (noise_per_box_v2_) is not supported on the device")
+        if not isinstance(rot_range, (list, tuple, np.ndarray)):
+            rot_range = [-rot_range, rot_range]
+        if not isinstance(translation_std, (list, tuple, np.ndarray)):
+            translation_std = [translation_std] * 3
+        self.translation_std = np.asarray(translation_std, np.float32)
+        self.rot_range, self.global_rot_range, self.num_try = list(rot_range), list(global_rot_range), int(num_try)
+
+    def __call__(self, batch):
+        g = batch.get("gt_bboxes_3d")
+        if g is None:
+            return batch
+        so, go = batch["scene_off"], batch["gt_off"]
+        B = so.numel() - 1
+        go_h, so_h = go.cpu().numpy(), so.cpu().numpy()
+        gc = batch["gt_count"].cpu().numpy() if "gt_count" in batch else np.diff(go_h)
+        nc = batch["count"].cpu().numpy() if "count" in batch else np.diff(so_h)
+        if "object_noise" not in batch:
+            loc, rot = [], []
+            for b in range(B):
+                n = int(gc[b])
+                loc.append(np.random.normal(scale=self.translation_std, size=[n, self.num_try, 3]).astype(np.float32))
+                rot.append(np.random.uniform(self.rot_range[0], self.rot_range[1], size=[n, self.num_try]).astype(np.float32))
+                np.random.uniform(self.global_rot_range[0], self.global_rot_range[1], size=[n, self.num_try])   # upstream's global draw
+            batch["object_noise"] = dict(loc=loc, rot=rot)
+        if int(gc.max(initial=0)) > nv.OA_CAP:
+            raise ValueError(f"ObjectNoise: {int(gc.max())} boxes in one scene, at most {nv.OA_CAP}")
+        G, T = g.shape[0], self.num_try
+        if G == 0:
+            batch["object_noise_try"] = torch.zeros((0,), dtype=torch.int32, device=g.device)
+            return batch
+        loc = np.zeros((G, T, 3), np.float32)
+        rot = np.zeros((G, T), np.float32)
+        for b in range(B):
+            n = int(gc[b])
+            loc[go_h[b]:go_h[b] + n] = batch["object_noise"]["loc"][b]
+            rot[go_h[b]:go_h[b] + n] = batch["object_noise"]["rot"][b]
+        dev = g.device
+        g_live = torch.from_numpy(np.asarray(gc, np.int32)).to(dev)
+        n_live = batch["count"] if "count" in batch else None
+        batch["object_noise_try"] = nv.object_noise(batch["points"], so, n_live, int(nc.max(initial=0)), g, go, g_live,
+                                                    torch.from_numpy(loc).to(dev), torch.from_numpy(rot).to(dev))
+        return batch
+
+
 _PASSTHROUGH = {"LoadPointsFromFile", "LoadAnnotations3D", "DefaultFormatBundle3D", "Collect3D", "CollectUnified3D", "LoadPointsFromMultiSweeps",
                 "ObjectNameFilter", "PointShuffle", "ObjectSample", "UnifiedObjectSample", "ObjectNoise", "NormalizePointsColor",
                 "LoadImageFromFile", "LoadMultiViewImageFromFiles"}
@@ -221,10 +367,18 @@ class DevicePipeline:
     """The device-side part of a config's `train_pipeline` / `test_pipeline` list: loading / formatting entries (and the
     ground-truth database sampler, which needs the dataset's files) stay with the host loader and are skipped here."""
 
-    def __init__(self, pipeline_cfg):
+    def __init__(self, pipeline_cfg, gt_database=None, object_noise=False):
+        """gt_database (uni3detr_amd.gtdb.GTDatabase): run ObjectSample / UnifiedObjectSample on the device; object_noise=True: run
+        ObjectNoise on the device.  Without them both stay in `skipped`."""
         self.transforms, self.skipped = [], []
         for c in pipeline_cfg:
-            if c["type"] in PIPELINES:
+            if c["type"] in ("ObjectSample", "UnifiedObjectSample") and gt_database is not None:
+                if "db_sampler" not in c:
+                    raise KeyError(f"pipeline entry {c['type']!r}: a device GT-paste needs the entry's db_sampler (sample_groups, rate)")
+                self.transforms.append(OBJECT_AUG.build(c, gt_database=gt_database))
+            elif c["type"] == "ObjectNoise" and object_noise:
+                self.transforms.append(OBJECT_AUG.build(c))
+            elif c["type"] in PIPELINES:
                 self.transforms.append(PIPELINES.build(c))
             elif c["type"] in _PASSTHROUGH:
                 self.skipped.append(c["type"])

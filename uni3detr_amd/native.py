@@ -205,6 +205,12 @@ _SIGS = {
     "u3d_value_records_bytes": (_L, [_I]),
     "u3d_value_scatter_workspace": (_L, [_I]),
     "u3d_value_scatter": (_I, [_P, _I, _I, _P, _I, _P, _L, _P]),
+    "u3d_objaug_stats": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "u3d_objaug_accept": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "u3d_points_in_boxes": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "u3d_objaug_paste": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P,
+                              _P, _P, _P, _P, _P, _P]),
+    "u3d_object_noise": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 
@@ -1821,3 +1827,96 @@ def point_sample(points, scene_off, count, num_points, seed, want_idx=False):
     _check(lib().u3d_point_sample(_ptr(points), _ptr(scene_off), _ptr(count), batch, points.shape[1], int(num_points), _ptr(seed), _ptr(out),
                                   _ptr(idx), _stream()), "point_sample")
     return (out, idx) if want_idx else out
+
+
+# --------------------------------------------------------------------------------------------------
+# GT-paste / ObjectNoise (csrc/objaug.hip)
+# --------------------------------------------------------------------------------------------------
+OA_CAP = 1024          # boxes per scene the collision / noise kernels stage in LDS
+
+
+def _tiles(max_rows):
+    return (int(max_rows) + 255) // 256
+
+
+def _nz(t):
+    """a zero-row tensor has no device pointer to hand over: one spare element instead (never read)"""
+    return t if t.numel() else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+
+
+def objaug_stats(scene_off, count, gt_off, gt_count, labels, ncls):
+    """-> int32 [2B + B*ncls] on the device: live points | live GT rows | GT rows per (scene, class)."""
+    batch = scene_off.numel() - 1
+    stats = torch.empty((2 * batch + batch * ncls,), dtype=torch.int32, device=scene_off.device)
+    _check(lib().u3d_objaug_stats(_ptr(scene_off), _ptr(count), _ptr(gt_off), _ptr(gt_count), _ptr(_nz(labels)), batch, int(ncls), _ptr(stats),
+                                  _stream()), "objaug_stats")
+    return stats
+
+
+def objaug_accept(gt, gt_off, g_live, db_boxes, cand_ids, cand_off, cand_grp, max_per_scene):
+    """-> acc int32 [K]: 1 where the candidate survives sample_class_v2's collision rule."""
+    assert gt.dtype == torch.float32 and gt.shape[1] == db_boxes.shape[1] and 0 < max_per_scene <= OA_CAP
+    batch, K = gt_off.numel() - 1, cand_ids.numel()
+    words = (int(max_per_scene) + 31) // 32
+    acc = torch.empty((K,), dtype=torch.int32, device=gt.device)
+    hit = torch.empty((K,), dtype=torch.int32, device=gt.device)
+    cc = torch.empty((K * words,), dtype=torch.int32, device=gt.device)
+    _check(lib().u3d_objaug_accept(_ptr(_nz(gt)), _ptr(gt_off), _ptr(g_live), gt.shape[1], _ptr(db_boxes), _ptr(cand_ids), _ptr(cand_off),
+                                   _ptr(cand_grp), batch, words, _ptr(hit), _ptr(cc), _ptr(acc), _stream()), "objaug_accept")
+    return acc
+
+
+def points_in_boxes(points, scene_off, n_live, max_rows, boxes, box_off, box_live=None, box_active=None, max_boxes=0, want_bits=False,
+                    want_tile_free=False):
+    """-> (first int32 [rows], bits int32 [rows, words] or None, tile_free int32 [B, tiles] or None)."""
+    assert points.dtype == torch.float32 and points.is_contiguous() and boxes.dtype == torch.float32 and boxes.shape[1] in (7, 9)
+    batch, dev = scene_off.numel() - 1, points.device
+    tiles = _tiles(max_rows)
+    words = max(1, (int(max_boxes) + 31) // 32)
+    first = torch.full((max(1, points.shape[0]),), -1, dtype=torch.int32, device=dev)
+    bits = torch.zeros((max(1, points.shape[0]), words), dtype=torch.int32, device=dev) if want_bits else None
+    tile_free = torch.zeros((batch, max(1, tiles)), dtype=torch.int32, device=dev) if want_tile_free else None
+    _check(lib().u3d_points_in_boxes(_ptr(_nz(points)), _ptr(scene_off), _ptr(n_live), batch, points.shape[1], tiles, _ptr(_nz(boxes)),
+                                     _ptr(box_off), _ptr(box_live), _ptr(box_active), boxes.shape[1], words, _ptr(first), _ptr(bits),
+                                     _ptr(tile_free), _stream()), "points_in_boxes")
+    return first, bits, tile_free
+
+
+def objaug_paste(points, scene_off, n_live, max_rows, gt, labels, gt_off, g_live, db_points, db_obj_off, db_boxes, db_labels, cand_ids,
+                 cand_off, acc, max_obj_points, out_rows, out_box_rows, sampled_first):
+    """ObjectSample's point removal + paste -> (points [out_rows, F], scene_off, boxes [out_box_rows, D], labels, gt_off): every scene
+    exactly packed, the scenes back to back from row 0 (rows past scene_off[-1] / gt_off[-1] are spare capacity)."""
+    batch, dev, feat, dim = scene_off.numel() - 1, points.device, points.shape[1], gt.shape[1]
+    K = cand_ids.numel()
+    cand_boxes = db_boxes.index_select(0, cand_ids.long()) if K else torch.zeros((0, dim), dtype=torch.float32, device=dev)
+    first, _, tile_free = points_in_boxes(points, scene_off, n_live, max_rows, cand_boxes, cand_off if K else torch.zeros_like(scene_off),
+                                          None, acc if K else None, want_tile_free=True)
+    tiles = tile_free.shape[1]
+    out_p = torch.empty((max(1, out_rows), feat), dtype=torch.float32, device=dev)
+    out_b = torch.empty((max(1, out_box_rows), dim), dtype=torch.float32, device=dev)
+    out_l = torch.empty((max(1, out_box_rows),), dtype=torch.int32, device=dev)
+    out_so = torch.empty_like(scene_off)
+    out_go = torch.empty_like(gt_off)
+    tile_base = torch.empty((batch * tiles,), dtype=torch.int32, device=dev)
+    cand_base = torch.empty((max(1, K),), dtype=torch.int32, device=dev)
+    cand_row = torch.empty((max(1, K),), dtype=torch.int32, device=dev)
+    _check(lib().u3d_objaug_paste(_ptr(_nz(points)), _ptr(scene_off), _ptr(n_live), feat, _ptr(first), _ptr(tile_free), tiles, _ptr(_nz(gt)),
+                                  _ptr(_nz(labels)), _ptr(gt_off), _ptr(g_live), dim, _ptr(db_points), _ptr(db_obj_off), _ptr(db_boxes),
+                                  _ptr(db_labels), _ptr(cand_ids) if K else None, _ptr(cand_off) if K else None, _ptr(acc) if K else None, K,
+                                  int(max_obj_points), batch, int(bool(sampled_first)), _ptr(tile_base), _ptr(cand_base), _ptr(cand_row),
+                                  _ptr(out_p), _ptr(out_so), _ptr(out_b), _ptr(out_l), _ptr(out_go), _stream()), "objaug_paste")
+    return out_p[:out_rows], out_so, out_b[:out_box_rows], out_l[:out_box_rows], out_go
+
+
+def object_noise(points, scene_off, n_live, max_rows, boxes, gt_off, g_live, loc, rot):
+    """ObjectNoise in place on points / boxes -> chosen try per box row (int32, -1 = none)."""
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.shape[1] in (7, 9) and points.is_contiguous()
+    batch, dev = scene_off.numel() - 1, points.device
+    num_try = rot.shape[1]
+    first = torch.empty((max(1, points.shape[0]),), dtype=torch.int32, device=dev)
+    sel = torch.empty((max(1, boxes.shape[0]) * 8,), dtype=torch.float32, device=dev)
+    chosen = torch.full((max(1, boxes.shape[0]),), -1, dtype=torch.int32, device=dev)
+    _check(lib().u3d_object_noise(_ptr(_nz(points)), _ptr(scene_off), _ptr(n_live), batch, points.shape[1], _tiles(max_rows), _ptr(_nz(boxes)),
+                                  _ptr(gt_off), _ptr(g_live), boxes.shape[1], num_try, _ptr(_nz(loc.contiguous())), _ptr(_nz(rot.contiguous())),
+                                  _ptr(first), _ptr(sel), _ptr(chosen), _stream()), "object_noise")
+    return chosen[:boxes.shape[0]]
