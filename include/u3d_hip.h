@@ -646,6 +646,50 @@ int32_t u3d_eval_ap(const uint8_t* tp, int32_t n_det, const int32_t* seg, const 
                     int32_t n_gt, double* prec_ws, float* ap, double* rec, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
+ * KITTI 3-D detection evaluation (mmdet3d's kitti_eval: clean_data, compute_statistics, get_thresholds, eval_class; semantics in
+ * uni3detr_amd/kitti_eval.py).  Records are f32 [., 16]: camera box (x, y, z bottom centre, l, h, w, ry), 2-D box (x1, y1, x2, y2),
+ * alpha, score (detections) / ignore bits of the three difficulties (GT), class code (0 Car, 1 Pedestrian, 2 Cyclist, 3 Van,
+ * 4 Person_sitting, 5 DontCare, 6 other), 2 unused.  Scenes are CSR: dt_off / gt_off int32 [n_scene+1]; ov_off int64 [n_scene+1] =
+ * exclusive scan of nd * ng, ov f32 [3][n_pairs] = bbox / bev / 3d overlap matrices [dt][gt] per scene.
+ * u3d_kitti_convert: LiDAR bottom-centre boxes [n,7] + scores + labels -> rec [n,16] and valid int32 [n] (inside the image and strictly
+ *   inside lim = pcd_limit_range); calib f32 [n_scene][32] = R0_rect @ Tr_velo_to_cam then P2 (row-major 4x4), img f32 [n_scene][2] = (H, W).
+ * u3d_kitti_compact: out[pos[d]] = rec[d] where valid[d] (pos = exclusive scan of valid).
+ * u3d_kitti_flags: for the K <= 3 class codes cls, flag index f = class slot * 3 + difficulty: gt_flag / dt_flag int8 [3K][n] in
+ *   {-1, 0, 1}, nvalid int32 [3K] = GT with flag 0, dc_iof f32 [n_dt] = max DontCare intersection over the detection's area.
+ * Groups g (n_group): flag index gfid, metric gmet (0 bbox, 1 bev, 2 3d), min overlap gmin.
+ * u3d_kitti_pass1: TP scores of compute_statistics(compute_fp = False) at tp_sc f32 [n_group][n_gt] (scene s's TPs from gt_off[s] on,
+ *   -inf after them).  U3D_ERR_UNSUPPORTED above 4096 detections in a scene (max_dt).
+ * u3d_kitti_thresholds: get_thresholds over rows of tp_sc sorted descending -> thr f32 [n_group][41], nthr int32 [n_group].
+ * u3d_kitti_pass2: per (group, scene, threshold) tp / fp / fn int32 and similarity f64 [n_group][n_scene][41] of
+ *   compute_statistics(compute_fp = True) (similarity only for bbox groups when aos, -1 = not accumulated); lds_bytes = max over the
+ *   scenes of u3d_kitti_pass2_lds(nd, ng), at most 160 KiB (else U3D_ERR_UNSUPPORTED).
+ * u3d_kitti_reduce: tot int32 [n_group][3][41], sim_tot f64 [n_group][41], ap f64 [n_group][4] = (AP11, AP40, AOS AP11, AOS AP40).
+ * ---------------------------------------------------------------------------------------------- */
+int32_t u3d_kitti_convert(const float* boxes, const float* scores, const int32_t* labels, const int32_t* off, int32_t n_scene, int32_t n,
+                          const float* calib, const float* img, const int32_t* label_code, int32_t n_label, const float* lim, float* rec,
+                          int32_t* valid, u3d_stream s);
+int32_t u3d_kitti_compact(const float* rec, const int32_t* valid, const int32_t* pos, int32_t n, float* out, u3d_stream s);
+int32_t u3d_kitti_overlaps(const float* dt, const int32_t* dt_off, const float* gt, const int32_t* gt_off, const int64_t* ov_off,
+                           int32_t n_scene, int64_t n_pairs, float* ov, u3d_stream s);
+int32_t u3d_kitti_flags(const float* dt, const int32_t* dt_off, int32_t n_scene, int32_t n_dt, const float* gt, const int32_t* gt_off,
+                        int32_t n_gt, const int32_t* cls, int32_t K, int8_t* gt_flag, int32_t* nvalid, int8_t* dt_flag, float* dc_iof,
+                        u3d_stream s);
+int32_t u3d_kitti_pass1(const float* dt, const int32_t* dt_off, int32_t n_dt, const int32_t* gt_off, int32_t n_gt, int32_t n_scene,
+                        const int64_t* ov_off, int64_t n_pairs, const float* ov, const int8_t* gt_flag, const int8_t* dt_flag,
+                        const int32_t* gfid, const int32_t* gmet, const float* gmin, int32_t n_group, int32_t max_dt, float* tp_sc,
+                        u3d_stream s);
+int32_t u3d_kitti_thresholds(const float* sorted, int32_t n_gt, int32_t n_group, const int32_t* gfid, const int32_t* nvalid, float* thr,
+                             int32_t* nthr, u3d_stream s);
+int64_t u3d_kitti_pass2_lds(int32_t nd, int32_t ng);
+int32_t u3d_kitti_pass2(const float* dt, const int32_t* dt_off, int32_t n_dt, const float* gt, const int32_t* gt_off, int32_t n_gt,
+                        int32_t n_scene, const int64_t* ov_off, int64_t n_pairs, const float* ov, const int8_t* gt_flag, const int8_t* dt_flag,
+                        const float* dc_iof, const int32_t* gfid, const int32_t* gmet, const float* gmin, const float* thr, const int32_t* nthr,
+                        int32_t n_group, int32_t aos, int64_t lds_bytes, int32_t* st_tp, int32_t* st_fp, int32_t* st_fn, double* st_sim,
+                        u3d_stream s);
+int32_t u3d_kitti_reduce(const int32_t* st_tp, const int32_t* st_fp, const int32_t* st_fn, const double* st_sim, int32_t n_scene,
+                         const int32_t* nthr, int32_t n_group, int32_t* tot, double* sim_tot, double* ap, u3d_stream s);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused decoder layer (bf16 MFMA, f32 accumulation / residual stream / LayerNorm statistics / softmax statistics).
  * One call = one Uni3DETRTransformerDecoder layer over ALL query groups of all scenes, plus everything the decoder loop and the head
  * hang on that layer's state (ref: models/utils/uni3detr_transformer.py:145-212 decoder loop, :33-65 sine embedding, :271-360

@@ -188,6 +188,15 @@ _SIGS = {
     "u3d_eval_first_hit": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "u3d_eval_tp": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "u3d_eval_ap": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "u3d_kitti_convert": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "u3d_kitti_compact": (_I, [_P, _P, _P, _I, _P, _P]),
+    "u3d_kitti_overlaps": (_I, [_P, _P, _P, _P, _P, _I, _L, _P, _P]),
+    "u3d_kitti_flags": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "u3d_kitti_pass1": (_I, [_P, _P, _I, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "u3d_kitti_thresholds": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "u3d_kitti_pass2_lds": (_L, [_I, _I]),
+    "u3d_kitti_pass2": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P]),
+    "u3d_kitti_reduce": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "u3d_decoder_layer_slots": (_I, [_I, _I, _I, _P, _P]),
     "u3d_decoder_layer_blocks": (_I, [_I]),
     "u3d_decoder_layer_fwd": (_I, [C.POINTER(DecLayerParams), C.POINTER(DecLayerDims)] + [_P] * 11 + [_L, _P]),
@@ -1351,6 +1360,72 @@ def eval_indoor(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels,
     rec = torch.empty((t, num_classes), dtype=torch.float64, device=dev)
     _check(lib().u3d_eval_ap(_ptr(tp), n, _ptr(seg), _ptr(npos), num_classes, t, g, _ptr(prec), _ptr(ap), _ptr(rec), _stream()), "eval_ap")
     return dict(iou_max=iou, jmax=jmax, perm=perm, seg=seg, npos=npos, tp=tp, ap=ap, rec=rec)
+
+
+KITTI_NT = 41
+
+
+def kitti_convert(boxes, scores, labels, off, calib, img, label_code, lim):
+    """LiDAR detections -> KITTI records (u3d_kitti_convert + a stable compaction).  boxes f32 [n,7] bottom-centre, scores f32 [n],
+    labels int32 [n], off int32 [S+1], calib f32 [S,32], img f32 [S,2] (H, W), label_code int32 [L], lim f32 [6] (all on the device).
+    -> (records f32 [m,16] of the valid detections in input order, their offsets int32 [S+1]).  One host synchronisation (m)."""
+    n, S = boxes.shape[0], off.numel() - 1
+    dev = off.device
+    rec = torch.empty((n, 16), dtype=torch.float32, device=dev)
+    valid = torch.empty((n,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_kitti_convert(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(off), S, n, _ptr(calib), _ptr(img), _ptr(label_code),
+                                   label_code.numel(), _ptr(lim), _ptr(rec), _ptr(valid), _stream()), "kitti_convert")
+    incl = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), torch.cumsum(valid, 0, dtype=torch.int32)])
+    new_off = incl[off.long()].to(torch.int32).contiguous()
+    pos = incl[:-1].contiguous()
+    m = int(incl[-1])
+    out = torch.empty((m, 16), dtype=torch.float32, device=dev)
+    _check(lib().u3d_kitti_compact(_ptr(rec), _ptr(valid), _ptr(pos), n, _ptr(out), _stream()), "kitti_compact")
+    return out, new_off
+
+
+def kitti_eval_core(dt, dt_off, gt, gt_off, cls, gfid, gmet, gmin, aos, dt_counts, gt_counts):
+    """KITTI AP on the device (u3d_kitti_*).  dt / gt: records f32 [.,16], offsets int32 [S+1], cls int32 [K] class codes, groups gfid /
+    gmet int32 [NG], gmin f32 [NG] (device); dt_counts / gt_counts: the per-scene counts as host lists (buffer sizes, LDS size).
+    -> dict of device tensors: ov f32 [3,P], ov_off, gt_flag / dt_flag int8 [3K,.], nvalid [3K], dc_iof, tp_sc [NG,G] (sorted
+    descending), thr [NG,41], nthr [NG], tot int32 [NG,3,41], sim f64 [NG,41], ap f64 [NG,4]."""
+    dev = dt_off.device
+    S, N, G, K, NG = len(dt_counts), dt.shape[0], gt.shape[0], cls.numel(), gfid.numel()
+    pairs = [int(a) * int(b) for a, b in zip(dt_counts, gt_counts)]
+    ov_off_h = [0]
+    for p in pairs:
+        ov_off_h.append(ov_off_h[-1] + p)
+    P = ov_off_h[-1]
+    ov_off = torch.tensor(ov_off_h, dtype=torch.int64, device=dev)
+    ov = torch.empty((3, P), dtype=torch.float32, device=dev)
+    _check(lib().u3d_kitti_overlaps(_ptr(dt), _ptr(dt_off), _ptr(gt), _ptr(gt_off), _ptr(ov_off), S, P, _ptr(ov), _stream()), "kitti_overlaps")
+    gt_flag = torch.empty((3 * K, G), dtype=torch.int8, device=dev)
+    dt_flag = torch.empty((3 * K, N), dtype=torch.int8, device=dev)
+    nvalid = torch.empty((3 * K,), dtype=torch.int32, device=dev)
+    dc_iof = torch.empty((N,), dtype=torch.float32, device=dev)
+    _check(lib().u3d_kitti_flags(_ptr(dt), _ptr(dt_off), S, N, _ptr(gt), _ptr(gt_off), G, _ptr(cls), K, _ptr(gt_flag), _ptr(nvalid),
+                                 _ptr(dt_flag), _ptr(dc_iof), _stream()), "kitti_flags")
+    tp_sc = torch.empty((NG, G), dtype=torch.float32, device=dev)
+    max_dt = max([int(c) for c in dt_counts] + [0])
+    _check(lib().u3d_kitti_pass1(_ptr(dt), _ptr(dt_off), N, _ptr(gt_off), G, S, _ptr(ov_off), P, _ptr(ov), _ptr(gt_flag), _ptr(dt_flag),
+                                 _ptr(gfid), _ptr(gmet), _ptr(gmin), NG, max_dt, _ptr(tp_sc), _stream()), "kitti_pass1")
+    tp_sc = torch.sort(tp_sc, dim=1, descending=True).values.contiguous()      # only the values matter
+    thr = torch.zeros((NG, KITTI_NT), dtype=torch.float32, device=dev)
+    nthr = torch.empty((NG,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_kitti_thresholds(_ptr(tp_sc), G, NG, _ptr(gfid), _ptr(nvalid), _ptr(thr), _ptr(nthr), _stream()), "kitti_thresholds")
+    lds = max([int(lib().u3d_kitti_pass2_lds(int(a), int(b))) for a, b in zip(dt_counts, gt_counts)] + [0])
+    st = [torch.empty((NG, S, KITTI_NT), dtype=torch.int32, device=dev) for _ in range(3)]
+    st_sim = torch.empty((NG, S, KITTI_NT), dtype=torch.float64, device=dev)
+    _check(lib().u3d_kitti_pass2(_ptr(dt), _ptr(dt_off), N, _ptr(gt), _ptr(gt_off), G, S, _ptr(ov_off), P, _ptr(ov), _ptr(gt_flag),
+                                 _ptr(dt_flag), _ptr(dc_iof), _ptr(gfid), _ptr(gmet), _ptr(gmin), _ptr(thr), _ptr(nthr), NG, int(aos), lds,
+                                 _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st_sim), _stream()), "kitti_pass2")
+    tot = torch.empty((NG, 3, KITTI_NT), dtype=torch.int32, device=dev)
+    sim = torch.empty((NG, KITTI_NT), dtype=torch.float64, device=dev)
+    ap = torch.empty((NG, 4), dtype=torch.float64, device=dev)
+    _check(lib().u3d_kitti_reduce(_ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st_sim), S, _ptr(nthr), NG, _ptr(tot), _ptr(sim), _ptr(ap),
+                                  _stream()), "kitti_reduce")
+    return dict(ov=ov, ov_off=ov_off, gt_flag=gt_flag, dt_flag=dt_flag, nvalid=nvalid, dc_iof=dc_iof, tp_sc=tp_sc, thr=thr, nthr=nthr,
+                tot=tot, sim=sim, ap=ap)
 
 
 def count_tensor(n, device):

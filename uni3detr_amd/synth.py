@@ -92,3 +92,108 @@ def eval_scenes(n_scenes, n_det, num_classes, seed=0, max_gt=12, pc_range=SUNRGB
         p = rng.permutation(nd)
         out.append((gt, gl.astype(np.int64), db[p], ds[p], dl[p]))
     return out
+
+
+# KITTI-like camera calibration (public KITTI object-benchmark values, rounded)
+_KITTI_P2 = np.array([[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884],
+                      [0.0, 0.0, 0.0, 1.0]])
+_KITTI_TR = np.array([[7.533745e-03, -9.999714e-01, -6.166020e-04, -4.069766e-03], [1.480249e-02, 7.280733e-04, -9.998902e-01, -7.631618e-02],
+                      [9.998621e-01, 7.523790e-03, 1.480755e-02, -2.717806e-01], [0.0, 0.0, 0.0, 1.0]])
+# (name, l, h, w, weight)
+_KITTI_OBJECTS = (("Car", 3.9, 1.55, 1.65, 0.45), ("Van", 5.0, 2.1, 1.9, 0.08), ("Pedestrian", 0.85, 1.75, 0.65, 0.2),
+                  ("Person_sitting", 0.8, 1.25, 0.6, 0.05), ("Cyclist", 1.75, 1.72, 0.6, 0.12), ("DontCare", 0, 0, 0, 0.1))
+
+
+def _rot_x(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+
+
+def kitti_scenes(n, max_objects=16, det_per_scene=40, class_names=("Pedestrian", "Cyclist", "Car"), seed=0, image_shape=(375, 1242),
+                 miss=0.15, dup=0.2):
+    """Seeded KITTI-shaped evaluation sets -> (infos, results).
+
+    infos: mmdet3d KITTI info dicts (image.image_idx / image_shape, calib.P2 / R0_rect / Tr_velo_to_cam as 4x4, annos in the camera frame
+    with name / truncated / occluded / alpha / bbox / dimensions (l, h, w) / location (bottom centre) / rotation_y; DontCare rows have
+    location -1000, dimensions -1, rotation_y and alpha -10).  Objects are Car / Van / Pedestrian / Person_sitting / Cyclist / DontCare at
+    5-65 m, so 2-D heights spread around the 25 / 40 px limits; occlusion 0-3, truncation 0-0.6.
+    results: `simple_test`-style dicts of LiDAR bottom-centre boxes f32 [m,7] (counter-clockwise yaw), scores f32 [m], labels i64 [m] in
+    `class_names` order: perturbed copies of the GT (Van detected as Car, Person_sitting as Pedestrian; some missed, some duplicated)
+    plus false positives, `det_per_scene` rows at most (an int, or a [n] array)."""
+    from .kitti_eval import project_bbox
+    rng = np.random.default_rng(seed)
+    H, W = image_shape
+    names = [o[0] for o in _KITTI_OBJECTS]
+    prob = np.array([o[4] for o in _KITTI_OBJECTS])
+    prob = prob / prob.sum()
+    as_det = {"Car": "Car", "Van": "Car", "Pedestrian": "Pedestrian", "Person_sitting": "Pedestrian", "Cyclist": "Cyclist"}
+    infos, results = [], []
+    for s in range(n):
+        R0 = np.eye(4)
+        R0[:3, :3] = _rot_x(rng.normal(0, 0.004))
+        Tr = _KITTI_TR.copy()
+        Tr[:3, 3] += rng.normal(0, 0.01, 3)
+        P2 = _KITTI_P2.copy()
+        m = int(rng.integers(0, max_objects + 1))
+        kinds = rng.choice(len(names), m, p=prob)
+        rows = []
+        placed = []
+        for k in kinds:
+            name, l, h, w, _ = _KITTI_OBJECTS[k]
+            if name == "DontCare":
+                x1, y1 = rng.uniform(0, W - 40), rng.uniform(100, H - 20)
+                bw, bh = rng.uniform(15, 120), rng.uniform(10, 60)
+                rows.append((name, -1.0, -1, -10.0, [x1, y1, min(x1 + bw, W), min(y1 + bh, H)], [-1.0, -1.0, -1.0], [-1000.0, -1000.0, -1000.0], -10.0))
+                continue
+            dims = np.array([l, h, w]) * rng.uniform(0.9, 1.1, 3)
+            for _ in range(20):
+                z = rng.uniform(5, 65)
+                x = rng.uniform(-0.45, 0.45) * z
+                if all(abs(x - px) > 2.5 or abs(z - pz) > 5.5 for px, pz in placed):
+                    break
+            placed.append((x, z))
+            loc = np.array([x, 1.65 + rng.normal(0, 0.05), z])
+            ry = rng.uniform(-np.pi, np.pi)
+            bb = project_bbox(loc, dims, ry, P2)[0]
+            bb[:2] = np.maximum(bb[:2], 0)
+            bb[2:] = np.minimum(bb[2:], [W, H])
+            if not (bb[2] > bb[0] + 1 and bb[3] > bb[1] + 1):
+                continue
+            trunc = float(rng.choice([0.0, 0.0, 0.0, 0.1, 0.2, 0.4, 0.6]))
+            occ = int(rng.choice([0, 0, 1, 2, 3], p=[0.4, 0.2, 0.2, 0.15, 0.05]))
+            rows.append((name, trunc, occ, float(ry - np.arctan2(x, z)), bb.tolist(), dims.tolist(), loc.tolist(), float(ry)))
+        annos = dict(name=np.array([r[0] for r in rows], dtype="<U14"), truncated=np.array([r[1] for r in rows], np.float64),
+                     occluded=np.array([r[2] for r in rows], np.int64), alpha=np.array([r[3] for r in rows], np.float64),
+                     bbox=np.array([r[4] for r in rows], np.float64).reshape(-1, 4),
+                     dimensions=np.array([r[5] for r in rows], np.float64).reshape(-1, 3),
+                     location=np.array([r[6] for r in rows], np.float64).reshape(-1, 3),
+                     rotation_y=np.array([r[7] for r in rows], np.float64))
+        infos.append(dict(image=dict(image_idx=s, image_shape=np.array([H, W], np.int32)),
+                          calib=dict(P2=P2, R0_rect=R0, Tr_velo_to_cam=Tr), annos=annos))
+        # detections: camera -> LiDAR with inv(R0_rect @ Tr_velo_to_cam), yaw = -ry - pi/2, (dx, dy, dz) = (l, w, h)
+        Tinv = np.linalg.inv(R0 @ Tr)
+        nd = int(det_per_scene[s]) if np.ndim(det_per_scene) else int(det_per_scene)
+        boxes, labels, scores = [], [], []
+        for r in rows:
+            if r[0] not in as_det or as_det[r[0]] not in class_names or rng.uniform() < miss:
+                continue
+            for _ in range(2 if rng.uniform() < dup else 1):
+                loc = np.array(r[6]) + rng.normal(0, 0.15, 3) * np.array([1.0, 0.3, 1.0])
+                dims = np.array(r[5]) * rng.uniform(0.9, 1.1, 3)
+                ry = r[7] + rng.normal(0, 0.1)
+                p = Tinv @ np.append(loc, 1.0)
+                boxes.append([p[0], p[1], p[2], dims[0], dims[2], dims[1], -ry - np.pi / 2])
+                labels.append(class_names.index(as_det[r[0]]))
+                scores.append(rng.uniform(0.3, 1.0))
+        boxes, labels, scores = boxes[:nd], labels[:nd], scores[:nd]
+        nfp = nd - len(boxes)
+        for _ in range(nfp):
+            c = int(rng.integers(0, len(class_names)))
+            _, l, h, w, _ = _KITTI_OBJECTS[names.index(class_names[c])]
+            boxes.append([rng.uniform(0, 70), rng.uniform(-40, 40), rng.uniform(-2.5, -1.0), l, w, h, rng.uniform(-np.pi, np.pi)])
+            labels.append(c)
+            scores.append(rng.uniform(0.0, 0.7))
+        perm = rng.permutation(len(boxes))
+        results.append(dict(boxes_3d=np.asarray(boxes, np.float32).reshape(-1, 7)[perm], scores_3d=np.asarray(scores, np.float32)[perm],
+                            labels_3d=np.asarray(labels, np.int64)[perm]))
+    return infos, results
