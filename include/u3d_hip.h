@@ -690,6 +690,47 @@ int32_t u3d_kitti_reduce(const int32_t* st_tp, const int32_t* st_fp, const int32
                          const int32_t* nthr, int32_t n_group, int32_t* tot, double* sim_tot, double* ap, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
+ * nuScenes detection evaluation (the nuscenes-devkit's detection_cvpr_2019: filter_eval_boxes, accumulate, calc_ap, calc_tp; semantics
+ * in uni3detr_amd/nuscenes_eval.py).  Records are f64 [., 12]: global centre (gravity), size (w, l, h), global yaw, global velocity
+ * (x, y), score (predictions) / num_lidar_pts + num_radar_pts (GT), class (0..n_cls-1, -1 other, -2 bicycle rack), attribute code
+ * (-1 = ''; a rack row holds its LiDAR-frame yaw there).  Samples are CSR: off int32 [n_sample+1]; calib f64 [n_sample][24] =
+ * lidar2ego rotation (3x3 row-major), translation, ego2global rotation, translation.  Thresholds: ths f64 [4], tp_th = the index of
+ * the TP-error threshold.
+ * u3d_nusc_convert: LiDAR rows f64 [n][9] (x, y, z, l, w, h, yaw, vx, vy; z is the bottom for predictions, the gravity centre for GT),
+ *   cls int32 [n], attr int32 [n] (GT), aux f64 [n] (score / points) -> rec [n][12], valid int32 [n] (predictions: a label in range
+ *   and ego-frame xy radius <= cls_range; GT: an evaluated class or a rack).  attr_moving / attr_still int32 [n_cls]: the prediction
+ *   attribute codes by |global v_xy| > 0.2.
+ * u3d_nusc_filter: valid &= ego_dist < cls_range, GT points != 0, not (bike[class] and centre inside a rack row of gt / gt_off).
+ * u3d_nusc_compact: out[pos[d]] = rec[d] where valid[d] (pos = exclusive scan of valid).
+ * u3d_nusc_rank_keys: key int64 [n] / idx int32 [n]: key[n-1-i] = descending-orderable score of row i, idx[n-1-i] = i.
+ * u3d_nusc_match: one wave per segment (class * n_sample + sample): rank int32 [n] = prediction rows in rank order, mperm int32 [n] =
+ *   rank positions grouped by segment, mseg [n_seg+1]; gord = GT rows grouped by segment, gseg [n_seg+1]; max_gt = the largest GT
+ *   segment (U3D_ERR_UNSUPPORTED above 2048; dynamic LDS u3d_nusc_match_lds(max_gt)) -> tp int8 [4][n], match int32 [n] (GT row at
+ *   tp_th, -1 = none), by rank position.
+ * u3d_nusc_accumulate: one workgroup per (class, threshold).  cseg [n_cls+1] = class segments of the rank order, npos [n_cls],
+ *   gcoff [n_cls] = exclusive scan of npos, rec_interp f64 [101], period f64 [n_cls]; ws of u3d_nusc_accumulate_workspace(n, n_gt)
+ *   bytes -> prec / conf f64 [n_cls][4][101], err f64 [n_cls][5][101] (trans, scale, orient, vel, attr), ap f64 [n_cls][4],
+ *   tp_err f64 [n_cls][5] (calc_tp), mri int32 [n_cls][4] (max_recall_ind).
+ * ---------------------------------------------------------------------------------------------- */
+int32_t u3d_nusc_convert(const double* rows, const int32_t* cls, const int32_t* attr, const double* aux, const int32_t* off, int32_t n_sample,
+                         int32_t n, const double* calib, int32_t is_pred, const double* cls_range, const int32_t* attr_moving,
+                         const int32_t* attr_still, int32_t n_cls, double* rec, int32_t* valid, u3d_stream s);
+int32_t u3d_nusc_filter(const double* rec, const int32_t* off, int32_t n_sample, int32_t n, int32_t is_pred, const double* calib,
+                        const double* gt, const int32_t* gt_off, const double* cls_range, const int32_t* bike, int32_t n_cls, int32_t* valid,
+                        u3d_stream s);
+int32_t u3d_nusc_compact(const double* rec, const int32_t* valid, const int32_t* pos, int32_t n, double* out, u3d_stream s);
+int32_t u3d_nusc_rank_keys(const double* rec, int32_t n, int64_t* key, int32_t* idx, u3d_stream s);
+int64_t u3d_nusc_match_lds(int32_t max_gt);
+int32_t u3d_nusc_match(const double* pred, const int32_t* rank, const int32_t* mperm, const int32_t* mseg, int32_t n_seg, int32_t n,
+                       const double* gt, const int32_t* gord, const int32_t* gseg, int32_t max_gt, const double* ths, int32_t tp_th, int8_t* tp,
+                       int32_t* match, u3d_stream s);
+int64_t u3d_nusc_accumulate_workspace(int32_t n, int32_t n_gt);
+int32_t u3d_nusc_accumulate(const double* pred, const double* gt, const int32_t* rank, const int32_t* cseg, const int32_t* npos,
+                            const int32_t* gcoff, int32_t n_cls, int32_t n, int32_t n_gt, const int8_t* tp, const int32_t* match,
+                            const double* rec_interp, const double* period, int32_t tp_th, void* ws, int64_t ws_bytes, double* prec,
+                            double* conf, double* err, double* ap, double* tp_err, int32_t* mri, u3d_stream s);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused decoder layer (bf16 MFMA, f32 accumulation / residual stream / LayerNorm statistics / softmax statistics).
  * One call = one Uni3DETRTransformerDecoder layer over ALL query groups of all scenes, plus everything the decoder loop and the head
  * hang on that layer's state (ref: models/utils/uni3detr_transformer.py:145-212 decoder loop, :33-65 sine embedding, :271-360

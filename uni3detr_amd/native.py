@@ -197,6 +197,14 @@ _SIGS = {
     "u3d_kitti_pass2_lds": (_L, [_I, _I]),
     "u3d_kitti_pass2": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P]),
     "u3d_kitti_reduce": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "u3d_nusc_convert": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "u3d_nusc_filter": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "u3d_nusc_compact": (_I, [_P, _P, _P, _I, _P, _P]),
+    "u3d_nusc_rank_keys": (_I, [_P, _I, _P, _P, _P]),
+    "u3d_nusc_match_lds": (_L, [_I]),
+    "u3d_nusc_match": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "u3d_nusc_accumulate_workspace": (_L, [_I, _I]),
+    "u3d_nusc_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "u3d_decoder_layer_slots": (_I, [_I, _I, _I, _P, _P]),
     "u3d_decoder_layer_blocks": (_I, [_I]),
     "u3d_decoder_layer_fwd": (_I, [C.POINTER(DecLayerParams), C.POINTER(DecLayerDims)] + [_P] * 11 + [_L, _P]),
@@ -1426,6 +1434,86 @@ def kitti_eval_core(dt, dt_off, gt, gt_off, cls, gfid, gmet, gmin, aos, dt_count
                                   _stream()), "kitti_reduce")
     return dict(ov=ov, ov_off=ov_off, gt_flag=gt_flag, dt_flag=dt_flag, nvalid=nvalid, dc_iof=dc_iof, tp_sc=tp_sc, thr=thr, nthr=nthr,
                 tot=tot, sim=sim, ap=ap)
+
+
+NUSC_REC, NUSC_NTH, NUSC_NI = 12, 4, 101
+
+
+def nusc_to_global(rows, cls, attr, aux, off, calib, is_pred, cls_range, attr_moving, attr_still, bike, gt_rec=None, gt_off=None):
+    """nuScenes boxes -> filtered global records (u3d_nusc_convert, u3d_nusc_filter + a stable compaction).  rows f64 [n,9] LiDAR
+    (x, y, z, l, w, h, yaw, vx, vy), cls int32 [n], attr int32 [n] (GT; None for predictions), aux f64 [n] (score / points), off int32
+    [S+1], calib f64 [S,24], cls_range f64 [C], attr_moving / attr_still / bike int32 [C]; gt_rec / gt_off: the converted, uncompacted GT
+    of the same samples (its rack rows) for predictions, None for GT itself.
+    -> (all f64 [n,12] before the filters, valid int32 [n], records f64 [m,12] of the valid rows in input order, offsets int32 [S+1]).
+    One host synchronisation (m)."""
+    n, S, C = rows.shape[0], off.numel() - 1, cls_range.numel()
+    dev = off.device
+    rec = torch.empty((n, NUSC_REC), dtype=torch.float64, device=dev)
+    valid = torch.empty((n,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_nusc_convert(_ptr(rows), _ptr(cls), _ptr(attr), _ptr(aux), _ptr(off), S, n, _ptr(calib), int(is_pred), _ptr(cls_range),
+                                  _ptr(attr_moving), _ptr(attr_still), C, _ptr(rec), _ptr(valid), _stream()), "nusc_convert")
+    if gt_rec is None:
+        gt_rec, gt_off = rec, off
+    _check(lib().u3d_nusc_filter(_ptr(rec), _ptr(off), S, n, int(is_pred), _ptr(calib), _ptr(gt_rec) if gt_rec.numel() else None,
+                                 _ptr(gt_off), _ptr(cls_range), _ptr(bike), C, _ptr(valid), _stream()), "nusc_filter")
+    incl = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), torch.cumsum(valid, 0, dtype=torch.int32)])
+    new_off = incl[off.long()].to(torch.int32).contiguous()
+    pos = incl[:-1].contiguous()
+    m = int(incl[-1])
+    out = torch.empty((m, NUSC_REC), dtype=torch.float64, device=dev)
+    _check(lib().u3d_nusc_compact(_ptr(rec), _ptr(valid), _ptr(pos), n, _ptr(out), _stream()), "nusc_compact")
+    return rec, valid, out, new_off
+
+
+def _segments(key, n_seg):
+    """stable order of int64 keys in [0, n_seg) and their CSR offsets int32 [n_seg+1]"""
+    order = torch.sort(key, stable=True).indices
+    seg = torch.zeros(n_seg + 1, dtype=torch.int64, device=key.device)
+    seg[1:] = torch.cumsum(torch.bincount(key, minlength=n_seg), 0)
+    return order, seg.to(torch.int32)
+
+
+def nusc_metrics(pred, pred_off, gt, gt_off, n_cls, ths, tp_th, rec_interp, period):
+    """nuScenes matching and accumulation over filtered global records (u3d_nusc_rank_keys, u3d_nusc_match, u3d_nusc_accumulate; ATen
+    sorts the keys).  pred / gt f64 [.,12] with offsets int32 [S+1], ths f64 [4], rec_interp f64 [101], period f64 [C] (device).
+    -> dict of device tensors: rank int32 [n] (prediction rows in rank order), cseg int32 [C+1], npos int32 [C], tp int8 [4,n] and
+    match int32 [n] by rank position, prec / conf f64 [C,4,101], err f64 [C,5,101], ap f64 [C,4], tp_err f64 [C,5], mri int32 [C,4].
+    One host synchronisation (the largest GT segment, for the LDS size)."""
+    dev = pred_off.device
+    n, g, S, C = pred.shape[0], gt.shape[0], pred_off.numel() - 1, n_cls
+    samp = lambda off, m: torch.repeat_interleave(torch.arange(S, device=dev), (off[1:] - off[:-1]).long(), output_size=m)  # noqa: E731
+    key = torch.empty((n,), dtype=torch.int64, device=dev)
+    idx = torch.empty((n,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_nusc_rank_keys(_ptr(pred), n, _ptr(key), _ptr(idx), _stream()), "nusc_rank_keys")
+    by_score = idx.long()[torch.sort(key, stable=True).indices]              # (score desc, row desc)
+    pcls = pred[:, 10].long()
+    o, cseg = _segments(pcls[by_score], C)
+    rank = by_score[o]
+    mkey = pcls[rank] * S + samp(pred_off, n)[rank]
+    mperm, mseg = _segments(mkey, C * S)
+    gkey = gt[:, 10].long() * S + samp(gt_off, g)
+    gord, gseg = _segments(gkey, C * S)
+    npos = torch.bincount(gt[:, 10].long(), minlength=C).to(torch.int32)
+    gcoff = (torch.cumsum(npos, 0, dtype=torch.int32) - npos).contiguous()
+    max_gt = int((gseg[1:] - gseg[:-1]).max()) if g else 0
+    rank, mperm, gord = rank.to(torch.int32).contiguous(), mperm.to(torch.int32).contiguous(), gord.to(torch.int32).contiguous()
+    tp = torch.empty((NUSC_NTH, n), dtype=torch.int8, device=dev)
+    match = torch.empty((n,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_nusc_match(_ptr(pred) if n else None, _ptr(rank) if n else None, _ptr(mperm) if n else None, _ptr(mseg), C * S, n,
+                                _ptr(gt) if g else None, _ptr(gord) if g else None, _ptr(gseg), max_gt, _ptr(ths), tp_th,
+                                _ptr(tp) if n else None, _ptr(match) if n else None, _stream()), "nusc_match")
+    ws = torch.empty((int(lib().u3d_nusc_accumulate_workspace(n, g)),), dtype=torch.uint8, device=dev)
+    prec = torch.empty((C, NUSC_NTH, NUSC_NI), dtype=torch.float64, device=dev)
+    conf = torch.empty_like(prec)
+    err = torch.empty((C, 5, NUSC_NI), dtype=torch.float64, device=dev)
+    ap = torch.empty((C, NUSC_NTH), dtype=torch.float64, device=dev)
+    tp_err = torch.empty((C, 5), dtype=torch.float64, device=dev)
+    mri = torch.empty((C, NUSC_NTH), dtype=torch.int32, device=dev)
+    nz = lambda t: _ptr(t) if t.numel() else None  # noqa: E731
+    _check(lib().u3d_nusc_accumulate(nz(pred), nz(gt), nz(rank), _ptr(cseg), _ptr(npos), _ptr(gcoff), C, n, g, nz(tp), nz(match),
+                                     _ptr(rec_interp), _ptr(period), tp_th, nz(ws), ws.numel(), _ptr(prec), _ptr(conf), _ptr(err), _ptr(ap),
+                                     _ptr(tp_err), _ptr(mri), _stream()), "nusc_accumulate")
+    return dict(rank=rank, cseg=cseg, npos=npos, tp=tp, match=match, prec=prec, conf=conf, err=err, ap=ap, tp_err=tp_err, mri=mri)
 
 
 def count_tensor(n, device):

@@ -197,3 +197,113 @@ def kitti_scenes(n, max_objects=16, det_per_scene=40, class_names=("Pedestrian",
         results.append(dict(boxes_3d=np.asarray(boxes, np.float32).reshape(-1, 7)[perm], scores_3d=np.asarray(scores, np.float32)[perm],
                             labels_3d=np.asarray(labels, np.int64)[perm]))
     return infos, results
+
+
+# nuScenes-like object sizes (l, w, h) and how often each class appears
+_NUSC_OBJECTS = (("car", 4.6, 1.9, 1.7, 0.3), ("truck", 6.9, 2.5, 2.8, 0.08), ("trailer", 12.0, 2.9, 3.9, 0.04), ("bus", 11.0, 2.9, 3.5, 0.03),
+                 ("construction_vehicle", 6.4, 2.8, 3.2, 0.03), ("bicycle", 1.7, 0.6, 1.3, 0.06), ("motorcycle", 2.1, 0.8, 1.5, 0.06),
+                 ("pedestrian", 0.7, 0.7, 1.8, 0.2), ("traffic_cone", 0.4, 0.4, 1.1, 0.1), ("barrier", 2.5, 0.5, 1.0, 0.1))
+
+
+def _quat(roll, pitch, yaw):
+    """(w, x, y, z) of R = Rz(yaw) Ry(pitch) Rx(roll)"""
+    cr, sr, cp, sp, cy, sy = (np.cos(roll / 2), np.sin(roll / 2), np.cos(pitch / 2), np.sin(pitch / 2), np.cos(yaw / 2), np.sin(yaw / 2))
+    return [cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy]
+
+
+def nusc_samples(n, preds_per_sample=60, seed=0, class_names=None, max_gt=30, miss=0.15, dup=0.2):
+    """Seeded nuScenes-shaped evaluation sets -> (infos, results).
+
+    infos: mmdet3d v1.0 nuScenes info dicts (token, lidar2ego / ego2global rotation (w, x, y, z) with small pitch / roll and translation,
+    global translations of 300-2000 m; gt_boxes [g, 7] gravity centre (x, y, z, l, w, h, yaw), gt_names, gt_velocity [g, 2] (some NaN),
+    num_lidar_pts (some 0), num_radar_pts, gt_attr_names).  Every sample holds all 10 classes at 0-60 m, so the class ranges cut; every
+    third sample has a `static_object.bicycle_rack` row with a bicycle inside, and some rows have a non-evaluated name.  GT attributes
+    follow the prediction heuristic of the GT's own global velocity.
+    results: `simple_test`-style dicts of LiDAR bottom-centre boxes f32 [m, 9] (x, y, z, l, w, h, yaw, vx, vy), scores f32 [m] (some on a
+    0.05 grid, so equal scores occur), labels i64 [m] in `class_names` order: perturbed copies of the GT (some missed, some duplicated,
+    a few turned by pi) plus false positives, `preds_per_sample` rows at most (an int, or a [n] array)."""
+    from .nuscenes_eval import CLASSES, _attr_code, _calib, _pred_attribute, _Tables, to_global
+    class_names = tuple(CLASSES if class_names is None else class_names)
+    tab = _Tables(CLASSES)
+    rng = np.random.default_rng(seed)
+    names = [o[0] for o in _NUSC_OBJECTS]
+    prob = np.array([o[4] for o in _NUSC_OBJECTS])
+    prob = prob / prob.sum()
+    infos, results = [], []
+    for s in range(n):
+        info = dict(token=f"nusc_{seed}_{s}", lidar2ego_rotation=_quat(rng.normal(0, 0.01), rng.normal(0, 0.01), rng.uniform(-np.pi, np.pi)),
+                    lidar2ego_translation=[0.94 + rng.normal(0, 0.02), rng.normal(0, 0.02), 1.84 + rng.normal(0, 0.02)],
+                    ego2global_rotation=_quat(rng.normal(0, 0.02), rng.normal(0, 0.02), rng.uniform(-np.pi, np.pi)),
+                    ego2global_translation=[rng.uniform(300, 2000), rng.uniform(300, 2000), rng.normal(0, 1)])
+        m = int(rng.integers(len(names), max_gt + 1))
+        kinds = np.concatenate([np.arange(len(names)), rng.choice(len(names), m - len(names), p=prob)])
+        rows, gnames, vel, lid, rad = [], [], [], [], []
+        for k in kinds:
+            name, l, w, h, _ = _NUSC_OBJECTS[k]
+            r, a = rng.uniform(2, 60), rng.uniform(-np.pi, np.pi)
+            dims = np.array([l, w, h]) * rng.uniform(0.85, 1.15, 3)
+            rows.append([r * np.cos(a), r * np.sin(a), rng.normal(-1.0, 0.3), *dims, rng.uniform(-np.pi, np.pi)])
+            gnames.append(name)
+            if name in ("barrier", "traffic_cone"):
+                v = [0.0, 0.0]
+            else:
+                sp, d = (rng.uniform(0.15, 0.25) if rng.uniform() < 0.2 else rng.uniform(0, 8)), rng.uniform(-np.pi, np.pi)
+                v = [sp * np.cos(d), sp * np.sin(d)] if rng.uniform() > 0.1 else [np.nan, np.nan]
+            vel.append(v)
+            lid.append(0 if rng.uniform() < 0.08 else int(rng.integers(1, 200)))
+            rad.append(int(rng.integers(0, 4)))
+        if s % 3 == 0:                                     # a rack with a parked bicycle in it
+            c = rows[0][:2]
+            rows.append([c[0] + 4.0, c[1] + 4.0, -1.0, 3.0, 1.5, 1.2, rng.uniform(-np.pi, np.pi)])
+            gnames.append("static_object.bicycle_rack")
+            vel.append([0.0, 0.0]); lid.append(30); rad.append(0)                        # noqa: E702
+            rows.append([c[0] + 4.2, c[1] + 3.9, -1.1, 1.7, 0.6, 1.0, rng.uniform(-np.pi, np.pi)])
+            gnames.append("bicycle")
+            vel.append([0.0, 0.0]); lid.append(20); rad.append(0)                        # noqa: E702
+        if s % 4 == 1:                                     # a class outside the evaluation
+            rows.append([5.0, -3.0, -1.0, 1.0, 0.6, 0.5, 0.3])
+            gnames.append("animal")
+            vel.append([np.nan, np.nan]); lid.append(5); rad.append(0)                   # noqa: E702
+        rows = np.asarray(rows, np.float64).reshape(-1, 7)
+        vel = np.asarray(vel, np.float64).reshape(-1, 2)
+        g = rows.shape[0]
+        # GT attributes: the heuristic of the GT's global velocity
+        grows = np.concatenate([rows, vel], 1)
+        cls = np.asarray([tab.index.get(nm, -1) for nm in gnames], np.int32)
+        rec, _ = to_global(grows, np.maximum(cls, 0), np.zeros(g), None, [g], _calib(info)[None], True, tab)
+        speed = np.sqrt(rec[:, 7] * rec[:, 7] + rec[:, 8] * rec[:, 8])
+        attrs = [_pred_attribute(nm, bool(sp > 0.2)) if nm in tab.index else "" for nm, sp in zip(gnames, speed)]
+        assert all(_attr_code(a) >= -1 for a in attrs)
+        info.update(gt_boxes=rows, gt_names=np.array(gnames), gt_velocity=vel, num_lidar_pts=np.asarray(lid, np.int64),
+                    num_radar_pts=np.asarray(rad, np.int64), gt_attr_names=np.array(attrs), valid_flag=np.ones(g, bool))
+        infos.append(info)
+        # predictions
+        nd = int(preds_per_sample[s]) if np.ndim(preds_per_sample) else int(preds_per_sample)
+        boxes, labels, scores = [], [], []
+        for i in range(g):
+            if gnames[i] not in class_names or rng.uniform() < miss:
+                continue
+            for _ in range(2 if rng.uniform() < dup else 1):
+                sig = rng.choice([0.05, 0.3, 0.8, 1.5])
+                x, y, z, l, w, h, yaw = rows[i]
+                yaw = yaw + (np.pi if rng.uniform() < 0.05 else rng.normal(0, 0.15))
+                v = np.nan_to_num(vel[i]) + rng.normal(0, 0.3, 2)
+                boxes.append([x + rng.normal(0, sig), y + rng.normal(0, sig), z - h / 2 + rng.normal(0, 0.1), *(rows[i, 3:6] * rng.uniform(0.9, 1.1, 3)),
+                              yaw, v[0], v[1]])
+                labels.append(class_names.index(gnames[i]))
+                scores.append(rng.uniform(0.3, 1.0))
+        boxes, labels, scores = boxes[:nd], labels[:nd], scores[:nd]
+        for _ in range(nd - len(boxes)):
+            c = int(rng.integers(0, len(class_names)))
+            _, l, w, h, _ = _NUSC_OBJECTS[names.index(class_names[c])]
+            r, a = rng.uniform(0, 60), rng.uniform(-np.pi, np.pi)
+            boxes.append([r * np.cos(a), r * np.sin(a), rng.normal(-1.8, 0.3), l, w, h, rng.uniform(-np.pi, np.pi), *rng.normal(0, 2, 2)])
+            labels.append(c)
+            scores.append(rng.uniform(0.0, 0.6))
+        scores = np.asarray(scores, np.float64)
+        grid = rng.uniform(size=scores.shape) < 0.15
+        scores[grid] = np.round(scores[grid] * 20) / 20
+        perm = rng.permutation(len(boxes))
+        results.append(dict(boxes_3d=np.asarray(boxes, np.float32).reshape(-1, 9)[perm], scores_3d=scores.astype(np.float32)[perm],
+                            labels_3d=np.asarray(labels, np.int64)[perm]))
+    return infos, results
