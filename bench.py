@@ -2,11 +2,14 @@
 
   python bench.py --gpus N --steps K --warmup W          (N>1: one rank per GPU - started by torch.distributed.run, or, when
                                                           run bare, by bench.py itself: uni3detr_amd/launch.py)
+  python bench.py --full                                 (also everything beside the headline: roofline, CPU baseline, deviation
+                                                          from the fp32 oracle, the other precision modes and shipped workloads)
 
 One "step" = voxelize -> SparseEncoderHD -> SECOND3D/FPN -> 2xFPS -> decoder/head -> device Hungarian -> losses ->
 backward (RCCL gradient all-reduce overlapped) -> grad-clip -> AdamW, over a batch of B=8 synthetic SUN-RGB-D-shaped
 scenes per GPU (20 000 points, 300 queries; BASELINE.json configs[1]).  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs; the blocks that take runs of their own
+(`roofline`, `cpu_baseline`, `*_vs_fp32_oracle`, `modes`, `workloads`) are measured with --full.
 """
 import argparse
 import json
@@ -54,12 +57,17 @@ def parse():
     ap.add_argument("--points", type=int, default=None, help="points per scene (default: the workload's)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "mixed", "parity"],
                     help="bf16: BASELINE configs[1]; mixed: the reference's recipe (fp32 encoder + backbone, 16-bit neck + head); fp32: parity mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the `roofline`, `cpu_baseline`, `*_vs_fp32_oracle`, `modes` and `workloads` "
+                         "blocks (each can be left out with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` and `*_vs_fp32_oracle` blocks "
+                                                                   "(and with them `modes`)")
+    ap.add_argument("--no-roofline", action="store_true", help="no event-record nodes in the captured step; with --full: skip the "
+                                                               "`roofline` block")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--allow-eager", action="store_true", help="if the hipGraph capture fails, fall back to eager launches instead of exiting non-zero")
-    ap.add_argument("--no-modes", action="store_true", help="skip the `modes` block (mixed / parity throughput + logits deviation beside the bf16 headline)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` block (BASELINE.json configs[2..4] beside the headline)")
+    ap.add_argument("--no-modes", action="store_true", help="with --full: skip the `modes` block (mixed / parity throughput + logits deviation beside the bf16 headline)")
+    ap.add_argument("--no-workloads", action="store_true", help="with --full: skip the `workloads` block (BASELINE.json configs[2..4] beside the headline)")
     ap.add_argument("--workload-steps", type=int, default=30, help="timed steps of each entry of the `workloads` block (5 warm-up steps, 4 rotating batches)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (losses, head outputs, a fixed sample of the "
@@ -213,7 +221,7 @@ def time_mode(precision, args, dev, rot, cfg):
 def time_workload(name, args, dev, rank=0):
     """One more shipped configuration (BASELINE.json configs[2..4]) under the headline's protocol - bf16, hipGraph replay, capture over
     the rotating batches, untimed warm-up, timed steps between synchronisations, loss checked finite - at that configuration's own
-    batch / cloud size.  N = 1, rank 0; fewer steps and rotating batches than the headline so the default run stays within minutes."""
+    batch / cloud size.  N = 1, rank 0; fewer steps and rotating batches than the headline so a --full run stays within minutes."""
     import types
     wl = WORKLOADS[name]
     cfg = workload_cfg(name)
@@ -309,7 +317,9 @@ def main():
         if rank == 0 and not args.no_roofline and os.environ.get("U3D_GRAPH_MARKS", "1") == "1":
             # roofline timing INSIDE the replayed graphs: one exact-size eager step prices every conv launch (census); the heaviest
             # launches (equal flops: forward / input gradient / weight gradient of the 256-channel 3x3x3 layers) get an external
-            # HIP event pair each, which the capture turns into event-record nodes around those kernels (native.KernelTimer 'mark')
+            # HIP event pair each, which the capture turns into event-record nodes around those kernels (native.KernelTimer 'mark').
+            # A plain run captures them too and never reads them: the timed steps are then the same replays with or without --full
+            # (the census step also advances the dropout stream the timed steps draw from)
             nv.TIMER = nv.KernelTimer("census")
             ts.eager_step()
             torch.cuda.synchronize()
@@ -368,6 +378,7 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     dt_local = dt
+    loss_val = float(last.detach())                     # the last timed step's (the instrumented replays below overwrite it)
     if args.dump_outputs and rank == 0:
         dump_outputs(ts, args.dump_outputs)           # before the instrumented steps below train the model any further
     comm = ts.comm_exposed_ms() if use_dist else None
@@ -380,7 +391,7 @@ def main():
     timer = None
     mark_ms = None
     MARK_REPLAYS = 10
-    if marker is not None and not args.no_graph and marker.marks:
+    if args.full and marker is not None and not args.no_graph and marker.marks:
         # per-launch durations of the marked kernels as they run inside the replayed step: MARK_REPLAYS more replays (untimed),
         # events read after each
         ts.dist_on = False                               # rank 0 only from here on: no collectives
@@ -391,7 +402,7 @@ def main():
                 acc[i].append(ms)
         mark_ms = {i: float(np.mean(v)) for i, v in acc.items() if v}
     ROOF_STEPS = 3
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         ts.dist_on = False                               # instrumented steps are local to rank 0: no collectives
         from uni3detr_amd.plugin import dense as _dense
         _dense.PARALLEL_BRANCHES = False                 # one stream: per-launch event timings must not overlap other work
@@ -435,7 +446,6 @@ def main():
                  "overlap_reduce": bool(ts.overlap),
                  "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if hasattr(torch.cuda, "nccl") else None}
     dt = float(tt.item())
-    loss_val = float(last.detach())
     if not np.isfinite(loss_val):
         raise SystemExit(f"bench: training diverged (loss = {loss_val}) — a throughput number for a broken step would be meaningless")
 
@@ -604,7 +614,7 @@ def main():
                 out["roofline"]["pmc_pass"] = {"tag": pmc.get("tag"), "sources_checked": sorted(pmc.get("source_sha16", {})), "stale_sources": stale}
             if os.environ.get("U3D_BENCH_DUMP_CALLS"):
                 json.dump(calls, open(os.environ["U3D_BENCH_DUMP_CALLS"], "w"))
-        if not args.no_cpu_baseline and world == 1 and args.config == "sunrgbd":      # the CPU leg is quoted on the headline workload only
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "sunrgbd":      # the CPU leg is quoted on the headline workload only
             faulthandler.cancel_dump_traceback_later()       # CPU leg: no GPU work can hang here
             out["cpu_baseline"] = cpu_baseline(args.points)
             # checker leg: deviation of each mode from the fp32 CPU oracle on the same workload shape (2 scenes, seeded weights, dropout
@@ -632,7 +642,7 @@ def main():
                         faulthandler.cancel_dump_traceback_later()
                         print(f"[bench] modes.{mode} failed: {type(e).__name__}: {e}", file=sys.stderr, flush=True)
                         out["modes"][mode] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.config == "sunrgbd" and args.precision == "bf16" and not args.no_workloads and not args.no_graph:
+        if args.full and world == 1 and args.config == "sunrgbd" and args.precision == "bf16" and not args.no_workloads and not args.no_graph:
             # the other shipped configurations (ScanNet-large, KITTI, nuScenes were builder-run lines only): same
             # protocol, each at its own batch / cloud size; a failure is recorded, never raised
             out["workloads"] = {}

@@ -15,7 +15,7 @@ deviation drifts above them:
                         131 / 144 (91.0 %) with the direct-operand ones - same arithmetic, same precision.  The gate was 90 % when
                         only the first figure had been seen; 85 % leaves that order-dependence room and still fails on a real defect
                         (a wrong BatchNorm statistic or a dropped neighbour moves it below 60 %).
-(fp32 mode holds 1e-3 on the same quantities: tests/test_model_gpu.py.)  bench.py reports the same figures in its JSON line."""
+(fp32 mode holds 1e-3 on the same quantities: tests/test_model_gpu.py.)  `bench.py --full` reports the same figures in its JSON line."""
 import json
 import os
 
