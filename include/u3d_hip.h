@@ -170,8 +170,8 @@ int32_t u3d_linear_bf16(const void* x, const void* w, const float* bias, int32_t
  * auto_fp16).  An f32 row matrix x travels as two bf16 planes (u3d_split_rows_f32: hi = bf16(x), lo = bf16(x - hi), stacked as rows
  * [hi ; lo] with a plane stride of n_cap rows) and x.w ~ hi.wh + hi.wl + lo.wh with f32 accumulation.  The caller passes the three
  * products as three sets of offsets: nbr int32 [kvol3][ld] = (nbr, nbr, nbr + n_in_cap), w bf16 [kvol3][Cout][Cin] = (wh, wl, wh),
- * kvol3 = 3 x offsets.  out is F32 [n_out_cap][Cout]; stats: NULL or f64 [ceil(n_out_cap / u3d_igemm_fwd_stats_rows(.., kvol3))][2][Cout]
- * per-tile BatchNorm sums of the f32 output; addend: NULL or f32 [n_out_cap][Cout] summed into the result in the epilogue (the
+ * kvol3 = 3 x offsets.  out is F32 [n_out_cap][Cout]; stats: NULL or f64 [partials][2][Cout] (u3d_igemm_fwd_stats_layout(.., kvol3, 1,
+ * ..)) per-tile BatchNorm sums of the f32 output; addend: NULL or f32 [n_out_cap][Cout] summed into the result in the epilogue (the
  * residual / fan-out gradient sums of the input gradients, as u3d_igemm_fwd_add_bf16).  U3D_ERR_UNSUPPORTED unless Cin % 64 == 0 and
  * Cout % 64 == 0. */
 int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, float* out, const int32_t* n_out_dev,
@@ -206,27 +206,24 @@ int32_t u3d_split3_weights_batch(const void* jobs, int32_t njobs, int32_t total_
 /* dst bf16 [2 * n_cap][c]: rows [0, n) = bf16(x), rows [n_cap, n_cap + n) = bf16(x - hi), n = min(*n_dev, n_cap); c % 4 == 0. */
 int32_t u3d_split_rows_f32(const float* x, const int32_t* n_dev, int32_t n_cap, int32_t c, void* dst, u3d_stream s);
 /* Forward with n-major weights w[K][Cout][Cin] (the layout u3d_igemm_fwd_bf16 takes with transpose_w = 1) that also emits the
- * BatchNorm statistics of its (bf16-rounded) output per row tile: stats f64 [ceil(n_out_cap / T)][2][Cout] with
- * T = u3d_igemm_fwd_stats_tile_rows(...) (0: shape not served - use u3d_igemm_fwd_bf16 + u3d_bn_stats).  Feeds
- * u3d_bn_finalize_partials; saves the separate statistics pass over the conv output (ref: conv -> BatchNorm pairs of
- * sparse_encoder_hd.py:71-104 and second_3d.py:52-76). */
-int32_t u3d_igemm_fwd_stats_tile_rows(int32_t n_out_cap, int32_t cin, int32_t cout);
-/* Number of partials [blocks][2][Cout] u3d_igemm_fwd_stats_bf16 writes for this shape (0: not served).  The direct-operand kernels of
- * the narrow 27-offset levels (Cin, Cout in {16, 32, 64}, not 64 -> 64) write one partial per WAVE of their persistent grid:
- * u3d_igemm_fwd_stats_tile_rows is 0 for them and u3d_bn_finalize_partials takes rows_per_block = 0 (= every partial counts). */
-int32_t u3d_igemm_fwd_stats_blocks(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol);
-/* Rows per partial (= rows_per_block of u3d_bn_finalize_partials) for a conv with a neighbour table and kvol offsets: like
- * u3d_igemm_fwd_stats_tile_rows, but aware of the kernels whose choice depends on the reduction length (256 x 128 eight-phase tiles
- * for long reductions); 0 = per-wave partials / shape not served. */
-int32_t u3d_igemm_fwd_stats_rows(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol);
+ * BatchNorm statistics of its (bf16-rounded) output: stats f64 [partials][2][Cout] in the layout u3d_igemm_fwd_stats_layout reports
+ * (U3D_ERR_UNSUPPORTED there: shape not served - use u3d_igemm_fwd_bf16 + u3d_bn_stats).  Feeds u3d_bn_finalize_partials; saves the
+ * separate statistics pass over the conv output (ref: conv -> BatchNorm pairs of sparse_encoder_hd.py:71-104 and second_3d.py:52-76). */
 int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
                                  const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                  double* stats, u3d_stream s);
+/* The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (has_nbr: a neighbour table is passed), computed by the plan the
+ * launch follows: *partials row tiles of *rows_per_partial rows (= rows_per_block of u3d_bn_finalize_partials), or with
+ * *rows_per_partial = 0 one partial per WAVE of the direct-operand kernels of the narrow 27-offset levels (every partial counts).
+ * U3D_ERR_UNSUPPORTED: no kernel with a statistics epilogue serves the shape.  u3d_igemm_fwd_split_bf16 and
+ * u3d_igemm_dgrad_bnstats_bf16 write the same row-tile layout wherever they serve a shape. */
+int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
+                                   int32_t* rows_per_partial);
 /* BatchNorm-BACKWARD statistics out of the input-gradient launch that writes the BatchNorm's dy (ref: the conv -> BatchNorm -> ReLU
  * chains of sparse_encoder_hd.py:71-104 / second_3d.py:52-76; torch's batch_norm_backward makes a separate reduction pass over dy and
  * x).  x: the BatchNorm's input (bf16 [n][C]); y: its output when the ReLU mask cannot be recomputed from x (residual layers), else
  * NULL; mean/invstd (+ gamma/beta when relu and y == NULL) f32 [C].  The launch leaves, per row tile, sum(g) and sum(g * xhat) with
- * g = dy under the ReLU mask: f64 [ceil(n/T)][2][C], T = u3d_igemm_fwd_stats_rows(...) (128 for the halo kernel), which
+ * g = dy under the ReLU mask: f64 [partials][2][C] as u3d_igemm_fwd_stats_layout(.., 1, ..) reports (128-row tiles for the halo kernel), which
  * u3d_bn_bwd_finalize_partials reduces to what u3d_bn_bwd_stats returns. */
 typedef struct {
   const void* x;

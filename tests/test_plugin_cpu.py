@@ -47,6 +47,62 @@ def test_library_exports_every_declared_symbol():
     assert lib.u3d_version() >= 1
 
 
+# u3d_igemm_fwd_stats_layout: (n_out_cap, cin, cout, kvol, has_nbr) -> (statistics partials, rows per partial), None = no kernel with a
+# statistics epilogue serves the shape; rows 0 = one partial per wave of the direct-operand kernels.  Direct-operand row counts are
+# small enough that the grid is bounded by the tiles, not by the CU count (256 assumed without a GPU, as the MI355X has).
+STATS_LAYOUT = [
+    # tests/test_sparse_gpu.py::test_conv_epilogue_bn_statistics_match_separate_pass
+    (1200, 64, 64, 27, 1, (10, 128)), (1188, 128, 256, 27, 1, (10, 128)), (192000, 256, 256, 27, 1, (750, 256)),
+    (3003, 32, 32, 27, 1, (64, 0)), (1200, 16, 32, 27, 1, (32, 0)), (1512, 64, 32, 27, 1, (64, 0)), (12240, 32, 16, 27, 1, (192, 0)),
+    (60, 64, 16, 27, 1, (32, 0)), (12000, 512, 512, 27, 1, (63, 192)), (44640, 256, 256, 27, 1, (233, 192)),
+    (40000, 512, 512, 27, 1, (209, 192)),
+    # 256-column tiles at 127 / 128 workgroups, with and without a table
+    (32512, 256, 256, 27, 1, (127, 256)), (32513, 256, 256, 27, 1, (170, 192)), (32512, 256, 256, 1, 0, (254, 128)),
+    (32513, 256, 256, 1, 0, (128, 256)),
+    # 256 x 128 eight-phase tiles: 159 / 160 workgroups, 47 / 48 k-tiles
+    (40704, 128, 128, 27, 1, (318, 128)), (40705, 128, 128, 27, 1, (213, 192)), (48000, 64, 128, 47, 1, (375, 128)),
+    (48000, 64, 128, 48, 1, (250, 192)),
+    # 192-row tiles flip back to 256 rows (both eight-phase kernels); one offset: never 192 rows
+    (49152, 256, 256, 27, 1, (256, 192)), (49153, 256, 256, 27, 1, (193, 256)), (49152, 128, 128, 27, 1, (256, 192)),
+    (49153, 128, 128, 27, 1, (193, 256)), (49152, 256, 256, 1, 1, (192, 256)),
+    # cout % 128 against cout % 256
+    (48000, 128, 384, 27, 1, (250, 192)), (48000, 128, 512, 27, 1, (250, 192)), (12000, 512, 384, 27, 1, (94, 128)),
+    (12000, 512, 512, 27, 1, (63, 192)),
+    # no table
+    (48000, 256, 256, 1, 0, (188, 256)), (12000, 512, 512, 1, 0, (94, 128)),
+    # without a table the long-reduction rule does not apply, even at 3072 input channels: 128-row tiles
+    (12000, 3072, 512, 1, 0, (94, 128)),
+    # direct-operand shapes, 64 -> 64 (LDS-DMA), a 32 -> 64 statistics launch (none), not 27 offsets, empty outputs, cin % 64
+    (12240, 16, 16, 27, 1, (192, 0)), (12240, 32, 32, 27, 1, (192, 0)), (12240, 64, 16, 27, 1, (192, 0)),
+    (12240, 64, 32, 27, 1, (192, 0)), (12240, 64, 64, 27, 1, (96, 128)), (12240, 32, 64, 27, 1, None),
+    (12240, 32, 32, 9, 1, None), (0, 32, 32, 27, 1, (0, 0)), (0, 64, 64, 27, 1, None), (1200, 48, 64, 27, 1, None),
+    # the statistics launches of bench.py's workloads (sunrgbd bf16 / parity, kitti_3classes, scannet_large, nuscenes): smallest and
+    # largest row count per shape
+    (64000, 16, 16, 27, 1, (1024, 0)), (206938, 32, 64, 27, 1, None), (960000, 32, 64, 27, 1, None),
+    (206938, 64, 64, 81, 1, (1617, 128)), (272384, 64, 64, 81, 1, (2128, 128)), (53947, 64, 128, 27, 1, (422, 128)),
+    (363264, 64, 128, 27, 1, (2838, 128)), (53947, 64, 128, 81, 1, (211, 256)), (71680, 64, 128, 81, 1, (374, 192)),
+    (192000, 128, 128, 9, 1, (1500, 128)), (704000, 128, 128, 9, 1, (5500, 128)), (192000, 128, 128, 27, 1, (750, 256)),
+    (53947, 128, 128, 81, 1, (211, 256)), (71680, 128, 128, 81, 1, (374, 192)), (53947, 128, 256, 1, 0, (211, 256)),
+    (704000, 128, 256, 1, 0, (2750, 256)), (53947, 128, 256, 3, 1, (211, 256)), (192000, 128, 256, 3, 1, (750, 256)),
+    (70348, 128, 256, 27, 1, (367, 192)), (91648, 128, 256, 27, 1, (478, 192)), (192000, 256, 128, 9, 1, (1500, 128)),
+    (704000, 256, 128, 9, 1, (5500, 128)), (192000, 256, 128, 27, 1, (750, 256)), (48000, 256, 256, 9, 1, (250, 192)),
+    (176000, 256, 256, 9, 1, (688, 256)), (48000, 256, 256, 27, 1, (250, 192)), (704000, 256, 256, 27, 1, (2750, 256)),
+    (192000, 256, 256, 81, 1, (750, 256)), (70348, 256, 512, 1, 0, (275, 256)), (91648, 256, 512, 1, 0, (358, 256)),
+    (12000, 256, 512, 9, 1, (94, 128)), (44000, 256, 512, 9, 1, (230, 192)), (12000, 256, 512, 27, 1, (63, 192)),
+    (384000, 512, 128, 9, 1, (1500, 256)), (96000, 512, 256, 9, 1, (500, 192)), (12000, 512, 512, 9, 1, (63, 192)),
+    (44000, 512, 512, 9, 1, (230, 192)), (12000, 512, 512, 27, 1, (63, 192)),
+]
+
+
+def test_fwd_stats_layout_follows_the_dispatch():
+    lib = ctypes.CDLL(nv.LIB_PATH)
+    for n, cin, cout, kvol, has_nbr, want in STATS_LAYOUT:
+        p, r = ctypes.c_int32(-1), ctypes.c_int32(-1)
+        rc = lib.u3d_igemm_fwd_stats_layout(n, cin, cout, kvol, has_nbr, ctypes.byref(p), ctypes.byref(r))
+        got = (p.value, r.value) if rc == 0 else (None if rc == -2 else rc)
+        assert got == want, ((n, cin, cout, kvol, has_nbr), got, want)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(nv, "_lib", None)
     monkeypatch.setattr(nv, "LIB_PATH", "/nonexistent/libu3d_hip.so")

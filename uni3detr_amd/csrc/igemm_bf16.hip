@@ -10,6 +10,7 @@
 // Operands whose reduction index is the LDS row (W[k][n] in forward, both operands in wgrad) are fetched with
 // ds_read_b64_tr_b16; rows are padded by 16 elements so that those reads are bank-conflict free.
 #include "common.h"
+#include "igemm_direct.h"
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -100,15 +101,6 @@ __device__ __forceinline__ void bn_bwd_tile_sums(const BnEpi bn, u16* smem, int 
   }
 }
 
-#ifndef IGEMM_SMALL_C
-#define IGEMM_SMALL_C 1
-#endif
-#ifndef IGEMM_DIRECT
-#define IGEMM_DIRECT 1     /* narrow sparse levels on the direct-operand kernel (igemm_direct.hip); 0: the tiled BK = 32 kernels below */
-#endif
-int u3d_launch_igemm_direct(const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev, int n_out_cap,
-                            int cin, int cout, int kvol, int transpose_w, hipStream_t s, const void* addend = nullptr,
-                            double* stats = nullptr, int* stats_blocks = nullptr, int f32acc = 0);
 #ifndef IGEMM_SMALL_PF
 #define IGEMM_SMALL_PF 1   /* stages of operand loads in flight in the 16/32-channel kernels (1: the wide layers' one-stage pipeline) */
 #endif
@@ -488,9 +480,6 @@ static int launch_igemm_fwd(const void* in, const void* w, const int32_t* nbr, i
 // by an XOR swizzle applied on the SOURCE side: 16-byte part p of row r is stored in slot p ^ ((r >> 1) & 7); a fragment read
 // (16 rows x 8 B per k-group) then covers all 64 banks exactly once.
 // =============================================================================================
-#ifndef IGEMM_GLDS
-#define IGEMM_GLDS 1
-#endif
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, bool F32OUT = false>
@@ -765,9 +754,6 @@ __device__ __forceinline__ void igemm_glds_body(const u16* __restrict__ in, cons
 // A0 + B0 one barrier before their first reader - two barriers for the wave row that runs behind.  Nothing waits for vmcnt(0)
 // inside the loop.  Rows / swizzle / fragment layout / epilogue as igemm_glds_body.
 // =============================================================================================
-#ifndef IGEMM_GLDS8
-#define IGEMM_GLDS8 1
-#endif
 #ifndef GLDS8_PRIO
 #define GLDS8_PRIO 1
 #endif
@@ -780,7 +766,7 @@ __device__ __forceinline__ void igemm_glds_body(const u16* __restrict__ in, cons
 // RB = 16-row blocks per wave and row half: 4 = the 256-row tile; 3 = a 192-row tile in the SAME LDS image and schedule (the last
 // 16 rows of every 64-row piece quarter are dead: never requested - their LDS-DMA lanes carry the "no row" offset -, never read,
 // never multiplied).  For row counts where 256-row tiles leave a quarter of the CUs without a workgroup (48 000 rows x 256 columns:
-// 188 tiles for 256 CUs; 192-row tiles: 250) - see igemm_rows192().
+// 188 tiles for 256 CUs; 192-row tiles: 250) - see igemm_rows192() and fwd_plan().
 template <bool F32OUT = false, int RB = 4>
 __device__ __forceinline__ void igemm_glds8_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr,
                                                  int ld, u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap,
@@ -1012,12 +998,8 @@ __global__ __launch_bounds__(512) void k_igemm_glds8_192x256_f32o(const u16* in,
 }
 // 192-row tiles instead of 256-row ones when they finish sooner on 256 CUs with one workgroup each (time ~ rounds x tile rows): the
 // mid-size layers of the dense stack (48 000 rows x 256 columns: 188 -> 250 workgroups, 12 000 rows x 512 columns in 128-column
-// tiles: 188 -> 252).  Convolutions with a neighbour table and more than one offset only (the plain-GEMM callers stay on 256 rows).
-#ifndef IGEMM_ROWS192
-#define IGEMM_ROWS192 1
-#endif
-static inline bool igemm_rows192(const int32_t* nbr, int n_out_cap, int col_blocks, int kvol) {
-  if (!IGEMM_ROWS192 || !nbr || kvol <= 1) return false;
+// tiles: 188 -> 252).  Where fwd_plan() asks.
+static inline bool igemm_rows192(int n_out_cap, int col_blocks) {
   const long long w256 = (long long)u3d_cdiv(n_out_cap, 256) * col_blocks, w192 = (long long)u3d_cdiv(n_out_cap, 192) * col_blocks;
   return (double)u3d_cdiv(w192, 256) * 192.0 * 1.05 < (double)u3d_cdiv(w256, 256) * 256.0;
 }
@@ -1035,9 +1017,6 @@ static inline bool igemm_rows192(const int32_t* nbr, int n_out_cap, int col_bloc
 // Not for short reductions: with 18 k-tiles per tile a quarter of a workgroup's life is prologue + epilogue, which a second
 // resident workgroup hides and this 144 KiB one cannot (measured on par there).
 // =============================================================================================
-#ifndef IGEMM_GLDS8N
-#define IGEMM_GLDS8N 1
-#endif
 template <bool F32OUT = false, int RB = 4>      // RB = 3: 192-row tiles (48 live rows per wave), see igemm_glds8_body
 __device__ __forceinline__ void igemm_glds8n_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr,
                                                   int ld, u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap,
@@ -1248,31 +1227,6 @@ __global__ __launch_bounds__(512) void k_igemm_glds8_192x128_f32o(const u16* in,
                                                                   const float* bias, int relu, double* stats, BnEpi bn) {
   igemm_glds8n_body<true, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
 }
-// the 256 x 128 eight-phase kernel for the shapes it is dispatched on: long reductions (>= GLDS8N_MIN_KTILES k-tiles), enough
-// workgroups to keep most CUs busy with ONE per CU
-#ifndef GLDS8N_MIN_KTILES
-#define GLDS8N_MIN_KTILES 48
-#endif
-static bool igemm_glds8n_shape(const int32_t* nbr, int n_out_cap, int cin, int cout, int kvol) {
-  return IGEMM_GLDS8N && nbr && cin % 64 == 0 && cout % 128 == 0 && kvol * (cin / 64) >= GLDS8N_MIN_KTILES
-         && (long long)u3d_cdiv(n_out_cap, 256) * (cout / 128) >= 160;
-}
-static int launch_igemm_glds8n(const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
-                               int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const float* bias = nullptr, int relu = 0,
-                               double* stats = nullptr, const BnEpi bn = BnEpi{}, bool f32o = false) {
-  constexpr size_t lds = 3 * (size_t)(256 + 128) * 64 * 2;      // 144 KiB
-  U3D_ALLOW_LDS(k_igemm_glds8_256x128, lds);
-  U3D_ALLOW_LDS(k_igemm_glds8_256x128_f32o, lds);
-  U3D_ALLOW_LDS(k_igemm_glds8_192x128, lds);
-  U3D_ALLOW_LDS(k_igemm_glds8_192x128_f32o, lds);
-  const bool r192 = igemm_rows192(nbr, n_out_cap, cout / 128, kvol);
-  dim3 grid(u3d_cdiv(n_out_cap, r192 ? 192 : 256), cout / 128);
-  hipLaunchKernelGGL(r192 ? (f32o ? k_igemm_glds8_192x128_f32o : k_igemm_glds8_192x128) : (f32o ? k_igemm_glds8_256x128_f32o : k_igemm_glds8_256x128),
-                     grid, dim3(512), lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap,
-                     cin, cout, kvol, bias, relu, stats, bn);
-  return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
-}
-
 // concrete kernels (a __global__ TEMPLATE with this body lost its host stub under hipcc 7.2: undefined symbol at load time)
 #define U3D_GLDS_KERNEL(NAME, A, B, C, D)                                                                                        \
   __global__ __launch_bounds__(A* B * 64) void NAME(const u16* in, const u16* w, const int* nbr, int ld, u16* out,               \
@@ -1300,34 +1254,120 @@ U3D_GLDS_KERNEL_F32O(k_igemm_glds_128x128_f32o, 2, 2, 4, 4)
 #undef U3D_GLDS_KERNEL_F32O
 typedef void (*glds_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const float*, int, double*, BnEpi);
 
-template <int WAVES_M, int WAVES_N, int WM, int WN>
-static int launch_igemm_glds(const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
-                             int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const float* bias = nullptr, int relu = 0,
-                             double* stats = nullptr, const BnEpi bn = BnEpi{}, bool f32o = false) {
-  constexpr int BM = WAVES_M * WM * 16, BN = WAVES_N * WN * 16;
-  constexpr size_t lds = 2 * (size_t)(BM + BN) * 64 * 2;        // 256 x 256: 128 KiB
-  glds_kernel_t kern = (BM == 256 && BN == 256) ? ((IGEMM_GLDS8 && nbr) ? k_igemm_glds8_256x256 : k_igemm_glds_256x256)
-                       : (BM == 256 ? k_igemm_glds_256x128 : (BN == 128 ? k_igemm_glds_128x128 : k_igemm_glds_128x64));
-  if (f32o) {      // f32-output instantiations exist for the shapes u3d_igemm_fwd_split_bf16 dispatches: 256 x 256 (eight-phase), 128 x 128, 128 x 64
-    if (BM == 256 && BN == 256 && IGEMM_GLDS8 && nbr) kern = k_igemm_glds8_256x256_f32o;
-    else if (BM == 128 && BN == 128) kern = k_igemm_glds_128x128_f32o;
-    else if (BM == 128 && BN == 64) kern = k_igemm_glds_128x64_f32o;
-    else return U3D_ERR_UNSUPPORTED;
-  }
-  int rows = BM;
-  if (BM == 256 && BN == 256 && IGEMM_GLDS8 && nbr && igemm_rows192(nbr, n_out_cap, u3d_cdiv(cout, BN), kvol)) {
-    kern = f32o ? k_igemm_glds8_192x256_f32o : k_igemm_glds8_192x256;      // same LDS image, 192 live rows (igemm_glds8_body<., 3>)
-    rows = 192;
-  }
-  if (lds > 64 * 1024) U3D_ALLOW_LDS(kern, lds);      // one call site per template instantiation: per-kernel, per-device
-  dim3 grid(u3d_cdiv(n_out_cap, rows), u3d_cdiv(cout, BN));
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES_M * WAVES_N * 64), lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap, cin,
-                     cout, kvol, bias, relu, stats, bn);
-  return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
-}
-
 // (The register-staged "ping-pong" kernel of round 1 - two wave groups in opposite phases, measured on par with k_igemm_fwd -
 //  was removed when igemm_glds8_body took that idea to the LDS-DMA kernels; DESIGN.md 3.1 keeps its numbers.)
+
+// =============================================================================================
+// ONE launch plan for the forward / input-gradient launches on the LDS-DMA and the direct-operand kernels: fwd_plan() decides the
+// kernel, tile, grid and statistics layout of u3d_igemm_fwd_bf16 / _fwd_add_bf16 / _fwd_stats_bf16 / _fwd_split_bf16 /
+// _dgrad_bnstats_bf16 and u3d_linear_bf16, and u3d_igemm_fwd_stats_layout reports that same layout to size the buffers.
+// =============================================================================================
+// The LDS-DMA kernels: bf16- and f32-output instantiations (nullptr: none), tile, threads, dynamic LDS, and whether the epilogue
+// takes an addend (relu & 2) and the BatchNorm-backward sums (GLDS_EPI_ADDEND).
+struct GldsKernel {
+  glds_kernel_t bf16, f32;
+  int rows, cols, threads;
+  size_t lds;
+  bool addend;
+};
+#define GLDS_GEOM(A, B, C, D) A * C * 16, B * D * 16, A * B * 64, (size_t)2 * (A * C * 16 + B * D * 16) * 64 * 2     /* U3D_GLDS_KERNEL(A, B, C, D) */
+#define GLDS_GEOM_X(...) GLDS_GEOM(__VA_ARGS__)
+enum { G_256x256, G8_256x256, G8_192x256, G8_256x128, G8_192x128, G_256x128, G_128x128, G_128x64, G_COUNT };
+static const GldsKernel GLDS_KERNELS[G_COUNT] = {
+    {k_igemm_glds_256x256, nullptr, GLDS_GEOM_X(GLDS256_CFG), false},                                   // two-phase
+    {k_igemm_glds8_256x256, k_igemm_glds8_256x256_f32o, 256, 256, 512, 2 * (256 + 256) * 64 * 2, true},      // eight-phase, 128 KiB
+    {k_igemm_glds8_192x256, k_igemm_glds8_192x256_f32o, 192, 256, 512, 2 * (256 + 256) * 64 * 2, true},      // (same LDS image)
+    {k_igemm_glds8_256x128, k_igemm_glds8_256x128_f32o, 256, 128, 512, 3 * (256 + 128) * 64 * 2, true},      // eight-phase, 144 KiB
+    {k_igemm_glds8_192x128, k_igemm_glds8_192x128_f32o, 192, 128, 512, 3 * (256 + 128) * 64 * 2, true},
+    {k_igemm_glds_256x128, nullptr, GLDS_GEOM(4, 2, 4, 4), true},
+    {k_igemm_glds_128x128, k_igemm_glds_128x128_f32o, GLDS_GEOM(2, 2, 4, 4), true},
+    {k_igemm_glds_128x64, k_igemm_glds_128x64_f32o, GLDS_GEOM(4, 1, 2, 4), true},
+};
+#undef GLDS_GEOM_X
+#undef GLDS_GEOM
+
+// what the launch must do besides the convolution: PLAIN (u3d_igemm_fwd_bf16), BIAS_RELU (u3d_linear_bf16), ADD = + bf16 addend
+// (u3d_igemm_fwd_add_bf16), F32 / F32_ADD = f32 output without / with an f32 addend (u3d_igemm_fwd_split_bf16; its statistics do not
+// change the kernel), STATS = + BatchNorm statistics (u3d_igemm_fwd_stats_bf16), BN_BWD = + BatchNorm-backward sums, addend optional
+// (u3d_igemm_dgrad_bnstats_bf16)
+enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_BN_BWD };
+
+struct FwdPlan {
+  DirectPlan direct;             // direct.slot >= 0: a direct-operand kernel (igemm_direct.hip), else
+  glds_kernel_t fn = nullptr;    // an LDS-DMA kernel (GLDS_KERNELS[glds]; nullptr and direct.slot < 0: no kernel serves the shape)
+  int glds = -1, rows = 0;       // rows = row-tile height = rows per statistics partial (0: per-wave partials of the direct kernels)
+  dim3 grid;
+  int threads = 0;
+  size_t lds = 0;
+  int partials = 0;              // statistics partials a STATS / BN_BWD launch writes: [partials][2][cout]
+  bool served() const { return fn || direct.slot >= 0; }
+};
+
+constexpr int GLDS8N_MIN_KTILES = 48;     // 256 x 128 eight-phase tiles: long reductions only (k-tiles of 64 = kvol * cin / 64) ...
+constexpr int GLDS8N_MIN_WGS = 160;       // ... and enough 256-row workgroups to keep most CUs busy with ONE per CU
+
+// The rules, first match wins (n = n_out_cap; "table": a neighbour table is passed):
+//   1. PLAIN / ADD / STATS: the direct-operand kernels wherever u3d_plan_igemm_direct serves the shape (its rule: igemm_direct.h).
+//      Statistics: one partial per wave.
+//   Otherwise the LDS-DMA kernels, for n-major weights, cin % 64 == 0, cout % 64 == 0 and n > 0 only:
+//   BIAS_RELU (plain GEMM, its own thresholds): 256 x 256 two-phase if cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128,
+//      256 x 128 two-phase if cout % 128 == 0 and ceil(n / 256) * cout / 128 >= 128, else 128 x 64.
+//   2. cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128: with a table 256 x 256 eight-phase (192 x 256 when R192(cout / 256));
+//      without one the two-phase 256 x 256, which has no addend, f32-output or BatchNorm-backward epilogue (ADD, F32*, BN_BWD: none).
+//   3. a table, cout % 128 == 0, kvol * cin / 64 >= GLDS8N_MIN_KTILES k-tiles, ceil(n / 256) * cout / 128 >= GLDS8N_MIN_WGS:
+//      256 x 128 eight-phase (192 x 128 when R192(cout / 128)).
+//   4. cout % 128 == 0: 128 x 128.
+//   5. 128 x 64.
+//   F32 / F32_ADD take the tile's f32-output instantiation.  R192(c): a table, kvol > 1 and igemm_rows192(n, c).
+//   Statistics partials of the LDS-DMA kernels: one per row tile, ceil(n / rows).
+static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, bool nmajor, FwdEpi epi) {
+  FwdPlan p;
+  if (epi == EPI_PLAIN || epi == EPI_ADD || epi == EPI_STATS) {
+    p.direct = u3d_plan_igemm_direct(n_out_cap, cin, cout, kvol, has_nbr, nmajor, epi == EPI_STATS ? DIR_STATS : DIR_BF16);
+    if (p.direct.slot >= 0) {
+      p.partials = p.direct.partials;
+      return p;
+    }
+  }
+  if (!nmajor || cin <= 0 || cout <= 0 || cin % 64 != 0 || cout % 64 != 0 || n_out_cap <= 0) return p;
+  const long long tiles256 = u3d_cdiv(n_out_cap, 256);
+  const bool r192 = has_nbr && kvol > 1;
+  int g;
+  if (epi == EPI_BIAS_RELU)
+    g = (cout % 256 == 0 && tiles256 * (cout / 256) >= 128) ? G_256x256
+        : (cout % 128 == 0 && tiles256 * (cout / 128) >= 128) ? G_256x128 : G_128x64;
+  else if (cout % 256 == 0 && tiles256 * (cout / 256) >= 128)
+    g = !has_nbr ? G_256x256 : (r192 && igemm_rows192(n_out_cap, cout / 256)) ? G8_192x256 : G8_256x256;
+  else if (has_nbr && cout % 128 == 0 && kvol * (cin / 64) >= GLDS8N_MIN_KTILES && tiles256 * (cout / 128) >= GLDS8N_MIN_WGS)
+    g = (r192 && igemm_rows192(n_out_cap, cout / 128)) ? G8_192x128 : G8_256x128;
+  else
+    g = cout % 128 == 0 ? G_128x128 : G_128x64;
+  const GldsKernel& k = GLDS_KERNELS[g];
+  const bool f32 = epi == EPI_F32 || epi == EPI_F32_ADD;
+  if (!k.addend && (epi == EPI_ADD || epi == EPI_F32_ADD || epi == EPI_BN_BWD)) return p;
+  p.fn = f32 ? k.f32 : k.bf16;
+  if (!p.fn) return p;
+  p.glds = g;
+  p.rows = k.rows;
+  p.grid = dim3(u3d_cdiv(n_out_cap, k.rows), u3d_cdiv(cout, k.cols));
+  p.threads = k.threads;
+  p.lds = k.lds;
+  p.partials = (int)p.grid.x;
+  return p;
+}
+
+// bias: f32 bias (relu & 1: ReLU after it), or with relu & 2 the addend (bf16, or f32 for the f32-output kernels; the direct-operand
+// kernels take a bf16 addend here); stats / bn: the statistics epilogue of the plan's epilogue kind
+static int fwd_launch(const FwdPlan& p, const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
+                      int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const void* bias = nullptr, int relu = 0,
+                      double* stats = nullptr, const BnEpi bn = BnEpi{}) {
+  if (p.direct.slot >= 0) return u3d_launch_igemm_direct(p.direct, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, s, bias, stats);
+  static unsigned long long lds_mask[G_COUNT][2] = {};          // U3D_ALLOW_LDS's per-device mask, one per kernel
+  if (p.lds > 64 * 1024) u3d_allow_lds_impl((const void*)p.fn, (int)p.lds, &lds_mask[p.glds][p.fn == GLDS_KERNELS[p.glds].f32]);
+  hipLaunchKernelGGL(p.fn, p.grid, dim3(p.threads), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap, cin,
+                     cout, kvol, (const float*)bias, relu, stats, bn);
+  return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
+}
 
 // Dense layer on rows: out[M,N] = act(x[M,K] @ W[N,K]^T + bias) — nn.Linear layout, bf16 in/out, f32 accumulate/bias.
 // Small M (decoder: B*900 rows): 128x64 tiles so that a few hundred workgroups exist.
@@ -1337,67 +1377,31 @@ extern "C" int32_t u3d_linear_bf16(const void* x, const void* w, const float* bi
   if (k % 64 != 0 || n % 64 != 0) return U3D_ERR_UNSUPPORTED;
   if (m_cap <= 0) return U3D_OK;
   // nn.Linear's [N, K] weight IS the n-major layout of the LDS-DMA kernels
-  const long long wg256 = (long long)u3d_cdiv(m_cap, 256) * (n / 256);
-  if (n % 256 == 0 && wg256 >= 128) return launch_igemm_glds<GLDS256_CFG>(x, w, nullptr, 0, out, m_dev, m_cap, k, n, 1, s, bias, relu);
-  if (n % 128 == 0 && (long long)u3d_cdiv(m_cap, 256) * (n / 128) >= 128)
-    return launch_igemm_glds<4, 2, 4, 4>(x, w, nullptr, 0, out, m_dev, m_cap, k, n, 1, s, bias, relu);
-  return launch_igemm_glds<4, 1, 2, 4>(x, w, nullptr, 0, out, m_dev, m_cap, k, n, 1, s, bias, relu ? 1 : 0);
+  const FwdPlan p = fwd_plan(m_cap, k, n, 1, false, true, EPI_BIAS_RELU);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, x, w, nullptr, 0, out, m_dev, m_cap, k, n, 1, s, bias, relu ? 1 : 0);
 }
 
-// row-tile height of the n-major (LDS-DMA) kernel u3d_igemm_fwd_stats_bf16 would launch for this shape; 0 = not served by it
-extern "C" int32_t u3d_igemm_fwd_stats_tile_rows(int32_t n_out_cap, int32_t cin, int32_t cout) {
-  if (!IGEMM_GLDS || cin % 64 != 0 || cout % 64 != 0 || n_out_cap <= 0) return 0;
-  const long long wg256 = (long long)u3d_cdiv(n_out_cap, 256) * (cout / 256 > 0 ? cout / 256 : 1);
-  if (cout % 256 == 0 && wg256 >= 128) return 256;
-  return 128;
+// The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (fwd_plan, STATS).  u3d_igemm_fwd_split_bf16 and
+// u3d_igemm_dgrad_bnstats_bf16 write the same one wherever they serve the shape: there the plan never picks a direct-operand kernel.
+extern "C" int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
+                                              int32_t* rows_per_partial) {
+  U3D_REQUIRE(partials && rows_per_partial, U3D_ERR_ARG);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, has_nbr != 0, true, EPI_STATS);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  *partials = p.partials;
+  *rows_per_partial = p.rows;
+  return U3D_OK;
 }
-// forward with n-major weights w[kappa][cout][cin] that also leaves the per-row-tile BatchNorm statistics of the (bf16-rounded)
-// output: stats f64 [ceil(n_out_cap / tile_rows)][2][cout] = (sum, sum of squares) per tile and column
-// number of statistics partials u3d_igemm_fwd_stats_bf16 writes for this shape (0: not served).  LDS-DMA kernels: one per row tile
-// (ceil(n_out_cap / u3d_igemm_fwd_stats_tile_rows)); direct-operand kernels of the narrow 27-offset levels: one per WAVE of their
-// persistent grid - u3d_igemm_fwd_stats_tile_rows is 0 there and u3d_bn_finalize_partials takes rows_per_block = 0 ("all of them")
-// rows per statistics partial of u3d_igemm_fwd_stats_bf16 for a conv WITH a neighbour table and `kvol` offsets (what
-// u3d_bn_finalize_partials takes as rows_per_block): the LDS-DMA kernels' row-tile height - which depends on kvol where the
-// 256 x 128 eight-phase kernel serves long reductions -, 0 for the per-wave partials of the direct-operand kernels / unserved shapes
-extern "C" int32_t u3d_igemm_fwd_stats_rows(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol) {
-  // the dispatch order of u3d_igemm_fwd_stats_bf16 / _dgrad_bnstats: 256-column tiles first, then the 256 x 128 eight-phase kernel
-  const int32_t* some = (const int32_t*)16;      // "there is a neighbour table"
-  const int tr = u3d_igemm_fwd_stats_tile_rows(n_out_cap, cin, cout);
-  if (tr == 256) return (IGEMM_GLDS8 && igemm_rows192(some, n_out_cap, cout / 256, kvol)) ? 192 : 256;      // (launch_igemm_glds's choice)
-  if (igemm_glds8n_shape(some, n_out_cap, cin, cout, kvol)) return igemm_rows192(some, n_out_cap, cout / 128, kvol) ? 192 : 256;
-  return tr;
-}
-#ifndef DIRECT_STATS
-#define DIRECT_STATS 1
-#endif
-extern "C" int32_t u3d_igemm_fwd_stats_blocks(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol) {
-#if IGEMM_DIRECT && DIRECT_STATS
-  if (n_out_cap > 0) {
-    int nb = 0;
-    if (u3d_launch_igemm_direct(nullptr, nullptr, (const int32_t*)16, 1, nullptr, nullptr, n_out_cap, cin, cout, kvol, 1, nullptr, nullptr, nullptr, &nb) == U3D_OK)
-      return nb;
-  }
-#endif
-  const int tr = u3d_igemm_fwd_stats_rows(n_out_cap, cin, cout, kvol);
-  return tr ? u3d_cdiv(n_out_cap, tr) : 0;
-}
+// forward with n-major weights w[kappa][cout][cin] that also leaves the BatchNorm statistics of the (bf16-rounded) output:
+// stats f64 [partials][2][cout] = (sum, sum of squares) per row tile (or per wave) and column, u3d_igemm_fwd_stats_layout
 extern "C" int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
                                             const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                             double* stats, u3d_stream s) {
   U3D_REQUIRE(in && w && out && n_out_dev && stats && (nbr || kvol == 1), U3D_ERR_ARG);
-#if IGEMM_DIRECT && DIRECT_STATS
-  {
-    const int rc = u3d_launch_igemm_direct(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, 1, s, nullptr, stats);
-    if (rc != U3D_ERR_UNSUPPORTED) return rc;
-  }
-#endif
-  const int tr = u3d_igemm_fwd_stats_tile_rows(n_out_cap, cin, cout);
-  if (tr == 0) return U3D_ERR_UNSUPPORTED;
-  if (tr == 256) return launch_igemm_glds<GLDS256_CFG>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
-  if (igemm_glds8n_shape(nbr, n_out_cap, cin, cout, kvol))          // (256-row tiles too: u3d_igemm_fwd_stats_rows)
-    return launch_igemm_glds8n(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
-  if (cout % 128 == 0) return launch_igemm_glds<2, 2, 4, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
-  return launch_igemm_glds<4, 1, 2, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, true, EPI_STATS);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1408,20 +1412,16 @@ extern "C" int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const
 // the three products are three sets of "offsets" - the caller stacks the planes as rows [hi ; lo] of one matrix, triples the
 // neighbour table (nbr, nbr, nbr + plane stride) and the weights (wh, wl, wh) - and this entry only picks the f32-output instantiations.
 //   in   bf16 [2 * n_in_cap][cin] (u3d_split_rows_f32), w bf16 [kvol3][cout][cin] (n-major, kvol3 = 3 * offsets), nbr int32 [kvol3][ld],
-//   out  f32 [n_out_cap][cout]; stats (optional) f64 [ceil(n_out_cap / u3d_igemm_fwd_stats_rows(.., kvol3))][2][cout] of the f32 output
+//   out  f32 [n_out_cap][cout]; stats (optional) f64 [partials][2][cout] of the f32 output (u3d_igemm_fwd_stats_layout(.., kvol3, 1, ..))
 extern "C" int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, float* out,
                                             const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol3,
                                             double* stats, const float* addend, u3d_stream s) {
   U3D_REQUIRE(in && w && out && n_out_dev && nbr && kvol3 > 0, U3D_ERR_ARG);
-  if (!IGEMM_GLDS || cin % 64 != 0 || cout % 64 != 0) return U3D_ERR_UNSUPPORTED;
+  if (cin % 64 != 0 || cout % 64 != 0) return U3D_ERR_UNSUPPORTED;
   if (n_out_cap <= 0) return U3D_OK;
-  const int tr = u3d_igemm_fwd_stats_tile_rows(n_out_cap, cin, cout);
-  if (tr == 256 && addend && !(IGEMM_GLDS8 && nbr)) return U3D_ERR_UNSUPPORTED;      // (the two-phase 256 x 256 kernel has no addend epilogue)
-  if (tr == 256) return launch_igemm_glds<GLDS256_CFG>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats, BnEpi{}, true);
-  if (igemm_glds8n_shape(nbr, n_out_cap, cin, cout, kvol3))
-    return launch_igemm_glds8n(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats, BnEpi{}, true);
-  if (cout % 128 == 0) return launch_igemm_glds<2, 2, 4, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats, BnEpi{}, true);
-  return launch_igemm_glds<4, 1, 2, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats, BnEpi{}, true);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol3, true, true, addend ? EPI_F32_ADD : EPI_F32);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats);
 }
 
 // hi / lo bf16 planes of an f32 row matrix: dst[r] = bf16(x[r]), dst[n_cap + r] = bf16(x[r] - dst[r]) (round to nearest even both)
@@ -1683,69 +1683,32 @@ __global__ __launch_bounds__(1024) void k_conv_in_reduce(const float* __restrict
 static inline bool convin_shape(int cin, int cout, int kvol) { return cin == CONVIN_CIN && cout == CONVIN_COUT && kvol >= 1 && kvol <= CONVIN_MAXK; }
 
 // out = conv(in) + addend (bf16, out's shape) in one pass - the input gradient of a residual block's first conv with the residual
-// branch's gradient summed in by the epilogue.  Shapes: the direct-operand kernels (16/32/64 channels, 27 offsets) and the n-major
-// LDS-DMA kernels (transpose_w != 0, cin % 64 == 0; 256 x 256 tiles: the eight-phase kernel only); anything else: U3D_ERR_UNSUPPORTED (the caller adds).
+// branch's gradient summed in by the epilogue.  Shapes without that epilogue (fwd_plan, ADD): U3D_ERR_UNSUPPORTED (the caller adds).
 extern "C" int32_t u3d_igemm_fwd_add_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
                                           const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                           int32_t transpose_w, u3d_stream s) {
   U3D_REQUIRE(in && w && out && addend && n_out_dev && nbr, U3D_ERR_ARG);
   if (n_out_cap <= 0) return U3D_OK;
-#if IGEMM_DIRECT
-  {
-    const int rc = u3d_launch_igemm_direct(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, transpose_w, s, addend);
-    if (rc != U3D_ERR_UNSUPPORTED) return rc;
-  }
-#endif
-#if IGEMM_GLDS
-  if (transpose_w && cin % 64 == 0 && cout % 64 == 0) {
-    const long long wg256 = (long long)u3d_cdiv(n_out_cap, 256) * (cout / 256 > 0 ? cout / 256 : 1);
-    if (cout % 256 == 0 && wg256 >= 128) {                                            // 256 x 256: the eight-phase kernel's epilogue takes the addend
-      if (!(IGEMM_GLDS8 && nbr)) return U3D_ERR_UNSUPPORTED;
-      return launch_igemm_glds<GLDS256_CFG>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, (const float*)addend, 2);
-    }
-    if (igemm_glds8n_shape(nbr, n_out_cap, cin, cout, kvol))
-      return launch_igemm_glds8n(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, (const float*)addend, 2);
-    if (cout % 128 == 0) return launch_igemm_glds<2, 2, 4, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, (const float*)addend, 2);
-    return launch_igemm_glds<4, 1, 2, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, (const float*)addend, 2);
-  }
-#endif
-  return U3D_ERR_UNSUPPORTED;
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, true, transpose_w != 0, EPI_ADD);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, 2);
 }
 
 // Input gradient (n-major weights [K][Cin][Cout] as the dgrad passes them) + optional addend + the BatchNorm-BACKWARD statistics of the
-// layer that produced the conv's input, per row tile: stats f64 [ceil(n_out_cap / T)][2][cout] = (sum g, sum g * xhat), T =
-// u3d_igemm_fwd_stats_rows(n_out_cap, cin, cout, kvol) (the dispatch below is u3d_igemm_fwd_stats_bf16's).  LDS-DMA kernels with the
-// addend epilogue only: U3D_ERR_UNSUPPORTED for the direct-operand shapes and the two-phase 256 x 256 kernel (the caller then runs
-// u3d_igemm_fwd_add_bf16 / u3d_igemm_fwd_bf16 and u3d_bn_bwd_stats).
+// layer that produced the conv's input, per row tile: stats f64 [partials][2][cout] = (sum g, sum g * xhat), the layout
+// u3d_igemm_fwd_stats_layout reports.  LDS-DMA kernels with the addend epilogue only (fwd_plan, BN_BWD): U3D_ERR_UNSUPPORTED otherwise
+// (the caller then runs u3d_igemm_fwd_add_bf16 / u3d_igemm_fwd_bf16 and u3d_bn_bwd_stats).
 extern "C" int32_t u3d_igemm_dgrad_bnstats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
                                                 const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                                 const u3d_bn_epi* bn, double* stats, u3d_stream s) {
   U3D_REQUIRE(in && w && out && n_out_dev && nbr && bn && bn->x && bn->mean && bn->invstd && stats, U3D_ERR_ARG);
   U3D_REQUIRE(!bn->relu || bn->y || (bn->gamma && bn->beta), U3D_ERR_ARG);
-#if IGEMM_GLDS
-  if (n_out_cap <= 0 || cin % 64 != 0 || cout % 64 != 0) return U3D_ERR_UNSUPPORTED;
-#if IGEMM_DIRECT
-  if (u3d_launch_igemm_direct(nullptr, nullptr, (const int32_t*)16, 1, nullptr, nullptr, n_out_cap, cin, cout, kvol, 1, nullptr, nullptr, nullptr, nullptr)
-      != U3D_ERR_UNSUPPORTED) return U3D_ERR_UNSUPPORTED;                 // a direct-operand shape: its partial layout is per wave
-#endif
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, true, true, EPI_BN_BWD);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
   BnEpi e;
   e.x = (const u16*)bn->x; e.y = (const u16*)bn->y; e.mean = bn->mean; e.invstd = bn->invstd; e.gamma = bn->gamma; e.beta = bn->beta;
   e.relu = bn->relu;
-  const float* add = (const float*)addend;
-  const int fl = addend ? 2 : 0;
-  const int tr = u3d_igemm_fwd_stats_tile_rows(n_out_cap, cin, cout);
-  if (tr == 0) return U3D_ERR_UNSUPPORTED;
-  if (tr == 256) {
-    if (!(IGEMM_GLDS8 && nbr)) return U3D_ERR_UNSUPPORTED;
-    return launch_igemm_glds<GLDS256_CFG>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, add, fl, stats, e);
-  }
-  if (igemm_glds8n_shape(nbr, n_out_cap, cin, cout, kvol))
-    return launch_igemm_glds8n(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, add, fl, stats, e);
-  if (cout % 128 == 0) return launch_igemm_glds<2, 2, 4, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, add, fl, stats, e);
-  return launch_igemm_glds<4, 1, 2, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, add, fl, stats, e);
-#else
-  return U3D_ERR_UNSUPPORTED;
-#endif
+  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, addend ? 2 : 0, stats, e);
 }
 
 extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
@@ -1758,18 +1721,14 @@ extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32
                        n_out_cap, kvol);
     return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
   }
-#if IGEMM_DIRECT
-  // 16/32/64-channel sparse levels with 27 offsets (not 64 -> 64): activations gathered straight into the MFMA operand registers,
-  // all weights LDS-resident, persistent barrier-free waves (igemm_direct.hip)
-  {
-    const int rc = u3d_launch_igemm_direct(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, transpose_w, s);
-    if (rc != U3D_ERR_UNSUPPORTED) return rc;
-  }
-#endif
-#if IGEMM_SMALL_C
-  // 16/32-channel sparse levels (and the 32<->64 transitions): 256-row tiles, one MFMA k-step per stage (BK = 32), the same
-  // register-staged, software-pipelined loop as the wide layers - the first-generation kernel it replaces does
-  // "indices -> barrier -> gather -> barrier -> MFMA -> barrier" per offset with nothing in flight across the barriers
+  // the narrow sparse levels' direct-operand kernels (activations gathered straight into the MFMA operand registers, all weights
+  // LDS-resident, persistent barrier-free waves: igemm_direct.hip) and the n-major LDS-DMA kernels
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, transpose_w != 0, EPI_PLAIN);
+  if (p.served()) return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
+  // what the plan does not serve runs on the register-staged kernels: 16/32-channel sparse levels (and the 32<->64 transitions):
+  // 256-row tiles, one MFMA k-step per stage (BK = 32), the same register-staged, software-pipelined loop as the wide layers - the
+  // first-generation kernel it replaces does "indices -> barrier -> gather -> barrier -> MFMA -> barrier" per offset with nothing in
+  // flight across the barriers
   if (n_out_cap > 0 && cin % 16 == 0 && cout % 16 == 0 && cin <= 64 && cout <= 64 && (cin < 64 || cout < 64)) {
 #define IG_SMALL(WNV, BKV)                                                                                                                          \
     return transpose_w ? launch_igemm_fwd<4, 1, IGEMM_SMALL_WM, WNV, false, BKV, IGEMM_SMALL_PF>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s)   \
@@ -1782,7 +1741,6 @@ extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32
     }
 #undef IG_SMALL
   }
-#endif
   if (cin % 64 != 0 || cout % 8 != 0 || cout < 64) return U3D_ERR_UNSUPPORTED;
   if (n_out_cap <= 0) return U3D_OK;
 #define IG_CASE(A, B, C, D)                                                                                                  \
@@ -1792,15 +1750,6 @@ extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32
   //  the smaller tile outweighs the better CU fill; not dispatched)
   // few row tiles (the stride-4 branch of SECOND3D: 12000 rows): 256 x 256 tiles leave most CUs idle -> narrower tiles
   const long long wg256 = (long long)u3d_cdiv(n_out_cap, 256) * (cout / 256 > 0 ? cout / 256 : 1);
-#if IGEMM_GLDS
-  if (transpose_w) {                                                // n-major weights: LDS-DMA staged kernels
-    if (cout % 256 == 0 && wg256 >= 128) return launch_igemm_glds<GLDS256_CFG>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-    // 128 x 128 (4 waves, 64 KiB LDS, two workgroups per CU out of phase): +3...6 % over 256 x 128 on the 128- and 512-channel layers
-    if (igemm_glds8n_shape(nbr, n_out_cap, cin, cout, kvol)) return launch_igemm_glds8n(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-    if (cout % 128 == 0) return launch_igemm_glds<2, 2, 4, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-    if (cout % 64 == 0) return launch_igemm_glds<4, 1, 2, 4>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-  }
-#endif
   if (cout % 256 == 0 && wg256 < 128) { IG_CASE(4, 2, 4, 4) }       // measured: 94 workgroups (N=12000, 512 ch) 0.136 -> 0.100 ms;
                                                                     // 188 workgroups (N=48000, 256 ch) stay faster on 256 x 256
   if (cout >= 256 && cout % 256 == 0) { IG_CASE(2, 4, 8, 4) }       // 256 x 256
@@ -2225,9 +2174,6 @@ __device__ __forceinline__ void igemm_wgrad_glds_body(const u16* __restrict__ in
 // pieces gather the SAME 64 rows: two index registers per lane.  Needs a neighbour table (the batched linear-layer form stays on
 // igemm_wgrad_glds_body).
 // ---------------------------------------------------------------------------------------------
-#ifndef IGEMM_WGRAD_GLDS8
-#define IGEMM_WGRAD_GLDS8 1
-#endif
 __device__ __forceinline__ void igemm_wgrad_glds8_body(const u16* __restrict__ in, const u16* __restrict__ dout,
                                                        const int* __restrict__ nbr, int ld, float* __restrict__ partial,
                                                        const int* __restrict__ n_out_dev, int n_out_cap, int cin, int cout, int kvol,
@@ -2568,18 +2514,14 @@ static WgPlan wgrad_plan(int n_out_cap, int cin, int cout, int kvol) {
   return p;
 }
 
-#ifndef IGEMM_WGRAD_NARROW
-#define IGEMM_WGRAD_NARROW 1   /* 16/32-channel 27-offset weight gradients on wgrad_narrow.hip (0: the tiled kernels below) */
-#endif
+// 16/32-channel 27-offset weight gradients: wgrad_narrow.hip
 bool u3d_wgrad_narrow_shape(int cin, int cout, int kvol);
 int64_t u3d_wgrad_narrow_workspace(int n_out_cap, int cin, int cout);
 int u3d_launch_wgrad_narrow(const void* in, const void* dout, const int32_t* nbr, int ld, float* dw, const int32_t* n_out_dev, int n_out_cap,
                             int cin, int cout, int kvol, int out_oik, void* workspace, int64_t workspace_bytes, hipStream_t s);
 
 extern "C" int64_t u3d_igemm_wgrad_bf16_workspace(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol) {
-#if IGEMM_WGRAD_NARROW
   if (u3d_wgrad_narrow_shape(cin, cout, kvol)) return u3d_wgrad_narrow_workspace(n_out_cap, cin, cout);
-#endif
   if (convin_shape(cin, cout, kvol)) return (int64_t)u3d_cdiv(n_out_cap > 0 ? n_out_cap : 1, CONVIN_WG_ROWS) * kvol * cin * cout * 4;
   WgPlan p = wgrad_plan(n_out_cap, cin, cout, kvol);
   return (int64_t)p.nsplit * kvol * cin * cout * 4;
@@ -2598,20 +2540,17 @@ static int launch_igemm_wgrad(const void* in, const void* dout, const int32_t* n
   return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
 }
 
-#ifndef IGEMM_WGRAD_GLDS
-#define IGEMM_WGRAD_GLDS 1
-#endif
 #ifndef IGEMM_WGRAD_GLDS_MIN_TILE
 #define IGEMM_WGRAD_GLDS_MIN_TILE 64
 #endif
 static int launch_igemm_wgrad_glds(int tile, const void* in, const void* dout, const int32_t* nbr, int ld, float* partial,
                                    const int32_t* n_out_dev, int n_out_cap, int cin, int cout, int kvol, const WgPlan& p, hipStream_t s) {
-  wgrad_glds_kernel_t kern = tile == 256 ? ((IGEMM_WGRAD_GLDS8 && nbr) ? k_igemm_wgrad_glds8_256 : k_igemm_wgrad_glds_256)
+  wgrad_glds_kernel_t kern = tile == 256 ? (nbr ? k_igemm_wgrad_glds8_256 : k_igemm_wgrad_glds_256)
                                          : (tile == 128 ? k_igemm_wgrad_glds_128 : k_igemm_wgrad_glds_64);
   const int nthreads = tile == 256 ? 512 : 256;
   const size_t lds = 2 * (size_t)(64 * tile + 64 * tile) * 2;
   if (lds > 64 * 1024) {                       // one per-device mask per kernel
-    if (tile == 256 && IGEMM_WGRAD_GLDS8 && nbr) U3D_ALLOW_LDS(k_igemm_wgrad_glds8_256, lds);
+    if (tile == 256 && nbr) U3D_ALLOW_LDS(k_igemm_wgrad_glds8_256, lds);
     else if (tile == 256) U3D_ALLOW_LDS(k_igemm_wgrad_glds_256, lds);
     else if (tile == 128) U3D_ALLOW_LDS(k_igemm_wgrad_glds_128, lds);
     else U3D_ALLOW_LDS(k_igemm_wgrad_glds_64, lds);
@@ -2637,22 +2576,17 @@ extern "C" int32_t u3d_igemm_wgrad_bf16(const void* in, const void* dout, const 
     return U3D_OK;
   }
   if (cin % 16 != 0 || cout % 16 != 0) return U3D_ERR_UNSUPPORTED;
-#if IGEMM_WGRAD_NARROW
   if (nbr && u3d_wgrad_narrow_shape(cin, cout, kvol)) {
     if (n_out_cap <= 0) { hipMemsetAsync(dw, 0, sizeof(float) * kvol * cin * cout, s); return U3D_OK; }
     return u3d_launch_wgrad_narrow(in, dout, nbr, ld, dw, n_out_dev, n_out_cap, cin, cout, kvol, out_layout, workspace, workspace_bytes, s);
   }
-#endif
   WgPlan p = wgrad_plan(n_out_cap, cin, cout, kvol);
   long long n = (long long)kvol * cin * cout;
   U3D_REQUIRE(workspace_bytes >= (int64_t)p.nsplit * n * 4, U3D_ERR_WORKSPACE);
   int rc;
-#if IGEMM_WGRAD_GLDS
   if (p.tile >= IGEMM_WGRAD_GLDS_MIN_TILE && cin % p.tile == 0 && cout % p.tile == 0)
     rc = launch_igemm_wgrad_glds(p.tile, in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);
-  else
-#endif
-  if (p.tile == 256) rc = launch_igemm_wgrad<2, 4, 8, 4>(in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);
+  else if (p.tile == 256) rc = launch_igemm_wgrad<2, 4, 8, 4>(in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);
   else if (p.tile == 128) rc = launch_igemm_wgrad<2, 2, 4, 4>(in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);
   else if (p.tile == 64) rc = launch_igemm_wgrad<2, 2, 2, 2>(in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);
   else if (p.tile == 32) rc = launch_igemm_wgrad<2, 2, 1, 1>(in, dout, nbr, ld, (float*)workspace, n_out_dev, n_out_cap, cin, cout, kvol, p, s);

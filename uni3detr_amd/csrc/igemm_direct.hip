@@ -17,7 +17,7 @@
 //     the lane that needs them with ds_bpermute (LDS crossbar, no LDS memory); the slot of an index is reloaded for the next tile
 //     right after its last use, so the gather chain index -> row never waits on vmcnt's in-order retirement;
 //   * operands swapped (D^T = W X^T): a lane ends up with four consecutive output channels of one row -> 8-byte stores.
-#include "common.h"
+#include "igemm_direct.h"
 
 typedef unsigned short u16;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -43,11 +43,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #endif
 #ifndef DIR_WAVES_PER_SIMD
 #define DIR_WAVES_PER_SIMD 2
-#endif
-#ifndef DIR_SPLIT_64
-#define DIR_SPLIT_64 0    /* 1: 64 -> 64 layers as two 64 -> 32 launches.  Measured SLOWER on the 207 k-row level (17.5 of 27 neighbours
-                             exist there: 2 x 78 us against 73 us on the LDS-DMA tiled kernel - each half gathers all 64 input channels
-                             again and the level is bound by real L2 -> L1 bytes, not by empty slots) */
 #endif
 #ifndef DIR_SCHED_BARRIER
 #define DIR_SCHED_BARRIER 1 /* pin the step's three phases (LDS requests | MFMAs | gathers): hipcc otherwise sinks the requests to their uses */
@@ -76,7 +71,8 @@ __device__ __forceinline__ void igemm_direct_body(const u16* __restrict__ in, co
   // and sums of squares over the rows this wave wrote (f32 per lane over its ~20 rows, 16 lanes by shuffles at the end, f64 from
   // there on) - u3d_bn_finalize_partials with rows_per_block = 0 adds them up; waves without tiles write zeros.
   // cout = channels of a row of `out` (and of the weight tensor); this launch computes the COUT = 16 * WN columns from co0 on
-  // (a 64 -> 64 layer is two launches of the 64 -> 32 kernel: the weights of 27 x 64 x 64 do not fit LDS, those of one half do)
+  // (64 -> 64 is not served: the weights of 27 x 64 x 64 do not fit LDS, and two launches over 32 columns each measured slower
+  // than the LDS-DMA tiled kernel on the 207 k-row level - 2 x 78 us against 73 us: each half gathers all 64 input channels again)
   static_assert(DIR_K % P == 0, "operand register sets are indexed statically");
   constexpr int NT = NW * 64;
   constexpr int KP = KS * 32;                 // padded reduction length
@@ -371,55 +367,30 @@ U3D_DIRECT_KERNEL_F(k_igemm_direct_64x32_nf, 2, 2, DIR_NW_B, DIR_P2)
 
 typedef void (*direct_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const u16*, double*);
 
-// 0 = launched, U3D_ERR_UNSUPPORTED = shape not served here (caller falls through to the tiled kernels)
-int u3d_launch_igemm_direct(const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev, int n_out_cap,
-                            int cin, int cout, int kvol, int transpose_w, hipStream_t s, const void* addend, double* stats,
-                            int* stats_blocks, int f32acc) {
-  // f32acc: 0 = bf16 output (+ bf16 addend); 1 / 2 = F32 output of an n-major launch, written (1) or accumulated into (2)
-  // stats_blocks != nullptr: a QUERY - nothing is launched, *stats_blocks = number of per-wave statistics partials a launch writes
-  if (kvol != DIR_K || !nbr || (cin != 16 && cin != 32 && cin != 64) || (cout != 16 && cout != 32 && cout != 64))
-    return U3D_ERR_UNSUPPORTED;
-#if !DIR_SPLIT_64
-  if (cin == 64 && cout == 64) return U3D_ERR_UNSUPPORTED;
-#endif
-  const int ks = cin > 32 ? 2 : 1, kp = ks * 32;
-  const int cout_total = cout;
-  const int halves = (cin == 64 && cout == 64) ? 2 : 1;          // 64 -> 64: two launches over 32 output columns each
-  if (halves == 2) cout = 32;
-  const size_t lds = (size_t)DIR_K * cout * (kp + 8) * 2;
-  if (lds > 160 * 1024) return U3D_ERR_UNSUPPORTED;
-  direct_kernel_t kern = nullptr;
-  int nw = 4;
-#define DIR_PICK(KSV, CO, NAMEK, NAMEN, NWV)                              \
-  if (ks == KSV && cout == CO) {                                          \
-    kern = transpose_w ? NAMEN : NAMEK;                                   \
-    nw = NWV;                                                             \
-    if (transpose_w) U3D_ALLOW_LDS(NAMEN, lds); else U3D_ALLOW_LDS(NAMEK, lds); \
-  }
-  DIR_PICK(1, 16, k_igemm_direct_32x16_k, k_igemm_direct_32x16_n, DIR_NW_A)
-  DIR_PICK(1, 32, k_igemm_direct_32x32_k, k_igemm_direct_32x32_n, DIR_NW_A)
-  DIR_PICK(1, 64, k_igemm_direct_32x64_k, k_igemm_direct_32x64_n, DIR_NW_B)
-  DIR_PICK(2, 16, k_igemm_direct_64x16_k, k_igemm_direct_64x16_n, DIR_NW_A)
-  DIR_PICK(2, 32, k_igemm_direct_64x32_k, k_igemm_direct_64x32_n, DIR_NW_B)
-#undef DIR_PICK
-  if (!kern) return U3D_ERR_UNSUPPORTED;
-  if (f32acc) {
-    if (!transpose_w || stats || stats_blocks || halves == 2) return U3D_ERR_UNSUPPORTED;
-    if (ks == 1 && cout == 16) { kern = k_igemm_direct_32x16_nf; U3D_ALLOW_LDS(k_igemm_direct_32x16_nf, lds); }
-    if (ks == 1 && cout == 32) { kern = k_igemm_direct_32x32_nf; U3D_ALLOW_LDS(k_igemm_direct_32x32_nf, lds); }
-    if (ks == 1 && cout == 64) { kern = k_igemm_direct_32x64_nf; U3D_ALLOW_LDS(k_igemm_direct_32x64_nf, lds); }
-    if (ks == 2 && cout == 16) { kern = k_igemm_direct_64x16_nf; U3D_ALLOW_LDS(k_igemm_direct_64x16_nf, lds); }
-    if (ks == 2 && cout == 32) { kern = k_igemm_direct_64x32_nf; U3D_ALLOW_LDS(k_igemm_direct_64x32_nf, lds); }
-    addend = f32acc == 2 ? out : nullptr;                        // the F32ACC kernels read `addend` as the accumulate flag
-  }
-  if (stats || stats_blocks) {                                   // statistics epilogue: n-major kernels with <= 32 output columns
-    if (halves == 2 || !transpose_w || cout > 32) return U3D_ERR_UNSUPPORTED;
-    if (ks == 1 && cout == 16) { kern = k_igemm_direct_32x16_ns; U3D_ALLOW_LDS(k_igemm_direct_32x16_ns, lds); }
-    if (ks == 1 && cout == 32) { kern = k_igemm_direct_32x32_ns; U3D_ALLOW_LDS(k_igemm_direct_32x32_ns, lds); }
-    if (ks == 2 && cout == 16) { kern = k_igemm_direct_64x16_ns; U3D_ALLOW_LDS(k_igemm_direct_64x16_ns, lds); }
-    if (ks == 2 && cout == 32) { kern = k_igemm_direct_64x32_ns; U3D_ALLOW_LDS(k_igemm_direct_64x32_ns, lds); }
-  }
-  if (n_out_cap <= 0) { if (stats_blocks) *stats_blocks = 0; return U3D_OK; }
+// slot = shape * 4 + variant; waves per workgroup as instantiated above
+enum { DIR_V_K, DIR_V_N, DIR_V_NS, DIR_V_NF };           // k-major / n-major weights, n-major + statistics, n-major F32 output
+static const struct { int kp, cout, waves; direct_kernel_t k[4]; } DIR_SHAPES[] = {
+    {32, 16, DIR_NW_A, {k_igemm_direct_32x16_k, k_igemm_direct_32x16_n, k_igemm_direct_32x16_ns, k_igemm_direct_32x16_nf}},
+    {32, 32, DIR_NW_A, {k_igemm_direct_32x32_k, k_igemm_direct_32x32_n, k_igemm_direct_32x32_ns, k_igemm_direct_32x32_nf}},
+    {32, 64, DIR_NW_B, {k_igemm_direct_32x64_k, k_igemm_direct_32x64_n, nullptr, k_igemm_direct_32x64_nf}},
+    {64, 16, DIR_NW_A, {k_igemm_direct_64x16_k, k_igemm_direct_64x16_n, k_igemm_direct_64x16_ns, k_igemm_direct_64x16_nf}},
+    {64, 32, DIR_NW_B, {k_igemm_direct_64x32_k, k_igemm_direct_64x32_n, k_igemm_direct_64x32_ns, k_igemm_direct_64x32_nf}},
+};
+constexpr int DIR_NSHAPES = sizeof(DIR_SHAPES) / sizeof(DIR_SHAPES[0]);
+
+DirectPlan u3d_plan_igemm_direct(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, bool nmajor, DirEpi epi) {
+  DirectPlan p;
+  if (kvol != DIR_K || !has_nbr || (cin != 16 && cin != 32 && cin != 64)) return p;
+  const int kp = cin > 32 ? 64 : 32;
+  const int variant = epi == DIR_STATS ? DIR_V_NS : epi == DIR_F32 ? DIR_V_NF : nmajor ? DIR_V_N : DIR_V_K;
+  if (epi != DIR_BF16 && !nmajor) return p;
+  int shape = 0;
+  while (shape < DIR_NSHAPES && !(DIR_SHAPES[shape].kp == kp && DIR_SHAPES[shape].cout == cout)) ++shape;
+  if (shape == DIR_NSHAPES || !DIR_SHAPES[shape].k[variant]) return p;
+  p.slot = shape * 4 + variant;
+  p.waves = DIR_SHAPES[shape].waves;
+  p.lds = (size_t)DIR_K * cout * (kp + 8) * 2;
+  if (n_out_cap <= 0) return p;
   // persistent grid: as many workgroups as fit on the chip at once (LDS-limited), a multiple of 8 (one share per XCD), and no
   // more than there are tiles
   static int cu_count[64] = {0};                           // per device, read once (plain host query, legal during stream capture)
@@ -430,19 +401,26 @@ int u3d_launch_igemm_direct(const void* in, const void* w, const int32_t* nbr, i
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (dev >= 0 && dev < 64) cu_count[dev] = cus;
   }
-  int per_cu = (int)((160 * 1024) / lds);
-  const int by_waves = (4 * DIR_WAVES_PER_SIMD) / nw > 0 ? (4 * DIR_WAVES_PER_SIMD) / nw : 1;   // waves per SIMD: the register budget of these kernels
+  int per_cu = (int)((160 * 1024) / p.lds);
+  const int by_waves = (4 * DIR_WAVES_PER_SIMD) / p.waves > 0 ? (4 * DIR_WAVES_PER_SIMD) / p.waves : 1;   // waves per SIMD: the register budget of these kernels
   if (per_cu > by_waves) per_cu = by_waves;
   if (per_cu < 1) per_cu = 1;
   int grid = cus * per_cu;
-  const int ntiles = u3d_cdiv(n_out_cap, 64);
-  const int need = u3d_cdiv(ntiles, nw);
+  const int need = u3d_cdiv(u3d_cdiv(n_out_cap, 64), p.waves);
   if (grid > need) grid = need;
-  grid = (grid + 7) / 8 * 8;
-  if (stats_blocks) { *stats_blocks = grid * nw; return U3D_OK; }
-  for (int h = 0; h < halves; ++h)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap, cin,
-                       cout_total, h * 32, (const u16*)addend, stats);
+  p.grid = (grid + 7) / 8 * 8;
+  p.partials = p.grid * p.waves;
+  return p;
+}
+
+int u3d_launch_igemm_direct(const DirectPlan& p, const void* in, const void* w, const int32_t* nbr, int ld, void* out,
+                            const int32_t* n_out_dev, int n_out_cap, int cin, int cout, hipStream_t s, const void* addend, double* stats) {
+  if (p.grid == 0) return U3D_OK;
+  static unsigned long long lds_mask[DIR_NSHAPES * 4] = {0};   // U3D_ALLOW_LDS's per-device mask, one per kernel
+  const direct_kernel_t kern = DIR_SHAPES[p.slot / 4].k[p.slot % 4];
+  u3d_allow_lds_impl((const void*)kern, (int)p.lds, &lds_mask[p.slot]);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.waves * 64), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap,
+                     cin, cout, 0, (const u16*)addend, stats);
   return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
 }
 
@@ -458,9 +436,11 @@ extern "C" int32_t u3d_igemm_direct_split_bf16(const void* in, const void* w3, c
   const u16* lo = hi + (long long)n_in_cap * cin;
   const u16* wh = (const u16*)w3;
   const u16* wl = wh + (long long)DIR_K * cout * cin;
-  int rc = u3d_launch_igemm_direct(hi, wh, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, DIR_K, 1, (hipStream_t)s, nullptr, nullptr, nullptr, 1);
+  const DirectPlan p = u3d_plan_igemm_direct(n_out_cap, cin, cout, DIR_K, true, true, DIR_F32);
+  if (p.slot < 0) return U3D_ERR_UNSUPPORTED;
+  int rc = u3d_launch_igemm_direct(p, hi, wh, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, (hipStream_t)s, nullptr, nullptr);
   if (rc != U3D_OK) return rc;
-  rc = u3d_launch_igemm_direct(hi, wl, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, DIR_K, 1, (hipStream_t)s, nullptr, nullptr, nullptr, 2);
+  rc = u3d_launch_igemm_direct(p, hi, wl, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, (hipStream_t)s, out, nullptr);      // accumulate
   if (rc != U3D_OK) return rc;
-  return u3d_launch_igemm_direct(lo, wh, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, DIR_K, 1, (hipStream_t)s, nullptr, nullptr, nullptr, 2);
+  return u3d_launch_igemm_direct(p, lo, wh, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, (hipStream_t)s, out, nullptr);
 }

@@ -91,8 +91,7 @@ _SIGS = {
     "u3d_spconv_wgrad_workspace": (_L, [_I, _I, _I, _I]),
     "u3d_spconv_wgrad": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
     "u3d_igemm_fwd_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "u3d_igemm_fwd_stats_blocks": (_I, [_I, _I, _I, _I]),
-    "u3d_igemm_fwd_stats_rows": (_I, [_I, _I, _I, _I]),
+    "u3d_igemm_fwd_stats_layout": (_I, [_I, _I, _I, _I, _I, _P, _P]),
     "u3d_igemm_fwd_add_bf16": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "u3d_linear_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "u3d_igemm_wgrad_bf16_workspace": (_L, [_I, _I, _I, _I]),
@@ -104,7 +103,6 @@ _SIGS = {
     "u3d_bn_finalize": (_I, [_P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
     "u3d_bn_forward_stats": (_I, [_P, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _L, _P]),
     "u3d_bn_finalize_partials": (_I, [_P, _I, _I, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
-    "u3d_igemm_fwd_stats_tile_rows": (_I, [_I, _I, _I]),
     "u3d_igemm_fwd_stats_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "u3d_igemm_fwd_split_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "u3d_split_rows_f32": (_I, [_P, _P, _I, _I, _P, _P]),
@@ -470,19 +468,26 @@ CALL_KIND = "sparse"
 USE_IGEMM_V2 = True
 
 
+def fwd_stats_layout(n_out, cin, cout, kvol, has_nbr):
+    """(partials, rows per partial) of the statistics u3d_igemm_fwd_stats_bf16 writes for this shape, None when no kernel with a
+    statistics epilogue serves it.  Rows 0: one partial per wave of the direct-operand kernels, all of them count (rows_per_block = 0
+    downstream).  u3d_igemm_fwd_split_bf16 / u3d_igemm_dgrad_bnstats_bf16 write the same layout wherever they serve the shape."""
+    p, r = C.c_int32(0), C.c_int32(0)
+    if lib().u3d_igemm_fwd_stats_layout(n_out, cin, cout, kvol, int(has_nbr), C.byref(p), C.byref(r)) != 0:
+        return None
+    return p.value, r.value
+
+
 def spconv_fwd_stats(inp, w_nmajor, nbr, n_out_dev, n_out, cout):
     """Forward with n-major weights [K, Cout, Cin] + per-row-tile BatchNorm statistics of the output.
     -> (out [n_out, cout], stats f64 [nblocks, 2, cout], tile_rows) or None when the shape is not served by that kernel."""
     cin, kvol = inp.shape[1], w_nmajor.shape[0]
-    if inp.dtype != torch.bfloat16 or not USE_IGEMM_V2:
+    if inp.dtype != torch.bfloat16 or not USE_IGEMM_V2 or (nbr is None and kvol != 1):
         return None
-    nblocks = int(lib().u3d_igemm_fwd_stats_blocks(n_out, cin, cout, kvol)) if (nbr is not None or kvol == 1) else 0
-    if nblocks == 0:
+    layout = fwd_stats_layout(n_out, cin, cout, kvol, nbr is not None)
+    if layout is None or layout[0] == 0:
         return None
-    # 0 for the direct-operand kernels of the narrow levels: per-wave partials, all of them count (rows_per_block = 0 downstream)
-    tr = int(lib().u3d_igemm_fwd_stats_rows(n_out, cin, cout, kvol)) if nbr is not None else int(lib().u3d_igemm_fwd_stats_tile_rows(n_out, cin, cout))
-    if tr and nblocks != (n_out + tr - 1) // tr:
-        tr = 0
+    nblocks, tr = layout
     out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
     stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=inp.device)
     ld = nbr.shape[1] if nbr is not None else 0
@@ -518,11 +523,12 @@ def spconv_dgrad_bnstats(dout, w_nmajor, nbr, n_dev, n, cout, addend, epi):
     kvol, cin = w_nmajor.shape[0], dout.shape[1]
     if dout.dtype != torch.bfloat16 or not USE_IGEMM_V2 or nbr is None:
         return None
-    tr = int(lib().u3d_igemm_fwd_stats_rows(n, cin, cout, kvol))
-    if tr == 0:
+    layout = fwd_stats_layout(n, cin, cout, kvol, True)
+    if layout is None or layout[1] == 0:            # (per-wave partials: a direct-operand shape, which has no BatchNorm-backward epilogue)
         return None
+    nblocks, tr = layout
     out = torch.empty((n, cout), dtype=dout.dtype, device=dout.device)
-    stats = torch.empty(((n + tr - 1) // tr, 2, cout), dtype=torch.float64, device=dout.device)
+    stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=dout.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
     t = TIMER
     e0 = t.begin() if t is not None else None
@@ -744,6 +750,12 @@ def split_rows(x, n_dev, n_cap=None):
     return out
 
 
+def direct_serves(cin, cout, kvol):
+    """The shapes of the direct-operand kernels (igemm_direct.hip, u3d_plan_igemm_direct): 27 offsets, 16 / 32 / 64 channels, not
+    64 -> 64."""
+    return kvol == 27 and cin in (16, 32, 64) and cout in (16, 32, 64) and not (cin == 64 and cout == 64)
+
+
 def spconv_fwd_split_direct(xs, w3, nbr, n_out_dev, n_out, cout, tag="spconv_fwd"):
     """Split-bf16 product on a narrow 27-offset level (u3d_igemm_direct_split_bf16): xs bf16 planes [2 * n_in, cin], w3 bf16
     [81, cout, cin] = (wh, wl, wh), nbr the PLAIN table (or a RevNbr) -> f32 [n_out, cout]."""
@@ -927,9 +939,10 @@ def spconv_fwd_split(xs, w3, nbr3, n_out_dev, n_out, cout, want_stats=False, tag
     out = torch.empty((n_out, cout), dtype=torch.float32, device=xs.device)
     stats, tr = None, 0
     if want_stats:
-        tr = int(lib().u3d_igemm_fwd_stats_rows(n_out, cin, cout, kvol3))
-        if tr:
-            stats = torch.empty(((n_out + tr - 1) // tr, 2, cout), dtype=torch.float64, device=xs.device)
+        layout = fwd_stats_layout(n_out, cin, cout, kvol3, True)
+        if layout is not None and layout[1]:
+            stats = torch.empty((layout[0], 2, cout), dtype=torch.float64, device=xs.device)
+            tr = layout[1]
     t = TIMER
     e0 = t.begin() if t is not None else None
     assert addend is None or (addend.dtype == torch.float32 and tuple(addend.shape) == (n_out, cout))

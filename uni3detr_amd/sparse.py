@@ -238,7 +238,7 @@ def _split_serves(feats, cin, cout, kvol=None):
         return None
     if cin % 64 == 0 and cout % 64 == 0:
         return "wide"
-    if kvol == 27 and cin in (16, 32, 64) and cout in (16, 32, 64):
+    if nv.direct_serves(cin, cout, kvol):
         return "narrow"
     return None
 
@@ -277,8 +277,7 @@ class _SparseConv(torch.autograd.Function):
         # n-major forward weights: the LDS-DMA kernels (channels % 64) and the direct-operand kernel of the narrow 27-offset levels
         # (igemm_direct.hip stages [K][Cout][Cin] rows as they are; the k-major layout costs it a transposing prologue)
         kv = kio_shape[0] * kio_shape[1] * kio_shape[2]
-        narrow = kv == 27 and cin in (16, 32, 64) and cout in (16, 32, 64) and not (cin == 64 and cout == 64)
-        nmajor = NMAJOR_FWD and bf16 and ((cin % 64 == 0 and cout % 64 == 0) or narrow)
+        nmajor = NMAJOR_FWD and bf16 and ((cin % 64 == 0 and cout % 64 == 0) or nv.direct_serves(cin, cout, kv))
         split = _split_serves(feats, cin, cout, kv)
         if split == "narrow" and geom.nbr_fwd is None:
             split = None
