@@ -936,6 +936,25 @@ int32_t u3d_object_noise(float* points, const int32_t* scene_off, const int32_t*
                          float* boxes, const int32_t* gt_off, const int32_t* g_live, int32_t box_dim, int32_t num_try, const float* loc,
                          const float* rot, int32_t* first_ws, float* sel_ws, int32_t* chosen, u3d_stream s);
 
+/* Test-time augmentation: the multi-view box merge (ref: projects/mmdet3d_plugin/core/merge_all_augs.py:9-98, core/bbox/util.py:82-102)
+ * for all scenes at once: uni3detr_amd/csrc/tta.hip.  Candidates: boxes [n, box_dim] f32 bottom-centre (box_dim 7 or 9), scores [n]
+ * f32, labels [n] int32; det_off int32 [batch*views + 1] (device): view v = rows det_off[v] .. det_off[v+1]), scene s = views
+ * s*views .. s*views + views - 1; params f32 [batch*views][U3D_AUG_NPARAM]: every view's FORWARD parameters (rotation by angle and
+ * scale, then the flips - the inner test pipeline's order; translation ignored).  Per scene: every candidate is mapped back with
+ * exactly the arithmetic of u3d_boxes_augment under (fh, fv, -sin, cos, -angle, 1/scale, 0, 0, 0); candidates with a non-finite score
+ * or a label outside [0, num_classes) are dropped; per class (ascending; empty classes skipped) greedy rotated-BEV NMS in (score desc,
+ * concatenated index asc) order - suppressed iff a kept higher-ranked candidate has BEV IoU > nms_thr, the BEV rows after the f32
+ * round trip of xywhr2xyxyr + mmcv nms_bev; the kept ones class-major, stably sorted by descending score, the first max_num:
+ * out_boxes [batch][max_num][box_dim], out_scores / out_labels [batch][max_num], out_count [batch] (rows past the count untouched).
+ * max_per_scene >= the candidates of every scene: segments of more than U3D_TTA_LDS_CAP candidates take the global-memory path,
+ * whose suppression masks the workspace holds when max_per_scene > U3D_TTA_LDS_CAP. */
+#define U3D_TTA_LDS_CAP 2048
+int64_t u3d_tta_merge_workspace(int32_t n, int32_t box_dim, int32_t batch, int32_t views, int32_t num_classes, int32_t max_per_scene);
+int32_t u3d_tta_merge(const float* boxes, const float* scores, const int32_t* labels, int32_t n, int32_t box_dim, const int32_t* det_off,
+                      const float* params, int32_t batch, int32_t views, int32_t coord, int32_t num_classes, float nms_thr, int32_t max_num,
+                      int32_t max_per_scene, void* workspace, int64_t workspace_bytes, float* out_boxes, float* out_scores,
+                      int32_t* out_labels, int32_t* out_count, u3d_stream s);
+
 #ifdef __cplusplus
 }
 #endif

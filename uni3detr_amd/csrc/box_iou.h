@@ -46,6 +46,17 @@ __device__ static float pp_inter_area(const Q2* a, const Q2* b) {
   }
   return inter;
 }
+// rotated BEV IoU of (cx, cy, w, h, angle) rows: the arithmetic of bev_iou_rot (query.hip, class-aware NMS) on 5-column rows
+// (tta.hip: the box merge of test-time augmentation)
+__device__ static float pp_iou_bev(const float* p, const float* q) {
+  float a1 = p[2] * p[3], a2 = q[2] * q[3];
+  if (a1 <= 0.f || a2 <= 0.f) return 0.f;
+  Q2 ra[4], rb[4];
+  pp_rect(0.f, 0.f, p[2], p[3], p[4], ra);
+  pp_rect(q[0] - p[0], q[1] - p[1], q[2], q[3], q[4], rb);
+  float inter = pp_inter_area(ra, rb);
+  return inter / fmaxf(a1 + a2 - inter, 1e-8f);
+}
 // rotated 3-D IoU of bottom-centre LiDAR boxes (x, y, z_bottom, dx, dy, dz, yaw): the arithmetic of k_iou3d_rotated_aligned (query.hip)
 __device__ static float pp_iou3d(const float* p, const float* q) {
   float w1 = fmaxf(p[3], 1e-4f), h1 = fmaxf(p[4], 1e-4f), w2 = fmaxf(q[3], 1e-4f), h2 = fmaxf(q[4], 1e-4f);

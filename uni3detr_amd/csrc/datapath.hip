@@ -11,6 +11,7 @@
 // = (flip_horizontal, flip_vertical, rot_sin, rot_cos, rot_angle, scale, tx, ty, tz): flip -> rotate -> scale -> translate, the order of
 // mmdet3d's GlobalRotScaleTrans.  Everything is order-preserving and deterministic.
 #include "common.h"
+#include "box_aug.h"
 
 #define AUG_NP U3D_AUG_NPARAM
 
@@ -21,14 +22,6 @@ __device__ __forceinline__ int dp_scene_of(const int* __restrict__ off, int batc
     if (off[mid] <= i) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-// coord: 0 = Depth (SUN RGB-D / ScanNet boxes), 1 = LiDAR (KITTI / nuScenes).  Flip axes follow mmdet3d v1.0 (recalled):
-//   Depth : horizontal x -> -x (yaw -> pi - yaw), vertical y -> -y (yaw -> -yaw)
-//   LiDAR : horizontal y -> -y (yaw -> -yaw),     vertical x -> -x (yaw -> pi - yaw)
-__device__ __forceinline__ void dp_flip_xy(int coord, bool fh, bool fv, float& x, float& y) {
-  if (coord == 0) { if (fh) x = -x; if (fv) y = -y; }
-  else { if (fh) y = -y; if (fv) x = -x; }
 }
 
 __global__ void k_points_augment(float* __restrict__ pts, const int* __restrict__ scene_off, int batch, int n_total, int feat,
@@ -54,26 +47,8 @@ __global__ void k_boxes_augment(float* __restrict__ boxes, const int* __restrict
   if (i >= n) return;
   const int b = dp_scene_of(gt_off, batch, i);
   if (i >= gt_off[batch]) return;
-  const float* p = params + b * AUG_NP;
   float* r = boxes + (long long)i * dim;
-  const bool fh = p[0] != 0.f, fv = p[1] != 0.f;
-  float x = r[0], y = r[1], yaw = r[6];
-  dp_flip_xy(coord, fh, fv, x, y);
-  const float PI = 3.14159265358979323846f;
-  if (coord == 0) { if (fh) yaw = -yaw + PI; if (fv) yaw = -yaw; }
-  else { if (fh) yaw = -yaw; if (fv) yaw = -yaw + PI; }
-  const float s = p[2], c = p[3], sc = p[5];
-  r[0] = (x * c - y * s) * sc + p[6];
-  r[1] = (x * s + y * c) * sc + p[7];
-  r[2] = r[2] * sc + p[8];
-  r[3] *= sc; r[4] *= sc; r[5] *= sc;
-  r[6] = yaw + p[4];
-  if (dim >= 9) {      // velocities flip and rotate with the frame and SCALE with it (mmdet3d BaseInstance3DBoxes.scale: tensor[:, 7:] *= s, recalled)
-    float vx = r[7], vy = r[8];
-    dp_flip_xy(coord, fh, fv, vx, vy);
-    r[7] = (vx * c - vy * s) * sc;
-    r[8] = (vx * s + vy * c) * sc;
-  }
+  dp_box_augment(r, r, dim, params + b * AUG_NP, coord);
 }
 
 // PointsRangeFilter (mmdet3d, recalled: BasePoints.in_range_3d, strict inequalities on x, y, z): one workgroup per scene walks the

@@ -112,8 +112,9 @@ class GlobalRotScaleTrans:
         B = batch["scene_off"].numel() - 1
         if "pcd_rotation_angle" not in batch:        # per sample: rotation first, then scale, then translation (transform_3d.py:456-460)
             ang, sc, tr = np.zeros(B, np.float32), np.ones(B, np.float32), np.zeros((B, 3), np.float32)
+            preset = batch.get("rot_degree")         # a test-time view's angle (transform_3d.py:368-372)
             for b in range(B):
-                ang[b] = np.random.uniform(self.rot_range[0], self.rot_range[1])
+                ang[b] = preset[b] if preset is not None else np.random.uniform(self.rot_range[0], self.rot_range[1])
                 sc[b] = np.random.uniform(self.scale_ratio_range[0], self.scale_ratio_range[1])
                 if np.any(self.translation_std != 0):
                     tr[b] = np.random.normal(scale=self.translation_std, size=3)
@@ -200,17 +201,108 @@ class ObjectRangeFilter:
         return batch
 
 
+def _replicate(x, off, views):
+    """rows of every segment of x (segment i = rows off[i] .. off[i+1]), each repeated `views` times in a row: (rows, offsets) - one
+    gather on the device, no host loop over the views"""
+    dev = x.device
+    n = int(x.shape[0])
+    lens = (off[1:] - off[:-1]).long()
+    lens_v = lens.repeat_interleave(views)
+    off_v = torch.zeros(lens_v.numel() + 1, dtype=torch.long, device=dev)
+    off_v[1:] = torch.cumsum(lens_v, 0)
+    seg = torch.repeat_interleave(torch.arange(lens_v.numel(), device=dev), lens_v, output_size=n * views)
+    src = off.long()[seg // views] + torch.arange(n * views, device=dev) - off_v[seg]
+    return x.index_select(0, src), off_v.to(torch.int32)
+
+
 @PIPELINES.register_module()
 class MultiScaleFlipAug3D:
-    """Test-time wrapper (mmdet3d): one scale, no flip in the plugin's use - the inner transforms run as they are."""
+    """Test-time augmentation (mmdet3d MultiScaleFlipAug3D; the plugin's MultiRotScaleFlipAug3D, test_time_aug.py:10-125, adds
+    `rotate_degree`, angles in radians).  A packed batch of B scenes becomes one packed batch of B*A scenes, scene-major, view-minor,
+    the views enumerated in the reference's loop order (test_time_aug.py:84-107): rotation, scale, flip (`[True] if flip else [False]`),
+    horizontal flip ([False, True] when enabled), vertical flip (likewise).  The scenes are replicated by one device gather; every
+    view's draws are preset in the batch keys the inner transforms honour (pcd_horizontal_flip, pcd_vertical_flip, pcd_scale_factor,
+    rot_degree -> GlobalRotScaleTrans's angle), and the inner transforms run once over the expanded batch.  batch["tta_views"] = A,
+    batch["tta_params"] = f32 [B*A, 9] view table (flip_h, flip_v, sin, cos, angle, scale, 0, 0, 0): rotation and scale first, then the
+    flips - the order of the inner pipelines (GlobalRotScaleTrans before RandomFlip3D); tta_forward_inputs() gives the reference's
+    forward_test(points, img_metas) shape.  img_scale and flip_direction have no effect without images."""
+    rotations = (0.0,)
 
-    def __init__(self, transforms, img_scale=None, pts_scale_ratio=1, flip=False, **kwargs):
-        if flip or (pts_scale_ratio not in (1, 1.0, [1], [1.0])):
-            raise NotImplementedError("test-time flips / point scaling are not used by any shipped Uni3DETR config")
+    def __init__(self, transforms, img_scale=None, pts_scale_ratio=1, flip=False, flip_direction="horizontal", pcd_horizontal_flip=False,
+                 pcd_vertical_flip=False, rotate_degree=None):
+        self.pts_scale_ratio = [float(r) for r in pts_scale_ratio] if isinstance(pts_scale_ratio, (list, tuple)) else [float(pts_scale_ratio)]
+        self.img_scale = img_scale if isinstance(img_scale, list) else [img_scale]
+        self.rotate_degree = [float(r) for r in (rotate_degree if rotate_degree is not None else self.rotations)]
+        self.flip, self.pcd_horizontal_flip, self.pcd_vertical_flip = bool(flip), bool(pcd_horizontal_flip), bool(pcd_vertical_flip)
+        types = [t["type"] for t in transforms]
+        flips = [i for i, t in enumerate(types) if t in ("RandomFlip3D", "UnifiedRandomFlip3D")]
+        rots = [i for i, t in enumerate(types) if t in ("GlobalRotScaleTrans", "UnifiedRotScaleTrans")]
+        if any(r != 0.0 for r in self.rotate_degree) and flips and (not rots or flips[0] < rots[0]):
+            raise NotImplementedError("test-time rotations need GlobalRotScaleTrans before RandomFlip3D in the inner transforms")
         self.inner = DevicePipeline(transforms)
 
+    def views(self):
+        """[(rot, scale ratio, flip, horizontal, vertical)] in the reference's loop order (one entry per img_scale as well)."""
+        fl = [True] if self.flip else [False]
+        hf = [False, True] if self.flip and self.pcd_horizontal_flip else [False]
+        vf = [False, True] if self.flip and self.pcd_vertical_flip else [False]
+        return [(r, s, f, h, v) for r in self.rotate_degree for _ in self.img_scale for s in self.pts_scale_ratio for f in fl for h in hf
+                for v in vf]
+
     def __call__(self, batch):
-        return self.inner(batch)
+        views = self.views()
+        A = len(views)
+        B = batch["scene_off"].numel() - 1
+        if views == [(0.0, 1.0, False, False, False)]:
+            # the single identity view: the inner transforms run on the batch as they are (no replication, nothing preset)
+            batch["tta_views"] = 1
+            batch["tta_params"] = _params(dict(scene_off=batch["scene_off"], points=batch["points"]))
+            return self.inner(batch)
+        out = {k: v for k, v in batch.items() if k not in ("points", "scene_off", "count", "gt_bboxes_3d", "gt_off", "gt_labels_3d", "gt_count")}
+        if "count" in batch:
+            raise ValueError("MultiScaleFlipAug3D expects a packed batch (no `count`): it runs first in a test pipeline")
+        out["points"], out["scene_off"] = _replicate(batch["points"], batch["scene_off"], A)
+        if batch.get("gt_bboxes_3d") is not None:
+            out["gt_bboxes_3d"], out["gt_off"] = _replicate(batch["gt_bboxes_3d"], batch["gt_off"], A)
+            if batch.get("gt_labels_3d") is not None:
+                out["gt_labels_3d"], _ = _replicate(batch["gt_labels_3d"], batch["gt_off"], A)
+        rot = np.array([v[0] for v in views] * B, np.float32)
+        sc = np.array([v[1] for v in views] * B, np.float32)
+        out.update(rot_degree=rot, pcd_scale_factor=sc, flip=np.array([v[2] for v in views] * B, bool),
+                   pcd_horizontal_flip=np.array([v[3] for v in views] * B, bool), pcd_vertical_flip=np.array([v[4] for v in views] * B, bool),
+                   tta_views=A)
+        out["tta_params"] = _params(dict(scene_off=out["scene_off"], points=out["points"], pcd_horizontal_flip=out["pcd_horizontal_flip"],
+                                         pcd_vertical_flip=out["pcd_vertical_flip"], pcd_rotation_angle=rot, pcd_scale_factor=sc))
+        return self.inner(out)
+
+
+@PIPELINES.register_module()
+class MultiRotScaleFlipAug3D(MultiScaleFlipAug3D):
+    """ref: projects/mmdet3d_plugin/datasets/pipelines/test_time_aug.py:10-125 (rotate_degree: angles in radians)."""
+
+    def __init__(self, transforms, img_scale=None, pts_scale_ratio=1, rotate_degree=(0.0,), flip=False, flip_direction="horizontal",
+                 pcd_horizontal_flip=False, pcd_vertical_flip=False):
+        super().__init__(transforms, img_scale, pts_scale_ratio, flip, flip_direction, pcd_horizontal_flip, pcd_vertical_flip,
+                         rotate_degree=list(rotate_degree))
+
+
+def tta_forward_inputs(batch):
+    """an expanded batch (MultiScaleFlipAug3D) -> (points, img_metas) in the reference's forward_test shape: points[a][b] and
+    img_metas[a][b] for view a of scene b, the metas holding pcd_scale_factor, pcd_horizontal_flip, pcd_vertical_flip, rot_degree and
+    box_type_3d (views of the packed tensors: no copies)."""
+    A = int(batch["tta_views"])
+    pts = unpack_batch(batch)[0]
+    B = len(pts) // A
+    box_type = batch.get("box_type_3d", "Depth")
+    points = [[pts[b * A + a] for b in range(B)] for a in range(A)]
+    n = A * B
+    sc = np.asarray(batch.get("pcd_scale_factor", np.ones(n)), np.float32)
+    fh = np.asarray(batch.get("pcd_horizontal_flip", np.zeros(n, bool)), bool)
+    fv = np.asarray(batch.get("pcd_vertical_flip", np.zeros(n, bool)), bool)
+    rot = np.asarray(batch.get("rot_degree", np.zeros(n)), np.float32)
+    metas = [[dict(pcd_scale_factor=float(sc[b * A + a]), pcd_horizontal_flip=bool(fh[b * A + a]), pcd_vertical_flip=bool(fv[b * A + a]),
+                   rot_degree=float(rot[b * A + a]), box_type_3d=box_type) for b in range(B)] for a in range(A)]
+    return points, metas
 
 
 @OBJECT_AUG.register_module()

@@ -6,6 +6,7 @@ current HIP stream.  There is NO CPU fallback: if the library is missing or a ca
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -146,6 +147,8 @@ _SIGS = {
     "u3d_trilinear_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "u3d_nms3d_workspace": (_L, [_I]),
     "u3d_nms3d": (_I, [_P, _P, _I, C.c_float, _P, _P, _L, _P]),
+    "u3d_tta_merge_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
+    "u3d_tta_merge": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, C.c_float, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "u3d_iou3d_rotated_aligned": (_I, [_P, _P, _I, _P, _P]),
     "u3d_tap_gather_sum": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "u3d_tap_gather_sum_add": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -2096,3 +2099,49 @@ def object_noise(points, scene_off, n_live, max_rows, boxes, gt_off, g_live, loc
                                   _ptr(gt_off), _ptr(g_live), boxes.shape[1], num_try, _ptr(_nz(loc.contiguous())), _ptr(_nz(rot.contiguous())),
                                   _ptr(first), _ptr(sel), _ptr(chosen), _stream()), "object_noise")
     return chosen[:boxes.shape[0]]
+
+
+# --------------------------------------------------------------------------------------------------
+# Test-time augmentation: the multi-view box merge (csrc/tta.hip)
+# --------------------------------------------------------------------------------------------------
+TTA_LDS_CAP = 2048     # U3D_TTA_LDS_CAP: larger (scene, class) segments take the global-memory path
+
+
+def tta_inverse_params(params):
+    """[V,9] forward view table (rotation + scale, then flips) -> the u3d_boxes_augment parameters of its inverse, as the merge applies
+    them: (fh, fv, -sin, cos, -angle, 1/scale, 0, 0, 0)."""
+    p = params.detach().float().cpu().numpy()
+    inv = np.zeros_like(p)
+    inv[:, 0], inv[:, 1], inv[:, 2], inv[:, 3], inv[:, 4] = p[:, 0], p[:, 1], -p[:, 2], p[:, 3], -p[:, 4]
+    inv[:, 5] = np.float32(1) / p[:, 5]                   # IEEE division, as the kernel's (torch's 1 / t is a reciprocal product)
+    return torch.from_numpy(inv).to(params.device)
+
+
+def tta_merge(boxes, scores, labels, det_off, params, views, coord, num_classes, nms_thr=0.1, max_num=500):
+    """Merge the per-view detections of B scenes (views scene-major, view-minor: det_off [B*views+1], HOST ints or a CPU tensor; a
+    device tensor costs one copy to the host) -> (boxes [B, max_num, D], scores [B, max_num], labels int32 [B, max_num], count int32 [B])
+    on the device, no host sync; rows past count[b] are undefined.  params: f32 [B*views, 9] forward view table (csrc/tta.hip)."""
+    dev = params.device
+    off_h = [int(v) for v in (det_off.cpu().tolist() if torch.is_tensor(det_off) else det_off)]
+    nviews = len(off_h) - 1
+    assert nviews > 0 and nviews % views == 0 and params.shape == (nviews, AUG_NPARAM)
+    batch = nviews // views
+    n = off_h[-1]
+    dim = boxes.shape[1] if boxes.dim() == 2 else 7
+    assert dim in (7, 9) and boxes.shape[0] == n and scores.shape[0] == n and labels.shape[0] == n
+    max_per_scene = max(off_h[(b + 1) * views] - off_h[b * views] for b in range(batch))
+    max_num = int(max_num)
+    out_b = torch.empty((batch, max_num, dim), dtype=torch.float32, device=dev)
+    out_s = torch.empty((batch, max_num), dtype=torch.float32, device=dev)
+    out_l = torch.empty((batch, max_num), dtype=torch.int32, device=dev)
+    out_c = torch.empty((batch,), dtype=torch.int32, device=dev)
+    off_d = torch.tensor(off_h, dtype=torch.int32, device=dev)
+    wsb = int(lib().u3d_tta_merge_workspace(n, dim, batch, int(views), int(num_classes), max_per_scene))
+    ws = torch.empty((max(1, wsb),), dtype=torch.uint8, device=dev)
+    b = _nz(boxes.float().contiguous().reshape(n, dim))
+    sc = _nz(scores.float().contiguous())
+    lb = _nz(labels.to(torch.int32).contiguous())
+    _check(lib().u3d_tta_merge(_ptr(b), _ptr(sc), _ptr(lb), n, dim, _ptr(off_d), _ptr(params.float().contiguous()), batch, int(views),
+                               int(coord), int(num_classes), float(nms_thr), max_num, max_per_scene, _ptr(ws), wsb, _ptr(out_b), _ptr(out_s),
+                               _ptr(out_l), _ptr(out_c), _stream()), "tta_merge")
+    return out_b, out_s, out_l, out_c
