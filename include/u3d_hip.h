@@ -896,6 +896,16 @@ int32_t u3d_point_sample(const float* points, const int32_t* scene_off, const in
  * front of the scene's segment (labels int32, nullable, move with them), yaw wrapped into [-pi, pi); count[b] = survivors. */
 int32_t u3d_boxes_range_filter(float* boxes, int32_t* labels, const int32_t* gt_off, int32_t batch, int32_t box_dim,
                                const float* bev_range4, int32_t* count, u3d_stream s);
+/* PointShuffle: out [n_total, feat] f32, written out of place (out must not alias points): the first count[b] rows of scene b's
+ * segment (count NULL = the whole segment) permuted by a keyed pseudo-random permutation (the PointSample one), every other row copied
+ * as it is; seed: device u64, the scene index goes into the key (advance it per call). */
+int32_t u3d_point_shuffle(const float* points, const int32_t* scene_off, const int32_t* count, int32_t batch, int32_t n_total, int32_t feat,
+                          const uint64_t* seed, float* out, u3d_stream s);
+/* ObjectNameFilter: in place, per scene, order kept: of the first gt_count[b] rows of scene b's segment (gt_count NULL = the whole
+ * segment), the boxes whose label lies in [0, num_classes) move to the front (labels int32 move with them); count[b] = survivors
+ * (count must not alias gt_count). */
+int32_t u3d_boxes_label_filter(float* boxes, int32_t* labels, const int32_t* gt_off, const int32_t* gt_count, int32_t batch, int32_t box_dim,
+                               int32_t num_classes, int32_t* count, u3d_stream s);
 
 /* GT-paste (mmdet3d ObjectSample / the plugin's UnifiedObjectSample, ref: projects/mmdet3d_plugin/datasets/pipelines/dbsampler.py,
  * transform_3d.py:591-786) and ObjectNoise (global_rot_range = 0) on a packed batch: uni3detr_amd/csrc/objaug.hip.  The random draws
@@ -954,6 +964,29 @@ int32_t u3d_tta_merge(const float* boxes, const float* scores, const int32_t* la
                       const float* params, int32_t batch, int32_t views, int32_t coord, int32_t num_classes, float nms_thr, int32_t max_num,
                       int32_t max_per_scene, void* workspace, int64_t workspace_bytes, float* out_boxes, float* out_scores,
                       int32_t* out_labels, int32_t* out_count, u3d_stream s);
+
+/* LoadPointsFromMultiSweeps (mmdet3d, recalled): uni3detr_amd/csrc/sweeps.hip.  Output, scene after scene:
+ * the key frame (time column 4 set to 0), then every chosen sweep's rows that survive remove_close (|x| < 1 and |y| < 1 dropped, on
+ * the raw coordinates), transformed in float64 as xyz_f32 = f32((r0*x + r1*y) + r2*z), xyz = f32(xyz_f32 + t), column 4 = f32(lag);
+ * or the pad copies of the key frame (remove_close applied, untransformed, time 0); then out[:, k] = row[use_dim[k]].
+ * Segments (key frame, sweep or pad copy), scene-major in output order: seg_tab int32 [n_seg][U3D_SWEEPS_SEG_FIELDS] = (kind, first
+ * source row, rows): a sweep reads raw [n_raw_rows, load_dim], the key frame and pad copies key_points [n_key_rows, load_dim];
+ * seg_param f64 [n_seg][U3D_SWEEPS_NPARAM] = (R row-major [9], t [3], lag); seg_chunk0 int32 [n_seg + 1] = the first chunk of
+ * U3D_SWEEPS_CHUNK rows of every segment (ceil(rows / U3D_SWEEPS_CHUNK) chunks each, seg_chunk0[n_seg] = n_chunks); scene_chunk0
+ * int32 [batch + 1] = the first chunk of every scene (n_chunks past the last).  All of them device arrays; use_dim (n_use <= 8) a HOST
+ * array; 5 <= load_dim <= 8.  out [out_rows, n_use] (out_rows >= the sum of all segment rows); out_scene_off int32 [batch + 1]: the
+ * output is exactly packed, rows past out_scene_off[batch] are untouched.  workspace: u3d_sweeps_merge_workspace(n_chunks) bytes. */
+#define U3D_SWEEPS_CHUNK 256
+#define U3D_SWEEPS_NPARAM 13
+#define U3D_SWEEPS_SEG_FIELDS 3
+#define U3D_SWEEP_SEG_KEY 0
+#define U3D_SWEEP_SEG_SWEEP 1
+#define U3D_SWEEP_SEG_PAD 2
+int64_t u3d_sweeps_merge_workspace(int32_t n_chunks);
+int32_t u3d_sweeps_merge(const float* key_points, int64_t n_key_rows, const float* raw, int64_t n_raw_rows, int32_t load_dim,
+                         const int32_t* seg_tab, const double* seg_param, int32_t n_seg, const int32_t* seg_chunk0, const int32_t* scene_chunk0,
+                         int32_t batch, int32_t n_chunks, const int32_t* use_dim, int32_t n_use, int32_t remove_close, void* workspace,
+                         int64_t workspace_bytes, float* out, int64_t out_rows, int32_t* out_scene_off, u3d_stream s);
 
 #ifdef __cplusplus
 }

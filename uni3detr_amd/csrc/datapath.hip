@@ -173,6 +173,64 @@ __global__ __launch_bounds__(64) void k_boxes_range_filter(float* __restrict__ b
   if (lane == 0) count[b] = base;
 }
 
+// PointShuffle (mmdet3d, recalled: BasePoints.shuffle = torch.randperm per sample).  The torch stream cannot be replayed on the
+// device; what is kept is the distribution, by PointSample's rule: the live rows of every scene go through a keyed permutation (dp_perm,
+// the key from the device seed and the scene index), gathered out of place.  Dead rows past count[b], and rows outside every scene,
+// are copied as they are, so `count` and `scene_off` stay valid.
+__global__ void k_point_shuffle(const float* __restrict__ pts, const int* __restrict__ scene_off, const int* __restrict__ count, int batch,
+                                int n_total, int feat, const unsigned long long* __restrict__ seed, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_total) return;
+  int src = i;
+  if (i >= scene_off[0] && i < scene_off[batch]) {
+    const int b = dp_scene_of(scene_off, batch, i);
+    const int r0 = scene_off[b], seg = scene_off[b + 1] - r0;
+    int n = count ? count[b] : seg;
+    n = n > seg ? seg : (n < 0 ? 0 : n);
+    const int k = i - r0;
+    if (k < n) {
+      const unsigned long long sd = *seed;
+      const unsigned key = dp_mix((unsigned)sd ^ dp_mix((unsigned)(sd >> 32) + 0x85ebca6bu * (unsigned)(b + 1)) ^ 0x27d4eb2fu);
+      src = r0 + (int)dp_perm((unsigned)k, (unsigned)n, key);
+    }
+  }
+  const float* r = pts + (long long)src * feat;
+  float* o = out + (long long)i * feat;
+  for (int f = 0; f < feat; ++f) o[f] = r[f];
+}
+
+// ObjectNameFilter (mmdet3d, recalled: keep the GT rows whose label is in range(len(classes))): one wave per scene compacts the live
+// prefix (gt_count[b] rows, set by ObjectRangeFilter, or the whole segment) in place, order kept, as k_boxes_range_filter does.
+__global__ __launch_bounds__(64) void k_boxes_label_filter(float* __restrict__ boxes, int* __restrict__ labels, const int* __restrict__ gt_off,
+                                                           const int* __restrict__ gt_count, int dim, int ncls, int* __restrict__ count) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int r0 = gt_off[b];
+  int r1 = gt_off[b + 1];
+  if (gt_count) {
+    const int live = gt_count[b];
+    r1 = live < 0 ? r0 : (live < r1 - r0 ? r0 + live : r1);
+  }
+  int base = 0;
+  for (int c0 = r0; c0 < r1; c0 += 64) {
+    const int i = c0 + lane;
+    float v[9];
+    int lab = -1;
+    if (i < r1) {
+      for (int f = 0; f < dim; ++f) v[f] = boxes[(long long)i * dim + f];
+      lab = labels[i];
+    }
+    const bool keep = i < r1 && lab >= 0 && lab < ncls;
+    const unsigned long long m = __ballot(keep);          // every lane has read its row before any lane writes (one wave, in order)
+    const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (keep) {
+      for (int f = 0; f < dim; ++f) boxes[(long long)(r0 + pos) * dim + f] = v[f];
+      labels[r0 + pos] = lab;
+    }
+    base += __popcll(m);
+  }
+  if (lane == 0) count[b] = base;
+}
+
 extern "C" int32_t u3d_points_augment(float* points, const int32_t* scene_off, int32_t batch, int32_t n_total, int32_t feat,
                                       const float* params, int32_t coord, int32_t height_dim, u3d_stream s) {
   U3D_REQUIRE(points && scene_off && params && batch > 0 && feat >= 3 && (coord == 0 || coord == 1), U3D_ERR_ARG);
@@ -211,6 +269,23 @@ extern "C" int32_t u3d_boxes_range_filter(float* boxes, int32_t* labels, const i
   U3D_REQUIRE(boxes && gt_off && bev_range4 && count && batch > 0 && (box_dim == 7 || box_dim == 9), U3D_ERR_ARG);
   hipLaunchKernelGGL(k_boxes_range_filter, dim3(batch), dim3(64), 0, s, boxes, labels, gt_off, box_dim, bev_range4[0], bev_range4[1],
                      bev_range4[2], bev_range4[3], count);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+extern "C" int32_t u3d_point_shuffle(const float* points, const int32_t* scene_off, const int32_t* count, int32_t batch, int32_t n_total,
+                                     int32_t feat, const uint64_t* seed, float* out, u3d_stream s) {
+  U3D_REQUIRE(points && scene_off && seed && out && out != points && batch > 0 && feat >= 1 && n_total >= 0, U3D_ERR_ARG);
+  if (n_total == 0) return U3D_OK;
+  hipLaunchKernelGGL(k_point_shuffle, dim3(u3d_cdiv(n_total, 256)), dim3(256), 0, s, points, scene_off, count, batch, n_total, feat,
+                     (const unsigned long long*)seed, out);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+extern "C" int32_t u3d_boxes_label_filter(float* boxes, int32_t* labels, const int32_t* gt_off, const int32_t* gt_count, int32_t batch,
+                                          int32_t box_dim, int32_t num_classes, int32_t* count, u3d_stream s) {
+  U3D_REQUIRE(boxes && labels && gt_off && count && count != gt_count && batch > 0 && (box_dim == 7 || box_dim == 9) && num_classes >= 0,
+              U3D_ERR_ARG);
+  hipLaunchKernelGGL(k_boxes_label_filter, dim3(batch), dim3(64), 0, s, boxes, labels, gt_off, gt_count, box_dim, num_classes, count);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

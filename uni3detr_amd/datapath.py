@@ -203,16 +203,20 @@ class ObjectRangeFilter:
 
 def _replicate(x, off, views):
     """rows of every segment of x (segment i = rows off[i] .. off[i+1]), each repeated `views` times in a row: (rows, offsets) - one
-    gather on the device, no host loop over the views"""
+    gather on the device, no host loop over the views.  Rows of x past off[-1] (spare capacity, as the sweep merge and ObjectSample
+    leave it) are allowed: the output then has spare rows past the new off[-1] too (x's spare rows, then copies of its last row)."""
     dev = x.device
     n = int(x.shape[0])
     lens = (off[1:] - off[:-1]).long()
     lens_v = lens.repeat_interleave(views)
     off_v = torch.zeros(lens_v.numel() + 1, dtype=torch.long, device=dev)
     off_v[1:] = torch.cumsum(lens_v, 0)
-    seg = torch.repeat_interleave(torch.arange(lens_v.numel(), device=dev), lens_v, output_size=n * views)
+    # one extra segment takes the n * views - off_v[-1] spare output rows (none for an exactly packed x), so that the repeat counts
+    # always sum to output_size: repeat_interleave does not check that on the device
+    counts = torch.cat([lens_v, (n * views - off_v[-1:]).clamp(min=0)])
+    seg = torch.repeat_interleave(torch.arange(lens_v.numel() + 1, device=dev), counts, output_size=n * views)
     src = off.long()[seg // views] + torch.arange(n * views, device=dev) - off_v[seg]
-    return x.index_select(0, src), off_v.to(torch.int32)
+    return x.index_select(0, src.clamp(max=max(n - 1, 0))), off_v.to(torch.int32)
 
 
 @PIPELINES.register_module()
@@ -450,6 +454,177 @@ class ObjectNoise:
         return batch
 
 
+@OBJECT_AUG.register_module()
+class LoadPointsFromMultiSweeps:
+    """ref: mmdet3d LoadPointsFromMultiSweeps (v1.0.0rc5, recalled), the second entry of the nuScenes train and test pipelines.  The host
+    part is read_sweeps (the choice draw and the file reads, one record per scene) and pack_batch(..., sweeps=records) (one upload);
+    this transform merges on the device (csrc/sweeps.hip): per scene the key frame with time 0, then the chosen sweeps in choice order
+    (remove_close, rotation and translation into the key frame in float64, the time lag in column 4) or `sweeps_num` pad copies of the
+    key frame, then the use_dim gather.  The output is exactly packed: new points / scene_off, rows past scene_off[-1] are spare
+    capacity.  It runs on the packed key frames, before any other transform."""
+
+    def __init__(self, sweeps_num=10, load_dim=5, use_dim=(0, 1, 2, 4), file_client_args=None, pad_empty_sweeps=False, remove_close=False,
+                 test_mode=False):
+        backend = (file_client_args or {}).get("backend", "disk")
+        if backend != "disk" or any(k != "backend" for k in (file_client_args or {})):
+            raise NotImplementedError(f"LoadPointsFromMultiSweeps: file_client_args {dict(file_client_args)} (only the disk backend)")
+        if not isinstance(remove_close, bool) and float(remove_close) not in (0.0, 1.0):
+            raise NotImplementedError(f"LoadPointsFromMultiSweeps: remove_close radius {remove_close} (upstream removes within 1.0)")
+        self.sweeps_num, self.load_dim = int(sweeps_num), int(load_dim)
+        self.use_dim = [int(d) for d in use_dim]
+        if not 5 <= self.load_dim <= 8 or not 1 <= len(self.use_dim) <= 8 or not all(0 <= d < self.load_dim for d in self.use_dim):
+            raise NotImplementedError(f"LoadPointsFromMultiSweeps: load_dim {load_dim} / use_dim {list(use_dim)} (5 <= load_dim <= 8, "
+                                      "at most 8 columns)")
+        self.pad_empty_sweeps, self.remove_close, self.test_mode = bool(pad_empty_sweeps), bool(remove_close), bool(test_mode)
+
+    def choose(self, n_sweeps, rng=np.random):
+        """upstream's choice rule: all sweeps when there are at most sweeps_num, the first sweeps_num in test mode, else a draw."""
+        if n_sweeps <= self.sweeps_num:
+            return np.arange(n_sweeps)
+        if self.test_mode:
+            return np.arange(self.sweeps_num)
+        return rng.choice(n_sweeps, self.sweeps_num, replace=False)
+
+    def __call__(self, batch):
+        sw = batch["sweeps"]
+        if "count" in batch:
+            raise ValueError("LoadPointsFromMultiSweeps expects the packed key frames (no `count`): it runs first")
+        pts = batch["points"]
+        if sw["load_dim"] != self.load_dim or pts.shape[1] != self.load_dim or pts.shape[0] != sw["n_key"]:
+            raise ValueError(f"LoadPointsFromMultiSweeps: the batch holds [{pts.shape[0]}, {pts.shape[1]}] key rows, the sweep record "
+                             f"[{sw['n_key']}, {sw['load_dim']}], the entry load_dim {self.load_dim}")
+        if any(r["sweeps_num"] != self.sweeps_num for r in sw["records"]):
+            raise ValueError("LoadPointsFromMultiSweeps: the sweep records were read with another sweeps_num")
+        batch["points"], batch["scene_off"] = nv.sweeps_merge(pts.contiguous(), sw["raw"], sw["seg_tab"], sw["seg_param"], sw["seg_chunk0"],
+                                                              sw["scene_chunk0"], sw["n_chunks"], sw["out_rows"], self.use_dim,
+                                                              self.remove_close)
+        del batch["sweeps"]            # the raw rows and tables on the device are spent (stream-ordered free); sweep_choices stays
+        return batch
+
+
+def read_sweeps(info_like, entry_cfg, rng=np.random, choices=None):
+    """The host part of LoadPointsFromMultiSweeps for one scene.  info_like: the dict NuScenesSweepDataset.get_data_info makes
+    (`timestamp` in seconds, `sweeps`: dicts with data_path, timestamp in microseconds, sensor2lidar_rotation / _translation);
+    entry_cfg: the pipeline entry.  Makes upstream's choice draw from `rng` (or reuses `choices`, e.g. a recorded
+    batch["sweep_choices"][b]) and reads only the chosen files -> record dict(points=[float32 [n_j, load_dim]], rot f64 [S,3,3],
+    trans f64 [S,3], dt f64 [S] (= timestamp - sweep timestamp / 1e6), choices int64 [S], pad, sweeps_num, load_dim)."""
+    entry = LoadPointsFromMultiSweeps(**{k: v for k, v in entry_cfg.items() if k != "type"})
+    sweeps, ts = info_like["sweeps"], info_like["timestamp"]
+    pad = entry.pad_empty_sweeps and len(sweeps) == 0
+    if pad:
+        choices = np.zeros(0, np.int64)
+    elif choices is None:
+        choices = entry.choose(len(sweeps), rng)
+    choices = np.asarray(choices, np.int64).reshape(-1)
+    pts, rot, trans, dt = [], [], [], []
+    for idx in choices:
+        sweep = sweeps[int(idx)]
+        pts.append(np.fromfile(sweep["data_path"], dtype=np.float32).reshape(-1, entry.load_dim))
+        rot.append(np.asarray(sweep["sensor2lidar_rotation"], np.float64).reshape(3, 3))
+        trans.append(np.asarray(sweep["sensor2lidar_translation"], np.float64).reshape(3))
+        dt.append(ts - sweep["timestamp"] / 1e6)
+    return dict(points=pts, rot=np.asarray(rot, np.float64).reshape(-1, 3, 3), trans=np.asarray(trans, np.float64).reshape(-1, 3),
+                dt=np.asarray(dt, np.float64).reshape(-1), choices=choices, pad=bool(pad), sweeps_num=entry.sweeps_num,
+                load_dim=entry.load_dim)
+
+
+def _upload_sweeps(records, key_lens, feat, dev):
+    """The segment tables of u3d_sweeps_merge and every raw sweep row, in one pinned buffer and one host-to-device copy."""
+    if len(records) != len(key_lens):
+        raise ValueError(f"{len(records)} sweep records for {len(key_lens)} scenes")
+    ld = int(records[0]["load_dim"]) if records else feat
+    if any(int(r["load_dim"]) != ld for r in records) or ld != feat:
+        raise ValueError(f"sweep records of load_dim {[r['load_dim'] for r in records]} for key frames of {feat} columns")
+    C = nv.SWEEPS_CHUNK
+    seg, par, chunk0, scene_chunk0, raws = [], [], [0], [], []
+    key_off = np.concatenate([[0], np.cumsum(key_lens)]).astype(np.int64)
+    raw_rows = 0
+
+    def add(kind, src, rows, p):
+        seg.append((kind, src, rows))
+        par.append(p)
+        chunk0.append(chunk0[-1] + (rows + C - 1) // C)
+
+    zero = np.zeros(nv.SWEEPS_NPARAM, np.float64)
+    for b, r in enumerate(records):
+        scene_chunk0.append(chunk0[-1])
+        add(nv.SWEEP_SEG_KEY, int(key_off[b]), int(key_lens[b]), zero)
+        if r["pad"]:
+            for _ in range(int(r["sweeps_num"])):
+                add(nv.SWEEP_SEG_PAD, int(key_off[b]), int(key_lens[b]), zero)
+            continue
+        for j, a in enumerate(r["points"]):
+            a = np.asarray(a, np.float32).reshape(-1, ld)
+            add(nv.SWEEP_SEG_SWEEP, raw_rows, a.shape[0], np.concatenate([r["rot"][j].reshape(9), r["trans"][j], [r["dt"][j]]]))
+            raws.append(a)
+            raw_rows += a.shape[0]
+    scene_chunk0.append(chunk0[-1])
+    out_rows = sum(e[2] for e in seg)
+    if max(raw_rows, out_rows, int(key_off[-1]), chunk0[-1]) >= 2 ** 31:
+        raise ValueError("sweep merge: 2^31 rows or more in the batch (the device offsets are int32)")
+    S = len(seg)
+    ints = np.concatenate([np.asarray(seg, np.int32).reshape(-1), np.asarray(chunk0, np.int32), np.asarray(scene_chunk0, np.int32)])
+    nb_p, nb_i = S * nv.SWEEPS_NPARAM * 8, ints.size * 4
+    nb_i_pad = (nb_i + 15) // 16 * 16
+    buf = torch.empty((nb_p + nb_i_pad + raw_rows * ld * 4,), dtype=torch.uint8, pin_memory=True)
+    host = buf.numpy()
+    host[:nb_p].view(np.float64)[:] = np.asarray(par, np.float64).reshape(-1)
+    host[nb_p:nb_p + nb_i].view(np.int32)[:] = ints
+    if raw_rows:
+        np.concatenate(raws, 0, out=host[nb_p + nb_i_pad:].view(np.float32).reshape(raw_rows, ld))
+    d = buf.to(dev, non_blocking=True)                    # the one upload; the caching host allocator keeps buf until it is done
+    di = d[nb_p:nb_p + nb_i].view(torch.int32)
+    return dict(records=records, seg_param=d[:nb_p].view(torch.float64).reshape(S, nv.SWEEPS_NPARAM),
+                seg_tab=di[:3 * S].reshape(S, 3), seg_chunk0=di[3 * S:4 * S + 1], scene_chunk0=di[4 * S + 1:],
+                raw=d[nb_p + nb_i_pad:].view(torch.float32).reshape(raw_rows, ld), n_chunks=int(chunk0[-1]),
+                out_rows=int(out_rows), n_key=int(key_off[-1]), load_dim=ld)
+
+
+@OBJECT_AUG.register_module()
+class PointShuffle:
+    """ref: mmdet3d PointShuffle (recalled: BasePoints.shuffle, one torch.randperm per sample).  The torch stream cannot be replayed
+    on the device, so the rule is PointSample's: the live rows of every scene (`count`, or the whole segment) go through a keyed
+    pseudo-random permutation, out of place; the key comes from a device int64 seed that advances on every call (capturable).
+    `count` and `scene_off` stay as they are."""
+
+    def __init__(self):
+        self._seed = None
+
+    def __call__(self, batch):
+        dev = batch["points"].device
+        if self._seed is None or self._seed.device != dev:
+            # one draw from the host stream, uploaded from pinned memory: no synchronising copy
+            self._seed = torch.tensor([int(np.random.randint(0, 2 ** 62))], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        else:
+            self._seed += 0x9E3779B97F4A7C15 - (1 << 64)
+        batch["points"] = nv.point_shuffle(batch["points"], batch["scene_off"], batch.get("count"), self._seed)
+        return batch
+
+
+@OBJECT_AUG.register_module()
+class ObjectNameFilter:
+    """ref: mmdet3d ObjectNameFilter (recalled): the GT rows whose label is in range(len(classes)) are kept (LoadAnnotations3D labels
+    names outside `classes` -1).  Per scene, in place, order kept, over the live prefix (`gt_count` after ObjectRangeFilter, or the
+    whole segment); the survivors' count becomes `gt_count`.  7- and 9-column boxes."""
+
+    def __init__(self, classes):
+        self.classes = list(classes)
+        self.labels = list(range(len(self.classes)))
+
+    def __call__(self, batch):
+        g = batch.get("gt_bboxes_3d")
+        if g is None:
+            return batch
+        lab = batch["gt_labels_3d"]
+        if lab.dtype != torch.int32 or not lab.is_contiguous():
+            lab = batch["gt_labels_3d"] = lab.to(torch.int32).contiguous()
+        if g.shape[0] == 0:
+            batch["gt_count"] = torch.zeros(batch["gt_off"].numel() - 1, dtype=torch.int32, device=batch["gt_off"].device)
+            return batch
+        batch["gt_count"] = nv.boxes_label_filter(g, lab, batch["gt_off"], batch.get("gt_count"), len(self.classes))
+        return batch
+
+
 _PASSTHROUGH = {"LoadPointsFromFile", "LoadAnnotations3D", "DefaultFormatBundle3D", "Collect3D", "CollectUnified3D", "LoadPointsFromMultiSweeps",
                 "ObjectNameFilter", "PointShuffle", "ObjectSample", "UnifiedObjectSample", "ObjectNoise", "NormalizePointsColor",
                 "LoadImageFromFile", "LoadMultiViewImageFromFiles"}
@@ -459,16 +634,19 @@ class DevicePipeline:
     """The device-side part of a config's `train_pipeline` / `test_pipeline` list: loading / formatting entries (and the
     ground-truth database sampler, which needs the dataset's files) stay with the host loader and are skipped here."""
 
-    def __init__(self, pipeline_cfg, gt_database=None, object_noise=False):
+    def __init__(self, pipeline_cfg, gt_database=None, object_noise=False, sweeps=False, point_shuffle=False, name_filter=False):
         """gt_database (uni3detr_amd.gtdb.GTDatabase): run ObjectSample / UnifiedObjectSample on the device; object_noise=True: run
-        ObjectNoise on the device.  Without them both stay in `skipped`."""
+        ObjectNoise on the device; sweeps=True: LoadPointsFromMultiSweeps (the batch then needs pack_batch(..., sweeps=...));
+        point_shuffle=True: PointShuffle; name_filter=True: ObjectNameFilter.  Without them these entries stay in `skipped`."""
         self.transforms, self.skipped = [], []
+        opt_in = {"ObjectNoise": object_noise, "LoadPointsFromMultiSweeps": sweeps, "PointShuffle": point_shuffle,
+                  "ObjectNameFilter": name_filter}
         for c in pipeline_cfg:
             if c["type"] in ("ObjectSample", "UnifiedObjectSample") and gt_database is not None:
                 if "db_sampler" not in c:
                     raise KeyError(f"pipeline entry {c['type']!r}: a device GT-paste needs the entry's db_sampler (sample_groups, rate)")
                 self.transforms.append(OBJECT_AUG.build(c, gt_database=gt_database))
-            elif c["type"] == "ObjectNoise" and object_noise:
+            elif opt_in.get(c["type"], False):
                 self.transforms.append(OBJECT_AUG.build(c))
             elif c["type"] in PIPELINES:
                 self.transforms.append(PIPELINES.build(c))
@@ -483,9 +661,11 @@ class DevicePipeline:
         return batch
 
 
-def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_labels_3d=None):
+def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_labels_3d=None, *, sweeps=None):
     """list of per-scene [n_i,F] tensors (+ list of [g_i,7|9] box tensors, + list of label tensors) on one device -> the batch dict
-    the transforms take."""
+    the transforms take.  sweeps: one read_sweeps record per scene (the points are then the key frames): every raw sweep row goes up
+    in one copy from pinned memory, batch["sweeps"] holds the records and the device tables until the merge drops them,
+    batch["sweep_choices"] the choices."""
     dev = points[0].device
     lens = [int(p.shape[0]) for p in points]
     off = torch.tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=dev)
@@ -499,6 +679,9 @@ def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_
         if gt_labels_3d is not None:
             batch["gt_labels_3d"] = (torch.cat([l.to(torch.int32) for l in gt_labels_3d]).contiguous() if sum(gl)
                                      else torch.zeros((0,), dtype=torch.int32, device=dev))
+    if sweeps is not None:
+        batch["sweeps"] = _upload_sweeps(list(sweeps), lens, int(batch["points"].shape[1]), dev)
+        batch["sweep_choices"] = [r["choices"] for r in sweeps]
     return batch
 
 

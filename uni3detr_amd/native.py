@@ -70,6 +70,10 @@ _SIGS = {
     "u3d_points_range_filter": (_I, [_P, _P, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "u3d_point_sample": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "u3d_boxes_range_filter": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P]),
+    "u3d_point_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "u3d_boxes_label_filter": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "u3d_sweeps_merge_workspace": (_L, [_I]),
+    "u3d_sweeps_merge": (_I, [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _I, _P, _L, _P, _L, _P, _P]),
     "u3d_event_create": (_I, [C.POINTER(C.c_void_p)]),
     "u3d_event_record": (_I, [C.c_void_p, _I, _P]),
     "u3d_event_elapsed_ms": (_I, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
@@ -2006,6 +2010,57 @@ def point_sample(points, scene_off, count, num_points, seed, want_idx=False):
     _check(lib().u3d_point_sample(_ptr(points), _ptr(scene_off), _ptr(count), batch, points.shape[1], int(num_points), _ptr(seed), _ptr(out),
                                   _ptr(idx), _stream()), "point_sample")
     return (out, idx) if want_idx else out
+
+
+def point_shuffle(points, scene_off, count, seed):
+    """PointShuffle -> out [N,F]: the first count[b] rows of every scene (count None = the whole segment) permuted by a keyed
+    permutation, every other row copied; seed: device int64/uint64 tensor with one element."""
+    assert points.dtype == torch.float32 and points.is_contiguous() and seed.numel() == 1 and seed.element_size() == 8
+    batch = scene_off.numel() - 1
+    out = torch.empty_like(points)
+    _check(lib().u3d_point_shuffle(_ptr(_nz(points)), _ptr(scene_off), _ptr(count), batch, points.shape[0], points.shape[1], _ptr(seed),
+                                   _ptr(_nz(out)), _stream()), "point_shuffle")
+    return out
+
+
+def boxes_label_filter(boxes, labels, gt_off, gt_count, num_classes):
+    """ObjectNameFilter in place: the live (boxes, labels) of every scene whose label is in [0, num_classes) compacted to the front of
+    its segment -> count int32 [B]."""
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.shape[1] in (7, 9)
+    assert labels.dtype == torch.int32 and labels.is_contiguous()
+    batch = gt_off.numel() - 1
+    count = torch.empty((batch,), dtype=torch.int32, device=boxes.device)
+    _check(lib().u3d_boxes_label_filter(_ptr(boxes), _ptr(labels), _ptr(gt_off), _ptr(gt_count), batch, boxes.shape[1], int(num_classes),
+                                        _ptr(count), _stream()), "boxes_label_filter")
+    return count
+
+
+# --------------------------------------------------------------------------------------------------
+# LoadPointsFromMultiSweeps (csrc/sweeps.hip)
+# --------------------------------------------------------------------------------------------------
+SWEEPS_CHUNK = 256     # U3D_SWEEPS_CHUNK
+SWEEPS_NPARAM = 13     # U3D_SWEEPS_NPARAM: R row-major, t, lag
+SWEEP_SEG_KEY, SWEEP_SEG_SWEEP, SWEEP_SEG_PAD = 0, 1, 2
+
+
+def sweeps_merge(key_points, raw, seg_tab, seg_param, seg_chunk0, scene_chunk0, n_chunks, out_rows, use_dim, remove_close):
+    """-> (out [out_rows, len(use_dim)] f32, scene_off int32 [B+1]): the merged scenes exactly packed, rows past scene_off[-1] spare
+    (the tables: include/u3d_hip.h u3d_sweeps_merge; all on the device, no host sync)."""
+    assert key_points.dtype == torch.float32 and key_points.is_contiguous() and raw.dtype == torch.float32 and raw.is_contiguous()
+    assert seg_param.dtype == torch.float64 and seg_tab.dtype == torch.int32 and seg_chunk0.dtype == torch.int32
+    dev = key_points.device
+    batch, n_seg, load_dim = scene_chunk0.numel() - 1, seg_tab.shape[0], key_points.shape[1]
+    assert raw.numel() == 0 or raw.shape[1] == load_dim
+    use = [int(d) for d in use_dim]
+    out = torch.empty((max(1, int(out_rows)), len(use)), dtype=torch.float32, device=dev)
+    so = torch.empty((batch + 1,), dtype=torch.int32, device=dev)
+    wsb = int(lib().u3d_sweeps_merge_workspace(int(n_chunks)))
+    ws = torch.empty((max(1, wsb),), dtype=torch.uint8, device=dev)
+    _check(lib().u3d_sweeps_merge(_ptr(_nz(key_points)), key_points.shape[0], _ptr(_nz(raw.reshape(-1, load_dim))), raw.shape[0] if raw.numel() else 0,
+                                  load_dim, _ptr(seg_tab), _ptr(seg_param), n_seg, _ptr(seg_chunk0), _ptr(scene_chunk0), batch, int(n_chunks),
+                                  (C.c_int32 * len(use))(*use), len(use), int(bool(remove_close)), _ptr(ws), wsb, _ptr(out), int(out_rows),
+                                  _ptr(so), _stream()), "sweeps_merge")
+    return out[:int(out_rows)], so
 
 
 # --------------------------------------------------------------------------------------------------
