@@ -988,6 +988,28 @@ int32_t u3d_sweeps_merge(const float* key_points, int64_t n_key_rows, const floa
                          int32_t batch, int32_t n_chunks, const int32_t* use_dim, int32_t n_use, int32_t remove_close, void* workspace,
                          int64_t workspace_bytes, float* out, int64_t out_rows, int32_t* out_scene_off, u3d_stream s);
 
+/* The GT-paste object database cropped on the device (mmdet3d create_groundtruth_database / the plugin's
+ * extra_tools/data_converter/create_unified_gt_database.py:85-176 without the image part):
+ * uni3detr_amd/csrc/gtdb.hip.  points [n_rows, feat] f32 (3 <= feat <= 8), scene b = rows scene_off[b] .. scene_off[b+1], of which the
+ * first n_live[b] are live (n_live nullable); boxes [n_boxes, box_dim] f32 bottom-centre (box_dim 7 or 9), scene b owns box rows
+ * box_off[b] .. box_off[b+1] (box_off[batch] == n_boxes); box_valid (nullable) int32 per box row: 0 = the box holds nothing.  Box row j
+ * becomes object j: the live points of its scene strictly inside all six faces (the test of u3d_points_in_boxes, csrc/point_box.h), in
+ * scene order, all feat columns, columns 0-2 minus the box's (x, y, z) in f32; a point inside two boxes goes to both.  No atomics: the
+ * output is the same bytes on every run.  tiles = ceil(max live points of a scene / 256); tile_ws int32 [n_boxes][tiles].
+ *   u3d_gtdb_count  tile_ws[j][t] = points of the scene's 256-point tile t inside box j
+ *   u3d_gtdb_scan   tile_ws in place to its exclusive scan over t, num_points [n_boxes] = the row sums, obj_off [n_boxes + 1] = their
+ *                   exclusive scan, total int64 [1] = their exact sum (device memory: the caller's one read, to size the output)
+ *   u3d_gtdb_crop   out [total, feat]: object j = rows obj_off[j] .. obj_off[j+1]; `total` as read back from u3d_gtdb_scan
+ * max_boxes: an upper bound of the boxes of one scene, known to the host; more than 1024 is U3D_ERR_UNSUPPORTED, and so is
+ * n_boxes * tiles or total above INT32_MAX (the offsets are int32: crop fewer scenes per call) - all checked before any launch. */
+int32_t u3d_gtdb_count(const float* points, int64_t n_rows, const int32_t* scene_off, const int32_t* n_live, int32_t batch, int32_t feat,
+                       int32_t tiles, const float* boxes, int32_t n_boxes, const int32_t* box_off, const int32_t* box_valid, int32_t box_dim,
+                       int32_t max_boxes, int32_t* tile_ws, u3d_stream s);
+int32_t u3d_gtdb_scan(int32_t* tile_ws, int32_t n_boxes, int32_t tiles, int32_t* num_points, int32_t* obj_off, int64_t* total, u3d_stream s);
+int32_t u3d_gtdb_crop(const float* points, int64_t n_rows, const int32_t* scene_off, const int32_t* n_live, int32_t batch, int32_t feat,
+                      int32_t tiles, const float* boxes, int32_t n_boxes, const int32_t* box_off, const int32_t* box_valid, int32_t box_dim,
+                      int32_t max_boxes, const int32_t* tile_ws, const int32_t* obj_off, int64_t total, float* out, u3d_stream s);
+
 #ifdef __cplusplus
 }
 #endif

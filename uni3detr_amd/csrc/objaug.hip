@@ -12,6 +12,7 @@
 // (mmdet3d points_in_rbbox with origin (0.5, 0.5, 0), recalled).  Everything is deterministic and order-preserving.
 #include "common.h"
 #include "box_iou.h"
+#include "point_box.h"
 
 #define OA_T 256            // threads per workgroup of every kernel except k_oa_greedy (one wave)
 #define OA_CAP 1024         // boxes staged in LDS per scene (collision, noise search)
@@ -19,23 +20,6 @@
 
 __device__ __forceinline__ int oa_live(const int32_t* live, const int32_t* off, int b) {
   return live ? live[b] : off[b + 1] - off[b];
-}
-
-// exclusive scan of one int per thread over a 256-thread workgroup; every thread must call it
-__device__ int oa_scan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  int base = 0;
-  for (int i = 0; i < w; ++i) base += sh[i];
-  total = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return base + x - v;
 }
 
 // stats = [n_live[B] | g_live[B] | hist[B][C]]: live points, live GT rows, GT rows per class label in [0, C)
@@ -153,18 +137,14 @@ __global__ void __launch_bounds__(OA_T) k_oa_mask(const float* pts, const int32_
     for (int j = threadIdx.x; j < nc; j += OA_T) {
       const float* r = boxes + (long long)(q0 + c0 + j) * dim;
       const bool on = !box_active || box_active[q0 + c0 + j];
-      bs[j][0] = r[0]; bs[j][1] = r[1]; bs[j][2] = r[2];
-      bs[j][3] = on ? 0.5f * r[3] : -1.f;          // an inactive box holds nothing
-      bs[j][4] = 0.5f * r[4]; bs[j][5] = r[5]; bs[j][6] = cosf(r[6]); bs[j][7] = sinf(r[6]);
+      pb_stage(bs[j], r, on);
     }
     __syncthreads();
     if (!valid) continue;
     for (int w0 = 0; w0 < nc; w0 += 32) {
       uint32_t m = 0;
       for (int j = w0; j < min(nc, w0 + 32); ++j) {
-        const float dx = px - bs[j][0], dy = py - bs[j][1];
-        const float lx = dx * bs[j][6] + dy * bs[j][7], ly = -dx * bs[j][7] + dy * bs[j][6];
-        if (fabsf(lx) < bs[j][3] && fabsf(ly) < bs[j][4] && pz > bs[j][2] && pz < bs[j][2] + bs[j][5]) m |= 1u << (j - w0);
+        if (pb_inside(px, py, pz, bs[j])) m |= 1u << (j - w0);
       }
       if (m && fst < 0) fst = c0 + w0 + __builtin_ctz(m);
       if (bits) bits[row * words + ((c0 + w0) >> 5)] = m;
@@ -173,7 +153,7 @@ __global__ void __launch_bounds__(OA_T) k_oa_mask(const float* pts, const int32_
   if (valid) first[row] = fst;
   if (tile_free) {
     int tot;
-    oa_scan(valid && fst < 0 ? 1 : 0, sh, tot);
+    pb_scan256(valid && fst < 0 ? 1 : 0, sh, tot);
     if (threadIdx.x == 0) tile_free[b * tiles + t] = tot;
   }
 }
@@ -191,21 +171,21 @@ __global__ void __launch_bounds__(OA_T) k_oa_layout(int batch, int tiles, const 
     int kept = 0, paste = 0, nacc = 0, tot;
     for (int c = 0; c < tiles; c += OA_T) {
       const int t = c + threadIdx.x;
-      oa_scan(t < tiles ? tile_free[b * tiles + t] : 0, sh, tot);
+      pb_scan256(t < tiles ? tile_free[b * tiles + t] : 0, sh, tot);
       kept += tot;
     }
     for (int c = 0; c < nk; c += OA_T) {
       const int k = c + threadIdx.x;
       const bool a = k < nk && acc[k0 + k];
       const int id = a ? cand_ids[k0 + k] : 0;
-      oa_scan(a ? db_obj_off[id + 1] - db_obj_off[id] : 0, sh, tot);
+      pb_scan256(a ? db_obj_off[id + 1] - db_obj_off[id] : 0, sh, tot);
       paste += tot;
     }
     const int kbase = pbase + (sampled_first ? paste : 0), sbase = pbase + (sampled_first ? 0 : kept);
     int run = 0;
     for (int c = 0; c < tiles; c += OA_T) {
       const int t = c + threadIdx.x;
-      const int e = oa_scan(t < tiles ? tile_free[b * tiles + t] : 0, sh, tot);
+      const int e = pb_scan256(t < tiles ? tile_free[b * tiles + t] : 0, sh, tot);
       if (t < tiles) tile_base[b * tiles + t] = kbase + run + e;
       run += tot;
     }
@@ -216,9 +196,9 @@ __global__ void __launch_bounds__(OA_T) k_oa_layout(int batch, int tiles, const 
       const int k = c + threadIdx.x;
       const bool a = k < nk && acc[k0 + k];
       const int id = a ? cand_ids[k0 + k] : 0;
-      const int e = oa_scan(a ? db_obj_off[id + 1] - db_obj_off[id] : 0, sh, tot);
+      const int e = pb_scan256(a ? db_obj_off[id + 1] - db_obj_off[id] : 0, sh, tot);
       int atot;
-      const int ae = oa_scan(a ? 1 : 0, sh, atot);
+      const int ae = pb_scan256(a ? 1 : 0, sh, atot);
       if (k < nk) {
         cand_base[k0 + k] = a ? sbase + run + e : -1;
         cand_row[k0 + k] = a ? gbase + gl + arun + ae : -1;
@@ -241,7 +221,7 @@ __global__ void __launch_bounds__(OA_T) k_oa_scatter_kept(const float* pts, cons
   const long long row = (long long)scene_off[b] + i;
   const bool keep = i < n_live[b] && first[row] < 0;
   int tot;
-  const int r = oa_scan(keep ? 1 : 0, sh, tot);
+  const int r = pb_scan256(keep ? 1 : 0, sh, tot);
   if (!keep) return;
   const long long o = (long long)tile_base[b * tiles + t] + r;
   for (int f = 0; f < feat; ++f) out[o * feat + f] = pts[row * feat + f];

@@ -233,6 +233,9 @@ _SIGS = {
     "u3d_objaug_paste": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P,
                               _P, _P, _P, _P, _P, _P]),
     "u3d_object_noise": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "u3d_gtdb_count": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
+    "u3d_gtdb_scan": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "u3d_gtdb_crop": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _L, _P, _P]),
 }
 
 
@@ -2114,6 +2117,45 @@ def points_in_boxes(points, scene_off, n_live, max_rows, boxes, box_off, box_liv
                                      _ptr(box_off), _ptr(box_live), _ptr(box_active), boxes.shape[1], words, _ptr(first), _ptr(bits),
                                      _ptr(tile_free), _stream()), "points_in_boxes")
     return first, bits, tile_free
+
+
+GTDB_MAX_BOXES = 1024  # boxes of one scene u3d_gtdb_count / u3d_gtdb_crop take
+
+
+def gtdb_crop(points, scene_off, n_live, max_rows, boxes, box_off, box_valid=None, max_boxes=None):
+    """Every box row becomes one database object (csrc/gtdb.hip): -> (obj_points [P, F] f32, obj_off int32 [D+1], num_points int32 [D]),
+    object d = the live points of its scene strictly inside box d, in scene order, columns 0-2 relative to the box's (x, y, z_bottom).
+    box_valid (int32 per box row, optional): 0 = an empty object.  max_boxes: an upper bound of the boxes of one scene if the caller
+    knows one (default: all D rows; more than 1024 is an error).  Three entry points, four launches and ONE host read (the total, to
+    size the output), whatever the number of scenes and boxes."""
+    assert points.dtype == torch.float32 and points.is_contiguous() and boxes.dtype == torch.float32 and boxes.is_contiguous()
+    assert boxes.shape[1] in (7, 9) and scene_off.dtype == torch.int32 and box_off.dtype == torch.int32
+    batch, dev, feat, D = scene_off.numel() - 1, points.device, points.shape[1], boxes.shape[0]
+    assert box_off.numel() == batch + 1 and (box_valid is None or (box_valid.dtype == torch.int32 and box_valid.numel() == D))
+    tiles = _tiles(max_rows)
+    mb = D if max_boxes is None else int(max_boxes)
+    tile_ws = torch.empty((max(1, D * tiles),), dtype=torch.int32, device=dev)
+    num = torch.empty((D,), dtype=torch.int32, device=dev)
+    off = torch.empty((D + 1,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int64, device=dev)
+    geom = (_ptr(_nz(points)), points.shape[0], _ptr(scene_off), _ptr(n_live), batch, feat, tiles, _ptr(_nz(boxes)), D, _ptr(box_off),
+            _ptr(box_valid), boxes.shape[1], mb)
+    t = TIMER
+    e = t.begin() if t is not None else None
+    _check(lib().u3d_gtdb_count(*geom, _ptr(tile_ws), _stream()), "gtdb_count")
+    if t is not None:
+        t.end("gtdb_count", e)
+        e = t.begin()
+    _check(lib().u3d_gtdb_scan(_ptr(tile_ws), D, tiles, _ptr(_nz(num)), _ptr(off), _ptr(total), _stream()), "gtdb_scan")
+    if t is not None:
+        t.end("gtdb_scan", e)
+    n_out = int(total.item())                                  # the one host read
+    out = torch.empty((n_out, feat), dtype=torch.float32, device=dev) if n_out < 2 ** 31 else None   # else: u3d_gtdb_crop refuses the total
+    e = t.begin() if t is not None else None
+    _check(lib().u3d_gtdb_crop(*geom, _ptr(tile_ws), _ptr(off), n_out, _ptr(_nz(out)) if out is not None else None, _stream()), "gtdb_crop")
+    if t is not None:
+        t.end("gtdb_crop", e)
+    return out, off, num
 
 
 def objaug_paste(points, scene_off, n_live, max_rows, gt, labels, gt_off, g_live, db_points, db_obj_off, db_boxes, db_labels, cand_ids,

@@ -307,3 +307,52 @@ def nusc_samples(n, preds_per_sample=60, seed=0, class_names=None, max_gt=30, mi
         results.append(dict(boxes_3d=np.asarray(boxes, np.float32).reshape(-1, 9)[perm], scores_3d=scores.astype(np.float32)[perm],
                             labels_3d=np.asarray(labels, np.int64)[perm]))
     return infos, results
+
+
+def gtdb_scenes(kind, n, seed=0):
+    """Seeded scenes shaped like what the GT-paste database builder crops, as the dicts gtdb.create_groundtruth_database takes.
+    kind 'nuscenes': a 10-sweep cloud already merged (250-300 k points, 5 columns: x, y, z, intensity, time lag), about 35 boxes of 9
+    columns over the ten classes, a valid flag; kind 'kitti': about 120 k points of 4 columns, about 10 boxes of 7 columns, difficulty.
+    Ground points on a ring pattern plus a cluster of points on every box, so that objects hold from a handful to a few thousand."""
+    rng = np.random.default_rng(seed)
+    nusc = kind == "nuscenes"
+    if kind not in ("nuscenes", "kitti"):
+        raise ValueError(f"kind {kind!r} (nuscenes or kitti)")
+    objects = _NUSC_OBJECTS if nusc else tuple(o for o in _KITTI_OBJECTS if o[0] != "DontCare")
+    prob = np.array([o[4] for o in objects])
+    out = []
+    for s in range(n):
+        g = int(rng.integers(25, 46)) if nusc else int(rng.integers(5, 16))
+        kinds = rng.choice(len(objects), g, p=prob / prob.sum())
+        boxes = np.zeros((g, 9 if nusc else 7), np.float32)
+        r, a = rng.uniform(4, 50 if nusc else 60, g), rng.uniform(-np.pi, np.pi, g) if nusc else rng.uniform(-0.6, 0.6, g)
+        boxes[:, 0], boxes[:, 1], boxes[:, 2] = r * np.cos(a), r * np.sin(a), rng.normal(-1.8, 0.15, g)
+        for j, k in enumerate(kinds):
+            o = objects[k]
+            boxes[j, 3:6] = np.array((o[1], o[2], o[3]) if nusc else (o[1], o[3], o[2])) * rng.uniform(0.9, 1.1, 3)
+        boxes[:, 6] = rng.uniform(-np.pi, np.pi, g)
+        if nusc:
+            boxes[:, 7:] = rng.normal(0, 2, (g, 2))
+        npts = int(rng.integers(250_000, 300_001)) if nusc else int(rng.integers(110_000, 130_001))
+        feat = 5 if nusc else 4
+        rr = rng.gamma(2.0, 9.0, npts) + 1.5
+        aa = rng.uniform(-np.pi, np.pi, npts) if nusc else rng.uniform(-0.8, 0.8, npts)
+        pts = np.zeros((npts, feat), np.float32)
+        pts[:, 0], pts[:, 1], pts[:, 2], pts[:, 3] = rr * np.cos(aa), rr * np.sin(aa), rng.normal(-1.8, 0.1, npts), rng.uniform(0, 1, npts)
+        if nusc:
+            pts[:, 4] = rng.integers(0, 11, npts) * np.float32(0.05)
+        on = rng.integers(0, g, npts // 20)                       # a twentieth of the cloud sits on the objects, fewer far away
+        on = on[rng.uniform(0, 1, len(on)) < np.minimum(1.0, 12.0 / r[on])]
+        q = rng.uniform(-0.5, 0.5, (len(on), 3)) * boxes[on, 3:6] + np.array([0, 0, 0.5]) * boxes[on, 3:6]
+        c, sn = np.cos(boxes[on, 6]), np.sin(boxes[on, 6])
+        pts[:len(on), 0] = q[:, 0] * c - q[:, 1] * sn + boxes[on, 0]
+        pts[:len(on), 1] = q[:, 0] * sn + q[:, 1] * c + boxes[on, 1]
+        pts[:len(on), 2] = q[:, 2] + boxes[on, 2]
+        pts = pts[rng.permutation(npts)]
+        sc = dict(sample_idx=f"{s:06d}" if nusc else s, points=pts, gt_bboxes_3d=boxes, gt_names=np.array([objects[k][0] for k in kinds]))
+        if nusc:
+            sc["valid_flag"] = rng.uniform(0, 1, g) < 0.9
+        else:
+            sc["difficulty"] = rng.integers(-1, 3, g).astype(np.int32)
+        out.append(sc)
+    return out
