@@ -108,7 +108,8 @@ int32_t u3d_dense_nbr_table(int32_t batch, const int32_t q_dims[3], const int32_
  * hard mode + HardSimpleVFE).  Sequential semantics reproduced exactly: voxels in
  * first-appearance point order, first `max_points` points per voxel in point order, at most `max_voxels`
  * voxels per scene.
- *   points      f32 [n_total, nfeat], scenes concatenated; scene_off int32 [B+1] (device)
+ *   points      f32 [n_total, nfeat], scenes concatenated; scene_off int32 [B+1] (device).  n_total and max_pts_per_scene are
+ *               upper bounds: rows at or past scene_off[B] (read on the device) are spare capacity and never become points
  *   voxel_size/pc_range: host arrays (x,y,z) / (x0,y0,z0,x1,y1,z1)
  *   outputs (capacity B*max_voxels rows, scene-major, compacted):
  *     voxels  f32 [cap, max_points, nfeat] or NULL, coors int32 [cap,4] (b,z,y,x), num_points int32 [cap],
@@ -906,6 +907,21 @@ int32_t u3d_point_shuffle(const float* points, const int32_t* scene_off, const i
  * (count must not alias gt_count). */
 int32_t u3d_boxes_label_filter(float* boxes, int32_t* labels, const int32_t* gt_off, const int32_t* gt_count, int32_t batch, int32_t box_dim,
                                int32_t num_classes, int32_t* count, u3d_stream s);
+
+/* Batch ingest (uni3detr_amd/csrc/ingest.hip): a packed pipeline batch -> the static input buffers of a capacity-mode training step,
+ * two launches, no allocation, no synchronisation (capturable).  In: points f32 [n_src, feat], scene_off int32 [batch + 1], count
+ * int32 [batch] (nullable: live prefix of every segment); gt f32 [g_src, box_dim] bottom-centre (nullable / g_src 0: no boxes),
+ * gt_labels int32 [g_src], gt_off int32 [batch + 1], gt_count (nullable).  Out (caller-owned, addresses kept): cat f32
+ * [batch * point_cap, feat] exactly packed - scene b = rows dst_off[b] .. dst_off[b + 1], live rows only, order kept, rows past
+ * dst_off[batch] untouched - and dst_off int32 [batch + 1]; gt_out f32 [batch * gt_cap, gt_dim] (gravity centre z + dz / 2, gt_dim 7 or
+ * 9: a 7-column input gets zero velocities, a 9-column input is cut to 7), labels_out int32, gt_off_out int32 [batch + 1] (the three
+ * nullable together).  A scene with more than point_cap live rows or more than gt_cap live boxes is cut to the capacity; then
+ * flag[0] (one device float) is incremented by 1 and overflow (nullable int32 [2]) counts the call: [0] points, [1] boxes.
+ * 16-byte copies when feat % 4 == 0 and both point buffers are 16-byte aligned; batch <= 4096. */
+int32_t u3d_batch_ingest(const float* points, int32_t n_src, int32_t feat, const int32_t* scene_off, const int32_t* count, int32_t batch,
+                         int32_t point_cap, const float* gt, int32_t g_src, int32_t box_dim, const int32_t* gt_labels, const int32_t* gt_off,
+                         const int32_t* gt_count, int32_t gt_cap, int32_t gt_dim, float* cat, int32_t* dst_off, float* gt_out,
+                         int32_t* labels_out, int32_t* gt_off_out, float* flag, int32_t* overflow, u3d_stream s);
 
 /* GT-paste (mmdet3d ObjectSample / the plugin's UnifiedObjectSample, ref: projects/mmdet3d_plugin/datasets/pipelines/dbsampler.py,
  * transform_3d.py:591-786) and ObjectNoise (global_rot_range = 0) on a packed batch: uni3detr_amd/csrc/objaug.hip.  The random draws

@@ -448,6 +448,8 @@ __global__ void k_vox_insert(const float* __restrict__ pts, const int* __restric
                              int* __restrict__ next, int* __restrict__ slot_of) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_total) return;
+  // n_total is an upper bound (capacity-sized buffers): a row at or past scene_off[B] is spare capacity, not a point of the last scene
+  if (i >= scene_off[B]) { slot_of[i] = -1; next[i] = -1; return; }
   // scene of point i (B small: linear search)
   int b = 0;
   while (b + 1 < B && i >= scene_off[b + 1]) ++b;
@@ -529,7 +531,7 @@ __global__ void k_vox_write(const float* __restrict__ pts, const int* __restrict
                             const int* __restrict__ voxel_off, float* __restrict__ voxels, int4* __restrict__ coors,
                             int* __restrict__ num_points, float* __restrict__ mean) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_total) return;
+  if (i >= n_total || i >= scene_off[B]) return;
   int sl = slot_of[i];
   if (sl < 0) return;
   int b = 0;

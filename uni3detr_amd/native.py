@@ -72,6 +72,7 @@ _SIGS = {
     "u3d_boxes_range_filter": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P]),
     "u3d_point_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "u3d_boxes_label_filter": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "u3d_batch_ingest": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "u3d_sweeps_merge_workspace": (_L, [_I]),
     "u3d_sweeps_merge": (_I, [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _I, _P, _L, _P, _L, _P, _P]),
     "u3d_event_create": (_I, [C.POINTER(C.c_void_p)]),
@@ -2036,6 +2037,39 @@ def boxes_label_filter(boxes, labels, gt_off, gt_count, num_classes):
     _check(lib().u3d_boxes_label_filter(_ptr(boxes), _ptr(labels), _ptr(gt_off), _ptr(gt_count), batch, boxes.shape[1], int(num_classes),
                                         _ptr(count), _stream()), "boxes_label_filter")
     return count
+
+
+# --------------------------------------------------------------------------------------------------
+# batch ingest (csrc/ingest.hip)
+# --------------------------------------------------------------------------------------------------
+def batch_ingest(points, scene_off, count, point_cap, cat, dst_off, flag, gt=None, gt_labels=None, gt_off=None, gt_count=None, gt_cap=0,
+                 gt_out=None, labels_out=None, gt_off_out=None, overflow=None):
+    """A packed pipeline batch -> the caller's static buffers (u3d_batch_ingest; two launches on the current stream, no allocation, no
+    host read).  points f32 [n_src, F], scene_off int32 [B+1], count int32 [B] | None -> cat f32 [B*point_cap, F] exactly packed +
+    dst_off int32 [B+1]; gt f32 [g_src, 7|9] bottom-centre, gt_labels int32, gt_off, gt_count | None -> gt_out f32 [B*gt_cap, 7|9]
+    gravity-centre, labels_out int32 [B*gt_cap], gt_off_out int32 [B+1] (gt None / empty with gt_out given: gt_off_out <- zeros).
+    flag: one device float, += 1 when a scene was cut to a capacity; overflow: int32 [2] | None, += (points cut, boxes cut)."""
+    B = scene_off.numel() - 1
+    F_ = points.shape[1]
+    assert points.dtype == torch.float32 and cat.dtype == torch.float32 and points.is_contiguous() and cat.shape == (B * point_cap, F_)
+    assert scene_off.dtype == torch.int32 and dst_off.dtype == torch.int32 and dst_off.numel() == B + 1
+    assert count is None or (count.dtype == torch.int32 and count.numel() == B)
+    assert flag.dtype == torch.float32 and flag.numel() == 1 and (overflow is None or (overflow.dtype == torch.int32 and overflow.numel() == 2))
+    g_src = sd = gd = 0
+    if gt_out is not None:
+        gd = gt_out.shape[1]
+        assert gt_out.dtype == torch.float32 and gt_out.shape[0] == B * gt_cap and labels_out.dtype == torch.int32
+        assert labels_out.numel() == B * gt_cap and gt_off_out.dtype == torch.int32 and gt_off_out.numel() == B + 1
+    if gt is not None and gt.shape[0] > 0:
+        g_src, sd = gt.shape
+        assert gt_out is not None and gt.dtype == torch.float32 and gt.is_contiguous() and gt_labels.dtype == torch.int32
+        assert gt_labels.numel() == g_src and gt_off.dtype == torch.int32 and gt_off.numel() == B + 1
+        assert gt_count is None or (gt_count.dtype == torch.int32 and gt_count.numel() == B)
+    else:
+        gt = gt_labels = gt_off = gt_count = None
+    _check(lib().u3d_batch_ingest(_ptr(points) if points.numel() else None, points.shape[0], F_, _ptr(scene_off), _ptr(count), B, int(point_cap), _ptr(gt), g_src, sd,
+                                  _ptr(gt_labels), _ptr(gt_off), _ptr(gt_count), int(gt_cap), gd, _ptr(cat), _ptr(dst_off), _ptr(gt_out),
+                                  _ptr(labels_out), _ptr(gt_off_out), _ptr(flag), _ptr(overflow), _stream()), "batch_ingest")
 
 
 # --------------------------------------------------------------------------------------------------

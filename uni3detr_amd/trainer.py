@@ -18,7 +18,11 @@ the job-wide value) and G3's update is held when it is set (u3d_adamw_step_hold)
 ranks cannot diverge.  Every `check_every` steps the host reads the held-step counter (identical on all ranks) and re-captures with more
 room: on one rank directly; with a live process group through `pg_hooks` (tear the group down, capture, create it again - capture and
 RCCL do not mix on this stack), or it raises on ALL ranks when no hooks were given.
+The point buffer is a capacity too when the step is built with `point_capacity=P` (scenes of differing size, e.g. a pipeline without
+PointSample): set_packed_batch() fills the static buffers from a DevicePipeline batch on the device (u3d_batch_ingest), a scene above
+the capacity is cut and raises the same HOLD flag.
 """
+import math
 import os
 
 import torch
@@ -33,12 +37,45 @@ class FpsTimeout(RuntimeError):
     """check_capacities(): the step's FPS launch did not finish (the caller re-captures with the single-workgroup FPS)."""
 
 
+def plan_point_capacity(scene_sizes, margin=1.25, multiple=1024):
+    """Per-scene point capacity `P` for TrainStep(point_capacity=P) from observed scene sizes (ints, or one list of ints per batch):
+    the largest size times `margin`, rounded up to a multiple of `multiple` (at least one multiple).  Pure host arithmetic."""
+    sizes = []
+    for s in scene_sizes:
+        sizes.extend(int(v) for v in s) if isinstance(s, (list, tuple)) else sizes.append(int(s))
+    if not sizes or min(sizes) < 0:
+        raise ValueError("plan_point_capacity: needs at least one scene size, none negative")
+    if margin < 1.0 or int(multiple) < 1:
+        raise ValueError("plan_point_capacity: margin >= 1 and multiple >= 1")
+    multiple = int(multiple)
+    need = max(1, math.ceil(max(sizes) * float(margin)))
+    return (need + multiple - 1) // multiple * multiple
+
+
 class TrainStep:
     def __init__(self, model, points, gt_bboxes_3d, gt_labels_3d, lr=1e-4, weight_decay=0.01, max_norm=10.0, graph=True,
                  capacity_margin=1.25, flat_update=True, overlap_reduce=False, betas=(0.9, 0.999), eps=1e-8, gt_capacity=64,
-                 check_every=50, pg_hooks=None, fps_graph=None, grad_comm_dtype=torch.float32, reduce_buckets=None):
+                 check_every=50, pg_hooks=None, fps_graph=None, grad_comm_dtype=torch.float32, reduce_buckets=None, point_capacity=None):
         """pg_hooks: (teardown, setup) callables that destroy / re-create the default process group; needed only for a collective
-        re-capture after a capacity overflow on a multi-rank run (bench.py passes them)."""
+        re-capture after a capacity overflow on a multi-rank run (bench.py passes them).
+        point_capacity: None - the static point buffer has exactly the initial batch's layout (set_batch takes that layout only).  An
+        int P - capacity mode: the buffer holds B * P rows, every scene may have any number of points up to P, and
+        set_packed_batch() fills the buffers from a DevicePipeline batch on the device (hard voxelization, flat_update=True)."""
+        if point_capacity is not None:
+            point_capacity = int(point_capacity)
+            if getattr(model, "dynamic_voxelization", False):
+                raise NotImplementedError("TrainStep(point_capacity=...): capacity mode serves hard voxelization only; this model has "
+                                          "dynamic_voxelization=True (end its pipeline in PointSample and use the fixed layout)")
+            if not flat_update:
+                raise NotImplementedError("TrainStep(point_capacity=...) needs flat_update=True: a scene cut to the capacity is kept from "
+                                          "training by the device-side hold of the flat AdamW step")
+            if isinstance(points, dict) or isinstance(gt_bboxes_3d, dict):
+                raise TypeError("TrainStep(point_capacity=...): the initial batch is given as lists (points, boxes, labels) - "
+                                "datapath.unpack_batch(batch) makes them from a packed batch")
+            if point_capacity < 1 or point_capacity < max(int(p.shape[0]) for p in points):
+                raise ValueError(f"point_capacity {point_capacity} is smaller than the largest scene of the initial batch "
+                                 f"({max(int(p.shape[0]) for p in points)} points)")
+        self.point_capacity = point_capacity
         self.model = model
         # gradient exchange dtype (N > 1): float32 (default: the all-reduced gradient is the exact mean) or bfloat16 - half the xGMI
         # bytes (63 instead of 127 MB per step), the mean rounded to 8 mantissa bits per hop of the ring (what torch's bf16 DDP
@@ -132,15 +169,106 @@ class TrainStep:
             self.set_hyper()
         else:
             self.opt = torch.optim.AdamW(self.params, lr=lr, betas=self.betas, eps=eps, weight_decay=weight_decay, fused=True, capturable=graph)
-        self.pts = model.pack_points(points) if not isinstance(points, dict) else points
         self.gt_capacity = gt_capacity
-        self.gts = self._pack_gts_static(gt_bboxes_3d, gt_labels_3d) if not isinstance(gt_bboxes_3d, dict) else gt_bboxes_3d
+        if point_capacity is None:
+            self.pts = model.pack_points(points) if not isinstance(points, dict) else points
+            self.gts = self._pack_gts_static(gt_bboxes_3d, gt_labels_3d) if not isinstance(gt_bboxes_3d, dict) else gt_bboxes_3d
+        else:
+            self._alloc_capacity_buffers(points, gt_bboxes_3d)
+            self.set_batch(points, gt_bboxes_3d, gt_labels_3d)
         self.labels = gt_labels_3d
         self.capacity_margin = capacity_margin
         self._graphs = None
         self.loss = None
 
     # ---- batches --------------------------------------------------------------------------------------------------------
+    def _alloc_capacity_buffers(self, points, gt_bboxes_3d):
+        """Capacity mode: `cat` holds B * P rows of which scene_off[B] are live (the detector and its kernels take `lens` = [P] * B as
+        upper bounds and read the real extents from scene_off on the device), the GT buffers B * G rows as in _pack_gts_static.  One
+        spare row behind `cat`: an empty LAST scene makes the FPS gather read the row at scene_off[B] (its value cannot matter: all
+        samples of an empty set are that one row, the unit-cube map of a single point is 0 / 0)."""
+        B, P, F_ = len(points), self.point_capacity, int(points[0].shape[1])
+        G = max(int(self.gt_capacity), max((int(g.tensor.shape[0] if hasattr(g, "tensor") else g.shape[0]) for g in gt_bboxes_3d), default=0), 1)
+        gd = int(self.model.pts_bbox_head.gt_dim)
+        dev = self.dev
+        self.pts = dict(cat=torch.zeros((B * P + 1, F_), dtype=torch.float32, device=dev)[:B * P],
+                        scene_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), lens=[P] * B)
+        self.gts = dict(gt=torch.zeros((B * G, gd), dtype=torch.float32, device=dev), labels=torch.zeros(B * G, dtype=torch.int32, device=dev),
+                        gt_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), gmax=G)
+        # [0]: the bound batch had a scene cut to P or G (ORed into the step's HOLD flag, _stage1_head); counters: calls of
+        # set_packed_batch that cut (points, boxes), read with the held-step counter
+        self._ingest_flag = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._ingest_over = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def set_packed_batch(self, batch):
+        """Capacity mode: load the batch dict a DevicePipeline returns (points, scene_off[, count], gt_bboxes_3d, gt_off[, gt_count],
+        gt_labels_3d) INTO the static buffers with u3d_batch_ingest on the current stream - no device-to-host copy, no host
+        synchronisation.  The host checks what it knows without a read (scene count, columns, dtypes, devices); what only the device
+        knows is handled there: a scene above the point capacity or above `gmax` boxes is cut to it and the step's update is held
+        (ingest_overflows() counts such batches; step() raises at its periodic check)."""
+        if self.point_capacity is None:
+            raise RuntimeError("set_packed_batch needs a TrainStep built with point_capacity=P (capacity mode)")
+        if "sweeps" in batch:
+            raise ValueError("set_packed_batch: the batch still carries batch['sweeps'] - run the pipeline's LoadPointsFromMultiSweeps first")
+        pts, off = batch["points"], batch["scene_off"]
+        cat, B = self.pts["cat"], len(self.pts["lens"])
+
+        def dev_ok(t):
+            return t is None or (torch.is_tensor(t) and t.device == cat.device)
+
+        def i32(t, n, what):
+            if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
+                raise ValueError(f"set_packed_batch: {what} must be a contiguous int32 tensor of {n} elements")
+
+        g, lab, go = batch.get("gt_bboxes_3d"), batch.get("gt_labels_3d"), batch.get("gt_off")
+        cnt, gc = batch.get("count"), batch.get("gt_count")
+        if not all(dev_ok(t) for t in (pts, off, cnt, g, lab, go, gc)):
+            raise ValueError(f"set_packed_batch: every tensor of the batch must live on {cat.device}")
+        if pts.dim() != 2 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[1] != cat.shape[1]:
+            raise ValueError(f"set_packed_batch: points must be contiguous float32 [n, {cat.shape[1]}], got {pts.dtype} {tuple(pts.shape)}")
+        if off.numel() != B + 1:
+            raise ValueError(f"set_packed_batch: {off.numel() - 1} scenes, the step was built for {B}")
+        i32(off, B + 1, "scene_off"); i32(cnt, B, "count")
+        if g is not None:
+            if g.dim() != 2 or g.dtype != torch.float32 or not g.is_contiguous() or g.shape[1] not in (7, 9):
+                raise ValueError(f"set_packed_batch: gt_bboxes_3d must be contiguous float32 [g, 7 | 9], got {g.dtype} {tuple(g.shape)}")
+            if lab is None or go is None:
+                raise ValueError("set_packed_batch: gt_bboxes_3d needs gt_labels_3d and gt_off")
+            i32(lab, g.shape[0], "gt_labels_3d"); i32(go, B + 1, "gt_off"); i32(gc, B, "gt_count")
+        self._ingest_flag.zero_()
+        nv.batch_ingest(pts, off, cnt, self.point_capacity, cat, self.pts["scene_off"], self._ingest_flag, gt=g, gt_labels=lab, gt_off=go,
+                        gt_count=gc, gt_cap=int(self.gts["gmax"]), gt_out=self.gts["gt"], labels_out=self.gts["labels"],
+                        gt_off_out=self.gts["gt_off"], overflow=self._ingest_over)
+
+    def _set_batch_capacity(self, points, gt_bboxes_3d, gt_labels_3d):
+        """set_batch in capacity mode for lists of tensors: the sizes are known on the host, so nothing is cut - a scene above the
+        point capacity or above gmax raises before anything is written."""
+        P, B = self.point_capacity, len(self.pts["lens"])
+        if len(points) != B or len(gt_bboxes_3d) != B:
+            raise ValueError(f"set_batch: {len(points)} scenes, the step was built for {B}")
+        lens = [int(p.shape[0]) for p in points]
+        if max(lens) > P:
+            raise ValueError(f"set_batch: a scene of {max(lens)} points exceeds point_capacity {P}")
+        if any(int(p.shape[1]) != self.pts["cat"].shape[1] for p in points):
+            raise ValueError(f"set_batch: points must have {self.pts['cat'].shape[1]} columns")
+        d = self.model.pts_bbox_head.pack_gts(gt_bboxes_3d, gt_labels_3d, self.dev)
+        if int(d["gmax"]) > int(self.gts["gmax"]):
+            raise ValueError(f"set_batch: {int(d['gmax'])} boxes in one scene exceed the capacity {int(self.gts['gmax'])}")
+        pts = self.model.pack_points(points)
+        n, g = sum(lens), d["gt"].shape[0]
+        self.pts["cat"][:n].copy_(pts["cat"])
+        self.pts["scene_off"].copy_(pts["scene_off"])
+        self.gts["gt"][:g].copy_(d["gt"])
+        self.gts["labels"][:g].copy_(d["labels"])
+        self.gts["gt_off"].copy_(d["gt_off"])
+        self._ingest_flag.zero_()
+
+    def ingest_overflows(self):
+        """Batches set_packed_batch had to cut (a scene above point_capacity, or above gmax boxes) since the last check; their steps
+        were held.  One small device-to-host read, made where held_steps() is read."""
+        if self.point_capacity is None:
+            return 0
+        return int(self._ingest_over.sum().item())
     def _pack_gts_static(self, gt_bboxes_3d, gt_labels_3d):
         """GT buffers with a fixed per-scene capacity (`gt_capacity` boxes): the captured graphs size the cost matrix by the capacity
         and read the real per-scene counts from the device-side `gt_off`, so the next batch may hold any number of boxes up to it."""
@@ -158,7 +286,10 @@ class TrainStep:
         """Load the next batch INTO the static input buffers the captured graphs read (device-to-device copies on the current
         stream; ref: the runner's data loader feeding train_step, extra_tools/train.py:204-254).  Shapes the graphs were captured
         with must hold: same number of scenes, the same number of points per scene, at most `gmax` boxes per scene - anything else
-        raises (build a new TrainStep / call capture() again for a different shape)."""
+        raises (build a new TrainStep / call capture() again for a different shape).  Capacity mode (point_capacity=P): lists of
+        tensors of any per-scene size up to P; beyond P or gmax raises ValueError before anything is written."""
+        if self.point_capacity is not None and not isinstance(points, dict):
+            return self._set_batch_capacity(points, gt_bboxes_3d, gt_labels_3d)
         pts = self.model.pack_points(points) if not isinstance(points, dict) else points
         if list(pts["lens"]) != list(self.pts["lens"]) or pts["cat"].shape != self.pts["cat"].shape:
             raise ValueError(f"set_batch: points per scene {list(pts['lens'])} differ from the captured layout {list(self.pts['lens'])}")
@@ -248,6 +379,8 @@ class TrainStep:
             nv.capacity_flag(cnts, cps, self._msg[L:])
         else:
             self._msg[L:].zero_()
+        if self.point_capacity is not None:
+            self._msg[L:].add_(self._ingest_flag)                # the bound batch was cut to the point / GT capacity: hold, as above
         self._num_pos = self._msg[:L]
 
     def _fps_can_time_out(self):
@@ -578,7 +711,8 @@ class TrainStep:
     # ---- capture ------------------------------------------------------------------------------------------------
     def measure_capacities(self, batches=None):
         """Run exact-size eager steps (the bound batch, or every batch of `batches`) and size the strided sparse levels from the
-        largest counts seen (x margin, multiple of 256)."""
+        largest counts seen (x margin, multiple of 256).  An entry of `batches` is a (points, gts, labels) triple or, in capacity mode,
+        a packed batch dict as set_packed_batch takes it."""
         m = self.model
         m.static_shapes = False
         m.pts_middle_encoder.level_capacities = None
@@ -587,7 +721,9 @@ class TrainStep:
             vfe.capacity = None
         counts = None
         for b in (batches if batches else [None]):
-            if b is not None:
+            if isinstance(b, dict):
+                self.set_packed_batch(b)
+            elif b is not None:
                 self.set_batch(*b)
             self.eager_step()
             c = [int(c.item()) for c in m.pts_middle_encoder.last_level_counts]
@@ -619,7 +755,7 @@ class TrainStep:
         return counts
 
     def capture(self, warmup=3, keep_state=True, batches=None, remember_batches=True):
-        """Measure the sparse-level capacities (over `batches`, a list of (points, gts, labels), when given), warm up, capture.
+        """Measure the sparse-level capacities (over `batches`, a list of (points, gts, labels) or packed batch dicts, when given), warm up, capture.
         keep_state: weights, BatchNorm statistics and optimizer state are restored afterwards - the measuring / warm-up iterations
         are real optimizer steps and must not count as training."""
         assert self.graph
@@ -836,11 +972,33 @@ class TrainStep:
         cur.wait_stream(side)
         g1c.replay()
 
+    def _raise_on_ingest_overflow(self):
+        """Periodic check, capacity mode: batches that set_packed_batch had to cut were held on the device; neither P nor gmax grows
+        on its own, so the caller is told which one to raise.  The counters are cleared first: a caller that catches this (and, say,
+        drops such batches) can go on stepping."""
+        if self.point_capacity is None:
+            return
+        n_pts, n_gt = (int(v) for v in self._ingest_over.tolist())
+        if n_pts == 0 and n_gt == 0:
+            return
+        held = self.held_steps()
+        self._ingest_over.zero_()
+        self.opt_state[11:13].zero_()
+        what = []
+        if n_pts:
+            what.append(f"{n_pts} batch(es) had a scene above point_capacity={self.point_capacity} points: build the TrainStep with a larger "
+                        "point_capacity (trainer.plan_point_capacity)")
+        if n_gt:
+            what.append(f"{n_gt} batch(es) had a scene above gt_capacity={int(self.gts['gmax'])} boxes: build the TrainStep with a larger "
+                        "gt_capacity")
+        raise RuntimeError(f"ingest overflow: {held} step(s) were held (no update applied); " + "; ".join(what))
+
     def _eager_check(self):
         """Eager mode has no graph to re-capture, but the device-side HOLD still skips updates (level overflow cannot happen without
         captured capacities; a persistent FPS time-out can): every `check_every` steps read the counters and, on a time-out, fall back
         to the single-workgroup FPS - otherwise every step would be a silent no-op that still returns a finite loss."""
         self._steps_since_check = 0
+        self._raise_on_ingest_overflow()
         held, n_to = self.held_steps(), self.fps_timeouts()
         if n_to > 0:
             import sys
@@ -876,6 +1034,7 @@ class TrainStep:
             # one small device-to-host read every `check_every` steps, then a collective re-capture with room to spare
             self._steps_since_check = 0
             if self.held_steps() > 0:
+                self._raise_on_ingest_overflow()       # a batch above the point / GT capacity: re-capturing grows the sparse levels only
                 # the reason (level overflow vs FPS time-out) is per rank; the decision what to change must not be: job-wide maximum
                 self._job_fps_timeouts = self.fps_timeouts()
                 if self.dist_on:
