@@ -476,6 +476,35 @@ int64_t u3d_nms3d_workspace(int32_t n);
 int32_t u3d_nms3d(const float* boxes, const int32_t* labels, int32_t n, float thr, uint8_t* keep, void* workspace,
                   int64_t workspace_bytes, u3d_stream s);
 
+/* The inference tail for every scene of a batch in one call: NMSFreeCoder.decode_single's selection and Uni3DETRHead.get_bboxes'
+ * post-processing for post_processing None / 'nms' (ref: core/bbox/coders/nms_free_coder.py:42-100,
+ * models/dense_heads/uni3detr_head.py:827-918), bit for bit what the per-scene host loop gives (csrc/det_tail.hip).
+ * prob f32 [B,Q,C] sigmoid class scores, fused f32 [B,Q,C] = prob^alpha * iou^(1-alpha) (what is reported), boxes f32 [B,Q,box_dim]
+ * denormalised, gravity centre, box_dim 7 or 9; center_range f32 [6] on the device; K = min(max_num, Q*C).  Per scene:
+ *   1. the K largest of prob, ordered by descending score, then ascending flat (query, class) index; label = idx % C, query = idx / C;
+ *   2. kept if the three centre coordinates lie within center_range (inclusive) and, when score_threshold > 0, prob > score_threshold;
+ *      stable compaction; the reported score is fused[query, class];
+ *   3. z -= dz * 0.5 in two rounded f32 steps (bottom centre), except in mode U3D_DET_TAIL_DECODE;
+ *   4. U3D_DET_TAIL_NONE / _DECODE: that list; U3D_DET_TAIL_NMS: greedy same-label rotated-BEV NMS in (fused score descending, compacted
+ *      position ascending) order with u3d_nms3d's IoU, suppression at IoU > nms_thr; survivors by label ascending, inside a label
+ *      by descending score, stable;
+ *   5. score_thr (f32 [C] on the device, or NULL): keep fused > score_thr[label]; num_thr > 0: the first num_thr by descending fused
+ *      score, ties by the order of step 4 (the per-scene path's argsort leaves those ties open: this is the pin).
+ * Outputs: out_boxes [B,K,box_dim], out_scores [B,K], out_labels int32 [B,K] with the rows past out_count[b] zeroed, out_count int32
+ * [B], out_off int32 [B+1] = exclusive scan of out_count (the det_off layout of u3d_eval_* / u3d_tta_merge).  No atomics on global
+ * memory: equal inputs give equal bytes.  U3D_ERR_UNSUPPORTED for K > U3D_DET_TAIL_MAX_K, Q*C >= 2^31, C > 65536, B > 65535.  NMS
+ * segments (one scene, one class) of more than U3D_DET_TAIL_LDS_CAP candidates read their BEV rows from the workspace instead of LDS. */
+#define U3D_DET_TAIL_NONE 0
+#define U3D_DET_TAIL_NMS 1
+#define U3D_DET_TAIL_DECODE 2    /* as NONE with the boxes left gravity-centre: what NMSFreeCoder.decode returns */
+#define U3D_DET_TAIL_MAX_K 8192
+#define U3D_DET_TAIL_LDS_CAP 2048
+int64_t u3d_det_tail_workspace(int32_t batch, int32_t nq, int32_t num_classes, int32_t max_num, int32_t box_dim);
+int32_t u3d_det_tail(const float* prob, const float* fused, const float* boxes, int32_t batch, int32_t nq, int32_t num_classes,
+                     int32_t box_dim, int32_t max_num, const float* center_range, float score_threshold, int32_t mode, float nms_thr,
+                     const float* score_thr, int32_t num_thr, float* out_boxes, float* out_scores, int32_t* out_labels,
+                     int32_t* out_count, int32_t* out_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
+
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad

@@ -152,6 +152,8 @@ _SIGS = {
     "u3d_trilinear_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "u3d_nms3d_workspace": (_L, [_I]),
     "u3d_nms3d": (_I, [_P, _P, _I, C.c_float, _P, _P, _L, _P]),
+    "u3d_det_tail_workspace": (_L, [_I, _I, _I, _I, _I]),
+    "u3d_det_tail": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, C.c_float, _I, C.c_float, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "u3d_tta_merge_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
     "u3d_tta_merge": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, C.c_float, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "u3d_iou3d_rotated_aligned": (_I, [_P, _P, _I, _P, _P]),
@@ -2276,3 +2278,85 @@ def tta_merge(boxes, scores, labels, det_off, params, views, coord, num_classes,
                                int(coord), int(num_classes), float(nms_thr), max_num, max_per_scene, _ptr(ws), wsb, _ptr(out_b), _ptr(out_s),
                                _ptr(out_l), _ptr(out_c), _stream()), "tta_merge")
     return out_b, out_s, out_l, out_c
+
+
+# --------------------------------------------------------------------------------------------------
+# The batched inference tail (csrc/det_tail.hip)
+# --------------------------------------------------------------------------------------------------
+DET_TAIL_NONE, DET_TAIL_NMS, DET_TAIL_DECODE = 0, 1, 2
+DET_TAIL_MAX_K = 8192
+
+
+class DetBatch:
+    """The detections of B scenes as padded tensors on one device: boxes [B,K,D], scores [B,K], labels int32 [B,K] (rows past count[b]
+    are zero), count int32 [B], off int32 [B+1] = exclusive scan of count (the det_off layout of the evaluators and of tta_merge)."""
+
+    def __init__(self, boxes, scores, labels, count, off):
+        self.boxes, self.scores, self.labels, self.count, self.off = boxes, scores, labels, count, off
+
+    def __len__(self):
+        return int(self.count.shape[0])
+
+    def cpu(self):
+        """The same batch on the host: one copy per tensor."""
+        return DetBatch(self.boxes.cpu(), self.scores.cpu(), self.labels.cpu(), self.count.cpu(), self.off.cpu())
+
+    def packed(self):
+        """-> (boxes [N,D], scores [N], labels int32 [N], det_off int32 [B+1]); N is read with ONE copy of off[-1] to the host."""
+        n = int(self.off[-1])
+        B, K, D = self.boxes.shape
+        i = torch.arange(n, dtype=torch.int32, device=self.off.device)
+        scene = torch.searchsorted(self.off[1:].contiguous(), i, right=True)      # empty scenes are stepped over
+        row = scene * K + (i - self.off[scene])
+        return self.boxes.reshape(B * K, D)[row], self.scores.reshape(-1)[row], self.labels.reshape(-1)[row], self.off
+
+    def to_list(self):
+        """-> get_bboxes' format [[boxes [n,D], scores [n], labels long [n]], ...]; ONE copy of count to the host."""
+        cnt = self.count.cpu().tolist()
+        lab = self.labels.long()
+        return [[self.boxes[b, :c], self.scores[b, :c], lab[b, :c]] for b, c in enumerate(cnt)]
+
+    @staticmethod
+    def from_list(dets, K, dim, device):
+        """Pack per-scene (boxes, scores, labels) of at most K rows each (the per-scene post-processing modes)."""
+        B = len(dets)
+        boxes = torch.zeros((B, K, dim), dtype=torch.float32, device=device)
+        scores = torch.zeros((B, K), dtype=torch.float32, device=device)
+        labels = torch.zeros((B, K), dtype=torch.int32, device=device)
+        cnt = [int(d[1].shape[0]) for d in dets]
+        for b, (bx, sc, lb) in enumerate(dets):
+            boxes[b, :cnt[b]], scores[b, :cnt[b]], labels[b, :cnt[b]] = bx, sc, lb
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+        return DetBatch(boxes, scores, labels, torch.tensor(cnt, dtype=torch.int32, device=device), torch.from_numpy(off).to(device))
+
+
+def det_tail(prob, fused, boxes, max_num, center_range, score_threshold=None, mode=DET_TAIL_NONE, nms_thr=0.0, score_thr=None,
+             num_thr=None):
+    """The decode selection + post-processing of every scene in one call, no host sync (csrc/det_tail.hip; include/u3d_hip.h states
+    the per-scene semantics).  prob / fused f32 [B,Q,C], boxes f32 [B,Q,7|9] gravity centre, center_range f32 [6] device tensor,
+    score_thr f32 [C] device tensor or None, mode DET_TAIL_NONE / DET_TAIL_NMS / DET_TAIL_DECODE -> DetBatch with K = min(max_num, Q*C)."""
+    B, Q, Cn = prob.shape
+    dim = boxes.shape[-1]
+    dev = prob.device
+    for t in (prob, fused, boxes, center_range) + (() if score_thr is None else (score_thr,)):
+        if t.dtype != torch.float32:
+            raise U3DError(f"det_tail takes float32 tensors, got {t.dtype}")
+    if fused.shape != prob.shape or boxes.shape[:2] != prob.shape[:2] or center_range.numel() != 6:
+        raise U3DError("det_tail: prob / fused [B,Q,C], boxes [B,Q,D] and center_range [6] do not fit together")
+    if score_thr is not None and score_thr.numel() != Cn:
+        raise U3DError(f"det_tail: score_thr needs one entry per class ({Cn}), got {score_thr.numel()}")
+    K = min(int(max_num), Q * Cn)
+    if B <= 0 or K <= 0 or K > DET_TAIL_MAX_K or dim not in (7, 9) or Q * Cn >= 2 ** 31:
+        raise U3DError(f"det_tail: unsupported shape (B={B}, Q*C={Q * Cn}, K={K} of at most {DET_TAIL_MAX_K}, box_dim={dim})")
+    out = DetBatch(torch.empty((B, K, dim), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.float32, device=dev),
+                   torch.empty((B, K), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                   torch.empty((B + 1,), dtype=torch.int32, device=dev))
+    wsb = int(lib().u3d_det_tail_workspace(B, Q, Cn, int(max_num), dim))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    # named locals: a copy that .contiguous() makes must stay alive until the launch, or the allocator hands its block to the next one
+    p, f, bx, rng = prob.contiguous(), fused.contiguous(), boxes.contiguous(), center_range.contiguous()
+    thr = None if score_thr is None else score_thr.contiguous()
+    _check(lib().u3d_det_tail(_ptr(p), _ptr(f), _ptr(bx), B, Q, Cn, dim, int(max_num), _ptr(rng), float(score_threshold or 0.0),
+                              int(mode), float(nms_thr), _ptr(thr), int(num_thr or 0), _ptr(out.boxes),
+                              _ptr(out.scores), _ptr(out.labels), _ptr(out.count), _ptr(out.off), _ptr(ws), wsb, _stream()), "det_tail")
+    return out

@@ -189,3 +189,28 @@ class NMSFreeCoder:
         box = preds_dicts["all_bbox_preds"][1:].mean(0)
         iou = preds_dicts["all_iou_preds"][1:].mean(0)
         return [self.decode_single(cls[i], box[i], iou[i]) for i in range(cls.size(0))]
+
+    def batched_prelude(self, preds_dicts):
+        """The elementwise part of `decode` over the whole batch, a handful of launches and no host sync: layer mean, sigmoid,
+        denormalize_bbox, score fusion -> (prob [B,Q,C], fused [B,Q,C], boxes [B,Q,7|9] gravity centre, centre range f32 [6] on the
+        device).  The same torch operators on the same values as decode_single, so every element has decode_single's bits."""
+        if self.post_center_range is None:
+            raise NotImplementedError("only post_center_range is not None is supported (as in the reference)")
+        cls = preds_dicts["all_cls_scores"][1:].mean(0)
+        box = preds_dicts["all_bbox_preds"][1:].mean(0)
+        iou = preds_dicts["all_iou_preds"][1:].mean(0)
+        prob = cls.sigmoid()
+        fused = prob ** self.alpha * iou.sigmoid() ** (1 - self.alpha)        # [B,Q,C] * [B,Q,1]
+        boxes = denormalize_bbox(box, self.pc_range)
+        key = (prob.device, tuple(float(v) for v in self.post_center_range))
+        # one host-to-device copy per coder and device.  Keyed by value, so no invalidation is needed (nor done) when
+        # post_center_range is mutated in place: a changed range is a changed key
+        if getattr(self, "_range_dev", (None, None))[0] != key:
+            self._range_dev = (key, torch.tensor(key[1], dtype=torch.float32, device=prob.device))
+        return prob, fused, boxes, self._range_dev[1]
+
+    def decode_batched(self, preds_dicts):
+        """`decode` for all scenes in one device call (native.det_tail, mode DET_TAIL_DECODE): a DetBatch whose scene b carries
+        decode(...)[b]'s bboxes (gravity centre), scores and labels (int32 there), bit for bit, in the same order; `ious` is not kept."""
+        prob, fused, boxes, rng = self.batched_prelude(preds_dicts)
+        return nv.det_tail(prob, fused, boxes, self.max_num, rng, self.score_threshold, mode=nv.DET_TAIL_DECODE)

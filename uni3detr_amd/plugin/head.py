@@ -403,42 +403,79 @@ class Uni3DETRHead(nn.Module):
 
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):
         """Decode + post-processing on the device (ref :827-918).  Returns [[boxes [n,7] bottom-centre, scores, labels], ...]."""
-        from .. import native as nv
         preds = self.bbox_coder.decode(preds_dicts)
+        return [self._post_process_scene(p["bboxes"], p["scores"], p["labels"]) for p in preds]
+
+    def _post_process_scene(self, bboxes, scores, labels):
+        """One scene of get_bboxes: the coder's boxes (gravity centre), fused scores, labels -> [boxes bottom-centre, scores, labels]."""
+        from .. import native as nv
         pp = self.post_processing
-        ret = []
-        for p in preds:
-            boxes = p["bboxes"].clone()
-            boxes[:, 2] = boxes[:, 2] - boxes[:, 5] * 0.5          # gravity centre -> bottom centre (ref :842)
-            scores, labels = p["scores"], p["labels"]
-            if pp is not None:
-                if pp["type"] == "nms":
-                    keep = nv.nms3d_classwise(boxes, scores, labels, pp["nms_thr"])
-                    boxes, scores, labels = boxes[keep], scores[keep], labels[keep]
-                elif pp["type"] == "soft_nms":
-                    # all classes in one launch (one workgroup per class); result class-major like the reference's per-class loop
-                    ki, scores, labels = nv.soft_nms_classwise(boxes, scores, labels, self.num_classes, pp["gaussian_sigma"], pp["prune_threshold"])
-                    boxes = boxes[ki]
-                elif pp["type"] == "box_merging":
-                    # ref :881-891: nms_boxes_3d_merge_only(..., overlapped_thres=0.1, top_k=-1): score sort, greedy same-class merge,
-                    # kept boxes replaced by the median of what they absorbed - on the device (u3d_box_merge)
-                    order = torch.argsort(-scores, stable=True)
-                    boxes, scores, labels = boxes[order], scores[order], labels[order]
-                    merged, keep = nv.box_merge(boxes[:, :7], labels, 0.1)
-                    boxes = torch.cat([merged, boxes[:, 7:]], 1)[keep] if boxes.shape[1] > 7 else merged[keep]
-                    scores, labels = scores[keep], labels[keep]
+        boxes = bboxes.clone()
+        boxes[:, 2] = boxes[:, 2] - boxes[:, 5] * 0.5          # gravity centre -> bottom centre (ref :842)
+        if pp is not None:
+            if pp["type"] == "nms":
+                keep = nv.nms3d_classwise(boxes, scores, labels, pp["nms_thr"])
+                boxes, scores, labels = boxes[keep], scores[keep], labels[keep]
+            elif pp["type"] == "soft_nms":
+                # all classes in one launch (one workgroup per class); result class-major like the reference's per-class loop
+                ki, scores, labels = nv.soft_nms_classwise(boxes, scores, labels, self.num_classes, pp["gaussian_sigma"], pp["prune_threshold"])
+                boxes = boxes[ki]
+            elif pp["type"] == "box_merging":
+                # ref :881-891: nms_boxes_3d_merge_only(..., overlapped_thres=0.1, top_k=-1): score sort, greedy same-class merge,
+                # kept boxes replaced by the median of what they absorbed - on the device (u3d_box_merge)
+                order = torch.argsort(-scores, stable=True)
+                boxes, scores, labels = boxes[order], scores[order], labels[order]
+                merged, keep = nv.box_merge(boxes[:, :7], labels, 0.1)
+                boxes = torch.cat([merged, boxes[:, 7:]], 1)[keep] if boxes.shape[1] > 7 else merged[keep]
+                scores, labels = scores[keep], labels[keep]
+            else:
+                raise NotImplementedError(pp["type"] + " not implemented.")
+            if "score_thr" in pp:
+                thr = pp["score_thr"]
+                if isinstance(thr, (list, tuple)):
+                    assert len(thr) == self.num_classes
+                    ind = scores > scores.new_tensor(list(thr))[labels]
                 else:
-                    raise NotImplementedError(pp["type"] + " not implemented.")
-                if "score_thr" in pp:
-                    thr = pp["score_thr"]
-                    if isinstance(thr, (list, tuple)):
-                        assert len(thr) == self.num_classes
-                        ind = scores > scores.new_tensor(list(thr))[labels]
-                    else:
-                        ind = scores > thr
-                    boxes, scores, labels = boxes[ind], scores[ind], labels[ind]
-                if "num_thr" in pp:
-                    ind = torch.argsort(-scores)[: pp["num_thr"]]
-                    boxes, scores, labels = boxes[ind], scores[ind], labels[ind]
-            ret.append([boxes, scores, labels])
-        return ret
+                    ind = scores > thr
+                boxes, scores, labels = boxes[ind], scores[ind], labels[ind]
+            if "num_thr" in pp:
+                ind = torch.argsort(-scores)[: pp["num_thr"]]
+                boxes, scores, labels = boxes[ind], scores[ind], labels[ind]
+        return [boxes, scores, labels]
+
+    def get_bboxes_batched(self, preds_dicts, img_metas, rescale=False):
+        """get_bboxes for all scenes at once -> native.DetBatch (padded device tensors + count / off); `.to_list()` gives get_bboxes'
+        format, scene by scene bit-identical to it.  post_processing None and 'nms' (with score_thr, scalar or per class, and num_thr)
+        run entirely in one device call (u3d_det_tail) after a handful of batched torch launches, with no host sync; where
+        get_bboxes' `torch.argsort(-scores)` leaves equal scores under num_thr in an open order, they keep the order the NMS emitted.
+        'soft_nms' and 'box_merging' are NOT batched: the decode runs in the device call, then every scene goes through the same
+        per-scene routines as get_bboxes, with their launches and host synchronisations, and the results are packed."""
+        from .. import native as nv
+        pp = self.post_processing
+        coder = self.bbox_coder
+        if pp is not None and pp["type"] not in ("nms", "soft_nms", "box_merging"):
+            raise NotImplementedError(pp["type"] + " not implemented.")
+        if pp is None or pp["type"] == "nms":
+            prob, fused, boxes, rng = coder.batched_prelude(preds_dicts)
+            thr = None
+            if pp is not None and "score_thr" in pp:
+                thr = pp["score_thr"]
+                if isinstance(thr, (list, tuple)):
+                    assert len(thr) == self.num_classes
+                else:
+                    thr = [thr] * prob.shape[-1]
+                key = (prob.device, tuple(float(v) for v in thr))
+                # one host-to-device copy per setting and device.  Keyed by value, so no invalidation is needed (nor done) when
+                # post_processing is mutated in place: a changed score_thr is a changed key
+                if getattr(self, "_score_thr_dev", (None, None))[0] != key:
+                    self._score_thr_dev = (key, prob.new_tensor(key[1]))
+                thr = self._score_thr_dev[1]
+            if pp is not None and "num_thr" in pp and int(pp["num_thr"]) <= 0:
+                raise ValueError("num_thr must be positive")
+            if pp is None:
+                return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, mode=nv.DET_TAIL_NONE)
+            return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, mode=nv.DET_TAIL_NMS, nms_thr=pp["nms_thr"],
+                               score_thr=thr, num_thr=pp.get("num_thr"))
+        dec = coder.decode_batched(preds_dicts)
+        dets = [self._post_process_scene(b, s, l) for b, s, l in dec.to_list()]
+        return nv.DetBatch.from_list(dets, dec.scores.shape[1], dec.boxes.shape[2], dec.boxes.device)
