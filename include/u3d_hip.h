@@ -505,6 +505,34 @@ int32_t u3d_det_tail(const float* prob, const float* fused, const float* boxes, 
                      const float* score_thr, int32_t num_thr, float* out_boxes, float* out_scores, int32_t* out_labels,
                      int32_t* out_count, int32_t* out_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
 
+/* u3d_det_tail with get_bboxes' other two post-processing types: every argument of u3d_det_tail, soft_sigma / soft_prune after num_thr.
+ * All five modes are accepted (NONE / NMS / DECODE as above, u3d_det_tail forwards here); steps 1-3 and 5 are those of u3d_det_tail,
+ * step 4 becomes
+ *   U3D_DET_TAIL_SOFT_NMS  per label the Gaussian soft-NMS of u3d_soft_nms on the bottom-centre boxes (first 7 columns, rotated 3-D
+ *      IoU): select the highest current score, ties to the lowest compacted position; every other live box of the label is decayed by
+ *      exp(-iou^2 / soft_sigma) and dies when its score is <= soft_prune.  Output by label ascending, inside a label in selection
+ *      order; the REPORTED SCORE IS THE DECAYED ONE, and step 5 (score_thr, num_thr with ties by this order) works on it.
+ *      soft_sigma <= 0 is U3D_ERR_ARG.
+ *   U3D_DET_TAIL_MERGE  the KITTI box merging of u3d_box_merge: the candidates in (fused score descending, compacted position
+ *      ascending) order - the stable argsort(-scores) -; a live box is kept and absorbs every later live box of its label with
+ *      overlap > nms_thr (the reference's overlap with its camera-axis reading of the LiDAR columns, on the un-merged bottom-centre
+ *      boxes).  A kept box takes in its first 7 columns the per-column median of {absorbed boxes in that order, itself last}: numpy's
+ *      median, the mean of the two middle values for an even count, equal values ranked by that position; columns 7 and up are its
+ *      own, the reported score is its fused score.  Output in that scene-wide order, NOT by label; step 5 keeps it (num_thr ties
+ *      by compacted position).
+ * Limits as for u3d_det_tail, K = U3D_DET_TAIL_MAX_K served in every mode, checked before any launch (U3D_ERR_UNSUPPORTED); a
+ * workspace below u3d_det_tail_pp_workspace(..., mode) is U3D_ERR_WORKSPACE.  A (scene, label) segment keeps its scores, its sweep
+ * flags and its member list in LDS for any size, its boxes too up to U3D_DET_TAIL_LDS_CAP candidates (read from the workspace above
+ * that); the merge needs no mask matrix, so the workspace stays linear in B * K.  No atomics on global memory, no synchronisation,
+ * no allocation. */
+#define U3D_DET_TAIL_SOFT_NMS 3
+#define U3D_DET_TAIL_MERGE 4
+int64_t u3d_det_tail_pp_workspace(int32_t batch, int32_t nq, int32_t num_classes, int32_t max_num, int32_t box_dim, int32_t mode);
+int32_t u3d_det_tail_pp(const float* prob, const float* fused, const float* boxes, int32_t batch, int32_t nq, int32_t num_classes,
+                        int32_t box_dim, int32_t max_num, const float* center_range, float score_threshold, int32_t mode, float nms_thr,
+                        const float* score_thr, int32_t num_thr, float soft_sigma, float soft_prune, float* out_boxes, float* out_scores,
+                        int32_t* out_labels, int32_t* out_count, int32_t* out_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
+
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad

@@ -4,10 +4,12 @@ simple_test_pts) against the batched one (get_bboxes_batched + .to_list(): one d
     python tools/det_tail_bench.py [--iters 30] [--warmup 5] [--timeout 120]
 
 Shapes: nuscenes (B=4, Q=900, C=10, K=900, nms 0.2, num_thr 500, 9 box columns), sunrgbd (B=4, Q=300, C=10, K=1000, nms 0.5), scannet
-(B=3, Q=300, C=18, K=5000, no post-processing), tta16 (the nuscenes shape with the 16 views of a double-flip batch of 4 samples) and
-nuscenes_b1 (one scene).  Every case runs in a process of its own under `timeout`; the first failure ends the run.  One JSON line per
+(B=3, Q=300, C=18, K=5000, no post-processing), tta16 (the nuscenes shape with the 16 views of a double-flip batch of 4 samples),
+nuscenes_b1 (one scene), kitti_b1 / kitti_b8 / kitti_b16 (Q=300, C=3, K=150, box_merging with the shipped per-class score_thr) and
+sunrgbd_soft (the sunrgbd shape with soft_nms).  Every case runs in a process of its own under `timeout`; the first failure ends the run.  One JSON line per
 case: per_scene_ms, batched_ms (device slices from .to_list()) and batched_host_ms (.cpu().to_list(): host tensors, the end state of
-the per-scene number), medians of wall time with a device synchronisation after every repetition, and whether the two paths agree."""
+the per-scene number), medians of wall time with a device synchronisation after every repetition - each with its [min, max] under
+*_range_ms -, and whether the two paths agree."""
 import argparse
 import copy
 import json
@@ -25,6 +27,10 @@ CASES = dict(
     scannet=dict(B=3, Q=300, C=18, K=5000, dim=7, spread=2.0, pp=None),
     tta16=dict(B=16, Q=900, C=10, K=900, dim=9, spread=12.0, pp=dict(type="nms", nms_thr=0.2, num_thr=500)),
     nuscenes_b1=dict(B=1, Q=900, C=10, K=900, dim=9, spread=12.0, pp=dict(type="nms", nms_thr=0.2, num_thr=500)),
+    kitti_b1=dict(B=1, Q=300, C=3, K=150, dim=7, spread=12.0, pp=dict(type="box_merging", score_thr=[0.0, 0.3, 0.65])),
+    kitti_b8=dict(B=8, Q=300, C=3, K=150, dim=7, spread=12.0, pp=dict(type="box_merging", score_thr=[0.0, 0.3, 0.65])),
+    kitti_b16=dict(B=16, Q=300, C=3, K=150, dim=7, spread=12.0, pp=dict(type="box_merging", score_thr=[0.0, 0.3, 0.65])),
+    sunrgbd_soft=dict(B=4, Q=300, C=10, K=1000, dim=7, spread=2.0, pp=dict(type="soft_nms", gaussian_sigma=0.3, prune_threshold=1e-3)),
 )
 
 
@@ -64,7 +70,7 @@ def run_case(name, iters, warmup):
             out = fn()
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
-        return float(np.median(ts)), out
+        return (float(np.median(ts)), float(np.min(ts)), float(np.max(ts))), out
 
     with torch.no_grad():
         t_ref, ref = timed(per_scene)
@@ -72,8 +78,10 @@ def run_case(name, iters, warmup):
         t_host, got = timed(lambda: head.get_bboxes_batched(preds, None).cpu().to_list())
     same = all(all(torch.equal(x, y) for x, y in zip(a, b)) for a, b in zip(got, ref))
     print(json.dumps(dict(tool="det_tail_bench", case=name, B=B, Q=Q, C=c["C"], K=c["K"], post_processing=c["pp"],
-                          kept_per_scene=[int(x[1].numel()) for x in ref], per_scene_ms=round(t_ref, 3), batched_ms=round(t_dev, 3),
-                          batched_host_ms=round(t_host, 3), identical=bool(same))), flush=True)
+                          kept_per_scene=[int(x[1].numel()) for x in ref], per_scene_ms=round(t_ref[0], 3), batched_ms=round(t_dev[0], 3),
+                          batched_host_ms=round(t_host[0], 3), per_scene_range_ms=[round(v, 3) for v in t_ref[1:]],
+                          batched_range_ms=[round(v, 3) for v in t_dev[1:]], batched_host_range_ms=[round(v, 3) for v in t_host[1:]],
+                          identical=bool(same))), flush=True)
     return 0 if same else 1
 
 

@@ -1,6 +1,7 @@
-// The inference tail after the head's forward, for every scene of a batch in one call (u3d_det_tail): the selection of
+// The inference tail after the head's forward, for every scene of a batch in one call (u3d_det_tail / u3d_det_tail_pp): the selection of
 // NMSFreeCoder.decode_single (ref: core/bbox/coders/nms_free_coder.py:42-100) and the post-processing of Uni3DETRHead.get_bboxes (ref:
-// models/dense_heads/uni3detr_head.py:827-918) for post_processing None / 'nms', bit for bit what the per-scene host loop gives.  The
+// models/dense_heads/uni3detr_head.py:827-918) for post_processing None / 'nms' / 'soft_nms' / 'box_merging', bit for bit what the
+// per-scene host loop gives.  The
 // transcendental part (layer mean, sigmoid, denormalize_bbox, score fusion) stays in torch, batched; the kernels here only select,
 // compare, move and run the rotated IoU:
 //   k_dt_select  one workgroup per scene.  Key of a (query, class) entry = monotone-uint32(prob) in the high word (inverted), flat index
@@ -10,26 +11,45 @@
 //                (centre within center_range, prob > score_threshold) compacts that list stably -> the coder's output order.
 //                NMS mode: the kept candidates are sorted once more by (label asc, fused score desc, compacted position asc) - the order
 //                nms3d_classwise emits - their BEV rows (cx, cy, dx, dy, yaw) and the (scene, class) segments go to the workspace.
+//                MERGE mode: the same order with 7-column bottom-centre rows, plus the compacted position of every row.  SOFT_NMS mode:
+//                (label asc, compacted position asc) - u3d_soft_nms's member order, which its tie rule reads - and 7-column rows.
 //   k_dt_nms     one workgroup per (scene, class) segment: greedy rotated-BEV NMS in that order with pp_iou_bev, the arithmetic of
 //                bev_iou_rot (u3d_nms3d).  Suppression never crosses labels, so the greedy pass per segment equals the pass over the
 //                whole score-sorted scene.  Segments of at most DT_LDS_CAP = 2048 candidates hold their BEV rows in LDS (40 KiB); larger
 //                ones run the same loop on the rows in the workspace (no mask matrix: K <= 8192 rows stay in L2).
-//   k_dt_emit    one workgroup per scene: survivors with fused score > score_thr[label], stably compacted; with num_thr > 0 sorted by
+//   k_dt_soft    one workgroup per (scene, class) segment: the Gaussian soft-NMS loop of k_soft_nms (postproc.hip) with pp_iou3d and
+//                pp_soft_decay; the current scores of up to 8192 members live in LDS (32 KiB), the rows too up to DT_LDS_CAP (56 KiB),
+//                above that they are read from the workspace.  Selected members go, in selection order, to the front of the segment
+//                (flat index, decayed score, keep = 1); the emit then reads them class-major.
+//   k_dt_merge   one workgroup per (scene, class) segment: the greedy sweep of u3d_box_merge with pp_merge_overlap on the un-merged
+//                rows.  Absorption never crosses labels and a segment is in scene-wide (score, position) order, so the sweep per
+//                segment equals the sweep over the score-sorted scene.  A live row i marks every later live row it overlaps (the
+//                reference's mask row & ~removed, without the mask matrix: kept rows x cnt overlap evaluations instead of cnt^2 / 2);
+//                they are compacted in ascending order, i itself goes last - the member order of k_merge_median - and each of the
+//                first 7 columns becomes the median by rank selection (ties by that position).  Flags, member list and one column of
+//                values live in LDS for any segment size (8 + 16 + 32 KiB), the rows as in k_dt_soft.
+//   k_dt_emit    one workgroup per scene: survivors with score > score_thr[label], stably compacted (the score is the fused one, in
+//                SOFT_NMS mode the decayed one k_dt_soft left); MERGE mode sorts them by (fused score desc, compacted position asc),
+//                the scene-wide order of the per-scene path, and takes columns 0-6 from the merged rows; with num_thr > 0 sorted by
 //                (fused score desc, position asc) and cut - the per-scene path's torch.argsort(-scores) leaves ties open there, this is the
 //                pin -; boxes gathered (z -= dz * 0.5 in two rounded f32 steps unless the caller asks for the coder's gravity centres),
 //                rows past the count zeroed, count written.
 //   k_dt_offsets out_off = exclusive scan of out_count (the det_off layout of u3d_eval_* / u3d_tta_merge).
 // No atomics on global memory (LDS counters are integers: any order gives the same sum), so two runs give the same bytes.
-// Limits: K = min(max_num, nq * num_classes) <= 8192, box_dim 7 or 9, nq * num_classes < 2^31, num_classes <= 65536.
+// Limits: K = min(max_num, nq * num_classes) <= 8192, box_dim 7 or 9, nq * num_classes < 2^31, num_classes <= 65536, in every mode.
 // Non-finite scores are outside the contract (torch orders NaN above everything; here a NaN orders by its bit pattern).
 #include "common.h"
 #include "box_iou.h"
+#include "postproc_math.h"
 
 #define DT_THREADS 1024
 #define DT_WAVES (DT_THREADS / 64)
 #define DT_MAX_K U3D_DET_TAIL_MAX_K
 #define DT_LDS_CAP U3D_DET_TAIL_LDS_CAP
 #define DT_NMS_THREADS 256
+#define DT_PP_THREADS 256                  /* k_dt_soft, k_dt_merge */
+#define DT_ORDER_SCORE 1                /* k_dt_select: label, fused score descending, compacted position */
+#define DT_ORDER_POS 2                  /* label, compacted position */
 #define DT_POS_BITS 13                 /* a position < DT_MAX_K = 2^13 */
 #define DT_PAD 0xffffffffffffffffull
 
@@ -43,7 +63,8 @@ __device__ __forceinline__ unsigned dt_mono(float v) {
 }
 
 // rank of this thread's flag among the set flags of the workgroup in thread order; *total = how many are set.  Called by ALL threads.
-__device__ __forceinline__ int dt_scan(bool f, int* wsum, int* total) {
+template <int WAVES>
+__device__ __forceinline__ int dt_scan_w(bool f, int* wsum, int* total) {
   const dt_u64 b = __ballot(f);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
@@ -51,7 +72,7 @@ __device__ __forceinline__ int dt_scan(bool f, int* wsum, int* total) {
   if (lane == 0) wsum[w] = __popcll(b);
   __syncthreads();
   int before = 0, tot = 0;
-  for (int k = 0; k < DT_WAVES; ++k) {
+  for (int k = 0; k < WAVES; ++k) {
     const int v = wsum[k];
     if (k < w) before += v;
     tot += v;
@@ -59,6 +80,7 @@ __device__ __forceinline__ int dt_scan(bool f, int* wsum, int* total) {
   *total = tot;
   return before + in_wave;
 }
+__device__ __forceinline__ int dt_scan(bool f, int* wsum, int* total) { return dt_scan_w<DT_WAVES>(f, wsum, total); }
 
 // ascending bitonic sort of a[0 .. p), p a power of two, in LDS; ends with a barrier
 __device__ void dt_bitonic(dt_u64* a, int p) {
@@ -75,13 +97,22 @@ __device__ void dt_bitonic(dt_u64* a, int p) {
   __syncthreads();
 }
 
+// the two steps of get_bboxes' `boxes[:, 2] - boxes[:, 5] * 0.5`, each rounded to f32 (no contraction into one fused multiply-add)
+__device__ __forceinline__ float dt_bottom_z(float z, float dz) {
+#pragma clang fp contract(off)
+  const float half = dz * 0.5f;
+  return z - half;
+}
+
 // cand0 [B][K]: flat index by compacted position (NMS mode); cand [B][K]: flat index by final position of this kernel; ncand [B];
-// seg [B][C][2] = (first, one past last) position of the class; bev [B][K][5]
+// seg [B][C][2] = (first, one past last) position of the class; rows [B][K][rowdim]: rowdim 5 = BEV (cx, cy, dx, dy, yaw), 7 = the
+// bottom-centre box; cpos [B][K] (or null): compacted position by final position.  order: 0, DT_ORDER_SCORE or DT_ORDER_POS
 __global__ __launch_bounds__(DT_THREADS) void k_dt_select(const float* __restrict__ prob, const float* __restrict__ fused,
                                                           const float* __restrict__ boxes, int nq, int ncls, int dim, int K, int P,
-                                                          const float* __restrict__ range, float score_threshold, int nms,
-                                                          int* __restrict__ cand0, int* __restrict__ cand, int* __restrict__ ncand,
-                                                          int* __restrict__ seg, float* __restrict__ bev) {
+                                                          const float* __restrict__ range, float score_threshold, int order,
+                                                          int rowdim, int* __restrict__ cand0, int* __restrict__ cand,
+                                                          int* __restrict__ ncand, int* __restrict__ seg, float* __restrict__ rows,
+                                                          int* __restrict__ cpos) {
   extern __shared__ dt_u64 keys[];                             // [P]
   __shared__ int hist[256];
   __shared__ int wsum[DT_WAVES];
@@ -92,7 +123,8 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_select(const float* __restric
   const float* pr = prob + (long long)b * N;
   const float* fu = fused + (long long)b * N;
   const float* bx = boxes + (long long)b * nq * dim;
-  cand0 += (long long)b * K; cand += (long long)b * K; bev += (long long)b * K * 5; seg += (long long)b * ncls * 2;
+  cand0 += (long long)b * K; cand += (long long)b * K; rows += (long long)b * K * rowdim; seg += (long long)b * ncls * 2;
+  if (cpos) cpos += (long long)b * K;
 
   // ---- the K-th largest score key: 8 bits per pass, most significant first ----
   if (tid == 0) { sel_prefix = 0u; sel_remaining = K; }
@@ -136,7 +168,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_select(const float* __restric
   for (int i = K + tid; i < P; i += DT_THREADS) keys[i] = DT_PAD;
   dt_bitonic(keys, P);                                         // descending score, ascending flat index
 
-  // ---- keep mask, stable compaction.  In NMS mode the new key of compacted position j overwrites keys[j]: j <= the position read,
+  // ---- keep mask, stable compaction.  In the ordered modes the new key of compacted position j overwrites keys[j]: j <= the position read,
   //      and every read of a tile happens before the barriers inside dt_scan, every write after them ----
   float lo[3], hi[3];
   for (int a = 0; a < 3; ++a) { lo[a] = range[a]; hi[a] = range[3 + a]; }
@@ -154,9 +186,10 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_select(const float* __restric
     int tot;
     const int j = n + dt_scan(keep, wsum, &tot);
     if (keep) {
-      if (nms) {
+      if (order) {
         cand0[j] = idx;
-        keys[j] = ((dt_u64)(unsigned)(idx % ncls) << (32 + DT_POS_BITS)) | ((dt_u64)(~dt_mono(fu[idx])) << DT_POS_BITS) | (unsigned)j;
+        const dt_u64 sk = order == DT_ORDER_SCORE ? (dt_u64)(~dt_mono(fu[idx])) << DT_POS_BITS : 0ull;
+        keys[j] = ((dt_u64)(unsigned)(idx % ncls) << (32 + DT_POS_BITS)) | sk | (unsigned)j;
       } else {
         cand[j] = idx;
       }
@@ -164,21 +197,27 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_select(const float* __restric
     n += tot;
   }
   if (tid == 0) ncand[b] = n;
-  if (!nms) return;
+  if (!order) return;
 
-  // ---- NMS order: label ascending, fused score descending, compacted position ascending ----
+  // ---- label ascending, then (DT_ORDER_SCORE) fused score descending, then compacted position ascending ----
   for (int c = tid; c < 2 * ncls; c += DT_THREADS) seg[c] = 0;
   __syncthreads();
   for (int i = n + tid; i < P; i += DT_THREADS) keys[i] = DT_PAD;
   dt_bitonic(keys, P);
   for (int r = tid; r < n; r += DT_THREADS) {
     const dt_u64 k = keys[r];
-    const int idx = cand0[(int)(k & ((1u << DT_POS_BITS) - 1u))];
+    const int j = (int)(k & ((1u << DT_POS_BITS) - 1u));
+    const int idx = cand0[j];
     const int lab = (int)(k >> (32 + DT_POS_BITS));
     cand[r] = idx;
+    if (cpos) cpos[r] = j;
     const float* c = bx + (long long)(idx / ncls) * dim;
-    float* o = bev + (long long)r * 5;
-    o[0] = c[0]; o[1] = c[1]; o[2] = c[3]; o[3] = c[4]; o[4] = c[6];
+    float* o = rows + (long long)r * rowdim;
+    if (rowdim == 5) {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[3]; o[3] = c[4]; o[4] = c[6];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = dt_bottom_z(c[2], c[5]); o[3] = c[3]; o[4] = c[4]; o[5] = c[5]; o[6] = c[6];
+    }
     if (r == 0 || (int)(keys[r - 1] >> (32 + DT_POS_BITS)) != lab) seg[2 * lab] = r;
     if (r == n - 1 || (int)(keys[r + 1] >> (32 + DT_POS_BITS)) != lab) seg[2 * lab + 1] = r + 1;
   }
@@ -216,30 +255,176 @@ __global__ __launch_bounds__(DT_NMS_THREADS) void k_dt_nms(const float* __restri
   for (int r = t; r < cnt; r += DT_NMS_THREADS) keep[(long long)b * K + start + r] = removed[r] ? 0 : 1;
 }
 
-// the two steps of get_bboxes' `boxes[:, 2] - boxes[:, 5] * 0.5`, each rounded to f32 (no contraction into one fused multiply-add)
-__device__ __forceinline__ float dt_bottom_z(float z, float dz) {
-#pragma clang fp contract(off)
-  const float half = dz * 0.5f;
-  return z - half;
+// ---- SOFT_NMS: the loop of k_soft_nms over rows[0 .. cnt) (7 floats each, member k = compacted order), sc[] current scores in LDS ----
+__device__ __forceinline__ int dt_soft_loop(const float* rows, int cnt, float sigma, float prune, float* sc, float* red_v, int* red_i,
+                                            float* topbox, const int* __restrict__ cand, int* __restrict__ sel,
+                                            float* __restrict__ sel_score) {
+  const int tid = threadIdx.x;
+  int n_sel = 0;
+  while (true) {
+    float bv = -1.f;
+    int bi = 0x7fffffff;
+    for (int k = tid; k < cnt; k += DT_PP_THREADS) {
+      const float v = sc[k];
+      if (v >= 0.f && (v > bv || (v == bv && k < bi))) { bv = v; bi = k; }
+    }
+    red_v[tid] = bv; red_i[tid] = bi;
+    __syncthreads();
+    for (int s = DT_PP_THREADS / 2; s > 0; s >>= 1) {
+      if (tid < s) {
+        const float v2 = red_v[tid + s];
+        const int i2 = red_i[tid + s];
+        if (v2 > red_v[tid] || (v2 == red_v[tid] && i2 < red_i[tid])) { red_v[tid] = v2; red_i[tid] = i2; }
+      }
+      __syncthreads();
+    }
+    const int top = red_i[0];
+    if (top == 0x7fffffff) break;                              // nothing alive
+    if (tid == 0) { sel[n_sel] = cand[top]; sel_score[n_sel] = red_v[0]; }
+    if (tid < 7) topbox[tid] = rows[top * 7 + tid];
+    __syncthreads();                                           // topbox is there; red_v[0] / red_i[0] are read
+    for (int k = tid; k < cnt; k += DT_PP_THREADS) {
+      float v = sc[k];
+      if (v < 0.f) continue;
+      v = pp_soft_decay(v, pp_iou3d(topbox, rows + k * 7), sigma);
+      sc[k] = (k != top && v > prune) ? v : -1.f;
+    }
+    ++n_sel;
+    __syncthreads();
+  }
+  return n_sel;
 }
 
-__device__ __forceinline__ void dt_write(const float* __restrict__ bx, const float* __restrict__ fu, int idx, int ncls, int dim,
-                                         int bottom, long long o, float* __restrict__ out_boxes, float* __restrict__ out_scores,
-                                         int* __restrict__ out_labels) {
+// sel [B][K] / sel_score [B][K]: the selected members of a segment, in selection order, at the segment's first positions;
+// keep [B][K] = 1 there, 0 on the rest of the segment
+__global__ __launch_bounds__(DT_PP_THREADS) void k_dt_soft(const float* __restrict__ rows7, const float* __restrict__ fused,
+                                                           const int* __restrict__ cand, const int* __restrict__ seg, int nq, int ncls,
+                                                           int K, float sigma, float prune, int* __restrict__ sel,
+                                                           float* __restrict__ sel_score, unsigned char* __restrict__ keep) {
+  __shared__ float sb[DT_LDS_CAP * 7];
+  __shared__ float sc[DT_MAX_K];
+  __shared__ float red_v[DT_PP_THREADS];
+  __shared__ int red_i[DT_PP_THREADS];
+  __shared__ float topbox[7];
+  const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  const int start = seg[((long long)b * ncls + c) * 2], end = seg[((long long)b * ncls + c) * 2 + 1];
+  const int cnt = end - start;
+  if (cnt <= 0) return;
+  const long long base = (long long)b * K + start;
+  const float* rows = rows7 + base * 7;
+  const float* fu = fused + (long long)b * nq * ncls;
+  for (int r = t; r < cnt; r += DT_PP_THREADS) sc[r] = fu[cand[base + r]];
+  int n_sel;
+  if (cnt <= DT_LDS_CAP) {
+    for (int r = t; r < cnt * 7; r += DT_PP_THREADS) sb[r] = rows[r];
+    __syncthreads();
+    n_sel = dt_soft_loop(sb, cnt, sigma, prune, sc, red_v, red_i, topbox, cand + base, sel + base, sel_score + base);
+  } else {
+    __syncthreads();
+    n_sel = dt_soft_loop(rows, cnt, sigma, prune, sc, red_v, red_i, topbox, cand + base, sel + base, sel_score + base);
+  }
+  for (int r = t; r < cnt; r += DT_PP_THREADS) keep[base + r] = r < n_sel ? 1 : 0;
+}
+
+// ---- MERGE: greedy sweep over rows[0 .. cnt) (7 floats each, best first) with the medians; flag 0 live, 1 absorbed, 2 absorbed in
+//      the running step.  merged: the segment's [cnt][7] output (rows of absorbed boxes are left unwritten: the emit skips them) ----
+__device__ __forceinline__ void dt_merge_sweep(const float* rows, int cnt, float thr, unsigned char* flag, unsigned short* members,
+                                               float* vals, float* med, int* wsum, int* lasthit, float* __restrict__ merged) {
+  const int t = threadIdx.x;
+  for (int i = 0; i < cnt; ++i) {
+    __syncthreads();                                           // flag[i] is final; the previous step's reads of members / med are over
+    if (flag[i]) continue;
+    const float* bi = rows + i * 7;
+    bool mine = false;
+    for (int j = i + 1 + t; j < cnt; j += DT_PP_THREADS)
+      if (!flag[j] && pp_merge_overlap(bi, rows + j * 7) > thr) { flag[j] = 2; mine = true; }
+    if (mine) *lasthit = i;                                    // any writer writes the same value
+    __syncthreads();
+    if (*lasthit != i) {                                       // nothing absorbed: the median of one value
+      if (t < 7) merged[i * 7 + t] = bi[t];
+      continue;
+    }
+    int m = 0;
+    for (int base = i + 1; base < cnt; base += DT_PP_THREADS) {   // the absorbed rows in ascending order
+      const int j = base + t;
+      const bool hit = j < cnt && flag[j] == 2;
+      int tot;
+      const int pos = m + dt_scan_w<DT_PP_THREADS / 64>(hit, wsum, &tot);
+      if (hit) { flag[j] = 1; members[pos] = (unsigned short)j; }
+      m += tot;
+    }
+    if (t == 0) members[m] = (unsigned short)i;                // itself last, as k_merge_median lists it
+    ++m;
+    for (int col = 0; col < 7; ++col) {
+      __syncthreads();                                         // members are there; the previous column's reads of vals are over
+      for (int a = t; a < m; a += DT_PP_THREADS) vals[a] = rows[(int)members[a] * 7 + col];
+      __syncthreads();
+      // rank selection: the element whose rank (ties by position) is (m-1)/2 and the one of rank m/2
+      for (int a = t; a < m; a += DT_PP_THREADS) {
+        const float va = vals[a];
+        int rank = 0;
+        for (int q = 0; q < m; ++q) {
+          const float vq = vals[q];
+          rank += (vq < va || (vq == va && q < a)) ? 1 : 0;
+        }
+        if (rank == (m - 1) / 2) med[col] = va;
+        if (rank == m / 2) med[7 + col] = va;
+      }
+    }
+    __syncthreads();
+    if (t < 7) merged[i * 7 + t] = pp_median_of(med[t], med[7 + t], m);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(DT_PP_THREADS) void k_dt_merge(const float* __restrict__ rows7, const int* __restrict__ seg, int ncls, int K,
+                                                            float thr, float* __restrict__ merged, unsigned char* __restrict__ keep) {
+  __shared__ float sb[DT_LDS_CAP * 7];
+  __shared__ float vals[DT_MAX_K];
+  __shared__ unsigned short members[DT_MAX_K];
+  __shared__ unsigned char flag[DT_MAX_K];
+  __shared__ float med[14];
+  __shared__ int wsum[DT_PP_THREADS / 64];
+  __shared__ int lasthit;
+  const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  const int start = seg[((long long)b * ncls + c) * 2], end = seg[((long long)b * ncls + c) * 2 + 1];
+  const int cnt = end - start;
+  if (cnt <= 0) return;
+  const long long base = (long long)b * K + start;
+  const float* rows = rows7 + base * 7;
+  for (int r = t; r < cnt; r += DT_PP_THREADS) flag[r] = 0;
+  if (t == 0) lasthit = -1;
+  if (cnt <= DT_LDS_CAP) {
+    for (int r = t; r < cnt * 7; r += DT_PP_THREADS) sb[r] = rows[r];
+    dt_merge_sweep(sb, cnt, thr, flag, members, vals, med, wsum, &lasthit, merged + base * 7);
+  } else {
+    dt_merge_sweep(rows, cnt, thr, flag, members, vals, med, wsum, &lasthit, merged + base * 7);
+  }
+  for (int r = t; r < cnt; r += DT_PP_THREADS) keep[base + r] = flag[r] ? 0 : 1;
+}
+
+// row: the first 7 columns from elsewhere (MERGE), or null
+__device__ __forceinline__ void dt_write(const float* __restrict__ bx, float score, const float* __restrict__ row, int idx, int ncls,
+                                         int dim, int bottom, long long o, float* __restrict__ out_boxes,
+                                         float* __restrict__ out_scores, int* __restrict__ out_labels) {
   const float* c = bx + (long long)(idx / ncls) * dim;
   float* ob = out_boxes + o * dim;
-  for (int k = 0; k < dim; ++k) ob[k] = (k == 2 && bottom) ? dt_bottom_z(c[2], c[5]) : c[k];
-  out_scores[o] = fu[idx];
+  for (int k = 0; k < dim; ++k) ob[k] = (row && k < 7) ? row[k] : (k == 2 && bottom) ? dt_bottom_z(c[2], c[5]) : c[k];
+  out_scores[o] = score;
   out_labels[o] = idx % ncls;
 }
+
+// score_over [B][K] (or null): the score of position r instead of fused[cand[r]]; row_over [B][K][7] (or null): its first 7 columns;
+// tie [B][K] (or null): what orders equal scores before the position does; sort_all: sort even without num_thr
 
 __global__ __launch_bounds__(DT_THREADS) void k_dt_emit(const float* __restrict__ fused, const float* __restrict__ boxes, int nq, int ncls,
                                                         int dim, int K, int P, const int* __restrict__ cand,
                                                         const int* __restrict__ ncand, const unsigned char* __restrict__ keep,
                                                         const float* __restrict__ score_thr, int num_thr, int bottom,
-                                                        float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                        const float* __restrict__ score_over, const float* __restrict__ row_over,
+                                                        const int* __restrict__ tie, int sort_all, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                                                         int* __restrict__ out_labels, int* __restrict__ out_count) {
-  extern __shared__ dt_u64 keys[];                             // [P] when num_thr > 0
+  extern __shared__ dt_u64 keys[];                             // [P] when sorting
   __shared__ int wsum[DT_WAVES];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int N = nq * ncls;
@@ -247,32 +432,41 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_emit(const float* __restrict_
   const float* bx = boxes + (long long)b * nq * dim;
   cand += (long long)b * K;
   const int n = ncand[b];
+  const long long bk = (long long)b * K;
+  const bool sorting = num_thr > 0 || sort_all;
+  const unsigned rmask = (1u << DT_POS_BITS) - 1u;
   int m = 0;
   for (int base = 0; base < n; base += DT_THREADS) {
     const int r = base + tid;
     bool ok = r < n;
     int idx = 0;
+    float sc = 0.f;
     if (ok) {
       idx = cand[r];
-      if (keep) ok = keep[(long long)b * K + r] != 0;
-      if (ok && score_thr) ok = fu[idx] > score_thr[idx % ncls];
+      if (keep) ok = keep[bk + r] != 0;
+      if (ok) sc = score_over ? score_over[bk + r] : fu[idx];
+      if (ok && score_thr) ok = sc > score_thr[idx % ncls];
     }
     int tot;
     const int pos = m + dt_scan(ok, wsum, &tot);
     if (ok) {
-      if (num_thr > 0) keys[pos] = ((dt_u64)(~dt_mono(fu[idx])) << 32) | (unsigned)r;
-      else dt_write(bx, fu, idx, ncls, dim, bottom, (long long)b * K + pos, out_boxes, out_scores, out_labels);
+      if (sorting) keys[pos] = ((dt_u64)(~dt_mono(sc)) << 32) | ((unsigned)(tie ? tie[bk + r] : 0) << DT_POS_BITS) | (unsigned)r;
+      else dt_write(bx, sc, row_over ? row_over + (bk + r) * 7 : nullptr, idx, ncls, dim, bottom, bk + pos, out_boxes, out_scores, out_labels);
     }
     m += tot;
   }
   int count = m;
-  if (num_thr > 0) {
+  if (sorting) {
     __syncthreads();
     for (int i = m + tid; i < P; i += DT_THREADS) keys[i] = DT_PAD;
-    dt_bitonic(keys, P);                                       // descending fused score, ties by the order above
-    count = min(m, num_thr);
-    for (int pos = tid; pos < count; pos += DT_THREADS)
-      dt_write(bx, fu, cand[(int)(unsigned)keys[pos]], ncls, dim, bottom, (long long)b * K + pos, out_boxes, out_scores, out_labels);
+    dt_bitonic(keys, P);                                       // descending score, ties by `tie`, then by the order above
+    if (num_thr > 0) count = min(m, num_thr);
+    for (int pos = tid; pos < count; pos += DT_THREADS) {
+      const int r = (int)((unsigned)keys[pos] & rmask);
+      const int idx = cand[r];
+      dt_write(bx, score_over ? score_over[bk + r] : fu[idx], row_over ? row_over + (bk + r) * 7 : nullptr, idx, ncls, dim, bottom,
+               bk + pos, out_boxes, out_scores, out_labels);
+    }
   }
   for (int pos = count + tid; pos < K; pos += DT_THREADS) {
     const long long o = (long long)b * K + pos;
@@ -307,11 +501,85 @@ static inline int dt_k(int nq, int ncls, int max_num) {
   return (int)(n < max_num ? n : max_num);
 }
 
+// the workspace, in order: cand0 | cand | ncand | seg | rows | keep, then SOFT_NMS: decayed scores; MERGE: merged rows | compacted positions
+struct dt_ws { size_t cand0, cand, ncand, seg, rows, keep, f_aux, i_aux, total; };
+static inline dt_ws dt_layout(size_t B, size_t K, size_t C, int mode) {
+  const bool pp = mode == U3D_DET_TAIL_SOFT_NMS || mode == U3D_DET_TAIL_MERGE;
+  dt_ws w;
+  size_t o = 0;
+  w.cand0 = o; o += dt_align(B * K * 4);
+  w.cand = o; o += dt_align(B * K * 4);
+  w.ncand = o; o += dt_align(B * 4);
+  w.seg = o; o += dt_align(B * C * 2 * 4);
+  w.rows = o; o += dt_align(B * K * (pp ? 7 : 5) * 4);
+  w.keep = o; o += dt_align(B * K);
+  w.f_aux = o;
+  if (mode == U3D_DET_TAIL_SOFT_NMS) o += dt_align(B * K * 4);
+  if (mode == U3D_DET_TAIL_MERGE) o += dt_align(B * K * 7 * 4);
+  w.i_aux = o;
+  if (mode == U3D_DET_TAIL_MERGE) o += dt_align(B * K * 4);
+  w.total = o;
+  return w;
+}
+
+extern "C" int64_t u3d_det_tail_pp_workspace(int32_t batch, int32_t nq, int32_t num_classes, int32_t max_num, int32_t box_dim, int32_t mode) {
+  if (batch <= 0 || nq <= 0 || num_classes <= 0 || max_num <= 0 || (box_dim != 7 && box_dim != 9) || mode < U3D_DET_TAIL_NONE ||
+      mode > U3D_DET_TAIL_MERGE)
+    return -1;
+  return (int64_t)dt_layout((size_t)batch, (size_t)dt_k(nq, num_classes, max_num), (size_t)num_classes, mode).total;
+}
+
 extern "C" int64_t u3d_det_tail_workspace(int32_t batch, int32_t nq, int32_t num_classes, int32_t max_num, int32_t box_dim) {
-  if (batch <= 0 || nq <= 0 || num_classes <= 0 || max_num <= 0 || (box_dim != 7 && box_dim != 9)) return -1;
-  const size_t K = (size_t)dt_k(nq, num_classes, max_num), B = (size_t)batch;
-  return (int64_t)(2 * dt_align(B * K * 4) + dt_align(B * 4) + dt_align(B * num_classes * 2 * 4) + dt_align(B * K * 5 * 4) +
-                   dt_align(B * K));
+  return u3d_det_tail_pp_workspace(batch, nq, num_classes, max_num, box_dim, U3D_DET_TAIL_NMS);
+}
+
+extern "C" int32_t u3d_det_tail_pp(const float* prob, const float* fused, const float* boxes, int32_t batch, int32_t nq, int32_t num_classes,
+                                   int32_t box_dim, int32_t max_num, const float* center_range, float score_threshold, int32_t mode,
+                                   float nms_thr, const float* score_thr, int32_t num_thr, float soft_sigma, float soft_prune,
+                                   float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_count, int32_t* out_off,
+                                   void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  U3D_REQUIRE(prob && fused && boxes && center_range && out_boxes && out_scores && out_labels && out_count && out_off && workspace &&
+              batch > 0 && nq > 0 && num_classes > 0 && max_num > 0 && (box_dim == 7 || box_dim == 9) && mode >= U3D_DET_TAIL_NONE &&
+              mode <= U3D_DET_TAIL_MERGE && (mode != U3D_DET_TAIL_SOFT_NMS || soft_sigma > 0.f), U3D_ERR_ARG);
+  U3D_REQUIRE((long long)nq * num_classes < (1ll << 31) && num_classes <= 65536 && batch <= 65535, U3D_ERR_UNSUPPORTED);
+  const int K = dt_k(nq, num_classes, max_num);
+  U3D_REQUIRE(K <= DT_MAX_K, U3D_ERR_UNSUPPORTED);
+  U3D_REQUIRE(workspace_bytes >= u3d_det_tail_pp_workspace(batch, nq, num_classes, max_num, box_dim, mode), U3D_ERR_WORKSPACE);
+  int P = 1;
+  while (P < K) P <<= 1;
+  const dt_ws l = dt_layout((size_t)batch, (size_t)K, (size_t)num_classes, mode);
+  char* w = (char*)workspace;
+  int* cand0 = (int*)(w + l.cand0);
+  int* cand = (int*)(w + l.cand);
+  int* ncand = (int*)(w + l.ncand);
+  int* seg = (int*)(w + l.seg);
+  float* rows = (float*)(w + l.rows);
+  unsigned char* keep = (unsigned char*)(w + l.keep);
+  float* f_aux = (float*)(w + l.f_aux);
+  int* i_aux = (int*)(w + l.i_aux);
+  const bool nms = mode == U3D_DET_TAIL_NMS, soft = mode == U3D_DET_TAIL_SOFT_NMS, merge = mode == U3D_DET_TAIL_MERGE;
+  const int order = soft ? DT_ORDER_POS : (nms || merge) ? DT_ORDER_SCORE : 0;
+  const bool sorting = num_thr > 0 || merge;
+  U3D_ALLOW_LDS(k_dt_select, DT_MAX_K * 8);
+  U3D_ALLOW_LDS(k_dt_emit, DT_MAX_K * 8);
+  hipLaunchKernelGGL(k_dt_select, dim3(batch), dim3(DT_THREADS), (size_t)P * 8, s, prob, fused, boxes, nq, num_classes, box_dim, K, P,
+                     center_range, score_threshold, order, (soft || merge) ? 7 : 5, cand0, cand, ncand, seg, rows,
+                     merge ? i_aux : (int*)nullptr);
+  if (nms)
+    hipLaunchKernelGGL(k_dt_nms, dim3(num_classes, batch), dim3(DT_NMS_THREADS), 0, s, rows, seg, num_classes, K, nms_thr, keep);
+  // SOFT_NMS: cand0 (the flat index by compacted position) has served k_dt_select; it now takes the selected members
+  if (soft)
+    hipLaunchKernelGGL(k_dt_soft, dim3(num_classes, batch), dim3(DT_PP_THREADS), 0, s, rows, fused, cand, seg, nq, num_classes, K,
+                       soft_sigma, soft_prune, cand0, f_aux, keep);
+  if (merge)
+    hipLaunchKernelGGL(k_dt_merge, dim3(num_classes, batch), dim3(DT_PP_THREADS), 0, s, rows, seg, num_classes, K, nms_thr, f_aux, keep);
+  hipLaunchKernelGGL(k_dt_emit, dim3(batch), dim3(DT_THREADS), sorting ? (size_t)P * 8 : 0, s, fused, boxes, nq, num_classes, box_dim, K, P,
+                     soft ? cand0 : cand, ncand, order ? keep : (const unsigned char*)nullptr, score_thr, num_thr,
+                     mode != U3D_DET_TAIL_DECODE ? 1 : 0, soft ? f_aux : (const float*)nullptr, merge ? f_aux : (const float*)nullptr,
+                     merge ? i_aux : (const int*)nullptr, merge ? 1 : 0, out_boxes, out_scores, out_labels, out_count);
+  hipLaunchKernelGGL(k_dt_offsets, dim3(1), dim3(64), 0, s, out_count, batch, out_off);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
 }
 
 extern "C" int32_t u3d_det_tail(const float* prob, const float* fused, const float* boxes, int32_t batch, int32_t nq, int32_t num_classes,
@@ -319,34 +587,7 @@ extern "C" int32_t u3d_det_tail(const float* prob, const float* fused, const flo
                                 float nms_thr, const float* score_thr, int32_t num_thr, float* out_boxes, float* out_scores,
                                 int32_t* out_labels, int32_t* out_count, int32_t* out_off, void* workspace, int64_t workspace_bytes,
                                 u3d_stream s) {
-  U3D_REQUIRE(prob && fused && boxes && center_range && out_boxes && out_scores && out_labels && out_count && out_off && workspace &&
-              batch > 0 && nq > 0 && num_classes > 0 && max_num > 0 && (box_dim == 7 || box_dim == 9) &&
-              (mode == U3D_DET_TAIL_NONE || mode == U3D_DET_TAIL_NMS || mode == U3D_DET_TAIL_DECODE), U3D_ERR_ARG);
-  U3D_REQUIRE((long long)nq * num_classes < (1ll << 31) && num_classes <= 65536 && batch <= 65535, U3D_ERR_UNSUPPORTED);
-  const int K = dt_k(nq, num_classes, max_num);
-  U3D_REQUIRE(K <= DT_MAX_K, U3D_ERR_UNSUPPORTED);
-  U3D_REQUIRE(workspace_bytes >= u3d_det_tail_workspace(batch, nq, num_classes, max_num, box_dim), U3D_ERR_WORKSPACE);
-  int P = 1;
-  while (P < K) P <<= 1;
-  const size_t B = (size_t)batch;
-  char* w = (char*)workspace;
-  int* cand0 = (int*)w; w += dt_align(B * K * 4);
-  int* cand = (int*)w; w += dt_align(B * K * 4);
-  int* ncand = (int*)w; w += dt_align(B * 4);
-  int* seg = (int*)w; w += dt_align(B * num_classes * 2 * 4);
-  float* bev = (float*)w; w += dt_align(B * K * 5 * 4);
-  unsigned char* keep = (unsigned char*)w;
-  const int nms = mode == U3D_DET_TAIL_NMS;
-  U3D_ALLOW_LDS(k_dt_select, DT_MAX_K * 8);
-  U3D_ALLOW_LDS(k_dt_emit, DT_MAX_K * 8);
-  hipLaunchKernelGGL(k_dt_select, dim3(batch), dim3(DT_THREADS), (size_t)P * 8, s, prob, fused, boxes, nq, num_classes, box_dim, K, P,
-                     center_range, score_threshold, nms, cand0, cand, ncand, seg, bev);
-  if (nms)
-    hipLaunchKernelGGL(k_dt_nms, dim3(num_classes, batch), dim3(DT_NMS_THREADS), 0, s, bev, seg, num_classes, K, nms_thr, keep);
-  hipLaunchKernelGGL(k_dt_emit, dim3(batch), dim3(DT_THREADS), num_thr > 0 ? (size_t)P * 8 : 0, s, fused, boxes, nq, num_classes, box_dim,
-                     K, P, cand, ncand, nms ? keep : (const unsigned char*)nullptr, score_thr, num_thr, mode != U3D_DET_TAIL_DECODE ? 1 : 0,
-                     out_boxes, out_scores, out_labels, out_count);
-  hipLaunchKernelGGL(k_dt_offsets, dim3(1), dim3(64), 0, s, out_count, batch, out_off);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
+  U3D_REQUIRE(mode == U3D_DET_TAIL_NONE || mode == U3D_DET_TAIL_NMS || mode == U3D_DET_TAIL_DECODE, U3D_ERR_ARG);
+  return u3d_det_tail_pp(prob, fused, boxes, batch, nq, num_classes, box_dim, max_num, center_range, score_threshold, mode, nms_thr,
+                         score_thr, num_thr, 1.f, 0.f, out_boxes, out_scores, out_labels, out_count, out_off, workspace, workspace_bytes, s);
 }

@@ -7,6 +7,7 @@
 //                  reference is numpy + shapely on the CPU
 #include "common.h"
 #include "box_iou.h"
+#include "postproc_math.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // soft-NMS: one workgroup per class.  out_idx / out_score: [num_classes][n] (selection order), out_cnt [num_classes].
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(SNMS_THREADS) void k_soft_nms(const float* __restri
       float v = sc[k];
       if (v < 0.f) continue;
       const float iou = pp_iou3d(topbox, boxes + (long long)mem[k] * 7);
-      v *= expf(-iou * iou / sigma);
+      v = pp_soft_decay(v, iou, sigma);
       sc[k] = (k != top && v > prune) ? v : -1.f;
     }
     ++cnt;
@@ -88,34 +89,9 @@ extern "C" int32_t u3d_soft_nms(const float* boxes, const float* scores, const i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// box merging.  Input boxes are ALREADY sorted by descending score.  The reference hands its LiDAR boxes (x, y, z, dx, dy, dz, yaw) to
-// a routine written for (x3d, y3d, z3d, l, h, w, yaw) camera boxes, so the polygon lives in the (x, z) plane with extents (dx, dz),
-// rotated by -yaw, and the "height" interval is [y - dy, y]: reproduced as is.
+// box merging.  Input boxes are ALREADY sorted by descending score.  The overlap is pp_merge_overlap (postproc_math.h), which keeps
+// the reference's camera-axis reading of the LiDAR columns.
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ static float pp_merge_overlap(const float* p, const float* q) {
-  Q2 a[4], b[4];
-  pp_rect(0.f, 0.f, p[3], p[5], -p[6], a);
-  pp_rect(q[0] - p[0], q[2] - p[2], q[3], q[5], -q[6], b);
-  float ax0 = a[0].x, ax1 = a[0].x, az0 = a[0].y, az1 = a[0].y, bx0 = b[0].x, bx1 = b[0].x, bz0 = b[0].y, bz1 = b[0].y;
-  for (int i = 1; i < 4; ++i) {
-    ax0 = fminf(ax0, a[i].x); ax1 = fmaxf(ax1, a[i].x); az0 = fminf(az0, a[i].y); az1 = fmaxf(az1, a[i].y);
-    bx0 = fminf(bx0, b[i].x); bx1 = fmaxf(bx1, b[i].x); bz0 = fminf(bz0, b[i].y); bz1 = fmaxf(bz1, b[i].y);
-  }
-  const float ay1 = fmaxf(p[1], p[1] - p[4]), ay0 = fminf(p[1], p[1] - p[4]);
-  const float by1 = fmaxf(q[1], q[1] - q[4]), by0 = fminf(q[1], q[1] - q[4]);
-  if (ax1 < bx0 || ax0 > bx1 || az1 < bz0 || az0 > bz1 || ay1 < by0 || ay0 > by1) return 0.f;
-  const float area1 = fabsf(p[3] * p[5]), area2 = fabsf(q[3] * q[5]);
-  // clip in whichever orientation the corner lists have (negative extents flip it): use absolute areas
-  Q2 bb[4] = {b[0], b[1], b[2], b[3]};
-  float cross = (b[1].x - b[0].x) * (b[2].y - b[1].y) - (b[1].y - b[0].y) * (b[2].x - b[1].x);
-  if (cross < 0.f) { bb[1] = b[3]; bb[3] = b[1]; }
-  const float shared = pp_inter_area(a, bb);
-  const float shared_y = fminf(by1, ay1) - fmaxf(by0, ay0);
-  const float inter = shared_y * shared;
-  const float uni = (by1 - by0) * area2 + (ay1 - ay0) * area1;
-  return inter / (uni - inter);
-}
-
 __global__ void k_merge_mask(const float* __restrict__ boxes, const int* __restrict__ labels, int n, float thr,
                              unsigned long long* __restrict__ mask, int nw) {
   const int i = blockIdx.x, j = blockIdx.y * 64 + threadIdx.x;
@@ -183,7 +159,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void k_merge_median(const float* __r
     }
   }
   __syncthreads();
-  if (tid < 7) out[(long long)i * 7 + tid] = (m & 1) ? lo[tid] : 0.5f * (lo[tid] + hi[tid]);      // numpy's median: mean of the two middle values
+  if (tid < 7) out[(long long)i * 7 + tid] = pp_median_of(lo[tid], hi[tid], m);
 }
 
 extern "C" int64_t u3d_box_merge_workspace(int32_t n) { return (int64_t)n * ((n + 63) / 64) * 8; }

@@ -154,6 +154,9 @@ _SIGS = {
     "u3d_nms3d": (_I, [_P, _P, _I, C.c_float, _P, _P, _L, _P]),
     "u3d_det_tail_workspace": (_L, [_I, _I, _I, _I, _I]),
     "u3d_det_tail": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, C.c_float, _I, C.c_float, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "u3d_det_tail_pp_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
+    "u3d_det_tail_pp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, C.c_float, _I, C.c_float, _P, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P,
+                             _P, _L, _P]),
     "u3d_tta_merge_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
     "u3d_tta_merge": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, C.c_float, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "u3d_iou3d_rotated_aligned": (_I, [_P, _P, _I, _P, _P]),
@@ -1358,8 +1361,9 @@ def box_merge(boxes_sorted, labels_sorted, thr):
     if n == 0:
         return merged, keep.bool()
     ws = torch.empty(max(int(lib().u3d_box_merge_workspace(n)), 16), dtype=torch.uint8, device=dev)
-    _check(lib().u3d_box_merge(_ptr(boxes_sorted.contiguous().float()), _ptr(labels_sorted.contiguous().int()), n, float(thr), _ptr(merged),
-                               _ptr(keep), _ptr(ws), ws.numel(), _stream()), "box_merge")
+    # named locals: the copy of a column slice must stay alive until the launch, or the allocator hands its block to the labels' copy
+    b, l = boxes_sorted.contiguous().float(), labels_sorted.contiguous().int()
+    _check(lib().u3d_box_merge(_ptr(b), _ptr(l), n, float(thr), _ptr(merged), _ptr(keep), _ptr(ws), ws.numel(), _stream()), "box_merge")
     return merged, keep.bool()
 
 
@@ -2283,7 +2287,7 @@ def tta_merge(boxes, scores, labels, det_off, params, views, coord, num_classes,
 # --------------------------------------------------------------------------------------------------
 # The batched inference tail (csrc/det_tail.hip)
 # --------------------------------------------------------------------------------------------------
-DET_TAIL_NONE, DET_TAIL_NMS, DET_TAIL_DECODE = 0, 1, 2
+DET_TAIL_NONE, DET_TAIL_NMS, DET_TAIL_DECODE, DET_TAIL_SOFT_NMS, DET_TAIL_MERGE = 0, 1, 2, 3, 4
 DET_TAIL_MAX_K = 8192
 
 
@@ -2331,10 +2335,11 @@ class DetBatch:
 
 
 def det_tail(prob, fused, boxes, max_num, center_range, score_threshold=None, mode=DET_TAIL_NONE, nms_thr=0.0, score_thr=None,
-             num_thr=None):
+             num_thr=None, soft_sigma=0.3, soft_prune=1e-3):
     """The decode selection + post-processing of every scene in one call, no host sync (csrc/det_tail.hip; include/u3d_hip.h states
     the per-scene semantics).  prob / fused f32 [B,Q,C], boxes f32 [B,Q,7|9] gravity centre, center_range f32 [6] device tensor,
-    score_thr f32 [C] device tensor or None, mode DET_TAIL_NONE / DET_TAIL_NMS / DET_TAIL_DECODE -> DetBatch with K = min(max_num, Q*C)."""
+    score_thr f32 [C] device tensor or None, mode DET_TAIL_NONE / _NMS / _DECODE / _SOFT_NMS (soft_sigma, soft_prune; the scores are the
+    decayed ones) / _MERGE (nms_thr is the overlap threshold; scene-wide score order) -> DetBatch with K = min(max_num, Q*C)."""
     B, Q, Cn = prob.shape
     dim = boxes.shape[-1]
     dev = prob.device
@@ -2351,12 +2356,17 @@ def det_tail(prob, fused, boxes, max_num, center_range, score_threshold=None, mo
     out = DetBatch(torch.empty((B, K, dim), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.float32, device=dev),
                    torch.empty((B, K), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
                    torch.empty((B + 1,), dtype=torch.int32, device=dev))
-    wsb = int(lib().u3d_det_tail_workspace(B, Q, Cn, int(max_num), dim))
+    if mode == DET_TAIL_SOFT_NMS and not float(soft_sigma) > 0.0:
+        raise U3DError(f"det_tail: soft_sigma must be positive, got {soft_sigma}")
+    wsb = int(lib().u3d_det_tail_pp_workspace(B, Q, Cn, int(max_num), dim, int(mode)))
+    if wsb <= 0:
+        raise U3DError(f"det_tail: unknown mode {mode}")
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
     # named locals: a copy that .contiguous() makes must stay alive until the launch, or the allocator hands its block to the next one
     p, f, bx, rng = prob.contiguous(), fused.contiguous(), boxes.contiguous(), center_range.contiguous()
     thr = None if score_thr is None else score_thr.contiguous()
-    _check(lib().u3d_det_tail(_ptr(p), _ptr(f), _ptr(bx), B, Q, Cn, dim, int(max_num), _ptr(rng), float(score_threshold or 0.0),
-                              int(mode), float(nms_thr), _ptr(thr), int(num_thr or 0), _ptr(out.boxes),
-                              _ptr(out.scores), _ptr(out.labels), _ptr(out.count), _ptr(out.off), _ptr(ws), wsb, _stream()), "det_tail")
+    _check(lib().u3d_det_tail_pp(_ptr(p), _ptr(f), _ptr(bx), B, Q, Cn, dim, int(max_num), _ptr(rng), float(score_threshold or 0.0),
+                                 int(mode), float(nms_thr), _ptr(thr), int(num_thr or 0), float(soft_sigma), float(soft_prune),
+                                 _ptr(out.boxes), _ptr(out.scores), _ptr(out.labels), _ptr(out.count), _ptr(out.off), _ptr(ws), wsb,
+                                 _stream()), "det_tail")
     return out

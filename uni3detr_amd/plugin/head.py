@@ -445,37 +445,38 @@ class Uni3DETRHead(nn.Module):
 
     def get_bboxes_batched(self, preds_dicts, img_metas, rescale=False):
         """get_bboxes for all scenes at once -> native.DetBatch (padded device tensors + count / off); `.to_list()` gives get_bboxes'
-        format, scene by scene bit-identical to it.  post_processing None and 'nms' (with score_thr, scalar or per class, and num_thr)
-        run entirely in one device call (u3d_det_tail) after a handful of batched torch launches, with no host sync; where
-        get_bboxes' `torch.argsort(-scores)` leaves equal scores under num_thr in an open order, they keep the order the NMS emitted.
-        'soft_nms' and 'box_merging' are NOT batched: the decode runs in the device call, then every scene goes through the same
-        per-scene routines as get_bboxes, with their launches and host synchronisations, and the results are packed."""
+        format, scene by scene bit-identical to it.  Every post_processing the head knows - None, 'nms', 'soft_nms' (gaussian_sigma,
+        prune_threshold; the scores are the decayed ones) and 'box_merging' (overlap threshold 0.1, scene-wide score order) - with
+        score_thr, scalar or per class, and num_thr runs entirely in one device call (u3d_det_tail_pp) after a handful of batched
+        torch launches, with no per-scene loop and no host sync; where get_bboxes' `torch.argsort(-scores)` leaves equal scores under
+        num_thr in an open order, they keep the order the post-processing emitted."""
         from .. import native as nv
         pp = self.post_processing
         coder = self.bbox_coder
         if pp is not None and pp["type"] not in ("nms", "soft_nms", "box_merging"):
             raise NotImplementedError(pp["type"] + " not implemented.")
-        if pp is None or pp["type"] == "nms":
-            prob, fused, boxes, rng = coder.batched_prelude(preds_dicts)
-            thr = None
-            if pp is not None and "score_thr" in pp:
-                thr = pp["score_thr"]
-                if isinstance(thr, (list, tuple)):
-                    assert len(thr) == self.num_classes
-                else:
-                    thr = [thr] * prob.shape[-1]
-                key = (prob.device, tuple(float(v) for v in thr))
-                # one host-to-device copy per setting and device.  Keyed by value, so no invalidation is needed (nor done) when
-                # post_processing is mutated in place: a changed score_thr is a changed key
-                if getattr(self, "_score_thr_dev", (None, None))[0] != key:
-                    self._score_thr_dev = (key, prob.new_tensor(key[1]))
-                thr = self._score_thr_dev[1]
-            if pp is not None and "num_thr" in pp and int(pp["num_thr"]) <= 0:
-                raise ValueError("num_thr must be positive")
-            if pp is None:
-                return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, mode=nv.DET_TAIL_NONE)
-            return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, mode=nv.DET_TAIL_NMS, nms_thr=pp["nms_thr"],
-                               score_thr=thr, num_thr=pp.get("num_thr"))
-        dec = coder.decode_batched(preds_dicts)
-        dets = [self._post_process_scene(b, s, l) for b, s, l in dec.to_list()]
-        return nv.DetBatch.from_list(dets, dec.scores.shape[1], dec.boxes.shape[2], dec.boxes.device)
+        prob, fused, boxes, rng = coder.batched_prelude(preds_dicts)
+        if pp is None:
+            return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, mode=nv.DET_TAIL_NONE)
+        thr = None
+        if "score_thr" in pp:
+            thr = pp["score_thr"]
+            if isinstance(thr, (list, tuple)):
+                assert len(thr) == self.num_classes
+            else:
+                thr = [thr] * prob.shape[-1]
+            key = (prob.device, tuple(float(v) for v in thr))
+            # one host-to-device copy per setting and device.  Keyed by value, so no invalidation is needed (nor done) when
+            # post_processing is mutated in place: a changed score_thr is a changed key
+            if getattr(self, "_score_thr_dev", (None, None))[0] != key:
+                self._score_thr_dev = (key, prob.new_tensor(key[1]))
+            thr = self._score_thr_dev[1]
+        if "num_thr" in pp and int(pp["num_thr"]) <= 0:
+            raise ValueError("num_thr must be positive")
+        if pp["type"] == "nms":
+            kw = dict(mode=nv.DET_TAIL_NMS, nms_thr=pp["nms_thr"])
+        elif pp["type"] == "soft_nms":
+            kw = dict(mode=nv.DET_TAIL_SOFT_NMS, soft_sigma=pp["gaussian_sigma"], soft_prune=pp["prune_threshold"])
+        else:
+            kw = dict(mode=nv.DET_TAIL_MERGE, nms_thr=0.1)               # ref :881-891: overlapped_thres=0.1
+        return nv.det_tail(prob, fused, boxes, coder.max_num, rng, coder.score_threshold, score_thr=thr, num_thr=pp.get("num_thr"), **kw)
