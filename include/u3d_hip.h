@@ -166,6 +166,35 @@ int32_t u3d_igemm_fwd_add_bf16(const void* in, const void* w, const int32_t* nbr
  * models/dense_heads/uni3detr_head.py:365-387.)  U3D_ERR_UNSUPPORTED unless K % 64 == 0 and N % 64 == 0. */
 int32_t u3d_linear_bf16(const void* x, const void* w, const float* bias, int32_t relu, void* out, const int32_t* m_dev,
                         int32_t m_cap, int32_t k, int32_t n, u3d_stream s);
+/* Inference: eval-mode BatchNorm folded into the convolution in front of it.  In eval mode BatchNorm is y = x * scale + shift per
+ * channel, scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale (ref: the conv -> BatchNorm -> ReLU chains of
+ * sparse_encoder_hd.py:71-104, second_3d.py:52-76, second3d_fpn.py:60-90 under model.eval()).
+ *
+ * u3d_bn_fold_batched folds every pair of a model in ONE launch.  jobs: DEVICE array of njobs records of u3d_bn_fold_job_bytes()
+ * bytes, natural C layout
+ *   { const float* w; const float *gamma, *beta, *mean, *var; void* w_folded; float* shift; int64_t sk, sa, sb; float eps;
+ *     int32_t kvol, cout, cin, scale_only, first_block; }
+ * w: the f32 master weight, element (k, co, ci) at w[k * sk + co * sa + ci * sb] (element strides: the checkpoint layouts
+ * [kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW] are read in place); gamma / beta / mean / var f32 [cout].  Written: w_folded bf16
+ * [kvol][cout][cin] (the n-major layout of the LDS-DMA kernels) = bf16_rne(w * scale[co]) with scale computed in f32, and shift f32
+ * [cout]; scale_only != 0: only w_folded is written and shift may be NULL (a second copy of a layer's weights whose shift another job
+ * leaves).  cin % 4 == 0, w_folded 8-byte aligned.  first_block = the sum of u3d_bn_fold_job_blocks(kvol, cout, cin) over the jobs
+ * before this one, total_blocks = that sum over all jobs. */
+int64_t u3d_bn_fold_job_bytes(void);
+int32_t u3d_bn_fold_job_blocks(int32_t kvol, int32_t cout, int32_t cin);
+int32_t u3d_bn_fold_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
+/* out = act(conv(in; w_folded) + shift[col]) in one pass: bf16 in / w_folded / out, f32 shift [cout] (required), relu != 0 applies
+ * max(., 0).  w_folded is n-major [kvol][Cout][Cin] (u3d_bn_fold_batched); nbr / ld as u3d_igemm_fwd_bf16 (NULL for kvol == 1).  The
+ * kernels are the LDS-DMA kernels of u3d_igemm_fwd_bf16 with the epilogue u3d_linear_bf16 uses; a direct-operand kernel is never
+ * picked.  Rows at or past *n_out_dev are left untouched.  With shift == 0 and relu == 0 the result equals u3d_igemm_fwd_bf16
+ * (transpose_w = 1) on the same weights bit for bit.  U3D_ERR_UNSUPPORTED unless Cin % 64 == 0 and Cout % 64 == 0. */
+int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift, int32_t relu,
+                                  void* out, const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
+                                  u3d_stream s);
+/* The kernel u3d_igemm_fwd_affine_bf16 takes for a shape: *kernel = 0 two-phase 256 x 256, 1 / 2 eight-phase 256 / 192 x 256, 3 / 4
+ * eight-phase 256 / 192 x 128, 5 two-phase 256 x 128, 6 128 x 128, 7 128 x 64; *rows x *cols: its tile. */
+int32_t u3d_igemm_fwd_affine_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* kernel,
+                                  int32_t* rows, int32_t* cols);
 /* Split-bf16 convolution: f32-grade products on the bf16 matrix pipe, for the modules the reference keeps in fp32 (ref:
  * models/pts_encoder/sparse_encoder_hd.py:62-64 fp16_enabled=False, models/detectors/uni3detr.py:150-151; SECOND3D is never wrapped in
  * auto_fp16).  An f32 row matrix x travels as two bf16 planes (u3d_split_rows_f32: hi = bf16(x), lo = bf16(x - hi), stacked as rows

@@ -1,0 +1,92 @@
+"""Eval forward, ms per batch: InferenceModel (eval-mode BatchNorm folded into the convolutions) against model.eval(), same process,
+the two paths alternating, medians of the replays after warm-up.  Needs the GPU.
+
+    python tools/infer_bench.py [--reps 20] [--warmup 5]
+
+Workloads: the benched SUN RGB-D shape (B = 8 scenes of 20 000 points) and a smaller batch (B = 2, 12 000 points), both on the
+SUN RGB-D model in bf16 precision.  Per workload one JSON line: feature extractor (voxelize + encoder + SECOND3D + FPN) and the whole
+simple_test_batched(on_device=True), folded and unfolded, and the number of u3d_bn_apply launches per forward.
+"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import projects.mmdet3d_plugin  # noqa: E402,F401
+from oracle.weights import seeded_tensor  # noqa: E402
+from uni3detr_amd import native as nv  # noqa: E402
+from uni3detr_amd.configs.sunrgbd import model as MODEL_CFG  # noqa: E402
+from uni3detr_amd.inference import InferenceModel  # noqa: E402
+from uni3detr_amd.registry import build_model  # noqa: E402
+from uni3detr_amd.synth import room_scene  # noqa: E402
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    model = build_model(copy.deepcopy(MODEL_CFG))
+    model.load_state_dict({k: seeded_tensor(k, tuple(v.shape), 3) for k, v in model.state_dict().items()})
+    model = model.to(dev).set_precision("bf16").eval()
+    inf = InferenceModel(model)
+    for name, B, npts in (("sunrgbd_b8_20000", 8, 20000), ("sunrgbd_b2_12000", 2, 12000)):
+        pts = [torch.from_numpy(room_scene(i, npts)[0]).to(dev) for i in range(B)]
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):      # (the unfolded head needs the autocast; the folded scope brings its own)
+            paths = {
+                "features_unfolded": lambda: model.extract_pts_feat(pts),
+                "features_folded": lambda: inf.extract_pts_feat(pts),
+                "detect_unfolded": lambda: model.simple_test_batched(None, pts, on_device=True),
+                "detect_folded": lambda: inf.simple_test_batched(None, pts, on_device=True),
+            }
+            calls = {}
+            orig = nv.bn_apply
+            for k in ("features_unfolded", "features_folded"):
+                n = [0]
+
+                def counting(*args, _n=n, **kw):
+                    _n[0] += 1
+                    return orig(*args, **kw)
+                nv.bn_apply = counting
+                try:
+                    paths[k]()
+                finally:
+                    nv.bn_apply = orig
+                calls[k] = n[0]
+            # alternate the paths round by round: drift of the box hits both alike
+            for fn in paths.values():
+                timed(fn, 0, a.warmup)
+            samples = {k: [] for k in paths}
+            for _ in range(a.reps):
+                for k, fn in paths.items():
+                    samples[k] += timed(fn, 1, 0)
+        res = {k: round(statistics.median(v), 3) for k, v in samples.items()}
+        res.update(workload=name, batch=B, points=npts, reps=a.reps, bn_apply_unfolded=calls["features_unfolded"],
+                   bn_apply_folded=calls["features_folded"], folded_layers=len(inf.folded), unfolded_layers=len(inf.unfolded))
+        print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -1289,8 +1289,9 @@ static const GldsKernel GLDS_KERNELS[G_COUNT] = {
 // what the launch must do besides the convolution: PLAIN (u3d_igemm_fwd_bf16), BIAS_RELU (u3d_linear_bf16), ADD = + bf16 addend
 // (u3d_igemm_fwd_add_bf16), F32 / F32_ADD = f32 output without / with an f32 addend (u3d_igemm_fwd_split_bf16; its statistics do not
 // change the kernel), STATS = + BatchNorm statistics (u3d_igemm_fwd_stats_bf16), BN_BWD = + BatchNorm-backward sums, addend optional
-// (u3d_igemm_dgrad_bnstats_bf16)
-enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_BN_BWD };
+// (u3d_igemm_dgrad_bnstats_bf16), AFFINE = + per-column f32 shift and optional ReLU on a CONVOLUTION (u3d_igemm_fwd_affine_bf16: an
+// eval-mode BatchNorm folded into the weights, bn_fold.hip)
+enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_BN_BWD, EPI_AFFINE };
 
 struct FwdPlan {
   DirectPlan direct;             // direct.slot >= 0: a direct-operand kernel (igemm_direct.hip), else
@@ -1318,6 +1319,8 @@ constexpr int GLDS8N_MIN_WGS = 160;       // ... and enough 256-row workgroups t
 //      256 x 128 eight-phase (192 x 128 when R192(cout / 128)).
 //   4. cout % 128 == 0: 128 x 128.
 //   5. 128 x 64.
+//   AFFINE never takes rule 1 (the direct-operand kernels read `bias` as an addend) and follows rules 2-5; the two-phase 256 x 256
+//      kernel serves it (the shift is the per-column bias, not the addend epilogue it lacks).
 //   F32 / F32_ADD take the tile's f32-output instantiation.  R192(c): a table, kvol > 1 and igemm_rows192(n, c).
 //   Statistics partials of the LDS-DMA kernels: one per row tile, ceil(n / rows).
 static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, bool nmajor, FwdEpi epi) {
@@ -1380,6 +1383,33 @@ extern "C" int32_t u3d_linear_bf16(const void* x, const void* w, const float* bi
   const FwdPlan p = fwd_plan(m_cap, k, n, 1, false, true, EPI_BIAS_RELU);
   if (!p.served()) return U3D_ERR_UNSUPPORTED;
   return fwd_launch(p, x, w, nullptr, 0, out, m_dev, m_cap, k, n, 1, s, bias, relu ? 1 : 0);
+}
+
+// Convolution + per-column f32 shift (+ ReLU) in one pass: conv -> eval-mode BatchNorm -> ReLU with the BatchNorm's scale folded into
+// the n-major weights w_folded[kvol][cout][cin] and its shift passed here (u3d_bn_fold_batched, bn_fold.hip).  The kernels and their
+// epilogue are those of u3d_igemm_fwd_bf16 / u3d_linear_bf16, unchanged: the plan only keeps the launch off the direct-operand kernels.
+// Rows at or past *n_out_dev are left untouched, as u3d_igemm_fwd_bf16 leaves them.
+extern "C" int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift,
+                                             int32_t relu, void* out, const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin,
+                                             int32_t cout, int32_t kvol, u3d_stream s) {
+  U3D_REQUIRE(in && w_folded && out && n_out_dev && shift && kvol > 0 && (nbr || kvol == 1), U3D_ERR_ARG);
+  if (cin <= 0 || cout <= 0 || cin % 64 != 0 || cout % 64 != 0) return U3D_ERR_UNSUPPORTED;
+  if (n_out_cap <= 0) return U3D_OK;
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, true, EPI_AFFINE);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, in, w_folded, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, shift, relu ? 1 : 0);
+}
+// The kernel that launch takes for a shape: *kernel = its index in the plan's table (0 two-phase 256 x 256, 1 / 2 eight-phase
+// 256 / 192 x 256, 3 / 4 eight-phase 256 / 192 x 128, 5 two-phase 256 x 128, 6 128 x 128, 7 128 x 64), *rows x *cols its tile.
+extern "C" int32_t u3d_igemm_fwd_affine_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* kernel,
+                                             int32_t* rows, int32_t* cols) {
+  U3D_REQUIRE(kernel && rows && cols, U3D_ERR_ARG);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, has_nbr != 0, true, EPI_AFFINE);
+  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  *kernel = p.glds;
+  *rows = p.rows;
+  *cols = GLDS_KERNELS[p.glds].cols;
+  return U3D_OK;
 }
 
 // The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (fwd_plan, STATS).  u3d_igemm_fwd_split_bf16 and

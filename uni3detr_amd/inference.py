@@ -1,0 +1,197 @@
+"""Inference with eval-mode BatchNorm folded into the convolutions (bf16 mode).
+
+In eval mode a BatchNorm is a constant per-channel affine map, y = x * scale + shift.  `model.eval()` still runs it as its own pass
+(`u3d_bn_apply`): conv -> BatchNorm -> ReLU is two launches and three trips over the activation tensor, plus a cast and a re-layout
+of the f32 master weight per conv and forward.  InferenceModel multiplies the scale into a bf16 copy of the weights once (ONE launch
+for the whole model, native.bn_fold) and hands the shift to the epilogue of the implicit-GEMM kernels (sparse.conv_affine): one
+launch, one trip, no per-forward weight cast.
+
+    model.set_precision("bf16").eval()
+    inf = InferenceModel(model)
+    det = inf.simple_test_batched(img_metas, points, on_device=True)
+    inf.refresh()            # after parameters or running statistics changed
+    inf.folded, inf.unfolded
+
+What folds: every conv + BatchNorm (+ ReLU) pair whose channel counts are multiples of 64 and whose BatchNorm does nothing else -
+all of SECOND3D, the FPN's extra_blocks and its first level when that is a plain convolution, and in SparseEncoderHD the strided
+64 / 128-channel convolutions and conv_out.  What keeps conv + u3d_bn_apply, exactly as under model.eval() (`inf.unfolded` names each
+layer and the reason):
+  * conv_input and the narrow sparse levels (16 / 32 channels): direct-operand kernels, whose `bias` argument is an addend;
+  * the SubM residual blocks of the 64- / 128-channel levels: the halo kernels (csrc/subm_halo.hip) have no shift epilogue, and
+    conv2's BatchNorm also adds the identity;
+  * the FPN's transposed-conv levels and every level after the first: their BatchNorm apply carries the lattice permutation
+    (row_map) and the running level sum (post_add) for free.
+The model itself is not changed: the folded route is taken only inside InferenceModel's own scope (sparse.fold_scope), and
+`model.simple_test*` called directly stays the unfolded yardstick.
+
+Numerics: not bit-identical to conv + u3d_bn_apply.  Folded: bf16(w * scale) once, output rounded once.  Unfolded: bf16(w), conv
+output rounded to bf16, y rounded.  Both are a few bf16 roundings of the same real number (tests/test_bn_fold_gpu.py holds the folded
+error within 2 x the unfolded one against a float64 restatement).
+"""
+import contextlib
+
+import torch
+from torch import nn
+
+from . import native as nv
+from . import sparse as sp
+
+_WHY_NARROW = "narrow level ({cin} -> {cout} channels): direct-operand kernels read `bias` as an addend"
+_WHY_INPUT = "conv_input: {cin} -> {cout} channels on its own kernel"
+_WHY_BLOCK = "SubM residual block: the halo kernels have no shift epilogue (conv2's BatchNorm also adds the identity)"
+_WHY_DECONV = "transposed conv: its BatchNorm apply carries the lattice permutation (row_map) and the level sum (post_add)"
+_WHY_LEVEL = "FPN level sum rides this BatchNorm apply (post_add)"
+
+
+def _wide(cin, cout):
+    return cin % 64 == 0 and cout % 64 == 0
+
+
+def classify(model):
+    """-> (folded, unfolded): folded = [(name, weight parameter, layout, BatchNorm module)], unfolded = [(name, reason)], in forward
+    order.  `name` is the convolution's module path.  Needs no device."""
+    from .plugin.dense import SECOND3D, SECOND3DFPN
+    from .plugin.sparse_encoder import SparseBasicBlock, SparseEncoderHD
+    names = {id(m): n for n, m in model.named_modules()}
+    folded, unfolded = [], []
+
+    def pair(conv, bn, weight, layout, cin, cout, why=None):
+        name = names[id(conv)]
+        if why is None and not _wide(cin, cout):
+            why = _WHY_NARROW.format(cin=cin, cout=cout)
+        if why is None and not (isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.affine and bn.track_running_stats):
+            why = "BatchNorm without affine parameters or running statistics"
+        if why is None:
+            folded.append((name, weight, layout, bn))
+        else:
+            unfolded.append((name, why))
+
+    enc = getattr(model, "pts_middle_encoder", None)
+    if isinstance(enc, SparseEncoderHD):
+        c = enc.conv_input[0]
+        pair(c, enc.conv_input[1], c.weight, "dhwio", c.cin, c.cout, _WHY_INPUT.format(cin=c.cin, cout=c.cout))
+        for stage in enc.encoder_layers:
+            for m in stage:
+                if isinstance(m, SparseBasicBlock):
+                    for conv, bn in ((m.conv1, m.bn1), (m.conv2, m.bn2)):
+                        pair(conv, bn, conv.weight, "dhwio", conv.cin, conv.cout, _WHY_BLOCK if _wide(conv.cin, conv.cout) else None)
+                else:
+                    pair(m[0], m[1], m[0].weight, "dhwio", m[0].cin, m[0].cout)
+        c = enc.conv_out[0]
+        pair(c, enc.conv_out[1], c.weight, "dhwio", c.cin, c.cout)
+    elif enc is not None:
+        raise TypeError(f"InferenceModel knows SparseEncoderHD, not {type(enc).__name__}")
+    bb = getattr(model, "pts_backbone", None)
+    if isinstance(bb, SECOND3D):
+        for blk in bb.blocks:
+            mods = list(blk)
+            for j in range(0, len(mods), 3):
+                pair(mods[j], mods[j + 1], mods[j].weight, "oidhw", mods[j].in_channels, mods[j].out_channels)
+    elif bb is not None:
+        raise TypeError(f"InferenceModel knows SECOND3D, not {type(bb).__name__}")
+    neck = getattr(model, "pts_neck", None)
+    if isinstance(neck, SECOND3DFPN):
+        for i, d in enumerate(neck.deblocks):
+            if isinstance(d[0], nn.ConvTranspose3d):
+                unfolded.append((names[id(d[0])], _WHY_DECONV))
+            else:
+                pair(d[0], d[1], d[0].weight, "oidhw", d[0].in_channels, d[0].out_channels, _WHY_LEVEL if i > 0 else None)
+        if neck.extra_conv is not None:
+            mods = list(neck.extra_blocks)
+            for j in range(0, len(mods), 3):
+                pair(mods[j], mods[j + 1], mods[j].weight, "oidhw", mods[j].in_channels, mods[j].out_channels)
+    elif neck is not None:
+        raise TypeError(f"InferenceModel knows SECOND3DFPN, not {type(neck).__name__}")
+    return folded, unfolded
+
+
+class InferenceModel:
+    """A Uni3DETR in eval mode and bf16 precision with its foldable BatchNorms folded away.  Owns the folded weights and shifts;
+    the wrapped model keeps its parameters, its state_dict and its own (unfolded) eval path."""
+
+    def __init__(self, model):
+        if model.training:
+            raise RuntimeError("InferenceModel folds eval-mode BatchNorm: call model.eval() first")
+        prec = getattr(model, "precision", None)
+        if prec != "bf16":
+            raise ValueError(f"InferenceModel folds into bf16 weights: set_precision('bf16') first (the model is in {prec!r} mode, "
+                             "which keeps the unfolded path)")
+        self.model = model
+        self._pairs, unfolded = classify(model)
+        self.folded = [p[0] for p in self._pairs]
+        self.unfolded = list(unfolded)
+        self._table, self._sig = None, None
+        self._map = {}
+        self._buffers = []
+        if self._pairs and self._pairs[0][1].is_cuda:
+            self._allocate()
+            self.refresh()
+
+    def _allocate(self):
+        self._buffers = []
+        for _, w, layout, bn in self._pairs:
+            k, cout, cin = nv.conv_weight_strides(tuple(w.shape), layout)[:3]
+            self._buffers.append((torch.empty((k, cout, cin), dtype=torch.bfloat16, device=w.device),
+                                  torch.empty((cout,), dtype=torch.float32, device=w.device)))
+        self._map = {id(p[3]): b for p, b in zip(self._pairs, self._buffers)}
+
+    def refresh(self):
+        """Fold again: after an optimizer step, load_state_dict or a change of the running statistics.  One launch; the job table is
+        rebuilt only when a parameter or buffer moved in memory."""
+        if not self._pairs:
+            return self
+        if not self._buffers or self._buffers[0][0].device != self._pairs[0][1].device:
+            self._allocate()
+            self._table = None
+        sig = tuple(t.data_ptr() for _, w, _, bn in self._pairs for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        if self._table is None or sig != self._sig:
+            rows = []
+            for (_, w, layout, bn), (wf, shift) in zip(self._pairs, self._buffers):
+                for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var):
+                    if t.dtype != torch.float32:
+                        raise TypeError("InferenceModel folds from f32 master parameters and statistics")
+                rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, wf, shift))
+            self._table, self._sig = nv.BnFoldTable(rows), sig
+        self._table.run()
+        return self
+
+    @contextlib.contextmanager
+    def scope(self):
+        """Inside: the wrapped model's forward takes the folded route, under bf16 autocast.  Refuses training mode and enabled
+        gradients."""
+        if self.model.training:
+            raise RuntimeError("InferenceModel: the model went back to training mode")
+        if torch.is_grad_enabled():
+            raise RuntimeError("InferenceModel: gradients are enabled - the folded forward records no autograd graph (use torch.no_grad())")
+        if not self._map:
+            raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
+        # the head runs under bf16 autocast, as Uni3DETR.forward_pts_train runs it in this mode (the fused decoder takes bf16 rows)
+        with sp.fold_scope(self._map), torch.autocast("cuda", dtype=torch.bfloat16):
+            yield self
+
+    @torch.no_grad()
+    def extract_pts_feat(self, points):
+        with self.scope():
+            return self.model.extract_pts_feat(points)
+
+    @torch.no_grad()
+    def head_outputs(self, points, img_metas=None):
+        """The detection head's raw outputs (all_cls_scores, all_bbox_preds, ...) of the folded forward."""
+        with self.scope():
+            feat, fps = self.model.extract_pts_feat(points)
+            return self.model.pts_bbox_head(feat, img_metas, fps)
+
+    @torch.no_grad()
+    def simple_test(self, img_metas, points=None, rescale=False):
+        with self.scope():
+            return self.model.simple_test(img_metas, points, rescale=rescale)
+
+    @torch.no_grad()
+    def simple_test_batched(self, img_metas, points=None, rescale=False, on_device=False):
+        with self.scope():
+            return self.model.simple_test_batched(img_metas, points, rescale=rescale, on_device=on_device)
+
+    @torch.no_grad()
+    def aug_test(self, points, img_metas, **kwargs):
+        with self.scope():
+            return self.model.aug_test(points, img_metas, **kwargs)

@@ -118,6 +118,11 @@ _SIGS = {
     "u3d_split3_job_bytes": (C.c_int64, []),
     "u3d_split3_job_blocks": (_I, [_I, _I, _I]),
     "u3d_split3_weights_batch": (_I, [_P, _I, _I, _P]),
+    "u3d_bn_fold_job_bytes": (C.c_int64, []),
+    "u3d_bn_fold_job_blocks": (_I, [_I, _I, _I]),
+    "u3d_bn_fold_batched": (_I, [_P, _I, _I, _P]),
+    "u3d_igemm_fwd_affine_bf16": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "u3d_igemm_fwd_affine_plan": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "u3d_igemm_direct_split_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "u3d_igemm_dgrad_bnstats_bf16": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "u3d_bn_bwd_finalize_partials": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
@@ -945,6 +950,122 @@ def split3_weights(weight, layout, nmajor, cache=None):
     # new memory every time - its entry would be pruned and re-added at every refresh and keep the job table dirty for ever
     if cache is not None and isinstance(weight, torch.nn.Parameter) and not torch.cuda.is_current_stream_capturing():
         cache.add(weight, layout, nmajor, out)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
+# Inference: eval-mode BatchNorm folded into the convolution in front of it (csrc/bn_fold.hip, u3d_igemm_fwd_affine_bf16)
+# --------------------------------------------------------------------------------------------------
+class BnFoldJob(C.Structure):
+    """One record of u3d_bn_fold_batched's device job table (include/u3d_hip.h)."""
+    _fields_ = [("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
+                ("w_folded", C.c_void_p), ("shift", C.c_void_p), ("sk", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64),
+                ("eps", C.c_float), ("kvol", C.c_int32), ("cout", C.c_int32), ("cin", C.c_int32), ("scale_only", C.c_int32),
+                ("first_block", C.c_int32)]
+
+
+def conv_weight_strides(shape, layout):
+    """(kvol, cout, cin, sk, sa, sb) of a conv parameter of `shape` in its checkpoint layout ("dhwio" [kD,kH,kW,Cin,Cout] / "oidhw"
+    [Cout,Cin,kD,kH,kW]): element (k, co, ci) lies at k * sk + co * sa + ci * sb."""
+    if layout == "dhwio":
+        kd, kh, kw, cin, cout = shape
+        k = kd * kh * kw
+        return k, cout, cin, cin * cout, 1, cout
+    if layout != "oidhw":
+        raise ValueError(f"unknown conv weight layout {layout!r}")
+    cout, cin, kd, kh, kw = shape
+    k = kd * kh * kw
+    return k, cout, cin, 1, cin * k, k
+
+
+def bn_fold_job_table(specs):
+    """Host side of the job table.  specs: dicts with w / gamma / beta / mean / var / w_folded / shift (addresses; shift None with
+    scale_only), shape + layout of the master weight, eps, scale_only.  -> (ctypes array of BnFoldJob, total blocks of the launch)."""
+    assert int(lib().u3d_bn_fold_job_bytes()) == C.sizeof(BnFoldJob)
+    jobs = (BnFoldJob * len(specs))()
+    fb = 0
+    for j, sp in zip(jobs, specs):
+        k, cout, cin, sk, sa, sb = conv_weight_strides(tuple(sp["shape"]), sp["layout"])
+        if cin % 4:
+            raise U3DError(f"bn_fold: Cin = {cin} is not a multiple of 4")
+        so = int(bool(sp.get("scale_only", False)))
+        if not so and not sp.get("shift"):
+            raise U3DError("bn_fold: a job that is not scale_only needs a shift buffer")
+        j.w, j.gamma, j.beta, j.mean, j.var = sp["w"], sp["gamma"], sp["beta"], sp["mean"], sp["var"]
+        j.w_folded, j.shift = sp["w_folded"], sp.get("shift") or None
+        j.sk, j.sa, j.sb, j.eps = sk, sa, sb, float(sp["eps"])
+        j.kvol, j.cout, j.cin, j.scale_only, j.first_block = k, cout, cin, so, fb
+        fb += int(lib().u3d_bn_fold_job_blocks(k, cout, cin))
+    return jobs, fb
+
+
+class BnFoldTable:
+    """A job table on the device + what it points at (kept alive).  run(): ONE launch folds every pair (u3d_bn_fold_batched)."""
+
+    def __init__(self, pairs):
+        """pairs: (weight f32 parameter, layout, gamma, beta, running_mean, running_var (f32 [Cout] each), eps, w_folded bf16
+        [kvol, Cout, Cin], shift f32 [Cout] or None = scale_only)."""
+        specs = []
+        for w, layout, gamma, beta, mean, var, eps, wf, shift in pairs:
+            k, cout, cin = conv_weight_strides(tuple(w.shape), layout)[:3]
+            for t in (w, gamma, beta, mean, var):
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "bn_fold reads contiguous f32 device tensors"
+            assert all(tuple(t.shape) == (cout,) for t in (gamma, beta, mean, var))
+            assert wf.is_cuda and wf.dtype == torch.bfloat16 and wf.is_contiguous() and tuple(wf.shape) == (k, cout, cin)
+            assert shift is None or (shift.is_cuda and shift.dtype == torch.float32 and tuple(shift.shape) == (cout,))
+            specs.append(dict(w=w.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), mean=mean.data_ptr(), var=var.data_ptr(),
+                              w_folded=wf.data_ptr(), shift=None if shift is None else shift.data_ptr(), shape=w.shape, layout=layout,
+                              eps=eps, scale_only=shift is None))
+        jobs, self.total_blocks = bn_fold_job_table(specs)
+        self.njobs, self.pairs = len(specs), list(pairs)
+        self.jobs_dev = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(pairs[0][7].device)
+
+    def run(self):
+        _check(lib().u3d_bn_fold_batched(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), "bn_fold_batched")
+
+
+def bn_fold(pairs):
+    """Fold every (conv weight, BatchNorm) pair in one launch; -> the BnFoldTable (run() folds again after the sources changed)."""
+    t = BnFoldTable(pairs)
+    t.run()
+    return t
+
+
+AFFINE_KERNELS = ("glds_256x256", "glds8_256x256", "glds8_192x256", "glds8_256x128", "glds8_192x128", "glds_256x128", "glds_128x128",
+                  "glds_128x64")
+
+
+def igemm_fwd_affine_plan(n_out, cin, cout, kvol, has_nbr):
+    """(kernel name, tile rows, tile columns) u3d_igemm_fwd_affine_bf16 takes for the shape; None when it does not serve it."""
+    k, r, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if lib().u3d_igemm_fwd_affine_plan(n_out, cin, cout, kvol, int(has_nbr), C.byref(k), C.byref(r), C.byref(c)) != 0:
+        return None
+    return AFFINE_KERNELS[k.value], r.value, c.value
+
+
+def igemm_fwd_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, out=None, tag="spconv_fwd"):
+    """out = act(conv(inp; w_folded) + shift): conv -> eval BatchNorm (-> ReLU) in one launch (u3d_igemm_fwd_affine_bf16).  inp bf16
+    [n_in, cin], w_folded bf16 [kvol, cout, cin] (bn_fold), nbr int32 [kvol, ld] or None for kvol == 1, shift f32 [cout].  Rows at or
+    past *n_out_dev of `out` are left as they are.  A shape the entry does not serve is an error: there is no other route."""
+    kvol, cout, cin = w_folded.shape
+    assert inp.dtype == torch.bfloat16 and w_folded.dtype == torch.bfloat16 and shift.dtype == torch.float32
+    assert inp.shape[1] == cin and tuple(shift.shape) == (cout,) and (nbr is not None or kvol == 1)
+    assert nbr is None or (nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.shape[1] >= n_out)
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=inp.device)
+    assert tuple(out.shape) == (n_out, cout) and out.dtype == torch.bfloat16
+    t = TIMER
+    e0 = t.begin() if t is not None else None
+    _check(lib().u3d_igemm_fwd_affine_bf16(_ptr(inp), _ptr(w_folded), _ptr(nbr), nbr.shape[1] if nbr is not None else 0, _ptr(shift),
+                                           int(bool(relu)), _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol, _stream()),
+           "igemm_fwd_affine_bf16")
+    if t is not None:
+        meta = None
+        if t.mode == "census":
+            pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
+            meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
+                        bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
+        t.end(tag, e0, meta)
     return out
 
 

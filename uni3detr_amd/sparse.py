@@ -532,10 +532,48 @@ BN_GRAD_FUSION = False
 FUSED_CONV_STATS = True
 
 
+# ---- inference: eval-mode BatchNorm folded into the convolution (uni3detr_amd/inference.py) ---------------------------------------------
+# Inside fold_scope(table) a conv_bn() call whose BatchNorm module is in `table` (id(bn) -> (w_folded, shift), the buffers an
+# InferenceModel owns) runs as ONE launch, conv_affine(); every other call, and every call outside a scope, is what it always was.
+_FOLD = [None]
+
+
+@contextlib.contextmanager
+def fold_scope(table):
+    prev = _FOLD[0]
+    _FOLD[0] = table
+    try:
+        yield
+    finally:
+        _FOLD[0] = prev
+
+
+def conv_affine(feats, w_folded, shift, geom, relu=True):
+    """relu(conv(feats; w_folded) + shift) in one launch (u3d_igemm_fwd_affine_bf16): conv -> eval-mode BatchNorm -> ReLU with the
+    BatchNorm's scale folded into the bf16 n-major weights [kvol, Cout, Cin] and its shift kept in f32 (native.bn_fold).  Inference
+    only (no autograd node); bf16 rows, channels % 64 == 0 - anything else is an error, not a detour."""
+    if torch.is_grad_enabled() and (feats.requires_grad or w_folded.requires_grad):
+        raise RuntimeError("conv_affine is an inference path: it records no autograd node")
+    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
+        raise RuntimeError(f"conv_affine needs bf16 device rows, got {feats.dtype} on {feats.device}")
+    kvol, cin = w_folded.shape[0], w_folded.shape[2]
+    if feats.shape[1] != cin:
+        raise ValueError(f"conv_affine: input has {feats.shape[1]} channels, folded weight expects {cin}")
+    nv.CALL_KIND = geom.kind
+    nbr = geom.nbr_fwd if kvol > 1 else None
+    return nv.igemm_fwd_affine(feats.contiguous(), w_folded, nbr, shift, relu, geom.n_out_dev, geom.n_out)
+
+
 def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dhwio", post_add=None, res_take=None, res_give=None,
             fan_token=None, bn_in=None, bn_out=None):
     """conv -> BatchNorm rows (+ residual) (+ ReLU).  In training the conv's epilogue already reduces the BatchNorm statistics per row
     tile where its kernel supports it (bf16, channels % 64 == 0): the separate statistics pass over the conv output disappears."""
+    if _FOLD[0] is not None:
+        ent = _FOLD[0].get(id(bn))
+        if ent is not None:
+            if bn.training or residual is not None or post_add is not None:
+                raise RuntimeError("a folded conv + BatchNorm pair was called in training mode, or with a residual / level sum")
+            return conv_affine(feats, ent[0], ent[1], geom, relu)
     if FUSED_CONV_STATS and bn.training and feats.is_cuda and (feats.dtype == torch.bfloat16 or _split_serves(feats, feats.shape[1], bn.num_features) == "wide"):
         # res_take: this conv's input is the identity of a residual block - its backward sums the token's gradient into the input
         # gradient; res_give: this BatchNorm adds that identity - its backward leaves the identity's gradient in the token
