@@ -660,6 +660,26 @@ int32_t u3d_adamw_step_state(float* param, const float* grad, float* exp_avg, fl
  * positive-count all-reduce - never trains on truncated levels; the host reads state[12] now and then and re-captures. */
 int32_t u3d_adamw_step_hold(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
                             const uint8_t* skip, const float* hold, void* workspace, int64_t workspace_bytes, u3d_stream s);
+/* u3d_adamw_step_hold with gradient accumulation, a non-finite skip and EMA weights, all decided on the device (no host read, no
+ * allocation, capturable; three launches).  One call is a MICRO-step: unless held, acc += grad; every k-th such call applies clip +
+ * AdamW with the window's mean gradient gbar = acc / k (mmcv GradientCumulativeOptimizerHook's arithmetic; k = 1: u3d_adamw_step_hold
+ * bit for bit) and clears acc.  A window whose gbar has a NaN / Inf norm is DROPPED instead: acc is cleared, param, moments,
+ * state[0..4] and ema keep their bits (what the reference's fp16 loss scaler does with such a step).  After an applied update, if ema
+ * is non-null and d > 0: ema += (1 - d) * (param_new - ema).  A held call (hold non-null, *hold > 0) is exactly u3d_adamw_step_hold's:
+ * state[11] = 1, state[12] += 1, acc and the window counter untouched (the held batch's gradient is discarded, the window stays open).
+ * state: the 16 floats described above, unchanged in meaning.  acc_state: 8 floats of device memory, zero-initialised by the caller:
+ * [0] k = accum_steps (u3d_adamw_set_accum; < 1 reads as 1), [1] micro-steps accumulated in the open window, [2] applied updates so
+ * far, [3] windows dropped as non-finite so far, [4] EMA decay d (<= 0: no EMA even if ema is given), [5] outcome of THIS call:
+ * 0 accumulated, 1 applied, 2 dropped, 3 held, [6] norm of gbar at the last apply or drop, [7] reserved.
+ * acc, ema (nullable): n floats, 16-byte aligned; acc zero-initialised.  skip == 1 chunks are left untouched in param, moments, acc
+ * and ema; to the norm they contribute this call's grad / k (as they contribute grad to u3d_adamw_step_hold's norm).  The sum of
+ * squares is taken over float squares accumulated in double: |gbar| above ~1.8e19 reads as non-finite.
+ * workspace: u3d_adamw_workspace(n) bytes. */
+int32_t u3d_adamw_step_accum(float* param, const float* grad, float* acc, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                             float* state, float* acc_state, const uint8_t* skip, const float* hold, void* workspace,
+                             int64_t workspace_bytes, u3d_stream s);
+/* acc_state[0] = accum_steps (>= 1), acc_state[4] = ema_decay (< 1; <= 0: no EMA): a one-thread launch, stream-ordered */
+int32_t u3d_adamw_set_accum(float* acc_state, int32_t accum_steps, float ema_decay, u3d_stream s);
 /* flag[0] = number of i < n (n <= 8) with *counts[i] > caps[i]; counts: HOST array of device pointers, caps: HOST array */
 int32_t u3d_capacity_flag(const int32_t* const* counts, const int32_t* caps, int32_t n, float* flag, u3d_stream s);
 int32_t u3d_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

@@ -3,6 +3,8 @@
 //  upstream torch.optim.AdamW + torch.nn.utils.clip_grad_norm_).  Parameters, gradients and both moments live in four flat f32
 // buffers, so the whole update is three launches (partial sum of squares -> coefficients -> element-wise update) that stream
 // 7 x 4 bytes per parameter once, instead of ~30 multi-tensor launches.  Capturable: the step counter is device state.
+// u3d_adamw_step_accum (below) is the same step as a micro-step: gradient accumulation over k calls, a device-side skip of windows whose
+// mean gradient is not finite, and EMA weights - still three launches, still no host read.
 #include "common.h"
 
 #define OPT_BLOCK 256
@@ -148,6 +150,212 @@ extern "C" int32_t u3d_adamw_step_hold(float* param, const float* grad, float* e
 extern "C" int32_t u3d_adamw_step_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
                                         const uint8_t* skip, void* workspace, int64_t workspace_bytes, u3d_stream s) {
   return u3d_adamw_step_hold(param, grad, exp_avg, exp_avg_sq, n, state, skip, nullptr, workspace, workspace_bytes, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same step with gradient accumulation, a non-finite skip and EMA weights (u3d_adamw_step_accum): one captured batch is a
+// MICRO-step, an update is applied every k-th of them with the window's mean gradient (ref: mmcv GradientCumulativeOptimizerHook -
+// the shipped recipes train 8 GPUs x samples_per_gpu scenes per update).  Everything is decided on the device, as the HOLD flag is:
+//   launch 1  k_accum_sumsq        acc += grad, fused with the partial sums of squares of gbar = acc / k (grid and summation order of
+//                                  k_sumsq_partial: for k = 1 the norm - and so the whole step - is bit for bit u3d_adamw_step_hold's)
+//   launch 2  k_accum_prepare      outcome of this call -> acc_state[5]: 0 accumulated | 1 applied | 2 dropped (the norm of gbar is
+//                                  NaN / Inf: nothing but `acc` is touched) | 3 held; coefficients as k_adamw_prepare writes them
+//   launch 3  k_adamw_accum_flat   returns at once for 0 / 3; 2: acc = 0; 1: AdamW with gbar, acc = 0, ema += (1 - d) * (p_new - ema)
+// f32 streams of n elements: an accumulate-only call 3 (acc read + write, grad read); an applying call those 3 + 8 (param, acc, both
+// moments read and written), + 2 with EMA; u3d_adamw_step_hold 8 (grad for the norm + the 7 of its update).
+// acc_state (8 floats, zero-initialised by the caller): [0] k (u3d_adamw_set_accum; < 1 reads as 1), [1] micro-steps in the open
+//   window, [2] applied updates, [3] windows dropped as non-finite, [4] EMA decay d (<= 0: no EMA), [5] outcome of this call,
+//   [6] norm of gbar at the last apply / drop, [7] reserved.
+// skip == 1 chunks are left alone in acc too; to the norm they contribute this call's grad / k, as they contribute grad to
+// u3d_adamw_step_hold's norm (the trainer zeroes the gradient of such parameters, so both are zero there).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OPT_BLOCK) void k_accum_sumsq(float* __restrict__ acc, const float* __restrict__ g, long long n,
+                                                           const float* __restrict__ acc_state, const unsigned char* __restrict__ skip,
+                                                           const float* __restrict__ hold, double* __restrict__ partial) {
+  if (hold != nullptr && *hold > 0.f) return;             // held (uniform): the batch's gradient is discarded, the window stays open
+  const float k = fmaxf(acc_state[0], 1.f);
+  const long long base = (long long)blockIdx.x * OPT_ELEMS_PER_BLOCK;
+  double sum = 0.0;
+#pragma unroll 2
+  for (int i = 0; i < 8; ++i) {
+    long long o = base + ((long long)i * OPT_BLOCK + threadIdx.x) * 4;
+    if (o >= n) break;
+    const bool skipped = skip && skip[o >> 6];
+    if (o + 3 < n) {
+      float4 v = *(const float4*)(g + o);
+      if (!skipped) {
+        const float4 a = *(const float4*)(acc + o);
+        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+        *(float4*)(acc + o) = v;
+      }
+      v.x /= k; v.y /= k; v.z /= k; v.w /= k;
+      sum += (double)(v.x * v.x + v.y * v.y) + (double)(v.z * v.z + v.w * v.w);
+    } else {
+      for (int e = 0; e < 4; ++e)
+        if (o + e < n) {
+          float x = g[o + e];
+          if (!skipped) { x += acc[o + e]; acc[o + e] = x; }
+          x /= k;
+          sum += (double)x * (double)x;
+        }
+    }
+  }
+  sum = u3d_wave_sum_d(sum);
+  __shared__ double red[OPT_BLOCK / 64];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < OPT_BLOCK / 64; ++i) s += red[i];
+    partial[blockIdx.x] = s;
+  }
+}
+
+__global__ void k_adamw_set_accum(float* __restrict__ acc_state, float k, float ema_decay) {
+  if (threadIdx.x == 0) { acc_state[0] = k; acc_state[4] = ema_decay; }
+}
+
+__global__ __launch_bounds__(256) void k_accum_prepare(const double* __restrict__ partial, int nb, float* __restrict__ state,
+                                                       float* __restrict__ acc_state, const float* __restrict__ hold) {
+  const float max_norm = state[10], beta1 = state[6], beta2 = state[7];
+  const bool held = hold != nullptr && *hold > 0.f;          // uniform
+  double s = 0.0;
+  if (!held)                                                 // (a held call's launch 1 wrote no partial sums)
+    for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];
+  s = u3d_wave_sum_d(s);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    state[11] = held ? 1.f : 0.f;
+    if (held) {
+      state[12] += 1.f;
+      acc_state[5] = 3.f;
+      return;
+    }
+    const float k = fmaxf(acc_state[0], 1.f), c = acc_state[1] + 1.f;
+    if (c < k) {
+      acc_state[1] = c;
+      acc_state[5] = 0.f;
+      return;
+    }
+    const double tot = sqrt(red[0] + red[1] + red[2] + red[3]);
+    acc_state[1] = 0.f;
+    acc_state[6] = (float)tot;
+    if (!(tot <= 1.79769313486231570e308)) {                 // NaN or Inf: the window is dropped, nothing else moves
+      acc_state[3] += 1.f;
+      acc_state[5] = 2.f;
+      return;
+    }
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      coef = max_norm / ((float)tot + 1e-6f);                // as k_adamw_prepare
+      coef = coef < 1.f ? coef : 1.f;
+    }
+    float t = state[0] + 1.f;
+    state[0] = t;
+    state[1] = coef;
+    state[2] = 1.f - powf(beta1, t);
+    state[3] = 1.f - powf(beta2, t);
+    state[4] = (float)tot;
+    acc_state[2] += 1.f;
+    acc_state[5] = 1.f;
+  }
+}
+
+__global__ __launch_bounds__(OPT_BLOCK) void k_adamw_accum_flat(float* __restrict__ p, float* __restrict__ acc, float* __restrict__ m,
+                                                                float* __restrict__ v, float* __restrict__ ema, long long n,
+                                                                const float* __restrict__ state, const float* __restrict__ acc_state,
+                                                                const unsigned char* __restrict__ skip) {
+  const float outcome = acc_state[5];                     // uniform
+  if (outcome != 1.f && outcome != 2.f) return;           // accumulated / held: nothing to stream
+  const long long base = (long long)blockIdx.x * OPT_ELEMS_PER_BLOCK;
+  if (outcome == 2.f) {                                   // dropped window: only the accumulator is cleared
+#pragma unroll 2
+    for (int i = 0; i < 8; ++i) {
+      long long o = base + ((long long)i * OPT_BLOCK + threadIdx.x) * 4;
+      if (o >= n) break;
+      if (skip && skip[o >> 6]) continue;
+      if (o + 3 < n) *(float4*)(acc + o) = make_float4(0.f, 0.f, 0.f, 0.f);
+      else
+        for (int e = 0; e < 4; ++e)
+          if (o + e < n) acc[o + e] = 0.f;
+    }
+    return;
+  }
+  const float coef = state[1], bc1 = state[2], bc2 = state[3];
+  const float lr = state[5], beta1 = state[6], beta2 = state[7], eps = state[8], wd = state[9];
+  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2), decay = 1.f - lr * wd;
+  const float k = fmaxf(acc_state[0], 1.f), d = acc_state[4], omd = 1.f - d;
+  const bool do_ema = ema != nullptr && d > 0.f;          // uniform
+#pragma unroll 2
+  for (int i = 0; i < 8; ++i) {
+    long long o = base + ((long long)i * OPT_BLOCK + threadIdx.x) * 4;
+    if (o >= n) break;
+    if (skip && skip[o >> 6]) continue;
+    float pv[4], gv[4], mv[4], vv[4], ev[4] = {0.f, 0.f, 0.f, 0.f};
+    const bool full = o + 3 < n;
+    if (full) {
+      float4 a = *(const float4*)(p + o), b = *(const float4*)(acc + o), c = *(const float4*)(m + o), dd = *(const float4*)(v + o);
+      pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w; gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
+      mv[0] = c.x; mv[1] = c.y; mv[2] = c.z; mv[3] = c.w; vv[0] = dd.x; vv[1] = dd.y; vv[2] = dd.z; vv[3] = dd.w;
+      if (do_ema) { float4 x = *(const float4*)(ema + o); ev[0] = x.x; ev[1] = x.y; ev[2] = x.z; ev[3] = x.w; }
+    } else {
+      for (int e = 0; e < 4; ++e) {
+        bool ok = o + e < n;
+        pv[e] = ok ? p[o + e] : 0.f; gv[e] = ok ? acc[o + e] : 0.f; mv[e] = ok ? m[o + e] : 0.f; vv[e] = ok ? v[o + e] : 0.f;
+        if (do_ema) ev[e] = ok ? ema[o + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gr = (gv[e] / k) * coef;                 // gbar = acc / k, then k_adamw_flat's arithmetic
+      float pe = pv[e] * decay;
+      mv[e] = mv[e] + (gr - mv[e]) * (1.f - beta1);
+      vv[e] = beta2 * vv[e] + (1.f - beta2) * gr * gr;
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pv[e] = pe - step_size * (mv[e] / denom);
+      ev[e] = ev[e] + omd * (pv[e] - ev[e]);
+    }
+    if (full) {
+      *(float4*)(p + o) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+      *(float4*)(m + o) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      *(float4*)(v + o) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+      *(float4*)(acc + o) = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (do_ema) *(float4*)(ema + o) = make_float4(ev[0], ev[1], ev[2], ev[3]);
+    } else {
+      for (int e = 0; e < 4; ++e)
+        if (o + e < n) {
+          p[o + e] = pv[e]; m[o + e] = mv[e]; v[o + e] = vv[e]; acc[o + e] = 0.f;
+          if (do_ema) ema[o + e] = ev[e];
+        }
+    }
+  }
+}
+
+extern "C" int32_t u3d_adamw_set_accum(float* acc_state, int32_t accum_steps, float ema_decay, u3d_stream s) {
+  U3D_REQUIRE(acc_state && accum_steps >= 1 && ema_decay < 1.f, U3D_ERR_ARG);
+  hipLaunchKernelGGL(k_adamw_set_accum, dim3(1), dim3(64), 0, s, acc_state, (float)accum_steps, ema_decay);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+extern "C" int32_t u3d_adamw_step_accum(float* param, const float* grad, float* acc, float* exp_avg, float* exp_avg_sq, float* ema,
+                                        int64_t n, float* state, float* acc_state, const uint8_t* skip, const float* hold,
+                                        void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  U3D_REQUIRE(param && grad && acc && exp_avg && exp_avg_sq && state && acc_state && workspace && n >= 0, U3D_ERR_ARG);
+  U3D_REQUIRE(workspace_bytes >= u3d_adamw_workspace(n), U3D_ERR_WORKSPACE);
+  U3D_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)acc | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema) & 15) == 0,
+              U3D_ERR_ARG);
+  const int nb = u3d_cdiv(n > 0 ? n : 1, OPT_ELEMS_PER_BLOCK);
+  hipLaunchKernelGGL(k_accum_sumsq, dim3(nb), dim3(OPT_BLOCK), 0, s, acc, grad, (long long)n, (const float*)acc_state, skip, hold,
+                     (double*)workspace);
+  hipLaunchKernelGGL(k_accum_prepare, dim3(1), dim3(256), 0, s, (const double*)workspace, nb, state, acc_state, hold);
+  if (n > 0)
+    hipLaunchKernelGGL(k_adamw_accum_flat, dim3(nb), dim3(OPT_BLOCK), 0, s, param, acc, exp_avg, exp_avg_sq, ema, (long long)n,
+                       (const float*)state, (const float*)acc_state, skip);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
 }
 
 // flag[0] = number of sparse levels whose device-side row count exceeds its capacity.  counts: HOST array of n (<= 8) device pointers

@@ -194,6 +194,8 @@ _SIGS = {
     "u3d_adamw_set_hyper": (_I, [_P] + [C.c_float] * 6 + [_P]),
     "u3d_adamw_step_state": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P]),
     "u3d_adamw_step_hold": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
+    "u3d_adamw_step_accum": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
+    "u3d_adamw_set_accum": (_I, [_P, C.c_int32, C.c_float, _P]),
     "u3d_capacity_flag": (_I, [_P, _P, _I, _P, _P]),
     "u3d_gather_rows": (_I, [_P, _P, _I, _I, _P, _P]),
     "u3d_soft_nms": (_I, [_P, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
@@ -1711,6 +1713,25 @@ def adamw_step_state(param, grad, exp_avg, exp_avg_sq, state, skip=None, workspa
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=param.device)
     _check(lib().u3d_adamw_step_hold(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, _ptr(state), _ptr(skip), _ptr(hold),
                                      _ptr(ws), ws.numel(), _stream()), "adamw_step_hold")
+
+
+def adamw_set_accum(acc_state, accum_steps, ema_decay=None):
+    """accum_steps (>= 1) and the EMA decay (None / <= 0: no EMA) into slots [0] and [4] of the 8-float device vector `acc_state`
+    (stream-ordered, one tiny launch)."""
+    _check(lib().u3d_adamw_set_accum(_ptr(acc_state), int(accum_steps), 0.0 if ema_decay is None else float(ema_decay), _stream()),
+           "adamw_set_accum")
+
+
+def adamw_step_accum(param, grad, acc, exp_avg, exp_avg_sq, state, acc_state, ema=None, skip=None, workspace=None, hold=None):
+    """adamw_step_state as a MICRO-step: acc += grad, and every acc_state[0]-th call that is not held applies clip + AdamW with the
+    window's mean gradient, drops the window if its norm is NaN / Inf, and moves `ema` (flat f32 or None) after an applied update.
+    `acc_state` = 8 zero-initialised device floats (include/u3d_hip.h), set up with adamw_set_accum; acc_state[5] = what this call did."""
+    n = param.numel()
+    assert acc.numel() == n and (ema is None or ema.numel() == n) and acc_state.numel() >= 8
+    wsb = int(lib().u3d_adamw_workspace(n))
+    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=param.device)
+    _check(lib().u3d_adamw_step_accum(_ptr(param), _ptr(grad), _ptr(acc), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema), n, _ptr(state),
+                                      _ptr(acc_state), _ptr(skip), _ptr(hold), _ptr(ws), ws.numel(), _stream()), "adamw_step_accum")
 
 
 def capacity_flag(counts, caps, flag):

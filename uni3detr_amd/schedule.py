@@ -90,5 +90,8 @@ def build_schedule(cfg, iters_per_epoch):
 
 
 def apply(ts, schedule, it):
-    """Set the hyper-parameters of iteration `it` on a TrainStep (one tiny launch; replayed graphs read them from device memory)."""
-    ts.set_hyper(**schedule.hyper(it))
+    """Set the hyper-parameters of iteration `it` on a TrainStep (one tiny launch; replayed graphs read them from device memory).
+    `it` counts calls of ts.step(): with gradient accumulation (TrainStep(accum_steps=k)) those are micro-steps and the schedule
+    advances once per window, at index it // k - a host count, which ignores held steps and dropped windows as `it` ignores held
+    steps today."""
+    ts.set_hyper(**schedule.hyper(it // getattr(ts, "accum_steps", 1)))

@@ -55,12 +55,30 @@ def plan_point_capacity(scene_sizes, margin=1.25, multiple=1024):
 class TrainStep:
     def __init__(self, model, points, gt_bboxes_3d, gt_labels_3d, lr=1e-4, weight_decay=0.01, max_norm=10.0, graph=True,
                  capacity_margin=1.25, flat_update=True, overlap_reduce=False, betas=(0.9, 0.999), eps=1e-8, gt_capacity=64,
-                 check_every=50, pg_hooks=None, fps_graph=None, grad_comm_dtype=torch.float32, reduce_buckets=None, point_capacity=None):
+                 check_every=50, pg_hooks=None, fps_graph=None, grad_comm_dtype=torch.float32, reduce_buckets=None, point_capacity=None,
+                 accum_steps=1, skip_nonfinite=False, ema_decay=None):
         """pg_hooks: (teardown, setup) callables that destroy / re-create the default process group; needed only for a collective
         re-capture after a capacity overflow on a multi-rank run (bench.py passes them).
         point_capacity: None - the static point buffer has exactly the initial batch's layout (set_batch takes that layout only).  An
         int P - capacity mode: the buffer holds B * P rows, every scene may have any number of points up to P, and
-        set_packed_batch() fills the buffers from a DevicePipeline batch on the device (hard voxelization, flat_update=True)."""
+        set_packed_batch() fills the buffers from a DevicePipeline batch on the device (hard voxelization, flat_update=True).
+        accum_steps / skip_nonfinite / ema_decay: any non-default value makes the update stage u3d_adamw_step_accum (flat_update=True;
+        INTEGRATION.md M): step() is then a MICRO-step, an update is applied every `accum_steps`-th one that was not held, with the
+        window's mean gradient; a window whose mean gradient has a NaN / Inf norm is dropped on the device (that entry always does so:
+        skip_nonfinite=True asks for it alone); ema_decay=d in (0, 1) keeps EMA weights (ema_state_dict / ema_scope).  Counters:
+        applied_updates(), nonfinite_skips(), window_fill().  With the defaults nothing of this is allocated or launched."""
+        accum_steps = int(accum_steps)
+        if accum_steps < 1:
+            raise ValueError(f"TrainStep(accum_steps={accum_steps}): at least 1 micro-step per update")
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"TrainStep(ema_decay={ema_decay}): the EMA decay lies in (0, 1)")
+        self.accum_steps, self.skip_nonfinite = accum_steps, bool(skip_nonfinite)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.accum = accum_steps != 1 or self.skip_nonfinite or self.ema_decay is not None
+        if self.accum and not flat_update:
+            raise NotImplementedError("TrainStep(accum_steps=... / skip_nonfinite=... / ema_decay=...) needs flat_update=True: the window, "
+                                      "the non-finite skip and the EMA weights are kept by the device-side flat AdamW step")
+        self.acc = self.ema = self.acc_state = None
         if point_capacity is not None:
             point_capacity = int(point_capacity)
             if getattr(model, "dynamic_voxelization", False):
@@ -166,6 +184,12 @@ class TrainStep:
             self.opt = None
             self._skip = None                 # uint8 per 64-element chunk: parameters without a gradient (set after the first backward)
             self._skip_known = False
+            if self.accum:
+                # allocated once: captured graphs keep these addresses (include/u3d_hip.h: u3d_adamw_step_accum)
+                self.acc = torch.zeros_like(self.flat_param)
+                self.acc_state = torch.zeros(8, dtype=torch.float32, device=self.dev)
+                self.ema = self.flat_param.clone() if self.ema_decay is not None else None
+                nv.adamw_set_accum(self.acc_state, self.accum_steps, self.ema_decay)
             self.set_hyper()
         else:
             self.opt = torch.optim.AdamW(self.params, lr=lr, betas=self.betas, eps=eps, weight_decay=weight_decay, fused=True, capturable=graph)
@@ -601,6 +625,10 @@ class TrainStep:
             self._all_reduce_slice(0, self.flat_grad.numel())
 
     def _stage3(self):
+        if self.accum:
+            nv.adamw_step_accum(self.flat_param, self.flat_grad, self.acc, self.exp_avg, self.exp_avg_sq, self.opt_state, self.acc_state,
+                                ema=self.ema, skip=self._skip, workspace=self._opt_ws, hold=None if self._msg is None else self._msg[-1:])
+            return
         if self.flat_update:
             nv.adamw_step_state(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.opt_state, self._skip, self._opt_ws,
                                  hold=None if self._msg is None else self._msg[-1:])
@@ -614,6 +642,11 @@ class TrainStep:
             self.exp_avg_sq.zero_()
             self.opt_state[:5].zero_()            # step count and derived values; the hyper-parameter slots stay
             self.opt_state[11:13].zero_()         # hold flag / held-step counter
+            if self.accum:                        # a fresh window, no updates counted, EMA = the (restored) parameters
+                self.acc.zero_()
+                self.acc_state[1:4].zero_()
+                if self.ema is not None:
+                    self.ema.copy_(self.flat_param)
             return
         for st in self.opt.state.values():
             for v in st.values():
@@ -625,9 +658,14 @@ class TrainStep:
         """Flat AdamW state as a dict of CPU tensors (per-parameter views are recoverable through `offsets`)."""
         if not self.flat_update:
             return dict(kind="torch", state=self.opt.state_dict())
-        return dict(kind="flat", exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), opt_state=self.opt_state.cpu(),
-                    offsets=list(self.offsets), numels=[p.numel() for p in self.params],
-                    skip=None if self._skip is None else self._skip.cpu())
+        sd = dict(kind="flat", exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), opt_state=self.opt_state.cpu(),
+                  offsets=list(self.offsets), numels=[p.numel() for p in self.params],
+                  skip=None if self._skip is None else self._skip.cpu())
+        if self.accum:                            # the open window and the EMA weights travel with the moments
+            sd.update(accum_steps=self.accum_steps, acc=self.acc.cpu(), acc_state=self.acc_state.cpu())
+            if self.ema is not None:
+                sd["ema"] = self.ema.cpu()
+        return sd
 
     def load_optimizer_state_dict(self, sd):
         if sd.get("kind") == "torch":
@@ -635,11 +673,23 @@ class TrainStep:
             return
         if list(sd["offsets"]) != list(self.offsets) or list(sd["numels"]) != [p.numel() for p in self.params]:
             raise ValueError("optimizer state was saved for a different parameter layout")
+        if "acc_state" in sd and int(sd["accum_steps"]) != self.accum_steps:
+            raise ValueError(f"optimizer state was saved with accum_steps={int(sd['accum_steps'])}, this step has accum_steps="
+                             f"{self.accum_steps}: an open window of another length cannot be continued")
         self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"]); self.opt_state.copy_(sd["opt_state"])
         self.opt_state[11:13].zero_()
         if sd.get("skip") is not None:
             self._skip = sd["skip"].to(self.dev)
             self._skip_known = True
+        if self.accum:
+            # a dict saved without a window loads as a fresh one (EMA = the current parameters); k and d stay this step's own
+            if "acc_state" in sd:
+                self.acc.copy_(sd["acc"]); self.acc_state.copy_(sd["acc_state"])
+            else:
+                self.acc.zero_(); self.acc_state.zero_()
+            nv.adamw_set_accum(self.acc_state, self.accum_steps, self.ema_decay)
+            if self.ema is not None:
+                self.ema.copy_(sd["ema"] if sd.get("ema") is not None else self.flat_param)
         self.set_hyper()
 
     def eager_step(self, stage1_done=False):
@@ -677,6 +727,8 @@ class TrainStep:
         snap = dict(model=self.snapshot())
         if self.flat_update:
             snap.update(m=self.exp_avg.clone(), v=self.exp_avg_sq.clone(), st=self.opt_state.clone())
+            if self.accum:
+                snap.update(acc=self.acc.clone(), acc_st=self.acc_state.clone(), ema=None if self.ema is None else self.ema.clone())
         else:       # torch.optim.AdamW: moments and step counters of every parameter that has state already
             snap["opt"] = {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.opt.state.get(p, {}).items()}
                            for i, p in enumerate(self.params)}
@@ -688,6 +740,10 @@ class TrainStep:
                 t.copy_(s_)
             if self.flat_update:
                 self.exp_avg.copy_(snap["m"]); self.exp_avg_sq.copy_(snap["v"]); self.opt_state.copy_(snap["st"])
+                if self.accum:
+                    self.acc.copy_(snap["acc"]); self.acc_state.copy_(snap["acc_st"])
+                    if self.ema is not None:
+                        self.ema.copy_(snap["ema"])
             else:
                 # in place (a captured optimizer step holds these addresses); state created after the snapshot goes back to zero
                 for i, p in enumerate(self.params):
@@ -854,6 +910,59 @@ class TrainStep:
         if not self.flat_update:
             return 0
         return int(self.opt_state[12].item())
+
+    # ---- accumulation window / EMA (accum_steps, skip_nonfinite, ema_decay) -----------------------------------
+    def applied_updates(self):
+        """Optimizer updates applied so far (one small device-to-host read, made where held_steps() is read - never per step).
+        Without accumulation: the step count of the flat AdamW state."""
+        if not self.accum:
+            return int(self.opt_state[0].item()) if self.flat_update else 0
+        return int(self.acc_state[2].item())
+
+    def nonfinite_skips(self):
+        """Windows dropped on the device because their mean gradient had a NaN / Inf norm (0 without the accumulating entry)."""
+        return int(self.acc_state[3].item()) if self.accum else 0
+
+    def window_fill(self):
+        """Micro-steps accumulated in the open window, 0 .. accum_steps - 1."""
+        return int(self.acc_state[1].item()) if self.accum else 0
+
+    def ema_state_dict(self):
+        """The model's state_dict with every trained parameter taken from the EMA weights (clones); buffers - BatchNorm running
+        statistics included - are the live ones."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dict needs a TrainStep built with ema_decay=d")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        where = {id(p): o for p, o in zip(self.params, self.offsets)}
+        for name, p in self.model.named_parameters():
+            if id(p) in where and name in sd:
+                sd[name] = self.ema[where[id(p)]:where[id(p)] + p.numel()].view_as(p).clone()
+        return sd
+
+    def ema_scope(self):
+        """Context manager: the CONTENTS of flat_param and ema are exchanged in place on entry and exchanged back on exit (captured
+        graphs hold addresses, so no pointer moves).  Inside it model.eval() inference runs on the EMA weights - the model's bf16
+        shadows are re-cast from flat_param by every forward; an InferenceModel built on the model holds folded copies of its own and
+        needs refresh() inside the scope (and again after it).  Entering with an open window (window_fill() != 0) is allowed: the
+        accumulator is not touched.  Do not step inside the scope."""
+        import contextlib
+        if self.ema is None:
+            raise RuntimeError("ema_scope needs a TrainStep built with ema_decay=d")
+
+        def swap():
+            with torch.no_grad():
+                tmp = self.flat_param.clone()
+                self.flat_param.copy_(self.ema)
+                self.ema.copy_(tmp)
+
+        @contextlib.contextmanager
+        def scope():
+            swap()
+            try:
+                yield self
+            finally:
+                swap()
+        return scope()
 
     def fps_timeouts(self):
         """FPS launches of THIS rank that timed out since the last check (host read of model.fps_err[1])."""
