@@ -317,6 +317,12 @@ int64_t u3d_igemm_wgrad_bf16_workspace(int32_t n_out_cap, int32_t cin, int32_t c
 int32_t u3d_igemm_wgrad_bf16(const void* in, const void* dout, const int32_t* nbr, int32_t ld, float* dw,
                              const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                              int32_t out_layout, void* workspace, int64_t workspace_bytes, u3d_stream s);
+/* The launch plan of u3d_igemm_wgrad_bf16 for a shape (host only; the counterpart of u3d_igemm_fwd_affine_plan): *kernel = the kernel
+ * family (1 conv-in 8 -> 16, 2 narrow 16/32-channel, 3 / 4 eight- / two-phase LDS-DMA 256, 5 / 6 LDS-DMA 128 / 64, 7 / 8 register-staged
+ * 32 / 16), *tile its square channel tile (0: conv-in, narrow), *nsplit the f32 partials it sums, *workspace their bytes (what
+ * u3d_igemm_wgrad_bf16_workspace returns).  U3D_ERR_UNSUPPORTED where the launch returns it. */
+int32_t u3d_igemm_wgrad_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t out_layout,
+                             int32_t* kernel, int32_t* tile, int32_t* nsplit, int64_t* workspace);
 
 /* dW[kappa] = sum_m in[nbr[kappa][m],:]^T @ dout[m,:]   (f32 accumulate, dW f32 [K,Cin,Cout], overwritten).
  * workspace: u3d_spconv_wgrad_workspace() bytes. */

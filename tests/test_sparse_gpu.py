@@ -323,7 +323,7 @@ def test_dense_roundtrip(cuda):
 
 
 BF16_CASES = [(8, 16, 27), (16, 32, 27), (32, 64, 27), (64, 64, 27), (64, 128, 27), (128, 128, 27), (128, 256, 1), (256, 256, 27),
-              (256, 128, 27), (512, 512, 1), (128, 64, 27)]
+              (256, 128, 27), (512, 512, 1), (128, 64, 27), (64, 32, 27), (64, 16, 27)]
 
 
 @pytest.mark.parametrize("v2", [True, False])

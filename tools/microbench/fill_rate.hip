@@ -1,4 +1,4 @@
-// tools/microbench/fill_rate.hip - what bounds k_igemm_glds8_256x256 (uni3detr_amd/csrc/igemm_bf16.hip)?
+// tools/microbench/fill_rate.hip - what bounds k_igemm_glds8_256x256 (uni3detr_amd/csrc/igemm_bf16.hip, the forward / input-gradient unit)?
 //
 // The dominant layer of the benched step (SECOND3DFPN's 256 -> 256 3x3x3 convolutions, ref models/necks/second3d_fpn.py:73-104) is an
 // implicit GEMM over 192 000 lattice rows x 27 offsets: 750 workgroups (8 waves) walk 108 k-tiles of 64 KiB (256 gathered activation

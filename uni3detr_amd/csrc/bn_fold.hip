@@ -6,7 +6,7 @@
 // launch and one trip over the activation tensor.
 //
 // One launch folds every conv + BatchNorm pair of a model: the job table lives on the device (as U3dSplit3Job does for the split-bf16
-// weights, igemm_bf16.hip), blocks [first_block[j], first_block[j + 1]) of the grid work on job j.  The f32 master weight is read in
+// weights, split_bf16.hip), blocks [first_block[j], first_block[j + 1]) of the grid work on job j.  The f32 master weight is read in
 // place through element strides, so both checkpoint layouts ([kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW]) need no re-laid-out copy.
 // Nothing here allocates or synchronises.
 #include "common.h"

@@ -1,4 +1,4 @@
-// Launch plan of the direct-operand implicit-GEMM kernels (igemm_direct.hip), shared with the forward plan of igemm_bf16.hip.
+// Launch plan of the direct-operand implicit-GEMM kernels (igemm_direct.hip), shared with the forward plan (fwd_plan) of igemm_bf16.hip.
 #pragma once
 #include "common.h"
 

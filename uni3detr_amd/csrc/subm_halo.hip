@@ -1,7 +1,7 @@
 // Output-stationary "halo" kernels for the 64- and 128-channel, 27-offset submanifold levels (ref: sparse_encoder_hd.py:106-138, the
 // SparseBasicBlock convs of the stride-4 / stride-8 stages; spconv's SubMConv3d gathers each of the 27 offsets' rows again).
 //
-// The LDS-DMA implicit-GEMM kernels (igemm_bf16.hip) fetch, per 128-row output tile, 27 x 128 operand rows through 27 x 128 one-row
+// The LDS-DMA implicit-GEMM kernels (igemm_bf16.hip; weight gradient: igemm_wgrad.hip) fetch, per 128-row output tile, 27 x 128 operand rows through 27 x 128 one-row
 // DMA pieces, and the fill rate of that path is what bounds them.  But rows are numbered in 4x4x4-block-major
 // order, so the 27 x 128 table entries of a tile name only ~210-420 DISTINCT rows (the tile's cells plus a one-cell shell).  This file:
 //   1. k_halo_build  (once per level and step, shared by all of the level's convs and their gradients): per tile, the sorted
@@ -187,7 +187,7 @@ __device__ __forceinline__ f32x4 hl_sel(bool c, f32x4 a, f32x4 b) {
   return r;
 }
 
-// BatchNorm-backward statistics mode of the epilogue (== u3d_bn_epi; see glds_epilogue.inc / BnEpi in igemm_bf16.hip)
+// BatchNorm-backward statistics mode of the epilogue (== u3d_bn_epi; see glds_epilogue.inc / BnEpi in igemm_bf16.hip, the forward / input-gradient unit)
 struct HlBn {
   const u16* x = nullptr; const u16* y = nullptr;
   const float *mean = nullptr, *invstd = nullptr, *gamma = nullptr, *beta = nullptr;

@@ -102,6 +102,7 @@ _SIGS = {
     "u3d_linear_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "u3d_igemm_wgrad_bf16_workspace": (_L, [_I, _I, _I, _I]),
     "u3d_igemm_wgrad_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "u3d_igemm_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "u3d_colsum_workspace": (_L, [_I, _I]),
     "u3d_colsum": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
     "u3d_bn_stats_workspace": (_L, [_I, _I]),
@@ -1099,49 +1100,52 @@ def spconv_fwd_split(xs, w3, nbr3, n_out_dev, n_out, cout, want_stats=False, tag
     return (out, stats, tr) if want_stats else out
 
 
+WGRAD_KERNELS = ("none", "conv_in", "narrow", "glds8_256", "glds_256", "glds_128", "glds_64", "reg_32", "reg_16")
+
+
+def igemm_wgrad_plan(n_out, cin, cout, kvol, has_nbr, out_oik=False):
+    """(kernel family, tile, nsplit, workspace bytes) u3d_igemm_wgrad_bf16 takes for the shape; None when it does not serve it."""
+    k, tile, ns, ws = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    if lib().u3d_igemm_wgrad_plan(n_out, cin, cout, kvol, int(bool(has_nbr)), 1 if out_oik else 0, C.byref(k), C.byref(tile), C.byref(ns),
+                                  C.byref(ws)) != 0:
+        return None
+    return WGRAD_KERNELS[k.value], tile.value, ns.value, ws.value
+
+
 def spconv_wgrad(inp, dout, nbr, n_out_dev, kvol, out_oik=False, out=None):
     """-> f32 [K, Cin, Cout]; with out_oik (bf16 second-generation path only): [Cout, Cin, K] (nn.Conv3d's layout).
     out: contiguous f32 tensor of kvol*cin*cout elements to write into (bf16 path) - returned viewed in the result's shape."""
     cin, cout, n_out = inp.shape[1], dout.shape[1], dout.shape[0]
-    v2 = bool(inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and cin % 16 == 0 and cout % 16 == 0)
+    bf16 = bool(inp.dtype == torch.bfloat16 and USE_IGEMM_V2)
+    v2 = bf16 and cin % 16 == 0 and cout % 16 == 0
     assert v2 or not out_oik, "out_oik needs the bf16 implicit-GEMM weight-gradient path"
     shape = (cout, cin, kvol) if out_oik else (kvol, cin, cout)
-    if out is not None and v2 and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == kvol * cin * cout:
-        dw = out.view(shape)
-    else:
-        dw = torch.empty(shape, dtype=torch.float32, device=inp.device)
     t = TIMER
     meta = None
     if t is not None and t.mode == "census":
         pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
         s = inp.element_size()
-        meta = dict(kind=CALL_KIND, v2=bool(inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and cin % 16 == 0 and cout % 16 == 0),
-                    n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
+        meta = dict(kind=CALL_KIND, v2=v2, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
                     bytes=inp.shape[0] * cin * s + n_out * cout * s + 8 * pairs + kvol * cin * cout * 4, flops=2 * pairs * cin * cout)
-    if inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and ((cin % 16 == 0 and cout % 16 == 0) or (cin == 8 and cout == 16 and not out_oik and kvol <= 27)):
-        wsb = int(lib().u3d_igemm_wgrad_bf16_workspace(n_out, cin, cout, kvol))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=inp.device)
-        ld = nbr.shape[1] if nbr is not None else 0
-        e0 = t.begin() if t is not None else None
-        rc = lib().u3d_igemm_wgrad_bf16(_ptr(inp), _ptr(dout), _ptr(nbr), ld, _ptr(dw), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                        1 if out_oik else 0, _ptr(ws), wsb, _stream())
-        if rc != -2:
-            _check(rc, "igemm_wgrad_bf16")
-            if t is not None:
-                t.end("spconv_wgrad", e0, meta)
-            return dw
-        # a channel pair the implicit-GEMM weight-gradient kernels do not serve (e.g. 32 -> 16): the first-generation kernel below
-        gen = spconv_wgrad_generic(inp, dout, nbr, n_out_dev, kvol)
-        dw.copy_(gen.permute(2, 1, 0) if out_oik else gen)
-        if t is not None:
-            t.end("spconv_wgrad", e0, meta)
-        return dw
-    wsb = int(lib().u3d_spconv_wgrad_workspace(n_out, cin, cout, kvol))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=inp.device)
-    ld = nbr.shape[1] if nbr is not None else 0
+    # the implicit-GEMM plan decides (u3d_igemm_wgrad_plan): None = no second-generation kernel serves the shape (e.g. 32 -> 16 x 27,
+    # channel counts off the 16 grid other than the 8 -> 16 input convolution) - the first-generation kernel then
+    plan = igemm_wgrad_plan(n_out, cin, cout, kvol, nbr is not None, out_oik) if bf16 else None
     e0 = t.begin() if t is not None else None
-    _check(lib().u3d_spconv_wgrad(_ptr(inp), _ptr(dout), _ptr(nbr), ld, _ptr(dw), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                  dtype_code(inp), _ptr(ws), wsb, _stream()), "spconv_wgrad")
+    if plan is None and not v2:
+        dw = spconv_wgrad_generic(inp, dout, nbr, n_out_dev, kvol)
+    else:
+        if out is not None and v2 and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == kvol * cin * cout:
+            dw = out.view(shape)
+        else:
+            dw = torch.empty(shape, dtype=torch.float32, device=inp.device)
+        if plan is not None:
+            ws = torch.empty(plan[3], dtype=torch.uint8, device=inp.device)
+            _check(lib().u3d_igemm_wgrad_bf16(_ptr(inp), _ptr(dout), _ptr(nbr), nbr.shape[1] if nbr is not None else 0, _ptr(dw),
+                                              _ptr(n_out_dev), n_out, cin, cout, kvol, 1 if out_oik else 0, _ptr(ws), plan[3], _stream()),
+                   "igemm_wgrad_bf16")
+        else:
+            gen = spconv_wgrad_generic(inp, dout, nbr, n_out_dev, kvol)
+            dw.copy_(gen.permute(2, 1, 0) if out_oik else gen)
     if t is not None:
         t.end("spconv_wgrad", e0, meta)
     return dw

@@ -157,7 +157,7 @@ def reset_conv_uses():
     _PLANES_BWD.clear()       # (gradient planes nobody picked up in the previous step: the 4 -> 16 input conv runs on the exact f32 kernel)
 
 
-# ---- split-bf16 convolutions: f32-grade products on the bf16 matrix pipe (csrc/igemm_bf16.hip, u3d_igemm_fwd_split_bf16) -------------
+# ---- split-bf16 convolutions: f32-grade products on the bf16 matrix pipe (csrc/igemm_bf16.hip: u3d_igemm_fwd_split_bf16; csrc/split_bf16.hip: the operand planes) -------------
 # `mixed` precision = the REFERENCE's recipe (SparseEncoderHD + SECOND3D in fp32: sparse_encoder_hd.py:62-64, uni3detr.py:150-151).
 # The exact f32 MFMA runs at 1/16 of the bf16 rate; inside split_scope() every f32 conv whose channel counts are multiples of 64 runs
 # instead as three bf16 products (hi.wh + hi.wl + lo.wh, f32 accumulation) on the LDS-DMA kernels the bf16 mode is benchmarked on:
