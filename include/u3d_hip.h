@@ -212,6 +212,16 @@ int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const int32_t* n
  * u3d_igemm_fwd_bf16 (ld < 0: the forward table read reversed = the SubM input gradient), out f32 [n_out_cap][cout]. */
 int32_t u3d_igemm_direct_split_bf16(const void* in, const void* w3, const int32_t* nbr, int32_t ld, float* out, const int32_t* n_out_dev,
                                     int32_t n_out_cap, int32_t n_in_cap, int32_t cin, int32_t cout, u3d_stream s);
+/* conv -> eval-mode BatchNorm (-> + residual) (-> ReLU) on the same narrow levels in one launch of the direct-operand kernel (the
+ * inference path; what u3d_igemm_fwd_affine_bf16 is for the wide ones): out = bf16_rne(act(conv(in; w_folded) + shift[col] +
+ * addend[m][col])), f32 until the one rounding, in that order.  w_folded bf16 n-major [27][cout][cin] (u3d_bn_fold_batched), shift f32
+ * [cout] (required, 16-byte aligned), addend NULL or bf16 [n_out_cap][cout], relu != 0 applies max(., 0); nbr / ld as
+ * u3d_igemm_fwd_bf16.  Rows at or past *n_out_dev are left untouched.  With shift == 0 and relu == 0 the result equals
+ * u3d_igemm_fwd_bf16 / u3d_igemm_fwd_add_bf16 (transpose_w = 1) on the same weights.  U3D_ERR_UNSUPPORTED unless cin, cout in
+ * {16, 32, 64} and not 64 -> 64 (27 offsets are implied). */
+int32_t u3d_igemm_direct_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift,
+                                     int32_t relu, const void* addend, void* out, const int32_t* n_out_dev, int32_t n_out_cap,
+                                     int32_t cin, int32_t cout, u3d_stream s);
 /* The weight side of the same product: dst bf16 [3][k][a][b] = (hi, lo, hi) of the f32 element src[ik * sk + ia * sa + ib * sb]
  * (element strides: the checkpoint layouts [kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW] are read in place). */
 int32_t u3d_split3_weights(const float* src, int64_t sk, int64_t sa, int64_t sb, int32_t k, int32_t a, int32_t b, void* dst, u3d_stream s);
@@ -302,6 +312,18 @@ int32_t u3d_subm_halo_wpack128_batched(const void* const* srcs_dev, void* const*
 int32_t u3d_subm_halo_conv128_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
                                    const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
                                    const void* addend, void* out, double* stats, int32_t max_slots, int32_t kvol, u3d_stream s);
+/* The forward of both with an eval-mode BatchNorm folded in (the inference path): w_packed = u3d_subm_halo_wpack / _wpack128 of the
+ * FOLDED n-major weights (u3d_bn_fold_batched), out = bf16_rne(act(conv + shift[col] + addend[m][col])) - f32 until the one
+ * rounding, in that order; shift f32 [64] / [128] (required, 16-byte aligned), addend nullable (the residual block's identity),
+ * relu != 0 applies max(., 0).  Rows at or past *n_dev are left untouched.  With shift == 0 and relu == 0 the result equals
+ * u3d_subm_halo_conv64_bf16 / _conv128_bf16 (krev = 0) on the same packed weights.  The epilogue is a compile-time variant of the
+ * kernels: the entries above run the code they ran without it. */
+int32_t u3d_subm_halo_conv64_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
+                                         const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend, void* out,
+                                         const float* shift, int32_t relu, int32_t max_slots, u3d_stream s);
+int32_t u3d_subm_halo_conv128_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
+                                          const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend, void* out,
+                                          const float* shift, int32_t relu, int32_t max_slots, int32_t kvol, u3d_stream s);
 /* Weight gradient of the same 64 -> 64 SubM layers from the same tables: dw f32 [27][64][64] (spconv-1.x layout) =
  * sum over rows m of x[nbr_k(m)]^T dy[m]; x / dy bf16 [n][64].  Persistent workgroups, both MFMA operands by transpose reads out of
  * the staged distinct rows / the dy tile, offsets split over four workgroup groups, one f32 partial per workgroup summed in a fixed

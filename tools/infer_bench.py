@@ -1,11 +1,13 @@
-"""Eval forward, ms per batch: InferenceModel (eval-mode BatchNorm folded into the convolutions) against model.eval(), same process,
-the two paths alternating, medians of the replays after warm-up.  Needs the GPU.
+"""Eval forward, ms per batch: InferenceModel (eval-mode BatchNorm folded into the convolutions), InferenceModel(sparse_levels=True)
+(the sparse encoder's blocks and narrow strided convs folded too) and model.eval(), same process, the three paths alternating, medians
+(and min .. max) of the replays after warm-up.  Needs the GPU.
 
     python tools/infer_bench.py [--reps 20] [--warmup 5]
 
 Workloads: the benched SUN RGB-D shape (B = 8 scenes of 20 000 points) and a smaller batch (B = 2, 12 000 points), both on the
 SUN RGB-D model in bf16 precision.  Per workload one JSON line: feature extractor (voxelize + encoder + SECOND3D + FPN) and the whole
-simple_test_batched(on_device=True), folded and unfolded, and the number of u3d_bn_apply launches per forward.
+simple_test_batched(on_device=True), unfolded, folded and folded with the sparse levels, and the number of u3d_bn_apply launches per
+forward.
 """
 import argparse
 import copy
@@ -52,18 +54,21 @@ def main():
     model.load_state_dict({k: seeded_tensor(k, tuple(v.shape), 3) for k, v in model.state_dict().items()})
     model = model.to(dev).set_precision("bf16").eval()
     inf = InferenceModel(model)
+    inf_sp = InferenceModel(model, sparse_levels=True)
     for name, B, npts in (("sunrgbd_b8_20000", 8, 20000), ("sunrgbd_b2_12000", 2, 12000)):
         pts = [torch.from_numpy(room_scene(i, npts)[0]).to(dev) for i in range(B)]
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):      # (the unfolded head needs the autocast; the folded scope brings its own)
             paths = {
                 "features_unfolded": lambda: model.extract_pts_feat(pts),
                 "features_folded": lambda: inf.extract_pts_feat(pts),
+                "features_folded_sparse": lambda: inf_sp.extract_pts_feat(pts),
                 "detect_unfolded": lambda: model.simple_test_batched(None, pts, on_device=True),
                 "detect_folded": lambda: inf.simple_test_batched(None, pts, on_device=True),
+                "detect_folded_sparse": lambda: inf_sp.simple_test_batched(None, pts, on_device=True),
             }
             calls = {}
             orig = nv.bn_apply
-            for k in ("features_unfolded", "features_folded"):
+            for k in ("features_unfolded", "features_folded", "features_folded_sparse"):
                 n = [0]
 
                 def counting(*args, _n=n, **kw):
@@ -83,8 +88,11 @@ def main():
                 for k, fn in paths.items():
                     samples[k] += timed(fn, 1, 0)
         res = {k: round(statistics.median(v), 3) for k, v in samples.items()}
+        res.update({k + "_min_max": [round(min(v), 3), round(max(v), 3)] for k, v in samples.items()})
         res.update(workload=name, batch=B, points=npts, reps=a.reps, bn_apply_unfolded=calls["features_unfolded"],
-                   bn_apply_folded=calls["features_folded"], folded_layers=len(inf.folded), unfolded_layers=len(inf.unfolded))
+                   bn_apply_folded=calls["features_folded"], bn_apply_folded_sparse=calls["features_folded_sparse"],
+                   folded_layers=len(inf.folded), unfolded_layers=len(inf.unfolded), folded_layers_sparse=len(inf_sp.folded),
+                   unfolded_layers_sparse=len(inf_sp.unfolded))
         print(json.dumps(res), flush=True)
 
 

@@ -62,10 +62,13 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 //   * weight fragments and permuted indices are requested one offset ahead (LDS round trips are not hidden by two waves per SIMD).
 // F32ACC (split-bf16 products of the fp32 modules' narrow levels, u3d_igemm_direct_split_bf16): `out` is an F32 matrix and `addend`
 // is only a FLAG - non-null: the tile is added to what `out` holds (the second and third of the three products hi.wh + hi.wl + lo.wh).
-template <int KS, int WN, bool W_KMAJOR, int NW, int P, bool STATS = false, bool F32ACC = false>
+// AFFINE (inference, eval-mode BatchNorm folded into the n-major weights, u3d_igemm_direct_affine_bf16): out = bf16(relu(acc +
+// shift[col] + addend)), one rounding; shift f32 [cout].  Every other instantiation never reads `shift` / `relu`.
+template <int KS, int WN, bool W_KMAJOR, int NW, int P, bool STATS = false, bool F32ACC = false, bool AFFINE = false>
 __device__ __forceinline__ void igemm_direct_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr, int ld,
                                                   u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap, int cin, int cout,
-                                                  int co0, const u16* __restrict__ addend, double* __restrict__ stats) {
+                                                  int co0, const u16* __restrict__ addend, double* __restrict__ stats,
+                                                  const float* __restrict__ shift = nullptr, int relu = 0) {
   // stats (STATS instantiations: the n-major kernels with <= 32 output columns - 32 more accumulator registers spill the 64-column
   // ones): BatchNorm statistics of the rounded output, one partial per WAVE: f64 [gridDim.x * NW][2][cout] = column sums
   // and sums of squares over the rows this wave wrote (f32 per lane over its ~20 rows, 16 lanes by shuffles at the end, f64 from
@@ -269,8 +272,15 @@ __device__ __forceinline__ void igemm_direct_body(const u16* __restrict__ in, co
             } else
             if (m < n_out) {
               f32x4 v = acc[a][b];
+              if constexpr (AFFINE) v += *(const f32x4*)(shift + co0 + b * 16 + g * 4);
               // addend (nullable): a bf16 tensor of out's shape summed in before the rounding (the residual branch's gradient)
               if (addend) v += __builtin_convertvector(*(const bf16x4*)(addend + (long long)m * cout + co0 + b * 16 + g * 4), f32x4);
+              if constexpr (AFFINE) {
+                if (relu) {
+#pragma unroll
+                  for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+                }
+              }
               const bf16x4 o = __builtin_convertvector(v, bf16x4);
               *(bf16x4*)(out + (long long)m * cout + co0 + b * 16 + g * 4) = o;
               if constexpr (STATS) {                            // of the ROUNDED values: what the BatchNorm behind this conv reads
@@ -365,6 +375,18 @@ U3D_DIRECT_KERNEL_F(k_igemm_direct_32x64_nf, 1, 4, DIR_NW_B, DIR_P1)
 U3D_DIRECT_KERNEL_F(k_igemm_direct_64x16_nf, 2, 1, DIR_NW_A, DIR_P2)
 U3D_DIRECT_KERNEL_F(k_igemm_direct_64x32_nf, 2, 2, DIR_NW_B, DIR_P2)
 
+// n-major weights folded with the BatchNorm scale, bf16 out, shift + optional addend + ReLU (the narrow levels of the inference path)
+#define U3D_DIRECT_KERNEL_A(NAME, KS, WN, NW, P)                                                                                     \
+  __global__ __launch_bounds__(NW * 64, DIR_WAVES_PER_SIMD) void NAME(const u16* in, const u16* w, const int* nbr, int ld, u16* out, const int* n_out_dev, \
+                                                  int n_out_cap, int cin, int cout, const u16* addend, const float* shift, int relu) {   \
+    igemm_direct_body<KS, WN, false, NW, P, false, false, true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, 0, addend, nullptr, shift, relu); \
+  }
+U3D_DIRECT_KERNEL_A(k_igemm_direct_32x16_na, 1, 1, DIR_NW_A, DIR_P1)
+U3D_DIRECT_KERNEL_A(k_igemm_direct_32x32_na, 1, 2, DIR_NW_A, DIR_P1)
+U3D_DIRECT_KERNEL_A(k_igemm_direct_32x64_na, 1, 4, DIR_NW_B, DIR_P1)
+U3D_DIRECT_KERNEL_A(k_igemm_direct_64x16_na, 2, 1, DIR_NW_A, DIR_P2)
+U3D_DIRECT_KERNEL_A(k_igemm_direct_64x32_na, 2, 2, DIR_NW_B, DIR_P2)
+
 typedef void (*direct_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const u16*, double*);
 
 // slot = shape * 4 + variant; waves per workgroup as instantiated above
@@ -377,6 +399,9 @@ static const struct { int kp, cout, waves; direct_kernel_t k[4]; } DIR_SHAPES[] 
     {64, 32, DIR_NW_B, {k_igemm_direct_64x32_k, k_igemm_direct_64x32_n, k_igemm_direct_64x32_ns, k_igemm_direct_64x32_nf}},
 };
 constexpr int DIR_NSHAPES = sizeof(DIR_SHAPES) / sizeof(DIR_SHAPES[0]);
+typedef void (*direct_affine_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, const u16*, const float*, int);
+static const direct_affine_kernel_t DIR_AFFINE[DIR_NSHAPES] = {      // in DIR_SHAPES' order
+    k_igemm_direct_32x16_na, k_igemm_direct_32x32_na, k_igemm_direct_32x64_na, k_igemm_direct_64x16_na, k_igemm_direct_64x32_na};
 
 DirectPlan u3d_plan_igemm_direct(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, bool nmajor, DirEpi epi) {
   DirectPlan p;
@@ -443,4 +468,21 @@ extern "C" int32_t u3d_igemm_direct_split_bf16(const void* in, const void* w3, c
   rc = u3d_launch_igemm_direct(p, hi, wl, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, (hipStream_t)s, out, nullptr);      // accumulate
   if (rc != U3D_OK) return rc;
   return u3d_launch_igemm_direct(p, lo, wh, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, (hipStream_t)s, out, nullptr);
+}
+
+// conv -> eval-mode BatchNorm (-> + residual) (-> ReLU) of the narrow 27-offset levels in one launch: the plan (grid, waves, LDS) is
+// the n-major bf16 one of the same shape, the kernel its AFFINE instantiation.
+extern "C" int32_t u3d_igemm_direct_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift,
+                                                int32_t relu, const void* addend, void* out, const int32_t* n_out_dev, int32_t n_out_cap,
+                                                int32_t cin, int32_t cout, u3d_stream s) {
+  U3D_REQUIRE(in && w_folded && nbr && shift && out && n_out_dev && n_out_cap >= 0 && (ld >= n_out_cap || -ld >= n_out_cap), U3D_ERR_ARG);
+  const DirectPlan p = u3d_plan_igemm_direct(n_out_cap, cin, cout, DIR_K, true, true, DIR_BF16);
+  if (p.slot < 0) return U3D_ERR_UNSUPPORTED;
+  if (p.grid == 0) return U3D_OK;
+  static unsigned long long lds_mask[DIR_NSHAPES] = {0};
+  const direct_affine_kernel_t kern = DIR_AFFINE[p.slot / 4];
+  u3d_allow_lds_impl((const void*)kern, (int)p.lds, &lds_mask[p.slot / 4]);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.waves * 64), p.lds, (hipStream_t)s, (const u16*)in, (const u16*)w_folded, nbr, ld, (u16*)out,
+                     n_out_dev, n_out_cap, cin, cout, (const u16*)addend, shift, relu != 0);
+  return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
 }

@@ -187,6 +187,13 @@ __device__ __forceinline__ f32x4 hl_sel(bool c, f32x4 a, f32x4 b) {
   return r;
 }
 
+// ReLU of the affine epilogue: v where it is positive, else +0
+__device__ __forceinline__ f32x4 hl_relu(f32x4 v) {
+  f32x4 r;
+  r[0] = v[0] > 0.f ? v[0] : 0.f; r[1] = v[1] > 0.f ? v[1] : 0.f; r[2] = v[2] > 0.f ? v[2] : 0.f; r[3] = v[3] > 0.f ? v[3] : 0.f;
+  return r;
+}
+
 // BatchNorm-backward statistics mode of the epilogue (== u3d_bn_epi; see glds_epilogue.inc / BnEpi in igemm_bf16.hip, the forward / input-gradient unit)
 struct HlBn {
   const u16* x = nullptr; const u16* y = nullptr;
@@ -195,11 +202,20 @@ struct HlBn {
 };
 
 // in/out/addend bf16 [n][64]; wgt: k_halo_wpack of bf16 [27][64 (n)][64 (reduction)]; stats f64 [tiles][2][64] or null
+// AFFINE (inference, eval-mode BatchNorm folded into wgt; u3d_subm_halo_conv64_affine_bf16): out = bf16(relu(acc + shift[col] +
+// addend)), one rounding, forward only and without statistics.  A compile-time switch: the kernel sits at 128 accumulator registers
+// and two workgroups per CU, and the training / eval instantiation <false> (AF is the empty pack: it has no further argument) stays the code it was.
+struct HlAffine { const float* shift; int relu; };      // shift f32 [C]; the one element of AF when AFFINE
+__device__ __forceinline__ HlAffine hl_affine(const HlAffine& a) { return a; }
+
+template <bool AFFINE, typename... AF>
 __global__ __launch_bounds__(256, 2) void k_subm_halo64(const u16* __restrict__ in, const u16* __restrict__ wgt,
                                                         const int32_t* __restrict__ tile_rows, const u16* __restrict__ loc,
                                                         const int32_t* __restrict__ tile_cnt, const int32_t* __restrict__ n_dev, int n_cap,
                                                         int krev, const u16* __restrict__ addend, u16* __restrict__ out,
-                                                        double* __restrict__ stats, const HlBn bn, int maxs) {
+                                                        double* __restrict__ stats, const HlBn bn, int maxs, const AF... af) {
+  static_assert(sizeof...(AF) == (AFFINE ? 1 : 0), "AFFINE: one HlAffine");
+  if constexpr (AFFINE) { krev = 0; stats = nullptr; }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u16* xs = (u16*)smem;                           // [HL_MAXS][HL_RS]
   const int tid = threadIdx.x;
@@ -330,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void k_subm_halo64(const u16* __restrict__ 
   // BatchNorm-backward statistics mode: this wave's x (and y) fragments of the rows it will own are requested before the
   // reduce-scatter (8 B loads with a row stride: their latency hides behind the exchange)
   bf16x4 xr[2][4], yr[2][4];
-  if (bn.x) {
+  if (!AFFINE && bn.x) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int m = m0 + (4 * (int)h + 2 * (int)q + j) * 16 + r16;
@@ -386,11 +402,15 @@ __global__ __launch_bounds__(256, 2) void k_subm_halo64(const u16* __restrict__ 
     for (int b = 0; b < 4; ++b) {
       const int col = b * 16 + 4 * kq;
       f32x4 v = fin[j][b];
+      if constexpr (AFFINE) v += *(const f32x4*)(hl_affine(af...).shift + col);
       if (addend) v += __builtin_convertvector(*(const bf16x4*)(addend + (long long)m * HL_C + col), f32x4);
+      if constexpr (AFFINE) {
+        if (hl_affine(af...).relu) v = hl_relu(v);
+      }
       const bf16x4 o = __builtin_convertvector(v, bf16x4);
       *(bf16x4*)(out + (long long)m * HL_C + col) = o;
       const f32x4 vr = __builtin_convertvector(o, f32x4);      // statistics of the ROUNDED values: what the BatchNorm behind reads
-      if (bn.x) {                                              // input gradient: the BatchNorm-backward sums of the producing layer
+      if (!AFFINE && bn.x) {                                              // input gradient: the BatchNorm-backward sums of the producing layer
         const f32x4 xh = (__builtin_convertvector(xr[j][b], f32x4) - *(const f32x4*)(bn.mean + col)) * *(const f32x4*)(bn.invstd + col);
         f32x4 gm = vr;
         if (bn.relu) {
@@ -453,11 +473,15 @@ __global__ __launch_bounds__(256) void k_halo_wpack128(const u16* __restrict__ s
 }
 
 #define HL_C2 128
+// AFFINE: as k_subm_halo64 (u3d_subm_halo_conv128_affine_bf16)
+template <bool AFFINE, typename... AF>
 __global__ __launch_bounds__(256, 2) void k_subm_halo128(const u16* __restrict__ in, const u16* __restrict__ wgt,
                                                          const int32_t* __restrict__ tile_rows, const u16* __restrict__ loc,
                                                          const int32_t* __restrict__ tile_cnt, const int32_t* __restrict__ n_dev, int n_cap,
                                                          int krev, const u16* __restrict__ addend, u16* __restrict__ out,
-                                                         double* __restrict__ stats, int maxs, int kvol) {
+                                                         double* __restrict__ stats, int maxs, int kvol, const AF... af) {
+  static_assert(sizeof...(AF) == (AFFINE ? 1 : 0), "AFFINE: one HlAffine");
+  if constexpr (AFFINE) { krev = 0; stats = nullptr; }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u16* xs = (u16*)smem;                           // [HL_MAXS][HL_RS]: one 64-channel half of the distinct rows
   const int tid = threadIdx.x;
@@ -569,7 +593,11 @@ __global__ __launch_bounds__(256, 2) void k_subm_halo128(const u16* __restrict__
     for (int b = 0; b < 2; ++b) {
       const int col = (2 * w + b) * 16 + 4 * kq;
       f32x4 v = acc[a][b];
+      if constexpr (AFFINE) v += *(const f32x4*)(hl_affine(af...).shift + col);
       if (addend) v += __builtin_convertvector(*(const bf16x4*)(addend + (long long)m * HL_C2 + col), f32x4);
+      if constexpr (AFFINE) {
+        if (hl_affine(af...).relu) v = hl_relu(v);
+      }
       const bf16x4 o = __builtin_convertvector(v, bf16x4);
       *(bf16x4*)(out + (long long)m * HL_C2 + col) = o;
       const f32x4 vr = __builtin_convertvector(o, f32x4);      // statistics of the ROUNDED values
@@ -853,10 +881,24 @@ extern "C" int32_t u3d_subm_halo_conv64_bf16(const void* in, const void* w_packe
   if (bn) { e.x = (const u16*)bn->x; e.y = (const u16*)bn->y; e.mean = bn->mean; e.invstd = bn->invstd; e.gamma = bn->gamma; e.beta = bn->beta; e.relu = bn->relu; }
   const int lds = HL_MAXS * HL_RS * 2;
   static_assert(HL_MAXS * HL_RS * 2 >= 4 * 16 * 64 * 16, "stage buffer holds the first reduce-scatter round");
-  U3D_ALLOW_LDS(k_subm_halo64, lds);
-  k_subm_halo64<<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
+  U3D_ALLOW_LDS(k_subm_halo64<false>, lds);
+  k_subm_halo64<false><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
                                                                     n_cap, krev, (const u16*)addend, (u16*)out, stats, e,
                                                                     (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+extern "C" int32_t u3d_subm_halo_conv64_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
+                                                    const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend,
+                                                    void* out, const float* shift, int32_t relu, int32_t max_slots, u3d_stream s) {
+  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && shift && n_cap > 0, U3D_ERR_ARG);
+  const int lds = HL_MAXS * HL_RS * 2;
+  U3D_ALLOW_LDS((k_subm_halo64<true, HlAffine>), lds);
+  k_subm_halo64<true, HlAffine><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
+                                                                          n_cap, 0, (const u16*)addend, (u16*)out, nullptr, HlBn{},
+                                                                          (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS,
+                                                                          HlAffine{shift, relu != 0});
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
@@ -901,11 +943,24 @@ extern "C" int32_t u3d_subm_halo_conv128_bf16(const void* in, const void* w_pack
                                               u3d_stream s) {
   U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && n_cap > 0 && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
   const int lds = HL_MAXS * HL_RS * 2;
-  U3D_ALLOW_LDS(k_subm_halo128, lds);
-  k_subm_halo128<<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev, n_cap,
+  U3D_ALLOW_LDS(k_subm_halo128<false>, lds);
+  k_subm_halo128<false><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev, n_cap,
                                                                      krev, (const u16*)addend, (u16*)out, stats,
                                                                      (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS, kvol);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
-
+extern "C" int32_t u3d_subm_halo_conv128_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
+                                                     const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend,
+                                                     void* out, const float* shift, int32_t relu, int32_t max_slots, int32_t kvol,
+                                                     u3d_stream s) {
+  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && shift && n_cap > 0 && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
+  const int lds = HL_MAXS * HL_RS * 2;
+  U3D_ALLOW_LDS((k_subm_halo128<true, HlAffine>), lds);
+  k_subm_halo128<true, HlAffine><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
+                                                                           n_cap, 0, (const u16*)addend, (u16*)out, nullptr,
+                                                                           (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS, kvol,
+                                                                           HlAffine{shift, relu != 0});
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}

@@ -7,20 +7,32 @@ for the whole model, native.bn_fold) and hands the shift to the epilogue of the 
 launch, one trip, no per-forward weight cast.
 
     model.set_precision("bf16").eval()
-    inf = InferenceModel(model)
+    inf = InferenceModel(model)                          # or InferenceModel(model, sparse_levels=True), see below
     det = inf.simple_test_batched(img_metas, points, on_device=True)
     inf.refresh()            # after parameters or running statistics changed
     inf.folded, inf.unfolded
 
-What folds: every conv + BatchNorm (+ ReLU) pair whose channel counts are multiples of 64 and whose BatchNorm does nothing else -
-all of SECOND3D, the FPN's extra_blocks and its first level when that is a plain convolution, and in SparseEncoderHD the strided
-64 / 128-channel convolutions and conv_out.  What keeps conv + u3d_bn_apply, exactly as under model.eval() (`inf.unfolded` names each
-layer and the reason):
-  * conv_input and the narrow sparse levels (16 / 32 channels): direct-operand kernels, whose `bias` argument is an addend;
-  * the SubM residual blocks of the 64- / 128-channel levels: the halo kernels (csrc/subm_halo.hip) have no shift epilogue, and
-    conv2's BatchNorm also adds the identity;
+What folds by default: every conv + BatchNorm (+ ReLU) pair whose channel counts are multiples of 64 and whose BatchNorm does nothing
+else - all of SECOND3D, the FPN's extra_blocks and its first level when that is a plain convolution, and in SparseEncoderHD the strided
+64 / 128-channel convolutions and conv_out.  What keeps conv + u3d_bn_apply by default, exactly as under model.eval() (`inf.unfolded`
+names each layer and the reason):
+  * conv_input (a padded 4 / 5-channel input on its own kernel);
+  * the narrow sparse levels (16 / 32 channels) and the SubM residual blocks of the 64- / 128-channel levels: the plain entries of
+    the direct-operand and halo kernels take an addend but no shift, and a block's second BatchNorm also adds the identity - these
+    are what sparse_levels=True folds, below;
   * the FPN's transposed-conv levels and every level after the first: their BatchNorm apply carries the lattice permutation
     (row_map) and the running level sum (post_add) for free.
+sparse_levels=True (off by default) also folds the rest of SparseEncoderHD: every SparseBasicBlock conv and the narrow strided
+convs.  The halo kernels and the direct-operand kernels have an affine instantiation for it (shift, then the block's identity as the
+addend, then ReLU, one rounding: u3d_subm_halo_conv64 / 128_affine_bf16, u3d_igemm_direct_affine_bf16), and refresh() packs the folded
+64- / 128-channel weights into the halo kernels' fragment order once (one batched launch per channel count) instead of once per conv
+and forward.  conv_input and the FPN entries above stay unfolded.  A folded conv is routed by shape when it runs (sparse.conv_folded):
+halo kernel, direct-operand kernel, the LDS-DMA affine kernel - and ONE case falls back to conv + u3d_bn_apply exactly as model.eval()
+runs it: the conv2 of a 64- / 128- / 256-channel block on a level the halo kernels do not serve (fewer than 4096 rows, more rows than
+the halo build's bitmap holds, or 256 channels as in ScanNet-large's last stage).  Its BatchNorm adds the identity, and the LDS-DMA
+kernels take a shift or an addend, not both.  Such a layer is listed in `folded` (its weights are folded; conv1 of the same block takes
+the LDS-DMA affine kernel) and costs its u3d_bn_apply launch on the levels where it falls back.
+
 The model itself is not changed: the folded route is taken only inside InferenceModel's own scope (sparse.fold_scope), and
 `model.simple_test*` called directly stays the unfolded yardstick.
 
@@ -47,17 +59,20 @@ def _wide(cin, cout):
     return cin % 64 == 0 and cout % 64 == 0
 
 
-def classify(model):
+def classify(model, sparse_levels=False):
     """-> (folded, unfolded): folded = [(name, weight parameter, layout, BatchNorm module)], unfolded = [(name, reason)], in forward
-    order.  `name` is the convolution's module path.  Needs no device."""
+    order.  `name` is the convolution's module path.  Needs no device.  sparse_levels: also fold SparseEncoderHD's block convs and
+    narrow strided convs (input channels % 4 == 0: what the fold kernel writes)."""
     from .plugin.dense import SECOND3D, SECOND3DFPN
     from .plugin.sparse_encoder import SparseBasicBlock, SparseEncoderHD
     names = {id(m): n for n, m in model.named_modules()}
     folded, unfolded = [], []
 
-    def pair(conv, bn, weight, layout, cin, cout, why=None):
+    def pair(conv, bn, weight, layout, cin, cout, why=None, sparse_level=False):
         name = names[id(conv)]
-        if why is None and not _wide(cin, cout):
+        if sparse_level and sparse_levels and cin % 4 == 0:
+            why = None                  # the halo / direct-operand affine kernels, else the LDS-DMA one (sparse.conv_folded)
+        elif why is None and not _wide(cin, cout):
             why = _WHY_NARROW.format(cin=cin, cout=cout)
         if why is None and not (isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.affine and bn.track_running_stats):
             why = "BatchNorm without affine parameters or running statistics"
@@ -74,9 +89,9 @@ def classify(model):
             for m in stage:
                 if isinstance(m, SparseBasicBlock):
                     for conv, bn in ((m.conv1, m.bn1), (m.conv2, m.bn2)):
-                        pair(conv, bn, conv.weight, "dhwio", conv.cin, conv.cout, _WHY_BLOCK if _wide(conv.cin, conv.cout) else None)
+                        pair(conv, bn, conv.weight, "dhwio", conv.cin, conv.cout, _WHY_BLOCK if _wide(conv.cin, conv.cout) else None, True)
                 else:
-                    pair(m[0], m[1], m[0].weight, "dhwio", m[0].cin, m[0].cout)
+                    pair(m[0], m[1], m[0].weight, "dhwio", m[0].cin, m[0].cout, None, True)
         c = enc.conv_out[0]
         pair(c, enc.conv_out[1], c.weight, "dhwio", c.cin, c.cout)
     elif enc is not None:
@@ -109,7 +124,7 @@ class InferenceModel:
     """A Uni3DETR in eval mode and bf16 precision with its foldable BatchNorms folded away.  Owns the folded weights and shifts;
     the wrapped model keeps its parameters, its state_dict and its own (unfolded) eval path."""
 
-    def __init__(self, model):
+    def __init__(self, model, sparse_levels=False):
         if model.training:
             raise RuntimeError("InferenceModel folds eval-mode BatchNorm: call model.eval() first")
         prec = getattr(model, "precision", None)
@@ -117,27 +132,40 @@ class InferenceModel:
             raise ValueError(f"InferenceModel folds into bf16 weights: set_precision('bf16') first (the model is in {prec!r} mode, "
                              "which keeps the unfolded path)")
         self.model = model
-        self._pairs, unfolded = classify(model)
+        self.sparse_levels = bool(sparse_levels)
+        self._pairs, unfolded = classify(model, self.sparse_levels)
+        # the pairs only sparse_levels folds: their entries carry a third item and take sparse.conv_folded's routing
+        self._sparse = {p[0] for p in self._pairs} - {p[0] for p in classify(model)[0]} if self.sparse_levels else set()
         self.folded = [p[0] for p in self._pairs]
         self.unfolded = list(unfolded)
         self._table, self._sig = None, None
         self._map = {}
         self._buffers = []
+        self._packs = None
         if self._pairs and self._pairs[0][1].is_cuda:
             self._allocate()
             self.refresh()
 
     def _allocate(self):
+        """Per pair (w_folded, shift); a pair that only sparse_levels folds gets a third item: w_packed, the folded weights in the
+        halo kernels' fragment order, for the SubM block convs those kernels serve (27 offsets, 64 -> 64 / 128 -> 128), else None."""
+        from .plugin.sparse_encoder import SparseConvWeight
+        halo_convs = {id(m.weight) for m in self.model.modules() if isinstance(m, SparseConvWeight) and m.subm} if self.sparse_levels else ()
         self._buffers = []
-        for _, w, layout, bn in self._pairs:
+        for name, w, layout, bn in self._pairs:
             k, cout, cin = nv.conv_weight_strides(tuple(w.shape), layout)[:3]
-            self._buffers.append((torch.empty((k, cout, cin), dtype=torch.bfloat16, device=w.device),
-                                  torch.empty((cout,), dtype=torch.float32, device=w.device)))
+            buf = (torch.empty((k, cout, cin), dtype=torch.bfloat16, device=w.device),
+                   torch.empty((cout,), dtype=torch.float32, device=w.device))
+            if name in self._sparse:
+                buf += (torch.empty_like(buf[0]) if (id(w) in halo_convs and k == 27 and cin == cout and cin in (64, 128)) else None,)
+            self._buffers.append(buf)
         self._map = {id(p[3]): b for p, b in zip(self._pairs, self._buffers)}
+        self._packs = None
 
     def refresh(self):
-        """Fold again: after an optimizer step, load_state_dict or a change of the running statistics.  One launch; the job table is
-        rebuilt only when a parameter or buffer moved in memory."""
+        """Fold again: after an optimizer step, load_state_dict or a change of the running statistics.  One launch - with
+        sparse_levels, one more per channel count (64, 128) that packs the folded block weights for the halo kernels; the job table
+        and the pack plans are rebuilt only when a parameter or buffer moved in memory."""
         if not self._pairs:
             return self
         if not self._buffers or self._buffers[0][0].device != self._pairs[0][1].device:
@@ -146,13 +174,22 @@ class InferenceModel:
         sig = tuple(t.data_ptr() for _, w, _, bn in self._pairs for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var))
         if self._table is None or sig != self._sig:
             rows = []
-            for (_, w, layout, bn), (wf, shift) in zip(self._pairs, self._buffers):
+            for (_, w, layout, bn), (wf, shift, *_) in zip(self._pairs, self._buffers):
                 for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var):
                     if t.dtype != torch.float32:
                         raise TypeError("InferenceModel folds from f32 master parameters and statistics")
                 rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, wf, shift))
             self._table, self._sig = nv.BnFoldTable(rows), sig
         self._table.run()
+        if self._packs is None:
+            dev = self._buffers[0][0].device
+            by_c = {}
+            for b in self._buffers:
+                if len(b) > 2 and b[2] is not None:
+                    by_c.setdefault(b[0].shape[1], []).append((b[0], b[2]))
+            self._packs = [nv.subm_halo_wpack_plan(by_c[c], dev) for c in sorted(by_c)]
+        for plan in self._packs:
+            nv.subm_halo_wpack_batched(plan)
         return self
 
     @contextlib.contextmanager

@@ -137,6 +137,9 @@ _SIGS = {
     "u3d_subm_halo_wpack": (_I, [_P, _P, _P]),
     "u3d_subm_halo_wpack_batched": (_I, [_P, _P, _I, _P]),
     "u3d_subm_halo_conv64_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "u3d_subm_halo_conv64_affine_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "u3d_subm_halo_conv128_affine_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "u3d_igemm_direct_affine_bf16": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "u3d_bn_apply": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "u3d_bn_bwd_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
     "u3d_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
@@ -689,6 +692,40 @@ def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=Fals
     return (out, stats, SubmHalo.TILE) if want_stats else out
 
 
+def subm_halo_conv_affine(inp, w_packed, halo, shift, relu, addend=None, max_slots=0, out=None, tag="spconv_fwd"):
+    """act(conv(inp) + shift + addend) of a 64 -> 64 / 128 -> 128 SubM conv whose eval-mode BatchNorm is folded into the weights, out
+    of the level's halo tables in one launch (u3d_subm_halo_conv64_affine_bf16 / _conv128_affine_bf16).  w_packed: subm_halo_wpack of
+    the FOLDED n-major weights (bn_fold), shift f32 [C], addend bf16 [n, C] or None (the residual block's identity).  Rows at or past
+    *halo.n_dev of `out` are left as they are."""
+    c = inp.shape[1]
+    assert inp.dtype == torch.bfloat16 and c in (64, 128) and tuple(w_packed.shape) == (halo.kvol, c, c) and inp.shape[0] == halo.n_cap
+    assert w_packed.dtype == torch.bfloat16 and (c == 128 or halo.kvol == 27)
+    assert shift.dtype == torch.float32 and tuple(shift.shape) == (c,) and shift.data_ptr() % 16 == 0
+    assert addend is None or (addend.dtype == torch.bfloat16 and addend.shape == inp.shape)
+    if out is None:
+        out = torch.empty_like(inp)
+    assert out.shape == inp.shape and out.dtype == torch.bfloat16
+    t = TIMER
+    e0 = t.begin() if t is not None else None
+    if c == 64:
+        _check(lib().u3d_subm_halo_conv64_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
+                                                      _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
+                                                      int(max_slots), _stream()), "subm_halo_conv64_affine_bf16")
+    else:
+        _check(lib().u3d_subm_halo_conv128_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
+                                                       _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
+                                                       int(max_slots), halo.kvol, _stream()), "subm_halo_conv128_affine_bf16")
+    if t is not None:
+        meta = None
+        if t.mode == "census":
+            n = halo.n_cap
+            pairs = int((halo.nbr[:, :n] >= 0).sum().item())
+            meta = dict(kind=CALL_KIND, v2=True, n_in=n, n_out=n, cin=c, cout=c, kvol=halo.kvol, pairs=pairs,
+                        bytes=n * c * 2 * 2 + 8 * pairs + halo.kvol * c * c * 2, flops=2 * pairs * c * c)
+        t.end(tag, e0, meta)
+    return out
+
+
 def bn_finalize_partials(stats, tile_rows, n_dev, n_cap, eps, momentum, running_mean=None, running_var=None, num_batches=None):
     nblocks, _, c = stats.shape
     mean = torch.empty((c,), dtype=torch.float32, device=stats.device)
@@ -1066,6 +1103,33 @@ def igemm_fwd_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, out=None
         meta = None
         if t.mode == "census":
             pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
+            meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
+                        bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
+        t.end(tag, e0, meta)
+    return out
+
+
+def igemm_direct_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, addend=None, out=None, tag="spconv_fwd"):
+    """act(conv(inp; w_folded) + shift + addend) on a narrow 27-offset level in one launch of the direct-operand kernel
+    (u3d_igemm_direct_affine_bf16): inp bf16 [n_in, cin], w_folded bf16 [27, cout, cin] (bn_fold), nbr int32 [27, ld], shift f32 [cout],
+    addend bf16 [n_out, cout] or None.  Rows at or past *n_out_dev of `out` are left as they are.  A shape direct_serves() does not
+    name is an error: there is no other route."""
+    kvol, cout, cin = w_folded.shape
+    assert inp.dtype == torch.bfloat16 and w_folded.dtype == torch.bfloat16 and shift.dtype == torch.float32
+    assert kvol == 27 and inp.shape[1] == cin and tuple(shift.shape) == (cout,) and shift.data_ptr() % 16 == 0
+    assert nbr is not None and nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.shape[1] >= n_out
+    assert addend is None or (addend.dtype == torch.bfloat16 and tuple(addend.shape) == (n_out, cout))
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=inp.device)
+    assert tuple(out.shape) == (n_out, cout) and out.dtype == torch.bfloat16
+    t = TIMER
+    e0 = t.begin() if t is not None else None
+    _check(lib().u3d_igemm_direct_affine_bf16(_ptr(inp), _ptr(w_folded), _ptr(nbr), nbr.shape[1], _ptr(shift), int(bool(relu)), _ptr(addend),
+                                              _ptr(out), _ptr(n_out_dev), n_out, cin, cout, _stream()), "igemm_direct_affine_bf16")
+    if t is not None:
+        meta = None
+        if t.mode == "census":
+            pairs = int((nbr[:, :n_out] >= 0).sum().item())
             meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
                         bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
         t.end(tag, e0, meta)

@@ -262,6 +262,17 @@ def _split_table(geom, which, n_rows, plane):
     return cache[key]
 
 
+def _halo_of(geom, kvol, cin, cout):
+    """(The condition under which _SparseConv.forward has always picked the halo kernels, term for term, moved here so that the
+    folded inference route asks the same question: tests/test_bn_fold_sparse_cpu.py pins it against the expression it replaced.)
+    The level's halo tables (native.SubmHalo) when the halo kernels (subm_halo.hip) serve a bf16 conv on n-major weights: a
+    27-offset SubM conv, 64 -> 64 or 128 -> 128 channels, on a level of at least 4096 rows.  Else None."""
+    if not (SUBM_HALO and REV_SUBM_TABLE and geom.level is not None and kvol == 27 and cin == cout
+            and (cin == 64 or (cin == 128 and HALO_128)) and geom.n_out >= 4096):
+        return None
+    return geom.level.halo()
+
+
 class _SparseConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, geom, layout, want_stats=False, res_token=None, fan_token=None, bn_in=None):
@@ -321,10 +332,8 @@ class _SparseConv(torch.autograd.Function):
         ctx.halo = False
         ctx.save_for_backward(feats, kio)
         nbr = geom.nbr_fwd if kio.shape[0] > 1 else None
-        ctx.halo = (SUBM_HALO and REV_SUBM_TABLE and nmajor and geom.level is not None and kv == 27 and cin == cout
-                    and (cin == 64 or (cin == 128 and HALO_128)) and geom.n_out >= 4096
-                    and geom.level.halo() is not None)
-        ctx.halo_tab = geom.level.halo() if ctx.halo else None
+        ctx.halo_tab = _halo_of(geom, kv, cin, cout) if nmajor else None
+        ctx.halo = ctx.halo_tab is not None
         if ctx.halo:
             pk_fwd, ctx.pk_bwd = halo_packs(weight, kio, koi)
             if want_stats:
@@ -535,6 +544,7 @@ FUSED_CONV_STATS = True
 # ---- inference: eval-mode BatchNorm folded into the convolution (uni3detr_amd/inference.py) ---------------------------------------------
 # Inside fold_scope(table) a conv_bn() call whose BatchNorm module is in `table` (id(bn) -> (w_folded, shift), the buffers an
 # InferenceModel owns) runs as ONE launch, conv_affine(); every other call, and every call outside a scope, is what it always was.
+# An entry of three, (w_folded, shift, w_packed or None), is a sparse-level pair of InferenceModel(sparse_levels=True): conv_folded().
 _FOLD = [None]
 
 
@@ -564,6 +574,33 @@ def conv_affine(feats, w_folded, shift, geom, relu=True):
     return nv.igemm_fwd_affine(feats.contiguous(), w_folded, nbr, shift, relu, geom.n_out_dev, geom.n_out)
 
 
+def conv_folded(feats, ent, geom, residual=None, relu=True):
+    """relu(conv(feats; w_folded) + shift + residual) of a folded pair in one launch, on the kernel that serves the shape; ent =
+    (w_folded, shift, w_packed or None).  -> None where no kernel has the epilogue: a residual (a block's conv2) on a level the halo and the
+    direct-operand kernels do not serve - the LDS-DMA kernels take a shift OR an addend; the caller then runs conv + u3d_bn_apply."""
+    w_folded, shift, w_packed = ent
+    kvol, cout, cin = w_folded.shape
+    if torch.is_grad_enabled() and (feats.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("a folded conv + BatchNorm pair is an inference path: it records no autograd node")
+    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
+        raise RuntimeError(f"a folded conv + BatchNorm pair needs bf16 device rows, got {feats.dtype} on {feats.device}")
+    if feats.shape[1] != cin:
+        raise ValueError(f"folded conv: input has {feats.shape[1]} channels, folded weight expects {cin}")
+    if residual is not None and not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == (geom.n_out, cout)):
+        raise ValueError("folded conv: the residual must be bf16 rows of the output's shape")
+    halo = _halo_of(geom, kvol, cin, cout) if w_packed is not None else None
+    if halo is not None:
+        nv.CALL_KIND = geom.kind
+        return nv.subm_halo_conv_affine(feats.contiguous(), w_packed, halo, shift, relu, None if residual is None else residual.contiguous())
+    if nv.direct_serves(cin, cout, kvol) and geom.nbr_fwd is not None:
+        nv.CALL_KIND = geom.kind
+        return nv.igemm_direct_affine(feats.contiguous(), w_folded, geom.nbr_fwd, shift, relu, geom.n_out_dev, geom.n_out,
+                                      None if residual is None else residual.contiguous())
+    if residual is None:
+        return conv_affine(feats, w_folded, shift, geom, relu)
+    return None
+
+
 def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dhwio", post_add=None, res_take=None, res_give=None,
             fan_token=None, bn_in=None, bn_out=None):
     """conv -> BatchNorm rows (+ residual) (+ ReLU).  In training the conv's epilogue already reduces the BatchNorm statistics per row
@@ -571,9 +608,15 @@ def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dh
     if _FOLD[0] is not None:
         ent = _FOLD[0].get(id(bn))
         if ent is not None:
-            if bn.training or residual is not None or post_add is not None:
-                raise RuntimeError("a folded conv + BatchNorm pair was called in training mode, or with a residual / level sum")
-            return conv_affine(feats, ent[0], ent[1], geom, relu)
+            if len(ent) == 2:                   # (w_folded, shift): the default fold - the LDS-DMA affine kernel or an error
+                if bn.training or residual is not None or post_add is not None:
+                    raise RuntimeError("a folded conv + BatchNorm pair was called in training mode, or with a residual / level sum")
+                return conv_affine(feats, ent[0], ent[1], geom, relu)
+            if bn.training or post_add is not None:     # (w_folded, shift, w_packed or None): InferenceModel(sparse_levels=True)
+                raise RuntimeError("a folded conv + BatchNorm pair of a sparse level was called in training mode, or with a level sum")
+            y = conv_folded(feats, ent, geom, residual, relu)
+            if y is not None:
+                return y
     if FUSED_CONV_STATS and bn.training and feats.is_cuda and (feats.dtype == torch.bfloat16 or _split_serves(feats, feats.shape[1], bn.num_features) == "wide"):
         # res_take: this conv's input is the identity of a residual block - its backward sums the token's gradient into the input
         # gradient; res_give: this BatchNorm adds that identity - its backward leaves the identity's gradient in the token
