@@ -1323,3 +1323,212 @@ def test_batched_row_split_and_three_way_sum(cuda):
     assert torch.equal(nv.sum3(a, b, c), (a + b) + c)
     two = torch.randn(54, 64, 128, device=cuda)
     assert torch.equal(nv.sum3(two[:27], two[27:], c), (two[:27] + two[27:]) + c)
+
+
+def test_census_entry_of_every_conv_wrapper(cuda):
+    """Each of the eleven convolution wrappers of native.py under KernelTimer("census"): ONE census entry per call, under the documented
+    tag, whose dict equals the one worked out here from the table and the shapes (SURVEY.md §8d pricing: element size 2 / s, f32 weights
+    for a weight gradient, a split product priced as the f32 conv it stands for) - and the same outputs, bit for bit, under
+    KernelTimer("time") and with no timer."""
+    from uni3detr_amd import sparse as sp
+    lvl, nbr = _level(seed=3, n_pts=300, dims=(8, 8, 8))
+    n, nd = lvl.n, lvl.n_dev
+    halo = nv.SubmHalo(nbr, nd, n)
+    assert halo.ok
+    rev = nv.RevNbr(nbr)
+    torch.manual_seed(1)
+    ident = torch.arange(n, dtype=torch.int32, device=cuda).view(1, -1)
+    tri = lambda t: torch.cat([t, t, torch.where(t >= 0, t + n, t)], 0).contiguous()      # noqa: E731  (t, t, t + plane)
+    xb = {c: torch.randn(n, c, device=cuda).bfloat16() for c in (32, 64, 128)}
+    xf = torch.randn(n, 32, device=cuda)
+    wb = {(k, c): (torch.randn(k, c, c, device=cuda) * 0.1).bfloat16() for k, c in ((27, 32), (27, 64), (27, 128), (1, 128), (81, 32), (81, 128), (3, 128))}
+    wf = torch.randn(27, 32, 32, device=cuda) * 0.1
+    pk = {c: nv.subm_halo_wpack(wb[(27, c)]) for c in (64, 128)}
+    sh = {c: torch.randn(c, device=cuda) for c in (32, 64, 128)}
+    xs = {c: nv.split_rows(torch.randn(n, c, device=cuda), nd) for c in (32, 128)}
+    mean, invstd, gamma, beta = (torch.randn(128, device=cuda), torch.rand(128, device=cuda) + 0.5, torch.rand(128, device=cuda) + 0.5,
+                                 torch.randn(128, device=cuda))
+    epi = nv.BnEpi.of(xb[128], None, mean, invstd, gamma, beta, True)
+    kind = nv.CALL_KIND
+    pairs = int((nbr[:, :n] >= 0).sum())
+    assert 0 < pairs < 27 * n
+
+    def entry(cin, cout, kvol, p, s=2, w=None, v2=True, split=False):
+        w = s if w is None else w
+        d = dict(kind=kind, v2=v2, n_in=n, n_out=n, cin=cin, cout=cout, kvol=kvol, pairs=p,
+                 bytes=n * cin * s + n * cout * s + 8 * p + kvol * cin * cout * w, flops=2 * p * cin * cout)
+        if split:
+            d["split"] = True
+        return d
+
+    calls = [     # (what runs, tag, census dict)
+        (lambda: nv.spconv_fwd_stats(xb[128], wb[(27, 128)], nbr, nd, n, 128), "spconv_fwd", entry(128, 128, 27, pairs)),
+        (lambda: nv.spconv_fwd_stats(xb[128], wb[(1, 128)], None, nd, n, 128), "spconv_fwd", entry(128, 128, 1, n)),
+        (lambda: nv.spconv_dgrad_bnstats(xb[128], wb[(27, 128)], rev, nd, n, 128, None, epi), "spconv_dgrad", entry(128, 128, 27, pairs)),
+        (lambda: nv.spconv_dgrad_bnstats(xb[128], wb[(27, 128)], nbr, nd, n, 128, xb[128], epi), "spconv_dgrad", entry(128, 128, 27, pairs)),
+        (lambda: nv.subm_halo_wgrad(xb[64], xb[64].flip(0).contiguous(), halo), "spconv_wgrad", entry(64, 64, 27, pairs, w=4)),
+        (lambda: nv.subm_halo_conv(xb[64], pk[64], halo), "spconv_fwd", entry(64, 64, 27, pairs)),
+        (lambda: nv.subm_halo_conv(xb[128], pk[128], halo, krev=True, addend=xb[128], want_stats=True, tag="spconv_dgrad"), "spconv_dgrad",
+         entry(128, 128, 27, pairs)),
+        (lambda: nv.subm_halo_conv_affine(xb[64], pk[64], halo, sh[64], True), "spconv_fwd", entry(64, 64, 27, pairs)),
+        (lambda: nv.subm_halo_conv_affine(xb[128], pk[128], halo, sh[128], False, addend=xb[128]), "spconv_fwd", entry(128, 128, 27, pairs)),
+        (lambda: nv.spconv_fwd(xb[32], wb[(27, 32)], nbr, nd, n, 32), "spconv_fwd", entry(32, 32, 27, pairs)),
+        (lambda: nv.spconv_fwd(xb[32], wb[(27, 32)], rev, nd, n, 32, transpose_w=True, addend=xb[32]), "spconv_dgrad", entry(32, 32, 27, pairs)),
+        (lambda: nv.spconv_fwd(xb[32], wb[(27, 32)], nbr, nd, n, 32, transpose_w=True, tag="spconv_fwd"), "spconv_fwd", entry(32, 32, 27, pairs)),
+        (lambda: nv.spconv_fwd(xf, wf, nbr, nd, n, 32), "spconv_fwd", entry(32, 32, 27, pairs, s=4, v2=False)),
+        (lambda: nv.spconv_fwd(xf, wf, rev, nd, n, 32, transpose_w=True), "spconv_dgrad", entry(32, 32, 27, pairs, s=4, v2=False)),
+        (lambda: nv.spconv_fwd_split_direct(xs[32], wb[(81, 32)], nbr, nd, n, 32), "spconv_fwd", entry(32, 32, 27, pairs, s=4, split=True)),
+        (lambda: nv.spconv_fwd_split_direct(xs[32], wb[(81, 32)], rev, nd, n, 32, tag="spconv_dgrad"), "spconv_dgrad",
+         entry(32, 32, 27, pairs, s=4, split=True)),
+        (lambda: nv.igemm_fwd_affine(xb[128], wb[(27, 128)], nbr, sh[128], True, nd, n), "spconv_fwd", entry(128, 128, 27, pairs)),
+        (lambda: nv.igemm_fwd_affine(xb[128], wb[(1, 128)], None, sh[128], False, nd, n), "spconv_fwd", entry(128, 128, 1, n)),
+        (lambda: nv.igemm_direct_affine(xb[32], wb[(27, 32)], nbr, sh[32], True, nd, n, addend=xb[32]), "spconv_fwd", entry(32, 32, 27, pairs)),
+        (lambda: nv.spconv_fwd_split(xs[128], wb[(81, 128)], tri(nbr), nd, n, 128, want_stats=True), "spconv_fwd",
+         entry(128, 128, 27, pairs, s=4, split=True)),
+        (lambda: nv.spconv_fwd_split(xs[128], wb[(3, 128)], tri(ident), nd, n, 128, tag="spconv_dgrad"), "spconv_dgrad",
+         entry(128, 128, 1, n, s=4, split=True)),
+        (lambda: nv.spconv_wgrad(xb[32], xb[32].flip(0).contiguous(), nbr, nd, 27), "spconv_wgrad", entry(32, 32, 27, pairs, w=4)),
+        (lambda: nv.spconv_wgrad(xb[128], xb[128].flip(0).contiguous(), None, nd, 1, out_oik=True), "spconv_wgrad", entry(128, 128, 1, n, w=4)),
+        (lambda: nv.spconv_wgrad(xf, xf.flip(0).contiguous(), nbr, nd, 27), "spconv_wgrad", entry(32, 32, 27, pairs, s=4, w=4, v2=False)),
+    ]
+
+    def run(timer):
+        nv.TIMER = timer
+        outs = []
+        for i, (fn, _, _) in enumerate(calls):
+            before = len(timer.calls) if timer is not None else 0
+            r = fn()
+            assert r is not None, i                      # the wrapper's own kernel served the call
+            if timer is not None:
+                assert len(timer.calls) == before + 1, i
+            outs.append([t for t in (r if isinstance(r, tuple) else (r,)) if torch.is_tensor(t)])
+        return outs
+
+    try:
+        census, timed = nv.KernelTimer("census"), nv.KernelTimer("time")
+        a = run(census)
+        assert len(census.census) == len(calls)
+        for i, ((tag, meta), (_, want_tag, want)) in enumerate(zip(census.census, calls)):
+            assert tag == want_tag and meta == want, (i, tag, meta, want)
+        assert [t for t, _, _ in census.calls] == [c[1] for c in calls]
+        b = run(timed)
+        assert timed.census == [] and [t for t, _, _ in timed.calls] == [c[1] for c in calls]
+        c = run(None)
+    finally:
+        nv.TIMER = None
+    for i, (p, q, r) in enumerate(zip(a, b, c)):
+        assert len(p) == len(q) == len(r) > 0
+        for u, v, w in zip(p, q, r):
+            assert torch.equal(u, v) and torch.equal(u, w), i
+    # (the calls compute what they say: the first spconv_fwd against the gather-matmul reference)
+    exp = _ref_conv(xb[32], wb[(27, 32)], nbr, n)
+    assert (a[9][0].float() - exp).abs().max() / exp.abs().max() < 1e-2
+    assert all(ms >= 0 for _, ms in timed.durations_ms())
+
+
+def _grads_with_and_without_tokens(build, x0, params):
+    """build(x, params, tokens: bool) -> (output, the tokens it made); -> {tokens: [x.grad, *param grads]} for one fixed output gradient."""
+    from uni3detr_amd import sparse as sp
+    res = {}
+    for tokens in (True, False):
+        x = x0.clone().requires_grad_(True)
+        ps = [p.clone().requires_grad_(True) for p in params]
+        y, toks = build(x, ps, tokens)
+        torch.manual_seed(77)
+        y.backward(torch.randn(y.shape, device=y.device).to(y.dtype))
+        for t in toks:
+            if isinstance(t, sp.ResidualToken):
+                assert t.dres is None
+            else:
+                assert t.acc is None and t.remaining == t.n
+        res[tokens] = [x.grad.float()] + [p.grad.float() for p in ps]
+    return res
+
+
+GRAD_ADDEND_ROUTES = ["bf16_table", "bf16_halo", "bf16_direct", "f32_exact", "split_wide", "split_narrow", "strided_bf16", "strided_split"]
+
+
+@pytest.mark.parametrize("route", GRAD_ADDEND_ROUTES)
+def test_gradient_addends_same_on_every_route(cuda, route):
+    """The residual identity's gradient (sp.ResidualToken) and the other fan-out branches' sum (sp.FanoutToken) enter a conv's input gradient
+    on every route - in the kernel's epilogue or added after it - and give what autograd's own sums give: x.grad and the weight gradients
+    with the tokens against the same graph with None in their place.  bf16: 1.6e-2 of the result's max (the two-pass form rounds
+    twice, as test_input_gradient_with_addend_epilogue); f32 and split-bf16: 1e-5 (as the SECOND3D fan-out test)."""
+    from uni3detr_amd import sparse as sp
+    if route.startswith("strided"):
+        return _strided_route_addends(cuda, route == "strided_bf16")
+    c = {"bf16_table": 128, "bf16_halo": 64, "bf16_direct": 32, "f32_exact": 32, "split_wide": 128, "split_narrow": 32}[route]
+    bf16 = route.startswith("bf16")
+    lvl0, _ = _level() if route == "bf16_halo" else _level(seed=3, n_pts=300, dims=(8, 8, 8))
+    assert (lvl0.n >= 4096) == (route == "bf16_halo")
+    tol = 1.6e-2 if bf16 else 1e-5
+    torch.manual_seed(c)
+    x0 = torch.randn(lvl0.n, c, device=cuda).to(torch.bfloat16 if bf16 else torch.float32)
+    ws = [torch.randn(3, 3, 3, c, c, device=cuda) * (0.6 / (27 * c) ** 0.5) for _ in range(2)]
+    levels = []
+
+    def geom_of():
+        lv = sp.Level(lvl0.grid, lvl0.coords, lvl0.n, lvl0.n_dev)
+        levels.append(lv)
+        return lv, sp.subm_geom(lv)
+
+    def residual_pair(x, w, tokens):
+        lv, geom = geom_of()
+        bns = [torch.nn.BatchNorm1d(c, eps=1e-3, momentum=0.01).to(cuda).train() for _ in range(2)]
+        tok = sp.ResidualToken() if tokens else None
+        o = sp.conv_bn(x, w[0], geom, bns[0], lv.n_dev, None, True, res_take=tok)
+        return sp.conv_bn(o, w[1], geom, bns[1], lv.n_dev, x, True, res_give=tok), [tok] if tokens else []
+
+    def fanout(x, w, tokens):
+        lv, geom = geom_of()
+        fan = sp.FanoutToken(2) if tokens else None
+        return sp.sparse_conv(x, w[0], geom, fan_token=fan) + sp.sparse_conv(x, w[1], geom, fan_token=fan), [fan] if tokens else []
+
+    with sp.split_scope(route.startswith("split")):
+        for build in (residual_pair, fanout):
+            res = _grads_with_and_without_tokens(build, x0, ws)
+            for i, (p, q) in enumerate(zip(res[True], res[False])):
+                err = float((p - q).abs().max() / q.abs().max())
+                print(route, build.__name__, i, err)
+                assert torch.isfinite(p).all() and err <= tol, (build.__name__, i, err)
+        if route == "bf16_table":
+            # no input gradient wanted, a token present: the conv's backward still clears what the BatchNorm left in it
+            x = x0.clone()
+            w = [p.clone().requires_grad_(True) for p in ws]
+            y, (tok,) = residual_pair(x, w, True)
+            y.backward(torch.ones_like(y))
+            assert tok.dres is None and x.grad is None and all(p.grad is not None for p in w)
+    if route == "bf16_halo":
+        assert all(isinstance(lv._halo, nv.SubmHalo) for lv in levels)          # halo tables were built: the halo kernels ran
+    elif route == "bf16_table":
+        assert all(lv._halo is None for lv in levels)                            # never asked for: the table kernels ran
+
+
+def _strided_route_addends(cuda, bf16):
+    """test_gradient_addends_same_on_every_route for the strided input gradient (per-offset products over the output rows + u3d_tap_gather_sum, bf16 and inside the split
+    scope), two-branch fan-out only, at the smallest lattice with n_out * 16 <= n_in: stride (1, 4, 4), 64 -> 64, one scene of (2, 16, 16)."""
+    from uni3detr_amd import sparse as sp
+    from uni3detr_amd.plugin import dense as dn
+    geom, _ = dn.Lattice.conv(cuda, 1, (2, 16, 16), (1, 3, 3), (1, 4, 4), (0, 1, 1))
+    assert geom.strided and geom.n_out * 16 <= geom.n_in and geom.n_in == 512
+    torch.manual_seed(4)
+    x0 = torch.randn(geom.n_in, 64, device=cuda).to(torch.bfloat16 if bf16 else torch.float32)
+    ws = [torch.randn(1, 3, 3, 64, 64, device=cuda) * 0.05 for _ in range(2)]
+    real, ran = nv.tap_gather_sum, []
+    nv.tap_gather_sum = lambda *a, **k: (ran.append(k.get("addend") is not None), real(*a, **k))[1]
+
+    def fanout(x, w, tokens):
+        fan = sp.FanoutToken(2) if tokens else None
+        return sp.sparse_conv(x, w[0], geom, fan_token=fan) + sp.sparse_conv(x, w[1], geom, fan_token=fan), [fan] if tokens else []
+
+    try:
+        with sp.split_scope(not bf16):
+            res = _grads_with_and_without_tokens(fanout, x0, ws)
+    finally:
+        nv.tap_gather_sum = real
+    assert len(ran) == 4                                   # two branches, with and without the token: the gather served every input gradient
+    tol = 1.6e-2 if bf16 else 1e-5
+    for i, (p, q) in enumerate(zip(res[True], res[False])):
+        err = float((p - q).abs().max() / q.abs().max())
+        print("strided", bf16, i, err)
+        assert torch.isfinite(p).all() and err <= tol, (i, err)

@@ -495,6 +495,41 @@ CALL_KIND = "sparse"
 USE_IGEMM_V2 = True
 
 
+def census_meta(n_in, n_out, cin, cout, kvol, nbr, act_bytes=2, w_bytes=None, v2=True, split=False):
+    """The census entry of one convolution launch: its valid rulebook pairs P (counted from `nbr`: a table, a RevNbr - reversing the
+    offsets does not change the count - or None for a plain row product, P = n_out; one host sync) and its algorithmic bytes
+    N_in*Cin*s + N_out*Cout*s + 8*P + K*Cin*Cout*w, s / w = bytes per activation / weight element (w_bytes=None: as the
+    activations; a weight gradient is written in f32: 4).
+    split: a split-bf16 launch (kvol = the offsets of ONE of its three products) is priced as the f32 convolution it stands for: f32
+    rows in and out, f32 weights, 2 * pairs * cin * cout flops (the kernel issues 3x)."""
+    if split:
+        act_bytes = w_bytes = 4
+    elif w_bytes is None:
+        w_bytes = act_bytes
+    tab = nbr.t if isinstance(nbr, RevNbr) else nbr
+    pairs = n_out if tab is None else int((tab[:kvol, :n_out] >= 0).sum().item())
+    meta = dict(kind=CALL_KIND, v2=v2, split=True) if split else dict(kind=CALL_KIND, v2=v2)
+    meta.update(n_in=n_in, n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
+                bytes=n_in * cin * act_bytes + n_out * cout * act_bytes + 8 * pairs + kvol * cin * cout * w_bytes, flops=2 * pairs * cin * cout)
+    return meta
+
+
+def timed_begin():
+    """Opens the timed region of one launch: exactly one TIMER.begin() (bench.py's "mark" mode indexes launches by that counter).
+    -> None when no timer is installed (nothing is recorded then; a wrapper on the step's host path skips its timed_end call
+    altogether), else what timed_end() takes."""
+    t = TIMER
+    return None if t is None else (t, t.begin())
+
+
+def timed_end(region, tag, *shape, **price):
+    """Closes the region under `tag`; shape / price: census_meta's arguments, evaluated in census mode only (the pair count reads the
+    device).  A launch that raised never gets here: no end() is recorded for it."""
+    if region is not None:
+        t, e0 = region
+        t.end(tag, e0, census_meta(*shape, **price) if (shape and t.mode == "census") else None)
+
+
 def fwd_stats_layout(n_out, cin, cout, kvol, has_nbr):
     """(partials, rows per partial) of the statistics u3d_igemm_fwd_stats_bf16 writes for this shape, None when no kernel with a
     statistics epilogue serves it.  Rows 0: one partial per wave of the direct-operand kernels, all of them count (rows_per_block = 0
@@ -518,17 +553,11 @@ def spconv_fwd_stats(inp, w_nmajor, nbr, n_out_dev, n_out, cout):
     out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
     stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=inp.device)
     ld = nbr.shape[1] if nbr is not None else 0
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_igemm_fwd_stats_bf16(_ptr(inp), _ptr(w_nmajor), _ptr(nbr), ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
                                           _ptr(stats), _stream()), "igemm_fwd_stats_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
-            meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                        bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
-        t.end("spconv_fwd", e0, meta)
+    if region is not None:      # (the shape facts are not even evaluated without a timer)
+        timed_end(region, "spconv_fwd", inp.shape[0], n_out, cin, cout, kvol, nbr)
     return out, stats, tr
 
 
@@ -557,21 +586,14 @@ def spconv_dgrad_bnstats(dout, w_nmajor, nbr, n_dev, n, cout, addend, epi):
     out = torch.empty((n, cout), dtype=dout.dtype, device=dout.device)
     stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=dout.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     rc = lib().u3d_igemm_dgrad_bnstats_bf16(_ptr(dout), _ptr(w_nmajor), nbr_p, ld, _ptr(addend), _ptr(out), _ptr(n_dev), n, cin, cout, kvol,
                                             C.byref(epi), _ptr(stats), _stream())
     if rc == -2:
         return None
     _check(rc, "igemm_dgrad_bnstats_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            tb = nbr.t.flip(0) if isinstance(nbr, RevNbr) else nbr
-            pairs = int((tb[:, :n] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, n_in=dout.shape[0], n_out=n, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                        bytes=dout.shape[0] * cin * 2 + n * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
-        t.end("spconv_dgrad", e0, meta)
+    if region is not None:
+        timed_end(region, "spconv_dgrad", dout.shape[0], n, cin, cout, kvol, nbr)
     return out, stats, tr
 
 
@@ -616,18 +638,11 @@ def subm_halo_wgrad(x, dy, halo, out=None, max_slots=0):
         else torch.empty((27, 64, 64), dtype=torch.float32, device=x.device)
     wsb = int(lib().u3d_subm_halo_wgrad64_workspace())
     ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_subm_halo_wgrad64_bf16(_ptr(x), _ptr(dy), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt), _ptr(halo.n_dev),
                                             halo.n_cap, _ptr(dw), _ptr(ws), wsb, int(max_slots), _stream()), "subm_halo_wgrad64_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            n = halo.n_cap
-            pairs = int((halo.nbr[:, :n] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, n_in=n, n_out=n, cin=64, cout=64, kvol=27, pairs=pairs,
-                        bytes=n * 64 * 2 * 2 + 8 * pairs + 27 * 64 * 64 * 4, flops=2 * pairs * 64 * 64)
-        t.end("spconv_wgrad", e0, meta)
+    if region is not None:
+        timed_end(region, "spconv_wgrad", halo.n_cap, halo.n_cap, 64, 64, 27, halo.nbr, w_bytes=4)
     return dw
 
 
@@ -670,8 +685,7 @@ def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=Fals
     assert c == 64 or bn_epi is None, "the BatchNorm-backward epilogue exists on the 64-channel kernel only"
     out = torch.empty_like(inp)
     stats = torch.empty((halo.tiles, 2, c), dtype=torch.float64, device=inp.device) if want_stats else None
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     if c == 64:
         _check(lib().u3d_subm_halo_conv64_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
@@ -681,14 +695,8 @@ def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=Fals
         _check(lib().u3d_subm_halo_conv128_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                 _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
                                                 int(max_slots), halo.kvol, _stream()), "subm_halo_conv128_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            n = halo.n_cap
-            pairs = int((halo.nbr[:, :n] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, n_in=n, n_out=n, cin=c, cout=c, kvol=halo.kvol, pairs=pairs,
-                        bytes=n * c * 2 * 2 + 8 * pairs + halo.kvol * c * c * 2, flops=2 * pairs * c * c)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, halo.n_cap, halo.n_cap, c, c, halo.kvol, halo.nbr)
     return (out, stats, SubmHalo.TILE) if want_stats else out
 
 
@@ -705,8 +713,7 @@ def subm_halo_conv_affine(inp, w_packed, halo, shift, relu, addend=None, max_slo
     if out is None:
         out = torch.empty_like(inp)
     assert out.shape == inp.shape and out.dtype == torch.bfloat16
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     if c == 64:
         _check(lib().u3d_subm_halo_conv64_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                       _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
@@ -715,14 +722,8 @@ def subm_halo_conv_affine(inp, w_packed, halo, shift, relu, addend=None, max_slo
         _check(lib().u3d_subm_halo_conv128_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                        _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
                                                        int(max_slots), halo.kvol, _stream()), "subm_halo_conv128_affine_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            n = halo.n_cap
-            pairs = int((halo.nbr[:, :n] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, n_in=n, n_out=n, cin=c, cout=c, kvol=halo.kvol, pairs=pairs,
-                        bytes=n * c * 2 * 2 + 8 * pairs + halo.kvol * c * c * 2, flops=2 * pairs * c * c)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, halo.n_cap, halo.n_cap, c, c, halo.kvol, halo.nbr)
     return out
 
 
@@ -765,10 +766,7 @@ def spconv_fwd(inp, w, nbr, n_out_dev, n_out, cout, transpose_w=False, tag=None,
     cin = inp.shape[1]
     out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
-    if isinstance(nbr, RevNbr):
-        nbr = nbr.t.flip(0) if (TIMER is not None and TIMER.mode == "census") else None      # only the census counts pairs from it
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     rc = -2
     if addend is not None and inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and ld != 0 and addend.dtype == torch.bfloat16 \
             and addend.shape == out.shape and addend.is_contiguous():
@@ -786,15 +784,9 @@ def spconv_fwd(inp, w, nbr, n_out_dev, n_out, cout, transpose_w=False, tag=None,
     if rc == -2:      # shape served by the first-generation kernel (small channel counts, f32)
         _check(lib().u3d_spconv_fwd(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
                                     1 if transpose_w else 0, dtype_code(inp), _stream()), "spconv_fwd")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
-            s = inp.element_size()
-            meta = dict(kind=CALL_KIND, v2=bool(rc == 0), n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                        bytes=inp.shape[0] * cin * s + n_out * cout * s + 8 * pairs + kvol * cin * cout * s,
-                        flops=2 * pairs * cin * cout)
-        t.end(tag or ("spconv_dgrad" if transpose_w else "spconv_fwd"), e0, meta)
+    if region is not None:
+        timed_end(region, tag or ("spconv_dgrad" if transpose_w else "spconv_fwd"), inp.shape[0], n_out, cin, cout, kvol, nbr,
+                  act_bytes=inp.element_size(), v2=bool(rc == 0))
     if addend is not None:
         out += addend
     return out
@@ -823,18 +815,11 @@ def spconv_fwd_split_direct(xs, w3, nbr, n_out_dev, n_out, cout, tag="spconv_fwd
     cin, n_in = xs.shape[1], xs.shape[0] // 2
     out = torch.empty((n_out, cout), dtype=torch.float32, device=xs.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_igemm_direct_split_bf16(_ptr(xs), _ptr(w3), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, n_in, cin, cout, _stream()),
            "igemm_direct_split_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            tab = nbr.t.flip(0) if isinstance(nbr, RevNbr) else nbr
-            pairs = int((tab[:, :n_out] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, split=True, n_in=n_in, n_out=n_out, cin=cin, cout=cout, kvol=27, pairs=pairs,
-                        bytes=n_in * cin * 4 + n_out * cout * 4 + 8 * pairs + 27 * cin * cout * 4, flops=2 * pairs * cin * cout)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, n_in, n_out, cin, cout, 27, nbr, split=True)
     return out
 
 
@@ -1094,18 +1079,12 @@ def igemm_fwd_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, out=None
     if out is None:
         out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=inp.device)
     assert tuple(out.shape) == (n_out, cout) and out.dtype == torch.bfloat16
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_igemm_fwd_affine_bf16(_ptr(inp), _ptr(w_folded), _ptr(nbr), nbr.shape[1] if nbr is not None else 0, _ptr(shift),
                                            int(bool(relu)), _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol, _stream()),
            "igemm_fwd_affine_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
-            meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                        bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, inp.shape[0], n_out, cin, cout, kvol, nbr)
     return out
 
 
@@ -1122,17 +1101,11 @@ def igemm_direct_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, adden
     if out is None:
         out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=inp.device)
     assert tuple(out.shape) == (n_out, cout) and out.dtype == torch.bfloat16
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_igemm_direct_affine_bf16(_ptr(inp), _ptr(w_folded), _ptr(nbr), nbr.shape[1], _ptr(shift), int(bool(relu)), _ptr(addend),
                                               _ptr(out), _ptr(n_out_dev), n_out, cin, cout, _stream()), "igemm_direct_affine_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            pairs = int((nbr[:, :n_out] >= 0).sum().item())
-            meta = dict(kind=CALL_KIND, v2=True, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                        bytes=inp.shape[0] * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, inp.shape[0], n_out, cin, cout, kvol, nbr)
     return out
 
 
@@ -1147,20 +1120,12 @@ def spconv_fwd_split(xs, w3, nbr3, n_out_dev, n_out, cout, want_stats=False, tag
         if layout is not None and layout[1]:
             stats = torch.empty((layout[0], 2, cout), dtype=torch.float64, device=xs.device)
             tr = layout[1]
-    t = TIMER
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     assert addend is None or (addend.dtype == torch.float32 and tuple(addend.shape) == (n_out, cout))
     _check(lib().u3d_igemm_fwd_split_bf16(_ptr(xs), _ptr(w3), _ptr(nbr3), nbr3.shape[1], _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol3,
                                           _ptr(stats), _ptr(addend), _stream()), "igemm_fwd_split_bf16")
-    if t is not None:
-        meta = None
-        if t.mode == "census":
-            k = kvol3 // 3
-            pairs = int((nbr3[:k, :n_out] >= 0).sum().item())
-            # priced as the f32 convolution it stands for: f32 rows in and out, f32 weights, 2 * pairs * cin * cout flops (the kernel issues 3x)
-            meta = dict(kind=CALL_KIND, v2=True, split=True, n_in=xs.shape[0] // 2, n_out=n_out, cin=cin, cout=cout, kvol=k, pairs=pairs,
-                        bytes=(xs.shape[0] // 2) * cin * 4 + n_out * cout * 4 + 8 * pairs + k * cin * cout * 4, flops=2 * pairs * cin * cout)
-        t.end(tag, e0, meta)
+    if region is not None:
+        timed_end(region, tag, xs.shape[0] // 2, n_out, cin, cout, kvol3 // 3, nbr3, split=True)      # (the first third of nbr3 is the plain table)
     return (out, stats, tr) if want_stats else out
 
 
@@ -1184,17 +1149,10 @@ def spconv_wgrad(inp, dout, nbr, n_out_dev, kvol, out_oik=False, out=None):
     v2 = bf16 and cin % 16 == 0 and cout % 16 == 0
     assert v2 or not out_oik, "out_oik needs the bf16 implicit-GEMM weight-gradient path"
     shape = (cout, cin, kvol) if out_oik else (kvol, cin, cout)
-    t = TIMER
-    meta = None
-    if t is not None and t.mode == "census":
-        pairs = int((nbr[:, :n_out] >= 0).sum().item()) if nbr is not None else n_out
-        s = inp.element_size()
-        meta = dict(kind=CALL_KIND, v2=v2, n_in=inp.shape[0], n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                    bytes=inp.shape[0] * cin * s + n_out * cout * s + 8 * pairs + kvol * cin * cout * 4, flops=2 * pairs * cin * cout)
     # the implicit-GEMM plan decides (u3d_igemm_wgrad_plan): None = no second-generation kernel serves the shape (e.g. 32 -> 16 x 27,
     # channel counts off the 16 grid other than the 8 -> 16 input convolution) - the first-generation kernel then
     plan = igemm_wgrad_plan(n_out, cin, cout, kvol, nbr is not None, out_oik) if bf16 else None
-    e0 = t.begin() if t is not None else None
+    region = timed_begin()
     if plan is None and not v2:
         dw = spconv_wgrad_generic(inp, dout, nbr, n_out_dev, kvol)
     else:
@@ -1210,8 +1168,8 @@ def spconv_wgrad(inp, dout, nbr, n_out_dev, kvol, out_oik=False, out=None):
         else:
             gen = spconv_wgrad_generic(inp, dout, nbr, n_out_dev, kvol)
             dw.copy_(gen.permute(2, 1, 0) if out_oik else gen)
-    if t is not None:
-        t.end("spconv_wgrad", e0, meta)
+    if region is not None:
+        timed_end(region, "spconv_wgrad", inp.shape[0], n_out, cin, cout, kvol, nbr, act_bytes=inp.element_size(), w_bytes=4, v2=v2)
     return dw
 
 
@@ -2390,21 +2348,17 @@ def gtdb_crop(points, scene_off, n_live, max_rows, boxes, box_off, box_valid=Non
     total = torch.empty((1,), dtype=torch.int64, device=dev)
     geom = (_ptr(_nz(points)), points.shape[0], _ptr(scene_off), _ptr(n_live), batch, feat, tiles, _ptr(_nz(boxes)), D, _ptr(box_off),
             _ptr(box_valid), boxes.shape[1], mb)
-    t = TIMER
-    e = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_gtdb_count(*geom, _ptr(tile_ws), _stream()), "gtdb_count")
-    if t is not None:
-        t.end("gtdb_count", e)
-        e = t.begin()
+    timed_end(region, "gtdb_count")
+    region = timed_begin()
     _check(lib().u3d_gtdb_scan(_ptr(tile_ws), D, tiles, _ptr(_nz(num)), _ptr(off), _ptr(total), _stream()), "gtdb_scan")
-    if t is not None:
-        t.end("gtdb_scan", e)
+    timed_end(region, "gtdb_scan")
     n_out = int(total.item())                                  # the one host read
     out = torch.empty((n_out, feat), dtype=torch.float32, device=dev) if n_out < 2 ** 31 else None   # else: u3d_gtdb_crop refuses the total
-    e = t.begin() if t is not None else None
+    region = timed_begin()
     _check(lib().u3d_gtdb_crop(*geom, _ptr(tile_ws), _ptr(off), n_out, _ptr(_nz(out)) if out is not None else None, _stream()), "gtdb_crop")
-    if t is not None:
-        t.end("gtdb_crop", e)
+    timed_end(region, "gtdb_crop")
     return out, off, num
 
 

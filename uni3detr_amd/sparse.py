@@ -4,6 +4,7 @@ sparse-conv / BatchNorm1d / dense() kernels.  Every op calls libu3d_hip.so; noth
 Replaces spconv's SparseConvTensor / indice_key machinery used by the reference encoder
 (ref: models/pts_encoder/sparse_encoder_hd.py:106-138).
 """
+import collections
 import contextlib
 import os
 
@@ -248,7 +249,7 @@ def _split_table(geom, which, n_rows, plane):
     which: "fwd" / "bwd" / "id" (identity: a plain row product) / "wgrad" ([2K, ld] = (t, t + plane): the two products whose second
     operand is dy's hi plane).
     Cached on the geometry (static for the dense lattice; the sparse levels' geometries live for one step)."""
-    owner = geom.level if (getattr(geom, "level", None) is not None and which != "id") else geom      # SubM: one set per Level, not per conv
+    owner = geom.level if (geom.level is not None and which != "id") else geom      # SubM: one set per Level, not per conv
     cache = owner.__dict__.setdefault("_split_tables", {})
     key = (which, plane)
     if key not in cache:
@@ -273,6 +274,56 @@ def _halo_of(geom, kvol, cin, cout):
     return geom.level.halo()
 
 
+# How ONE convolution runs, decided once in its forward; the backward reads the record (ctx.route) and decides nothing again.
+# split: None / "wide" / "narrow" (_split_serves); nmajor: bf16 forward on the n-major weight shadow; halo: the level's halo tables
+# (_halo_of) or None; strided_split: the input gradient runs as per-offset products over the output rows + u3d_tap_gather_sum.
+_ConvRoute = collections.namedtuple("_ConvRoute", "split nmajor halo kvol cin cout strided_split")
+
+
+def _conv_route(feats, kio_shape, geom):
+    """feats: only its dtype / is_cuda are read (and the split scope and the module flags, as they stand at this call)."""
+    kvol, cin, cout = kio_shape[0] * kio_shape[1] * kio_shape[2], kio_shape[3], kio_shape[4]
+    bf16 = feats.dtype == torch.bfloat16
+    # n-major forward weights: the LDS-DMA kernels (channels % 64) and the direct-operand kernel of the narrow 27-offset levels
+    # (igemm_direct.hip stages [K][Cout][Cin] rows as they are; the k-major layout costs it a transposing prologue)
+    nmajor = NMAJOR_FWD and bf16 and ((cin % 64 == 0 and cout % 64 == 0) or nv.direct_serves(cin, cout, kvol))
+    split = _split_serves(feats, cin, cout, kvol)
+    if split == "narrow" and geom.nbr_fwd is None:
+        split = None
+    halo = _halo_of(geom, kvol, cin, cout) if (nmajor and not split) else None
+    # stride 4: 15/16 of the output-stationary input gradient's MFMAs hit zero rows
+    strided_split = bool(STRIDED_DGRAD_SPLIT and geom.strided and kvol > 1 and (bf16 or split == "wide") and cout % 64 == 0
+                         and (kvol * cin) % 64 == 0
+                         and geom.n_out * (STRIDED_SPLIT_SPARSE_RATIO if geom.kind == "sparse" else STRIDED_SPLIT_MIN_RATIO) <= geom.n_in)
+    return _ConvRoute(split, nmajor, halo, kvol, cin, cout, strided_split)
+
+
+def _pending_addend(ctx):
+    """What the tokens hold for this conv's input gradient, as the ONE tensor a kernel epilogue can take: ResidualToken.dres,
+    FanoutToken.acc, their sum (formed first), or None.  The tokens keep their parts until _finish_din."""
+    tok, fan = ctx.res_token, ctx.fan_token
+    dres = tok.dres if tok is not None else None
+    facc = fan.acc if fan is not None else None          # partial sum of the branches that ran before this one
+    if dres is not None and facc is not None:
+        return dres + facc
+    return facc if dres is None else dres
+
+
+def _finish_din(ctx, din, taken):
+    """-> what the conv returns to autograd for its input.  taken: the launch that produced din already added _pending_addend(ctx);
+    else the parts are added here (fan.acc, then tok.dres).  din None (no input gradient wanted): the residual token is cleared all the
+    same."""
+    tok, fan = ctx.res_token, ctx.fan_token
+    if din is not None and not taken:
+        if fan is not None and fan.acc is not None:
+            din += fan.acc
+        if tok is not None and tok.dres is not None:
+            din = din + tok.dres
+    if tok is not None:
+        tok.dres = None
+    return fan.step(din) if (fan is not None and din is not None) else din
+
+
 class _SparseConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, geom, layout, want_stats=False, res_token=None, fan_token=None, bn_in=None):
@@ -280,23 +331,15 @@ class _SparseConv(torch.autograd.Function):
         # want_stats: also return the per-row-tile BatchNorm statistics of the output (empty tensor when the kernel serving this
         # shape does not produce them) - second, non-differentiable output
         ctx.set_materialize_grads(False)        # else autograd zero-fills a gradient for the statistics output on every backward
-        bf16 = feats.dtype == torch.bfloat16
         kio_shape = weight.shape if layout == "dhwio" else tuple(weight.shape[i] for i in (2, 3, 4, 1, 0))
-        cin, cout = kio_shape[3], kio_shape[4]
-        if feats.shape[1] != cin:               # the kernels take the channel counts from the weight: a mismatch would read out of bounds
-            raise ValueError(f"sparse conv: input has {feats.shape[1]} channels, weight expects {cin}")
-        # n-major forward weights: the LDS-DMA kernels (channels % 64) and the direct-operand kernel of the narrow 27-offset levels
-        # (igemm_direct.hip stages [K][Cout][Cin] rows as they are; the k-major layout costs it a transposing prologue)
-        kv = kio_shape[0] * kio_shape[1] * kio_shape[2]
-        nmajor = NMAJOR_FWD and bf16 and ((cin % 64 == 0 and cout % 64 == 0) or nv.direct_serves(cin, cout, kv))
-        split = _split_serves(feats, cin, cout, kv)
-        if split == "narrow" and geom.nbr_fwd is None:
-            split = None
-        kio, koi = (None, None) if split else conv_weights(weight, layout, feats.dtype, want_koi=nmajor)
+        if feats.shape[1] != kio_shape[3]:      # the kernels take the channel counts from the weight: a mismatch would read out of bounds
+            raise ValueError(f"sparse conv: input has {feats.shape[1]} channels, weight expects {kio_shape[3]}")
+        r = ctx.route = _conv_route(feats, kio_shape, geom)
         ctx.geom, ctx.layout = geom, layout
         ctx.res_token = res_token
         ctx.fan_token = fan_token if (fan_token is not None and feats.requires_grad) else None
-        ctx.bn_in = bn_in if (BN_GRAD_FUSION and bn_in is not None and bn_in.epi is not None and bf16 and fan_token is None) else None
+        ctx.bn_in = bn_in if (BN_GRAD_FUSION and bn_in is not None and bn_in.epi is not None and feats.dtype == torch.bfloat16
+                              and fan_token is None) else None
         # TrainStep: this parameter's slice of the flat gradient buffer - written in place by the backward ONLY if this is the
         # weight's single use in the step (a weight used twice gets two gradients that autograd must add: it may not alias them)
         _CONV_USES[id(weight)] = _CONV_USES.get(id(weight), 0) + 1
@@ -304,227 +347,160 @@ class _SparseConv(torch.autograd.Function):
         ctx.grad_view = getattr(weight, "_u3d_grad_view", None)
         ctx.kio_shape, ctx.wdtype = kio_shape, weight.dtype
         nv.CALL_KIND = geom.kind
-        ctx.split = split
-        if ctx.split:
-            n_in = feats.shape[0]
+        out_args = (geom.n_out_dev, geom.n_out, r.cout)
+        if r.split:
             xs = _planes_of(feats, geom.n_in_dev)                                        # bf16 [2 * n_in, cin]: hi | lo planes
-            ctx.save_for_backward(xs, weight)                                            # the weight gradient reads the planes
-            ctx.halo = False
+            saved = (xs, weight)                                                         # the weight gradient reads the planes
             ctx.split3 = nv.SPLIT3_ACTIVE                                                # the backward runs outside the scope: same set
             w3 = nv.split3_weights(weight, layout, nmajor=True)                          # [3K, cout, cin], straight from the parameter
-            if split == "narrow":
-                y = nv.spconv_fwd_split_direct(xs, w3, geom.nbr_fwd, geom.n_out_dev, geom.n_out, cout)
-                res = (y, None, 0)
+            if r.split == "narrow":
+                res = nv.spconv_fwd_split_direct(xs, w3, geom.nbr_fwd, *out_args)
             else:
-                t3 = _split_table(geom, "fwd", geom.n_out, n_in)
-                res = nv.spconv_fwd_split(xs, w3, t3, geom.n_out_dev, geom.n_out, cout, want_stats=want_stats)
-                if not want_stats:
-                    return res
-            if not want_stats:
-                return res[0]
-            y, stats, tr = res
-            if stats is None:
-                stats = torch.empty(0, dtype=torch.float64, device=feats.device)
+                res = nv.spconv_fwd_split(xs, w3, _split_table(geom, "fwd", geom.n_out, feats.shape[0]), *out_args, want_stats=want_stats)
+        else:
+            kio, koi = conv_weights(weight, layout, feats.dtype, want_koi=r.nmajor)
+            saved = (feats, kio)
+            nbr = geom.nbr_fwd if r.kvol > 1 else None
+            if r.halo is not None:
+                pk_fwd, ctx.pk_bwd = halo_packs(weight, kio, koi)
+                res = nv.subm_halo_conv(feats, pk_fwd, r.halo, want_stats=want_stats)
             else:
-                stats._u3d_tile_rows = tr
-            ctx.mark_non_differentiable(stats)
-            return y, stats
-        ctx.halo = False
-        ctx.save_for_backward(feats, kio)
-        nbr = geom.nbr_fwd if kio.shape[0] > 1 else None
-        ctx.halo_tab = _halo_of(geom, kv, cin, cout) if nmajor else None
-        ctx.halo = ctx.halo_tab is not None
-        if ctx.halo:
-            pk_fwd, ctx.pk_bwd = halo_packs(weight, kio, koi)
-            if want_stats:
-                y, stats, tr = nv.subm_halo_conv(feats, pk_fwd, ctx.halo_tab, want_stats=True)
-                stats._u3d_tile_rows = tr
-                ctx.mark_non_differentiable(stats)
-                return y, stats
-            return nv.subm_halo_conv(feats, pk_fwd, ctx.halo_tab)
-        if want_stats:
-            res = nv.spconv_fwd_stats(feats, koi, nbr, geom.n_out_dev, geom.n_out, cout) if nmajor else None
-            if res is not None:
-                y, stats, tr = res
-                stats._u3d_tile_rows = tr
-            else:
-                y = (nv.spconv_fwd(feats, koi, nbr, geom.n_out_dev, geom.n_out, cout, transpose_w=True, tag="spconv_fwd") if nmajor
-                     else nv.spconv_fwd(feats, kio, nbr, geom.n_out_dev, geom.n_out, cout))
-                stats = torch.empty(0, dtype=torch.float64, device=feats.device)
-            ctx.mark_non_differentiable(stats)
-            return y, stats
-        if nmajor:      # forward on the LDS-DMA kernel (n-major weight shadow)
-            return nv.spconv_fwd(feats, koi, nbr, geom.n_out_dev, geom.n_out, cout, transpose_w=True, tag="spconv_fwd")
-        return nv.spconv_fwd(feats, kio, nbr, geom.n_out_dev, geom.n_out, cout)
+                res = nv.spconv_fwd_stats(feats, koi, nbr, *out_args) if (want_stats and r.nmajor) else None
+                if res is None and r.nmajor:      # (no statistics epilogue for the shape) the LDS-DMA / direct-operand kernels on the n-major weight shadow
+                    res = nv.spconv_fwd(feats, koi, nbr, *out_args, transpose_w=True, tag="spconv_fwd")
+                elif res is None:
+                    res = nv.spconv_fwd(feats, kio, nbr, *out_args)
+        # a kernel with a statistics epilogue, asked for them: (y, stats or None, rows per tile); every other launch: y
+        y, stats, tr = res if isinstance(res, tuple) else (res, None, 0)
+        ctx.save_for_backward(*saved)
+        if not want_stats:
+            return y
+        if stats is None:
+            stats = torch.empty(0, dtype=torch.float64, device=feats.device)
+        else:
+            stats._u3d_tile_rows = tr
+        ctx.mark_non_differentiable(stats)
+        return y, stats
 
     @staticmethod
     def backward(ctx, dout, _dstats=None):
-        feats, wc = ctx.saved_tensors
-        g = ctx.geom
+        feats, wc = ctx.saved_tensors           # (a split route: the input's bf16 planes and the parameter)
         if dout is None:
             return None, None, None, None, None, None, None, None
+        r, g = ctx.route, ctx.geom
         dout = dout.contiguous()
-        kvol = wc.shape[0]
-        din = dw = None
         nv.CALL_KIND = g.kind
-        if ctx.split:
-            return _SparseConv._split_backward(ctx, feats, wc, dout)
-
-        def weight_grad():
-            nbr = g.nbr_fwd if kvol > 1 else None
-            cin_w, cout_w = wc.shape[1], wc.shape[2]
-            v2 = feats.dtype == torch.bfloat16 and nv.USE_IGEMM_V2 and cin_w % 16 == 0 and cout_w % 16 == 0 and ctx.wdtype == torch.float32
-            # the reduction stage can write the parameter's own layout straight into its slice of the flat gradient buffer (out=):
-            # autograd keeps that view as .grad and the step's packing copy has nothing to move for this parameter
-            gv = ctx.grad_view if (v2 and ctx.grad_view is not None and ctx.grad_view.is_contiguous()
-                                   and ctx.grad_view.dtype == torch.float32 and _CONV_USES.get(ctx.weight_id, 0) == 1) else None
-            if ctx.layout == "oidhw" and v2:
-                # nn.Conv3d's own [Cout,Cin,kD,kH,kW] layout: autograd keeps the tensor as the gradient
-                ks = ctx.kio_shape
-                dw = nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol, out_oik=True, out=gv).view(ks[4], ks[3], ks[0], ks[1], ks[2])
-            elif ctx.layout == "dhwio" and v2 and ctx.halo and HALO_WGRAD and cin_w == 64:
-                dw = nv.subm_halo_wgrad(feats, dout, ctx.halo_tab, out=gv).view(ctx.kio_shape)
-            elif ctx.layout == "dhwio" and v2:
-                dw = nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol, out=gv).view(ctx.kio_shape)
-            else:
-                dw = nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol).reshape(ctx.kio_shape).to(ctx.wdtype)
-                if ctx.layout == "oidhw":
-                    dw = dw.permute(4, 3, 0, 1, 2)
-            return dw
-
-        if ctx.needs_input_grad[1]:
-            dw = weight_grad()
-        if ctx.needs_input_grad[0]:
-            nbr = g.nbr_bwd if kvol > 1 else None
-            cin, cout = wc.shape[1], wc.shape[2]
-            fan = ctx.fan_token
-            facc = fan.acc if fan is not None else None          # partial sum of the branches that ran before this one
-            if (STRIDED_DGRAD_SPLIT and g.strided and kvol > 1 and dout.dtype == torch.bfloat16 and cout % 64 == 0
-                    and (kvol * cin) % 64 == 0
-                    and g.n_out * (STRIDED_SPLIT_SPARSE_RATIO if g.kind == "sparse" else STRIDED_SPLIT_MIN_RATIO) <= g.n_in):      # stride 4: 15/16 of the direct dgrad's MFMAs hit zero rows
-                prod = nv.linear_bf16(dout, wc.view(kvol * cin, cout), None, False)      # [n_out, K*Cin]
-                fa = facc if (facc is not None and facc.dtype == prod.dtype and facc.is_contiguous() and facc.shape == (g.n_in, cin)) else None
-                din = nv.tap_gather_sum(prod, nbr, g.n_in_dev, g.n_in, cin, kvol, addend=fa)      # the other branches' sum rides the gather
-                if facc is not None and fa is None:
-                    din += facc
-            else:
-                tok = ctx.res_token
-                add = tok.dres if tok is not None else None
-                if tok is not None:
-                    tok.dres = None
-                if add is not None and facc is not None:
-                    add = add + facc
-                elif facc is not None:
-                    add = facc
-                bt = ctx.bn_in
-                if bt is not None and (bt.c != cin or (add is not None and not (add.dtype == torch.bfloat16 and add.is_contiguous()))):
-                    bt = None
-                if ctx.halo and cin != 64:
-                    bt = None                    # (the 128-channel halo kernel has no BatchNorm-backward epilogue)
-                if ctx.halo:
-                    pk = ctx.pk_bwd if ctx.pk_bwd is not None else nv.subm_halo_wpack(wc)
-                    if bt is not None:
-                        din, st, tr = nv.subm_halo_conv(dout, pk, ctx.halo_tab, krev=True, addend=add, want_stats=True, tag="spconv_dgrad",
-                                                        bn_epi=bt.epi)
-                        bt.partial = (st, tr)
-                    else:
-                        din = nv.subm_halo_conv(dout, pk, ctx.halo_tab, krev=True, addend=add, tag="spconv_dgrad")
-                else:
-                    r = nv.spconv_dgrad_bnstats(dout, wc, nbr, g.n_in_dev, g.n_in, cin, add, bt.epi) if (bt is not None and kvol > 1) else None
-                    if r is not None:
-                        din, bt.partial = r[0], (r[1], r[2])
-                    else:
-                        din = nv.spconv_fwd(dout, wc, nbr, g.n_in_dev, g.n_in, cin, transpose_w=True, addend=add)
-            if fan is not None:
-                din = fan.step(din)
-        elif ctx.res_token is not None:
-            ctx.res_token.dres = None
-        return din, dw, None, None, None, None, None, None
-
-
-def _split_backward_impl(ctx, xs, wc, dout):
-    """Backward of a split-bf16 conv: dy is split into planes once; dx = three products as in the forward (transposed tables /
-    weights); dW = x^T dy ~ xh^T dyh + xl^T dyh + xh^T dyl: two launches of the bf16 weight-gradient kernel (offsets doubled for the
-    two products against dy's hi plane), summed in f32."""
-    g = ctx.geom
-    ks = ctx.kio_shape
-    kvol, cin, cout = ks[0] * ks[1] * ks[2], ks[3], ks[4]
-    n_in, n_out = xs.shape[0] // 2, dout.shape[0]
-    dys = _bwd_planes_of(dout, g.n_out_dev)                                              # bf16 [2 * n_out, cout]
-    din = dw = None
-    if ctx.split == "narrow":
-        if ctx.needs_input_grad[1]:
-            # three launches of the narrow weight-gradient kernels on plane views (the table indexes rows of a plane): no doubled table
-            xh, xl, dyh, dyl = xs[:n_in], xs[n_in:], dys[:n_out], dys[n_out:]
-            dwk = nv.sum3(nv.spconv_wgrad(xh, dyh, g.nbr_fwd, g.n_out_dev, kvol), nv.spconv_wgrad(xl, dyh, g.nbr_fwd, g.n_out_dev, kvol),
-                          nv.spconv_wgrad(xh, dyl, g.nbr_fwd, g.n_out_dev, kvol)).reshape(ctx.kio_shape).to(ctx.wdtype)
-            dw = dwk.permute(4, 3, 0, 1, 2) if ctx.layout == "oidhw" else dwk
-        if ctx.needs_input_grad[0]:
-            din = nv.spconv_fwd_split_direct(dys, nv.split3_weights(wc, ctx.layout, nmajor=False, cache=getattr(ctx, "split3", None)), g.nbr_bwd, g.n_in_dev, g.n_in, cin,
-                                             tag="spconv_dgrad")
-            fan, tok = ctx.fan_token, ctx.res_token
-            if fan is not None:
-                if fan.acc is not None:
-                    din += fan.acc
-                din = fan.step(din)
-            if tok is not None and tok.dres is not None:
-                din = din + tok.dres
-                tok.dres = None
-        elif ctx.res_token is not None:
-            ctx.res_token.dres = None
-        return din, dw, None, None, None, None, None, None
-    if ctx.needs_input_grad[1]:
-        ta = _split_table(g, "wgrad", n_out, n_in)                                         # [2K, ld]: (nbr, nbr + n_in)
-        tb = ta[:kvol]
-        a = nv.spconv_wgrad(xs, dys[:n_out], ta, g.n_out_dev, 2 * kvol)                    # [2K, cin, cout]: xh^T dyh | xl^T dyh
-        b = nv.spconv_wgrad(xs, dys[n_out:], tb, g.n_out_dev, kvol)                        # [K, cin, cout]: xh^T dyl
-        dwk = nv.sum3(a[:kvol], a[kvol:], b).reshape(ctx.kio_shape).to(ctx.wdtype)
-        dw = dwk.permute(4, 3, 0, 1, 2) if ctx.layout == "oidhw" else dwk
-    if ctx.needs_input_grad[0]:
-        if (STRIDED_DGRAD_SPLIT and g.strided and kvol > 1 and (kvol * cin) % 64 == 0
-                and n_out * (STRIDED_SPLIT_SPARSE_RATIO if g.kind == "sparse" else STRIDED_SPLIT_MIN_RATIO) <= g.n_in):
-            # strided conv: per-offset products over the (few) OUTPUT rows - one split product with the identity table, [n_out, K * Cin]
-            # f32 - then the gather over the offsets that reach each input row (as the bf16 path, u3d_tap_gather_sum; the
-            # output-stationary form runs all K x 3 products for every input row, 15/16 of them on absent neighbours at stride 4)
-            tid = _split_table(g, "id", n_out, n_out)
-            wt3 = nv.split3_weights(wc, ctx.layout, nmajor=False, cache=getattr(ctx, "split3", None)).view(3, kvol * cin, cout)      # [K, Cin, Cout] as ONE [K * Cin, Cout] matrix
-            prod = nv.spconv_fwd_split(dys, wt3, tid, g.n_out_dev, n_out, kvol * cin, tag="spconv_dgrad")
-            din = nv.tap_gather_sum(prod, g.nbr_bwd, g.n_in_dev, g.n_in, cin, kvol)
-            fused_add = False
+        want_din, want_dw = ctx.needs_input_grad[:2]
+        din, dw, taken = None, None, False
+        if r.split:
+            dys = _bwd_planes_of(dout, g.n_out_dev)                                      # bf16 [2 * n_out, cout]: dy is split into planes once
+            if want_dw:
+                dw = _split_weight_grad(ctx, r, feats, dys)
+            if want_din:
+                din, taken = _split_input_grad(ctx, r, wc, dys)
         else:
-            # the residual branch's / the other fan-out branches' gradient rides the launch's epilogue (f32 addend), as in bf16 mode
-            fan, tok = ctx.fan_token, ctx.res_token
-            add = tok.dres if (tok is not None and tok.dres is not None) else None
-            facc = fan.acc if fan is not None else None
-            if add is not None and facc is not None:
-                add = add + facc
-            elif facc is not None:
-                add = facc
-            fused_add = SPLIT_FUSED_ADD and (add is None or (add.dtype == torch.float32 and add.is_contiguous() and tuple(add.shape) == (g.n_in, cin)))
-            t3 = _split_table(g, "bwd", g.n_in, n_out)
-            din = nv.spconv_fwd_split(dys, nv.split3_weights(wc, ctx.layout, nmajor=False, cache=getattr(ctx, "split3", None)), t3, g.n_in_dev, g.n_in, cin, tag="spconv_dgrad",
-                                      addend=add if fused_add else None)
+            if want_dw:
+                dw = _weight_grad(ctx, r, feats, dout)
+            if want_din:
+                din, taken = _input_grad(ctx, r, wc, dout)
+        return _finish_din(ctx, din, taken), dw, None, None, None, None, None, None
+
+
+def _weight_grad(ctx, r, feats, dout):
+    g, kvol = ctx.geom, r.kvol
+    nbr = g.nbr_fwd if kvol > 1 else None
+    v2 = feats.dtype == torch.bfloat16 and nv.USE_IGEMM_V2 and r.cin % 16 == 0 and r.cout % 16 == 0 and ctx.wdtype == torch.float32
+    # the reduction stage can write the parameter's own layout straight into its slice of the flat gradient buffer (out=):
+    # autograd keeps that view as .grad and the step's packing copy has nothing to move for this parameter
+    gv = ctx.grad_view if (v2 and ctx.grad_view is not None and ctx.grad_view.is_contiguous()
+                           and ctx.grad_view.dtype == torch.float32 and _CONV_USES.get(ctx.weight_id, 0) == 1) else None
+    if ctx.layout == "oidhw" and v2:
+        # nn.Conv3d's own [Cout,Cin,kD,kH,kW] layout: autograd keeps the tensor as the gradient
+        ks = ctx.kio_shape
+        return nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol, out_oik=True, out=gv).view(ks[4], ks[3], ks[0], ks[1], ks[2])
+    if ctx.layout == "dhwio" and v2 and r.halo is not None and HALO_WGRAD and r.cin == 64:
+        return nv.subm_halo_wgrad(feats, dout, r.halo, out=gv).view(ctx.kio_shape)
+    if ctx.layout == "dhwio" and v2:
+        return nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol, out=gv).view(ctx.kio_shape)
+    dw = nv.spconv_wgrad(feats, dout, nbr, g.n_out_dev, kvol).reshape(ctx.kio_shape).to(ctx.wdtype)
+    return dw.permute(4, 3, 0, 1, 2) if ctx.layout == "oidhw" else dw
+
+
+def _input_grad(ctx, r, wc, dout):
+    """bf16 / exact f32 input gradient -> (din, whether the launch took _pending_addend(ctx))."""
+    g, kvol, cin, cout = ctx.geom, r.kvol, r.cin, r.cout
+    nbr = g.nbr_bwd if kvol > 1 else None
+    add = _pending_addend(ctx)
+    fits = add is not None and add.dtype == dout.dtype and add.is_contiguous() and tuple(add.shape) == (g.n_in, cin)
+    if r.strided_split:
+        prod = nv.linear_bf16(dout, wc.view(kvol * cin, cout), None, False)      # [n_out, K*Cin]
         fan = ctx.fan_token
-        tok = ctx.res_token
-        if fused_add:
-            if tok is not None:
-                tok.dres = None
-            if fan is not None:
-                din = fan.step(din)
-        else:
-            if fan is not None:
-                if fan.acc is not None:
-                    din += fan.acc
-                din = fan.step(din)
-            if tok is not None and tok.dres is not None:
-                din = din + tok.dres
-                tok.dres = None
-    elif ctx.res_token is not None:
-        ctx.res_token.dres = None
-    return din, dw, None, None, None, None, None, None
+        if not (fits and fan is not None and add is fan.acc):                    # only the other branches' sum rides the gather
+            add = None
+        return nv.tap_gather_sum(prod, nbr, g.n_in_dev, g.n_in, cin, kvol, addend=add), add is not None
+    bt = ctx.bn_in
+    if bt is not None and (bt.c != cin or not (add is None or fits)):
+        bt = None
+    if r.halo is not None:
+        if cin != 64:
+            bt = None                        # (the 128-channel halo kernel has no BatchNorm-backward epilogue)
+        if not fits:
+            add = None
+        pk = ctx.pk_bwd if ctx.pk_bwd is not None else nv.subm_halo_wpack(wc)
+        din = nv.subm_halo_conv(dout, pk, r.halo, krev=True, addend=add, want_stats=bt is not None, tag="spconv_dgrad",
+                                bn_epi=None if bt is None else bt.epi)
+        if bt is not None:
+            din, st, tr = din
+            bt.partial = (st, tr)
+        return din, add is not None
+    res = nv.spconv_dgrad_bnstats(dout, wc, nbr, g.n_in_dev, g.n_in, cin, add, bt.epi) if (bt is not None and kvol > 1) else None
+    if res is not None:
+        bt.partial = (res[1], res[2])
+        return res[0], True
+    # (an addend its epilogue cannot take - another shape or dtype, the first-generation kernel - nv.spconv_fwd adds after the launch)
+    return nv.spconv_fwd(dout, wc, nbr, g.n_in_dev, g.n_in, cin, transpose_w=True, addend=add), True
 
 
-_SparseConv._split_backward = staticmethod(_split_backward_impl)
+def _split_weight_grad(ctx, r, xs, dys):
+    """dW = x^T dy ~ xh^T dyh + xl^T dyh + xh^T dyl of a split-bf16 conv, summed in f32."""
+    g, kvol = ctx.geom, r.kvol
+    n_in, n_out = xs.shape[0] // 2, dys.shape[0] // 2
+    if r.split == "narrow":
+        # three launches of the narrow weight-gradient kernels on plane views (the table indexes rows of a plane): no doubled table
+        xh, xl, dyh, dyl = xs[:n_in], xs[n_in:], dys[:n_out], dys[n_out:]
+        parts = [nv.spconv_wgrad(x, dy, g.nbr_fwd, g.n_out_dev, kvol) for x, dy in ((xh, dyh), (xl, dyh), (xh, dyl))]
+    else:
+        # two launches of the bf16 weight-gradient kernel (offsets doubled for the two products against dy's hi plane)
+        ta = _split_table(g, "wgrad", n_out, n_in)                                         # [2K, ld]: (nbr, nbr + n_in)
+        a = nv.spconv_wgrad(xs, dys[:n_out], ta, g.n_out_dev, 2 * kvol)                    # [2K, cin, cout]: xh^T dyh | xl^T dyh
+        b = nv.spconv_wgrad(xs, dys[n_out:], ta[:kvol], g.n_out_dev, kvol)                 # [K, cin, cout]: xh^T dyl
+        parts = [a[:kvol], a[kvol:], b]
+    dwk = nv.sum3(*parts).reshape(ctx.kio_shape).to(ctx.wdtype)
+    return dwk.permute(4, 3, 0, 1, 2) if ctx.layout == "oidhw" else dwk
+
+
+def _split_input_grad(ctx, r, wc, dys):
+    """dx of a split-bf16 conv: three products as in the forward (transposed tables / weights) -> (din, whether the launch took
+    _pending_addend(ctx))."""
+    g, kvol, cin, cout = ctx.geom, r.kvol, r.cin, r.cout
+    n_out = dys.shape[0] // 2
+    w3 = nv.split3_weights(wc, ctx.layout, nmajor=False, cache=ctx.split3)
+    if r.split == "narrow":
+        return nv.spconv_fwd_split_direct(dys, w3, g.nbr_bwd, g.n_in_dev, g.n_in, cin, tag="spconv_dgrad"), False
+    if r.strided_split:
+        # strided conv: per-offset products over the (few) OUTPUT rows - one split product with the identity table, [n_out, K * Cin]
+        # f32 - then the gather over the offsets that reach each input row (as the bf16 path, u3d_tap_gather_sum; the
+        # output-stationary form runs all K x 3 products for every input row, 15/16 of them on absent neighbours at stride 4)
+        tid = _split_table(g, "id", n_out, n_out)
+        wt3 = w3.view(3, kvol * cin, cout)                                                 # [K, Cin, Cout] as ONE [K * Cin, Cout] matrix
+        prod = nv.spconv_fwd_split(dys, wt3, tid, g.n_out_dev, n_out, kvol * cin, tag="spconv_dgrad")
+        return nv.tap_gather_sum(prod, g.nbr_bwd, g.n_in_dev, g.n_in, cin, kvol), False
+    # the residual branch's / the other fan-out branches' gradient rides the launch's epilogue (f32 addend), as in bf16 mode
+    add = _pending_addend(ctx) if SPLIT_FUSED_ADD else None
+    if add is not None and not (add.dtype == torch.float32 and add.is_contiguous() and tuple(add.shape) == (g.n_in, cin)):
+        add = None
+    t3 = _split_table(g, "bwd", g.n_in, n_out)
+    return nv.spconv_fwd_split(dys, w3, t3, g.n_in_dev, g.n_in, cin, tag="spconv_dgrad", addend=add), add is not None
 
 
 def sparse_conv(feats, weight, geom, layout="dhwio", fan_token=None):
@@ -689,7 +665,7 @@ class _BNRows(torch.autograd.Function):
         else:
             sums, s32 = nv.bn_bwd_stats(dy, y, x, mean, invstd, ctx.relu, ctx.n_dev, gamma, beta, ctx.row_map, want_f32=True)
         use = sums if ctx.training else torch.zeros_like(sums)       # eval statistics are constants: dx = gamma*invstd*g
-        if getattr(ctx, "planes", False):
+        if ctx.planes:
             dx, dres, dpl = nv.bn_bwd_apply(dy, y, x, mean, invstd, gamma, use, ctx.relu, ctx.n_dev, ctx.has_res, beta, ctx.row_map, want_planes=True)
             _give_bwd_planes(dx, dpl)
         else:
