@@ -3,8 +3,6 @@ u3d_bn_fold_batched, the header / binding pair of the new entries, the launch pl
 restatement of the fold kernel's f32 arithmetic that justifies the GPU test's "at most 1 % of the elements differ" cap."""
 import copy
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import projects.mmdet3d_plugin  # noqa: F401
 from uni3detr_amd import native as nv
 from uni3detr_amd.inference import InferenceModel, classify
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("u3d_bn_fold_job_bytes", "u3d_bn_fold_job_blocks", "u3d_bn_fold_batched", "u3d_igemm_fwd_affine_bf16", "u3d_igemm_fwd_affine_plan")
 
 
@@ -35,12 +32,9 @@ def model():
 
 
 def test_new_symbols_are_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "u3d_hip.h")).read()
-    declared = set(re.findall(r"\b(u3d_[a-z0-9_]+)\s*\(", hdr))
     lib = ctypes.CDLL(nv.LIB_PATH)
     for name in NEW:
-        assert name in declared, name
-        assert name in nv.exported_symbols(), name
+        assert name in nv.exported_symbols(), name            # = declared in include/u3d_hip.h (tests/test_abi_cpu.py)
         assert hasattr(lib, name), name
     # the record the kernel reads and the one the host fills are the same bytes
     assert int(nv.lib().u3d_bn_fold_job_bytes()) == ctypes.sizeof(nv.BnFoldJob) == 104

@@ -4,8 +4,6 @@ float64 restatement of the affine epilogue of the halo and direct-operand kernel
 tests/test_bn_fold_sparse_gpu.py measures the kernels against."""
 import copy
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ from test_bn_fold_cpu import bf16_bits_from_f64, tiny_cfg
 from uni3detr_amd import native as nv
 from uni3detr_amd.inference import InferenceModel, classify
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("u3d_subm_halo_conv64_affine_bf16", "u3d_subm_halo_conv128_affine_bf16", "u3d_igemm_direct_affine_bf16")
 
 
@@ -54,11 +51,9 @@ def test_epilogue_restatement_order_and_single_rounding():
 
 
 def test_new_symbols_are_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "u3d_hip.h")).read()
-    declared = set(re.findall(r"\b(u3d_[a-z0-9_]+)\s*\(", hdr))
     lib = ctypes.CDLL(nv.LIB_PATH)
     for name in NEW:
-        assert name in declared and name in nv.exported_symbols() and hasattr(lib, name), name
+        assert name in nv.exported_symbols() and hasattr(lib, name), name     # exported_symbols() = declared in include/u3d_hip.h
     assert callable(nv.subm_halo_conv_affine) and callable(nv.igemm_direct_affine)
 
 

@@ -1,7 +1,6 @@
-"""The batched inference tail without a GPU: the two entry points declared in include/u3d_hip.h as native._SIGS binds them, and
-native.DetBatch's host-side views on hand-made CPU tensors."""
+"""The batched inference tail without a GPU: the two entry points are part of the build (their signatures are pinned in
+tests/test_abi_cpu.py), and native.DetBatch's host-side views on hand-made CPU tensors."""
 import os
-import re
 
 import torch
 
@@ -11,22 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_entry_points_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "u3d_hip.h")).read()
-    ctype = {"int32_t": nv.C.c_int32, "int64_t": nv.C.c_int64, "float": nv.C.c_float}
-    for name, restype in (("u3d_det_tail_workspace", "int64_t"), ("u3d_det_tail", "int32_t")):
-        m = re.search(restype + r"\s+" + name + r"\(([^;]*)\);", hdr)
-        assert m, name
-        params = [p.strip() for p in m.group(1).replace("\n", " ").split(",")]
-        res, args = nv._SIGS[name]
-        assert res is ctype[restype] and len(args) == len(params), (name, len(args), len(params))
-        for p, a in zip(params, args):
-            base = p.rsplit(" ", 1)[0].replace("const ", "").strip()
-            want = nv.C.c_void_p if ("*" in p or base == "u3d_stream") else ctype[base]
-            assert a is want, (name, p)
+    for name in ("u3d_det_tail_workspace", "u3d_det_tail"):
         assert name in nv.exported_symbols()
     assert os.path.exists(os.path.join(ROOT, "uni3detr_amd", "csrc", "det_tail.hip"))
-    for k in ("U3D_DET_TAIL_NONE 0", "U3D_DET_TAIL_NMS 1", "U3D_DET_TAIL_DECODE 2", f"U3D_DET_TAIL_MAX_K {nv.DET_TAIL_MAX_K}"):
-        assert re.search(r"#define\s+" + k + r"\b", hdr), k
     assert (nv.DET_TAIL_NONE, nv.DET_TAIL_NMS, nv.DET_TAIL_DECODE) == (0, 1, 2)
 
 

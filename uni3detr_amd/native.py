@@ -2,6 +2,9 @@
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw `data_ptr()`s and the
 current HIP stream.  There is NO CPU fallback: if the library is missing or a call fails, we raise.
+
+Signatures, struct layouts and constants are not restated here: abi.py reads them from the header, which therefore has to be on
+disk next to the package (include/u3d_hip.h) wherever this module is imported.
 """
 import ctypes as C
 import os
@@ -9,256 +12,56 @@ import os
 import numpy as np
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("U3D_LIB_PATH") or os.path.join(_HERE, "libu3d_hip.so")      # override: kernel experiments (tools/build_variant.sh)
 
-F32, BF16 = 0, 1
+_ABI = abi.load()
+_K = _ABI.constants
+
+
+def _struct(c_name, py_name):
+    return abi.structure(_ABI.structs[c_name], py_name)
+
+
+def _slot_names(prefix):
+    """The enumerators <prefix>* of the header in index order, without the prefix and the closing <prefix>COUNT."""
+    names = sorted((v, n[len(prefix):]) for n, v in _K.items() if n.startswith(prefix))
+    assert [v for v, _ in names] == list(range(len(names))) and names[-1][1] == "COUNT" and _K[prefix + "COUNT"] == len(names) - 1
+    return [n for _, n in names[:-1]]
+
+
+U3D_ERR_UNSUPPORTED = _K["U3D_ERR_UNSUPPORTED"]         # shape / dtype combination not compiled in: the caller takes another kernel
+F32, BF16 = _K["U3D_F32"], _K["U3D_BF16"]
 
 
 class U3DError(RuntimeError):
     pass
 
 
-class BitGridStruct(C.Structure):
-    _fields_ = [("words", C.c_void_p), ("prefix", C.c_void_p), ("batch", C.c_int32), ("dz", C.c_int32),
-                ("dy", C.c_int32), ("dx", C.c_int32), ("layout", C.c_int32), ("row_capacity", C.c_int32)]
+BitGridStruct = _struct("u3d_bitgrid", "BitGridStruct")
 
-
-DL_NLIN, DL_NLN = 22, 7
-(DL_RPH0, DL_RPH1, DL_RPH2, DL_QS0, DL_QS1, DL_QS2, DL_INQK, DL_INV, DL_OUTP, DL_OPROJ, DL_PE1, DL_FFN0, DL_FFN1, DL_REG0, DL_REG1,
- DL_REG2, DL_CLS0, DL_CLS1, DL_CLS2, DL_IOU0, DL_IOU1, DL_IOU2) = range(DL_NLIN)
-(DLN_1, DLN_2, DLN_3, DLN_PE0, DLN_PE1, DLN_C1, DLN_C2) = range(DL_NLN)
-DS_NAMES = ("SINE RPH1 RPH2 RAW QS1 QS2 QS POS QKIN QK V LSE O U1 MR QP SAMP GATED PEH0 UPE1 U2 X2C FFH U3 R1 R2 I1 I2 UC1 C1 UC2 "
-            "C2 AMASK").split()
-DG_NAMES = ("CLSO C2U C1U IOUO I2 I1 REGO R2 R1 F FFH OUT UPE1 P0 WL O2 DO DQK DV QS QS2 QS1 RAW RPH2 RPH1 LNP DU1 DPOSA "
-            "SINE").split()
-
-
-class DecLayerParams(C.Structure):
-    """u3d_declayer_params (include/u3d_hip.h)."""
-    _fields_ = [("w", C.c_void_p * DL_NLIN), ("wt", C.c_void_p * DL_NLIN), ("b", C.c_void_p * DL_NLIN),
-                ("ln_g", C.c_void_p * DL_NLN), ("ln_b", C.c_void_p * DL_NLN), ("attw_w", C.c_void_p), ("attw_b", C.c_void_p),
-                ("pe0_w", C.c_void_p), ("pe0_b", C.c_void_p), ("dim_t", C.c_void_p)]
-
-
-class DecLayerDims(C.Structure):
-    """u3d_declayer_dims."""
-    _fields_ = [(n, C.c_int32) for n in ("m", "nq", "qps", "batch", "dz", "dy", "dx", "ncls", "code", "has_qs", "need_dref", "layer")] + \
-               [("p_attn", C.c_float), ("p_drop", C.c_float), ("ln_eps", C.c_float), ("dtype", C.c_int32), ("reserved", C.c_int32)]
-
-
-class WPackDesc(C.Structure):
-    """u3d_wpack_desc."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("dst_t", C.c_void_p), ("n", C.c_int32), ("k", C.c_int32),
-                ("n_pad", C.c_int32), ("n_pad_t", C.c_int32), ("t_plain", C.c_int32), ("reserved", C.c_int32)]
-
+# DL_RPH0 .. DL_IOU2 and DL_NLIN, DL_NLN: the linears of a decoder layer (indices into DecLayerParams.w / .wt / .b); DLN_1 .. DLN_C2:
+# its LayerNorms (.ln_g / .ln_b).  The header's two enums, under their names without the U3D_ prefix.
+for _n, _v in _K.items():
+    if _n.startswith(("U3D_DL_", "U3D_DLN_")):
+        globals()[_n[4:]] = _v
+DS_NAMES = _slot_names("U3D_DS_")       # forward-save slots of the fused decoder layer: SINE, RPH1, ... AMASK
+DG_NAMES = _slot_names("U3D_DG_")       # its backward-workspace slots: CLSO, C2U, ... SINE
+DecLayerParams = _struct("u3d_declayer_params", "DecLayerParams")
+DecLayerDims = _struct("u3d_declayer_dims", "DecLayerDims")
+WPackDesc = _struct("u3d_wpack_desc", "WPackDesc")
 
 _lib = None
-_P = C.c_void_p
-_I = C.c_int32
-_L = C.c_int64
-_I3 = C.c_int32 * 3
+_I3 = C.c_int32 * 3     # the host arrays a few entry points take by pointer: constructors for the call sites
 _F3 = C.c_float * 3
 _F6 = C.c_float * 6
-
-_SIGS = {
-    # name: (restype, argtypes)
-    "u3d_version": (_I, []),
-    "u3d_strerror": (C.c_char_p, [_I]),
-    "u3d_points_augment": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P]),
-    "u3d_boxes_augment": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
-    "u3d_points_range_filter": (_I, [_P, _P, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
-    "u3d_point_sample": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "u3d_boxes_range_filter": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_float), _P, _P]),
-    "u3d_point_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "u3d_boxes_label_filter": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "u3d_batch_ingest": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "u3d_sweeps_merge_workspace": (_L, [_I]),
-    "u3d_sweeps_merge": (_I, [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _I, _P, _L, _P, _L, _P, _P]),
-    "u3d_event_create": (_I, [C.POINTER(C.c_void_p)]),
-    "u3d_event_record": (_I, [C.c_void_p, _I, _P]),
-    "u3d_event_elapsed_ms": (_I, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
-    "u3d_event_destroy": (_I, [C.c_void_p]),
-    "u3d_bitgrid_nwords": (_L, [_I, _I, _I, _I]),
-    "u3d_bitgrid_nwords_layout": (_L, [_I, _I, _I, _I, _I]),
-    "u3d_voxelize_dynamic": (_I, [_P, _P, _I, _I, _I, _F3, _F6, _P, _P]),
-    "u3d_scatter_mean": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
-    "u3d_bitgrid_mark": (_I, [C.POINTER(BitGridStruct), _P, _I, _P]),
-    "u3d_bitgrid_mark_strided": (_I, [C.POINTER(BitGridStruct), _P, _P, _I, _I3, _I3, _I3, _P]),
-    "u3d_bitgrid_scan_scratch": (_L, [_L]),
-    "u3d_bitgrid_scan": (_I, [C.POINTER(BitGridStruct), _P, _P]),
-    "u3d_bitgrid_rank": (_I, [C.POINTER(BitGridStruct), _P, _I, _P, _P]),
-    "u3d_bitgrid_coords": (_I, [C.POINTER(BitGridStruct), _P, _I, _P]),
-    "u3d_nbr_table": (_I, [C.POINTER(BitGridStruct), _P, _P, _I, _I3, _I3, _I3, _I, _P, _I, _P]),
-    "u3d_dense_nbr_table": (_I, [_I, _I3, _I3, _I3, _I3, _I3, _I, _P, _I, _P]),
-    "u3d_voxelize_hard_workspace": (_L, [_I, _I, _I]),
-    "u3d_voxelize_hard": (_I, [_P, _P, _I, _I, _I, _I, _F3, _F6, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "u3d_spconv_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "u3d_spconv_wgrad_workspace": (_L, [_I, _I, _I, _I]),
-    "u3d_spconv_wgrad": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "u3d_igemm_fwd_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "u3d_igemm_fwd_stats_layout": (_I, [_I, _I, _I, _I, _I, _P, _P]),
-    "u3d_igemm_fwd_add_bf16": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "u3d_linear_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
-    "u3d_igemm_wgrad_bf16_workspace": (_L, [_I, _I, _I, _I]),
-    "u3d_igemm_wgrad_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "u3d_igemm_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "u3d_colsum_workspace": (_L, [_I, _I]),
-    "u3d_colsum": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
-    "u3d_bn_stats_workspace": (_L, [_I, _I]),
-    "u3d_bn_stats": (_I, [_P, _P, _I, _I, _I, _P, _P, _L, _P]),
-    "u3d_bn_finalize": (_I, [_P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
-    "u3d_bn_forward_stats": (_I, [_P, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "u3d_bn_finalize_partials": (_I, [_P, _I, _I, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
-    "u3d_igemm_fwd_stats_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "u3d_igemm_fwd_split_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "u3d_split_rows_f32": (_I, [_P, _P, _I, _I, _P, _P]),
-    "u3d_split3_weights": (_I, [_P, C.c_int64, C.c_int64, C.c_int64, _I, _I, _I, _P, _P]),
-    "u3d_sum3_f32": (_I, [_P, _P, _P, _P, C.c_int64, _P]),
-    "u3d_split_rows_batch": (_I, [_P, _P]),
-    "u3d_split3_job_bytes": (C.c_int64, []),
-    "u3d_split3_job_blocks": (_I, [_I, _I, _I]),
-    "u3d_split3_weights_batch": (_I, [_P, _I, _I, _P]),
-    "u3d_bn_fold_job_bytes": (C.c_int64, []),
-    "u3d_bn_fold_job_blocks": (_I, [_I, _I, _I]),
-    "u3d_bn_fold_batched": (_I, [_P, _I, _I, _P]),
-    "u3d_igemm_fwd_affine_bf16": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
-    "u3d_igemm_fwd_affine_plan": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
-    "u3d_igemm_direct_split_bf16": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
-    "u3d_igemm_dgrad_bnstats_bf16": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "u3d_bn_bwd_finalize_partials": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
-    "u3d_subm_halo_sizes": (_I, [_I, _P, _P, _P]),
-    "u3d_subm_halo_build": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P]),
-    "u3d_subm_halo_wpack128": (_I, [_P, _P, _I, _P]),
-    "u3d_subm_halo_wpack128_batched": (_I, [_P, _P, _I, _I, _P]),
-    "u3d_subm_halo_conv128_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P]),
-    "u3d_subm_halo_wgrad64_workspace": (_L, []),
-    "u3d_subm_halo_wgrad64_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _I, _P]),
-    "u3d_subm_halo_wpack": (_I, [_P, _P, _P]),
-    "u3d_subm_halo_wpack_batched": (_I, [_P, _P, _I, _P]),
-    "u3d_subm_halo_conv64_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
-    "u3d_subm_halo_conv64_affine_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
-    "u3d_subm_halo_conv128_affine_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "u3d_igemm_direct_affine_bf16": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "u3d_bn_apply": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "u3d_bn_bwd_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
-    "u3d_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "u3d_bn_apply_planes": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
-    "u3d_bn_bwd_apply_planes": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
-    "u3d_to_dense": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P]),
-    "u3d_from_dense": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P]),
-    "u3d_fps": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P]),
-    "u3d_refine_decode_fwd": (_I, [_P, _P, _P, _I, _I, _P, C.c_float, _P, _P, _P, _P]),
-    "u3d_loss_targets": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "u3d_fps2": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P]),
-    "u3d_fps_prep": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "u3d_fps_points": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
-    "u3d_query_embed_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "u3d_query_embed_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "u3d_match_cost": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
-    "u3d_lsa": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "u3d_trilinear_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
-    "u3d_trilinear_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
-    "u3d_nms3d_workspace": (_L, [_I]),
-    "u3d_nms3d": (_I, [_P, _P, _I, C.c_float, _P, _P, _L, _P]),
-    "u3d_det_tail_workspace": (_L, [_I, _I, _I, _I, _I]),
-    "u3d_det_tail": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, C.c_float, _I, C.c_float, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "u3d_det_tail_pp_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
-    "u3d_det_tail_pp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, C.c_float, _I, C.c_float, _P, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P,
-                             _P, _L, _P]),
-    "u3d_tta_merge_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
-    "u3d_tta_merge": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, C.c_float, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
-    "u3d_iou3d_rotated_aligned": (_I, [_P, _P, _I, _P, _P]),
-    "u3d_tap_gather_sum": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "u3d_tap_gather_sum_add": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "u3d_wgrad_batched_workspace": (_L, [_I, _I, _I, _I]),
-    "u3d_wgrad_batched_bf16": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _L, _P]),
-    "u3d_skinny_wgrad_chunks": (_I, [_I]),
-    "u3d_skinny_wgrad_bf16": (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    "u3d_skinny_wgrad_batched": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "u3d_colsum_batched_workspace": (_L, [_I, _I, _I]),
-    "u3d_colsum_batched": (_I, [_P, _P, _I, _I, _I, _I, _P, _L, _P]),
-    "u3d_layernorm_blocks": (_I, [_I]),
-    "u3d_layernorm_fwd": (_I, [_P, _I, _I, _I, _P, _P, C.c_float, _I, _P, _I, _P, _P, _P]),
-    "u3d_layernorm_bwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
-    "u3d_det_loss_workspace": (_L, [_I, _I]),
-    "u3d_det_loss_fwd": (_I, [_P] * 10 + [_I] * 5 + [C.c_float] * 5 + [_P, _P, _L, _P]),
-    "u3d_det_loss_bwd": (_I, [_P] * 11 + [_I] * 5 + [C.c_float] * 5 + [_P, _P, _P, _P]),
-    "u3d_denormalize_boxes": (_I, [_P, _I, _I, _P, _P]),
-    "u3d_box_decode_fwd": (_I, [_P, _I, _P, _I, _I, _F6, C.c_float, _P, _P]),
-    "u3d_box_decode_bwd": (_I, [_P, _I, _P, _P, _I, _I, _F6, C.c_float, _P, _P, _P]),
-    "u3d_sine_embed_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "u3d_sine_embed_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "u3d_cast_bf16": (_I, [_P, _P, _L, _P]),
-    "u3d_permute_block_elems": (_I, []),
-    "u3d_permute_bf16_tiled": (_I, [_P, _P, _P, _P, _I, _I, _P]),
-    "u3d_permute_bf16_batched": (_I, [_P, _P, _P, _P, _I, _P]),
-    "u3d_adamw_workspace": (_L, [_L]),
-    "u3d_adamw_step": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _L, _P]),
-    "u3d_adamw_set_hyper": (_I, [_P] + [C.c_float] * 6 + [_P]),
-    "u3d_adamw_step_state": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P]),
-    "u3d_adamw_step_hold": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
-    "u3d_adamw_step_accum": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
-    "u3d_adamw_set_accum": (_I, [_P, C.c_int32, C.c_float, _P]),
-    "u3d_capacity_flag": (_I, [_P, _P, _I, _P, _P]),
-    "u3d_gather_rows": (_I, [_P, _P, _I, _I, _P, _P]),
-    "u3d_soft_nms": (_I, [_P, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
-    "u3d_box_merge_workspace": (_L, [_I]),
-    "u3d_box_merge": (_I, [_P, _P, _I, C.c_float, _P, _P, _P, _L, _P]),
-    "u3d_eval_iou_argmax": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "u3d_eval_segments": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
-    "u3d_eval_first_hit": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
-    "u3d_eval_tp": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
-    "u3d_eval_ap": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "u3d_kitti_convert": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
-    "u3d_kitti_compact": (_I, [_P, _P, _P, _I, _P, _P]),
-    "u3d_kitti_overlaps": (_I, [_P, _P, _P, _P, _P, _I, _L, _P, _P]),
-    "u3d_kitti_flags": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
-    "u3d_kitti_pass1": (_I, [_P, _P, _I, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
-    "u3d_kitti_thresholds": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
-    "u3d_kitti_pass2_lds": (_L, [_I, _I]),
-    "u3d_kitti_pass2": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P]),
-    "u3d_kitti_reduce": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
-    "u3d_nusc_convert": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
-    "u3d_nusc_filter": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
-    "u3d_nusc_compact": (_I, [_P, _P, _P, _I, _P, _P]),
-    "u3d_nusc_rank_keys": (_I, [_P, _I, _P, _P, _P]),
-    "u3d_nusc_match_lds": (_L, [_I]),
-    "u3d_nusc_match": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
-    "u3d_nusc_accumulate_workspace": (_L, [_I, _I]),
-    "u3d_nusc_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
-    "u3d_decoder_layer_slots": (_I, [_I, _I, _I, _P, _P]),
-    "u3d_decoder_layer_blocks": (_I, [_I]),
-    "u3d_decoder_layer_fwd": (_I, [C.POINTER(DecLayerParams), C.POINTER(DecLayerDims)] + [_P] * 11 + [_L, _P]),
-    "u3d_decoder_layer_bwd": (_I, [C.POINTER(DecLayerParams), C.POINTER(DecLayerDims)] + [_P] * 15 + [_L, _P]),
-    "u3d_mha_fwd": (_I, [_P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _P]),
-    "u3d_mha_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _P]),
-    "u3d_wpack_bf16": (_I, [_P, _I, _I, _P]),
-    "u3d_wpack": (_I, [_P, _I, _I, _I, _P]),
-    "u3d_decoder_layer_slots_dt": (_I, [_I, _I, _I, _I, _P, _P]),
-    "u3d_decoder_layer_blocks_dt": (_I, [_I, _I]),
-    "u3d_mha_fwd_dt": (_I, [_P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _I, _P]),
-    "u3d_mha_bwd_dt": (_I, [_P, _P, _P, _P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _I, _P]),
-    "u3d_dropout_mask": (_I, [_P, _I, _I, _L, C.c_float, _I, _P, _P]),
-    "u3d_scatter_rows": (_I, [_P, _P, _I, _I, _P, _P]),
-    "u3d_value_records_bytes": (_L, [_I]),
-    "u3d_value_scatter_workspace": (_L, [_I]),
-    "u3d_value_scatter": (_I, [_P, _I, _I, _P, _I, _P, _L, _P]),
-    "u3d_objaug_stats": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
-    "u3d_objaug_accept": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "u3d_points_in_boxes": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "u3d_objaug_paste": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P,
-                              _P, _P, _P, _P, _P, _P]),
-    "u3d_object_noise": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "u3d_gtdb_count": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
-    "u3d_gtdb_scan": (_I, [_P, _I, _I, _P, _P, _P, _P]),
-    "u3d_gtdb_crop": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _L, _P, _P]),
-}
 
 
 def exported_symbols():
     """Names every build of the library must export (checked by the CPU test-suite)."""
-    return sorted(_SIGS)
+    return sorted(_ABI.prototypes)
 
 
 def lib():
@@ -268,7 +71,7 @@ def lib():
             raise U3DError(f"{LIB_PATH} is missing: run `python -m uni3detr_amd.build` (hipcc, gfx950). "
                            "There is no CPU/PyTorch fallback for the HIP hot path.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in _ABI.prototypes.items():
             fn = getattr(l, name)   # AttributeError -> loud failure if a symbol is missing
             fn.restype = res
             fn.argtypes = args
@@ -561,10 +364,8 @@ def spconv_fwd_stats(inp, w_nmajor, nbr, n_out_dev, n_out, cout):
     return out, stats, tr
 
 
-class BnEpi(C.Structure):
+class BnEpi(_struct("u3d_bn_epi", "_BnEpi")):
     """u3d_bn_epi (include/u3d_hip.h): the BatchNorm whose dy an input-gradient launch writes."""
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p), ("gamma", C.c_void_p),
-                ("beta", C.c_void_p), ("relu", C.c_int32), ("reserved", C.c_int32)]
 
     @staticmethod
     def of(x, y, mean, invstd, gamma, beta, relu):
@@ -589,7 +390,7 @@ def spconv_dgrad_bnstats(dout, w_nmajor, nbr, n_dev, n, cout, addend, epi):
     region = timed_begin()
     rc = lib().u3d_igemm_dgrad_bnstats_bf16(_ptr(dout), _ptr(w_nmajor), nbr_p, ld, _ptr(addend), _ptr(out), _ptr(n_dev), n, cin, cout, kvol,
                                             C.byref(epi), _ptr(stats), _stream())
-    if rc == -2:
+    if rc == U3D_ERR_UNSUPPORTED:
         return None
     _check(rc, "igemm_dgrad_bnstats_bf16")
     if region is not None:
@@ -625,7 +426,7 @@ class SubmHalo:
         self.tile_cnt = torch.empty((t.value,), dtype=torch.int32, device=dev)
         rc = lib().u3d_subm_halo_build(_ptr(nbr_fwd), nbr_fwd.shape[1], _ptr(n_dev), n_cap, _ptr(self.tile_rows), _ptr(self.loc),
                                        _ptr(self.tile_cnt), self.kvol, _stream())
-        self.ok = rc != -2              # U3D_ERR_UNSUPPORTED: more rows than the LDS row bitmap holds - the caller keeps the table kernels
+        self.ok = rc != U3D_ERR_UNSUPPORTED     # more rows than the LDS row bitmap holds - the caller keeps the table kernels
         if self.ok:
             _check(rc, "subm_halo_build")
 
@@ -767,21 +568,21 @@ def spconv_fwd(inp, w, nbr, n_out_dev, n_out, cout, transpose_w=False, tag=None,
     out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
     region = timed_begin()
-    rc = -2
+    rc = U3D_ERR_UNSUPPORTED
     if addend is not None and inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and ld != 0 and addend.dtype == torch.bfloat16 \
             and addend.shape == out.shape and addend.is_contiguous():
         rc = lib().u3d_igemm_fwd_add_bf16(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(addend), _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
                                           1 if transpose_w else 0, _stream())
-        if rc not in (0, -2):
+        if rc not in (0, U3D_ERR_UNSUPPORTED):
             _check(rc, "igemm_fwd_add_bf16")
         if rc == 0:
             addend = None                      # already in
-    if rc == -2 and inp.dtype == torch.bfloat16 and USE_IGEMM_V2:
+    if rc == U3D_ERR_UNSUPPORTED and inp.dtype == torch.bfloat16 and USE_IGEMM_V2:
         rc = lib().u3d_igemm_fwd_bf16(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
                                       1 if transpose_w else 0, _stream())
-        if rc not in (0, -2):
+        if rc not in (0, U3D_ERR_UNSUPPORTED):
             _check(rc, "igemm_fwd_bf16")
-    if rc == -2:      # shape served by the first-generation kernel (small channel counts, f32)
+    if rc == U3D_ERR_UNSUPPORTED:      # shape served by the first-generation kernel (small channel counts, f32)
         _check(lib().u3d_spconv_fwd(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
                                     1 if transpose_w else 0, dtype_code(inp), _stream()), "spconv_fwd")
     if region is not None:
@@ -823,9 +624,7 @@ def spconv_fwd_split_direct(xs, w3, nbr, n_out_dev, n_out, cout, tag="spconv_fwd
     return out
 
 
-class _SplitRowsJobs(C.Structure):
-    _fields_ = [("src", C.c_void_p * 32), ("dst", C.c_void_p * 32), ("ld", C.c_int32 * 32), ("rows", C.c_int32 * 32), ("cols", C.c_int32 * 32),
-                ("first_block", C.c_int32 * 33), ("njobs", C.c_int32)]
+_SplitRowsJobs = _struct("U3dSplitRowsJobs", "_SplitRowsJobs")
 
 
 def split_rows_batch_into(tensors, outs):
@@ -1240,7 +1039,7 @@ def bn_apply(x, mean, invstd, gamma, beta, residual, relu, n_dev, row_map=None, 
                                            _ptr(planes), _ptr(n_dev), n, c, _ptr(row_map), _ptr(post_add), _stream())
             if rc == 0:
                 return y, planes
-            if rc != -2:
+            if rc != U3D_ERR_UNSUPPORTED:
                 _check(rc, "bn_apply_planes")
             planes = None
         _check(lib().u3d_bn_apply(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), int(relu),
@@ -1275,7 +1074,7 @@ def bn_bwd_apply(dy, y, x, mean, invstd, gamma, sums, relu, n_dev, want_dres, be
                                                _ptr(dx), _ptr(dres), _ptr(planes), _ptr(n_dev), n, c, _ptr(row_map), _stream())
             if rc == 0:
                 return dx, dres, planes
-            if rc != -2:
+            if rc != U3D_ERR_UNSUPPORTED:
                 _check(rc, "bn_bwd_apply_planes")
         _check(lib().u3d_bn_bwd_apply(_ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(sums), int(relu),
                                       _ptr(dx), _ptr(dres), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _stream()), "bn_bwd_apply")
@@ -1915,8 +1714,7 @@ def cast_bf16(src, dst):
     return dst
 
 
-PERMUTE_DESC_DTYPE = [("src_off", "<i8"), ("dst_off", "<i8"), ("n", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("reserved", "<i4"),
-                      ("stride_k", "<i8"), ("stride_r", "<i8"), ("stride_c", "<i8")]          # = struct u3d_permute_desc
+PERMUTE_DESC_DTYPE = abi.numpy_dtype(_ABI.structs["u3d_permute_desc"])
 
 
 PERMUTE_TILED = True
@@ -2008,7 +1806,7 @@ def sine_embed_bwd(logits, dim_t, dout):
 # fused decoder layer (csrc/decoder.hip, csrc/decoder_bwd.hip)
 # --------------------------------------------------------------------------------------------------
 _SLOT_CACHE = {}
-DT_F32, DT_BF16 = 0, 1                 # include/u3d_hip.h: enum { U3D_F32 = 0, U3D_BF16 = 1 }
+DT_F32, DT_BF16 = F32, BF16
 
 
 def dt_code(dtype):
@@ -2134,7 +1932,7 @@ def dropout_mask(rng, layer, site, n, p, cols=0):
 # --------------------------------------------------------------------------------------------------
 # on-device data path
 # --------------------------------------------------------------------------------------------------
-AUG_NPARAM = 9
+AUG_NPARAM = _K["U3D_AUG_NPARAM"]
 
 
 def points_augment(points, scene_off, params, coord, height_dim=-1):
@@ -2249,9 +2047,9 @@ def batch_ingest(points, scene_off, count, point_cap, cat, dst_off, flag, gt=Non
 # --------------------------------------------------------------------------------------------------
 # LoadPointsFromMultiSweeps (csrc/sweeps.hip)
 # --------------------------------------------------------------------------------------------------
-SWEEPS_CHUNK = 256     # U3D_SWEEPS_CHUNK
-SWEEPS_NPARAM = 13     # U3D_SWEEPS_NPARAM: R row-major, t, lag
-SWEEP_SEG_KEY, SWEEP_SEG_SWEEP, SWEEP_SEG_PAD = 0, 1, 2
+SWEEPS_CHUNK = _K["U3D_SWEEPS_CHUNK"]
+SWEEPS_NPARAM = _K["U3D_SWEEPS_NPARAM"]     # R row-major, t, lag
+SWEEP_SEG_KEY, SWEEP_SEG_SWEEP, SWEEP_SEG_PAD = _K["U3D_SWEEP_SEG_KEY"], _K["U3D_SWEEP_SEG_SWEEP"], _K["U3D_SWEEP_SEG_PAD"]
 
 
 def sweeps_merge(key_points, raw, seg_tab, seg_param, seg_chunk0, scene_chunk0, n_chunks, out_rows, use_dim, remove_close):
@@ -2405,7 +2203,7 @@ def object_noise(points, scene_off, n_live, max_rows, boxes, gt_off, g_live, loc
 # --------------------------------------------------------------------------------------------------
 # Test-time augmentation: the multi-view box merge (csrc/tta.hip)
 # --------------------------------------------------------------------------------------------------
-TTA_LDS_CAP = 2048     # U3D_TTA_LDS_CAP: larger (scene, class) segments take the global-memory path
+TTA_LDS_CAP = _K["U3D_TTA_LDS_CAP"]     # larger (scene, class) segments take the global-memory path
 
 
 def tta_inverse_params(params):
@@ -2451,8 +2249,8 @@ def tta_merge(boxes, scores, labels, det_off, params, views, coord, num_classes,
 # --------------------------------------------------------------------------------------------------
 # The batched inference tail (csrc/det_tail.hip)
 # --------------------------------------------------------------------------------------------------
-DET_TAIL_NONE, DET_TAIL_NMS, DET_TAIL_DECODE, DET_TAIL_SOFT_NMS, DET_TAIL_MERGE = 0, 1, 2, 3, 4
-DET_TAIL_MAX_K = 8192
+(DET_TAIL_NONE, DET_TAIL_NMS, DET_TAIL_DECODE, DET_TAIL_SOFT_NMS, DET_TAIL_MERGE,
+ DET_TAIL_MAX_K) = (_K["U3D_DET_TAIL_" + _n] for _n in ("NONE", "NMS", "DECODE", "SOFT_NMS", "MERGE", "MAX_K"))
 
 
 class DetBatch:
