@@ -960,6 +960,17 @@ int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_d
                               const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
                               const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
                               void* vrec, float* dref, void* grad, int64_t grad_bytes, u3d_stream s);
+/* The same two calls with the wave count of the row-chain launches as an argument: row_waves = 8 (bf16 only: two waves per SIMD, the
+ * default of bf16), 4 (one wave per SIMD: the f32 kernels, and the bf16 comparison partner), 0 = the element type's default.  Results
+ * are bit-identical for either count; forward and backward of one layer may use different ones. */
+int32_t u3d_decoder_layer_fwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                 const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
+                                 float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, int32_t row_waves,
+                                 u3d_stream s);
+int32_t u3d_decoder_layer_bwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                 const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
+                                 const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
+                                 void* vrec, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s);
 int64_t u3d_value_records_bytes(int32_t m);
 /* Adds the records of one u3d_decoder_layer_bwd call into dvalue [n_cells][256] (f32, or bf16 when dvalue_bf16): per cell the sum over
  * its (row, corner) entries in ascending entry order, in f32, added once - bitwise reproducible.  work: u3d_value_scatter_workspace

@@ -1,6 +1,8 @@
 """Fused decoder layer in isolation: `iters` forward + backward calls of one layer at the bench shape (8 scenes x 900 queries, dropout
 on), for kernel-level timing under a rocprofv3 kernel trace (tools/dec_bench.sh) and for A/B runs of kernel variants
-(U3D_LIB_PATH=uni3detr_amd/_variants/<name>.so).  Prints wall time per forward+backward pair as a sanity figure."""
+(U3D_LIB_PATH=uni3detr_amd/_variants/<name>.so).  Prints wall time per forward+backward pair as a sanity figure.
+`python tools/dec_bench.py [iters] [bf16|f32] [4|8|both]`: the third argument sets fused_decoder.ROW_WAVES (bf16); `both` runs the
+four-wave kernels (k_dec_*<EB4>) and then the eight-wave ones (k_dec_*<EB>) in ONE process, so that one kernel trace holds the pair."""
 import os
 import sys
 import time
@@ -47,14 +49,17 @@ def main():
         loss.backward()
         x.grad = None
         rows.grad = None
-    for _ in range(3):
-        once()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        once()
-    torch.cuda.synchronize()
-    print(f"dec_bench {et}: {(time.perf_counter() - t0) / iters * 1e3:.3f} ms per fwd+bwd (host wall, includes torch glue)")
+    waves = sys.argv[3] if len(sys.argv) > 3 else str(fdm.ROW_WAVES)
+    for nw in ((4, 8) if waves == "both" else (int(waves),)):
+        fdm.ROW_WAVES = nw
+        for _ in range(3):
+            once()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            once()
+        torch.cuda.synchronize()
+        print(f"dec_bench {et}, {nw} row waves: {(time.perf_counter() - t0) / iters * 1e3:.3f} ms per fwd+bwd (host wall, includes torch glue)")
     # -DDC_PHASE_TIMING builds: shader-clock stamps of one workgroup (wave 0) at the phase boundaries of the two post kernels
     import ctypes as C
     from uni3detr_amd import native as nv

@@ -179,7 +179,7 @@ extern "C" int32_t u3d_dropout_mask(const uint64_t* rng, int32_t layer, int32_t 
 // k_dec_pre
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename E>
-__global__ __launch_bounds__(DC_THREADS) void k_dec_pre(u3d_declayer_params P, u3d_declayer_dims dm, const typename E::T* __restrict__ xc,
+__global__ __launch_bounds__(E::NW * 64) void k_dec_pre(u3d_declayer_params P, u3d_declayer_dims dm, const typename E::T* __restrict__ xc,
                                                         const float* __restrict__ ref, DcPtrs<E> S, int skip_inproj) {
   typedef typename E::T T;
   typedef typename E::V4 V4;
@@ -191,7 +191,8 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre(u3d_declayer_params P, u
   T* A1 = (T*)(lds + L::A1);
   T* A2 = (T*)(lds + L::A2);
   const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_id();
-  const int wv = (wave + (int)(blockIdx.x >> 3)) & 3;      // which 64 output columns this wave computes: rotated per workgroup (see dc_gemm)
+  constexpr int NTW = 16 / E::NW, WC = NTW * 16;           // MFMA column tiles / output columns a wave owns of a 256-wide linear
+  const int wv = (wave + (int)(blockIdx.x >> 3)) & (E::NW - 1);      // which WC output columns this wave computes: rotated per workgroup (see dc_gemm)
   const int row0 = blockIdx.x * BM, M = dm.m;
   dc_poison_lds<E>(lds, tid);
   // sine embedding of the reference points -> A0 (ldk 384), saved for the first GEMM's weight gradient
@@ -221,30 +222,30 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre(u3d_declayer_params P, u
     return [=](int row, int col, f32x4 v) { *(V4*)(dst + dc_aoff<E>(row, col, DC_C)) = E::pack4(v + dc_bias4(bias, col)); };
   };
   T* A1b = A1 + BM * DC_C;
-  dc_linear<E, 384, 4>(A0, (const T*)P.w[U3D_DL_RPH0], wv * 64, lane, relu_to(A1, P.b[U3D_DL_RPH0]));
+  dc_linear<E, 384, NTW>(A0, (const T*)P.w[U3D_DL_RPH0], wv * WC, lane, relu_to(A1, P.b[U3D_DL_RPH0]));
   __syncthreads();
   dc_store_a<E, 256>(A1, S.rph1, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A1, (const T*)P.w[U3D_DL_RPH1], wv * 64, lane, relu_to(A0, P.b[U3D_DL_RPH1]));
+  dc_linear<E, 256, NTW>(A1, (const T*)P.w[U3D_DL_RPH1], wv * WC, lane, relu_to(A0, P.b[U3D_DL_RPH1]));
   __syncthreads();
   dc_store_a<E, 256>(A0, S.rph2, DC_C, row0, tid);
   // raw = ref_point_head's output -> A2; it is the position embedding itself in the first layer
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_RPH2], wv * 64, lane, lin_to(A2, P.b[U3D_DL_RPH2]));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_RPH2], wv * WC, lane, lin_to(A2, P.b[U3D_DL_RPH2]));
   __syncthreads();
   dc_store_a<E, 256>(A2, dm.has_qs ? S.raw : S.pos, DC_C, row0, tid);
   dc_load_a<E, 256, true>(A0, xc, DC_C, row0, M, tid);           // x: input of query_scale and of the value projection
   __syncthreads();
   if (dm.has_qs) {
-    dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_QS0], wv * 64, lane, relu_to(A1, P.b[U3D_DL_QS0]));
+    dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_QS0], wv * WC, lane, relu_to(A1, P.b[U3D_DL_QS0]));
     __syncthreads();
     dc_store_a<E, 256>(A1, S.qs1, DC_C, row0, tid);
     // A0 still holds x (the value projection needs it): the second hidden layer goes to the second BM x 256 half of A1
-    dc_linear<E, 256, 4>(A1, (const T*)P.w[U3D_DL_QS1], wv * 64, lane, relu_to(A1b, P.b[U3D_DL_QS1]));
+    dc_linear<E, 256, NTW>(A1, (const T*)P.w[U3D_DL_QS1], wv * WC, lane, relu_to(A1b, P.b[U3D_DL_QS1]));
     __syncthreads();
     dc_store_a<E, 256>(A1b, S.qs2, DC_C, row0, tid);
     const float* bias = P.b[U3D_DL_QS2];
     // pos = query_scale(x) * raw (both T tensors in the layer-by-layer formulation) -> A2 in place (same element, same lane);
     // the scale itself -> first half of A1 (free: its reader, the linear before, finished at the barrier)
-    dc_linear<E, 256, 4>(A1b, (const T*)P.w[U3D_DL_QS2], wv * 64, lane, [=](int row, int col, f32x4 v) {
+    dc_linear<E, 256, NTW>(A1b, (const T*)P.w[U3D_DL_QS2], wv * WC, lane, [=](int row, int col, f32x4 v) {
       const V4 q = E::pack4(v + dc_bias4(bias, col));
       const int ao = dc_aoff<E>(row, col, DC_C);
       const f32x4 raw = E::unpack4(*(const V4*)(A2 + ao));
@@ -269,17 +270,17 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre(u3d_declayer_params P, u
   if (skip_inproj) return;                               // (uniform) the attention launch projects its own head: k_mha_proj_fwd
   // in-projection: q = A1b . Wq^T + b -> A1, k -> A2 (pos is saved), v = A0 . Wv^T + b -> A1b; each block leaves for HBM from its tile
   // (the attention kernel regroups rows by (group, head))
-  dc_linear<E, 256, 4>(A1b, (const T*)P.w[U3D_DL_INQK], wv * 64, lane, lin_to(A1, P.b[U3D_DL_INQK]));
+  dc_linear<E, 256, NTW>(A1b, (const T*)P.w[U3D_DL_INQK], wv * WC, lane, lin_to(A1, P.b[U3D_DL_INQK]));
   {
     const float* bias = P.b[U3D_DL_INQK];
-    dc_linear<E, 256, 4>(A1b, (const T*)P.w[U3D_DL_INQK], 256 + wv * 64, lane, [=](int row, int col, f32x4 v) {
+    dc_linear<E, 256, NTW>(A1b, (const T*)P.w[U3D_DL_INQK], 256 + wv * WC, lane, [=](int row, int col, f32x4 v) {
       *(V4*)(A2 + dc_aoff<E>(row, col - 256, DC_C)) = E::pack4(v + dc_bias4(bias, col));
     });
   }
   __syncthreads();
   dc_store_a<E, 256>(A1, S.qk, 512, row0, tid);
   dc_store_a<E, 256>(A2, S.qk + 256, 512, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_INV], wv * 64, lane, lin_to(A1b, P.b[U3D_DL_INV]));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_INV], wv * WC, lane, lin_to(A1b, P.b[U3D_DL_INV]));
   __syncthreads();
   dc_store_a<E, 256>(A1b, S.v, DC_C, row0, tid);
 }
@@ -623,7 +624,7 @@ __global__ __launch_bounds__(MHA_PROJ_THREADS) void k_mha_proj_fwd(const u16* __
 // k_dec_post
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename E>
-__global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, u3d_declayer_dims dm, const float* __restrict__ x,
+__global__ __launch_bounds__(E::NW * 64) void k_dec_post(u3d_declayer_params P, u3d_declayer_dims dm, const float* __restrict__ x,
                                                          const float* __restrict__ ref, const typename E::T* __restrict__ value,
                                                          const unsigned long long* __restrict__ rng, DcPtrs<E> S, float* __restrict__ x_out,
                                                          typename E::T* __restrict__ xc_out, float* __restrict__ reg_out,
@@ -631,7 +632,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
   typedef typename E::T T;
   typedef typename E::V4 V4;
   typedef DcLds<E> L;
-  constexpr int BM = E::BM, RPW = E::BM / 4;
+  constexpr int BM = E::BM, RPW = E::BM / E::NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   T* A0 = (T*)(lds + L::A0);
   T* A1 = (T*)(lds + L::A1);
@@ -640,7 +641,8 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
   float* G = (float*)(lds + L::G);
   float* misc = (float*)(lds + L::MISC);
   const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_id();
-  const int wv = (wave + (int)(blockIdx.x >> 3)) & 3;      // which 64 output columns this wave computes: rotated per workgroup (see dc_gemm)
+  constexpr int NTW = 16 / E::NW, WC = NTW * 16;           // MFMA column tiles / output columns a wave owns of a 256-wide linear
+  const int wv = (wave + (int)(blockIdx.x >> 3)) & (E::NW - 1);      // which WC output columns this wave computes: rotated per workgroup (see dc_gemm)
   const int row0 = blockIdx.x * BM, M = dm.m;
   dc_poison_lds<E>(lds, tid);
   DcDrop drop = {dc_rng_load(rng), dc_thresh(dm.p_drop), dc_inv_keep(dm.p_drop), dm.layer};
@@ -664,7 +666,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
     };
   };
   DC_MARK(1);
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_OUTP], wv * 64, lane, add_to_F(P.b[U3D_DL_OUTP], 0));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_OUTP], wv * WC, lane, add_to_F(P.b[U3D_DL_OUTP], 0));
   __syncthreads();
   DC_MARK(2);
   {
@@ -728,17 +730,20 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
   DC_MARK(4);
   // position encoder, first layer (3 -> 256): plain VALU into G
   {
-    const int col = tid;
+    // a thread owns one column of BM / (NW / 4) rows: four waves cover the 256 columns
+    constexpr int PR = BM / (E::NW / 4);
+    const int col = E::NW > 4 ? tid & 255 : tid, prow0 = E::NW > 4 ? (wave >> 2) * PR : 0;
     const float w0 = E::round(P.pe0_w[col * 3 + 0]), w1 = E::round(P.pe0_w[col * 3 + 1]), w2 = E::round(P.pe0_w[col * 3 + 2]);
     const float b = P.pe0_b[col];
-    for (int row = 0; row < BM; ++row) {
+    for (int pr = 0; pr < PR; ++pr) {
+      const int row = prow0 + pr;
       const float* r3 = misc + row * DC_MISC_LD;
       G[row * DC_TS + col] = E::round(E::round(r3[0]) * w0 + E::round(r3[1]) * w1 + E::round(r3[2]) * w2 + b);
     }
   }
   __syncthreads();
   DC_MARK(5);
-  dc_linear<E, 256, 4>(A1, (const T*)P.w[U3D_DL_OPROJ], wv * 64, lane, add_to_F(P.b[U3D_DL_OPROJ], 1));
+  dc_linear<E, 256, NTW>(A1, (const T*)P.w[U3D_DL_OPROJ], wv * WC, lane, add_to_F(P.b[U3D_DL_OPROJ], 1));
   {
     DcLnOut<E> o = {nullptr, A0, DC_C, nullptr, S.peh0, S.mr, U3D_DLN_PE0, false, nullptr, nullptr};
     dc_layernorm<E>(G, P.ln_g[U3D_DLN_PE0], P.ln_b[U3D_DLN_PE0], dm.ln_eps, true, o, row0, wave, lane);   // overwrites A0 (x1: no longer needed)
@@ -747,7 +752,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
   DC_MARK(6);
   {
     const float* bias = P.b[U3D_DL_PE1];
-    dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_PE1], wv * 64, lane, [=](int row, int col, f32x4 v) {
+    dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_PE1], wv * WC, lane, [=](int row, int col, f32x4 v) {
       *(f32x4*)(G + row * DC_TS + col) = E::round4(v + dc_bias4(bias, col));       // saved by the LayerNorm below (its input rows)
     });
   }
@@ -778,13 +783,13 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
       const V4 hb = E::pack4(drop.apply(v, 2, (unsigned)((row0 + row) * DC_FF + col)));
       *(V4*)(A1 + dc_aoff<E>(row, col, DC_FF)) = hb;
     };
-    dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_FFN0], wv * 64, lane, ffh);
-    dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_FFN0], 256 + wv * 64, lane, ffh);
+    dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_FFN0], wv * WC, lane, ffh);
+    dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_FFN0], 256 + wv * WC, lane, ffh);
   }
   __syncthreads();
   DC_MARK(10);
   dc_store_a<E, 512>(A1, S.ffh, DC_FF, row0, tid);
-  dc_linear<E, 512, 4>(A1, (const T*)P.w[U3D_DL_FFN1], wv * 64, lane, add_to_F(P.b[U3D_DL_FFN1], 3));
+  dc_linear<E, 512, NTW>(A1, (const T*)P.w[U3D_DL_FFN1], wv * WC, lane, add_to_F(P.b[U3D_DL_FFN1], 3));
   __syncthreads();
   DC_MARK(11);
   {
@@ -810,59 +815,62 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post(u3d_declayer_params P, 
 #ifdef DC_PHASE_TIMING
   {     // one linear taken apart: burst + MFMAs | epilogue | barrier
     DC_MARK(20);
-    f32x4 acc[E::MT][4];
+    f32x4 acc[E::MT][NTW];
 #pragma unroll
     for (int mt = 0; mt < E::MT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    dc_gemm<E, 256, 4>(A2, (const T*)P.w[U3D_DL_REG0] + (size_t)(wv * 64) * 256, acc, lane);
+      for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    dc_gemm<E, 256, NTW>(A2, (const T*)P.w[U3D_DL_REG0] + (size_t)(wv * WC) * 256, acc, lane);
     __builtin_amdgcn_sched_barrier(0);
     DC_MARK(21);
     auto epi = relu_to(A0, P.b[U3D_DL_REG0]);
 #pragma unroll
     for (int mt = 0; mt < E::MT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) epi(mt * 16 + (lane & 15), wv * 64 + nt * 16 + (lane >> 4) * 4, acc[mt][nt]);
+      for (int nt = 0; nt < NTW; ++nt) epi(mt * 16 + (lane & 15), wv * WC + nt * 16 + (lane >> 4) * 4, acc[mt][nt]);
     __builtin_amdgcn_sched_barrier(0);
     DC_MARK(22);
     __syncthreads();
     DC_MARK(23);
   }
 #else
-  dc_linear<E, 256, 4>(A2, (const T*)P.w[U3D_DL_REG0], wv * 64, lane, relu_to(A0, P.b[U3D_DL_REG0]));
+  dc_linear<E, 256, NTW>(A2, (const T*)P.w[U3D_DL_REG0], wv * WC, lane, relu_to(A0, P.b[U3D_DL_REG0]));
   __syncthreads();
 #endif
   dc_store_a<E, 256>(A0, S.r1, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_REG1], wv * 64, lane, relu_to(A1, P.b[U3D_DL_REG1]));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_REG1], wv * WC, lane, relu_to(A1, P.b[U3D_DL_REG1]));
   __syncthreads();
   dc_store_a<E, 256>(A1, S.r2, DC_C, row0, tid);
-  dc_linear<E, 256, 1>(A1, (const T*)P.w[U3D_DL_REG2], wv * 16, lane, narrow_out(reg_out, dm.code, P.b[U3D_DL_REG2]));
-  dc_linear<E, 256, 4>(A2, (const T*)P.w[U3D_DL_IOU0], wv * 64, lane, relu_to(A0, P.b[U3D_DL_IOU0]));
+  // a narrow final layer has four column tiles (64 padded columns): of eight waves the four with wv >= 4 (a scalar test) go straight on
+  // to the next linear, which no barrier separates from this one
+  if (wv < 4) dc_linear<E, 256, 1>(A1, (const T*)P.w[U3D_DL_REG2], wv * 16, lane, narrow_out(reg_out, dm.code, P.b[U3D_DL_REG2]));
+  dc_linear<E, 256, NTW>(A2, (const T*)P.w[U3D_DL_IOU0], wv * WC, lane, relu_to(A0, P.b[U3D_DL_IOU0]));
   __syncthreads();
   dc_store_a<E, 256>(A0, S.i1, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_IOU1], wv * 64, lane, relu_to(A1b, P.b[U3D_DL_IOU1]));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_IOU1], wv * WC, lane, relu_to(A1b, P.b[U3D_DL_IOU1]));
   __syncthreads();
   dc_store_a<E, 256>(A1b, S.i2, DC_C, row0, tid);
-  dc_linear<E, 256, 1>(A1b, (const T*)P.w[U3D_DL_IOU2], wv * 16, lane, narrow_out(iou_out, 1, P.b[U3D_DL_IOU2]));
+  if (wv < 4) dc_linear<E, 256, 1>(A1b, (const T*)P.w[U3D_DL_IOU2], wv * 16, lane, narrow_out(iou_out, 1, P.b[U3D_DL_IOU2]));
+  DC_MARK(13);
   // cls: Linear -> LN -> ReLU twice, then the class logits (each linear's output is saved by the LayerNorm that reads it)
   auto to_G = [&](const float* bias) {
     return [=](int row, int col, f32x4 v) { *(f32x4*)(G + row * DC_TS + col) = E::round4(v + dc_bias4(bias, col)); };
   };
-  dc_linear<E, 256, 4>(A2, (const T*)P.w[U3D_DL_CLS0], wv * 64, lane, to_G(P.b[U3D_DL_CLS0]));
+  dc_linear<E, 256, NTW>(A2, (const T*)P.w[U3D_DL_CLS0], wv * WC, lane, to_G(P.b[U3D_DL_CLS0]));
   __syncthreads();
   {
     DcLnOut<E> o = {nullptr, A0, DC_C, nullptr, S.c1, S.mr, U3D_DLN_C1, false, nullptr, S.uc1};
     dc_layernorm<E>(G, P.ln_g[U3D_DLN_C1], P.ln_b[U3D_DLN_C1], dm.ln_eps, true, o, row0, wave, lane);
   }
   __syncthreads();
-  dc_linear<E, 256, 4>(A0, (const T*)P.w[U3D_DL_CLS1], wv * 64, lane, to_G(P.b[U3D_DL_CLS1]));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.w[U3D_DL_CLS1], wv * WC, lane, to_G(P.b[U3D_DL_CLS1]));
   __syncthreads();
   {
     DcLnOut<E> o = {nullptr, A1, DC_C, nullptr, S.c2, S.mr, U3D_DLN_C2, false, nullptr, S.uc2};
     dc_layernorm<E>(G, P.ln_g[U3D_DLN_C2], P.ln_b[U3D_DLN_C2], dm.ln_eps, true, o, row0, wave, lane);
   }
   __syncthreads();
-  dc_linear<E, 256, 1>(A1, (const T*)P.w[U3D_DL_CLS2], wv * 16, lane, narrow_out(cls_out, dm.ncls, P.b[U3D_DL_CLS2]));
+  if (wv < 4) dc_linear<E, 256, 1>(A1, (const T*)P.w[U3D_DL_CLS2], wv * 16, lane, narrow_out(cls_out, dm.ncls, P.b[U3D_DL_CLS2]));
   DC_MARK(14);
 }
 
@@ -893,7 +901,7 @@ static int32_t dc_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dim
   U3D_ALLOW_LDS(k_dec_post<E>, DcLds<E>::BYTES);
   // bf16, groups of at most one LDS chunk of queries: in-projection + attention in ONE launch per layer (k_mha_proj_fwd)
   const bool fused = mha_fused_inproj(E::DT, d->nq);
-  hipLaunchKernelGGL(k_dec_pre<E>, dim3(nb), dim3(DC_THREADS), DcLds<E>::BYTES, s, *p, *d, (const T*)xc, ref, S, fused ? 1 : 0);
+  hipLaunchKernelGGL(k_dec_pre<E>, dim3(nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, (const T*)xc, ref, S, fused ? 1 : 0);
   if (fused) {
     U3D_ALLOW_LDS(k_mha_proj_fwd, MhaProjLds::BYTES);
     const float scale_log2 = 1.4426950408889634f / sqrtf((float)DC_HD);
@@ -905,22 +913,33 @@ static int32_t dc_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dim
     int32_t rc = u3d_mha_fwd_dt(S.qk, S.v, d->m, d->nq, d->p_attn, d->layer, rng, S.o, S.lse, E::DT, s);
     if (rc != U3D_OK) return rc;
   }
-  hipLaunchKernelGGL(k_dec_post<E>, dim3(nb), dim3(DC_THREADS), DcLds<E>::BYTES, s, *p, *d, x, ref, (const T*)value,
+  hipLaunchKernelGGL(k_dec_post<E>, dim3(nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, x, ref, (const T*)value,
                      (const unsigned long long*)rng, S, x_out, (T*)xc_out, reg_out, cls_out, iou_out);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
 
-extern "C" int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                         const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
-                                         float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, u3d_stream s) {
+// row_waves: waves per workgroup of the two row-chain launches - 8 (bf16 only: two waves per SIMD) | 4 | 0 = the element type's default
+// (bf16: 8, f32: 4).  The results do not depend on it, bit for bit.
+extern "C" int32_t u3d_decoder_layer_fwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                            const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
+                                            float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes,
+                                            int32_t row_waves, u3d_stream s) {
   int32_t rc = dc_check(p, d);
   if (rc != U3D_OK) return rc;
   U3D_REQUIRE(x && xc && ref && value && x_out && xc_out && reg_out && cls_out && iou_out && save, U3D_ERR_ARG);
   U3D_REQUIRE((d->p_attn == 0.f && d->p_drop == 0.f) || rng, U3D_ERR_ARG);
+  U3D_REQUIRE(row_waves == 0 || row_waves == 4 || (row_waves == 8 && d->dtype == U3D_BF16), U3D_ERR_ARG);
   int64_t off[U3D_DS_COUNT + 1];
   u3d_decoder_layer_slots_dt(d->m, d->ncls, d->code, d->dtype, off, nullptr);
   U3D_REQUIRE(save_bytes >= off[U3D_DS_COUNT], U3D_ERR_WORKSPACE);
+  if (d->dtype == U3D_BF16 && row_waves == 4)
+    return dc_layer_fwd<EB4>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
   if (d->dtype == U3D_BF16) return dc_layer_fwd<EB>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
   return dc_layer_fwd<EF>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
+}
+extern "C" int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                         const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
+                                         float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, u3d_stream s) {
+  return u3d_decoder_layer_fwd_nw(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, save_bytes, 0, s);
 }

@@ -98,10 +98,15 @@ __device__ __forceinline__ void dc_layernorm_bwd(const float* T, LoadU load_u, c
                                                  const DcLnBwdOut<E>& o, float* __restrict__ lnp, int ln, int nb, float* red /* LDS [4][2][256] */,
                                                  int row0, int wave, int lane, int tid) {
   typedef typename E::V4 V4;
-  constexpr int RPW = E::BM / 4;
+  // (dgamma, dbeta) of the workgroup = the sum of four QUARTER sums, each over the BM / 4 rows of a quarter in row order - whatever
+  // the wave count, so that the partials do not depend on it bit for bit.  Four waves: a wave owns a quarter and sums as it goes.
+  // Eight: the CHAIN = 2 waves of a quarter keep (dy, x^) of their rows and take turns, the second continuing the first one's sum.
+  constexpr int RPW = E::BM / E::NW, CHAIN = E::NW / 4;
   const f32x4 ga = *(const f32x4*)(gamma + lane * 4), be = *(const f32x4*)(beta + lane * 4);
   f32x4 dg = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
+  constexpr int KEEP = CHAIN > 1 ? RPW : 1, UNROLL = CHAIN > 1 ? RPW : 2;      // kept rows are register arrays: whole unroll
+  f32x4 kdy[KEEP], kxh[KEEP];
+#pragma unroll UNROLL
   for (int rr = 0; rr < RPW; ++rr) {
     const int row = wave * RPW + rr;
     const int gr = row0 + row;                 // padded slots: rows past m carry zero gradients and finite saved values
@@ -117,8 +122,14 @@ __device__ __forceinline__ void dc_layernorm_bwd(const float* T, LoadU load_u, c
       dxh[j] = dy[j] * ga[j];
       s1 += dxh[j];
       s2 += dxh[j] * xh[j];
-      dg[j] += dy[j] * xh[j];
-      db[j] += dy[j];
+      if constexpr (CHAIN == 1) {
+        dg[j] += dy[j] * xh[j];
+        db[j] += dy[j];
+      }
+    }
+    if constexpr (CHAIN > 1) {
+      kdy[rr] = dy;
+      kxh[rr] = xh;
     }
     s1 = dc_wave_sum(s1) * (1.f / DC_C);
     s2 = dc_wave_sum(s2) * (1.f / DC_C);
@@ -130,9 +141,32 @@ __device__ __forceinline__ void dc_layernorm_bwd(const float* T, LoadU load_u, c
     if (o.a) *(V4*)(o.a + dc_aoff<E>(row, lane * 4, DC_C)) = dub;
     if (o.g16) *(V4*)(o.g16 + (size_t)gr * DC_C + lane * 4) = dub;
   }
-  *(f32x4*)(red + (wave * 2 + 0) * DC_C + lane * 4) = dg;
-  *(f32x4*)(red + (wave * 2 + 1) * DC_C + lane * 4) = db;
-  __syncthreads();
+  float* rq = red + (wave / CHAIN) * 2 * DC_C + lane * 4;      // this wave's quarter: [dgamma | dbeta][256]
+  if constexpr (CHAIN == 1) {
+    *(f32x4*)rq = dg;
+    *(f32x4*)(rq + DC_C) = db;
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int t = 0; t < CHAIN; ++t) {
+      if (wave % CHAIN == t) {                  // wave-uniform (the wave id is a scalar)
+        if (t > 0) {
+          dg = *(const f32x4*)rq;
+          db = *(const f32x4*)(rq + DC_C);
+        }
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            dg[j] += kdy[rr][j] * kxh[rr][j];
+            db[j] += kdy[rr][j];
+          }
+        *(f32x4*)rq = dg;
+        *(f32x4*)(rq + DC_C) = db;
+      }
+      __syncthreads();
+    }
+  }
   DC_FOR_TID(i, 2 * DC_C) {
     const int which = i >> 8, col = i & 255;
     const float v = red[(0 * 2 + which) * DC_C + col] + red[(1 * 2 + which) * DC_C + col] + red[(2 * 2 + which) * DC_C + col] +
@@ -146,7 +180,7 @@ __device__ __forceinline__ void dc_layernorm_bwd(const float* T, LoadU load_u, c
 // k_dec_post_bwd
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename E>
-__global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params P, u3d_declayer_dims dm, const float* __restrict__ ref,
+__global__ __launch_bounds__(E::NW * 64) void k_dec_post_bwd(u3d_declayer_params P, u3d_declayer_dims dm, const float* __restrict__ ref,
                                                              const typename E::T* __restrict__ value,
                                                              const unsigned long long* __restrict__ rng, DcSave<E> S, DcGrad<E> Gd,
                                                              const float* __restrict__ dx_out, const float* __restrict__ dreg,
@@ -159,7 +193,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   typedef typename E::T T;
   typedef typename E::V4 V4;
   typedef DcLds<E> L;
-  constexpr int BM = E::BM, RPW = E::BM / 4;
+  constexpr int BM = E::BM, RPW = E::BM / E::NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   T* A0 = (T*)(lds + L::A0);
   T* A1 = (T*)(lds + L::A1);
@@ -175,7 +209,8 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   T* Dn = A2;
   static_assert(BM * NLD <= BM * DC_C, "narrow-gradient tile must fit the A2 region");
   const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_id();
-  const int wv = (wave + (int)(blockIdx.x >> 3)) & 3;      // which 64 output columns this wave computes: rotated per workgroup (see dc_gemm)
+  constexpr int NTW = 16 / E::NW, WC = NTW * 16;           // MFMA column tiles / output columns a wave owns of a 256-wide linear
+  const int wv = (wave + (int)(blockIdx.x >> 3)) & (E::NW - 1);      // which WC output columns this wave computes: rotated per workgroup (see dc_gemm)
   const int row0 = blockIdx.x * BM, M = dm.m, nb = Gd.nb;
   dc_poison_lds<E>(lds, tid);
   DcDrop drop = {dc_rng_load(rng), dc_thresh(dm.p_drop), dc_inv_keep(dm.p_drop), dm.layer};
@@ -206,19 +241,19 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
     typedef typename E::VC VC;
     constexpr int KSN = 32 / E::KSTEP, WBLK = 64 * E::CH;
     const int r16 = lane & 15, kq = lane >> 4;
-    f32x4 acc[E::MT][4];
+    f32x4 acc[E::MT][NTW];
 #pragma unroll
     for (int mt = 0; mt < E::MT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks) {
       VC a[E::MT];
 #pragma unroll
       for (int mt = 0; mt < E::MT; ++mt) a[mt] = *(const VC*)(Dn + (mt * 16 + r16) * NLD + (ks * 4 + kq) * E::CH);
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const VC wf = *(const VC*)(wt + (size_t)((wv * 4 + nt) * KSN + ks) * WBLK + lane * E::CH);
+      for (int nt = 0; nt < NTW; ++nt) {
+        const VC wf = *(const VC*)(wt + (size_t)((wv * NTW + nt) * KSN + ks) * WBLK + lane * E::CH);
 #pragma unroll
         for (int mt = 0; mt < E::MT; ++mt) E::mma(wf, a[mt], acc[mt][nt]);
       }
@@ -226,8 +261,8 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
 #pragma unroll
     for (int mt = 0; mt < E::MT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const int row = mt * 16 + r16, col = wv * 64 + nt * 16 + kq * 4;
+      for (int nt = 0; nt < NTW; ++nt) {
+        const int row = mt * 16 + r16, col = wv * WC + nt * 16 + kq * 4;
         f32x4 v = acc[mt][nt];
         if (mask_src) {
           const V4 y = *(const V4*)(mask_src + (size_t)(row0 + row) * DC_C + col);
@@ -274,14 +309,14 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
     dc_layernorm_bwd<E>(G, u_elem(S.uc2), S.mr, U3D_DLN_C2, P.ln_g[U3D_DLN_C2], P.ln_b[U3D_DLN_C2], true, o, Gd.lnp, U3D_DLN_C2, nb, red, row0,
                         wave, lane, tid);
   }
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_CLS1], wv * 64, lane, to_G());
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_CLS1], wv * WC, lane, to_G());
   __syncthreads();
   {
     DcLnBwdOut<E> o = {nullptr, A0, Gd.c1u};
     dc_layernorm_bwd<E>(G, u_elem(S.uc1), S.mr, U3D_DLN_C1, P.ln_g[U3D_DLN_C1], P.ln_b[U3D_DLN_C1], true, o, Gd.lnp, U3D_DLN_C1, nb, red, row0,
                         wave, lane, tid);
   }
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_CLS0], wv * 64, lane, acc_to_F());
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_CLS0], wv * WC, lane, acc_to_F());
   __syncthreads();
   DC_MARK(2);
   // ---- iou branch ----------------------------------------------------------------------------------------------------------
@@ -290,10 +325,10 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   narrow_dgrad((const T*)P.wt[U3D_DL_IOU2], S.i2, A0);
   __syncthreads();
   dc_store_a<E, 256>(A0, Gd.i2, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_IOU1], wv * 64, lane, masked_to(A1, S.i1));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_IOU1], wv * WC, lane, masked_to(A1, S.i1));
   __syncthreads();
   dc_store_a<E, 256>(A1, Gd.i1, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A1, (const T*)P.wt[U3D_DL_IOU0], wv * 64, lane, acc_to_F());
+  dc_linear<E, 256, NTW>(A1, (const T*)P.wt[U3D_DL_IOU0], wv * WC, lane, acc_to_F());
   __syncthreads();
   DC_MARK(3);
   // ---- reg branch ----------------------------------------------------------------------------------------------------------
@@ -302,10 +337,10 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   narrow_dgrad((const T*)P.wt[U3D_DL_REG2], S.r2, A0);
   __syncthreads();
   dc_store_a<E, 256>(A0, Gd.r2, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_REG1], wv * 64, lane, masked_to(A1, S.r1));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_REG1], wv * WC, lane, masked_to(A1, S.r1));
   __syncthreads();
   dc_store_a<E, 256>(A1, Gd.r1, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A1, (const T*)P.wt[U3D_DL_REG0], wv * 64, lane, acc_to_F());
+  dc_linear<E, 256, NTW>(A1, (const T*)P.wt[U3D_DL_REG0], wv * WC, lane, acc_to_F());
   __syncthreads();
   DC_MARK(4);
   // ---- LN3 -> du3 (F) -------------------------------------------------------------------------------------------------------
@@ -338,12 +373,12 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
       const V4 o = E::pack4(v);
       *(V4*)(A1 + dc_aoff<E>(row, col, DC_FF)) = o;
     };
-    dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_FFN1], wv * 64, lane, dh);
-    dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_FFN1], 256 + wv * 64, lane, dh);
+    dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_FFN1], wv * WC, lane, dh);
+    dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_FFN1], 256 + wv * WC, lane, dh);
   }
   __syncthreads();
   dc_store_a<E, 512>(A1, Gd.ffh, DC_FF, row0, tid);
-  dc_linear<E, 512, 4>(A1, (const T*)P.wt[U3D_DL_FFN0], wv * 64, lane, acc_to_F());
+  dc_linear<E, 512, NTW>(A1, (const T*)P.wt[U3D_DL_FFN0], wv * WC, lane, acc_to_F());
   __syncthreads();
   DC_MARK(6);
   // ---- LN2 -> du2 (F) -------------------------------------------------------------------------------------------------------
@@ -364,7 +399,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
     dc_layernorm_bwd<E>(G, u_elem(S.upe1), S.mr, U3D_DLN_PE1, P.ln_g[U3D_DLN_PE1], P.ln_b[U3D_DLN_PE1], true, o, Gd.lnp, U3D_DLN_PE1, nb, red,
                         row0, wave, lane, tid);
   }
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_PE1], wv * 64, lane, to_G());
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_PE1], wv * WC, lane, to_G());
   __syncthreads();
   {
     // the first position-encoder layer's output is recomputed from the reference point (3 -> 256)
@@ -401,7 +436,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   // ---- output_proj, gate, trilinear scatter ------------------------------------------------------------------------------------
   branch_grad(1, A0, Gd.out);
   __syncthreads();
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_OPROJ], wv * 64, lane, to_G());      // d(gated) (T tensor)
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_OPROJ], wv * WC, lane, to_G());      // d(gated) (T tensor)
   __syncthreads();
   DC_MARK(9);
   {
@@ -480,7 +515,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_post_bwd(u3d_declayer_params
   dc_store_f<E>(F, Gd.du1, row0, tid);
   branch_grad(0, A0, Gd.o2);
   __syncthreads();
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_OUTP], wv * 64, lane, [=](int row, int col, f32x4 v) {
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_OUTP], wv * WC, lane, [=](int row, int col, f32x4 v) {
     *(V4*)(A1 + dc_aoff<E>(row, col, DC_C)) = E::pack4(v);              // A1 is free by now: d(attention output) leaves from the tile
   });
   __syncthreads();
@@ -627,7 +662,7 @@ __global__ __launch_bounds__(256, 2) void k_mha_bwd_dkv(const typename E::T* __r
         __syncthreads();
         H::stage(qk + h * DC_HD, 512, base, qc0, nq, Qs, Qt, tid);
         H::stage(d_o + h * DC_HD, 256, base, qc0, nq, Os, Ot, tid);
-        DC_FOR_TID(c, KC * NP) {                                // D[q] = dO[q] . O[q] over this head's 32 columns; lse[q]
+        MHA_FOR_TID(c, KC * NP) {                                // D[q] = dO[q] . O[q] over this head's 32 columns; lse[q]
           const int qq = c / NP, part = c % NP;
           float d = 0.f;
           if (qc0 + qq < nq) {
@@ -645,7 +680,7 @@ __global__ __launch_bounds__(256, 2) void k_mha_bwd_dkv(const typename E::T* __r
         }
         if constexpr (H::TR) {
           if (amask) {
-            DC_FOR_TID(c, KC * MW) Ms[c] = c < nq * MW ? amask[(size_t)bh * nq * MW + c] : 0u;
+            MHA_FOR_TID(c, KC * MW) Ms[c] = c < nq * MW ? amask[(size_t)bh * nq * MW + c] : 0u;
           }
         }
         __syncthreads();
@@ -721,7 +756,7 @@ extern "C" int32_t u3d_mha_bwd(const void* qk, const void* v, const void* o, con
 // k_dec_pre_bwd
 // ---------------------------------------------------------------------------------------------------------------------------
 template <typename E>
-__global__ __launch_bounds__(DC_THREADS) void k_dec_pre_bwd(u3d_declayer_params P, u3d_declayer_dims dm, DcSave<E> S, DcGrad<E> Gd,
+__global__ __launch_bounds__(E::NW * 64) void k_dec_pre_bwd(u3d_declayer_params P, u3d_declayer_dims dm, DcSave<E> S, DcGrad<E> Gd,
                                                             float* __restrict__ dx) {
   typedef typename E::T T;
   typedef typename E::V4 V4;
@@ -734,7 +769,8 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre_bwd(u3d_declayer_params 
   float* F = (float*)(lds + L::F);
   float* G = (float*)(lds + L::G);
   const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_id();
-  const int wv = (wave + (int)(blockIdx.x >> 3)) & 3;      // which 64 output columns this wave computes: rotated per workgroup (see dc_gemm)
+  constexpr int NTW = 16 / E::NW, WC = NTW * 16;           // MFMA column tiles / output columns a wave owns of a 256-wide linear
+  const int wv = (wave + (int)(blockIdx.x >> 3)) & (E::NW - 1);      // which WC output columns this wave computes: rotated per workgroup (see dc_gemm)
   const int row0 = blockIdx.x * BM, M = dm.m;
   dc_poison_lds<E>(lds, tid);
 
@@ -759,9 +795,9 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre_bwd(u3d_declayer_params 
     };
   };
   // gradient w.r.t. the q = k input (x + pos) -> G; it reaches x (F) and pos
-  dc_linear<E, 512, 4>(A1, (const T*)P.wt[U3D_DL_INQK], wv * 64, lane,
+  dc_linear<E, 512, NTW>(A1, (const T*)P.wt[U3D_DL_INQK], wv * WC, lane,
                        [=](int row, int col, f32x4 v) { *(f32x4*)(G + row * DC_TS + col) = E::round4(v); });
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_INV], wv * 64, lane, acc_to_F());
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_INV], wv * WC, lane, acc_to_F());
   __syncthreads();
   // dpos = d(q=k input) + gate path (post kernel); x gets d(q=k input) too.  d(raw), d(query_scale output) by the product rule.
   DC_FOR_TID(c, BM * 64) {
@@ -788,25 +824,25 @@ __global__ __launch_bounds__(DC_THREADS) void k_dec_pre_bwd(u3d_declayer_params 
   __syncthreads();
   T* A1b = A1 + BM * DC_C;
   if (dm.has_qs) {
-    dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_QS2], wv * 64, lane, masked_to(A1, S.qs2));
+    dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_QS2], wv * WC, lane, masked_to(A1, S.qs2));
     __syncthreads();
     dc_store_a<E, 256>(A1, Gd.qs2, DC_C, row0, tid);
-    dc_linear<E, 256, 4>(A1, (const T*)P.wt[U3D_DL_QS1], wv * 64, lane, masked_to(A1b, S.qs1));
+    dc_linear<E, 256, NTW>(A1, (const T*)P.wt[U3D_DL_QS1], wv * WC, lane, masked_to(A1b, S.qs1));
     __syncthreads();
     dc_store_a<E, 256>(A1b, Gd.qs1, DC_C, row0, tid);
-    dc_linear<E, 256, 4>(A1b, (const T*)P.wt[U3D_DL_QS0], wv * 64, lane, acc_to_F());
+    dc_linear<E, 256, NTW>(A1b, (const T*)P.wt[U3D_DL_QS0], wv * WC, lane, acc_to_F());
     __syncthreads();
   }
-  dc_linear<E, 256, 4>(A2, (const T*)P.wt[U3D_DL_RPH2], wv * 64, lane, masked_to(A0, S.rph2));
+  dc_linear<E, 256, NTW>(A2, (const T*)P.wt[U3D_DL_RPH2], wv * WC, lane, masked_to(A0, S.rph2));
   __syncthreads();
   dc_store_a<E, 256>(A0, Gd.rph2, DC_C, row0, tid);
-  dc_linear<E, 256, 4>(A0, (const T*)P.wt[U3D_DL_RPH1], wv * 64, lane, masked_to(A1, S.rph1));
+  dc_linear<E, 256, NTW>(A0, (const T*)P.wt[U3D_DL_RPH1], wv * WC, lane, masked_to(A1, S.rph1));
   __syncthreads();
   dc_store_a<E, 256>(A1, Gd.rph1, DC_C, row0, tid);
   if (dm.need_dref) {      // gradient w.r.t. the sine embedding [BM][384] -> slot (u3d_sine_embed_bwd turns it into d(logits))
     auto to_sine = [=](int row, int col, f32x4 v) { *(V4*)(Gd.sine + (size_t)(row0 + row) * 384 + col) = E::pack4(v); };
-    dc_linear<E, 256, 4>(A1, (const T*)P.wt[U3D_DL_RPH0], wv * 64, lane, to_sine);
-    dc_linear<E, 256, 2>(A1, (const T*)P.wt[U3D_DL_RPH0], 256 + wv * 32, lane, to_sine);
+    dc_linear<E, 256, NTW>(A1, (const T*)P.wt[U3D_DL_RPH0], wv * WC, lane, to_sine);
+    dc_linear<E, 256, NTW / 2>(A1, (const T*)P.wt[U3D_DL_RPH0], 256 + wv * (WC / 2), lane, to_sine);     // columns [256, 384): half a share
   }
   dc_store_f<E>(F, dx, row0, tid);
 }
@@ -837,25 +873,26 @@ static int32_t dcb_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_di
   const DcSave<E> S = dcb_resolve_save<E>(save, d->m);
   U3D_ALLOW_LDS(k_dec_post_bwd<E>, DcLds<E>::BYTES);
   U3D_ALLOW_LDS(k_dec_pre_bwd<E>, DcLds<E>::BYTES);
-  hipLaunchKernelGGL(k_dec_post_bwd<E>, dim3(G.nb), dim3(DC_THREADS), DcLds<E>::BYTES, s, *p, *d, ref, (const T*)value,
+  hipLaunchKernelGGL(k_dec_post_bwd<E>, dim3(G.nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, ref, (const T*)value,
                      (const unsigned long long*)rng, S, G, dx_out, dreg, dcls, diou, dvalue, dref);
   if (mha_fused_inproj(E::DT, d->nq) && d->p_attn > 0.f) {
     // the forward launch of this layer published its keep bits: the same decisions, read instead of hashed
     U3D_REQUIRE((long long)(d->m / d->nq) * DC_NHEAD * d->nq * (d->nq + 1) < (1ll << 32), U3D_ERR_UNSUPPORTED);
-    mha_bwd_launch<E>(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, s, S.amask);
+    mha_bwd_launch<typename E::ME>(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, s, S.amask);
   } else {
     int32_t rc = u3d_mha_bwd_dt(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, E::DT, s);
     if (rc != U3D_OK) return rc;
   }
-  hipLaunchKernelGGL(k_dec_pre_bwd<E>, dim3(G.nb), dim3(DC_THREADS), DcLds<E>::BYTES, s, *p, *d, S, G, dx);
+  hipLaunchKernelGGL(k_dec_pre_bwd<E>, dim3(G.nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, S, G, dx);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
 
-extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                         const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
-                                         const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                                         void* dvalue, float* dref, void* grad, int64_t grad_bytes, u3d_stream s) {
+// row_waves: as in u3d_decoder_layer_fwd_nw (it need not be the forward call's: the slots do not depend on it)
+extern "C" int32_t u3d_decoder_layer_bwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                            const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
+                                            const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
+                                            void* dvalue, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s) {
   (void)x; (void)xc; (void)xc_out;
   int32_t rc = dcb_check(p, d);
   if (rc != U3D_OK) return rc;
@@ -863,9 +900,19 @@ extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d
   U3D_REQUIRE(d->reserved == 0, U3D_ERR_ARG);
   U3D_REQUIRE(!d->need_dref || dref, U3D_ERR_ARG);
   U3D_REQUIRE((d->p_attn == 0.f && d->p_drop == 0.f) || rng, U3D_ERR_ARG);
+  U3D_REQUIRE(row_waves == 0 || row_waves == 4 || (row_waves == 8 && d->dtype == U3D_BF16), U3D_ERR_ARG);
+  if (d->dtype == U3D_BF16 && row_waves == 4)
+    return dcb_layer_bwd<EB4>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
   if (d->dtype == U3D_BF16)
     return dcb_layer_bwd<EB>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
   return dcb_layer_bwd<EF>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
+}
+extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                         const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
+                                         const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
+                                         void* dvalue, float* dref, void* grad, int64_t grad_bytes, u3d_stream s) {
+  return u3d_decoder_layer_bwd_nw(p, d, x, xc, ref, value, rng, xc_out, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes,
+                                  0, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,15 @@
 // Building blocks of the fused decoder-layer kernels (decoder.hip, decoder_bwd.hip): a block of rows of the layer state lives in LDS
-// through a whole chain of GEMMs / LayerNorms; weights stream from L2 straight into MFMA fragments (each wave owns 64 output
-// columns, so no two waves share a weight row and LDS staging of the weights would buy nothing).
+// through a whole chain of GEMMs / LayerNorms; weights stream from L2 straight into MFMA fragments (each of the E::NW waves owns
+// 256 / NW output columns, so no two waves share a weight row and LDS staging of the weights would buy nothing).
+// The tiles allow ONE workgroup per CU, so the wave count of the workgroup is the occupancy: the bf16 kernels run eight waves (two per
+// SIMD: while one wave waits for a weight burst, an LDS pass or a DPP chain, the other issues).  The wave count only deals columns and
+// rows to waves - no reduction changes its order, results are bit-identical (EB4, tests/test_decoder_waves_gpu.py).
 //
 // Every kernel is a template over an ELEMENT TRAIT E - the storage type of activations / weights / slots and the MFMA that consumes
-// them - and is instantiated twice:
-//   EB  bf16 storage, v_mfma_f32_16x16x32_bf16, 32 rows per workgroup            (throughput mode, U3D_BF16)
-//   EF  f32 storage,  v_mfma_f32_16x16x4_f32 (bitwise an fma chain), 16 rows     (parity mode, U3D_F32: the 1e-3 reference goldens)
+// them - and is instantiated on:
+//   EB  bf16 storage, v_mfma_f32_16x16x32_bf16, 32 rows per workgroup, 8 waves   (throughput mode, U3D_BF16)
+//   EB4 the same at 4 waves (row-chain kernels only; row_waves = 4 of u3d_decoder_layer_fwd_nw / _bwd_nw)
+//   EF  f32 storage,  v_mfma_f32_16x16x4_f32 (bitwise an fma chain), 16 rows, 4 waves   (parity mode, U3D_F32: the 1e-3 reference goldens)
 // Same source, same launch structure, same slot layout (element size aside): what the parity tests exercise IS the benchmarked code.
 //
 // MFMA orientation: D^T = W . X^T, i.e. a-operand = weight rows (lane l: row n = l&15, one 16-byte chunk of k at chunk (l>>4)),
@@ -22,7 +26,7 @@ typedef unsigned short u16;
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
-#define DC_THREADS 256
+#define MHA_THREADS 256       /* the attention kernels: four waves, two workgroups per CU */
 #define DC_C 256              /* embed dim */
 #define DC_FF 512             /* FFN hidden */
 #define DC_TS 260             /* row stride (floats) of the f32 tiles: 8-lane store groups land on distinct banks */
@@ -61,9 +65,11 @@ struct EB {                    // bf16 storage
   typedef u16 T;
   typedef u16x4 V4;            // 4 consecutive elements (a lane's share of one MFMA output row)
   typedef u16x8 VC;            // one 16-byte chunk
+  typedef EB ME;               // the trait the attention kernels (k_mha_*) are instantiated on
   static constexpr int CH = 8;        // elements per 16-byte chunk
   static constexpr int BM = 32;       // rows per workgroup of the row-chain kernels
   static constexpr int MT = 2;        // 16-row MFMA tiles per workgroup
+  static constexpr int NW = 8;        // waves per workgroup of the row-chain kernels: two per SIMD (the tiles allow ONE workgroup per CU)
   static constexpr int KSTEP = 32;    // reduction elements per dc_gemm step (4 chunk columns, one per 16-lane group)
   static constexpr int DT = U3D_BF16;
   static constexpr int MHA_KC = 320;  // rows per LDS chunk of the attention kernels: a 300-query group is ONE chunk
@@ -87,13 +93,17 @@ struct EB {                    // bf16 storage
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
   }
 };
+// the bf16 row-chain kernels at one wave per SIMD: the A/B partner of EB (fused_decoder.ROW_WAVES = 4), bit-identical results
+struct EB4 : EB { static constexpr int NW = 4; };
 struct EF {                    // f32 storage, exact-f32 MFMA
   typedef float T;
   typedef f32x4 V4;
   typedef f32x4 VC;
+  typedef EF ME;
   static constexpr int CH = 4;
   static constexpr int BM = 16;
   static constexpr int MT = 1;
+  static constexpr int NW = 4;
   static constexpr int KSTEP = 16;
   static constexpr int DT = U3D_F32;
   static constexpr int MHA_KC = 64;
@@ -189,6 +199,12 @@ struct DcDrop {
 #ifndef DC_PF
 #define DC_PF 8
 #endif
+// Burst depth of the eight-wave instantiation.  Half the column tiles per wave leave room for twice the depth (the same bytes in
+// flight per wave as at four waves); measured with -DDC_PF_NW8="(2*DC_PF)" it bought nothing - k_dec_post 73.0 against 72.7 us,
+// k_dec_post_bwd 81.3 / 79.8, k_dec_pre 31.6 / 31.3, k_dec_pre_bwd 34.4 / 33.2 - so the depth stays.
+#ifndef DC_PF_NW8
+#define DC_PF_NW8 DC_PF
+#endif
 constexpr int dc_burst(int ks, int want) {          // largest divisor of ks that is <= want
   int b = 1;
   for (int d = 1; d <= want && d <= ks; ++d)
@@ -200,7 +216,7 @@ __device__ __forceinline__ void dc_gemm(const typename E::T* A, const typename E
   typedef typename E::T T;
   typedef typename E::VC VC;
   constexpr int KS = K / E::KSTEP;
-  constexpr int PF = dc_burst(KS, DC_PF);
+  constexpr int PF = dc_burst(KS, E::NW == 8 ? DC_PF_NW8 : DC_PF);
   static_assert((K / E::CH) % 16 == 0, "the chunk swizzle permutes aligned groups of 16 chunks");
 #ifdef DC_ABL_NOGEMM
   return;
@@ -285,7 +301,9 @@ __device__ __forceinline__ f32x4 dc_relu4(f32x4 v) {
 // register-allocator copies (v_accvgpr_write) in the exit block of an exec-masked `for (i = tid; i < N; i += 256)` loop AHEAD of the
 // `s_or_b64 exec` that restores the lane mask - the copies ran with EXEC = 0 and the "saved" LDS addresses were garbage afterwards
 // (tools/check_exec_restore.py scans the ISA for that pattern; tests/test_build_cpu.py runs it).
-#define DC_FOR_TID(c, N) _Pragma("unroll") for (int it_ = 0, c = tid; it_ < (N) / DC_THREADS; ++it_, c += DC_THREADS)
+// DC_FOR_TID: the row-chain kernels (E::NW waves, E in scope); MHA_FOR_TID: the attention kernels (MHA_THREADS).
+#define DC_FOR_TID(c, N) _Pragma("unroll") for (int it_ = 0, c = tid; it_ < (N) / (E::NW * 64); ++it_, c += E::NW * 64)
+#define MHA_FOR_TID(c, N) _Pragma("unroll") for (int it_ = 0, c = tid; it_ < (N) / MHA_THREADS; ++it_, c += MHA_THREADS)
 __device__ __forceinline__ int dc_wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ---- tile movers ------------------------------------------------------------------------------------------------------------
@@ -294,7 +312,7 @@ template <typename E, int K, bool CLAMP>
 __device__ __forceinline__ void dc_load_a(typename E::T* A, const typename E::T* __restrict__ src, int ld, int row0, int M, int tid) {
   typedef typename E::VC VC;
   constexpr int CPR = K / E::CH;
-  static_assert((E::BM * CPR) % DC_THREADS == 0, "tile chunks must split evenly over the workgroup");
+  static_assert((E::BM * CPR) % (E::NW * 64) == 0, "tile chunks must split evenly over the workgroup");
   DC_FOR_TID(c, E::BM * CPR) {
     const int row = c / CPR, ch = c % CPR;
     const int gr = CLAMP ? min(row0 + row, M - 1) : row0 + row;
@@ -340,6 +358,7 @@ __device__ __forceinline__ void dc_store_f(const float* T, float* __restrict__ d
 }
 
 // ---- LayerNorm over the 256 columns of an f32 tile: wave w owns rows RPW*w .. RPW*w + RPW-1, a lane 4 consecutive columns ------
+// (a row stays with ONE wave whatever E::NW is: every row reduction keeps its order)
 template <typename E>
 struct DcLnOut {
   float* tile;                 // f32 tile to receive y (may alias the input tile), or null
@@ -356,7 +375,7 @@ template <typename E>
 __device__ __forceinline__ void dc_layernorm(const float* T, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                              bool relu, const DcLnOut<E>& o, int row0, int wave, int lane) {
   typedef typename E::V4 V4;
-  constexpr int RPW = E::BM / 4;
+  constexpr int RPW = E::BM / E::NW;
   const f32x4 ga = *(const f32x4*)(gamma + lane * 4), be = *(const f32x4*)(beta + lane * 4);
 #pragma unroll 2
   for (int rr = 0; rr < RPW; ++rr) {
@@ -419,12 +438,12 @@ __device__ __forceinline__ void dc_corners(const float* ref3, int b, int D, int 
 template <typename E>
 __device__ __forceinline__ void dc_poison_lds(unsigned char* lds, int tid) {
 #if DC_POISON_LDS == 1
-  for (int i = tid; i < DcLds<E>::BYTES / 4; i += DC_THREADS) ((unsigned*)lds)[i] = 0xFFFFFFFFu;
+  for (int i = tid; i < DcLds<E>::BYTES / 4; i += E::NW * 64) ((unsigned*)lds)[i] = 0xFFFFFFFFu;
   __syncthreads();
 #elif DC_POISON_LDS == 2
   __syncthreads();
 #elif DC_POISON_LDS == 3
-  for (int i = tid; i < DcLds<E>::BYTES / 4; i += DC_THREADS) ((unsigned*)lds)[i] = 0xFFFFFFFFu;
+  for (int i = tid; i < DcLds<E>::BYTES / 4; i += E::NW * 64) ((unsigned*)lds)[i] = 0xFFFFFFFFu;
 #endif
 }
 
@@ -466,7 +485,7 @@ struct Mha {
   // stage KC rows (head slice) of a row matrix into LDS: the row-major image and (EF) the transposed copy
   __device__ static __forceinline__ void stage(const T* __restrict__ src, int ld, long long base_row, int first, int nvalid, T* rowmajor,
                                                T* transposed, int tid) {
-    DC_FOR_TID(c, KC * NP) {
+    MHA_FOR_TID(c, KC * NP) {
       const int key = c / NP, part = c % NP;
       VC v = E::zero_chunk();
       if (first + key < nvalid) v = *(const VC*)(src + (base_row + first + key) * ld + part * E::CH);

@@ -1849,8 +1849,9 @@ def decoder_rows(m, dtype=torch.bfloat16):
     return decoder_blocks(m, dtype) * (32 if dtype == torch.bfloat16 else 16)
 
 
-def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save):
-    """xc / value_rows / the slots are in the element type dims.dtype names (bf16 | f32); in f32 mode xc_out IS x_out."""
+def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save, row_waves=0):
+    """xc / value_rows / the slots are in the element type dims.dtype names (bf16 | f32); in f32 mode xc_out IS x_out.
+    row_waves: waves per workgroup of the row-chain kernels (8: bf16 only | 4 | 0 = the element type's default); same bits either way."""
     m, code, ncls = dims.m, dims.code, dims.ncls
     et = torch.bfloat16 if dims.dtype == DT_BF16 else torch.float32
     assert xc.dtype == et and value_rows.dtype == et and x.dtype == torch.float32
@@ -1861,13 +1862,13 @@ def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save):
     reg = torch.empty((mp, code), dtype=torch.float32, device=dev)
     cls = torch.empty((mp, ncls), dtype=torch.float32, device=dev)
     iou = torch.empty((mp,), dtype=torch.float32, device=dev)
-    _check(lib().u3d_decoder_layer_fwd(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
-                                       _ptr(x_out), _ptr(xc_out), _ptr(reg), _ptr(cls), _ptr(iou), _ptr(save), save.numel(), _stream()),
-           "decoder_layer_fwd")
+    _check(lib().u3d_decoder_layer_fwd_nw(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
+                                          _ptr(x_out), _ptr(xc_out), _ptr(reg), _ptr(cls), _ptr(iou), _ptr(save), save.numel(),
+                                          int(row_waves), _stream()), "decoder_layer_fwd")
     return x_out[:m], xc_out[:m], reg[:m], cls[:m], iou[:m]
 
 
-def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad):
+def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad, row_waves=0):
     """dvalue: f32 [rows, 256] accumulator, or (bf16 kernels only) a bf16 one: the layer's value-volume gradient is ADDED to it, summed
     per cell in a fixed order (value_scatter: bitwise reproducible)."""
     m = dims.m
@@ -1877,9 +1878,10 @@ def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, d
     mp = decoder_rows(m, torch.bfloat16 if dims.dtype == DT_BF16 else torch.float32)
     dx = torch.empty((mp, 256), dtype=torch.float32, device=ref.device)
     dref = torch.empty((mp, 3), dtype=torch.float32, device=ref.device) if dims.need_dref else None
-    _check(lib().u3d_decoder_layer_bwd(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
-                                       _ptr(xc_out), _ptr(save), _ptr(dx_out), _ptr(dreg), _ptr(dcls), _ptr(diou), _ptr(dx),
-                                       _ptr(rec), _ptr(dref), _ptr(grad), grad.numel(), _stream()), "decoder_layer_bwd")
+    _check(lib().u3d_decoder_layer_bwd_nw(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
+                                          _ptr(xc_out), _ptr(save), _ptr(dx_out), _ptr(dreg), _ptr(dcls), _ptr(diou), _ptr(dx),
+                                          _ptr(rec), _ptr(dref), _ptr(grad), grad.numel(), int(row_waves), _stream()),
+           "decoder_layer_bwd")
     value_scatter(rec, m, dvalue)
     return dx[:m], (None if dref is None else dref[:m])
 

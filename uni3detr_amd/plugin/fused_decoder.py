@@ -28,6 +28,9 @@ SHARED_DEFER = True     # test-only module attribute: shared linears' gradients 
 PK_SCATTER = os.environ.get("U3D_PK_SCATTER", "0") == "1"
 POISON = os.environ.get("U3D_DEC_POISON", "0") == "1"      # debugging: NaN-fill the workspaces (read-before-write shows up as NaN)
 DEBUG_KEEP = None          # tests: a list that receives every backward call's gradient workspace
+# waves per workgroup of the bf16 row-chain kernels (k_dec_pre / k_dec_post and their backward), passed down every call: 8 = two waves
+# per SIMD, 4 = one (the comparison partner: same bits, tests/test_decoder_waves_gpu.py).  The f32 kernels always run four.
+ROW_WAVES = 8
 
 # (enum index, rows of the weight that belong to this linear) for the wide linears; narrow finals are padded
 _WIDE = [nv.DL_RPH0, nv.DL_RPH1, nv.DL_RPH2, nv.DL_QS0, nv.DL_QS1, nv.DL_QS2, nv.DL_INQK, nv.DL_INV, nv.DL_OUTP, nv.DL_OPROJ, nv.DL_PE1,
@@ -250,7 +253,8 @@ class FusedLayerFn(torch.autograd.Function):
         if POISON:
             save.fill_(255)
         params = fd._states[et].params[lid]
-        x_out, xc_out, reg, cls, iou = nv.decoder_layer_fwd(params, d, x, xc, ref, rows, fd.rng, save)
+        ctx.row_waves = ROW_WAVES if et == torch.bfloat16 else 4
+        x_out, xc_out, reg, cls, iou = nv.decoder_layer_fwd(params, d, x, xc, ref, rows, fd.rng, save, ctx.row_waves)
         ctx.save_for_backward(x, xc, ref, rows, xc_out, save)
         ctx.meta, ctx.dims, ctx.et, ctx.params = meta, d, et, params
         ctx.wids = []
@@ -297,7 +301,8 @@ class FusedLayerFn(torch.autograd.Function):
             dvalue = accum.buf
         else:
             dvalue = torch.zeros(rows.shape, dtype=acc_dt, device=dev)
-        dx, dref = nv.decoder_layer_bwd(ctx.params, d, x, xc, ref, rows, fd.rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad)
+        dx, dref = nv.decoder_layer_bwd(ctx.params, d, x, xc, ref, rows, fd.rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad,
+                                        ctx.row_waves)
         if DEBUG_KEEP is not None:
             DEBUG_KEEP.append(grad)
         drows = None
