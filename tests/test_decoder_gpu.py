@@ -437,6 +437,72 @@ def test_fused_layer_backward_is_deterministic(cuda, lid):
         fdm.DEBUG_KEEP = None
 
 
+def _two_layer_param_grads(cuda, head, fd, et, scope, shared_defer):
+    """Layers 0 and 1 chained as fused_decoder.run chains them (ref_point_head is used by both, query_scale by layer 1 only), M = 40
+    rows, one backward; -> {parameter name: gradient} over both layers' tensor_list."""
+    import contextlib
+    from uni3detr_amd.plugin import fused_decoder as fdm
+    from uni3detr_amd.plugin import transformer as T
+    B, nq, D, H, W = 1, 40, 3, 4, 5                  # the shapes of tests/test_decoder_waves_gpu.py
+    g = torch.Generator(device="cpu").manual_seed(23)
+    x = (torch.randn(B * nq, 256, generator=g) * 0.7).to(cuda).requires_grad_(True)
+    ref = (torch.randn(B * nq, 3, generator=g) * 1.2).to(cuda)
+    rows = torch.randn(B * D * H * W, 256, generator=g).to(cuda).to(et)
+    fd.refresh(cuda, et)
+    fd.rng.fill_(0x2545F4914F6C)
+    T.reset_param_uses()
+    outs, xc = [], None
+    for lid in (0, 1):
+        x, xc, reg, cls, iou = fdm.FusedLayerFn.apply(x, xc, ref, rows, (fd, lid, (B, nq, nq, D, H, W), None, et), *fdm.tensor_list(fd.specs[lid]))
+        ref = ref + reg.detach()[:, [0, 1, 4]]
+        outs += [x, reg, cls, iou]
+    loss = sum((o * torch.randn(o.shape, generator=g).to(cuda)).sum() for o in outs)
+    head.zero_grad(set_to_none=True)
+    old = fdm.SHARED_DEFER
+    fdm.SHARED_DEFER = shared_defer
+    try:
+        with (T.deferred_param_grads() if scope else contextlib.nullcontext()):
+            loss.backward()
+    finally:
+        fdm.SHARED_DEFER = old
+    names = {id(p): n for n, p in head.named_parameters()}
+    params = dict.fromkeys(t for lid in (0, 1) for t in fdm.tensor_list(fd.specs[lid]))
+    return {names[id(p)]: p.grad.clone() for p in params}
+
+
+@pytest.mark.parametrize("mode", ["bf16", "f32", "f32_split"])
+def test_parameter_gradients_do_not_depend_on_the_route(cuda, mode):
+    """Every parameter gradient of two chained fused layers computed (a) outside a deferred scope, (b) inside one, (c) inside one with
+    SHARED_DEFER off, under POISON (a placeholder nobody writes is NaN).  M = 40: one full 32-row block plus a partial one, so the
+    LayerNorm block partials and a linear shared by two layers (ref_point_head) both occur.
+    Measured before the route moved into plugin/param_grads.py: f32 and f32_split - all 108 gradients torch.equal in (a), (b), (c);
+    bf16 - (c) torch.equal to (a), (b) torch.equal but for ref_point_head.layers.2.bias at relative L2 1.3424e-08 (the batched launch
+    adds the two uses' column sums in another order than autograd adds two finished sums).  That one is held to twice the figure
+    (run-to-run slack of an order-dependent f32 sum), everything else to torch.equal."""
+    from uni3detr_amd.plugin import fused_decoder as fdm
+    et = torch.bfloat16 if mode == "bf16" else torch.float32
+    head = make_head(cuda, 7)
+    head.transformer.decoder.split_f32_wgrad = mode == "f32_split"
+    fd = fdm.FusedDecoder(head.transformer.decoder, head.reg_branches, head.cls_branches, head.iou_branches)
+    for sp in fd.specs:
+        sp.p_attn = sp.p_drop = 0.0
+    fdm.POISON = True
+    try:
+        a, b, c = (_two_layer_param_grads(cuda, head, fd, et, scope, shared) for scope, shared in ((False, True), (True, True), (True, False)))
+    finally:
+        fdm.POISON = False
+    assert len(a) == 108 and set(a) == set(b) == set(c)
+    bound = {("bf16", "b", "transformer.decoder.ref_point_head.layers.2.bias"): 2 * 1.3424e-08}
+    differ = {}
+    for tag, other in (("b", b), ("c", c)):
+        for n, ga in a.items():
+            assert bool(torch.isfinite(ga).all()) and bool(torch.isfinite(other[n]).all()), (mode, tag, n)
+            if not torch.equal(ga, other[n]):
+                differ[(mode, tag, n)] = rel(other[n], ga)
+    print(f"\n[param grad routes] {mode}: differing from (a): {differ}")
+    assert all(e <= bound.get(key, 0.0) for key, e in differ.items()), differ
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # U3D_F32 instantiation of the SAME kernels (csrc/decoder_common.h: element trait EF, exact v_mfma_f32_16x16x4_f32): the parity-grade
 # decoder.  Tolerances: 2e-5 relative L2 forward and on gradients (measured ~1e-6) - f32 arithmetic against torch's f32 ops, no storage rounding.

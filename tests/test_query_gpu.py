@@ -418,7 +418,7 @@ def test_safe_linear_and_in_proj_backward_match_torch(cuda, amp, defer):
     with (T.deferred_param_grads() if defer else contextlib.nullcontext()):
         ((y.float() * gy).sum() + (qkp.float() * gq).sum() + (v.float() * gv).sum()).backward()
         if defer:
-            assert len(T._Deferred.items) == 3                 # linear + the two halves of the packed in-projection
+            assert len(T.PG.QUEUE.products) == 3                # linear + the two halves of the packed in-projection
     assert lin.weight.grad.dtype == torch.float32 and mha.in_proj_weight.grad.shape == (3 * C, C)
     assert rel(lin.weight.grad, wl.grad) <= tol and rel(lin.bias.grad, bl.grad) <= tol
     assert rel(mha.in_proj_weight.grad, wi.grad) <= tol and rel(mha.in_proj_bias.grad, bi.grad) <= tol
@@ -581,7 +581,7 @@ def test_narrow_linear_bias_sum_is_deferred_and_correct(cuda, nout, kin):
         y = T.fast_linear(x2, lin)
     with T.deferred_param_grads():
         (y.float() * gy).sum().backward()
-        assert any(p is lin.bias for _, p in T._Deferred.sum_items)          # queued, not computed on the spot
+        assert any(p is lin.bias for _, p in T.PG.QUEUE.sums)          # queued, not computed on the spot
     rel = lambda a, b: (a.float() - b.float()).abs().max().item() / max(1.0, b.abs().max().item())
     assert rel(lin.bias.grad, br.grad) <= 3e-2 and rel(lin.weight.grad, wr.grad) <= 3e-2 and rel(x2.grad, xr.grad) <= 3e-2
 

@@ -11,7 +11,7 @@ models/dense_heads/uni3detr_head.py:367-387, 470-490 (branches; the box decode s
 
 The module layout is the registry's (plugin/transformer.py, plugin/head.py): this file only gathers the parameters, keeps bf16
 copies of the weights (one refresh launch per step: u3d_wpack_bf16) and turns the kernels' gradient slots into parameter
-gradients through the same deferred / batched mechanism the layer-by-layer path uses (plugin/transformer.py `_Deferred`).
+gradients through the same deferred / batched mechanism the layer-by-layer path uses (plugin/param_grads.py).
 """
 import os
 
@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from .. import native as nv
+from . import param_grads as PG
 
 ENABLED = True         # test-only module attribute: the GPU tests set it False to run the layer-by-layer formulation next to the fused one
 # value-volume gradient accumulated over the decoder layers in a bf16 buffer instead of an f32 one (no f32 volume to zero and cast).
@@ -32,10 +33,7 @@ DEBUG_KEEP = None          # tests: a list that receives every backward call's g
 # per SIMD, 4 = one (the comparison partner: same bits, tests/test_decoder_waves_gpu.py).  The f32 kernels always run four.
 ROW_WAVES = 8
 
-# (enum index, rows of the weight that belong to this linear) for the wide linears; narrow finals are padded
-_WIDE = [nv.DL_RPH0, nv.DL_RPH1, nv.DL_RPH2, nv.DL_QS0, nv.DL_QS1, nv.DL_QS2, nv.DL_INQK, nv.DL_INV, nv.DL_OUTP, nv.DL_OPROJ, nv.DL_PE1,
-         nv.DL_FFN0, nv.DL_FFN1, nv.DL_REG0, nv.DL_REG1, nv.DL_CLS0, nv.DL_CLS1, nv.DL_IOU0, nv.DL_IOU1]
-_NARROW = [nv.DL_REG2, nv.DL_CLS2, nv.DL_IOU2]
+_NARROW = [nv.DL_REG2, nv.DL_CLS2, nv.DL_IOU2]          # the branches' narrow final linears (their weight copies are padded)
 
 
 def _is_seq(seq, kinds):
@@ -105,16 +103,6 @@ class LayerSpec:
             raise ValueError("dropout layout")
         self.p_drop, self.p_attn = ps.pop(), float(sa.attn_drop)
         self.modules = (sa, ca, ffn)
-
-    def tensors(self):
-        """Flat list of the parameter tensors handed to autograd (order fixed: see FusedLayerFn.backward)."""
-        out = []
-        for w, _, _, b in self.lin:
-            out += [w, b]
-        for n in self.ln:
-            out += [n.weight, n.bias]
-        out += [self.attw.weight, self.attw.bias, self.pe0.weight, self.pe0.bias]
-        return out
 
 
 class FusedDecoder:
@@ -192,7 +180,7 @@ class FusedDecoder:
     def refresh(self, dev, et=torch.bfloat16):
         """Copies of the current master weights in the element type `et` (one launch); rebuilt when a parameter moved (e.g. into the
         trainer's flat buffer).  bf16: rounded copies; f32: the zero-padded / transposed layouts the kernels read."""
-        key = (str(dev),) + tuple(t.data_ptr() for sp in self.specs for t in sp.tensors())
+        key = (str(dev),) + tuple(t.data_ptr() for sp in self.specs for t in tensor_list(sp))
         st = self._states.get(et)
         if st is None or st.key != key:
             st = self._states[et] = self._build(dev, et)
@@ -257,17 +245,11 @@ class FusedLayerFn(torch.autograd.Function):
         x_out, xc_out, reg, cls, iou = nv.decoder_layer_fwd(params, d, x, xc, ref, rows, fd.rng, save, ctx.row_waves)
         ctx.save_for_backward(x, xc, ref, rows, xc_out, save)
         ctx.meta, ctx.dims, ctx.et, ctx.params = meta, d, et, params
-        ctx.wids = []
-        from .transformer import _Deferred
         for w, r0, rows_, b in sp.lin:
-            if r0 == 0:
-                _Deferred.uses[id(w)] = _Deferred.uses.get(id(w), 0) + 1
-                _Deferred.fused_uses[id(w)] = _Deferred.fused_uses.get(id(w), 0) + 1
-                _Deferred.params[id(w)] = (w, b)
-        for t in (sp.attw.weight, sp.pe0.weight):
-            _Deferred.uses[id(t)] = _Deferred.uses.get(id(t), 0) + 1
-        for n in sp.ln:
-            _Deferred.uses[id(n.weight)] = _Deferred.uses.get(id(n.weight), 0) + 1
+            if r0 == 0:                                          # the packed in-projection once, not per half
+                PG.USES.note(w, b, fused=True)
+        for mod in (sp.attw, sp.pe0, *sp.ln):
+            PG.USES.note(mod.weight, mod.bias)
         # f32 mode: the layer state IS its own compute copy (xc_out aliases x_out inside): hand autograd an empty stand-in instead of
         # two outputs over one storage; the next layer takes its x as xc
         xc_ret = xc_out if et == torch.bfloat16 else x_out.new_empty(0)
@@ -276,7 +258,6 @@ class FusedLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx_out, _dxc, dreg, dcls, diou):
-        from .transformer import _Deferred
         x, xc, ref, rows, xc_out, save = ctx.saved_tensors
         fd, lid, dims_t, accum = ctx.meta[:4]
         et = ctx.et
@@ -332,18 +313,14 @@ class FusedLayerFn(torch.autograd.Function):
         }
         if lid > 0:
             pairs.update({nv.DL_QS0: (Gv("QS1", 256), xc), nv.DL_QS1: (Gv("QS2", 256), S("QS1", 256)), nv.DL_QS2: (Gv("QS", 256), S("QS2", 256))})
-        # the deferred / batched parameter-gradient launches are bf16 kernels; parity mode computes every product right here on the
-        # exact-f32 weight-gradient kernel (u3d_spconv_wgrad, one offset)
-        deferred_ok = _Deferred.active and et == torch.bfloat16
+        # ---- one route per parameter (param_grads.fused_route), then dispatch -------------------------------------------------------
         # `parity` precision (f32 layer, split-bf16 products elsewhere in the model): the wide dY^T X products as THREE bf16 products of
-        # hi / lo planes (dyh.xh + dyl.xh + dyh.xl, f32 accumulation, ~2^-16 relative) in the batched bf16 weight-gradient launch -
-        # consecutive batch slots with one output are summed by the kernel.  54 launches of the exact-f32 kernel (2.7 ms per step: it
-        # walks 7 200 rows on one offset) become one launch per shape.
-        split_wg = et == torch.float32 and getattr(fd.decoder, "split_f32_wgrad", False)
-        planes = {}
+        # hi / lo planes (dyh.xh + dyl.xh + dyh.xl, f32 accumulation, ~2^-16 relative) in the batched bf16 weight-gradient launch, which
+        # sums consecutive batch slots with one output: one launch per shape instead of 54 of the exact-f32 kernel (2.7 ms per step).
+        split_wg = et == f32 and getattr(fd.decoder, "split_f32_wgrad", False)
         # every tensor that needs planes is split by ONE launch (u3d_split_rows_batch, strided slot views read in place) right before the
         # batched weight-gradient launch that consumes them: a copy + a u3d_split_rows_f32 launch per tensor was ~90 launches per step
-        to_split = []
+        planes, to_split = {}, []
         ok = lambda t: t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0      # noqa: E731
 
         def hi_lo(t):
@@ -354,103 +331,57 @@ class FusedLayerFn(torch.autograd.Function):
                 to_split.append((t2, pl))
                 planes[key] = (t, pl[:t2.shape[0]], pl[t2.shape[0]:])
             return planes[key][1], planes[key][2]
-        grads = []
-        wgrad_now = {}              # (n, k) -> list of (dy, x, out)
-        sums_now = []               # (matrix, out vector)
-        new = lambda *shape: torch.empty(shape, dtype=f32, device=dev)
 
-        def slot(param, deferred):
-            """Gradient tensor handed to autograd for `param`: under TrainStep, when the value is written later by the flush (so
-            nothing else accumulates into it), the parameter's own slice of the flat gradient buffer - the step's packing copy then
-            has nothing to move for it; else a fresh tensor."""
-            v = getattr(param, "_u3d_grad_view", None) if deferred else None
+        def slot(param, grad_view):
+            """Gradient tensor handed to autograd for `param`: under TrainStep, when only the flush writes it later, the parameter's own
+            slice of the flat gradient buffer - the step's packing copy then has nothing to move for it; else a fresh tensor."""
+            v = getattr(param, "_u3d_grad_view", None) if grad_view else None
             # (a fresh alias: AccumulateGrad keeps an incoming tensor as .grad only if nobody else holds that tensor object)
-            return v.view(v.shape) if (v is not None and v.dtype == f32 and v.is_contiguous()) else new(*param.shape)
+            return v.view(v.shape) if (v is not None and v.dtype == f32 and v.is_contiguous()) else torch.empty(param.shape, dtype=f32, device=dev)
 
-        def skinny_now(dy, xin, dw):
-            """dW = dY^T X for a product with a side <= 16, written into dw ([n, k] view)"""
-            if et == torch.bfloat16:
-                sums_now.append((nv.skinny_wgrad_partial(dy, xin), dw.view(-1)))
-            else:
-                dw.copy_(_wgrad_f32(dy, xin))
-        inproj_dw = inproj_db = None
-        for i, (w, r0, rows_, b) in enumerate(sp.lin):
-            if i not in pairs:                                   # query_scale in the first layer: unused
-                grads += [None, None]
-                continue
-            dy, xin = pairs[i]
-            n, k = rows_, w.shape[1]
-            if i in (nv.DL_INQK, nv.DL_INV):
-                if inproj_dw is None:
-                    dfr = deferred_ok and _Deferred.uses.get(id(w), 0) == 1
-                    inproj_dw, inproj_db = slot(w, dfr), slot(b, dfr)
-                dw, db = inproj_dw[r0:r0 + rows_], inproj_db[r0:r0 + rows_]
-            else:
-                dfr = deferred_ok and _Deferred.uses.get(id(w), 0) == 1
-                dw, db = slot(w, dfr), slot(b, dfr)
-            single = _Deferred.uses.get(id(w), 0) == 1
-            # a linear SHARED by several layers (ref_point_head, query_scale) whose every use is a fused layer: all its (dY, X) pairs are
-            # queued and the flush sums them into ONE gradient (consecutive batch slots with one output, u3d_wgrad_batched_bf16) - the
-            # first backward to get here hands autograd the placeholder, the others contribute None instead of a tensor to be added
-            shared = (SHARED_DEFER and deferred_ok and not single and i not in _NARROW and i not in (nv.DL_INQK, nv.DL_INV)
-                      and _Deferred.fused_uses.get(id(w), 0) == _Deferred.uses.get(id(w), 0))
-            if shared:
-                if id(w) in _Deferred.shared_seen:
-                    dw = db = None
-                else:
-                    _Deferred.shared_seen.add(id(w))
-                    dw, db = slot(w, True), slot(b, True)
-                _Deferred.items.append((dy, xin, id(w), r0, r0 + rows_, True))
-                grads += [dw, db]
-                continue
-            if i in _NARROW:
-                if deferred_ok and single:
-                    _Deferred.skinny.append((dy, xin, w))        # the product itself waits for the flush: one launch for all layers
-                    _Deferred.sum_items.append((dy, b))
-                else:
-                    skinny_now(dy, xin, dw)
-                    sums_now.append((dy, db))
-            elif deferred_ok and single:
-                _Deferred.items.append((dy, xin, id(w), r0, r0 + rows_, True))
-            elif et == torch.bfloat16:
-                wgrad_now.setdefault((n, k), []).append((dy, xin, dw))
-                sums_now.append((dy, db))
-            elif split_wg and n % 64 == 0 and k % 64 == 0:
-                (dyh, dyl), (xh, xl) = hi_lo(dy), hi_lo(xin)
-                wgrad_now.setdefault((n, k), []).extend([(dyh, xh, dw), (dyl, xh, dw), (dyh, xl, dw)])
-                sums_now.append((dy, db))
-            else:
-                dw.copy_(_wgrad_f32(dy, xin))
-                sums_now.append((dy, db))
-            if i == nv.DL_INV:
-                grads += []                                      # in_proj weight / bias were emitted with INQK
-            elif i == nv.DL_INQK:
-                grads += [inproj_dw, inproj_db]
-            else:
-                grads += [dw, db]
+        # (kind, weight, bias, first row, rows, dY, X) in the order of tensor_list; a LayerNorm's block partials stand for (dY, X)
+        kind_of = lambda i: "inproj" if i in (nv.DL_INQK, nv.DL_INV) else "narrow" if i in _NARROW else "wide"      # noqa: E731
+        entries = [(kind_of(i), w, b, r0, n) + pairs.get(i, (None, None)) for i, (w, r0, n, b) in enumerate(sp.lin)]
         nb = nv.decoder_blocks(M, et)
         lnp = nv.slot_view(grad, go["LNP"], nv.DL_NLN * 2 * nb, 256, f32)
-        for j, nmod in enumerate(sp.ln):
-            dfr = deferred_ok and _Deferred.uses.get(id(nmod.weight), 0) == 1
-            dg, db = slot(nmod.weight, dfr), slot(nmod.bias, dfr)
-            mg, mb = lnp[(2 * j) * nb:(2 * j + 1) * nb], lnp[(2 * j + 1) * nb:(2 * j + 2) * nb]
-            if deferred_ok and _Deferred.uses.get(id(nmod.weight), 0) == 1:
-                _Deferred.sum_items += [(mg, nmod.weight), (mb, nmod.bias)]
-            else:
-                sums_now += [(mg, dg), (mb, db)]
-            grads += [dg, db]
+        entries += [("norm", m.weight, m.bias, 0, 256, lnp[2 * j * nb:(2 * j + 1) * nb], lnp[(2 * j + 1) * nb:(2 * j + 2) * nb])
+                    for j, m in enumerate(sp.ln)]
         # attention_weights (256 -> 1) and the position encoder's first layer (3 -> 256): skinny products
-        for dy, xin, mod in ((Gv("WL", 1), S("QP", 256), sp.attw), (Gv("P0", 256), ref.to(et), sp.pe0)):
-            dfr = deferred_ok and _Deferred.uses.get(id(mod.weight), 0) == 1
-            dw, db = slot(mod.weight, dfr), slot(mod.bias, dfr)
-            if deferred_ok and _Deferred.uses.get(id(mod.weight), 0) == 1:
-                _Deferred.params[id(mod.weight)] = (mod.weight, mod.bias)
-                _Deferred.skinny.append((dy, xin.contiguous(), mod.weight))
-                _Deferred.sum_items.append((dy, mod.bias))
+        entries += [("skinny", m.weight, m.bias, 0, m.weight.shape[0], dy, xin.contiguous())
+                    for dy, xin, m in ((Gv("WL", 1), S("QP", 256), sp.attw), (Gv("P0", 256), ref.to(et), sp.pe0))]
+        q, grads, wgrad_now, sums_now = PG.QUEUE, [], {}, []     # this backward's own launches: (n, k) -> [(dy, x, out)]; (matrix, out vector)
+        for kind, w, b, r0, n, dy, xin in entries:
+            if dy is None:                                       # query_scale in the first layer: unused
+                grads += [None, None]
+                continue
+            k = w.shape[-1]
+            r = PG.fused_route(kind, q is not None, et == torch.bfloat16, n, k, PG.USES.single(w), PG.USES.all_fused(w), split_wg, SHARED_DEFER)
+            if r0 == 0:            # in_proj: two entries (INQK, then INV), ONE pair of gradients; a shared linear: GradQueue.first_use
+                later = r.dw == "queue_shared" and not q.first_use(w)
+                gw, gb = (None, None) if later else (slot(w, r.grad_view), slot(b, r.grad_view))
+                grads += [gw, gb]
+            dw, db = (gw[r0:r0 + n], gb[r0:r0 + n]) if kind == "inproj" else (gw, gb)
+            if r.dw in ("queue", "queue_shared"):
+                q.product(dy, xin, w, b, r0, r0 + n)
+            elif r.dw == "skinny_queue":                         # the product itself waits for the flush: one launch for all layers
+                q.skinny_product(dy, xin, w)
+                q.colsum(dy, b)
+            elif r.dw == "sum_queue":
+                q.colsum(dy, w)
+                q.colsum(xin, b)
+            elif r.dw == "sum":
+                sums_now += [(dy, dw), (xin, db)]
             else:
-                skinny_now(dy, xin.contiguous(), dw)
+                if r.dw == "batch":
+                    wgrad_now.setdefault((n, k), []).append((dy, xin, dw))
+                elif r.dw == "split":
+                    (dyh, dyl), (xh, xl) = hi_lo(dy), hi_lo(xin)
+                    wgrad_now.setdefault((n, k), []).extend([(dyh, xh, dw), (dyl, xh, dw), (dyh, xl, dw)])
+                elif r.dw == "partial":
+                    sums_now.append((nv.skinny_wgrad_partial(dy, xin), dw.view(-1)))
+                else:                                            # "own": the exact-f32 kernel, narrow sides zero-padded
+                    dw.copy_(_wgrad_f32(dy, xin))
                 sums_now.append((dy, db))
-            grads += [dw, db]
         if to_split:
             nv.split_rows_batch_into([a for a, _ in to_split], [b_ for _, b_ in to_split])
         for (n, k), lst in wgrad_now.items():
@@ -460,7 +391,6 @@ class FusedLayerFn(torch.autograd.Function):
             groups.setdefault((mat.shape[0], mat.shape[1], str(mat.dtype)), []).append((mat, out))
         for lst in groups.values():
             nv.colsum_batched([a for a, _ in lst], [b_ for _, b_ in lst])
-        # in_proj appears twice in sp.lin (INQK, INV) but once in the tensor list: the INV entry added nothing above
         return (dx, None, dref, drows, None) + tuple(grads)
 
 

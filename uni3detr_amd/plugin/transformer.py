@@ -17,6 +17,8 @@ from torch import nn
 from .. import native as nv
 from ..shadow import compute_copy
 from ..registry import ATTENTION, FEEDFORWARD_NETWORK, TRANSFORMER, TRANSFORMER_LAYER, TRANSFORMER_LAYER_SEQUENCE
+from . import param_grads as PG
+from .param_grads import deferred_param_grads, flush_deferred, reset_param_uses  # noqa: F401  (the trainer and the tests reach them here)
 
 
 def inverse_sigmoid(x, eps=1e-5):
@@ -59,136 +61,41 @@ def _mm_f32(a, b):
 MM_OUT_DTYPE = [None]
 
 
-class _Deferred:
-    """Deferred parameter gradients of the decoder / head linears.  Inside `deferred_param_grads()` a linear whose weight was used
-    ONCE in the forward hands autograd freshly allocated, UNWRITTEN dW / db placeholders and queues (dy, x, parameter);
-    `flush_deferred()` then writes all of them - into whatever tensor autograd stored as `.grad` - with one batched launch per shape
-    (u3d_wgrad_batched_bf16 / u3d_colsum_batched): ~45 independent [N x 7200] x [7200 x K] products of 14 us each become two
-    launches.  Valid because nothing reads a parameter gradient before the flush: with `.grad = None` AccumulateGrad keeps the
-    incoming tensor as is (a weight used twice would accumulate, hence the use count; no reference to the placeholder is kept
-    here, so it is not cloned either)."""
-    active = False
-    items = []          # (dy2 [M,N], x2 [M,K], weight id, first row, last row, has_bias)
-    sum_items = []      # (matrix [rows, C] f32, parameter): parameter.grad <- column sums
-    skinny = []         # (dy2 [M,n], x2 [M,k], weight) with min(n, k) <= 16: all products of a step in one launch per skinny side
-    uses = {}           # id(weight) -> number of forward uses in this step
-    fused_uses = {}     # id(weight) -> how many of those were fused decoder layers (plugin/fused_decoder.py)
-    shared_seen = set() # weights with several uses whose gradient placeholder has been handed to autograd in this backward
-    params = {}         # id(weight) -> (weight, bias)
-
-
-def reset_param_uses():
-    _Deferred.uses, _Deferred.params, _Deferred.fused_uses, _Deferred.shared_seen = {}, {}, {}, set()
-
-
-def flush_deferred():
-    """Returns everything the launches read (operands of the queued products): a caller that runs the flush on a side stream keeps
-    it alive until the streams are joined."""
-    items, _Deferred.items = _Deferred.items, []
-    sums, _Deferred.sum_items = _Deferred.sum_items, []
-    skinny, _Deferred.skinny = _Deferred.skinny, []
-    keep = (items, sums, skinny)
-    if skinny:
-        by_m = {}
-        for it in skinny:
-            by_m.setdefault(it[0].shape[0], []).append(it)
-        for lst in by_m.values():
-            parts = nv.skinny_wgrad_partial_batched([d for d, _, _ in lst], [x for _, x, _ in lst])
-            sums = sums + [(p_, w_) for p_, (_, _, w_) in zip(parts, lst)]
-    groups, bgroups = {}, {}
-    for mat, param in sums:                   # column sums of a [rows, C] matrix into param.grad (LayerNorm dgamma / dbeta, skinny dW / db)
-        if param.grad is None or param.grad.dtype != torch.float32 or not param.grad.is_contiguous() or param.grad.numel() != mat.shape[1]:
-            raise RuntimeError("deferred column sum: no matching contiguous f32 .grad to write into")
-        bgroups.setdefault((mat.shape[0], mat.shape[1], str(mat.dtype)), []).append((mat, param.grad))
-    for dy2, x2, wid, r0, r1, has_bias in items:
-        w, b = _Deferred.params[wid]
-        if w.grad is None or w.grad.dtype != torch.float32 or not w.grad.is_contiguous():
-            raise RuntimeError("deferred weight gradient: autograd did not leave a contiguous f32 .grad to write into")
-        groups.setdefault((dy2.shape[0], dy2.shape[1], x2.shape[1]), []).append((dy2, x2, w.grad[r0:r1]))
-        if has_bias:
-            if b.grad is None or b.grad.dtype != torch.float32:
-                raise RuntimeError("deferred bias gradient: no f32 .grad to write into")
-            bgroups.setdefault((dy2.shape[0], dy2.shape[1]), []).append((dy2, b.grad[r0:r1]))
-    # products / sums with one output tensor (a linear shared by several layers) in consecutive batch slots: the launch sums them
-    for g in groups.values():
-        g.sort(key=lambda t: t[2].data_ptr())
-        nv.wgrad_batched([a for a, _, _ in g], [b for _, b, _ in g], [c for _, _, c in g])
-    for g in bgroups.values():
-        g.sort(key=lambda t: t[1].data_ptr())
-        nv.colsum_batched([a for a, _ in g], [b for _, b in g])
-    _Deferred.shared_seen = set()
-    return keep
-
-
-import contextlib as _contextlib
-
-
-@_contextlib.contextmanager
-def deferred_param_grads():
-    prev = _Deferred.active
-    _Deferred.active, _Deferred.items, _Deferred.sum_items, _Deferred.skinny = True, [], [], []
-    _Deferred.shared_seen = set()
-    try:
-        yield
-        flush_deferred()
-    finally:
-        _Deferred.active, _Deferred.items, _Deferred.sum_items, _Deferred.skinny = prev, [], [], []
-
-
-def _linear_backward(dy2, x2, wc, need_dx, need_dw, need_db, xdtype, defer=None, dw_out=None, db_out=None):
-    """defer = (weight id, first row, last row) queues the parameter gradients (see _Deferred) instead of computing them now."""
-    """Shared backward of y = x2 @ wc^T + b.  dy2 [M,N], x2 [M,K], wc [N,K] (compute dtype).  Parameter gradients come back
-    in f32 (dW from the HIP row-split wgrad kernel when bf16: hipBLASLt runs these [N,M]x[M,K] products with M = B*900 on
-    16 tiles; db from u3d_colsum — NOT dy.sum(0), see colsum)."""
-    n, k = wc.shape
-    m = x2.shape[0]
+def _linear_backward(dy2, x2, wc, need_dx, need_dw, need_db, xdtype, wid, kind="linear", r0=0, dw_out=None, db_out=None):
+    """Shared backward of y = x2 @ wc^T + b.  dy2 [M,N], x2 [M,K], wc [N,K] (compute dtype) = rows r0.. of the weight noted as
+    `wid`.  Parameter gradients come back in f32, in dw_out / db_out when given (dW from the HIP row-split wgrad kernel when bf16:
+    hipBLASLt runs these [N,M]x[M,K] products with M = B*900 on 16 tiles; db from u3d_colsum — NOT dy.sum(0), see colsum), from
+    where param_grads.layer_route says; a queued one is an unwritten placeholder."""
+    (n, k), m, bf16 = wc.shape, x2.shape[0], wc.dtype == torch.bfloat16
     dx = dw = db = None
-    bf16 = wc.dtype == torch.bfloat16
     if need_dx:
         dx = _mm_f32(dy2, wc) if (bf16 and xdtype == torch.float32) else (dy2 @ wc).to(xdtype)
-    if defer is not None and need_dw and bf16 and OWN_WGRAD and n % 64 == 0 and k % 64 == 0 and m > 0:
-        _Deferred.items.append((dy2, x2.contiguous(), defer[0], defer[1], defer[2], bool(need_db)))
-        dw = dw_out if dw_out is not None else torch.empty((n, k), dtype=torch.float32, device=dy2.device)     # placeholder
-        db = (db_out if db_out is not None else torch.empty((n,), dtype=torch.float32, device=dy2.device)) if need_db else None
-        return dx, dw, db
-    if need_dw and bf16 and OWN_WGRAD and SKINNY_WGRAD and m > 0 and min(n, k) <= 16 and (dw_out is None and db_out is None):
-        # skinny product (heads' final layers, position encoder input): own kernel -> per-chunk partials; the sums are deferred
-        # (batched with the LayerNorm parameter sums) when possible
+    # a graph built before the last reset_param_uses() finds nothing under its `wid`: never single, nothing queued
+    weight, bias = PG.USES.params.get(wid, (None, None))
+    q = PG.QUEUE
+    r = PG.layer_route(kind, q is not None, PG.USES.single(weight), need_dw, need_db, bf16, m, n, k, has_bias=bias is not None,
+                       on_gpu=dy2.is_cuda, own_wgrad=OWN_WGRAD, skinny_wgrad=SKINNY_WGRAD)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dy2.device)      # noqa: E731
+    if r.dw == "queue":
+        q.product(dy2, x2.contiguous(), weight, bias if r.db else None, r0, r0 + n)
+        dw = dw_out if dw_out is not None else new(n, k)
+    elif r.dw in ("partial", "partial_queue"):
         partial = nv.skinny_wgrad_partial(dy2, x2.contiguous())
-        if defer is not None and defer[1] == 0 and defer[2] == n:
-            w_, b_ = _Deferred.params[defer[0]]
-            _Deferred.sum_items.append((partial, w_))
-            dw = torch.empty((n, k), dtype=torch.float32, device=dy2.device)
-            if need_db:
-                _Deferred.sum_items.append((dy2, b_))
-                db = torch.empty((n,), dtype=torch.float32, device=dy2.device)
-            return dx, dw, db
-        dw = nv.colsum(partial).view(n, k)
-        if need_db:
-            db = nv.colsum(dy2)
-        return dx, dw, db
-    if need_dw:
-        if bf16 and OWN_WGRAD and n % 16 == 0 and k % 16 == 0 and m > 0:
-            dw = nv.spconv_wgrad(dy2, x2.contiguous(), None, nv.count_tensor(m, dy2.device), 1).view(n, k)
-        elif bf16:
-            dw = _mm_f32(dy2.t(), x2)
-        else:
-            dw = dy2.t() @ x2
-        if dw_out is not None:
-            dw_out.copy_(dw)
-            dw = dw_out
-    if need_db:
-        if (defer is not None and _Deferred.active and db_out is None and defer[1] == 0 and defer[2] == n and dy2.is_cuda
-                and _Deferred.params[defer[0]][1] is not None):
-            # narrow linears (N or K not a multiple of 64: the heads' last layers, Linear(3,256), Linear(256,1)) keep their own dW path,
-            # but the bias column sum joins the batched sums: ~30 colsum launch pairs per step -> a handful
-            _Deferred.sum_items.append((dy2, _Deferred.params[defer[0]][1]))
-            db = torch.empty((n,), dtype=torch.float32, device=dy2.device)         # placeholder, written by flush_deferred()
-        else:
-            db = nv.colsum(dy2)
-            if db_out is not None:
-                db_out.copy_(db)
-                db = db_out
+        dw = nv.colsum(partial).view(n, k) if r.dw == "partial" else new(n, k)
+        if r.dw == "partial_queue":
+            q.colsum(partial, weight)
+    elif r.dw == "own":
+        dw = nv.spconv_wgrad(dy2, x2.contiguous(), None, nv.count_tensor(m, dy2.device), 1).view(n, k)
+    elif r.dw == "blas":
+        dw = _mm_f32(dy2.t(), x2) if bf16 else dy2.t() @ x2
+    if r.dw in ("own", "blas") and dw_out is not None:
+        dw = dw_out.copy_(dw)
+    if r.db in ("queue", "sum_queue"):
+        db = db_out if db_out is not None else new(n)
+        if r.db == "sum_queue":
+            q.colsum(dy2, bias)
+    elif r.db == "sum":
+        db = nv.colsum(dy2) if db_out is None else db_out.copy_(nv.colsum(dy2))
     return dx, dw, db
 
 
@@ -204,9 +111,7 @@ class _TorchLinearFn(torch.autograd.Function):
         else:
             xc, wc, bc = x, weight, bias
         ctx.has_bias, ctx.xdtype = bias is not None, x.dtype
-        ctx.wid = id(weight)
-        _Deferred.uses[ctx.wid] = _Deferred.uses.get(ctx.wid, 0) + 1
-        _Deferred.params[ctx.wid] = (weight, bias)
+        ctx.wid = PG.USES.note(weight, bias)
         ctx.relu = relu
         if relu:
             if bc is not None and xc.dim() >= 2 and bc.dtype == xc.dtype == wc.dtype:
@@ -230,9 +135,7 @@ class _TorchLinearFn(torch.autograd.Function):
         dy2 = (dy2 if dy2.dtype == wc.dtype else dy2.to(wc.dtype)).contiguous()
         x2 = xc.reshape(-1, xc.shape[-1])
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
-        ok = _Deferred.active and _Deferred.uses.get(ctx.wid, 0) == 1 and (need_db or not ctx.has_bias)
-        dx, dw, db = _linear_backward(dy2, x2, wc, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db, ctx.xdtype,
-                                      (ctx.wid, 0, wc.shape[0]) if ok else None)
+        dx, dw, db = _linear_backward(dy2, x2, wc, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db, ctx.xdtype, ctx.wid)
         return (None if dx is None else dx.view(xc.shape)), dw, db, None, None
 
 
@@ -251,9 +154,7 @@ class _InProjFn(torch.autograd.Function):
             qc, vc, wc, bc = qk, xv, weight, bias
         ctx.save_for_backward(qc, vc, wc)
         ctx.qdtype, ctx.vdtype = qk.dtype, xv.dtype
-        ctx.wid = id(weight)
-        _Deferred.uses[ctx.wid] = _Deferred.uses.get(ctx.wid, 0) + 1
-        _Deferred.params[ctx.wid] = (weight, bias)
+        ctx.wid = PG.USES.note(weight, bias)
         return F.linear(qc, wc[: 2 * c], bc[: 2 * c]), F.linear(vc, wc[2 * c:], bc[2 * c:])
 
     @staticmethod
@@ -262,14 +163,13 @@ class _InProjFn(torch.autograd.Function):
         c = wc.shape[1]
         cast = lambda t: (t if t.dtype == wc.dtype else t.to(wc.dtype)).reshape(-1, t.shape[-1]).contiguous()
         dqk2, dv2 = cast(dqk), cast(dv)
-        need_w = ctx.needs_input_grad[2]
-        ok = _Deferred.active and _Deferred.uses.get(ctx.wid, 0) == 1 and need_w and ctx.needs_input_grad[3]
+        need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         dw = torch.empty((3 * c, c), dtype=torch.float32, device=dqk2.device) if need_w else None
         db = torch.empty((3 * c,), dtype=torch.float32, device=dqk2.device) if need_w else None
-        dq_in, _, _ = _linear_backward(dqk2, qc.reshape(-1, c), wc[: 2 * c], ctx.needs_input_grad[0], need_w, need_w, ctx.qdtype,
-                                       (ctx.wid, 0, 2 * c) if ok else None, None if dw is None else dw[: 2 * c], None if db is None else db[: 2 * c])
-        dv_in, _, _ = _linear_backward(dv2, vc.reshape(-1, c), wc[2 * c:], ctx.needs_input_grad[1], need_w, need_w, ctx.vdtype,
-                                       (ctx.wid, 2 * c, 3 * c) if ok else None, None if dw is None else dw[2 * c:], None if db is None else db[2 * c:])
+        dq_in, _, _ = _linear_backward(dqk2, qc.reshape(-1, c), wc[: 2 * c], ctx.needs_input_grad[0], need_w, need_b, ctx.qdtype,
+                                       ctx.wid, "inproj", 0, None if dw is None else dw[: 2 * c], None if db is None else db[: 2 * c])
+        dv_in, _, _ = _linear_backward(dv2, vc.reshape(-1, c), wc[2 * c:], ctx.needs_input_grad[1], need_w, need_b, ctx.vdtype,
+                                       ctx.wid, "inproj", 2 * c, None if dw is None else dw[2 * c:], None if db is None else db[2 * c:])
         return (None if dq_in is None else dq_in.view(qc.shape)), (None if dv_in is None else dv_in.view(vc.shape)), dw, db, None
 
 
@@ -293,7 +193,6 @@ def fast_linear(x, lin, relu=False, weight=None, bias=None):
     """nn.Linear `lin` (or explicit weight/bias) applied to x; HIP GEMM with fused bias/ReLU when running in bf16 mode."""
     w = lin.weight if weight is None else weight
     b = (lin.bias if lin is not None else None) if bias is None and weight is None else bias
-    bf16_mode = x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16))
     if SAFE_LINEAR and x.is_cuda and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         if relu and RELU_EPILOGUE:
             return _TorchLinearFn.apply(x, w, b, _autocast_dtype(x), True)
@@ -315,9 +214,7 @@ class _FusedLN(torch.autograd.Function):
         y, mean, rstd = nv.layernorm_fwd(x2, weight, bias, eps, relu, out_dtype)
         ctx.save_for_backward(x2, weight, bias, mean, rstd)
         ctx.relu, ctx.shp = relu, shp
-        ctx.wid = id(weight)
-        _Deferred.uses[ctx.wid] = _Deferred.uses.get(ctx.wid, 0) + 1
-        _Deferred.params[ctx.wid] = (weight, bias)
+        PG.USES.note(weight, bias)
         return y.view(shp)
 
     @staticmethod
@@ -326,12 +223,12 @@ class _FusedLN(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
         dx, partial = nv.layernorm_bwd(dy2, x2, weight, bias, mean, rstd, ctx.relu)
-        c = x2.shape[1]
-        if _Deferred.active and _Deferred.uses.get(ctx.wid, 0) == 1 and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            _Deferred.sum_items.append((partial[0], weight))
-            _Deferred.sum_items.append((partial[1], bias))
-            dg = torch.empty((c,), dtype=torch.float32, device=x2.device)          # placeholders, written by flush_deferred()
-            db = torch.empty((c,), dtype=torch.float32, device=x2.device)
+        q = PG.QUEUE
+        r = PG.layer_route("norm", q is not None, PG.USES.single(weight), ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        if r.dw == "sum_queue":
+            q.colsum(partial[0], weight)
+            q.colsum(partial[1], bias)
+            dg, db = (torch.empty((x2.shape[1],), dtype=torch.float32, device=x2.device) for _ in "gb")     # written by the flush
         else:
             dg, db = nv.colsum(partial[0]), nv.colsum(partial[1])
         return dx.view(ctx.shp), dg, db, None, None, None
