@@ -51,7 +51,7 @@ def _worker(rank, world, port, q):
             _all_reduce_slice = TrainStep._all_reduce_slice
             _launch_bucket = TrainStep._launch_bucket
         st = _Stub(dist_on=True, world=world, flat_grad=local[rank].clone(), enc_end=384, bb_end=384, three_phase=False, grad_comm_dtype=torch.float32,
-                   _comm=None, _msg=torch.tensor([30.0, 20.0, 10.0, 1.0 if rank == 1 else 0.0]) * torch.tensor([rank + 1.0] * 3 + [1.0]))
+                   _comm=None, comm_diag=False, _msg=torch.tensor([30.0, 20.0, 10.0, 1.0 if rank == 1 else 0.0]) * torch.tensor([rank + 1.0] * 3 + [1.0]))
         st._works = []
         TrainStep._reduce_grads_a(st)
         assert len(st._works) == 1 and st._works[0][2:] == (384, 1000)
@@ -71,7 +71,7 @@ def _worker(rank, world, port, q):
         TrainStep._reduce_grads(st2)
         assert torch.allclose(st2.flat_grad, st.flat_grad, atol=1e-6)
         # (3b) the bf16 exchange option: same buckets, staged through a bf16 buffer - the mean to bf16 precision, identical on all ranks
-        st3 = _Stub(dist_on=True, world=world, flat_grad=local[rank].clone(), enc_end=384, bb_end=700, three_phase=True, _comm=None)
+        st3 = _Stub(dist_on=True, world=world, flat_grad=local[rank].clone(), enc_end=384, bb_end=700, three_phase=True, _comm=None, comm_diag=False)
         st3.grad_comm_dtype = torch.bfloat16
         st3._works = []
         TrainStep._reduce_grads_a(st3)

@@ -167,15 +167,9 @@ def _gpu_inputs(dev):
 def _train_step_grads(model, dev, overlap):
     pts, gts, labels = _gpu_inputs(dev)
     ts = TrainStep(model, pts, gts, labels, graph=False, lr=0.0, overlap_reduce=overlap)
-    ts._stage1()
-    ts._reduce_num_pos()
-    if ts.overlap:
-        ts._stage2a()
-        if ts.three_phase:                 # round 6: the backward is also cut at SECOND3D's outputs (three gradient buckets)
-            ts._stage2m()
-        ts._stage2b()
-    else:
-        ts._stage2()
+    assert ts.plan[-1].name == "_stage3"
+    for ph in ts.plan[:-1]:                # the step as TrainStep schedules it (one, two or three backward phases), without the update
+        getattr(ts, ph.name)()
     torch.cuda.synchronize()
     names = [n for n, p in model.named_parameters() if p.requires_grad]
     got = {n: (None if miss else v.clone()) for n, v, miss in zip(names, ts.views, ts._grad_missing)}

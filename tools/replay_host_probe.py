@@ -17,8 +17,8 @@ ts.capture()
 for _ in range(5):
     ts.step()
 torch.cuda.synchronize()
-g1, g2, g2b, g3 = ts._graphs
-names = ["g1a", "gfps", "g1b", "g1c", "g2", "g2b", "g3"]
+g1, rest = ts._graphs[0], ts._graphs[1:]          # one graph per captured stage of ts.plan; stage 1 is four graphs here
+names = ["g1a", "gfps", "g1b", "g1c"] + [ph.name for ph in ts.plan[1:] if ph.captured]
 for it in range(4):
     torch.cuda.synchronize()
     t = [time.perf_counter()]
@@ -31,8 +31,7 @@ for it in range(4):
     g1[2].replay(); t.append(time.perf_counter())
     cur.wait_stream(side)
     g1[3].replay(); t.append(time.perf_counter())
-    g2.replay(); t.append(time.perf_counter())
-    g2b.replay(); t.append(time.perf_counter())
-    g3.replay(); t.append(time.perf_counter())
+    for g in rest:
+        g.replay(); t.append(time.perf_counter())
     torch.cuda.synchronize(); t.append(time.perf_counter())
     print("host us per replay call:", {n: round((b - a) * 1e6) for n, a, b in zip(names, t, t[1:])}, "| sync", round((t[-1] - t[-2]) * 1e6), "| total", round((t[-1] - t[0]) * 1e6))

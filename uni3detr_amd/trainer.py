@@ -11,6 +11,7 @@ step consists of (host enqueue time ≈ GPU time in eager mode):
          all-reduce of the neck + head slice; G2m = SECOND3D's backward underneath it -> asynchronous all-reduce of the backbone
          slice; G2b = the sparse encoder's backward underneath both; then the all-reduce of the encoder's small slice)
     G3  gradient clipping + fused AdamW
+step_plan() states that order once; the eager step, the capture and the replay all walk it.
 The sparse levels run in static-shape mode (capacity-sized tensors, device-side row counts; uni3detr_amd/sparse.py), so the
 captured launches are valid for any batch whose level sizes fit the capacities.  A batch that does NOT fit is handled on the device and
 collectively: G1 ends with a capacity flag (u3d_capacity_flag), the flag travels in the positive-count all-reduce (so every rank sees
@@ -22,8 +23,13 @@ The point buffer is a capacity too when the step is built with `point_capacity=P
 PointSample): set_packed_batch() fills the static buffers from a DevicePipeline batch on the device (u3d_batch_ingest), a scene above
 the capacity is cut and raises the same HOLD flag.
 """
+import contextlib
+import gc
 import math
 import os
+import sys
+import time
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -50,6 +56,28 @@ def plan_point_capacity(scene_sizes, margin=1.25, multiple=1024):
     multiple = int(multiple)
     need = max(1, math.ceil(max(sizes) * float(margin)))
     return (need + multiple - 1) // multiple * multiple
+
+
+class Phase(NamedTuple):
+    """One record of a step's schedule: the TrainStep method that does the work (by NAME - the walkers look it up on the instance when
+    they run, so a method replaced on the instance is the one called) and whether it is device work that capture() puts into a hipGraph
+    of its own (`captured`) or a collective / wait the host runs un-captured in every mode."""
+    name: str
+    captured: bool
+
+
+def step_plan(overlap, three_phase):
+    """The order of the stages and collectives of one training step - the ONE statement of it: eager_step() calls the records in this
+    order, capture() captures the `captured` ones (one graph each, TrainStep._graphs in this order) and runs the others, step()
+    replays / calls them.  Pure: no device, no model.  three_phase cuts the backward a second time, so it needs overlap."""
+    if three_phase and not overlap:
+        raise ValueError("step_plan: three_phase without overlap - the second cut of the backward lies inside the first one's phase A")
+    if not overlap:
+        backward = ("_stage2", "_reduce_grads")
+    else:
+        backward = (("_stage2a", "_reduce_grads_a") + (("_stage2m", "_reduce_grads_m") if three_phase else ())
+                    + ("_stage2b", "_reduce_grads_b"))
+    return tuple(Phase(n, n.startswith("_stage")) for n in ("_stage1", "_reduce_num_pos") + backward + ("_stage3",))
 
 
 class TrainStep:
@@ -104,7 +132,8 @@ class TrainStep:
         # captured step: the FPS rounds as their own graph on a second stream next to the encoder / dense stack (see capture())
         self.fps_graph = (os.environ.get("U3D_FPS_GRAPH", "1") == "1") if fps_graph is None else bool(fps_graph)
         self._fps_stream = None
-        self.fps_timeouts_seen = 0
+        self.fps_stream_calibration_ms = self.fps_overlap_reference_ms = None      # set by the first capture (_pick_fps_stream)
+        self.fps_timeouts_seen = self._job_fps_timeouts = 0
         self.pg_hooks = pg_hooks
         self._capture_batches = None
         self._msg = None
@@ -138,6 +167,7 @@ class TrainStep:
         self.flat_update = flat_update
         self.check_every, self._steps_since_check, self.recaptures = check_every, 0, 0
         self._grad_missing = [False] * len(self.params)
+        self._seen_ranges, self._missing_idx = set(), set()                # _note_missing: parameter ranges packed so far, indices without a gradient
         # overlap_reduce: the backward runs in two phases cut at the sparse encoder's dense() output.  Phase A (losses, head, decoder,
         # dense stack: ~90 % of the gradient bytes) is followed by an ASYNCHRONOUS all-reduce of its slice of the flat buffer, which then
         # rides under phase B (the sparse encoder's backward); only the encoder's small slice is reduced after it.  The encoder's
@@ -162,6 +192,8 @@ class TrainStep:
         model.cut_backbone_backward = self.three_phase
         self.n_bb_end = n_enc + n_bb if self.three_phase else n_enc
         self.bb_end = self.offsets[self.n_bb_end] if self.three_phase else self.enc_end
+        self.plan = step_plan(self.overlap, self.three_phase)
+        self._gx = self._gbb = None                                        # gradients handed from one backward phase to the next
         self._works = []                                                   # asynchronous bucket reductions in flight: (work, staging, lo, hi)
         self.comm_diag, self._comm_events = False, []
         if flat_update:
@@ -245,8 +277,8 @@ class TrainStep:
                 raise ValueError(f"set_packed_batch: {what} must be a contiguous int32 tensor of {n} elements")
 
         g, lab, go = batch.get("gt_bboxes_3d"), batch.get("gt_labels_3d"), batch.get("gt_off")
-        cnt, gc = batch.get("count"), batch.get("gt_count")
-        if not all(dev_ok(t) for t in (pts, off, cnt, g, lab, go, gc)):
+        cnt, gcnt = batch.get("count"), batch.get("gt_count")
+        if not all(dev_ok(t) for t in (pts, off, cnt, g, lab, go, gcnt)):
             raise ValueError(f"set_packed_batch: every tensor of the batch must live on {cat.device}")
         if pts.dim() != 2 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[1] != cat.shape[1]:
             raise ValueError(f"set_packed_batch: points must be contiguous float32 [n, {cat.shape[1]}], got {pts.dtype} {tuple(pts.shape)}")
@@ -258,10 +290,10 @@ class TrainStep:
                 raise ValueError(f"set_packed_batch: gt_bboxes_3d must be contiguous float32 [g, 7 | 9], got {g.dtype} {tuple(g.shape)}")
             if lab is None or go is None:
                 raise ValueError("set_packed_batch: gt_bboxes_3d needs gt_labels_3d and gt_off")
-            i32(lab, g.shape[0], "gt_labels_3d"); i32(go, B + 1, "gt_off"); i32(gc, B, "gt_count")
+            i32(lab, g.shape[0], "gt_labels_3d"); i32(go, B + 1, "gt_off"); i32(gcnt, B, "gt_count")
         self._ingest_flag.zero_()
         nv.batch_ingest(pts, off, cnt, self.point_capacity, cat, self.pts["scene_off"], self._ingest_flag, gt=g, gt_labels=lab, gt_off=go,
-                        gt_count=gc, gt_cap=int(self.gts["gmax"]), gt_out=self.gts["gt"], labels_out=self.gts["labels"],
+                        gt_count=gcnt, gt_cap=int(self.gts["gmax"]), gt_out=self.gts["gt"], labels_out=self.gts["labels"],
                         gt_off_out=self.gts["gt_off"], overflow=self._ingest_over)
 
     def _set_batch_capacity(self, points, gt_bboxes_3d, gt_labels_3d):
@@ -293,6 +325,7 @@ class TrainStep:
         if self.point_capacity is None:
             return 0
         return int(self._ingest_over.sum().item())
+
     def _pack_gts_static(self, gt_bboxes_3d, gt_labels_3d):
         """GT buffers with a fixed per-scene capacity (`gt_capacity` boxes): the captured graphs size the cost matrix by the capacity
         and read the real per-scene counts from the device-side `gt_off`, so the next batch may hold any number of boxes up to it."""
@@ -423,9 +456,10 @@ class TrainStep:
             self._msg.div_(self.world)
             dist.all_reduce(self._msg)
 
-    def _stage2(self):
+    def _loss_backward(self, cut_leaves=()):
+        """Losses + backward from them (down to the cut leaves, when the forward made any: their .grad is cleared first)."""
         # .grad = None: autograd hands each parameter its gradient tensor as is (no per-parameter "grad += new" launch, ~270 of
-        # them); one multi-tensor copy then packs them into the flat buffer the all-reduce / clip / AdamW stages work on
+        # them); one multi-tensor copy (_pack) then puts them into the flat buffer the all-reduce / clip / AdamW stages work on
         for p in self.params:
             p.grad = None
         losses = self.model.pts_bbox_head.loss_from_targets(self._outs, self._T, self._num_pos)
@@ -434,21 +468,15 @@ class TrainStep:
         if loss is None or not all("loss" in k for k in losses):
             loss = sum(v for k, v in losses.items() if "loss" in k)
         self.model.pts_bbox_head._loss_total = None
+        for t in cut_leaves:
+            t.grad = None
         with _T.deferred_param_grads():      # dW / db of the decoder + head linears: queued, then one batched launch per shape
             loss.backward()
         self.loss = loss.detach()
-        dst, src, missing = [], [], []
-        for i, (p, v) in enumerate(zip(self.params, self.views)):
-            if p.grad is None:
-                missing.append(v)
-                self._grad_missing[i] = True
-            elif p.grad.data_ptr() != v.data_ptr():          # (already in place: written there by the producing kernel)
-                dst.append(v); src.append(p.grad)
-            p.grad = v
-        torch._foreach_copy_(dst, src)
-        if missing:
-            torch._foreach_zero_(missing)
-        self._note_missing(0, len(self.params))
+
+    def _stage2(self):
+        self._loss_backward()
+        self._pack(0, len(self.params))
 
     def _note_missing(self, lo, hi):
         """Parameters that received no gradient keep weights AND moments untouched, as torch.optim.AdamW skips `.grad is None`
@@ -456,14 +484,9 @@ class TrainStep:
         first eager backward, as a per-64-element skip mask for u3d_adamw_step_state."""
         if not self.flat_update or self._skip_known:
             return
-        seen = getattr(self, "_seen_ranges", set())
+        seen, miss = self._seen_ranges, self._missing_idx
         seen.add((lo, hi))
-        self._seen_ranges = seen
-        miss = getattr(self, "_missing_idx", set())
-        for i in range(lo, hi):
-            if self._grad_missing[i]:
-                miss.add(i)
-        self._missing_idx = miss
+        miss.update(i for i in range(lo, hi) if self._grad_missing[i])
         if sum(h - l for l, h in seen) >= len(self.params):
             self._skip_known = True
             if miss:
@@ -491,23 +514,9 @@ class TrainStep:
 
     def _stage2a(self):
         """Losses + backward down to the sparse encoder's dense() output (phase A of the two-phase backward)."""
-        for p in self.params:
-            p.grad = None
-        losses = self.model.pts_bbox_head.loss_from_targets(self._outs, self._T, self._num_pos)
-        self._losses = losses
-        loss = getattr(self.model.pts_bbox_head, "_loss_total", None)
-        if loss is None or not all("loss" in k for k in losses):
-            loss = sum(v for k, v in losses.items() if "loss" in k)
-        self.model.pts_bbox_head._loss_total = None
         cut = self.model._encoder_cut                # detached leaf the dense stack / head were fed with (detector.extract_pts_feat)
-        cut.grad = None
         bcut = self.model._backbone_cut if self.three_phase else None
-        if bcut is not None:
-            for t in bcut:
-                t.grad = None
-        with _T.deferred_param_grads():
-            loss.backward()
-        self.loss = loss.detach()
+        self._loss_backward([cut] + list(bcut or ()))
         self._gbb = None
         if bcut is not None:                         # the backward stopped at SECOND3D's outputs: phase M continues from their gradients
             self._pack(self.n_bb_end, len(self.params))
@@ -522,7 +531,7 @@ class TrainStep:
     def _stage2m(self):
         """Phase M (three-phase backward): SECOND3D's backward from the gradients of its three outputs down to the encoder cut."""
         m = self.model
-        if getattr(self, "_gbb", None) is None or m._backbone_out is None:
+        if self._gbb is None or m._backbone_out is None:
             return                       # the forward made no second cut (nothing behind SECOND3D required a gradient): phase A did it all
         cut = m._encoder_cut
         outs, gs = [], []
@@ -572,7 +581,7 @@ class TrainStep:
 
     def _reduce_grads_a(self):
         """First bucket on the wire: neck + head + decoder (three-phase) or everything behind the encoder (two-phase)."""
-        self._launch_bucket(self.bb_end if getattr(self, "three_phase", False) else self.enc_end, self.flat_grad.numel())
+        self._launch_bucket(self.bb_end if self.three_phase else self.enc_end, self.flat_grad.numel())
 
     def _reduce_grads_m(self):
         """Second bucket (three-phase): SECOND3D's slice, in flight underneath the encoder's backward."""
@@ -583,7 +592,7 @@ class TrainStep:
             # comm_diag: event pairs around the waits of the compute stream - how much of each asynchronous bucket is NOT hidden under
             # the backward that follows it (the stream stalls in work.wait()) and what the encoder's bucket (never overlapped) costs;
             # read by comm_exposed_ms()
-            diag = getattr(self, "comm_diag", False)
+            diag = self.comm_diag
             ev = []
             if diag:
                 ev.append(torch.cuda.Event(enable_timing=True)); ev[-1].record()
@@ -609,7 +618,7 @@ class TrainStep:
         if not self._comm_events:
             return None
         torch.cuda.synchronize()
-        three = bool(getattr(self, "three_phase", False))
+        three = self.three_phase
         rows = [[e[i].elapsed_time(e[i + 1]) for i in range(len(e) - 1)] for _, e in self._comm_events]
         mean = lambda k: sum(r[k] for r in rows if len(r) > k) / max(1, sum(1 for r in rows if len(r) > k))      # noqa: E731
         bpe = 4 if self.grad_comm_dtype == torch.float32 else 2
@@ -654,17 +663,23 @@ class TrainStep:
                     v.zero_()
 
     # ---- optimizer state export / import (ref: the runner's resume_from, extra_tools/train.py:141-142) -------------------------------
+    def _flat_state(self):
+        """(name, tensor) of every tensor of the flat optimizer state this configuration holds: the moments and the step state, with
+        accumulation the open window and, when kept, the EMA weights.  The names are the keys of optimizer_state_dict()."""
+        state = [("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq), ("opt_state", self.opt_state)]
+        if self.accum:
+            state += [("acc", self.acc), ("acc_state", self.acc_state)] + ([("ema", self.ema)] if self.ema is not None else [])
+        return state
+
     def optimizer_state_dict(self):
         """Flat AdamW state as a dict of CPU tensors (per-parameter views are recoverable through `offsets`)."""
         if not self.flat_update:
             return dict(kind="torch", state=self.opt.state_dict())
-        sd = dict(kind="flat", exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), opt_state=self.opt_state.cpu(),
-                  offsets=list(self.offsets), numels=[p.numel() for p in self.params],
+        sd = dict(kind="flat", offsets=list(self.offsets), numels=[p.numel() for p in self.params],
                   skip=None if self._skip is None else self._skip.cpu())
-        if self.accum:                            # the open window and the EMA weights travel with the moments
-            sd.update(accum_steps=self.accum_steps, acc=self.acc.cpu(), acc_state=self.acc_state.cpu())
-            if self.ema is not None:
-                sd["ema"] = self.ema.cpu()
+        sd.update((k, t.cpu()) for k, t in self._flat_state())      # (the open window and the EMA weights travel with the moments)
+        if self.accum:
+            sd["accum_steps"] = self.accum_steps
         return sd
 
     def load_optimizer_state_dict(self, sd):
@@ -693,17 +708,9 @@ class TrainStep:
         self.set_hyper()
 
     def eager_step(self, stage1_done=False):
-        if not stage1_done:
-            self._stage1()
-        self._reduce_num_pos()
-        if self.overlap:
-            self._stage2a(); self._reduce_grads_a()
-            if self.three_phase:
-                self._stage2m(); self._reduce_grads_m()
-            self._stage2b(); self._reduce_grads_b()
-        else:
-            self._stage2(); self._reduce_grads()
-        self._stage3()
+        """Every record of the plan, in order (stage1_done: the caller has run stage 1, the plan's first record, already)."""
+        for ph in self.plan[1:] if stage1_done else self.plan:
+            getattr(self, ph.name)()
         return self.loss
 
     def enable_dist(self):
@@ -726,9 +733,7 @@ class TrainStep:
         """Model state + optimizer state (moments, step count); restore_full() puts all of it back in place."""
         snap = dict(model=self.snapshot())
         if self.flat_update:
-            snap.update(m=self.exp_avg.clone(), v=self.exp_avg_sq.clone(), st=self.opt_state.clone())
-            if self.accum:
-                snap.update(acc=self.acc.clone(), acc_st=self.acc_state.clone(), ema=None if self.ema is None else self.ema.clone())
+            snap["flat"] = {k: t.clone() for k, t in self._flat_state()}
         else:       # torch.optim.AdamW: moments and step counters of every parameter that has state already
             snap["opt"] = {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.opt.state.get(p, {}).items()}
                            for i, p in enumerate(self.params)}
@@ -739,11 +744,8 @@ class TrainStep:
             for t, s_ in zip(list(self.model.parameters()) + list(self.model.buffers()), snap["model"]):
                 t.copy_(s_)
             if self.flat_update:
-                self.exp_avg.copy_(snap["m"]); self.exp_avg_sq.copy_(snap["v"]); self.opt_state.copy_(snap["st"])
-                if self.accum:
-                    self.acc.copy_(snap["acc"]); self.acc_state.copy_(snap["acc_st"])
-                    if self.ema is not None:
-                        self.ema.copy_(snap["ema"])
+                for k, t in self._flat_state():
+                    t.copy_(snap["flat"][k])
             else:
                 # in place (a captured optimizer step holds these addresses); state created after the snapshot goes back to zero
                 for i, p in enumerate(self.params):
@@ -810,6 +812,19 @@ class TrainStep:
             raise FpsTimeout("several-workgroup FPS timed out waiting for a sibling workgroup: this step's query samples are invalid")
         return counts
 
+    def _drop_step_state(self):
+        """Drop the eager iteration's activations / autograd graph BEFORE capturing: releasing them from inside a capture (when the
+        attributes are re-assigned) tears down autograd nodes mid-capture and crashes hipStreamEndCapture."""
+        self._outs = self._T = self._num_pos = self._msg = self._losses = self.loss = None
+        self._gx = self._v = self._fps = self._feat = None
+        self.model._encoder_out = self.model._encoder_cut = None
+        self.model.pts_bbox_head._loss_total = None
+        dec = getattr(getattr(self.model.pts_bbox_head, "transformer", None), "decoder", None)
+        if dec is not None:
+            dec._reg_outputs = dec._states_c = dec._cls_outputs = dec._iou_outputs = dec._coord_outputs = dec._refs_sig = None
+        gc.collect()
+        torch.cuda.synchronize()
+
     def capture(self, warmup=3, keep_state=True, batches=None, remember_batches=True):
         """Measure the sparse-level capacities (over `batches`, a list of (points, gts, labels) or packed batch dicts, when given), warm up, capture.
         keep_state: weights, BatchNorm statistics and optimizer state are restored afterwards - the measuring / warm-up iterations
@@ -829,73 +844,39 @@ class TrainStep:
                 self.eager_step()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        # drop the eager iteration's activations / autograd graph BEFORE capturing: releasing them from inside a capture
-        # (when the attributes are re-assigned) tears down autograd nodes mid-capture and crashes hipStreamEndCapture
-        self._outs = self._T = self._num_pos = self._msg = self._losses = self.loss = None
-        self._gx = self._v = self._fps = self._feat = None
-        self.model._encoder_out = self.model._encoder_cut = None
-        self.model.pts_bbox_head._loss_total = None
-        dec = getattr(getattr(self.model.pts_bbox_head, "transformer", None), "decoder", None)
-        if dec is not None:
-            dec._reg_outputs = None
-            dec._states_c = None
-            dec._cls_outputs = dec._iou_outputs = None
-            dec._coord_outputs = dec._refs_sig = None
-        import gc
-        gc.collect()
-        torch.cuda.synchronize()
-        g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        g2b = torch.cuda.CUDAGraph() if self.overlap else None
-        g2m = torch.cuda.CUDAGraph() if (self.overlap and self.three_phase) else None
+        self._drop_step_state()
         pool = torch.cuda.graph_pool_handle()
-        self._v = self._fps = self._feat = None
-        if self.fps_graph and not getattr(self.model, "dynamic_voxelization", False):
-            # stage 1 as FOUR graphs: voxelize | FPS || encoder + dense stack | head + matching.  Every node of one hipGraph runs on a
-            # single hardware queue on this stack, so the forked FPS branch of a monolithic stage-1 graph sat alone on the device for
-            # its ~1.1 ms (rocprofv3 timeline, profiles/r04a_timeline.txt); as its own graph, replayed on a second stream, it runs
-            # underneath the encoder.  The FPS graph has its OWN memory pool: it is the one graph that runs concurrently with another,
-            # and graphs sharing a pool may reuse each other's freed blocks.
-            g1a, gf, g1b, g1c = (torch.cuda.CUDAGraph() for _ in range(4))
-            if self._fps_stream is None:
-                self._fps_stream = torch.cuda.Stream()
-            with torch.cuda.graph(g1a, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage1a()
-            with torch.cuda.graph(gf, stream=s, capture_error_mode="thread_local"):
-                self._stage1_fps()
-            with torch.cuda.graph(g1b, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage1b()
-            with torch.cuda.graph(g1c, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage1c()
-            g1 = (g1a, gf, g1b, g1c)
-        else:
-            with torch.cuda.graph(g1, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage1()
-        self._reduce_num_pos()
-        if self.overlap:
-            with torch.cuda.graph(g2, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage2a()
-            self._reduce_grads_a()
-            if g2m is not None:
-                with torch.cuda.graph(g2m, pool=pool, stream=s, capture_error_mode="thread_local"):
-                    self._stage2m()
-                self._reduce_grads_m()
-            with torch.cuda.graph(g2b, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage2b()
-            self._reduce_grads_b()
-        else:
-            with torch.cuda.graph(g2, pool=pool, stream=s, capture_error_mode="thread_local"):
-                self._stage2()
-            self._reduce_grads()
-        with torch.cuda.graph(g3, pool=pool, stream=s, capture_error_mode="thread_local"):
-            self._stage3()
+
+        def captured(name, pool=pool):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode="thread_local"):
+                getattr(self, name)()
+            return g
+
+        # the plan, one graph per captured stage; stage 1 (the plan's first record) is ONE graph or, with fps_graph, FOUR:
+        # voxelize | FPS || encoder + dense stack | head + matching.  Every node of one hipGraph runs on a single hardware queue on this
+        # stack, so the forked FPS branch of a monolithic stage-1 graph sat alone on the device for its ~1.1 ms (rocprofv3 timeline,
+        # profiles/r04a_timeline.txt); as its own graph, replayed on a second stream, it runs underneath the encoder.  The FPS graph
+        # has its OWN memory pool: it is the one graph that runs concurrently with another, and graphs sharing a pool may reuse each
+        # other's freed blocks.
+        split = self.fps_graph and not getattr(self.model, "dynamic_voxelization", False)
+        if split and self._fps_stream is None:
+            self._fps_stream = torch.cuda.Stream()
+        graphs = []
+        for ph in self.plan:
+            if not ph.captured:
+                getattr(self, ph.name)()
+            elif split and ph.name == "_stage1":
+                graphs.append((captured("_stage1a"), captured("_stage1_fps", pool=None), captured("_stage1b"), captured("_stage1c")))
+            else:
+                graphs.append(captured(ph.name))
         torch.cuda.synchronize()
-        self._graphs = (g1, g2, g2b, g3)
-        self._g2m = g2m
-        if isinstance(g1, tuple) and getattr(self, "fps_stream_calibration_ms", None) is None:
+        self._graphs = tuple(graphs)
+        if split and self.fps_stream_calibration_ms is None:
             # once per TrainStep: a re-capture keeps the stream the first capture chose (every rank then keeps ITS choice for the
             # whole job, and a re-capture costs no calibration replays)
             bufs = [(b, b.clone()) for b in self.model.buffers()]
-            self._pick_fps_stream(g1)
+            self._pick_fps_stream(graphs[0])
             with torch.no_grad():
                 for b, v in bufs:                    # the ~40 calibration replays ran BatchNorm in training mode on one batch
                     b.copy_(v)
@@ -945,7 +926,6 @@ class TrainStep:
         shadows are re-cast from flat_param by every forward; an InferenceModel built on the model holds folded copies of its own and
         needs refresh() inside the scope (and again after it).  Entering with an open window (window_fill() != 0) is allowed: the
         accumulator is not touched.  Do not step inside the scope."""
-        import contextlib
         if self.ema is None:
             raise RuntimeError("ema_scope needs a TrainStep built with ema_decay=d")
 
@@ -969,6 +949,16 @@ class TrainStep:
         e = getattr(self.model, "fps_err", None)
         return int(e[1].item()) if e is not None else 0
 
+    def _single_wg_fps(self, n_to, clear_hold=True):
+        """Fall back to the single-workgroup FPS after `n_to` time-outs: the several-workgroup FPS needs all its workgroups resident
+        together and waited in vain, so from here on this rank samples with the single-workgroup streaming kernel (slower rounds, no
+        cross-workgroup wait) - same indices.  The time-out record is cleared and (clear_hold) the hold flag / held-step counter with it."""
+        self.fps_timeouts_seen += n_to
+        self.model.fps_max_wg = 1
+        self.model.fps_err.zero_()
+        if clear_hold and self.flat_update:
+            self.opt_state[11:13].zero_()
+
     def recapture(self):
         """Collective re-capture with more room (every rank calls it at the same step: the decision comes from the all-reduced
         counter).  With a live process group the group is torn down first and re-created afterwards through `pg_hooks`: capture and
@@ -989,16 +979,11 @@ class TrainStep:
         held = self.held_steps()
         # WHY steps were held is a per-rank fact, what to change must be a job-wide decision: step() exchanged the maximum over ranks
         # before the group was torn down (_job_fps_timeouts); a direct caller on one rank falls back to its own count
-        n_to = max(self.fps_timeouts(), getattr(self, "_job_fps_timeouts", 0))
+        n_to = max(self.fps_timeouts(), self._job_fps_timeouts)
         self._job_fps_timeouts = 0
         self.recaptures += 1
-        import sys
         if n_to > 0:
-            # the several-workgroup FPS needs all its workgroups resident together and waited in vain: from here on every rank samples
-            # with the single-workgroup streaming kernel (slower rounds, no cross-workgroup wait) - same indices
-            self.fps_timeouts_seen += n_to
-            self.model.fps_max_wg = 1
-            self.model.fps_err.zero_()
+            self._single_wg_fps(n_to, clear_hold=False)      # (the hold counter is cleared below, after the capture's own steps)
             print(f"[TrainStep] {held} step(s) held, {n_to} FPS launch(es) timed out waiting for a sibling workgroup; re-capturing with the "
                   f"single-workgroup FPS (re-capture #{self.recaptures})", file=sys.stderr, flush=True)
         else:
@@ -1026,8 +1011,6 @@ class TrainStep:
         after the other although nothing orders them - profiles/r04e_timeline.txt -, with a lucky pair the FPS rounds disappear under
         the encoder).  So the side stream is CHOSEN by measurement: stage 1 is replayed with each candidate stream and the fastest one
         is kept.  Runs inside capture(), before the state snapshot is put back (the replays touch BatchNorm running statistics)."""
-        import time
-        cur = torch.cuda.current_stream()
 
         def wall(side):
             self._fps_stream = side
@@ -1110,12 +1093,7 @@ class TrainStep:
         self._raise_on_ingest_overflow()
         held, n_to = self.held_steps(), self.fps_timeouts()
         if n_to > 0:
-            import sys
-            self.fps_timeouts_seen += n_to
-            self.model.fps_max_wg = 1
-            self.model.fps_err.zero_()
-            if self.flat_update:
-                self.opt_state[11:13].zero_()
+            self._single_wg_fps(n_to)
             print(f"[TrainStep] eager mode: {held} step(s) held, {n_to} FPS launch(es) timed out waiting for a sibling workgroup; "
                   "continuing with the single-workgroup FPS", file=sys.stderr, flush=True)
 
@@ -1129,10 +1107,7 @@ class TrainStep:
                 # forward and the backward; the forward is repeated with the single-workgroup FPS, nothing trains on invalid samples
                 self._stage1()
                 if int(self.model.fps_err[0].item()) != 0:
-                    import sys
-                    self.fps_timeouts_seen += 1
-                    self.model.fps_max_wg = 1
-                    self.model.fps_err.zero_()
+                    self._single_wg_fps(1)                 # (flat_update=False: there is no hold counter to clear)
                     print("[TrainStep] eager mode: the several-workgroup FPS timed out; repeating the forward with the single-workgroup "
                           "FPS", file=sys.stderr, flush=True)
                     self._stage1()
@@ -1152,8 +1127,7 @@ class TrainStep:
                     self._job_fps_timeouts = int(t.item())
                 self.recapture()
         self._steps_since_check += 1
-        g1, g2, g2b, g3 = self._graphs
-        self._replay_stage1(g1)
+        self._replay_stage1(self._graphs[0])
         if not self.flat_update:
             # torch.optim has no device-side hold flag (u3d_adamw_step_hold is the flat path's): without it a level that outgrew its
             # captured capacity would be truncated and trained on silently, so this configuration pays one host read per step and
@@ -1166,18 +1140,12 @@ class TrainStep:
                 if isinstance(e, FpsTimeout):
                     self._job_fps_timeouts = max(1, self.fps_timeouts())       # recapture() switches to the single-workgroup FPS
                 self.recapture()
-                g1, g2, g2b, g3 = self._graphs
-                self._replay_stage1(g1)
-        self._reduce_num_pos()
-        g2.replay()
-        if g2b is not None:
-            self._reduce_grads_a()
-            if getattr(self, "_g2m", None) is not None:
-                self._g2m.replay()
-                self._reduce_grads_m()
-            g2b.replay()
-            self._reduce_grads_b()
-        else:
-            self._reduce_grads()
-        g3.replay()
+                self._replay_stage1(self._graphs[0])
+        # stage 1 (the plan's first record) is replayed; the rest of the plan: a captured stage replays its graph, a host step is called
+        graphs = iter(self._graphs[1:])
+        for ph in self.plan[1:]:
+            if ph.captured:
+                next(graphs).replay()
+            else:
+                getattr(self, ph.name)()
         return self.loss
