@@ -85,6 +85,11 @@ int32_t u3d_bitgrid_rank(const u3d_bitgrid* g, const int32_t* coors, int32_t n, 
 /* Enumerate occupied cells in rank order: coors_out int32 [cap,4] (b,z,y,x); cap = rows available; rows [count, cap) = (-1,-1,-1,-1). */
 int32_t u3d_bitgrid_coords(const u3d_bitgrid* g, int32_t* coors_out, int32_t cap, u3d_stream s);
 
+/* u3d_bitgrid_scan followed by u3d_bitgrid_coords, with the same results.  Block-major grids of up to 2048 scan chunks take two
+ * launches (chunk sums; then every workgroup sums the chunk sums in front of it itself, writes its prefixes and emits the
+ * coordinates of its own words); the linear layout and larger grids run the two calls above. */
+int32_t u3d_bitgrid_scan_coords(const u3d_bitgrid* g, void* scratch, int32_t* coors_out, int32_t cap, u3d_stream s);
+
 /* Neighbour table ("rulebook") nbr[kappa][ld] int32, kappa = (kz*k1 + ky)*k2 + kx, -1 = no partner.
  *   mode 0 (gather/forward): partner of query q at kappa = target cell  q*stride - pad + kappa
  *       (SubMConv3d: stride 1, pad (k-1)/2, target == query grid; SparseConv3d forward: query = output sites).
@@ -95,6 +100,12 @@ int32_t u3d_bitgrid_coords(const u3d_bitgrid* g, int32_t* coors_out, int32_t cap
 int32_t u3d_nbr_table(const u3d_bitgrid* target, const int32_t* q_coors, const int32_t* n_dev, int32_t n_cap,
                       const int32_t ksize[3], const int32_t stride[3], const int32_t pad[3], int32_t mode,
                       int32_t* nbr, int32_t ld, u3d_stream s);
+
+/* The same table for ksize (3,3,3) on a block-major grid (layout 0), any stride, pad >= 0, both modes: the 27 targets of a row lie
+ * in at most 2 x 2 x 2 words, which the row loads at once (u3d_nbr_table: 54 dependent loads).  U3D_ERR_UNSUPPORTED for the linear
+ * layout, a negative pad, or a grid / table beyond 32-bit indices: the caller takes u3d_nbr_table. */
+int32_t u3d_nbr_table_k3(const u3d_bitgrid* target, const int32_t* q_coors, const int32_t* n_dev, int32_t n_cap,
+                         const int32_t stride[3], const int32_t pad[3], int32_t mode, int32_t* nbr, int32_t ld, u3d_stream s);
 
 /* Same table for a DENSE lattice (every cell of [batch, dims] is a row; row id = lexicographic (b,z,y,x) index, i.e. the
  * memory order of a channels-last volume): lets the dense SECOND3D / SECOND3DFPN convolutions run on the same
@@ -123,6 +134,13 @@ int32_t u3d_voxelize_hard(const float* points, const int32_t* scene_off, int32_t
                           const float pc_range[6], int32_t max_points, int32_t max_voxels,
                           float* voxels, int32_t* coors, int32_t* num_points, float* mean,
                           int32_t* voxel_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
+/* Same arguments, workspace and results; the first-appearance ranks are built in two levels over (scene, 1024-point chunk)
+ * workgroups instead of by one workgroup per scene, and the scene offsets by the same launch. */
+int32_t u3d_voxelize_hard_chunked(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total,
+                                  int32_t max_pts_per_scene, int32_t nfeat, const float voxel_size[3],
+                                  const float pc_range[6], int32_t max_points, int32_t max_voxels,
+                                  float* voxels, int32_t* coors, int32_t* num_points, float* mean,
+                                  int32_t* voxel_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
  * Dynamic voxelization + DynamicSimpleVFE (ref: models/detectors/uni3detr.py:155-171; upstream mmcv Voxelization with

@@ -293,6 +293,113 @@ extern "C" int32_t u3d_bitgrid_coords(const u3d_bitgrid* g, int32_t* coors_out, 
   return U3D_OK;
 }
 
+// ---- scan + coordinates in two launches (block-major layout) ---------------------------------------------------------------
+// Launch 1 is k_scan_chunksum (4096-word chunks).  Launch 2 runs one workgroup per 256 * ITEMS words, a piece of a chunk: a level
+// has a few to a few hundred chunks, and a thread that walks the set bits of 16 words in turn (one workgroup per chunk) leaves the
+// chip idle - 62 us per launch in that form; with 4 words per thread on the three small, dense levels still 21 us, the time going
+// into few waves' scattered 16-byte stores; now 10-13 us against 19-31 us for the three launches it replaces
+// (profiles/geometry_build_kernels_parent_vs_new.txt).  Every workgroup works out its own offset: the chunk sums in front of its
+// chunk, plus the popcounts of the words of its chunk in front of it (re-read, at most 16 - ITEMS per thread, out of L2).  No
+// workgroup waits for another.  It then writes the prefixes of its words and emits the coordinates of their set bits while it holds
+// word and running rank - what k_scan_top, k_scan_final and k_bitgrid_coords (which re-reads words and prefix) do in three launches.
+#define SCAN_FUSED_MAX_CHUNKS 2048      // 8 chunk sums per thread; larger grids keep the four-launch path
+#define SCAN_FUSED_ONE_WORD_MAX (1 << 19)      // up to here one word per thread (<= 2048 workgroups); above, four (the re-read grows as 16 / ITEMS)
+
+template <int ITEMS>
+__global__ __launch_bounds__(SCAN_TPB) void k_scan_final_coords(BitGridDev g, int nwords, const unsigned* __restrict__ chunk_sum,
+                                                                unsigned* __restrict__ prefix, int nchunks, int4* __restrict__ out,
+                                                                int cap) {
+  __shared__ unsigned lds[4];
+  __shared__ unsigned red[2][4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int sub0 = (int)blockIdx.x * (SCAN_TPB * ITEMS);              // first word of this workgroup
+  const int chunk = sub0 / SCAN_CHUNK;
+  // Every load of the kernel is issued here, before the first use: fixed trip counts, a slot that does not count reads a valid
+  // neighbouring address and adds 0.  Fixed order of the sums: thread t takes chunks (words) t, t + 256, ...; then lanes, then waves.
+  const int base = sub0 + (int)threadIdx.x * ITEMS;
+  unsigned long long wd[ITEMS];
+  unsigned cs[SCAN_FUSED_MAX_CHUNKS / SCAN_TPB];
+  unsigned long long pw[SCAN_CHUNK / SCAN_TPB - ITEMS];
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) wd[j] = g.words[min(base + j, nwords - 1)];
+#pragma unroll
+  for (int k = 0; k < SCAN_FUSED_MAX_CHUNKS / SCAN_TPB; ++k) cs[k] = chunk_sum[min(k * SCAN_TPB + (int)threadIdx.x, nchunks - 1)];
+#pragma unroll
+  for (int k = 0; k < SCAN_CHUNK / SCAN_TPB - ITEMS; ++k) {      // (a slot not in front of this workgroup's words: the thread's own word again)
+    const int wi = chunk * SCAN_CHUNK + k * SCAN_TPB + (int)threadIdx.x;
+    pw[k] = g.words[wi < sub0 ? wi : min(base, nwords - 1)];
+  }
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < SCAN_FUSED_MAX_CHUNKS / SCAN_TPB; ++k) {
+    const int ci = k * SCAN_TPB + (int)threadIdx.x;
+    all += (ci < nchunks) ? cs[k] : 0u;
+    before += (ci < chunk) ? cs[k] : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < SCAN_CHUNK / SCAN_TPB - ITEMS; ++k)
+    before += (chunk * SCAN_CHUNK + k * SCAN_TPB + (int)threadIdx.x < sub0) ? (unsigned)__popcll(pw[k]) : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); all += __shfl_xor(all, o, 64); }
+  if (lane == 0) { red[0][wid] = before; red[1][wid] = all; }
+  __syncthreads();
+  before = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+  all = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+
+  unsigned c = 0;
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    if (base + j >= nwords) wd[j] = 0ull;
+    c += (unsigned)__popcll(wd[j]);
+  }
+  unsigned ex = block_exclusive_scan(c, lds, nullptr) + before;
+  if (blockIdx.x == 0 && threadIdx.x == 0) prefix[nwords] = all;
+  // rows past the occupied count: (-1, -1, -1, -1), as k_bitgrid_coords writes them
+  for (long long i = (long long)blockIdx.x * SCAN_TPB + threadIdx.x; i < cap; i += (long long)gridDim.x * SCAN_TPB)
+    if (i >= (long long)all) out[i] = make_int4(-1, -1, -1, -1);
+  // block of the thread's first word: one division chain, then carried along its words
+  int t = base;
+  int bx = t % g.bx; t /= g.bx;
+  int by = t % g.by; t /= g.by;
+  int bz = t % g.bz;
+  int b = t / g.bz;
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    if (base + j < nwords) prefix[base + j] = ex;
+    unsigned long long bits = wd[j];
+    unsigned r = ex;
+    ex += (unsigned)__popcll(bits);
+    while (bits) {
+      const int bit = __ffsll((long long)bits) - 1;
+      bits &= bits - 1;
+      if (r < (unsigned)cap) out[r] = make_int4(b, bz * 4 + (bit >> 4), by * 4 + ((bit >> 2) & 3), bx * 4 + (bit & 3));
+      ++r;
+    }
+    if (++bx == g.bx) { bx = 0; if (++by == g.by) { by = 0; if (++bz == g.bz) { bz = 0; ++b; } } }
+  }
+}
+
+extern "C" int32_t u3d_bitgrid_scan_coords(const u3d_bitgrid* g, void* scratch, int32_t* coors_out, int32_t cap, u3d_stream s) {
+  U3D_REQUIRE(g && g->words && g->prefix && scratch && coors_out && cap >= 0, U3D_ERR_ARG);
+  const long long nwords = grid_nwords(g);
+  U3D_REQUIRE(nwords > 0, U3D_ERR_ARG);
+  const long long nchunks = (nwords + SCAN_CHUNK - 1) / SCAN_CHUNK;
+  if (g->layout != 0 || nchunks > SCAN_FUSED_MAX_CHUNKS) {      // linear layout, very large grids: the separate launches
+    const int32_t rc = u3d_bitgrid_scan(g, scratch, s);
+    return rc != U3D_OK ? rc : u3d_bitgrid_coords(g, coors_out, cap, s);
+  }
+  unsigned* cs = (unsigned*)scratch;
+  hipLaunchKernelGGL(k_scan_chunksum, dim3((int)nchunks), dim3(SCAN_TPB), 0, s, (const unsigned long long*)g->words, nwords, cs);
+  if (nwords <= SCAN_FUSED_ONE_WORD_MAX)
+    hipLaunchKernelGGL(k_scan_final_coords<1>, dim3(u3d_cdiv(nwords, SCAN_TPB)), dim3(SCAN_TPB), 0, s, u3d_make_grid(g), (int)nwords,
+                       (const unsigned*)cs, (unsigned*)g->prefix, (int)nchunks, (int4*)coors_out, cap);
+  else
+    hipLaunchKernelGGL(k_scan_final_coords<4>, dim3(u3d_cdiv(nwords, SCAN_TPB * 4)), dim3(SCAN_TPB), 0, s, u3d_make_grid(g), (int)nwords,
+                       (const unsigned*)cs, (unsigned*)g->prefix, (int)nchunks, (int4*)coors_out, cap);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
 // ============================================================================================
 // Neighbour table
 // ============================================================================================
@@ -333,6 +440,124 @@ extern "C" int32_t u3d_nbr_table(const u3d_bitgrid* target, const int32_t* q_coo
   for (int i = 0; i < 3; ++i) { cv.k[i] = ksize[i]; cv.s[i] = stride[i]; cv.p[i] = pad[i]; U3D_REQUIRE(stride[i] > 0 && ksize[i] > 0, U3D_ERR_ARG); }
   hipLaunchKernelGGL(k_nbr_table, dim3(u3d_cdiv(ld, 256)), dim3(256), 0, s, u3d_make_grid(target), (const int4*)q_coors,
                      n_dev, n_cap, cv, mode, nbr, ld);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+// ---- 3 x 3 x 3 tables of the block-major grid ------------------------------------------------------------------------------
+// k_nbr_table makes 54 loads per row, each issued after the previous one returned (words[w], bit test, prefix[w]; run-time loop
+// bounds).  The three targets of a row along one axis are at most three consecutive cells - q*s - p + {0,1,2} in mode 0, the
+// divisible ones among (q + p - {0,1,2}) / s in mode 1 - so they lie in at most two 4-cell blocks, and the 27 targets in at most
+// 2 x 2 x 2 words.  Here a row loads those 8 words and 8 prefixes at once (addresses depend on the coordinates only) and answers
+// the 27 lookups from registers.  A block past the grid's edge is clamped onto its neighbour: its targets are invalid anyway.
+template <int MODE>
+__device__ __forceinline__ void nbr_axis_k3(int c, int s, int p, int D, int nb, int (&t)[3], bool (&ok)[3], int (&blk)[2]) {
+  if (MODE == 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { t[j] = c * s - p + j; ok[j] = (unsigned)t[j] < (unsigned)D; }
+  } else {
+    const int u0 = c + p;                      // >= 0: the host admits pad >= 0 only
+    const int q0 = u0 / s, r0 = u0 - q0 * s;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {              // (u0 - j) / s and % s from the one division: j <= 2 wraps once for s >= 2
+      int r = (s == 1) ? 0 : r0 - j, q = (s == 1) ? u0 - j : q0;
+      if (r < 0) { r += s; q -= 1; }
+      t[j] = q;
+      ok[j] = u0 - j >= 0 && r == 0 && q < D;
+    }
+  }
+  int lo = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) if (ok[j]) lo = min(lo, t[j]);
+  blk[0] = (lo == 0x7fffffff) ? 0 : (lo >> 2);
+  blk[1] = min(blk[0] + 1, nb - 1);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_nbr_table_k3(BitGridDev g, const int4* __restrict__ q, const int* __restrict__ n_dev, int n_cap,
+                                                      Conv3 cv, int* __restrict__ nbr, int ld, int nwords) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ld) return;
+  const int n = min(*n_dev, n_cap);
+  if (i >= n) {
+#pragma unroll
+    for (int k = 0; k < 27; ++k) nbr[k * ld + i] = -1;
+    return;
+  }
+  const int4 c = q[i];
+  int tz[3], ty[3], tx[3], zb[2], yb[2], xb[2];
+  bool oz[3], oy[3], ox[3];
+  nbr_axis_k3<MODE>(c.y, cv.s[0], cv.p[0], g.Dz, g.bz, tz, oz, zb);
+  nbr_axis_k3<MODE>(c.z, cv.s[1], cv.p[1], g.Dy, g.by, ty, oy, yb);
+  nbr_axis_k3<MODE>(c.w, cv.s[2], cv.p[2], g.Dx, g.bx, tx, ox, xb);
+  int wi[2][2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d)
+        wi[a][b][d] = (int)min((unsigned)(((c.x * g.bz + zb[a]) * g.by + yb[b]) * g.bx + xb[d]), (unsigned)(nwords - 1));
+  unsigned long long W[2][2][2];
+  unsigned P[2][2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d) W[a][b][d] = g.words[wi[a][b][d]];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d) P[a][b][d] = g.prefix[wi[a][b][d]];
+#pragma unroll
+  for (int kz = 0; kz < 3; ++kz) {
+    const bool sz = (tz[kz] >> 2) != zb[0];
+    unsigned long long W4[2][2];
+    unsigned P4[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int d = 0; d < 2; ++d) { W4[b][d] = sz ? W[1][b][d] : W[0][b][d]; P4[b][d] = sz ? P[1][b][d] : P[0][b][d]; }
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const bool sy = (ty[ky] >> 2) != yb[0];
+      const unsigned long long W2[2] = {sy ? W4[1][0] : W4[0][0], sy ? W4[1][1] : W4[0][1]};
+      const unsigned P2[2] = {sy ? P4[1][0] : P4[0][0], sy ? P4[1][1] : P4[0][1]};
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const bool sx = (tx[kx] >> 2) != xb[0];
+        const unsigned long long bits = sx ? W2[1] : W2[0];
+        const unsigned pre = sx ? P2[1] : P2[0];
+        const int bit = ((tz[kz] & 3) << 4) | ((ty[ky] & 3) << 2) | (tx[kx] & 3);
+        const int r = (int)(pre + (unsigned)__popcll(bits & ((1ull << bit) - 1ull)));
+        const bool hit = (oz[kz] & oy[ky] & ox[kx]) & (bool)((bits >> bit) & 1ull) & !((g.cap > 0) & (r >= g.cap));   // no branches
+        nbr[((kz * 3 + ky) * 3 + kx) * ld + i] = hit ? r : -1;
+      }
+    }
+  }
+}
+
+extern "C" int32_t u3d_nbr_table_k3(const u3d_bitgrid* target, const int32_t* q_coors, const int32_t* n_dev, int32_t n_cap,
+                                    const int32_t stride[3], const int32_t pad[3], int32_t mode, int32_t* nbr, int32_t ld,
+                                    u3d_stream s) {
+  U3D_REQUIRE(target && target->words && target->prefix && q_coors && n_dev && nbr, U3D_ERR_ARG);
+  U3D_REQUIRE(ld >= n_cap && (mode == 0 || mode == 1), U3D_ERR_ARG);
+  if (ld <= 0) return U3D_OK;
+  Conv3 cv;
+  for (int i = 0; i < 3; ++i) { cv.k[i] = 3; cv.s[i] = stride[i]; cv.p[i] = pad[i]; U3D_REQUIRE(stride[i] > 0, U3D_ERR_ARG); }
+  const long long nwords = grid_nwords(target);
+  // block-major grid, pad >= 0 (mode 1 divides q + pad - kappa once), 32-bit word and table indices
+  U3D_REQUIRE(target->layout == 0 && pad[0] >= 0 && pad[1] >= 0 && pad[2] >= 0, U3D_ERR_UNSUPPORTED);
+  U3D_REQUIRE(nwords > 0 && nwords <= 0x7fffffffll && 27ll * ld <= 0x7fffffffll, U3D_ERR_UNSUPPORTED);
+  if (mode == 0)
+    hipLaunchKernelGGL(k_nbr_table_k3<0>, dim3(u3d_cdiv(ld, 256)), dim3(256), 0, s, u3d_make_grid(target), (const int4*)q_coors,
+                       n_dev, n_cap, cv, nbr, ld, (int)nwords);
+  else
+    hipLaunchKernelGGL(k_nbr_table_k3<1>, dim3(u3d_cdiv(ld, 256)), dim3(256), 0, s, u3d_make_grid(target), (const int4*)q_coors,
+                       n_dev, n_cap, cv, nbr, ld, (int)nwords);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
@@ -517,6 +742,92 @@ __global__ void k_vox_rank(const int* __restrict__ scene_off, VoxCfg cfg, const 
   if (threadIdx.x == 0) scene_cnt[b] = (int)min(carry_s, (unsigned)cfg.max_voxels);
 }
 
+// The same ranks in two levels over a (chunk, scene) grid of 1024-point chunks, instead of one workgroup walking its scene's chunks in
+// turn (8 workgroups on 256 CUs, a dependent slot_of -> first load pair and three barriers per chunk):
+//   k_vox_chunk_count: creator flags of a chunk -> chunk_cnt[scene][chunk];
+//   k_vox_rank_chunks: every workgroup adds up the counts in front of its chunk, ranks its points in point order and clamps at
+//                      max_voxels; workgroup (0, 0) also writes the scene counts and offsets (k_vox_offsets).
+#define VOX_CHUNK 1024
+
+__device__ __forceinline__ unsigned vox_creator_flags(const int* __restrict__ scene_off, int hsize, const unsigned* __restrict__ first,
+                                                      const int* __restrict__ slot_of, int b, int chunk, int& sl,
+                                                      unsigned& in_chunk_before, unsigned* wsum) {
+  // -> 1 when this thread's point created its cell; in_chunk_before: creators of the chunk in front of it; wsum[16]: per wave
+  const int p0 = scene_off[b], n = scene_off[b + 1] - p0;
+  const int il = chunk * VOX_CHUNK + (int)threadIdx.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  sl = -1;
+  unsigned flag = 0;
+  if (il < n) {
+    sl = slot_of[p0 + il];
+    if (sl >= 0 && first[(long long)b * hsize + sl] == (unsigned)il) flag = 1;
+  }
+  const unsigned long long bal = __ballot(flag);
+  if (lane == 0) wsum[wid] = __popcll(bal);
+  __syncthreads();
+  unsigned woff = 0;
+  for (int w = 0; w < 16; ++w) woff += (w < wid) ? wsum[w] : 0u;
+  in_chunk_before = woff + __popcll(bal & ((1ull << lane) - 1ull));
+  return flag;
+}
+
+__global__ __launch_bounds__(VOX_CHUNK) void k_vox_chunk_count(const int* __restrict__ scene_off, int hsize,
+                                                               const unsigned* __restrict__ first, const int* __restrict__ slot_of,
+                                                               unsigned* __restrict__ chunk_cnt) {
+  __shared__ unsigned wsum[16];
+  int sl;
+  unsigned before;
+  vox_creator_flags(scene_off, hsize, first, slot_of, blockIdx.y, blockIdx.x, sl, before, wsum);
+  if (threadIdx.x == 0) {
+    unsigned tot = 0;
+    for (int w = 0; w < 16; ++w) tot += wsum[w];
+    chunk_cnt[blockIdx.y * gridDim.x + blockIdx.x] = tot;
+  }
+}
+
+__device__ __forceinline__ unsigned vox_wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(VOX_CHUNK) void k_vox_rank_chunks(const int* __restrict__ scene_off, VoxCfg cfg, int B,
+                                                               const unsigned* __restrict__ first, const int* __restrict__ slot_of,
+                                                               const unsigned* __restrict__ chunk_cnt, int* __restrict__ vid,
+                                                               int* __restrict__ scene_cnt, int* __restrict__ voxel_off) {
+  __shared__ unsigned wsum[16];
+  __shared__ unsigned csum[16];
+  const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  unsigned carry = 0;
+  for (int j = threadIdx.x; j < chunk; j += VOX_CHUNK) carry += chunk_cnt[b * nchunk + j];
+  carry = vox_wave_sum(carry);
+  if (lane == 0) csum[wid] = carry;
+  int sl;
+  unsigned before;
+  const unsigned flag = vox_creator_flags(scene_off, cfg.hsize, first, slot_of, b, chunk, sl, before, wsum);   // (barrier: csum too)
+  carry = 0;
+  for (int w = 0; w < 16; ++w) carry += csum[w];
+  if (flag) {
+    const unsigned r = carry + before;
+    vid[(long long)b * cfg.hsize + sl] = (r < (unsigned)cfg.max_voxels) ? (int)r : -1;
+  }
+  if (b == 0 && chunk == 0) {
+    for (int sb = wid; sb < B; sb += 16) {      // one wave per scene
+      unsigned tot = 0;
+      for (int j = lane; j < nchunk; j += 64) tot += chunk_cnt[sb * nchunk + j];
+      tot = vox_wave_sum(tot);
+      if (lane == 0) scene_cnt[sb] = (int)min(tot, (unsigned)cfg.max_voxels);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int acc = 0;
+      for (int sb = 0; sb < B; ++sb) { voxel_off[sb] = acc; acc += scene_cnt[sb]; }
+      voxel_off[B] = acc;
+    }
+  }
+}
+
 __global__ void k_vox_offsets(const int* __restrict__ scene_cnt, int B, int* __restrict__ voxel_off) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     int acc = 0;
@@ -584,7 +895,7 @@ __global__ void k_fill_u32(unsigned* __restrict__ p, long long n, unsigned v) {
 
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-struct VoxWs { unsigned* keys; unsigned* first; int* head; int* vid; int* next; int* slot_of; int* scene_cnt; int hsize; int64_t bytes; };
+struct VoxWs { unsigned* keys; unsigned* first; int* head; int* vid; int* next; int* slot_of; int* scene_cnt; unsigned* chunk_cnt; int hsize; int nchunk; int64_t bytes; };
 
 static VoxWs vox_ws_layout(void* base, int n_total, int B, int max_pts_per_scene) {
   VoxWs w;
@@ -598,6 +909,8 @@ static VoxWs vox_ws_layout(void* base, int n_total, int B, int max_pts_per_scene
   w.next = (int*)p; p += (size_t)n_total * 4;
   w.slot_of = (int*)p; p += (size_t)n_total * 4;
   w.scene_cnt = (int*)p; p += (size_t)(B + 1) * 4;
+  w.nchunk = ((max_pts_per_scene > 1 ? max_pts_per_scene : 1) + VOX_CHUNK - 1) / VOX_CHUNK;
+  w.chunk_cnt = (unsigned*)p; p += (size_t)B * w.nchunk * 4;      // two-level ranks: creators per (scene, 1024-point chunk)
   w.bytes = (int64_t)(p - (char*)base);
   return w;
 }
@@ -606,11 +919,11 @@ extern "C" int64_t u3d_voxelize_hard_workspace(int32_t n_total, int32_t batch, i
   return vox_ws_layout(nullptr, n_total, batch, max_pts_per_scene).bytes;
 }
 
-extern "C" int32_t u3d_voxelize_hard(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total,
-                                     int32_t max_pts_per_scene, int32_t nfeat, const float voxel_size[3],
-                                     const float pc_range[6], int32_t max_points, int32_t max_voxels, float* voxels,
-                                     int32_t* coors, int32_t* num_points, float* mean, int32_t* voxel_off,
-                                     void* workspace, int64_t workspace_bytes, u3d_stream s) {
+static int32_t voxelize_hard(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total,
+                             int32_t max_pts_per_scene, int32_t nfeat, const float voxel_size[3],
+                             const float pc_range[6], int32_t max_points, int32_t max_voxels, float* voxels,
+                             int32_t* coors, int32_t* num_points, float* mean, int32_t* voxel_off,
+                             void* workspace, int64_t workspace_bytes, bool chunk_ranks, u3d_stream s) {
   U3D_REQUIRE(points && scene_off && coors && num_points && voxel_off && workspace, U3D_ERR_ARG);
   U3D_REQUIRE(batch > 0 && n_total >= 0 && nfeat >= 3 && nfeat <= 8 && max_points > 0 && max_voxels > 0, U3D_ERR_ARG);
   VoxWs w = vox_ws_layout(workspace, n_total, batch, max_pts_per_scene);
@@ -633,9 +946,16 @@ extern "C" int32_t u3d_voxelize_hard(const float* points, const int32_t* scene_o
     hipLaunchKernelGGL(k_vox_insert, dim3(u3d_cdiv(n_total, 256)), dim3(256), 0, s, points, scene_off, batch, n_total, cfg,
                        w.keys, w.first, w.head, w.next, w.slot_of);
   }
-  hipLaunchKernelGGL(k_vox_rank, dim3(batch), dim3(1024), 0, s, scene_off, cfg, (const unsigned*)w.first,
-                     (const int*)w.slot_of, w.vid, w.scene_cnt);
-  hipLaunchKernelGGL(k_vox_offsets, dim3(1), dim3(64), 0, s, (const int*)w.scene_cnt, batch, voxel_off);
+  if (chunk_ranks) {
+    hipLaunchKernelGGL(k_vox_chunk_count, dim3(w.nchunk, batch), dim3(VOX_CHUNK), 0, s, scene_off, w.hsize, (const unsigned*)w.first,
+                       (const int*)w.slot_of, w.chunk_cnt);
+    hipLaunchKernelGGL(k_vox_rank_chunks, dim3(w.nchunk, batch), dim3(VOX_CHUNK), 0, s, scene_off, cfg, batch,
+                       (const unsigned*)w.first, (const int*)w.slot_of, (const unsigned*)w.chunk_cnt, w.vid, w.scene_cnt, voxel_off);
+  } else {
+    hipLaunchKernelGGL(k_vox_rank, dim3(batch), dim3(1024), 0, s, scene_off, cfg, (const unsigned*)w.first,
+                       (const int*)w.slot_of, w.vid, w.scene_cnt);
+    hipLaunchKernelGGL(k_vox_offsets, dim3(1), dim3(64), 0, s, (const int*)w.scene_cnt, batch, voxel_off);
+  }
   if (n_total > 0) {
     hipLaunchKernelGGL(k_vox_write, dim3(u3d_cdiv(n_total, 256)), dim3(256), 0, s, points, scene_off, batch, n_total, cfg,
                        (const unsigned*)w.keys, (const unsigned*)w.first, (const int*)w.head, (const int*)w.next,
@@ -645,6 +965,22 @@ extern "C" int32_t u3d_voxelize_hard(const float* points, const int32_t* scene_o
   return U3D_OK;
 }
 
+extern "C" int32_t u3d_voxelize_hard(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total,
+                                     int32_t max_pts_per_scene, int32_t nfeat, const float voxel_size[3],
+                                     const float pc_range[6], int32_t max_points, int32_t max_voxels, float* voxels,
+                                     int32_t* coors, int32_t* num_points, float* mean, int32_t* voxel_off,
+                                     void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  return voxelize_hard(points, scene_off, batch, n_total, max_pts_per_scene, nfeat, voxel_size, pc_range, max_points, max_voxels, voxels,
+                       coors, num_points, mean, voxel_off, workspace, workspace_bytes, false, s);
+}
+extern "C" int32_t u3d_voxelize_hard_chunked(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total,
+                                             int32_t max_pts_per_scene, int32_t nfeat, const float voxel_size[3],
+                                             const float pc_range[6], int32_t max_points, int32_t max_voxels, float* voxels,
+                                             int32_t* coors, int32_t* num_points, float* mean, int32_t* voxel_off,
+                                             void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  return voxelize_hard(points, scene_off, batch, n_total, max_pts_per_scene, nfeat, voxel_size, pc_range, max_points, max_voxels, voxels,
+                       coors, num_points, mean, voxel_off, workspace, workspace_bytes, true, s);
+}
 
 // ============================================================================================
 // Dynamic voxelization + scatter-mean (DynamicSimpleVFE)

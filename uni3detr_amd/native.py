@@ -146,14 +146,35 @@ class BitGrid:
         _check(lib().u3d_bitgrid_coords(C.byref(self.c), _ptr(out), n, _stream()), "bitgrid_coords")
         return out
 
+    def scan_coords(self, n):
+        """scan() + coords(n); in two launches where FUSED_SCAN_COORDS and the library's route allow (u3d_bitgrid_scan_coords)."""
+        if not FUSED_SCAN_COORDS:
+            self.scan()
+            return self.coords(n)
+        out = torch.empty((n, 4), dtype=torch.int32, device=self.words.device)
+        _check(lib().u3d_bitgrid_scan_coords(C.byref(self.c), _ptr(self._scratch), _ptr(out), n, _stream()), "bitgrid_scan_coords")
+        return out
+
     def nbr_table(self, q_coors, n_dev, ksize, stride, pad, mode):
         n = q_coors.shape[0]
         ld = (n + 127) // 128 * 128
         kvol = ksize[0] * ksize[1] * ksize[2]
         nbr = torch.empty((kvol, ld), dtype=torch.int32, device=q_coors.device)
+        # route, decided here from host values: the 3x3x3 kernel on a block-major grid with 32-bit indices, else the generic one
+        if (NBR_TABLE_K3 and tuple(ksize) == (3, 3, 3) and not self.linear and min(pad) >= 0 and self.nwords < 2 ** 31
+                and 27 * ld < 2 ** 31):
+            _check(lib().u3d_nbr_table_k3(C.byref(self.c), _ptr(q_coors), _ptr(n_dev), n, _I3(*stride), _I3(*pad), mode, _ptr(nbr), ld,
+                                          _stream()), "nbr_table_k3")
+            return nbr
         _check(lib().u3d_nbr_table(C.byref(self.c), _ptr(q_coors), _ptr(n_dev), n, _I3(*ksize), _I3(*stride), _I3(*pad),
                                    mode, _ptr(nbr), ld, _stream()), "nbr_table")
         return nbr
+
+
+# A/B routes of the geometry build (tests/test_geometry_build_gpu.py runs both sides of each; no environment switch reads them)
+NBR_TABLE_K3 = True          # 3x3x3 tables: 8 words + 8 prefixes loaded at once per row (False: the generic kernel, 54 dependent loads)
+FUSED_SCAN_COORDS = True     # BitGrid.scan_coords in two launches (False: scan() + coords(), four)
+VOX_CHUNK_RANKS = True       # voxelize_hard ranks over (scene, chunk) workgroups (False: one workgroup per scene + an offsets launch)
 
 
 def dense_nbr_table(batch, q_dims, t_dims, ksize, stride, pad, mode, device):
@@ -184,9 +205,10 @@ def voxelize_hard(points, scene_off, batch, max_pts_per_scene, voxel_size, pc_ra
     voxel_off = torch.empty((batch + 1,), dtype=torch.int32, device=dev)
     wsb = int(lib().u3d_voxelize_hard_workspace(n_total, batch, max_pts_per_scene))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _check(lib().u3d_voxelize_hard(_ptr(points), _ptr(scene_off), batch, n_total, max_pts_per_scene, nfeat,
-                                   _F3(*voxel_size), _F6(*pc_range), max_points, max_voxels, _ptr(voxels), _ptr(coors),
-                                   _ptr(num), _ptr(mean), _ptr(voxel_off), _ptr(ws), wsb, _stream()), "voxelize_hard")
+    fn = lib().u3d_voxelize_hard_chunked if VOX_CHUNK_RANKS else lib().u3d_voxelize_hard
+    _check(fn(_ptr(points), _ptr(scene_off), batch, n_total, max_pts_per_scene, nfeat,
+              _F3(*voxel_size), _F6(*pc_range), max_points, max_voxels, _ptr(voxels), _ptr(coors),
+              _ptr(num), _ptr(mean), _ptr(voxel_off), _ptr(ws), wsb, _stream()), "voxelize_hard")
     return voxels, coors, num, mean, voxel_off
 
 

@@ -107,11 +107,11 @@ def level_from_coors(coors, batch, dims):
     dev = coors.device
     g = nv.BitGrid(batch, dims, dev)
     g.mark(coors)
-    g.scan()
     n = coors.shape[0]
+    coords = g.scan_coords(n)
     g.set_row_capacity(n)          # unique coors => count <= n always; guards static-shape buffers all the same
     rank = g.rank(coors)
-    lvl = Level(g, g.coords(n), n, g.count_dev)
+    lvl = Level(g, coords, n, g.count_dev)
     return lvl, rank
 
 
@@ -130,11 +130,15 @@ def strided_level(lvl, ksize, stride, pad, capacity=None):
     dims_out = tuple((d + 2 * p - k) // s + 1 for d, k, s, p in zip(lvl.dims, ksize, stride, pad))
     g = nv.BitGrid(lvl.batch, dims_out, lvl.coords.device)
     g.mark_strided(lvl.coords, lvl.n_dev, ksize, stride, pad)
-    g.scan()
-    n_out = int(g.count_dev.item()) if capacity is None else int(capacity)
-    if capacity is not None:
+    if capacity is None:           # the row count sizes the list: scan, read it, then the coordinates
+        g.scan()
+        n_out = int(g.count_dev.item())
+        coords = g.coords(n_out)
+    else:
+        n_out = int(capacity)
+        coords = g.scan_coords(n_out)
         g.set_row_capacity(n_out)
-    out = Level(g, g.coords(n_out), n_out, g.count_dev)
+    out = Level(g, coords, n_out, g.count_dev)
     fwd = lvl.grid.nbr_table(out.coords, out.n_dev, ksize, stride, pad, 0)
     bwd = g.nbr_table(lvl.coords, lvl.n_dev, ksize, stride, pad, 1)
     return out, ConvGeom(fwd, bwd, lvl.n, lvl.n_dev, n_out, out.n_dev, strided=True)
