@@ -273,31 +273,10 @@ int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const int32_t* n
 /* The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (has_nbr: a neighbour table is passed), computed by the plan the
  * launch follows: *partials row tiles of *rows_per_partial rows (= rows_per_block of u3d_bn_finalize_partials), or with
  * *rows_per_partial = 0 one partial per WAVE of the direct-operand kernels of the narrow 27-offset levels (every partial counts).
- * U3D_ERR_UNSUPPORTED: no kernel with a statistics epilogue serves the shape.  u3d_igemm_fwd_split_bf16 and
- * u3d_igemm_dgrad_bnstats_bf16 write the same row-tile layout wherever they serve a shape. */
+ * U3D_ERR_UNSUPPORTED: no kernel with a statistics epilogue serves the shape.  u3d_igemm_fwd_split_bf16 writes
+ * the same row-tile layout wherever it serves a shape. */
 int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
                                    int32_t* rows_per_partial);
-/* BatchNorm-BACKWARD statistics out of the input-gradient launch that writes the BatchNorm's dy (ref: the conv -> BatchNorm -> ReLU
- * chains of sparse_encoder_hd.py:71-104 / second_3d.py:52-76; torch's batch_norm_backward makes a separate reduction pass over dy and
- * x).  x: the BatchNorm's input (bf16 [n][C]); y: its output when the ReLU mask cannot be recomputed from x (residual layers), else
- * NULL; mean/invstd (+ gamma/beta when relu and y == NULL) f32 [C].  The launch leaves, per row tile, sum(g) and sum(g * xhat) with
- * g = dy under the ReLU mask: f64 [partials][2][C] as u3d_igemm_fwd_stats_layout(.., 1, ..) reports (128-row tiles for the halo kernel), which
- * u3d_bn_bwd_finalize_partials reduces to what u3d_bn_bwd_stats returns. */
-typedef struct {
-  const void* x;
-  const void* y;
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;
-  int32_t relu;
-  int32_t reserved;
-} u3d_bn_epi;
-int32_t u3d_igemm_dgrad_bnstats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
-                                     const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                     const u3d_bn_epi* bn, double* stats, u3d_stream s);
-int32_t u3d_bn_bwd_finalize_partials(const double* partial, int32_t nblocks, int32_t rows_per_block, const int32_t* n_dev,
-                                     int32_t n_cap, int32_t c, double* sums, float* sums_f32, u3d_stream s);
 /* Output-stationary path of the 64 -> 64 channel, 27-offset submanifold convs (the stride-4 stage's SparseBasicBlocks, ref:
  * sparse_encoder_hd.py:106-138): rows are numbered in 4x4x4-block-major order, so the 27 x 128 table entries of a 128-row tile name
  * only a few hundred DISTINCT rows.  u3d_subm_halo_build (once per level and step) leaves, per tile, the sorted distinct rows
@@ -307,8 +286,7 @@ int32_t u3d_bn_bwd_finalize_partials(const double* partial, int32_t nblocks, int
  * u3d_subm_halo_conv64_bf16 then computes what u3d_igemm_fwd_bf16 (transpose_w = 1) /
  * u3d_igemm_fwd_add_bf16 / u3d_igemm_fwd_stats_bf16 compute from the table: in/out/addend bf16 [n][64]; w_packed =
  * u3d_subm_halo_wpack of the n-major bf16 weights [27][64][64] (MFMA fragment order, same size); krev != 0 reads the offsets reversed (the transposed table of a SubM layer: input gradients, pass [K][Cin][Cout]);
- * addend nullable; stats nullable f64 [tiles][2][64] (128 rows per partial, as u3d_bn_finalize_partials takes them); bn nullable:
- * with it the statistics are the BatchNorm-backward sums described at u3d_bn_epi above, instead of the output's own. */
+ * addend nullable; stats nullable f64 [tiles][2][64] (128 rows per partial, as u3d_bn_finalize_partials takes them). */
 int32_t u3d_subm_halo_sizes(int32_t n_cap, int64_t* tile_rows_elems, int64_t* loc_elems, int32_t* tiles);
 int32_t u3d_subm_halo_build(const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t* tile_rows,
                             uint16_t* loc, int32_t* tile_cnt, int32_t kvol, u3d_stream s);
@@ -318,8 +296,7 @@ int32_t u3d_subm_halo_wpack(const void* w_nmajor, void* w_packed, u3d_stream s);
 int32_t u3d_subm_halo_wpack_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, u3d_stream s);
 int32_t u3d_subm_halo_conv64_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
                                   const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
-                                  const void* addend, void* out, double* stats, const u3d_bn_epi* bn, int32_t max_slots,
-                                  u3d_stream s);
+                                  const void* addend, void* out, double* stats, int32_t max_slots, u3d_stream s);
 /* The same for 128 -> 128 channels (the stride-8 stage): in/out/addend bf16 [n][128], w_packed = u3d_subm_halo_wpack128 of the n-major
  * bf16 weights [kvol][128][128]; stats f64 [tiles][2][128].  Tables from u3d_subm_halo_build (they do not depend on the channel count).
  * kvol <= 27 offsets (the build takes the same kvol; loc keeps 27 slots per tile): 27 for the sparse SubM levels, 9 for the stride-1

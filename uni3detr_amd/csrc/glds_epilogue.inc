@@ -1,6 +1,6 @@
 // Epilogue of the LDS-DMA forward/dgrad kernels, included textually into each kernel body (a helper taking the accumulator
 // array by reference cost the 256x256 kernel its register allocation: 256 VGPRs + spills, 25.4 -> 27.5 ms per step).
-// Expects in scope: acc, smem, m0, col0, tile, n_out, cout, out, bias, relu, stats, bn, wm, wn, g, li, tid, NW, BN, WAVES_M, WM, WN, F32OUT.
+// Expects in scope: acc, smem, m0, col0, tile, n_out, cout, out, bias, relu, stats, wm, wn, g, li, tid, NW, BN, WAVES_M, WM, WN, F32OUT.
 // bias / ReLU, bf16 store (transposed accumulator: 4 consecutive columns per lane), optional per-tile BatchNorm statistics.
   // epilogue: acc[a][b][r] = C[row (wm*WM+a)*16 + li][col (wn*WN+b)*16 + 4g + r]; v_cvt_pk_bf16_f32 (RNE) via convertvector
   f32x4 cs[WN], cq[WN];                                 // BatchNorm statistics of this wave's rows: column sums / sums of squares
@@ -39,23 +39,12 @@
         *(bf16x4*)(out + (long long)m * cout + col) = o;
         if (stats) {                                    // statistics of the ROUNDED values: what the BatchNorm that follows reads
           const f32x4 vr = __builtin_convertvector(o, f32x4);
-          if (GLDS_EPI_ADDEND && bn.x) {
-            // BatchNorm-backward sums (bn_bwd_tile_sums below): the rounded dy tile also goes to the dead stage buffers, 16 B chunks
-            // of a row XOR-swizzled with the row number (the 16 rows x 2 chunks of this store spread over all banks)
-            constexpr int CPR = BN / 8, SWZ = (CPR - 1) & 15;
-            const int row = (wm * WM + a) * 16 + li, cc = (wn * WN + b) * 2 + (g >> 1);
-            *(bf16x4*)(smem + ((row * CPR + (cc ^ (row & SWZ))) * 8 + (g & 1) * 4)) = o;
-          } else {
-            cs[b] += vr;
-            cq[b] += vr * vr;
-          }
+          cs[b] += vr;
+          cq[b] += vr * vr;
         }
       }
     }
   }
-  if (GLDS_EPI_ADDEND && stats && bn.x) {
-    bn_bwd_tile_sums<BM, BN, NW * 64>(bn, smem, m0, col0, n_out, cout, tile, stats, tid);
-  } else
   if (stats) {
     // the BatchNorm behind this conv needs per-column sum / sum of squares over ALL rows: reduce this tile here (16 lanes of a
     // column group by shuffles, the row waves through LDS) and leave one f64 partial per (row tile, column) - the separate

@@ -13,87 +13,6 @@
 #include "conv_in.h"
 #include "igemm_direct.h"
 
-// BatchNorm-BACKWARD statistics in the epilogue of an input-gradient launch (glds_epilogue.inc; == u3d_bn_epi of the C ABI): the
-// tensor this launch writes is dy of the BatchNorm that produced the conv's input, so sum(g) and sum(g * xhat) (g = dy under the
-// ReLU mask) can leave per row tile with the store - the separate pass over dy and x (k_col_stats_vec) disappears.
-struct BnEpi {
-  const u16* x = nullptr;        // the BatchNorm's input (bf16 [n][C]); nullptr: off
-  const u16* y = nullptr;        // its output, for the ReLU mask of layers with a residual; nullptr: mask recomputed from x
-  const float *mean = nullptr, *invstd = nullptr, *gamma = nullptr, *beta = nullptr;
-  int relu = 0, pad = 0;
-};
-// BatchNorm-backward sums of one BM x BN output tile whose rounded dy the epilogue left in LDS (16 B chunks, XOR-swizzled rows):
-// the per-tile form of k_col_stats_vec<., 1> (rowops.hip) - a thread owns 8 columns and every R-th row, x (and y for the mask of
-// layers with a residual) arrive by coalesced 16 B loads, the R row lanes are added in a fixed order, one f64 partial per
-// (tile, column) leaves.  It does not touch the accumulators (dead by then): a pass over the MFMA fragments cost the kernels their
-// register allocation (128 x 128 tiles: 180 -> 288 VGPRs; so did calling this out of line), and fragment-shaped 8 B global loads of
-// x made every (row block, column block) step wait for its own round trip (+35 us per launch).
-template <int BM, int BN, int NT>
-__device__ __forceinline__ void bn_bwd_tile_sums(const BnEpi bn, u16* smem, int m0, int col0, int n_out, int cout, int tile,
-                                              double* __restrict__ stats, int tid) {
-  constexpr int CPR = BN / 8, SWZ = (CPR - 1) & 15, R = NT / CPR, ROWS = BM / R, BATCH = ROWS < 8 ? ROWS : (ROWS % 8 == 0 ? 8 : (ROWS % 6 == 0 ? 6 : 4));
-  static_assert(NT % CPR == 0 && BM % R == 0 && ROWS % BATCH == 0, "tile / thread mismatch");
-  const int cc = tid % CPR, r0 = tid / CPR;
-  const int col = col0 + cc * 8;
-  const bool from_y = bn.relu && bn.y, remask = bn.relu && !bn.y;
-  float s0[8], s1[8], mu[8], is[8], ga[8], be[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { s0[e] = 0.f; s1[e] = 0.f; mu[e] = 0.f; is[e] = 0.f; ga[e] = 0.f; be[e] = 0.f; }
-  __syncthreads();                                      // every wave's dy fragments are in LDS
-  if (col < cout) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { mu[e] = bn.mean[col + e]; is[e] = bn.invstd[col + e]; }
-    if (remask) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { ga[e] = bn.gamma[col + e]; be[e] = bn.beta[col + e]; }
-    }
-    for (int i0 = 0; i0 < ROWS; i0 += BATCH) {
-      bf16x8 xv[BATCH], yv[BATCH];
-#pragma unroll
-      for (int i = 0; i < BATCH; ++i) {
-        const int r = r0 + (i0 + i) * R;
-        const long long o = (long long)(m0 + r) * cout + col;
-        if (m0 + r < n_out) {
-          xv[i] = *(const bf16x8*)(bn.x + o);
-          if (from_y) yv[i] = *(const bf16x8*)(bn.y + o);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < BATCH; ++i) {
-        const int r = r0 + (i0 + i) * R;
-        if (m0 + r >= n_out) continue;
-        const bf16x8 dv = *(const bf16x8*)(smem + (r * CPR + (cc ^ (r & SWZ))) * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xh = ((float)xv[i][e] - mu[e]) * is[e];
-          float gm = (float)dv[e];
-          const float yy = from_y ? (float)yv[i][e] : xh * ga[e] + be[e];
-          if (bn.relu && !(yy > 0.f)) gm = 0.f;
-          s0[e] += gm;
-          s1[e] += gm * xh;
-        }
-      }
-    }
-  }
-  __syncthreads();                                      // the dy tile is dead: the buffers take the row lanes' sums
-  float* red = (float*)smem;                            // [2][R][BN]
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    red[(0 * R + r0) * BN + cc * 8 + e] = s0[e];
-    red[(1 * R + r0) * BN + cc * 8 + e] = s1[e];
-  }
-  __syncthreads();
-  for (int t = tid; t < 2 * BN; t += NT) {
-    const int which = t / BN, cl = t % BN;
-    if (col0 + cl < cout) {
-      double a = 0.0;
-#pragma unroll 4
-      for (int k = 0; k < R; ++k) a += (double)red[(which * R + k) * BN + cl];
-      stats[((long long)tile * 2 + which) * cout + col0 + cl] = a;
-    }
-  }
-}
-
 #ifndef IGEMM_SMALL_WM
 #define IGEMM_SMALL_WM 4   /* 16-row blocks per wave: 4 waves x 4 = 256-row tiles */
 #endif
@@ -342,7 +261,7 @@ template <int WAVES_M, int WAVES_N, int WM, int WN, bool F32OUT = false>
 __device__ __forceinline__ void igemm_glds_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr,
                                                 int ld, u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap,
                                                 int cin, int cout, int kvol, const float* __restrict__ bias, int relu,
-                                                double* __restrict__ stats, const BnEpi bn) {
+                                                double* __restrict__ stats) {
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int BM = WAVES_M * WM * 16, BN = WAVES_N * WN * 16, BK = 64;
   constexpr int A_ELEMS = BM * BK, W_ELEMS = BN * BK;   // unpadded tiles, 128 B per row
@@ -547,7 +466,7 @@ template <bool F32OUT = false, int RB = 4>
 __device__ __forceinline__ void igemm_glds8_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr,
                                                  int ld, u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap,
                                                  int cin, int cout, int kvol, const float* __restrict__ bias, int relu,
-                                                 double* __restrict__ stats, const BnEpi bn) {
+                                                 double* __restrict__ stats) {
   constexpr int WAVES_M = 2, WAVES_N = 4, WM = 2 * RB, WN = 4, NW = 8;
   constexpr int BM = 64 * RB, BN = 256, BK = 64;
   constexpr int PIECE = 128 * BK;                         // elements of one piece (16 KiB)
@@ -754,23 +673,23 @@ __device__ __forceinline__ void igemm_glds8_body(const u16* __restrict__ in, con
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_256x256(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                              const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                             const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8_body(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                             const float* bias, int relu, double* stats) {
+  igemm_glds8_body(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_256x256_f32o(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                                   const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                                  const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8_body<true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                                  const float* bias, int relu, double* stats) {
+  igemm_glds8_body<true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_192x256(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                              const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                             const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8_body<false, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                             const float* bias, int relu, double* stats) {
+  igemm_glds8_body<false, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_192x256_f32o(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                                   const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                                  const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8_body<true, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                                  const float* bias, int relu, double* stats) {
+  igemm_glds8_body<true, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 // 192-row tiles instead of 256-row ones when they finish sooner on 256 CUs with one workgroup each (time ~ rounds x tile rows): the
 // mid-size layers of the dense stack (48 000 rows x 256 columns: 188 -> 250 workgroups, 12 000 rows x 512 columns in 128-column
@@ -797,7 +716,7 @@ template <bool F32OUT = false, int RB = 4>      // RB = 3: 192-row tiles (48 liv
 __device__ __forceinline__ void igemm_glds8n_body(const u16* __restrict__ in, const u16* __restrict__ w, const int* __restrict__ nbr,
                                                   int ld, u16* __restrict__ out, const int* __restrict__ n_out_dev, int n_out_cap,
                                                   int cin, int cout, int kvol, const float* __restrict__ bias, int relu,
-                                                  double* __restrict__ stats, const BnEpi bn) {
+                                                  double* __restrict__ stats) {
   constexpr int WAVES_M = 4, WAVES_N = 2, WM = RB, WN = 4, NW = 8;
   constexpr int BM = 64 * RB, BN = 128, BK = 64;
   constexpr int APIECE = 128 * BK, BPIECE = 64 * BK;
@@ -985,30 +904,30 @@ __device__ __forceinline__ void igemm_glds8n_body(const u16* __restrict__ in, co
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_256x128(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                              const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                             const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8n_body(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                             const float* bias, int relu, double* stats) {
+  igemm_glds8n_body(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_256x128_f32o(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                                   const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                                  const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8n_body<true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                                  const float* bias, int relu, double* stats) {
+  igemm_glds8n_body<true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_192x128(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                              const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                             const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8n_body<false, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                             const float* bias, int relu, double* stats) {
+  igemm_glds8n_body<false, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 __global__ __launch_bounds__(512) void k_igemm_glds8_192x128_f32o(const u16* in, const u16* w, const int* nbr, int ld, u16* out,
                                                                   const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,
-                                                                  const float* bias, int relu, double* stats, BnEpi bn) {
-  igemm_glds8n_body<true, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);
+                                                                  const float* bias, int relu, double* stats) {
+  igemm_glds8n_body<true, 3>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);
 }
 // concrete kernels (a __global__ TEMPLATE with this body lost its host stub under hipcc 7.2: undefined symbol at load time)
 #define U3D_GLDS_KERNEL(NAME, A, B, C, D)                                                                                        \
   __global__ __launch_bounds__(A* B * 64) void NAME(const u16* in, const u16* w, const int* nbr, int ld, u16* out,               \
                                                     const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,            \
-                                                    const float* bias, int relu, double* stats, BnEpi bn) {                      \
-    igemm_glds_body<A, B, C, D>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);               \
+                                                    const float* bias, int relu, double* stats) {                                \
+    igemm_glds_body<A, B, C, D>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);                   \
   }
 #define U3D_GLDS_KERNEL_X(NAME, ...) U3D_GLDS_KERNEL(NAME, __VA_ARGS__)
 U3D_GLDS_KERNEL_X(k_igemm_glds_256x256, GLDS256_CFG)
@@ -1022,24 +941,24 @@ U3D_GLDS_KERNEL(k_igemm_glds_128x128, 2, 2, 4, 4)      /* 4 waves, 64 KiB LDS: t
 #define U3D_GLDS_KERNEL_F32O(NAME, A, B, C, D)                                                                                   \
   __global__ __launch_bounds__(A* B * 64) void NAME(const u16* in, const u16* w, const int* nbr, int ld, u16* out,               \
                                                     const int* n_out_dev, int n_out_cap, int cin, int cout, int kvol,            \
-                                                    const float* bias, int relu, double* stats, BnEpi bn) {                      \
-    igemm_glds_body<A, B, C, D, true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats, bn);         \
+                                                    const float* bias, int relu, double* stats) {                                \
+    igemm_glds_body<A, B, C, D, true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, bias, relu, stats);             \
   }
 U3D_GLDS_KERNEL_F32O(k_igemm_glds_128x64_f32o, 4, 1, 2, 4)
 U3D_GLDS_KERNEL_F32O(k_igemm_glds_128x128_f32o, 2, 2, 4, 4)
 #undef U3D_GLDS_KERNEL_F32O
-typedef void (*glds_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const float*, int, double*, BnEpi);
+typedef void (*glds_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const float*, int, double*);
 
 // (The register-staged "ping-pong" kernel of round 1 - two wave groups in opposite phases, measured on par with k_igemm_fwd -
 //  was removed when igemm_glds8_body took that idea to the LDS-DMA kernels; DESIGN.md 3.1 keeps its numbers.)
 
 // =============================================================================================
 // ONE launch plan for the forward / input-gradient launches on the LDS-DMA and the direct-operand kernels: fwd_plan() decides the
-// kernel, tile, grid and statistics layout of u3d_igemm_fwd_bf16 / _fwd_add_bf16 / _fwd_stats_bf16 / _fwd_split_bf16 /
-// _dgrad_bnstats_bf16 and u3d_linear_bf16, and u3d_igemm_fwd_stats_layout reports that same layout to size the buffers.
+// kernel, tile, grid and statistics layout of u3d_igemm_fwd_bf16 / _fwd_add_bf16 / _fwd_stats_bf16 / _fwd_split_bf16
+// and u3d_linear_bf16, and u3d_igemm_fwd_stats_layout reports that same layout to size the buffers.
 // =============================================================================================
 // The LDS-DMA kernels: bf16- and f32-output instantiations (nullptr: none), tile, threads, dynamic LDS, and whether the epilogue
-// takes an addend (relu & 2) and the BatchNorm-backward sums (GLDS_EPI_ADDEND).
+// takes an addend (relu & 2; GLDS_EPI_ADDEND).
 struct GldsKernel {
   glds_kernel_t bf16, f32;
   int rows, cols, threads;
@@ -1064,10 +983,9 @@ static const GldsKernel GLDS_KERNELS[G_COUNT] = {
 
 // what the launch must do besides the convolution: PLAIN (u3d_igemm_fwd_bf16), BIAS_RELU (u3d_linear_bf16), ADD = + bf16 addend
 // (u3d_igemm_fwd_add_bf16), F32 / F32_ADD = f32 output without / with an f32 addend (u3d_igemm_fwd_split_bf16; its statistics do not
-// change the kernel), STATS = + BatchNorm statistics (u3d_igemm_fwd_stats_bf16), BN_BWD = + BatchNorm-backward sums, addend optional
-// (u3d_igemm_dgrad_bnstats_bf16), AFFINE = + per-column f32 shift and optional ReLU on a CONVOLUTION (u3d_igemm_fwd_affine_bf16: an
-// eval-mode BatchNorm folded into the weights, bn_fold.hip)
-enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_BN_BWD, EPI_AFFINE };
+// change the kernel), STATS = + BatchNorm statistics (u3d_igemm_fwd_stats_bf16), AFFINE = + per-column f32 shift and
+// optional ReLU on a CONVOLUTION (u3d_igemm_fwd_affine_bf16: an eval-mode BatchNorm folded into the weights, bn_fold.hip)
+enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_AFFINE };
 
 struct FwdPlan {
   DirectPlan direct;             // direct.slot >= 0: a direct-operand kernel (igemm_direct.hip), else
@@ -1076,7 +994,7 @@ struct FwdPlan {
   dim3 grid;
   int threads = 0;
   size_t lds = 0;
-  int partials = 0;              // statistics partials a STATS / BN_BWD launch writes: [partials][2][cout]
+  int partials = 0;              // statistics partials a STATS launch writes: [partials][2][cout]
   bool served() const { return fn || direct.slot >= 0; }
 };
 
@@ -1090,7 +1008,7 @@ constexpr int GLDS8N_MIN_WGS = 160;       // ... and enough 256-row workgroups t
 //   BIAS_RELU (plain GEMM, its own thresholds): 256 x 256 two-phase if cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128,
 //      256 x 128 two-phase if cout % 128 == 0 and ceil(n / 256) * cout / 128 >= 128, else 128 x 64.
 //   2. cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128: with a table 256 x 256 eight-phase (192 x 256 when R192(cout / 256));
-//      without one the two-phase 256 x 256, which has no addend, f32-output or BatchNorm-backward epilogue (ADD, F32*, BN_BWD: none).
+//      without one the two-phase 256 x 256, which has no addend or f32-output epilogue (ADD, F32*: none).
 //   3. a table, cout % 128 == 0, kvol * cin / 64 >= GLDS8N_MIN_KTILES k-tiles, ceil(n / 256) * cout / 128 >= GLDS8N_MIN_WGS:
 //      256 x 128 eight-phase (192 x 128 when R192(cout / 128)).
 //   4. cout % 128 == 0: 128 x 128.
@@ -1123,7 +1041,7 @@ static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr
     g = cout % 128 == 0 ? G_128x128 : G_128x64;
   const GldsKernel& k = GLDS_KERNELS[g];
   const bool f32 = epi == EPI_F32 || epi == EPI_F32_ADD;
-  if (!k.addend && (epi == EPI_ADD || epi == EPI_F32_ADD || epi == EPI_BN_BWD)) return p;
+  if (!k.addend && (epi == EPI_ADD || epi == EPI_F32_ADD)) return p;
   p.fn = f32 ? k.f32 : k.bf16;
   if (!p.fn) return p;
   p.glds = g;
@@ -1136,15 +1054,15 @@ static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr
 }
 
 // bias: f32 bias (relu & 1: ReLU after it), or with relu & 2 the addend (bf16, or f32 for the f32-output kernels; the direct-operand
-// kernels take a bf16 addend here); stats / bn: the statistics epilogue of the plan's epilogue kind
+// kernels take a bf16 addend here); stats: the statistics epilogue of the plan's epilogue kind
 static int fwd_launch(const FwdPlan& p, const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
                       int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const void* bias = nullptr, int relu = 0,
-                      double* stats = nullptr, const BnEpi bn = BnEpi{}) {
+                      double* stats = nullptr) {
   if (p.direct.slot >= 0) return u3d_launch_igemm_direct(p.direct, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, s, bias, stats);
   static unsigned long long lds_mask[G_COUNT][2] = {};          // U3D_ALLOW_LDS's per-device mask, one per kernel
   if (p.lds > 64 * 1024) u3d_allow_lds_impl((const void*)p.fn, (int)p.lds, &lds_mask[p.glds][p.fn == GLDS_KERNELS[p.glds].f32]);
   hipLaunchKernelGGL(p.fn, p.grid, dim3(p.threads), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap, cin,
-                     cout, kvol, (const float*)bias, relu, stats, bn);
+                     cout, kvol, (const float*)bias, relu, stats);
   return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
 }
 
@@ -1188,8 +1106,8 @@ extern "C" int32_t u3d_igemm_fwd_affine_plan(int32_t n_out_cap, int32_t cin, int
   return U3D_OK;
 }
 
-// The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (fwd_plan, STATS).  u3d_igemm_fwd_split_bf16 and
-// u3d_igemm_dgrad_bnstats_bf16 write the same one wherever they serve the shape: there the plan never picks a direct-operand kernel.
+// The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (fwd_plan, STATS).  u3d_igemm_fwd_split_bf16 writes
+// the same one wherever it serves the shape: there the plan never picks a direct-operand kernel.
 extern "C" int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
                                               int32_t* rows_per_partial) {
   U3D_REQUIRE(partials && rows_per_partial, U3D_ERR_ARG);
@@ -1241,23 +1159,6 @@ extern "C" int32_t u3d_igemm_fwd_add_bf16(const void* in, const void* w, const i
   const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, true, transpose_w != 0, EPI_ADD);
   if (!p.served()) return U3D_ERR_UNSUPPORTED;
   return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, 2);
-}
-
-// Input gradient (n-major weights [K][Cin][Cout] as the dgrad passes them) + optional addend + the BatchNorm-BACKWARD statistics of the
-// layer that produced the conv's input, per row tile: stats f64 [partials][2][cout] = (sum g, sum g * xhat), the layout
-// u3d_igemm_fwd_stats_layout reports.  LDS-DMA kernels with the addend epilogue only (fwd_plan, BN_BWD): U3D_ERR_UNSUPPORTED otherwise
-// (the caller then runs u3d_igemm_fwd_add_bf16 / u3d_igemm_fwd_bf16 and u3d_bn_bwd_stats).
-extern "C" int32_t u3d_igemm_dgrad_bnstats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
-                                                const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                                const u3d_bn_epi* bn, double* stats, u3d_stream s) {
-  U3D_REQUIRE(in && w && out && n_out_dev && nbr && bn && bn->x && bn->mean && bn->invstd && stats, U3D_ERR_ARG);
-  U3D_REQUIRE(!bn->relu || bn->y || (bn->gamma && bn->beta), U3D_ERR_ARG);
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, true, true, EPI_BN_BWD);
-  if (!p.served()) return U3D_ERR_UNSUPPORTED;
-  BnEpi e;
-  e.x = (const u16*)bn->x; e.y = (const u16*)bn->y; e.mean = bn->mean; e.invstd = bn->invstd; e.gamma = bn->gamma; e.beta = bn->beta;
-  e.relu = bn->relu;
-  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, addend ? 2 : 0, stats, e);
 }
 
 extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,

@@ -358,7 +358,7 @@ def timed_end(region, tag, *shape, **price):
 def fwd_stats_layout(n_out, cin, cout, kvol, has_nbr):
     """(partials, rows per partial) of the statistics u3d_igemm_fwd_stats_bf16 writes for this shape, None when no kernel with a
     statistics epilogue serves it.  Rows 0: one partial per wave of the direct-operand kernels, all of them count (rows_per_block = 0
-    downstream).  u3d_igemm_fwd_split_bf16 / u3d_igemm_dgrad_bnstats_bf16 write the same layout wherever they serve the shape."""
+    downstream).  u3d_igemm_fwd_split_bf16 writes the same layout wherever it serves the shape."""
     p, r = C.c_int32(0), C.c_int32(0)
     if lib().u3d_igemm_fwd_stats_layout(n_out, cin, cout, kvol, int(has_nbr), C.byref(p), C.byref(r)) != 0:
         return None
@@ -384,50 +384,6 @@ def spconv_fwd_stats(inp, w_nmajor, nbr, n_out_dev, n_out, cout):
     if region is not None:      # (the shape facts are not even evaluated without a timer)
         timed_end(region, "spconv_fwd", inp.shape[0], n_out, cin, cout, kvol, nbr)
     return out, stats, tr
-
-
-class BnEpi(_struct("u3d_bn_epi", "_BnEpi")):
-    """u3d_bn_epi (include/u3d_hip.h): the BatchNorm whose dy an input-gradient launch writes."""
-
-    @staticmethod
-    def of(x, y, mean, invstd, gamma, beta, relu):
-        p = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        return BnEpi(p(x), p(y), p(mean), p(invstd), p(gamma), p(beta), int(relu), 0)
-
-
-def spconv_dgrad_bnstats(dout, w_nmajor, nbr, n_dev, n, cout, addend, epi):
-    """Input gradient (weights [K, Cout_gemm, Cin_gemm] n-major as the dgrad passes them) + addend + per-row-tile BatchNorm-backward
-    sums of the layer that produced the conv's input (u3d_igemm_dgrad_bnstats_bf16).  -> (din, partial f64 [tiles, 2, cout],
-    tile_rows) or None when no kernel with that epilogue serves the shape."""
-    kvol, cin = w_nmajor.shape[0], dout.shape[1]
-    if dout.dtype != torch.bfloat16 or not USE_IGEMM_V2 or nbr is None:
-        return None
-    layout = fwd_stats_layout(n, cin, cout, kvol, True)
-    if layout is None or layout[1] == 0:            # (per-wave partials: a direct-operand shape, which has no BatchNorm-backward epilogue)
-        return None
-    nblocks, tr = layout
-    out = torch.empty((n, cout), dtype=dout.dtype, device=dout.device)
-    stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=dout.device)
-    nbr_p, ld = _nbr_ptr_ld(nbr)
-    region = timed_begin()
-    rc = lib().u3d_igemm_dgrad_bnstats_bf16(_ptr(dout), _ptr(w_nmajor), nbr_p, ld, _ptr(addend), _ptr(out), _ptr(n_dev), n, cin, cout, kvol,
-                                            C.byref(epi), _ptr(stats), _stream())
-    if rc == U3D_ERR_UNSUPPORTED:
-        return None
-    _check(rc, "igemm_dgrad_bnstats_bf16")
-    if region is not None:
-        timed_end(region, "spconv_dgrad", dout.shape[0], n, cin, cout, kvol, nbr)
-    return out, stats, tr
-
-
-def bn_bwd_finalize_partials(partial, tile_rows, n_dev, n_cap):
-    """per-row-tile (sum g, sum g * xhat) -> what bn_bwd_stats(..., want_f32=True) returns."""
-    nb, _, c = partial.shape
-    sums = torch.empty((2, c), dtype=torch.float64, device=partial.device)
-    s32 = torch.empty((2, c), dtype=torch.float32, device=partial.device)
-    _check(lib().u3d_bn_bwd_finalize_partials(_ptr(partial), nb, tile_rows, _ptr(n_dev), n_cap, c, _ptr(sums), _ptr(s32), _stream()),
-           "bn_bwd_finalize_partials")
-    return sums, s32
 
 
 class SubmHalo:
@@ -499,21 +455,19 @@ def subm_halo_wpack_batched(plan):
         _check(lib().u3d_subm_halo_wpack128_batched(_ptr(plan[0]), _ptr(plan[1]), plan[2], plan[5], _stream()), "subm_halo_wpack128_batched")
 
 
-def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=False, tag="spconv_fwd", bn_epi=None, max_slots=0):
+def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=False, tag="spconv_fwd", max_slots=0):
     """64 -> 64 channel, 27-offset SubM conv out of the tile's staged distinct rows (u3d_subm_halo_conv64_bf16).
     w_packed: subm_halo_wpack of bf16 [27, 64 (out), 64 (reduction)].  -> out, or (out, stats f64 [tiles, 2, 64], 128) with want_stats."""
     c = inp.shape[1]
     assert inp.dtype == torch.bfloat16 and c in (64, 128) and tuple(w_packed.shape) == (halo.kvol, c, c) and inp.shape[0] == halo.n_cap
     assert c == 128 or halo.kvol == 27
-    assert c == 64 or bn_epi is None, "the BatchNorm-backward epilogue exists on the 64-channel kernel only"
     out = torch.empty_like(inp)
     stats = torch.empty((halo.tiles, 2, c), dtype=torch.float64, device=inp.device) if want_stats else None
     region = timed_begin()
     if c == 64:
         _check(lib().u3d_subm_halo_conv64_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
-                                               None if bn_epi is None else C.byref(bn_epi), int(max_slots), _stream()),
-               "subm_halo_conv64_bf16")
+                                               int(max_slots), _stream()), "subm_halo_conv64_bf16")
     else:
         _check(lib().u3d_subm_halo_conv128_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
                                                 _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),

@@ -52,25 +52,6 @@ class ResidualToken:
         self.dres = None
 
 
-class BnGradToken:
-    """Side channel from a BatchNorm (+ ReLU) layer to the ONE conv that consumes its output (or, in a residual block, to the block's
-    first conv, whose input gradient already includes the identity branch's: ResidualToken): that conv's input-gradient launch writes
-    the BatchNorm's dy, so its epilogue reduces the BatchNorm-backward sums (sum g, sum g * xhat) per row tile on the way out
-    (u3d_igemm_dgrad_bnstats_bf16 / the halo kernel) and leaves them here; the BatchNorm's backward then skips its own pass over dy
-    and x (u3d_bn_bwd_stats).  The caller vouches that no other consumer of the BatchNorm's output contributes a gradient."""
-
-    def __init__(self):
-        self.epi = None          # native.BnEpi of the producing layer (+ the tensors it points at, kept alive)
-        self.keep = None
-        self.partial = None      # (f64 [tiles, 2, C], tile_rows) left by the consumer's backward
-        self.c = 0
-
-    def fill(self, x, y, mean, invstd, gamma, beta, relu):
-        self.keep = (x, y, mean, invstd, gamma, beta)
-        self.epi = nv.BnEpi.of(x, y, mean, invstd, gamma, beta, relu)
-        self.c = x.shape[1]
-
-
 class FanoutToken:
     """Side channel between the first convs of `n` branches that take the SAME input (SECOND3D with is_cascade=False): autograd
     would add their input gradients with n - 1 element-wise passes over the full tensor.  Instead each conv's backward adds what the
@@ -330,7 +311,7 @@ def _finish_din(ctx, din, taken):
 
 class _SparseConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, weight, geom, layout, want_stats=False, res_token=None, fan_token=None, bn_in=None):
+    def forward(ctx, feats, weight, geom, layout, want_stats=False, res_token=None, fan_token=None):
         # weight: the PARAMETER in its checkpoint layout: "dhwio" [kD,kH,kW,Cin,Cout] (mmcv spconv-1.x) or "oidhw" (nn.Conv3d)
         # want_stats: also return the per-row-tile BatchNorm statistics of the output (empty tensor when the kernel serving this
         # shape does not produce them) - second, non-differentiable output
@@ -342,8 +323,6 @@ class _SparseConv(torch.autograd.Function):
         ctx.geom, ctx.layout = geom, layout
         ctx.res_token = res_token
         ctx.fan_token = fan_token if (fan_token is not None and feats.requires_grad) else None
-        ctx.bn_in = bn_in if (BN_GRAD_FUSION and bn_in is not None and bn_in.epi is not None and feats.dtype == torch.bfloat16
-                              and fan_token is None) else None
         # TrainStep: this parameter's slice of the flat gradient buffer - written in place by the backward ONLY if this is the
         # weight's single use in the step (a weight used twice gets two gradients that autograd must add: it may not alias them)
         _CONV_USES[id(weight)] = _CONV_USES.get(id(weight), 0) + 1
@@ -390,7 +369,7 @@ class _SparseConv(torch.autograd.Function):
     def backward(ctx, dout, _dstats=None):
         feats, wc = ctx.saved_tensors           # (a split route: the input's bf16 planes and the parameter)
         if dout is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         r, g = ctx.route, ctx.geom
         dout = dout.contiguous()
         nv.CALL_KIND = g.kind
@@ -407,7 +386,7 @@ class _SparseConv(torch.autograd.Function):
                 dw = _weight_grad(ctx, r, feats, dout)
             if want_din:
                 din, taken = _input_grad(ctx, r, wc, dout)
-        return _finish_din(ctx, din, taken), dw, None, None, None, None, None, None
+        return _finish_din(ctx, din, taken), dw, None, None, None, None, None
 
 
 def _weight_grad(ctx, r, feats, dout):
@@ -442,25 +421,11 @@ def _input_grad(ctx, r, wc, dout):
         if not (fits and fan is not None and add is fan.acc):                    # only the other branches' sum rides the gather
             add = None
         return nv.tap_gather_sum(prod, nbr, g.n_in_dev, g.n_in, cin, kvol, addend=add), add is not None
-    bt = ctx.bn_in
-    if bt is not None and (bt.c != cin or not (add is None or fits)):
-        bt = None
     if r.halo is not None:
-        if cin != 64:
-            bt = None                        # (the 128-channel halo kernel has no BatchNorm-backward epilogue)
         if not fits:
             add = None
         pk = ctx.pk_bwd if ctx.pk_bwd is not None else nv.subm_halo_wpack(wc)
-        din = nv.subm_halo_conv(dout, pk, r.halo, krev=True, addend=add, want_stats=bt is not None, tag="spconv_dgrad",
-                                bn_epi=None if bt is None else bt.epi)
-        if bt is not None:
-            din, st, tr = din
-            bt.partial = (st, tr)
-        return din, add is not None
-    res = nv.spconv_dgrad_bnstats(dout, wc, nbr, g.n_in_dev, g.n_in, cin, add, bt.epi) if (bt is not None and kvol > 1) else None
-    if res is not None:
-        bt.partial = (res[1], res[2])
-        return res[0], True
+        return nv.subm_halo_conv(dout, pk, r.halo, krev=True, addend=add, tag="spconv_dgrad"), add is not None
     # (an addend its epilogue cannot take - another shape or dtype, the first-generation kernel - nv.spconv_fwd adds after the launch)
     return nv.spconv_fwd(dout, wc, nbr, g.n_in_dev, g.n_in, cin, transpose_w=True, addend=add), True
 
@@ -512,12 +477,6 @@ def sparse_conv(feats, weight, geom, layout="dhwio", fan_token=None):
     return _SparseConv.apply(feats, weight, geom, layout, False, None, fan_token)
 
 
-# BatchNorm-backward sums out of the consumer's dgrad epilogue (BnGradToken).  Measured in the captured step (profiles/
-# r03_bn_grad_fusion_diff.txt): 24 of the 45 statistics passes disappear (-0.47 ms of k_col_stats_vec), but the conv launches that
-# take them over grow by +0.44 ms (per-tile sums in a tail that runs at one or two workgroups per CU: its x loads and ~8 VALU ops per
-# element are exposed, where the separate pass streams at full occupancy), and k_bn_bwd_apply loses the L2 hits the statistics pass
-# left behind (+0.05 ms): 19.77 -> 19.85 ms per step.  Kept (parity-tested) but off.
-BN_GRAD_FUSION = False
 FUSED_CONV_STATS = True
 
 
@@ -581,8 +540,7 @@ def conv_folded(feats, ent, geom, residual=None, relu=True):
     return None
 
 
-def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dhwio", post_add=None, res_take=None, res_give=None,
-            fan_token=None, bn_in=None, bn_out=None):
+def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dhwio", post_add=None, res_take=None, res_give=None, fan_token=None):
     """conv -> BatchNorm rows (+ residual) (+ ReLU).  In training the conv's epilogue already reduces the BatchNorm statistics per row
     tile where its kernel supports it (bf16, channels % 64 == 0): the separate statistics pass over the conv output disappears."""
     if _FOLD[0] is not None:
@@ -601,16 +559,14 @@ def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dh
         # res_take: this conv's input is the identity of a residual block - its backward sums the token's gradient into the input
         # gradient; res_give: this BatchNorm adds that identity - its backward leaves the identity's gradient in the token
         # fan_token: this conv is one of several that take the same input (FanoutToken)
-        # bn_in: BnGradToken of the BatchNorm that produced `feats`, when this conv's input gradient is that layer's whole dy;
-        # bn_out: token this call's BatchNorm fills for ITS consumer
-        y, stats = _SparseConv.apply(feats, weight, geom, layout, True, res_take, fan_token, bn_in)
+        y, stats = _SparseConv.apply(feats, weight, geom, layout, True, res_take, fan_token)
         if stats.numel():
             tr = getattr(stats, "_u3d_tile_rows", None)
             if tr is None:                      # attribute lost on the way through autograd: recover it from the shape
                 nb = stats.shape[0]
                 tr = next((t for t in (128, 256, 192) if (y.shape[0] + t - 1) // t == nb), 0)
-            return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, True, stats, tr, None, post_add, res_give, bn_out)
-        return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, bn.training, None, 0, None, post_add, res_give, bn_out)
+            return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, True, stats, tr, None, post_add, res_give)
+        return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, bn.training, None, 0, None, post_add, res_give)
     return bn_rows(sparse_conv(feats, weight, geom, layout, fan_token), bn, n_dev, residual, relu, None, post_add)
 
 
@@ -618,8 +574,7 @@ class _BNRows(torch.autograd.Function):
     """BatchNorm1d over active rows (+ residual) (+ ReLU), training or eval statistics."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, n_dev, bn, relu, training, stats=None, tile_rows=0, row_map=None, post_add=None, res_token=None,
-                bn_tok=None):
+    def forward(ctx, x, gamma, beta, residual, n_dev, bn, relu, training, stats=None, tile_rows=0, row_map=None, post_add=None, res_token=None):
         n = x.shape[0]
         if training and stats is not None:
             mean, invstd = nv.bn_finalize_partials(stats, tile_rows, n_dev, n, bn.eps, bn.momentum if bn.momentum is not None else 0.1,
@@ -650,24 +605,13 @@ class _BNRows(torch.autograd.Function):
         ctx.row_map = row_map
         ctx.has_post = post_add is not None
         ctx.res_token = res_token if residual is not None else None
-        # BatchNorm-backward sums from the consumer's input-gradient launch (BnGradToken): training statistics, plain row order, bf16
-        ctx.bn_tok = None
-        if bn_tok is not None and training and row_map is None and post_add is None and x.dtype == torch.bfloat16 and x.is_cuda:
-            bn_tok.fill(x, None if ctx.remask else y, mean, invstd, g32, b32, relu)
-            ctx.bn_tok = bn_tok
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, mean, invstd, gamma, beta = ctx.saved_tensors
         dy = dy.contiguous()
-        tok, part = ctx.bn_tok, None
-        if tok is not None:
-            part, tok.partial, tok.epi, tok.keep = tok.partial, None, None, None
-        if part is not None:      # the conv that consumed this layer's output already reduced them per row tile on writing dy
-            sums, s32 = nv.bn_bwd_finalize_partials(part[0], part[1], ctx.n_dev, x.shape[0])
-        else:
-            sums, s32 = nv.bn_bwd_stats(dy, y, x, mean, invstd, ctx.relu, ctx.n_dev, gamma, beta, ctx.row_map, want_f32=True)
+        sums, s32 = nv.bn_bwd_stats(dy, y, x, mean, invstd, ctx.relu, ctx.n_dev, gamma, beta, ctx.row_map, want_f32=True)
         use = sums if ctx.training else torch.zeros_like(sums)       # eval statistics are constants: dx = gamma*invstd*g
         if ctx.planes:
             dx, dres, dpl = nv.bn_bwd_apply(dy, y, x, mean, invstd, gamma, use, ctx.relu, ctx.n_dev, ctx.has_res, beta, ctx.row_map, want_planes=True)
@@ -679,7 +623,7 @@ class _BNRows(torch.autograd.Function):
         if ctx.res_token is not None and dres is not None:
             ctx.res_token.dres, dres = dres, None            # picked up by the block's first conv (ResidualToken)
         # post_add enters y by a plain sum: its gradient is dy itself (no launch)
-        return dx, s32[1], s32[0], dres, None, None, None, None, None, None, None, (dy if ctx.has_post else None), None, None
+        return dx, s32[1], s32[0], dres, None, None, None, None, None, None, None, (dy if ctx.has_post else None), None
 
 
 def bn_rows(x, bn, n_dev, residual=None, relu=True, row_map=None, post_add=None):
