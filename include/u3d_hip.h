@@ -167,18 +167,40 @@ int32_t u3d_spconv_fwd(const void* in, const void* w, const int32_t* nbr, int32_
                        const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                        int32_t transpose_w, int32_t dtype, u3d_stream s);
 
-/* Second-generation bf16 kernels (256-row tiles, double-buffered LDS, LDS transpose reads): same contract as
- * u3d_spconv_fwd / u3d_spconv_wgrad with dtype U3D_BF16; return U3D_ERR_UNSUPPORTED for shapes (cin % 64, cout % 64)
- * that the first-generation kernels serve. */
+/* Second-generation bf16 implicit-GEMM kernels: same contract as u3d_spconv_fwd with dtype U3D_BF16.  Which kernel serves a shape is
+ * ONE decision, the launch plan, and a caller ASKS for it (u3d_igemm_fwd_plan, host only: no launch, no device access beyond a
+ * cached CU-count query) instead of trying launches: U3D_ERR_UNSUPPORTED there = no implicit-GEMM kernel serves the shape, take
+ * u3d_spconv_fwd.  nmajor: the weights are [K][Cout][Cin] (transpose_w = 1 of the launch); epi: what the launch does besides the
+ * convolution.  Asked with U3D_FWD_EPI_ADD for a shape whose kernel has no addend epilogue, the answer is the PLAIN plan with
+ * takes_addend = 0 (the caller adds afterwards); U3D_FWD_EPI_STATS is U3D_ERR_UNSUPPORTED where no kernel with a statistics epilogue
+ * serves the shape (use the PLAIN launch + u3d_bn_stats); U3D_FWD_EPI_AFFINE is the plan of u3d_igemm_fwd_affine_bf16.
+ *   family   U3D_FWD_FAM_CONV_IN the encoder's 8 -> 16 input convolution; DIRECT the direct-operand kernels of the narrow 27-offset
+ *            levels; GLDS the LDS-DMA kernels (n-major weights, channel counts % 64); REG the register-staged kernels
+ *   kernel   index within the family.  DIRECT: shape * 4 + variant, shapes 16/32 -> 16, 16/32 -> 32, 16/32 -> 64, 64 -> 16, 64 -> 32,
+ *            variants k-major, n-major, n-major + statistics, n-major f32 output.  GLDS: 0 two-phase 256 x 256, 1 / 2 eight-phase
+ *            256 / 192 x 256, 3 / 4 eight-phase 256 / 192 x 128, 5 two-phase 256 x 128, 6 128 x 128, 7 128 x 64.  REG: 0 / 1 k- / n-major
+ *            256 x 16, 2 / 3 256 x 32, 4 / 5 256 x 64 (cin 16 / 32), then k-major 6 256 x 256, 7 256 x 128, 8 128 x 64
+ *   rows, cols  its tile
+ *   partials, rows_per_partial  the statistics a STATS launch writes: [partials][2][Cout], one per rows_per_partial rows (=
+ *            rows_per_block of u3d_bn_finalize_partials), or with rows_per_partial = 0 one per WAVE of the direct-operand kernels
+ *            (every partial counts).  u3d_igemm_fwd_split_bf16 writes the same row-tile layout wherever it serves a shape. */
+enum { U3D_FWD_EPI_PLAIN, U3D_FWD_EPI_ADD, U3D_FWD_EPI_STATS, U3D_FWD_EPI_AFFINE, U3D_FWD_EPI_COUNT };
+enum { U3D_FWD_FAM_NONE, U3D_FWD_FAM_CONV_IN, U3D_FWD_FAM_DIRECT, U3D_FWD_FAM_GLDS, U3D_FWD_FAM_REG, U3D_FWD_FAM_COUNT };
+typedef struct u3d_fwd_plan_info {
+  int32_t family, kernel, rows, cols, partials, rows_per_partial, takes_addend;
+} u3d_fwd_plan_info;
+int32_t u3d_igemm_fwd_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t nmajor, int32_t epi,
+                           u3d_fwd_plan_info* info);
+/* The launch that follows the PLAIN / ADD / STATS plan.  addend: NULL or bf16 [n_out_cap][Cout], summed in by the epilogue before
+ * the one rounding (the input gradient of a residual block's first conv with the residual branch's gradient; ref: SparseBasicBlock's
+ * `out += identity`, mmdet3d - autograd adds the two gradients with a separate element-wise kernel); needs a table.  stats: NULL or
+ * f64 [partials][2][Cout], the BatchNorm statistics of the (bf16-rounded) output in the STATS plan's layout: feeds
+ * u3d_bn_finalize_partials and saves the separate statistics pass over the conv output (ref: conv -> BatchNorm pairs of
+ * sparse_encoder_hd.py:71-104 and second_3d.py:52-76).  Both: U3D_ERR_ARG.  U3D_ERR_UNSUPPORTED: the plan does not serve the shape,
+ * or not with that epilogue - the caller did not ask.  The entry and the query agree for every argument, n_out_cap <= 0 included. */
 int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
                            const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                           int32_t transpose_w, u3d_stream s);
-/* out = conv(in) + addend in one pass (addend bf16, out's shape): the input gradient of a residual block's first conv with the
- * residual branch's gradient summed in by the epilogue (ref: SparseBasicBlock's `out += identity`, mmdet3d; autograd adds the two
- * gradients with a separate element-wise kernel).  U3D_ERR_UNSUPPORTED for shapes without that epilogue: the caller adds. */
-int32_t u3d_igemm_fwd_add_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
-                               const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                               int32_t transpose_w, u3d_stream s);
+                           int32_t transpose_w, const void* addend, double* stats, u3d_stream s);
 /* nn.Linear on rows with the same kernel: out[M,N] = act(x[M,K] @ W[N,K]^T + bias); bf16 x/W/out, f32 bias (may be NULL),
  * relu != 0 applies max(.,0).  (ref: the Linear layers of models/utils/uni3detr_transformer.py:18-30,142-143,248-260 and
  * models/dense_heads/uni3detr_head.py:365-387.)  U3D_ERR_UNSUPPORTED unless K % 64 == 0 and N % 64 == 0. */
@@ -209,18 +231,14 @@ int32_t u3d_bn_fold_batched(const void* jobs, int32_t njobs, int32_t total_block
 int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift, int32_t relu,
                                   void* out, const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                   u3d_stream s);
-/* The kernel u3d_igemm_fwd_affine_bf16 takes for a shape: *kernel = 0 two-phase 256 x 256, 1 / 2 eight-phase 256 / 192 x 256, 3 / 4
- * eight-phase 256 / 192 x 128, 5 two-phase 256 x 128, 6 128 x 128, 7 128 x 64; *rows x *cols: its tile. */
-int32_t u3d_igemm_fwd_affine_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* kernel,
-                                  int32_t* rows, int32_t* cols);
 /* Split-bf16 convolution: f32-grade products on the bf16 matrix pipe, for the modules the reference keeps in fp32 (ref:
  * models/pts_encoder/sparse_encoder_hd.py:62-64 fp16_enabled=False, models/detectors/uni3detr.py:150-151; SECOND3D is never wrapped in
  * auto_fp16).  An f32 row matrix x travels as two bf16 planes (u3d_split_rows_f32: hi = bf16(x), lo = bf16(x - hi), stacked as rows
  * [hi ; lo] with a plane stride of n_cap rows) and x.w ~ hi.wh + hi.wl + lo.wh with f32 accumulation.  The caller passes the three
  * products as three sets of offsets: nbr int32 [kvol3][ld] = (nbr, nbr, nbr + n_in_cap), w bf16 [kvol3][Cout][Cin] = (wh, wl, wh),
- * kvol3 = 3 x offsets.  out is F32 [n_out_cap][Cout]; stats: NULL or f64 [partials][2][Cout] (u3d_igemm_fwd_stats_layout(.., kvol3, 1,
+ * kvol3 = 3 x offsets.  out is F32 [n_out_cap][Cout]; stats: NULL or f64 [partials][2][Cout] (the STATS plan of u3d_igemm_fwd_plan(.., kvol3, 1, 1,
  * ..)) per-tile BatchNorm sums of the f32 output; addend: NULL or f32 [n_out_cap][Cout] summed into the result in the epilogue (the
- * residual / fan-out gradient sums of the input gradients, as u3d_igemm_fwd_add_bf16).  U3D_ERR_UNSUPPORTED unless Cin % 64 == 0 and
+ * residual / fan-out gradient sums of the input gradients, as the addend of u3d_igemm_fwd_bf16).  U3D_ERR_UNSUPPORTED unless Cin % 64 == 0 and
  * Cout % 64 == 0. */
 int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, float* out, const int32_t* n_out_dev,
                                  int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol3, double* stats, const float* addend, u3d_stream s);
@@ -235,7 +253,7 @@ int32_t u3d_igemm_direct_split_bf16(const void* in, const void* w3, const int32_
  * addend[m][col])), f32 until the one rounding, in that order.  w_folded bf16 n-major [27][cout][cin] (u3d_bn_fold_batched), shift f32
  * [cout] (required, 16-byte aligned), addend NULL or bf16 [n_out_cap][cout], relu != 0 applies max(., 0); nbr / ld as
  * u3d_igemm_fwd_bf16.  Rows at or past *n_out_dev are left untouched.  With shift == 0 and relu == 0 the result equals
- * u3d_igemm_fwd_bf16 / u3d_igemm_fwd_add_bf16 (transpose_w = 1) on the same weights.  U3D_ERR_UNSUPPORTED unless cin, cout in
+ * u3d_igemm_fwd_bf16 (transpose_w = 1, without / with the addend) on the same weights.  U3D_ERR_UNSUPPORTED unless cin, cout in
  * {16, 32, 64} and not 64 -> 64 (27 offsets are implied). */
 int32_t u3d_igemm_direct_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift,
                                      int32_t relu, const void* addend, void* out, const int32_t* n_out_dev, int32_t n_out_cap,
@@ -263,28 +281,14 @@ int32_t u3d_split3_job_blocks(int32_t k, int32_t a, int32_t b);
 int32_t u3d_split3_weights_batch(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
 /* dst bf16 [2 * n_cap][c]: rows [0, n) = bf16(x), rows [n_cap, n_cap + n) = bf16(x - hi), n = min(*n_dev, n_cap); c % 4 == 0. */
 int32_t u3d_split_rows_f32(const float* x, const int32_t* n_dev, int32_t n_cap, int32_t c, void* dst, u3d_stream s);
-/* Forward with n-major weights w[K][Cout][Cin] (the layout u3d_igemm_fwd_bf16 takes with transpose_w = 1) that also emits the
- * BatchNorm statistics of its (bf16-rounded) output: stats f64 [partials][2][Cout] in the layout u3d_igemm_fwd_stats_layout reports
- * (U3D_ERR_UNSUPPORTED there: shape not served - use u3d_igemm_fwd_bf16 + u3d_bn_stats).  Feeds u3d_bn_finalize_partials; saves the
- * separate statistics pass over the conv output (ref: conv -> BatchNorm pairs of sparse_encoder_hd.py:71-104 and second_3d.py:52-76). */
-int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
-                                 const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                 double* stats, u3d_stream s);
-/* The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (has_nbr: a neighbour table is passed), computed by the plan the
- * launch follows: *partials row tiles of *rows_per_partial rows (= rows_per_block of u3d_bn_finalize_partials), or with
- * *rows_per_partial = 0 one partial per WAVE of the direct-operand kernels of the narrow 27-offset levels (every partial counts).
- * U3D_ERR_UNSUPPORTED: no kernel with a statistics epilogue serves the shape.  u3d_igemm_fwd_split_bf16 writes
- * the same row-tile layout wherever it serves a shape. */
-int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
-                                   int32_t* rows_per_partial);
 /* Output-stationary path of the 64 -> 64 channel, 27-offset submanifold convs (the stride-4 stage's SparseBasicBlocks, ref:
  * sparse_encoder_hd.py:106-138): rows are numbered in 4x4x4-block-major order, so the 27 x 128 table entries of a 128-row tile name
  * only a few hundred DISTINCT rows.  u3d_subm_halo_build (once per level and step) leaves, per tile, the sorted distinct rows
  * tile_rows int32 [tiles][3460] (slot 0 = the all-zero row), their number tile_cnt int32 [tiles] and the table rewritten as 16-bit
  * slots loc u16 [tiles][27][128] (within a (tile, offset): entry (r % 16) * 8 + r / 16 for row r).  u3d_subm_halo_sizes gives the
  * element counts for n_cap rows (the build returns U3D_ERR_UNSUPPORTED above 869 k rows: its per-tile row bitmap lives in LDS).
- * u3d_subm_halo_conv64_bf16 then computes what u3d_igemm_fwd_bf16 (transpose_w = 1) /
- * u3d_igemm_fwd_add_bf16 / u3d_igemm_fwd_stats_bf16 compute from the table: in/out/addend bf16 [n][64]; w_packed =
+ * u3d_subm_halo_conv64_bf16 then computes what u3d_igemm_fwd_bf16 (transpose_w = 1; plain,
+ * with an addend, with statistics) computes from the table: in/out/addend bf16 [n][64]; w_packed =
  * u3d_subm_halo_wpack of the n-major bf16 weights [27][64][64] (MFMA fragment order, same size); krev != 0 reads the offsets reversed (the transposed table of a SubM layer: input gradients, pass [K][Cin][Cout]);
  * addend nullable; stats nullable f64 [tiles][2][64] (128 rows per partial, as u3d_bn_finalize_partials takes them). */
 int32_t u3d_subm_halo_sizes(int32_t n_cap, int64_t* tile_rows_elems, int64_t* loc_elems, int32_t* tiles);
@@ -334,7 +338,7 @@ int64_t u3d_igemm_wgrad_bf16_workspace(int32_t n_out_cap, int32_t cin, int32_t c
 int32_t u3d_igemm_wgrad_bf16(const void* in, const void* dout, const int32_t* nbr, int32_t ld, float* dw,
                              const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                              int32_t out_layout, void* workspace, int64_t workspace_bytes, u3d_stream s);
-/* The launch plan of u3d_igemm_wgrad_bf16 for a shape (host only; the counterpart of u3d_igemm_fwd_affine_plan): *kernel = the kernel
+/* The launch plan of u3d_igemm_wgrad_bf16 for a shape (host only; the counterpart of u3d_igemm_fwd_plan): *kernel = the kernel
  * family (1 conv-in 8 -> 16, 2 narrow 16/32-channel, 3 / 4 eight- / two-phase LDS-DMA 256, 5 / 6 LDS-DMA 128 / 64, 7 / 8 register-staged
  * 32 / 16), *tile its square channel tile (0: conv-in, narrow), *nsplit the f32 partials it sums, *workspace their bytes (what
  * u3d_igemm_wgrad_bf16_workspace returns).  U3D_ERR_UNSUPPORTED where the launch returns it. */
@@ -393,7 +397,7 @@ int32_t u3d_bn_finalize(const double* sums, const int32_t* n_dev, int32_t n_cap,
 int32_t u3d_bn_forward_stats(const void* x, const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, float eps,
                              float momentum, float* running_mean, float* running_var, int64_t* num_batches, float* mean,
                              float* invstd, void* workspace, int64_t workspace_bytes, u3d_stream s);
-/* Same finalisation from statistics the producing convolution already reduced per row tile (u3d_igemm_fwd_stats_bf16):
+/* Same finalisation from statistics the producing convolution already reduced per row tile (u3d_igemm_fwd_bf16 with stats):
  * partial f64 [nblocks][2][C], tile b = rows [b*rows_per_block, (b+1)*rows_per_block). */
 int32_t u3d_bn_finalize_partials(const double* partial, int32_t nblocks, int32_t rows_per_block, const int32_t* n_dev,
                                  int32_t n_cap, int32_t c, float eps, float momentum, float* running_mean, float* running_var,

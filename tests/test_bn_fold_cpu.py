@@ -12,7 +12,7 @@ import projects.mmdet3d_plugin  # noqa: F401
 from uni3detr_amd import native as nv
 from uni3detr_amd.inference import InferenceModel, classify
 
-NEW = ("u3d_bn_fold_job_bytes", "u3d_bn_fold_job_blocks", "u3d_bn_fold_batched", "u3d_igemm_fwd_affine_bf16", "u3d_igemm_fwd_affine_plan")
+NEW = ("u3d_bn_fold_job_bytes", "u3d_bn_fold_job_blocks", "u3d_bn_fold_batched", "u3d_igemm_fwd_affine_bf16", "u3d_igemm_fwd_plan")
 
 
 def tiny_cfg():

@@ -141,7 +141,7 @@ class _Case:
         y = torch.empty((self.n, self.cout), dtype=torch.bfloat16, device=self.x.device) if out is None else out
         ld = self.nbr.shape[1] if self.nbr is not None else 0
         nv._check(nv.lib().u3d_igemm_fwd_bf16(nv._ptr(self.x), nv._ptr(w_bf16), nv._ptr(self.nbr), ld, nv._ptr(y), nv._ptr(self.n_dev),
-                                              self.n, self.cin, self.cout, self.kvol, 1, nv._stream()), "igemm_fwd_bf16")
+                                              self.n, self.cin, self.cout, self.kvol, 1, None, None, nv._stream()), "igemm_fwd_bf16")
         return y
 
 

@@ -133,10 +133,9 @@ def test_direct_affine_identities_padding_and_error_bound(cuda, cin, cout):
     # and both entries accept it - so the identities below compare one kernel family with itself
     assert nv.direct_serves(cin, cout, 27) and nv.igemm_fwd_affine_plan(n, cin, cout, 27, True) is None
     probe = torch.empty((n, cout), dtype=torch.bfloat16, device=cuda)
-    assert nv.lib().u3d_igemm_fwd_bf16(nv._ptr(c.x), nv._ptr(wb), nv._ptr(c.nbr), n, nv._ptr(probe), nv._ptr(c.n_dev), n, cin, cout, 27, 1,
-                                       nv._stream()) == 0
-    assert nv.lib().u3d_igemm_fwd_add_bf16(nv._ptr(c.x), nv._ptr(wb), nv._ptr(c.nbr), n, nv._ptr(res), nv._ptr(probe), nv._ptr(c.n_dev), n, cin,
-                                           cout, 27, 1, nv._stream()) == 0
+    for addend in (None, res):
+        assert nv.lib().u3d_igemm_fwd_bf16(nv._ptr(c.x), nv._ptr(wb), nv._ptr(c.nbr), n, nv._ptr(probe), nv._ptr(c.n_dev), n, cin, cout, 27, 1,
+                                           nv._ptr(addend), None, nv._stream()) == 0
     zero = torch.zeros(cout, device=cuda)
     for add in (None, res):
         base = nv.spconv_fwd(c.x, wb, c.nbr, c.n_dev, n, cout, transpose_w=True, addend=add)

@@ -99,7 +99,7 @@ def test_census_entry_of_every_pricing_variant(monkeypatch):
     t = _table(kvol, 56, 200, 0)                     # 56 columns, 50 of them rows of this call
     pairs = int((t[:, :n_out] >= 0).sum())
     assert 0 < kvol * n_out - pairs <= 200 and int((t >= 0).sum()) != pairs
-    # bf16 forward (spconv_fwd_stats, igemm_fwd_affine, igemm_direct_affine)
+    # bf16 forward (spconv_fwd with statistics, igemm_fwd_affine, igemm_direct_affine)
     assert nv.census_meta(n_in, n_out, cin, cout, kvol, t) == dict(
         kind="dense", v2=True, n_in=n_in, n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
         bytes=n_in * cin * 2 + n_out * cout * 2 + 8 * pairs + kvol * cin * cout * 2, flops=2 * pairs * cin * cout)

@@ -47,8 +47,8 @@ def test_library_exports_every_declared_symbol():
     assert lib.u3d_version() >= 1
 
 
-# u3d_igemm_fwd_stats_layout: (n_out_cap, cin, cout, kvol, has_nbr) -> (statistics partials, rows per partial), None = no kernel with a
-# statistics epilogue serves the shape; rows 0 = one partial per wave of the direct-operand kernels.  Direct-operand row counts are
+# u3d_igemm_fwd_plan asked with STATS and n-major weights: (n_out_cap, cin, cout, kvol, has_nbr) -> (statistics partials, rows per
+# partial), None = no kernel with a statistics epilogue serves the shape; rows 0 = one partial per wave of the direct-operand kernels.  Direct-operand row counts are
 # small enough that the grid is bounded by the tiles, not by the CU count (256 assumed without a GPU, as the MI355X has).
 STATS_LAYOUT = [
     # tests/test_sparse_gpu.py::test_conv_epilogue_bn_statistics_match_separate_pass
@@ -95,11 +95,10 @@ STATS_LAYOUT = [
 
 
 def test_fwd_stats_layout_follows_the_dispatch():
-    lib = ctypes.CDLL(nv.LIB_PATH)
     for n, cin, cout, kvol, has_nbr, want in STATS_LAYOUT:
-        p, r = ctypes.c_int32(-1), ctypes.c_int32(-1)
-        rc = lib.u3d_igemm_fwd_stats_layout(n, cin, cout, kvol, has_nbr, ctypes.byref(p), ctypes.byref(r))
-        got = (p.value, r.value) if rc == 0 else (None if rc == -2 else rc)
+        info = nv.FwdPlanInfo(partials=-1, rows_per_partial=-1)
+        rc = nv.lib().u3d_igemm_fwd_plan(n, cin, cout, kvol, has_nbr, 1, nv.FWD_EPI["stats"], ctypes.byref(info))
+        got = (info.partials, info.rows_per_partial) if rc == 0 else (None if rc == -2 else rc)
         assert got == want, ((n, cin, cout, kvol, has_nbr), got, want)
 
 

@@ -480,7 +480,7 @@ def test_strided_dgrad_split_path_matches_conv3d(cuda, stride, cout):
                                              # statistics buffer must be sized by the dispatched kernel's (u3d_igemm_fwd_stats_rows)
                                              (256, 256, 3, (15, 32, 31)), (512, 512, 10, (10, 20, 20))])
 def test_conv_epilogue_bn_statistics_match_separate_pass(cuda, cin, cout, B, dims):
-    """conv -> BatchNorm with the statistics reduced in the conv epilogue (u3d_igemm_fwd_stats_bf16 + u3d_bn_finalize_partials) equals
+    """conv -> BatchNorm with the statistics reduced in the conv epilogue (u3d_igemm_fwd_bf16 with stats + u3d_bn_finalize_partials) equals
     the conv followed by the stand-alone statistics pass: outputs, running statistics, and the backward through both."""
     from uni3detr_amd.plugin import dense as dn
     from uni3detr_amd import sparse as sp
@@ -555,9 +555,8 @@ def test_full_size_dominant_layer_properties(cuda):
     dy = (torch.randn(n, C, device=cuda) * 0.5).bfloat16()
     w = (torch.randn(27, C, C, device=cuda) * 0.03).bfloat16()            # kio [K, Cin, Cout]
     koi = w.transpose(1, 2).contiguous()                                  # n-major for the forward kernel
-    res = nv.spconv_fwd_stats(x, koi, nbr, nd, n, C)
-    assert res is not None
-    y, stats, tile_rows = res
+    y, stats, tile_rows = nv.spconv_fwd(x, koi, nbr, nd, n, C, transpose_w=True, tag="spconv_fwd", want_stats=True)
+    assert stats is not None
     # (1) sampled rows vs f32 gather-GEMM
     rows = torch.cat([torch.arange(0, 300, device=cuda), torch.arange(n // 2 - 150, n // 2 + 150, device=cuda), torch.arange(n - 300, n, device=cuda)])
     exp = torch.zeros(rows.numel(), C, device=cuda)
@@ -677,7 +676,7 @@ def test_narrow_weight_gradient_kernel_matches_f32_reference(cuda, cin, cout):
 
 @pytest.mark.parametrize("cin,cout", [(32, 32), (16, 32), (64, 32), (64, 64), (128, 128)])
 def test_input_gradient_with_addend_epilogue(cuda, cin, cout):
-    """u3d_igemm_fwd_add_bf16 (direct-operand kernels and the 128-row LDS-DMA tiles): conv + addend rounded once == f32 reference."""
+    """u3d_igemm_fwd_bf16 with an addend (direct-operand kernels and the 128-row LDS-DMA tiles): conv + addend rounded once == f32 reference."""
     import torch
     from uni3detr_amd import native as nv
     lvl, nbr = _level(seed=9)
@@ -1273,7 +1272,7 @@ def test_batched_row_split_and_three_way_sum(cuda):
 
 
 def test_census_entry_of_every_conv_wrapper(cuda):
-    """Each of the ten convolution wrappers of native.py under KernelTimer("census"): ONE census entry per call, under the documented
+    """Each of the nine convolution wrappers of native.py under KernelTimer("census"): ONE census entry per call, under the documented
     tag, whose dict equals the one worked out here from the table and the shapes (SURVEY.md §8d pricing: element size 2 / s, f32 weights
     for a weight gradient, a split product priced as the f32 conv it stands for) - and the same outputs, bit for bit, under
     KernelTimer("time") and with no timer."""
@@ -1305,9 +1304,13 @@ def test_census_entry_of_every_conv_wrapper(cuda):
             d["split"] = True
         return d
 
+    def fwd_stats(w, table):
+        r = nv.spconv_fwd(xb[128], w, table, nd, n, 128, transpose_w=True, tag="spconv_fwd", want_stats=True)
+        return r if r[1] is not None else None          # None: no statistics came back
+
     calls = [     # (what runs, tag, census dict)
-        (lambda: nv.spconv_fwd_stats(xb[128], wb[(27, 128)], nbr, nd, n, 128), "spconv_fwd", entry(128, 128, 27, pairs)),
-        (lambda: nv.spconv_fwd_stats(xb[128], wb[(1, 128)], None, nd, n, 128), "spconv_fwd", entry(128, 128, 1, n)),
+        (lambda: fwd_stats(wb[(27, 128)], nbr), "spconv_fwd", entry(128, 128, 27, pairs)),
+        (lambda: fwd_stats(wb[(1, 128)], None), "spconv_fwd", entry(128, 128, 1, n)),
         (lambda: nv.subm_halo_wgrad(xb[64], xb[64].flip(0).contiguous(), halo), "spconv_wgrad", entry(64, 64, 27, pairs, w=4)),
         (lambda: nv.subm_halo_conv(xb[64], pk[64], halo), "spconv_fwd", entry(64, 64, 27, pairs)),
         (lambda: nv.subm_halo_conv(xb[128], pk[128], halo, krev=True, addend=xb[128], want_stats=True, tag="spconv_dgrad"), "spconv_dgrad",

@@ -30,5 +30,6 @@ for n_out, cin, cout in ((12000, 256, 512), (48000, 256, 256)):
     nd = nv.count_tensor(n_out, "cuda")
     src = torch.randn(192000, cin, device="cuda").bfloat16()
     idx = torch.randint(0, 192000, (n_out * 9,), device="cuda")
-    print(f"n_out {n_out} {cin}->{cout}: fwd+stats {t(lambda: nv.spconv_fwd_stats(a, w, None, nd, n_out, cout)):7.1f} us | "
+    fwd_stats = lambda: nv.spconv_fwd(a, w, None, nd, n_out, cout, transpose_w=True, tag="spconv_fwd", want_stats=True)      # noqa: E731
+    print(f"n_out {n_out} {cin}->{cout}: fwd+stats {t(fwd_stats):7.1f} us | "
           f"wgrad {t(lambda: nv.spconv_wgrad(a, dy, None, nd, 1)):7.1f} us | gather (index_select stand-in) {t(lambda: src.index_select(0, idx)):7.1f} us")

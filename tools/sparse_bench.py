@@ -88,7 +88,7 @@ def main():
             print(f"{tagname:34s} halo: {halo.tiles} tiles, distinct rows per tile mean {tc.mean().item():.0f} p50 {tc.median().item():.0f} "
                   f"p90 {tc.quantile(0.9).item():.0f} max {tc.max().item():.0f}", flush=True)
             wn = w.transpose(1, 2).contiguous()
-            passes["fwd_nmajor_stats"] = lambda: nv.spconv_fwd_stats(x, wn, g.nbr_fwd, g.n_out_dev, g.n_out, co)
+            passes["fwd_nmajor_stats"] = lambda: nv.spconv_fwd(x, wn, g.nbr_fwd, g.n_out_dev, g.n_out, co, transpose_w=True, tag="spconv_fwd", want_stats=True)
             passes["halo_build"] = lambda: nv.SubmHalo(g.nbr_fwd, g.n_out_dev, g.n_out)
             wpf, wpb = nv.subm_halo_wpack(wn), nv.subm_halo_wpack(w)
             passes["halo_wpack"] = lambda: nv.subm_halo_wpack(wn)
@@ -100,7 +100,7 @@ def main():
             halo = g.level.halo()
             wn = w.transpose(1, 2).contiguous()
             wpf, wpb = nv.subm_halo_wpack(wn), nv.subm_halo_wpack(w)
-            passes["fwd_nmajor_stats"] = lambda: nv.spconv_fwd_stats(x, wn, g.nbr_fwd, g.n_out_dev, g.n_out, co)
+            passes["fwd_nmajor_stats"] = lambda: nv.spconv_fwd(x, wn, g.nbr_fwd, g.n_out_dev, g.n_out, co, transpose_w=True, tag="spconv_fwd", want_stats=True)
             passes["halo_fwd"] = lambda: nv.subm_halo_conv(x, wpf, halo)
             passes["halo_fwd_stats"] = lambda: nv.subm_halo_conv(x, wpf, halo, want_stats=True)
             passes["halo_dgrad"] = lambda: nv.subm_halo_conv(dy, wpb, halo, krev=True)

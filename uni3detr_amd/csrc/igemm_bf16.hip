@@ -230,19 +230,29 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void k_igemm_fwd(const u16* 
     }
 }
 
-template <int WAVES_M, int WAVES_N, int WM, int WN, bool WK, int BK = 64>
-static int launch_igemm_fwd(const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
-                            int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const float* bias = nullptr, int relu = 0) {
-  constexpr int BM = WAVES_M * WM * 16, BN = WAVES_N * WN * 16;
-  constexpr int LDA = BK + 8, LDW = WK ? BN + 16 : BK + 8;
-  const size_t lds = 2 * (size_t)(BM * LDA + (WK ? BK * LDW : BN * LDW)) * 2;
-  auto kern = k_igemm_fwd<WAVES_M, WAVES_N, WM, WN, WK, BK>;
-  if (lds > 64 * 1024) U3D_ALLOW_LDS(kern, lds);      // one call site per template instantiation: per-kernel, per-device
-  dim3 grid(u3d_cdiv(n_out_cap, BM), u3d_cdiv(cout, BN));
-  hipLaunchKernelGGL(kern, grid, dim3(WAVES_M * WAVES_N * 64), lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev,
-                     n_out_cap, cin, cout, kvol, bias, relu);
-  return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
-}
+// The instantiations fwd_plan launches: kernel, tile BM x BN, threads, and the dynamic LDS of the kernel's two stages of
+// (A tile [BM][BK + 8]) + (W tile [BK][BN + 16] k-major or [BN][BK + 8] n-major).
+typedef void (*reg_kernel_t)(const u16*, const u16*, const int*, int, u16*, const int*, int, int, int, int, const float*, int);
+struct RegKernel {
+  reg_kernel_t fn;
+  int rows, cols, threads;
+  size_t lds;
+};
+#define REG_KERNEL(A, B, C, D, WK, BK)                                      \
+  {k_igemm_fwd<A, B, C, D, WK, BK>, A * C * 16, B * D * 16, A * B * 64,     \
+   (size_t)2 * (A * C * 16 * (BK + 8) + (WK ? BK * (B * D * 16 + 16) : B * D * 16 * (BK + 8))) * 2}
+// R_N<cout>_<K|N>: the 16/32-channel sparse levels (and the 32 -> 64 transition), 256-row tiles, one MFMA k-step per stage (BK = 32),
+// k-major / n-major weights; R_<tile>: the k-major wide layers
+enum { R_N16_K, R_N16_N, R_N32_K, R_N32_N, R_N64_K, R_N64_N, R_256x256, R_256x128, R_128x64, R_COUNT };
+static const RegKernel REG_KERNELS[R_COUNT] = {
+    REG_KERNEL(4, 1, IGEMM_SMALL_WM, 1, true, 32), REG_KERNEL(4, 1, IGEMM_SMALL_WM, 1, false, 32),
+    REG_KERNEL(4, 1, IGEMM_SMALL_WM, 2, true, 32), REG_KERNEL(4, 1, IGEMM_SMALL_WM, 2, false, 32),
+    REG_KERNEL(4, 1, IGEMM_SMALL_WM, 4, true, 32), REG_KERNEL(4, 1, IGEMM_SMALL_WM, 4, false, 32),
+    REG_KERNEL(2, 4, 8, 4, true, 64),
+    REG_KERNEL(4, 2, 4, 4, true, 64),
+    REG_KERNEL(4, 1, 2, 4, true, 64),      // 128 x 64: 57 KB LDS -> 2 workgroups per CU hide the gather latency
+};
+#undef REG_KERNEL
 
 // =============================================================================================
 // forward / dgrad with LDS-DMA staging (256 x 256 tile, n-major weights w[kappa][n][k]).
@@ -953,9 +963,9 @@ typedef void (*glds_kernel_t)(const u16*, const u16*, const int*, int, u16*, con
 //  was removed when igemm_glds8_body took that idea to the LDS-DMA kernels; DESIGN.md 3.1 keeps its numbers.)
 
 // =============================================================================================
-// ONE launch plan for the forward / input-gradient launches on the LDS-DMA and the direct-operand kernels: fwd_plan() decides the
-// kernel, tile, grid and statistics layout of u3d_igemm_fwd_bf16 / _fwd_add_bf16 / _fwd_stats_bf16 / _fwd_split_bf16
-// and u3d_linear_bf16, and u3d_igemm_fwd_stats_layout reports that same layout to size the buffers.
+// ONE launch plan for every forward / input-gradient launch: fwd_plan() decides the kernel, tile, grid and statistics layout of
+// u3d_igemm_fwd_bf16 / _fwd_affine_bf16 / _fwd_split_bf16 and u3d_linear_bf16, and u3d_igemm_fwd_plan reports that same plan, so
+// that a caller asks which kernel serves a shape instead of trying launches.
 // =============================================================================================
 // The LDS-DMA kernels: bf16- and f32-output instantiations (nullptr: none), tile, threads, dynamic LDS, and whether the epilogue
 // takes an addend (relu & 2; GLDS_EPI_ADDEND).
@@ -981,75 +991,108 @@ static const GldsKernel GLDS_KERNELS[G_COUNT] = {
 #undef GLDS_GEOM_X
 #undef GLDS_GEOM
 
-// what the launch must do besides the convolution: PLAIN (u3d_igemm_fwd_bf16), BIAS_RELU (u3d_linear_bf16), ADD = + bf16 addend
-// (u3d_igemm_fwd_add_bf16), F32 / F32_ADD = f32 output without / with an f32 addend (u3d_igemm_fwd_split_bf16; its statistics do not
-// change the kernel), STATS = + BatchNorm statistics (u3d_igemm_fwd_stats_bf16), AFFINE = + per-column f32 shift and
-// optional ReLU on a CONVOLUTION (u3d_igemm_fwd_affine_bf16: an eval-mode BatchNorm folded into the weights, bn_fold.hip)
-enum FwdEpi { EPI_PLAIN, EPI_BIAS_RELU, EPI_ADD, EPI_F32, EPI_F32_ADD, EPI_STATS, EPI_AFFINE };
+// what the launch must do besides the convolution.  The first four are the header's U3D_FWD_EPI_*: PLAIN; ADD = + bf16 addend;
+// STATS = + BatchNorm statistics; AFFINE = + per-column f32 shift and optional ReLU on a CONVOLUTION (u3d_igemm_fwd_affine_bf16: an
+// eval-mode BatchNorm folded into the weights, bn_fold.hip).  BIAS_RELU: u3d_linear_bf16.  F32 / F32_ADD = f32 output without / with
+// an f32 addend (u3d_igemm_fwd_split_bf16; its statistics do not change the kernel).
+enum FwdEpi { EPI_PLAIN = U3D_FWD_EPI_PLAIN, EPI_ADD = U3D_FWD_EPI_ADD, EPI_STATS = U3D_FWD_EPI_STATS, EPI_AFFINE = U3D_FWD_EPI_AFFINE,
+              EPI_BIAS_RELU, EPI_F32, EPI_F32_ADD };
 
 struct FwdPlan {
-  DirectPlan direct;             // direct.slot >= 0: a direct-operand kernel (igemm_direct.hip), else
-  glds_kernel_t fn = nullptr;    // an LDS-DMA kernel (GLDS_KERNELS[glds]; nullptr and direct.slot < 0: no kernel serves the shape)
-  int glds = -1, rows = 0;       // rows = row-tile height = rows per statistics partial (0: per-wave partials of the direct kernels)
+  int family = U3D_FWD_FAM_NONE;   // U3D_FWD_FAM_*; NONE: no implicit-GEMM kernel serves the shape
+  int kernel = 0;                  // within the family: the direct-operand slot, the index into GLDS_KERNELS / REG_KERNELS
+  DirectPlan direct;               // DIRECT: its own plan (igemm_direct.hip)
+  glds_kernel_t fn = nullptr;      // GLDS: the bf16- or f32-output instantiation
+  int rows = 0, cols = 0;          // tile
   dim3 grid;
   int threads = 0;
   size_t lds = 0;
-  int partials = 0;              // statistics partials a STATS launch writes: [partials][2][cout]
-  bool served() const { return fn || direct.slot >= 0; }
+  int partials = 0, part_rows = 0; // statistics a STATS launch writes: [partials][2][cout], one per part_rows rows (0: one per wave)
+  bool addend = false;             // the kernel's epilogue takes an addend
+  bool served() const { return family != U3D_FWD_FAM_NONE; }
 };
 
 constexpr int GLDS8N_MIN_KTILES = 48;     // 256 x 128 eight-phase tiles: long reductions only (k-tiles of 64 = kvol * cin / 64) ...
 constexpr int GLDS8N_MIN_WGS = 160;       // ... and enough 256-row workgroups to keep most CUs busy with ONE per CU
 
-// The rules, first match wins (n = n_out_cap; "table": a neighbour table is passed):
-//   1. PLAIN / ADD / STATS: the direct-operand kernels wherever u3d_plan_igemm_direct serves the shape (its rule: igemm_direct.h).
-//      Statistics: one partial per wave.
-//   Otherwise the LDS-DMA kernels, for n-major weights, cin % 64 == 0, cout % 64 == 0 and n > 0 only:
-//   BIAS_RELU (plain GEMM, its own thresholds): 256 x 256 two-phase if cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128,
-//      256 x 128 two-phase if cout % 128 == 0 and ceil(n / 256) * cout / 128 >= 128, else 128 x 64.
-//   2. cout % 256 == 0 and ceil(n / 256) * cout / 256 >= 128: with a table 256 x 256 eight-phase (192 x 256 when R192(cout / 256));
-//      without one the two-phase 256 x 256, which has no addend or f32-output epilogue (ADD, F32*: none).
-//   3. a table, cout % 128 == 0, kvol * cin / 64 >= GLDS8N_MIN_KTILES k-tiles, ceil(n / 256) * cout / 128 >= GLDS8N_MIN_WGS:
-//      256 x 128 eight-phase (192 x 128 when R192(cout / 128)).
-//   4. cout % 128 == 0: 128 x 128.
-//   5. 128 x 64.
-//   AFFINE never takes rule 1 (the direct-operand kernels read `bias` as an addend) and follows rules 2-5; the two-phase 256 x 256
-//      kernel serves it (the shift is the per-column bias, not the addend epilogue it lacks).
-//   F32 / F32_ADD take the tile's f32-output instantiation.  R192(c): a table, kvol > 1 and igemm_rows192(n, c).
-//   Statistics partials of the LDS-DMA kernels: one per row tile, ceil(n / rows).
+// The rules, first match wins (n = n_out_cap; "table": a neighbour table is passed; tiles = ceil(n / 256)):
+//   1. PLAIN / ADD, k-major weights, 8 -> 16 with at most 27 offsets: the encoder's input convolution (conv_in.hip, w = [K][8][16]).
+//   2. PLAIN / ADD / STATS: the direct-operand kernels wherever u3d_plan_igemm_direct serves the shape (its rule: igemm_direct.h):
+//      the narrow sparse levels, activations gathered straight into the MFMA operand registers.  Statistics: one partial per wave.
+//   3. The LDS-DMA kernels, for n-major weights, cin % 64 == 0, cout % 64 == 0 and n > 0 only:
+//      BIAS_RELU (plain GEMM, its own thresholds): 256 x 256 two-phase if cout % 256 == 0 and tiles * cout / 256 >= 128,
+//         256 x 128 two-phase if cout % 128 == 0 and tiles * cout / 128 >= 128, else 128 x 64.
+//      a. cout % 256 == 0 and tiles * cout / 256 >= 128: with a table 256 x 256 eight-phase (192 x 256 when R192(cout / 256));
+//         without one the two-phase 256 x 256, which has no addend or f32-output epilogue (F32*: none).
+//      b. a table, cout % 128 == 0, kvol * cin / 64 >= GLDS8N_MIN_KTILES k-tiles, tiles * cout / 128 >= GLDS8N_MIN_WGS:
+//         256 x 128 eight-phase (192 x 128 when R192(cout / 128)).
+//      c. cout % 128 == 0: 128 x 128.
+//      d. 128 x 64.
+//      AFFINE never takes rule 2 (the direct-operand kernels read `bias` as an addend); the two-phase 256 x 256 kernel serves it (the
+//         shift is the per-column bias, not the addend epilogue it lacks).
+//      F32 / F32_ADD take the tile's f32-output instantiation.  R192(c): a table, kvol > 1 and igemm_rows192(n, c).
+//      Statistics partials: one per row tile, ceil(n / rows).
+//   The register-staged kernels (k_igemm_fwd), PLAIN / ADD and n > 0 only:
+//   4. cin in {16, 32} and cout in {16, 32, 64}: 256 x cout tiles in the weights' layout.  (cin = 64 -> cout 32 / 16, the dgrad of
+//      the 32 -> 64 transition, measured slower here than on the first-generation kernel: 212 vs 170 us.  Not served.)
+//   5. k-major weights, cin % 64 == 0, cout % 64 == 0: 256 x 256 if cout % 256 == 0 and tiles * cout / 256 >= 128 (few row tiles -
+//      the stride-4 branch of SECOND3D, 12000 rows - would leave most CUs idle; measured: 94 workgroups (N = 12000, 512 ch) 0.136 ->
+//      0.100 ms on 256 x 128, 188 workgroups (N = 48000, 256 ch) stay faster on 256 x 256), else 256 x 128 if cout % 128 == 0, else
+//      128 x 64.  (A 128 x 128 tile for layers with few rows was measured SLOWER: 285 vs 512 TF/s at N = 48000 - the L2->CU traffic
+//      of the smaller tile outweighs the better CU fill.)
+//   6. No implicit-GEMM kernel: the caller takes the first-generation u3d_spconv_fwd.
+//   ADD on a kernel without an addend epilogue (rules 1, 4, 5, the table-free 256 x 256 of 3a) is that kernel's PLAIN plan with
+//   addend = false: the caller adds afterwards.
 static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, bool nmajor, FwdEpi epi) {
   FwdPlan p;
-  if (epi == EPI_PLAIN || epi == EPI_ADD || epi == EPI_STATS) {
+  const bool plain = epi == EPI_PLAIN || epi == EPI_ADD;
+  auto tiled = [&](int family, int kernel, int rows, int cols, int threads, size_t lds) {
+    p.family = family, p.kernel = kernel, p.rows = rows, p.cols = cols, p.threads = threads, p.lds = lds;
+    p.grid = dim3(u3d_cdiv(n_out_cap, rows), u3d_cdiv(cout, cols));
+  };
+  if (plain && !nmajor && convin_shape(cin, cout, kvol)) {
+    tiled(U3D_FWD_FAM_CONV_IN, 0, 256, CONVIN_COUT, 256, 0);
+    return p;
+  }
+  if (plain || epi == EPI_STATS) {
     p.direct = u3d_plan_igemm_direct(n_out_cap, cin, cout, kvol, has_nbr, nmajor, epi == EPI_STATS ? DIR_STATS : DIR_BF16);
     if (p.direct.slot >= 0) {
+      p.family = U3D_FWD_FAM_DIRECT, p.kernel = p.direct.slot, p.rows = 64, p.cols = cout;
       p.partials = p.direct.partials;
+      p.addend = plain;            // (the statistics variants are never launched with one)
       return p;
     }
   }
-  if (!nmajor || cin <= 0 || cout <= 0 || cin % 64 != 0 || cout % 64 != 0 || n_out_cap <= 0) return p;
+  if (n_out_cap <= 0 || cin <= 0 || cout <= 0) return p;
   const long long tiles256 = u3d_cdiv(n_out_cap, 256);
-  const bool r192 = has_nbr && kvol > 1;
-  int g;
-  if (epi == EPI_BIAS_RELU)
-    g = (cout % 256 == 0 && tiles256 * (cout / 256) >= 128) ? G_256x256
-        : (cout % 128 == 0 && tiles256 * (cout / 128) >= 128) ? G_256x128 : G_128x64;
-  else if (cout % 256 == 0 && tiles256 * (cout / 256) >= 128)
-    g = !has_nbr ? G_256x256 : (r192 && igemm_rows192(n_out_cap, cout / 256)) ? G8_192x256 : G8_256x256;
-  else if (has_nbr && cout % 128 == 0 && kvol * (cin / 64) >= GLDS8N_MIN_KTILES && tiles256 * (cout / 128) >= GLDS8N_MIN_WGS)
-    g = (r192 && igemm_rows192(n_out_cap, cout / 128)) ? G8_192x128 : G8_256x128;
-  else
-    g = cout % 128 == 0 ? G_128x128 : G_128x64;
-  const GldsKernel& k = GLDS_KERNELS[g];
-  const bool f32 = epi == EPI_F32 || epi == EPI_F32_ADD;
-  if (!k.addend && (epi == EPI_ADD || epi == EPI_F32_ADD)) return p;
-  p.fn = f32 ? k.f32 : k.bf16;
-  if (!p.fn) return p;
-  p.glds = g;
-  p.rows = k.rows;
-  p.grid = dim3(u3d_cdiv(n_out_cap, k.rows), u3d_cdiv(cout, k.cols));
-  p.threads = k.threads;
-  p.lds = k.lds;
-  p.partials = (int)p.grid.x;
+  if (nmajor && cin % 64 == 0 && cout % 64 == 0) {
+    const bool r192 = has_nbr && kvol > 1;
+    int g;
+    if (epi == EPI_BIAS_RELU)
+      g = (cout % 256 == 0 && tiles256 * (cout / 256) >= 128) ? G_256x256
+          : (cout % 128 == 0 && tiles256 * (cout / 128) >= 128) ? G_256x128 : G_128x64;
+    else if (cout % 256 == 0 && tiles256 * (cout / 256) >= 128)
+      g = !has_nbr ? G_256x256 : (r192 && igemm_rows192(n_out_cap, cout / 256)) ? G8_192x256 : G8_256x256;
+    else if (has_nbr && cout % 128 == 0 && kvol * (cin / 64) >= GLDS8N_MIN_KTILES && tiles256 * (cout / 128) >= GLDS8N_MIN_WGS)
+      g = (r192 && igemm_rows192(n_out_cap, cout / 128)) ? G8_192x128 : G8_256x128;
+    else
+      g = cout % 128 == 0 ? G_128x128 : G_128x64;
+    const GldsKernel& k = GLDS_KERNELS[g];
+    p.fn = (epi == EPI_F32 || epi == EPI_F32_ADD) ? k.f32 : k.bf16;
+    if (!p.fn) return p;
+    tiled(U3D_FWD_FAM_GLDS, g, k.rows, k.cols, k.threads, k.lds);
+    p.partials = (int)p.grid.x;
+    p.part_rows = k.rows;
+    p.addend = k.addend;
+    return p;
+  }
+  if (!plain) return p;
+  int r = -1;
+  if ((cin == 16 || cin == 32) && (cout == 16 || cout == 32 || cout == 64))
+    r = (cout == 16 ? R_N16_K : cout == 32 ? R_N32_K : R_N64_K) + (nmajor ? 1 : 0);
+  else if (!nmajor && cin % 64 == 0 && cout % 64 == 0)
+    r = cout % 256 == 0 ? (tiles256 * (cout / 256) < 128 ? R_256x128 : R_256x256) : cout % 128 == 0 ? R_256x128 : R_128x64;
+  if (r >= 0) tiled(U3D_FWD_FAM_REG, r, REG_KERNELS[r].rows, REG_KERNELS[r].cols, REG_KERNELS[r].threads, REG_KERNELS[r].lds);
   return p;
 }
 
@@ -1058,11 +1101,22 @@ static FwdPlan fwd_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr
 static int fwd_launch(const FwdPlan& p, const void* in, const void* w, const int32_t* nbr, int ld, void* out, const int32_t* n_out_dev,
                       int n_out_cap, int cin, int cout, int kvol, hipStream_t s, const void* bias = nullptr, int relu = 0,
                       double* stats = nullptr) {
-  if (p.direct.slot >= 0) return u3d_launch_igemm_direct(p.direct, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, s, bias, stats);
-  static unsigned long long lds_mask[G_COUNT][2] = {};          // U3D_ALLOW_LDS's per-device mask, one per kernel
-  if (p.lds > 64 * 1024) u3d_allow_lds_impl((const void*)p.fn, (int)p.lds, &lds_mask[p.glds][p.fn == GLDS_KERNELS[p.glds].f32]);
-  hipLaunchKernelGGL(p.fn, p.grid, dim3(p.threads), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap, cin,
-                     cout, kvol, (const float*)bias, relu, stats);
+  static unsigned long long glds_mask[G_COUNT][2] = {}, reg_mask[R_COUNT] = {};      // U3D_ALLOW_LDS's per-device mask, one per kernel
+  switch (p.family) {
+    case U3D_FWD_FAM_CONV_IN: return u3d_launch_conv_in_fwd(in, w, nbr, ld, out, n_out_dev, n_out_cap, kvol, s);
+    case U3D_FWD_FAM_DIRECT: return u3d_launch_igemm_direct(p.direct, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, s, bias, stats);
+    case U3D_FWD_FAM_GLDS:
+      if (p.lds > 64 * 1024) u3d_allow_lds_impl((const void*)p.fn, (int)p.lds, &glds_mask[p.kernel][p.fn == GLDS_KERNELS[p.kernel].f32]);
+      hipLaunchKernelGGL(p.fn, p.grid, dim3(p.threads), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out, n_out_dev, n_out_cap,
+                         cin, cout, kvol, (const float*)bias, relu, stats);
+      break;
+    case U3D_FWD_FAM_REG:
+      if (p.lds > 64 * 1024) u3d_allow_lds_impl((const void*)REG_KERNELS[p.kernel].fn, (int)p.lds, &reg_mask[p.kernel]);
+      hipLaunchKernelGGL(REG_KERNELS[p.kernel].fn, p.grid, dim3(p.threads), p.lds, s, (const u16*)in, (const u16*)w, nbr, ld, (u16*)out,
+                         n_out_dev, n_out_cap, cin, cout, kvol, (const float*)nullptr, 0);
+      break;
+    default: return U3D_ERR_UNSUPPORTED;
+  }
   return hipGetLastError() == hipSuccess ? U3D_OK : U3D_ERR_LAUNCH;
 }
 
@@ -1093,39 +1147,17 @@ extern "C" int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folde
   if (!p.served()) return U3D_ERR_UNSUPPORTED;
   return fwd_launch(p, in, w_folded, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, shift, relu ? 1 : 0);
 }
-// The kernel that launch takes for a shape: *kernel = its index in the plan's table (0 two-phase 256 x 256, 1 / 2 eight-phase
-// 256 / 192 x 256, 3 / 4 eight-phase 256 / 192 x 128, 5 two-phase 256 x 128, 6 128 x 128, 7 128 x 64), *rows x *cols its tile.
-extern "C" int32_t u3d_igemm_fwd_affine_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* kernel,
-                                             int32_t* rows, int32_t* cols) {
-  U3D_REQUIRE(kernel && rows && cols, U3D_ERR_ARG);
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, has_nbr != 0, true, EPI_AFFINE);
-  if (!p.served()) return U3D_ERR_UNSUPPORTED;
-  *kernel = p.glds;
-  *rows = p.rows;
-  *cols = GLDS_KERNELS[p.glds].cols;
-  return U3D_OK;
-}
 
-// The statistics layout of u3d_igemm_fwd_stats_bf16 for a shape (fwd_plan, STATS).  u3d_igemm_fwd_split_bf16 writes
-// the same one wherever it serves the shape: there the plan never picks a direct-operand kernel.
-extern "C" int32_t u3d_igemm_fwd_stats_layout(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* partials,
-                                              int32_t* rows_per_partial) {
-  U3D_REQUIRE(partials && rows_per_partial, U3D_ERR_ARG);
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, has_nbr != 0, true, EPI_STATS);
+// The plan u3d_igemm_fwd_bf16 (PLAIN / ADD / STATS) and u3d_igemm_fwd_affine_bf16 (AFFINE) follow for a shape; host only.
+// u3d_igemm_fwd_split_bf16 writes the STATS plan's statistics layout wherever it serves a shape: there the plan never picks a
+// direct-operand kernel.
+extern "C" int32_t u3d_igemm_fwd_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t nmajor,
+                                      int32_t epi, u3d_fwd_plan_info* info) {
+  U3D_REQUIRE(info && epi >= 0 && epi < U3D_FWD_EPI_COUNT, U3D_ERR_ARG);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, has_nbr != 0, nmajor != 0, (FwdEpi)epi);
   if (!p.served()) return U3D_ERR_UNSUPPORTED;
-  *partials = p.partials;
-  *rows_per_partial = p.rows;
+  *info = {p.family, p.kernel, p.rows, p.cols, p.partials, p.part_rows, p.addend ? 1 : 0};
   return U3D_OK;
-}
-// forward with n-major weights w[kappa][cout][cin] that also leaves the BatchNorm statistics of the (bf16-rounded) output:
-// stats f64 [partials][2][cout] = (sum, sum of squares) per row tile (or per wave) and column, u3d_igemm_fwd_stats_layout
-extern "C" int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
-                                            const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                            double* stats, u3d_stream s) {
-  U3D_REQUIRE(in && w && out && n_out_dev && stats && (nbr || kvol == 1), U3D_ERR_ARG);
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, true, EPI_STATS);
-  if (!p.served()) return U3D_ERR_UNSUPPORTED;
-  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, nullptr, 0, stats);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1136,7 +1168,7 @@ extern "C" int32_t u3d_igemm_fwd_stats_bf16(const void* in, const void* w, const
 // the three products are three sets of "offsets" - the caller stacks the planes as rows [hi ; lo] of one matrix, triples the
 // neighbour table (nbr, nbr, nbr + plane stride) and the weights (wh, wl, wh) - and this entry only picks the f32-output instantiations.
 //   in   bf16 [2 * n_in_cap][cin] (u3d_split_rows_f32), w bf16 [kvol3][cout][cin] (n-major, kvol3 = 3 * offsets), nbr int32 [kvol3][ld],
-//   out  f32 [n_out_cap][cout]; stats (optional) f64 [partials][2][cout] of the f32 output (u3d_igemm_fwd_stats_layout(.., kvol3, 1, ..))
+//   out  f32 [n_out_cap][cout]; stats (optional) f64 [partials][2][cout] of the f32 output (the STATS plan of u3d_igemm_fwd_plan(.., kvol3, 1, 1, ..))
 extern "C" int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, float* out,
                                             const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol3,
                                             double* stats, const float* addend, u3d_stream s) {
@@ -1144,63 +1176,21 @@ extern "C" int32_t u3d_igemm_fwd_split_bf16(const void* in, const void* w, const
   if (cin % 64 != 0 || cout % 64 != 0) return U3D_ERR_UNSUPPORTED;
   if (n_out_cap <= 0) return U3D_OK;
   const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol3, true, true, addend ? EPI_F32_ADD : EPI_F32);
-  if (!p.served()) return U3D_ERR_UNSUPPORTED;
+  if (!p.served() || (addend && !p.addend)) return U3D_ERR_UNSUPPORTED;
   return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol3, s, addend, addend ? 2 : 0, stats);
 }
 
-
-// out = conv(in) + addend (bf16, out's shape) in one pass - the input gradient of a residual block's first conv with the residual
-// branch's gradient summed in by the epilogue.  Shapes without that epilogue (fwd_plan, ADD): U3D_ERR_UNSUPPORTED (the caller adds).
-extern "C" int32_t u3d_igemm_fwd_add_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, const void* addend, void* out,
-                                          const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                          int32_t transpose_w, u3d_stream s) {
-  U3D_REQUIRE(in && w && out && addend && n_out_dev && nbr, U3D_ERR_ARG);
-  if (n_out_cap <= 0) return U3D_OK;
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, true, transpose_w != 0, EPI_ADD);
-  if (!p.served()) return U3D_ERR_UNSUPPORTED;
-  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, 2);
-}
-
+// The convolution itself (forward with transpose_w = 0 / 1 for k- / n-major weights, input gradients), optionally with a bf16 addend
+// of out's shape summed in before the one rounding (the input gradient of a residual block's first conv with the residual branch's
+// gradient), or with the BatchNorm statistics of the bf16-rounded output: stats f64 [partials][2][cout] = (sum, sum of squares) per
+// row tile (or per wave) and column, in the STATS plan's layout.  The caller has asked u3d_igemm_fwd_plan: a shape, an addend or
+// statistics the plan does not serve are its error - an empty output (n_out_cap <= 0) included, which launches nothing where the plan
+// serves it (rules 1, 2) and is unsupported, as the query says, elsewhere.
 extern "C" int32_t u3d_igemm_fwd_bf16(const void* in, const void* w, const int32_t* nbr, int32_t ld, void* out,
                                       const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
-                                      int32_t transpose_w, u3d_stream s) {
-  U3D_REQUIRE(in && w && out && n_out_dev && (nbr || kvol == 1), U3D_ERR_ARG);
-  if (!transpose_w && convin_shape(cin, cout, kvol))              // the encoder's input convolution (w = [K][8][16]): conv_in.hip
-    return u3d_launch_conv_in_fwd(in, w, nbr, ld, out, n_out_dev, n_out_cap, kvol, s);
-  // the narrow sparse levels' direct-operand kernels (activations gathered straight into the MFMA operand registers, all weights
-  // LDS-resident, persistent barrier-free waves: igemm_direct.hip) and the n-major LDS-DMA kernels
-  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, transpose_w != 0, EPI_PLAIN);
-  if (p.served()) return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-  // what the plan does not serve runs on the register-staged kernels: 16/32-channel sparse levels (and the 32<->64 transitions):
-  // 256-row tiles, one MFMA k-step per stage (BK = 32), the same register-staged, software-pipelined loop as the wide layers - the
-  // first-generation kernel it replaces does "indices -> barrier -> gather -> barrier -> MFMA -> barrier" per offset with nothing in
-  // flight across the barriers
-  if (n_out_cap > 0 && cin % 16 == 0 && cout % 16 == 0 && cin <= 64 && cout <= 64 && (cin < 64 || cout < 64)) {
-#define IG_SMALL(WNV, BKV)                                                                                                                          \
-    return transpose_w ? launch_igemm_fwd<4, 1, IGEMM_SMALL_WM, WNV, false, BKV>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s)   \
-                       : launch_igemm_fwd<4, 1, IGEMM_SMALL_WM, WNV, true, BKV>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-    // (cin = 64 -> cout 32/16, the dgrad of the 32->64 transition, measured slower here than on the first-generation kernel: 212 vs 170 us)
-    if (cin == 16 || cin == 32) {
-      if (cout == 16) { IG_SMALL(1, 32) }
-      if (cout == 32) { IG_SMALL(2, 32) }
-      if (cout == 64) { IG_SMALL(4, 32) }
-    }
-#undef IG_SMALL
-  }
-  if (cin % 64 != 0 || cout % 64 != 0 || cout < 64) return U3D_ERR_UNSUPPORTED;
-  if (n_out_cap <= 0) return U3D_OK;
-  // k-major weights only from here on: fwd_plan has served every n-major shape with these channel counts
-  if (transpose_w) return U3D_ERR_UNSUPPORTED;
-#define IG_CASE(A, B, C, D) return launch_igemm_fwd<A, B, C, D, true>(in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s);
-  // (a 128x128-tile variant for layers with few rows was measured SLOWER: 285 vs 512 TF/s at N=48000 — the L2->CU traffic of
-  //  the smaller tile outweighs the better CU fill; not dispatched)
-  // few row tiles (the stride-4 branch of SECOND3D: 12000 rows): 256 x 256 tiles leave most CUs idle -> narrower tiles
-  const long long wg256 = (long long)u3d_cdiv(n_out_cap, 256) * (cout / 256 > 0 ? cout / 256 : 1);
-  if (cout % 256 == 0 && wg256 < 128) { IG_CASE(4, 2, 4, 4) }       // measured: 94 workgroups (N=12000, 512 ch) 0.136 -> 0.100 ms;
-                                                                    // 188 workgroups (N=48000, 256 ch) stay faster on 256 x 256
-  if (cout >= 256 && cout % 256 == 0) { IG_CASE(2, 4, 8, 4) }       // 256 x 256
-  if (cout >= 128 && cout % 128 == 0) { IG_CASE(4, 2, 4, 4) }       // 256 x 128
-  if (cout % 64 == 0) { IG_CASE(4, 1, 2, 4) }                        // 128 x 64: 57 KB LDS -> 2 workgroups per CU hide the gather latency
-#undef IG_CASE
-  return U3D_ERR_UNSUPPORTED;
+                                      int32_t transpose_w, const void* addend, double* stats, u3d_stream s) {
+  U3D_REQUIRE(in && w && out && n_out_dev && (nbr || (kvol == 1 && !addend)) && !(addend && stats), U3D_ERR_ARG);
+  const FwdPlan p = fwd_plan(n_out_cap, cin, cout, kvol, nbr != nullptr, transpose_w != 0, stats ? EPI_STATS : addend ? EPI_ADD : EPI_PLAIN);
+  if (!p.served() || (addend && !p.addend)) return U3D_ERR_UNSUPPORTED;
+  return fwd_launch(p, in, w, nbr, ld, out, n_out_dev, n_out_cap, cin, cout, kvol, s, addend, addend ? 2 : 0, stats);
 }

@@ -593,7 +593,7 @@ extern "C" int32_t u3d_bn_forward_stats(const void* x, const int32_t* n_dev, int
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
-// statistics already reduced per row block by the producer (u3d_igemm_fwd_stats_bf16): partial f64 [nblocks][2][C], block b covering
+// statistics already reduced per row block by the producer (u3d_igemm_fwd_bf16 with stats): partial f64 [nblocks][2][C], block b covering
 // rows [b*rows_per_block, (b+1)*rows_per_block) - only the blocks below the device-side row count are summed
 extern "C" int32_t u3d_bn_finalize_partials(const double* partial, int32_t nblocks, int32_t rows_per_block, const int32_t* n_dev,
                                             int32_t n_cap, int32_t c, float eps, float momentum, float* running_mean,

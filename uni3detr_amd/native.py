@@ -6,6 +6,7 @@ current HIP stream.  There is NO CPU fallback: if the library is missing or a ca
 Signatures, struct layouts and constants are not restated here: abi.py reads them from the header, which therefore has to be on
 disk next to the package (include/u3d_hip.h) wherever this module is imported.
 """
+import collections
 import ctypes as C
 import os
 
@@ -355,35 +356,38 @@ def timed_end(region, tag, *shape, **price):
         t.end(tag, e0, census_meta(*shape, **price) if (shape and t.mode == "census") else None)
 
 
+# The forward launch plan (fwd_plan in csrc/igemm_bf16.hip), as u3d_igemm_fwd_plan reports it: the kernel family, the kernel's name
+# within it, its tile, the statistics layout of a "stats" launch and whether the kernel's epilogue takes the addend.
+FWD_EPI = {n.lower(): i for i, n in enumerate(_slot_names("U3D_FWD_EPI_"))}      # plain, add, stats, affine
+FWD_FAMILIES = tuple(n.lower() for n in _slot_names("U3D_FWD_FAM_"))             # none, conv_in, direct, glds, reg
+AFFINE_KERNELS = ("glds_256x256", "glds8_256x256", "glds8_192x256", "glds8_256x128", "glds8_192x128", "glds_256x128", "glds_128x128",
+                  "glds_128x64")
+FWD_KERNELS = {"conv_in": ("conv_in",), "glds": AFFINE_KERNELS,
+               # <padded cin>x<cout>_<k-major | n-major | n-major + statistics | n-major f32 output>
+               "direct": tuple(f"{s}_{v}" for s in ("32x16", "32x32", "32x64", "64x16", "64x32") for v in ("k", "n", "ns", "nf")),
+               "reg": ("n16_k", "n16_n", "n32_k", "n32_n", "n64_k", "n64_n", "256x256", "256x128", "128x64")}
+FwdPlanInfo = _struct("u3d_fwd_plan_info", "FwdPlanInfo")
+FwdPlan = collections.namedtuple("FwdPlan", "family kernel rows cols partials rows_per_partial takes_addend")
+
+
+def fwd_plan(n_out, cin, cout, kvol, has_nbr, nmajor, epi="plain"):
+    """The kernel u3d_igemm_fwd_bf16 (epi "plain" / "add" / "stats") or u3d_igemm_fwd_affine_bf16 ("affine") takes for the shape, None
+    when no implicit-GEMM kernel serves it (with "stats": none with a statistics epilogue).  Asked with "add" for a kernel without an
+    addend epilogue, the answer is the plain plan with takes_addend False.  Host only: the library answers without a GPU."""
+    i = FwdPlanInfo()
+    rc = lib().u3d_igemm_fwd_plan(n_out, cin, cout, kvol, bool(has_nbr), bool(nmajor), FWD_EPI[epi], C.byref(i))
+    if rc:
+        return None if rc == U3D_ERR_UNSUPPORTED else _check(rc, "igemm_fwd_plan")
+    family = FWD_FAMILIES[i.family]
+    return FwdPlan(family, FWD_KERNELS[family][i.kernel], i.rows, i.cols, i.partials, i.rows_per_partial, bool(i.takes_addend))
+
+
 def fwd_stats_layout(n_out, cin, cout, kvol, has_nbr):
-    """(partials, rows per partial) of the statistics u3d_igemm_fwd_stats_bf16 writes for this shape, None when no kernel with a
-    statistics epilogue serves it.  Rows 0: one partial per wave of the direct-operand kernels, all of them count (rows_per_block = 0
-    downstream).  u3d_igemm_fwd_split_bf16 writes the same layout wherever it serves the shape."""
-    p, r = C.c_int32(0), C.c_int32(0)
-    if lib().u3d_igemm_fwd_stats_layout(n_out, cin, cout, kvol, int(has_nbr), C.byref(p), C.byref(r)) != 0:
-        return None
-    return p.value, r.value
-
-
-def spconv_fwd_stats(inp, w_nmajor, nbr, n_out_dev, n_out, cout):
-    """Forward with n-major weights [K, Cout, Cin] + per-row-tile BatchNorm statistics of the output.
-    -> (out [n_out, cout], stats f64 [nblocks, 2, cout], tile_rows) or None when the shape is not served by that kernel."""
-    cin, kvol = inp.shape[1], w_nmajor.shape[0]
-    if inp.dtype != torch.bfloat16 or not USE_IGEMM_V2 or (nbr is None and kvol != 1):
-        return None
-    layout = fwd_stats_layout(n_out, cin, cout, kvol, nbr is not None)
-    if layout is None or layout[0] == 0:
-        return None
-    nblocks, tr = layout
-    out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
-    stats = torch.empty((nblocks, 2, cout), dtype=torch.float64, device=inp.device)
-    ld = nbr.shape[1] if nbr is not None else 0
-    region = timed_begin()
-    _check(lib().u3d_igemm_fwd_stats_bf16(_ptr(inp), _ptr(w_nmajor), _ptr(nbr), ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                          _ptr(stats), _stream()), "igemm_fwd_stats_bf16")
-    if region is not None:      # (the shape facts are not even evaluated without a timer)
-        timed_end(region, "spconv_fwd", inp.shape[0], n_out, cin, cout, kvol, nbr)
-    return out, stats, tr
+    """(partials, rows per partial) of the statistics a "stats" launch with n-major weights writes for this shape, None when no kernel
+    with a statistics epilogue serves it.  Rows 0: one partial per wave of the direct-operand kernels, all of them count (rows_per_block
+    = 0 downstream).  u3d_igemm_fwd_split_bf16 writes the same layout wherever it serves the shape."""
+    p = fwd_plan(n_out, cin, cout, kvol, has_nbr, True, "stats")
+    return p and (p.partials, p.rows_per_partial)
 
 
 class SubmHalo:
@@ -536,37 +540,43 @@ def _nbr_ptr_ld(nbr):
     return _ptr(nbr), nbr.shape[1]
 
 
-def spconv_fwd(inp, w, nbr, n_out_dev, n_out, cout, transpose_w=False, tag=None, addend=None):
+def spconv_fwd(inp, w, nbr, n_out_dev, n_out, cout, transpose_w=False, tag=None, addend=None, want_stats=False):
     """out[m] = sum_k in[nbr[k][m]] @ W[k]; w: [K, Cin_w, Cout_w] contiguous. Returns [n_out, cout].  nbr may be a RevNbr.
-    addend (bf16 [n_out, cout], optional): summed into the result - by the kernel's epilogue where it has one, else afterwards."""
+    addend (bf16 [n_out, cout], optional): summed into the result - by the kernel's epilogue where it has one, else afterwards.
+    want_stats: -> (out, stats, rows per partial), stats = the BatchNorm statistics of the output per row tile or wave, f64 [partials, 2,
+    cout], or None where no kernel with a statistics epilogue serves the shape (they need n-major weights: transpose_w).
+    One plan query (two when statistics are wanted and not to be had), one launch: the plan's implicit-GEMM kernel, or the
+    first-generation kernel where there is none (small or odd channel counts, f32)."""
+    assert addend is None or not want_stats
     kvol = w.shape[0]
     cin = inp.shape[1]
     out = torch.empty((n_out, cout), dtype=inp.dtype, device=inp.device)
     nbr_p, ld = _nbr_ptr_ld(nbr)
+    tw = 1 if transpose_w else 0
+    plan = stats = None
+    fused = False                          # the launch takes the addend: in f32 before the one rounding (afterwards rounds twice)
+    if inp.dtype == torch.bfloat16 and USE_IGEMM_V2:
+        if want_stats:
+            plan = fwd_plan(n_out, cin, cout, kvol, ld != 0, tw, "stats")
+            if plan is not None and plan.partials:
+                stats = torch.empty((plan.partials, 2, cout), dtype=torch.float64, device=inp.device)
+        if stats is None:
+            fused = addend is not None and ld != 0 and addend.dtype == torch.bfloat16 and addend.shape == out.shape and addend.is_contiguous()
+            plan = fwd_plan(n_out, cin, cout, kvol, ld != 0, tw, "add" if fused else "plain")
+            fused = fused and plan is not None and plan.takes_addend
     region = timed_begin()
-    rc = U3D_ERR_UNSUPPORTED
-    if addend is not None and inp.dtype == torch.bfloat16 and USE_IGEMM_V2 and ld != 0 and addend.dtype == torch.bfloat16 \
-            and addend.shape == out.shape and addend.is_contiguous():
-        rc = lib().u3d_igemm_fwd_add_bf16(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(addend), _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                          1 if transpose_w else 0, _stream())
-        if rc not in (0, U3D_ERR_UNSUPPORTED):
-            _check(rc, "igemm_fwd_add_bf16")
-        if rc == 0:
-            addend = None                      # already in
-    if rc == U3D_ERR_UNSUPPORTED and inp.dtype == torch.bfloat16 and USE_IGEMM_V2:
-        rc = lib().u3d_igemm_fwd_bf16(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                      1 if transpose_w else 0, _stream())
-        if rc not in (0, U3D_ERR_UNSUPPORTED):
-            _check(rc, "igemm_fwd_bf16")
-    if rc == U3D_ERR_UNSUPPORTED:      # shape served by the first-generation kernel (small channel counts, f32)
-        _check(lib().u3d_spconv_fwd(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol,
-                                    1 if transpose_w else 0, dtype_code(inp), _stream()), "spconv_fwd")
+    if plan is not None:
+        _check(lib().u3d_igemm_fwd_bf16(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol, tw,
+                                        _ptr(addend) if fused else None, _ptr(stats), _stream()), "igemm_fwd_bf16")
+    else:
+        _check(lib().u3d_spconv_fwd(_ptr(inp), _ptr(w), nbr_p, ld, _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol, tw,
+                                    dtype_code(inp), _stream()), "spconv_fwd")
     if region is not None:
         timed_end(region, tag or ("spconv_dgrad" if transpose_w else "spconv_fwd"), inp.shape[0], n_out, cin, cout, kvol, nbr,
-                  act_bytes=inp.element_size(), v2=bool(rc == 0))
-    if addend is not None:
+                  act_bytes=inp.element_size(), v2=plan is not None)
+    if addend is not None and not fused:
         out += addend
-    return out
+    return (out, stats, plan.rows_per_partial if stats is not None else 0) if want_stats else out
 
 
 def split_rows(x, n_dev, n_cap=None):
@@ -831,16 +841,10 @@ def bn_fold(pairs):
     return t
 
 
-AFFINE_KERNELS = ("glds_256x256", "glds8_256x256", "glds8_192x256", "glds8_256x128", "glds8_192x128", "glds_256x128", "glds_128x128",
-                  "glds_128x64")
-
-
 def igemm_fwd_affine_plan(n_out, cin, cout, kvol, has_nbr):
     """(kernel name, tile rows, tile columns) u3d_igemm_fwd_affine_bf16 takes for the shape; None when it does not serve it."""
-    k, r, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    if lib().u3d_igemm_fwd_affine_plan(n_out, cin, cout, kvol, int(has_nbr), C.byref(k), C.byref(r), C.byref(c)) != 0:
-        return None
-    return AFFINE_KERNELS[k.value], r.value, c.value
+    p = fwd_plan(n_out, cin, cout, kvol, has_nbr, True, "affine")
+    return p and (p.kernel, p.rows, p.cols)
 
 
 def igemm_fwd_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, out=None, tag="spconv_fwd"):

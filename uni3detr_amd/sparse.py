@@ -46,7 +46,7 @@ class ResidualToken:
     """Side channel between the two autograd nodes of a residual block (ref: mmdet3d SparseBasicBlock, `out += identity`): the
     BatchNorm that adds the identity deposits the identity branch's gradient here in ITS backward, and the block's first conv - whose
     backward runs later, and whose input IS the identity - sums it into its input gradient in the kernel epilogue
-    (u3d_igemm_fwd_add_bf16).  Autograd would add the two gradients with a separate element-wise pass over both tensors."""
+    (u3d_igemm_fwd_bf16 with an addend).  Autograd would add the two gradients with a separate element-wise pass over both tensors."""
 
     def __init__(self):
         self.dres = None
@@ -55,7 +55,7 @@ class ResidualToken:
 class FanoutToken:
     """Side channel between the first convs of `n` branches that take the SAME input (SECOND3D with is_cascade=False): autograd
     would add their input gradients with n - 1 element-wise passes over the full tensor.  Instead each conv's backward adds what the
-    branches before it left here (kernel epilogue, u3d_igemm_fwd_add_bf16) and keeps the partial sum; only the last one hands the
+    branches before it left here (kernel epilogue, u3d_igemm_fwd_bf16 with an addend) and keeps the partial sum; only the last one hands the
     total to autograd, the others return no gradient for the input."""
 
     def __init__(self, n):
@@ -347,13 +347,10 @@ class _SparseConv(torch.autograd.Function):
             if r.halo is not None:
                 pk_fwd, ctx.pk_bwd = halo_packs(weight, kio, koi)
                 res = nv.subm_halo_conv(feats, pk_fwd, r.halo, want_stats=want_stats)
-            else:
-                res = nv.spconv_fwd_stats(feats, koi, nbr, *out_args) if (want_stats and r.nmajor) else None
-                if res is None and r.nmajor:      # (no statistics epilogue for the shape) the LDS-DMA / direct-operand kernels on the n-major weight shadow
-                    res = nv.spconv_fwd(feats, koi, nbr, *out_args, transpose_w=True, tag="spconv_fwd")
-                elif res is None:
-                    res = nv.spconv_fwd(feats, kio, nbr, *out_args)
-        # a kernel with a statistics epilogue, asked for them: (y, stats or None, rows per tile); every other launch: y
+            else:       # n-major: the LDS-DMA / direct-operand kernels on the n-major weight shadow (the only ones with a statistics epilogue)
+                res = nv.spconv_fwd(feats, koi if r.nmajor else kio, nbr, *out_args, transpose_w=r.nmajor, tag="spconv_fwd",
+                                    want_stats=want_stats and r.nmajor)
+        # a launch asked for statistics: (y, stats or None, rows per tile); every other launch: y
         y, stats, tr = res if isinstance(res, tuple) else (res, None, 0)
         ctx.save_for_backward(*saved)
         if not want_stats:
