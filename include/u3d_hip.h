@@ -114,6 +114,17 @@ int32_t u3d_dense_nbr_table(int32_t batch, const int32_t q_dims[3], const int32_
                             const int32_t stride[3], const int32_t pad[3], int32_t mode, int32_t* nbr, int32_t ld,
                             u3d_stream s);
 
+/* Tables of a dense lattice restricted to the active rows of a sparse level that lives on it: for each of `count` (<= 4) source
+ * tables src[b] int32 [kvol][ld_src] over the lattice [batch, dims] (u3d_dense_nbr_table; ld_src >= batch*dims), writes
+ *   out[b][k][i] = src[b][k][lattice row of coords[i]]  for level rows i < min(*n_dev, n_cap),  -1 for n <= i < ld_out.
+ * coords int32 [n_cap,4] (b,z,y,x); out int32 [count][kvol][ld_out], ld_out >= n_cap; src: HOST array of device pointers.  One
+ * launch, integer only, no host read: shapes follow the capacity.  With the transposed tables of the convolutions that read the
+ * level's dense() volume, their input and weight gradients run over the active rows only (ref: sparse_encoder_hd.py:133 feeding
+ * models/backbones/second_3d.py:52-76). */
+int32_t u3d_active_nbr_table(const int32_t* coords, const int32_t* n_dev, int32_t n_cap, int32_t batch, const int32_t dims[3],
+                             const int32_t* const* src, int32_t count, int32_t ld_src, int32_t kvol, int32_t* out, int32_t ld_out,
+                             u3d_stream s);
+
 /* ------------------------------------------------------------------------------------------------
  * Hard voxelization + mean VFE (ref: models/detectors/uni3detr.py:148-149; upstream mmcv Voxelization
  * hard mode + HardSimpleVFE).  Sequential semantics reproduced exactly: voxels in
@@ -334,7 +345,10 @@ int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, const int32_t*
                                    const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, float* dw, void* workspace,
                                    int64_t workspace_bytes, int32_t max_slots, u3d_stream s);
 int64_t u3d_igemm_wgrad_bf16_workspace(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol);
-/* out_layout 0: dw [K][Cin][Cout] (spconv-1.x / this library's layout); 1: dw [Cout][Cin][K] (nn.Conv3d's [Cout,Cin,kD,kH,kW]). */
+/* out_layout 0: dw [K][Cin][Cout] (spconv-1.x / this library's layout); 1: dw [Cout][Cin][K] (nn.Conv3d's [Cout,Cin,kD,kH,kW]);
+ * 2: dw [Cin][Cout][K] - for a call with the operands' roles exchanged (in = dy gathered through a transposed table restricted to
+ * the active input rows, u3d_active_nbr_table; dout = those rows' features; n_out = their count; cin / cout = the convolution's
+ * Cout / Cin), which again lands in nn.Conv3d's layout.  LDS-DMA / register-staged families only, kvol <= 27. */
 int32_t u3d_igemm_wgrad_bf16(const void* in, const void* dout, const int32_t* nbr, int32_t ld, float* dw,
                              const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                              int32_t out_layout, void* workspace, int64_t workspace_bytes, u3d_stream s);

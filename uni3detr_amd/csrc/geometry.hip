@@ -609,6 +609,44 @@ extern "C" int32_t u3d_dense_nbr_table(int32_t batch, const int32_t q_dims[3], c
   return U3D_OK;
 }
 
+// Tables of a dense lattice restricted to the ACTIVE rows of a sparse level on that lattice: t[k][i] = src[k][lattice row of coords[i]]
+// for the level's rows i < n, -1 past the count (up to ld_out).  `count` source tables of one lattice ([kvol][ld_src] each, e.g. the
+// transposed tables of SECOND3D's three first convolutions) are composed in one launch: grid.y = table, pointers by value.
+#define U3D_ACTIVE_TABLES_MAX 4
+struct ActiveTables { const int* src[U3D_ACTIVE_TABLES_MAX]; };
+__global__ __launch_bounds__(256) void k_active_nbr_table(ActiveTables tb, const int4* __restrict__ coords, const int* __restrict__ n_dev,
+                                                          int n_cap, int Dz, int Dy, int Dx, long long n_lattice, int ld_src, int kvol,
+                                                          int* __restrict__ out, int ld_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ld_out) return;
+  const int* __restrict__ src = tb.src[blockIdx.y];
+  int* __restrict__ t = out + (long long)blockIdx.y * kvol * ld_out;
+  const int n = min(*n_dev, n_cap);
+  long long row = -1;
+  if (i < n) {
+    const int4 c = coords[i];
+    row = (((long long)c.x * Dz + c.y) * Dy + c.z) * Dx + c.w;
+    if ((unsigned)c.y >= (unsigned)Dz || (unsigned)c.z >= (unsigned)Dy || (unsigned)c.w >= (unsigned)Dx || row < 0 || row >= n_lattice) row = -1;
+  }
+  for (int k = 0; k < kvol; ++k) t[(long long)k * ld_out + i] = row >= 0 ? src[(long long)k * ld_src + row] : -1;
+}
+
+extern "C" int32_t u3d_active_nbr_table(const int32_t* coords, const int32_t* n_dev, int32_t n_cap, int32_t batch, const int32_t dims[3],
+                                        const int32_t* const* src, int32_t count, int32_t ld_src, int32_t kvol, int32_t* out,
+                                        int32_t ld_out, u3d_stream s) {
+  U3D_REQUIRE(coords && n_dev && src && out && dims && batch > 0 && kvol > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(count >= 1 && count <= U3D_ACTIVE_TABLES_MAX && n_cap >= 0 && ld_out >= n_cap, U3D_ERR_ARG);
+  const long long n_lattice = (long long)batch * dims[0] * dims[1] * dims[2];
+  U3D_REQUIRE(dims[0] > 0 && dims[1] > 0 && dims[2] > 0 && ld_src >= n_lattice && n_lattice < 0x7fffffffll, U3D_ERR_ARG);
+  if (ld_out <= 0) return U3D_OK;
+  ActiveTables tb = {};
+  for (int b = 0; b < count; ++b) { U3D_REQUIRE(src[b], U3D_ERR_ARG); tb.src[b] = src[b]; }
+  hipLaunchKernelGGL(k_active_nbr_table, dim3(u3d_cdiv(ld_out, 256), count), dim3(256), 0, s, tb, (const int4*)coords, n_dev, n_cap, dims[0],
+                     dims[1], dims[2], n_lattice, ld_src, kvol, out, ld_out);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
 // ============================================================================================
 // Row gather / scatter (4-byte granularity, one wave per row segment)
 // ============================================================================================

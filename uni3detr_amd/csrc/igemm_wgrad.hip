@@ -684,6 +684,30 @@ __global__ void k_igemm_wgrad_reduce(const float* __restrict__ partial, float* _
   *(f32x4*)(dw + i) = wgrad_sum_splits(partial + i, n, nsplit);
 }
 
+// (shared by the two transposing reductions below: partial [nsplit][K][ca][cb]; the workgroup = (row a of ca, 64 columns of cb, a third
+//  of the offsets) sums the splits in a fixed order reading along cb, coalesced, and leaves its [column][k] tile in LDS)
+__device__ __forceinline__ void wgrad_reduce_tile(const float* __restrict__ partial, long long n, int nsplit, int ca, int cb, int a,
+                                                  int b0, int k0, int k1, float (&tile)[64][10]) {
+  const int t = threadIdx.x, col = t & 63;
+  for (int k = k0 + (t >> 6); k < k1; k += 4) {
+    float s = 0.f;
+    if (b0 + col < cb) {
+      const float* p = partial + ((long long)k * ca + a) * cb + b0 + col;
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+      int sp = 0;
+      for (; sp + 8 <= nsplit; sp += 8) {            // eight independent loads in flight, fixed summation order
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += p[(long long)(sp + j) * n];
+      }
+      for (; sp < nsplit; ++sp) acc[0] += p[(long long)sp * n];
+      s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    }
+    tile[col][k - k0] = s;
+  }
+  __syncthreads();
+}
 // same reduction, result written as [Cout][Cin][K] (nn.Conv3d's checkpoint layout): the gradient lands in the parameter's own
 // layout and autograd keeps it as is (a permuted view would be cloned into a contiguous tensor by AccumulateGrad: one more launch)
 __global__ __launch_bounds__(256) void k_igemm_wgrad_reduce_oik(const float* __restrict__ partial, float* __restrict__ dw, long long n,
@@ -693,29 +717,25 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad_reduce_oik(const float* __r
   __shared__ float tile[64][10];
   const int ci = blockIdx.x, co0 = blockIdx.y * 64;
   const int kper = (kvol + gridDim.z - 1) / gridDim.z, k0 = blockIdx.z * kper, k1 = min(kvol, k0 + kper);
-  const int t = threadIdx.x, col = t & 63;
-  for (int k = k0 + (t >> 6); k < k1; k += 4) {
-    float s = 0.f;
-    if (co0 + col < cout) {
-      const float* p = partial + ((long long)k * cin + ci) * cout + co0 + col;
-      float a[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] = 0.f;
-      int sp = 0;
-      for (; sp + 8 <= nsplit; sp += 8) {            // eight independent loads in flight, fixed summation order
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] += p[(long long)(sp + j) * n];
-      }
-      for (; sp < nsplit; ++sp) a[0] += p[(long long)sp * n];
-      s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    }
-    tile[col][k - k0] = s;
-  }
-  __syncthreads();
+  wgrad_reduce_tile(partial, n, nsplit, cin, cout, ci, co0, k0, k1, tile);
   const int nk = k1 - k0;
-  for (int idx = t; idx < 64 * nk; idx += 256) {
+  for (int idx = threadIdx.x; idx < 64 * nk; idx += 256) {
     const int cl = idx / nk, k = idx % nk;
     if (co0 + cl < cout) dw[((long long)(co0 + cl) * cin + ci) * kvol + k0 + k] = tile[cl][k];
+  }
+}
+// same reduction for out_layout 2: partial [nsplit][K][ca][cb] -> dw [ca][cb][K] (the call with the operands exchanged: ca = the
+// convolution's Cout, cb = its Cin, so this too is nn.Conv3d's layout); a workgroup's writes are one contiguous run of 64 * nk floats
+__global__ __launch_bounds__(256) void k_igemm_wgrad_reduce_abk(const float* __restrict__ partial, float* __restrict__ dw, long long n,
+                                                                int nsplit, int kvol, int ca, int cb) {
+  __shared__ float tile[64][10];
+  const int a = blockIdx.x, b0 = blockIdx.y * 64;
+  const int kper = (kvol + gridDim.z - 1) / gridDim.z, k0 = blockIdx.z * kper, k1 = min(kvol, k0 + kper);
+  wgrad_reduce_tile(partial, n, nsplit, ca, cb, a, b0, k0, k1, tile);
+  const int nk = k1 - k0;
+  for (int idx = threadIdx.x; idx < 64 * nk; idx += 256) {
+    const int cl = idx / nk, k = idx % nk;
+    if (b0 + cl < cb) dw[((long long)a * cb + b0 + cl) * kvol + k0 + k] = tile[cl][k];
   }
 }
 
@@ -745,7 +765,7 @@ static const WgradKernel WGRAD_KERNELS[WG_COUNT] = {
     {k_igemm_wgrad<2, 2, 1, 1>, nullptr, 32, 256, 4 * 64 * (32 + 16) * 2},        // register-staged: the 16/32-channel sparse levels,
     {k_igemm_wgrad<1, 1, 1, 1>, nullptr, 16, 64, 4 * 64 * (16 + 16) * 2},         // load/latency bound
 };
-enum WgReduce { WG_RED_OWN, WG_RED_KIO, WG_RED_OIK };     // done by the family's own launch / k_igemm_wgrad_reduce / _reduce_oik
+enum WgReduce { WG_RED_OWN, WG_RED_KIO, WG_RED_OIK, WG_RED_ABK };     // done by the family's own launch / k_igemm_wgrad_reduce / _reduce_oik / _reduce_abk
 
 struct WgradPlan {
   int family = WG_NONE;          // WG_NONE: no kernel serves the shape
@@ -795,18 +815,19 @@ int u3d_launch_wgrad_narrow(const void* in, const void* dout, const int32_t* nbr
                             int cin, int cout, int kvol, int out_oik, void* workspace, int64_t workspace_bytes, hipStream_t s);
 
 // The rules, first match wins (n = n_out_cap; "table": a neighbour table is passed - the launch refuses kvol > 1 without one, so the
-// plan of such a shape is the plan with a table; out_layout 0: dW [K][Cin][Cout], 1: [Cout][Cin][K]):
+// plan of such a shape is the plan with a table; out_layout 0: dW [K][Cin][Cout], 1: [Cout][Cin][K], 2: [Cin][Cout][K] - the call with
+// the operands exchanged, see u3d_hip.h):
 //   1. CONVIN: 8 -> 16, 1 <= kvol <= 27, out_layout 0.  One partial per 128 rows.
 //   2. cin % 16 != 0 or cout % 16 != 0: none.
-//   3. NARROW: a table, kvol 27 and (cin, cout) in 16 -> 16, 16 -> 32, 32 -> 32, 32 -> 64.  32 -> 16, which wgrad_narrow.hip claims
+//   3. NARROW: a table, kvol 27 and (cin, cout) in 16 -> 16, 16 -> 32, 32 -> 32, 32 -> 64; none of them for out_layout 2.  32 -> 16, which wgrad_narrow.hip claims
 //      without having a kernel for it, is none for n > 0 and takes the family's zero fill for n <= 0.
-//   4. out_layout 1 and kvol > 27: none (k_igemm_wgrad_reduce_oik turns at most 27 offsets).
+//   4. out_layout 1 or 2 and kvol > 27: none (k_igemm_wgrad_reduce_oik / _abk turn at most 27 offsets).
 //   5. the largest square tile of 256 / 128 / 64 / 32 that divides both channel counts, else 16, with wgrad_split_rows(); while the tile
 //      is above 64 and nsplit * kvol * ci_blocks * co_blocks < 192 workgroups (few rows: the decoder / head linears), half the tile.
 //      256: eight-phase with a table, two-phase without; 128 / 64: LDS-DMA; 32 / 16: register-staged.
 static WgradPlan wgrad_plan(int n_out_cap, int cin, int cout, int kvol, bool has_nbr, int out_layout) {
   WgradPlan p;
-  if (cin <= 0 || cout <= 0 || kvol <= 0) return p;
+  if (cin <= 0 || cout <= 0 || kvol <= 0 || out_layout < 0 || out_layout > 2) return p;
   const bool table = has_nbr || kvol > 1;
   const int64_t nw_bytes = (int64_t)kvol * cin * cout * 4;
   if (convin_shape(cin, cout, kvol) && out_layout == 0) {
@@ -817,13 +838,13 @@ static WgradPlan wgrad_plan(int n_out_cap, int cin, int cout, int kvol, bool has
   }
   if (cin % 16 != 0 || cout % 16 != 0) return p;
   if (table && u3d_wgrad_narrow_shape(cin, cout, kvol)) {
-    if (n_out_cap > 0 && cin == 32 && cout == 16) return p;
+    if ((n_out_cap > 0 && cin == 32 && cout == 16) || out_layout == 2) return p;
     p.family = WG_NARROW;
     p.workspace = u3d_wgrad_narrow_workspace(n_out_cap, cin, cout);
     p.nsplit = (int)(p.workspace / nw_bytes);
     return p;
   }
-  if (out_layout == 1 && kvol > 27) return p;
+  if (out_layout != 0 && kvol > 27) return p;
   const int mn = cin < cout ? cin : cout;
   int tile;
   if (mn >= 256 && cin % 256 == 0 && cout % 256 == 0) tile = 256;
@@ -835,7 +856,7 @@ static WgradPlan wgrad_plan(int n_out_cap, int cin, int cout, int kvol, bool has
   while (p.tile > 64 && (long long)p.nsplit * kvol * p.ci_blocks * p.co_blocks < 192) wgrad_split_rows(p, p.tile / 2, n_out_cap, cin, cout, kvol);
   wgrad_fill_tile(p, table, kvol);
   p.workspace = p.nsplit * nw_bytes;
-  p.reduce = out_layout == 1 ? WG_RED_OIK : WG_RED_KIO;
+  p.reduce = out_layout == 1 ? WG_RED_OIK : (out_layout == 2 ? WG_RED_ABK : WG_RED_KIO);
   return p;
 }
 
@@ -878,7 +899,9 @@ extern "C" int32_t u3d_igemm_wgrad_bf16(const void* in, const void* dout, const 
                      cin, cout, kvol, p.co_blocks);
   if (hipGetLastError() != hipSuccess) return U3D_ERR_LAUNCH;
   const long long n = (long long)kvol * cin * cout;
-  if (p.reduce == WG_RED_OIK)
+  if (p.reduce == WG_RED_ABK)
+    hipLaunchKernelGGL(k_igemm_wgrad_reduce_abk, dim3(cin, u3d_cdiv(cout, 64), kvol > 9 ? 3 : 1), dim3(256), 0, s, (const float*)workspace, dw, n, p.nsplit, kvol, cin, cout);
+  else if (p.reduce == WG_RED_OIK)
     hipLaunchKernelGGL(k_igemm_wgrad_reduce_oik, dim3(cin, u3d_cdiv(cout, 64), kvol > 9 ? 3 : 1), dim3(256), 0, s, (const float*)workspace, dw, n, p.nsplit, kvol, cin, cout);
   else
     hipLaunchKernelGGL(k_igemm_wgrad_reduce, dim3(u3d_cdiv(n / 4, 256)), dim3(256), 0, s, (const float*)workspace, dw, n, p.nsplit);

@@ -189,6 +189,21 @@ def dense_nbr_table(batch, q_dims, t_dims, ksize, stride, pad, mode, device):
     return nbr
 
 
+def active_nbr_table(coords, n_dev, batch, dims, tables):
+    """Tables of a dense lattice restricted to a sparse level's active rows (u3d_active_nbr_table): for each int32 [K, ld] table
+    of `tables` (one lattice [batch, dims], one K) -> int32 [K, ld_out] with t[k][i] = table[k][lattice row of coords[i]] for the
+    level's rows i < *n_dev and -1 from there to ld_out = the capacity coords.shape[0] rounded up to 128.  One launch for all of them."""
+    cap = coords.shape[0]
+    ld_out = (cap + 127) // 128 * 128
+    kvol, ld_src = tables[0].shape
+    assert all(t.shape == tables[0].shape and t.dtype == torch.int32 and t.is_contiguous() for t in tables)
+    out = torch.empty((len(tables), kvol, ld_out), dtype=torch.int32, device=coords.device)
+    srcs = (C.c_void_p * len(tables))(*[t.data_ptr() for t in tables])
+    _check(lib().u3d_active_nbr_table(_ptr(coords), _ptr(n_dev), cap, batch, _I3(*dims), srcs, len(tables), ld_src, kvol, _ptr(out),
+                                      ld_out, _stream()), "active_nbr_table")
+    return list(out.unbind(0))
+
+
 # --------------------------------------------------------------------------------------------------
 # voxelization
 # --------------------------------------------------------------------------------------------------
@@ -911,10 +926,12 @@ def spconv_fwd_split(xs, w3, nbr3, n_out_dev, n_out, cout, want_stats=False, tag
 WGRAD_KERNELS = ("none", "conv_in", "narrow", "glds8_256", "glds_256", "glds_128", "glds_64", "reg_32", "reg_16")
 
 
-def igemm_wgrad_plan(n_out, cin, cout, kvol, has_nbr, out_oik=False):
-    """(kernel family, tile, nsplit, workspace bytes) u3d_igemm_wgrad_bf16 takes for the shape; None when it does not serve it."""
+def igemm_wgrad_plan(n_out, cin, cout, kvol, has_nbr, out_oik=False, out_layout=None):
+    """(kernel family, tile, nsplit, workspace bytes) u3d_igemm_wgrad_bf16 takes for the shape; None when it does not serve it.
+    out_layout (0 / 1 / 2, see u3d_hip.h) overrides out_oik (= layout 1)."""
     k, tile, ns, ws = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    if lib().u3d_igemm_wgrad_plan(n_out, cin, cout, kvol, int(bool(has_nbr)), 1 if out_oik else 0, C.byref(k), C.byref(tile), C.byref(ns),
+    layout = (1 if out_oik else 0) if out_layout is None else int(out_layout)
+    if lib().u3d_igemm_wgrad_plan(n_out, cin, cout, kvol, int(bool(has_nbr)), layout, C.byref(k), C.byref(tile), C.byref(ns),
                                   C.byref(ws)) != 0:
         return None
     return WGRAD_KERNELS[k.value], tile.value, ns.value, ws.value
@@ -949,6 +966,31 @@ def spconv_wgrad(inp, dout, nbr, n_out_dev, kvol, out_oik=False, out=None):
             dw.copy_(gen.permute(2, 1, 0) if out_oik else gen)
     if region is not None:
         timed_end(region, "spconv_wgrad", inp.shape[0], n_out, cin, cout, kvol, nbr, act_bytes=inp.element_size(), w_bytes=4, v2=v2)
+    return dw
+
+
+def spconv_wgrad_active(dout, rows, t, n_dev, kvol, out=None):
+    """Weight gradient of a convolution over a dense lattice whose input is zero off a sparse level's rows, summed over those rows
+    only: dW[co][ci][k] = sum_{i < *n_dev} dout[t[k][i]][co] * rows[i][ci], f32 [Cout, Cin, K] (nn.Conv3d's layout).  dout bf16
+    [n_out, Cout]; rows bf16 [cap, Cin], the level's features; t int32 [K, ld] from active_nbr_table (transposed tables).  The
+    kernels of spconv_wgrad with the operands' roles exchanged (out_layout 2); no other kernel serves this: a missing plan is an error.
+    out: as spconv_wgrad."""
+    cap, cin = rows.shape
+    cout = dout.shape[1]
+    assert dout.dtype == torch.bfloat16 and rows.dtype == torch.bfloat16 and t.shape[0] == kvol and t.shape[1] >= cap
+    plan = igemm_wgrad_plan(cap, cout, cin, kvol, True, out_layout=2)
+    if plan is None:
+        raise U3DError(f"no weight-gradient kernel serves {cin} -> {cout} x {kvol} over active rows")
+    region = timed_begin()
+    if out is not None and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == kvol * cin * cout:
+        dw = out.view(cout, cin, kvol)
+    else:
+        dw = torch.empty((cout, cin, kvol), dtype=torch.float32, device=rows.device)
+    ws = torch.empty(plan[3], dtype=torch.uint8, device=rows.device)
+    _check(lib().u3d_igemm_wgrad_bf16(_ptr(dout), _ptr(rows), _ptr(t), t.shape[1], _ptr(dw), _ptr(n_dev), cap, cout, cin, kvol, 2,
+                                      _ptr(ws), plan[3], _stream()), "igemm_wgrad_bf16 (active rows)")
+    if region is not None:
+        timed_end(region, "spconv_wgrad", dout.shape[0], cap, cin, cout, kvol, t, act_bytes=2, w_bytes=4, v2=True)
     return dw
 
 

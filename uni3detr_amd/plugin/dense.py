@@ -169,6 +169,7 @@ class SECOND3D(nn.Module):
         return rows, dims
 
     def forward(self, x):
+        act = sp.take_active(x)       # SparseEncoderHD's last level, when x is its dense() and a gradient is wanted (else None)
         rows, B, dims = to_rows(x)
         outs = []
         if self.is_cascade:
@@ -185,6 +186,15 @@ class SECOND3D(nn.Module):
             # kernels own a CU's LDS, so branches cannot co-reside; streams only pay off against eager-mode launch gaps
             # the branches' input gradients are summed by the first convs' own backward launches (sp.FanoutToken), not by autograd
             fan = sp.FanoutToken(len(self.blocks)) if (FANOUT_FUSION and rows.requires_grad and len(self.blocks) > 1) else None
+            if fan is not None and act is not None and rows.dtype == torch.bfloat16:
+                # x is the dense() of a sparse level: the first convs' gradients run over its rows (sp.ACTIVE_FIRST_CONV); one launch
+                # composes their transposed tables with the level's coordinates
+                firsts = [blk[0] for blk in self.blocks]
+                geoms = [Lattice.conv(rows.device, B, dims, tuple(c.kernel_size), tuple(c.stride), tuple(c.padding))[0] for c in firsts]
+                if (len(geoms) <= 4 and len({c.kernel_size for c in firsts}) == 1 and all(g.nbr_bwd is not None for g in geoms)
+                        and len({id(g) for g in geoms}) == len(geoms)):
+                    act.claim(geoms)
+                    fan.active = act
             seq = [self._run_block(blk, rows, B, dims, fan) for blk in self.blocks]
             return tuple(to_volume(r, B, d) for r, d in seq)
         cur = torch.cuda.current_stream()

@@ -58,9 +58,10 @@ class FanoutToken:
     branches before it left here (kernel epilogue, u3d_igemm_fwd_bf16 with an addend) and keeps the partial sum; only the last one hands the
     total to autograd, the others return no gradient for the input."""
 
-    def __init__(self, n):
+    def __init__(self, n, active=None):
         self.n = self.remaining = n
         self.acc = None
+        self.active = active          # ActiveInput: the branches' input gradients are rows of its level ([cap, cin]), not of the lattice
 
     def step(self, din):
         """din already contains self.acc.  -> what this conv returns to autograd for its input."""
@@ -69,7 +70,49 @@ class FanoutToken:
             self.acc = din
             return None
         self.acc, self.remaining = None, self.n
+        if self.active is not None:       # the total stays in the level's row order: _ToDense.backward takes it from there
+            self.active.din = din
+            return None
         return din
+
+
+# SECOND3D's input volume is SparseEncoderHD's dense(): zero off the last level's rows (27.7 % of the cells on SUN RGB-D), and its
+# gradient is read at those rows only (_ToDense.backward).  With this switch the first convolution of each SECOND3D branch computes its
+# input gradient for those rows alone - the same kernels over the level's `cap` rows, through the lattice's transposed table composed
+# with the level's coordinates (native.active_nbr_table) - and the stride-1 branch its weight gradient as a sum over them
+# (native.spconv_wgrad_active) where ACTIVE_WGRAD allows.  bf16, FanoutToken path only; False: every launch as before.
+ACTIVE_FIRST_CONV = True
+# The input gradients above are bit-identical to the lattice route's at the level's rows.  The weight gradient over the level's rows is
+# the same sum in another order (the level's row order and its own row splits): equal to f32 rounding (relative L2 error against float64
+# 1.0e-7 vs 8.4e-8), not bit for bit - and 25 bf16 training steps carry that last-bit difference to 1e-2 in the head outputs.  Off by
+# default, so that a training run reproduces its earlier self exactly; on, it takes the stride-1 launch from 127 to 44 us.
+ACTIVE_WGRAD = False
+_ACTIVE = [None]          # the ActiveInput of the last _ToDense.forward that wanted a gradient, until a consumer asks for it
+
+
+class ActiveInput:
+    """Side channel from _ToDense to the convolutions that read its volume (in the style of the tokens above): the level, its
+    feature rows, and - once plugin.dense.SECOND3D has claimed it - the per-convolution tables and the total input gradient."""
+
+    def __init__(self, lvl, feats, vol):
+        self.lvl, self.feats = lvl, feats
+        self.key = (vol.data_ptr(), tuple(vol.shape), vol.dtype)
+        self.tables = {}          # id(ConvGeom) -> int32 [K, ld]: that convolution's transposed table over the level's rows
+        self.din = None           # bf16 [cap, C]: sum of the claimed convolutions' input gradients (FanoutToken.step)
+
+    def claim(self, geoms):
+        """One batched launch for the tables of `geoms` (same lattice, same offsets)."""
+        ts = nv.active_nbr_table(self.lvl.coords, self.lvl.n_dev, self.lvl.batch, self.lvl.dims, [g.nbr_bwd for g in geoms])
+        self.tables = {id(g): t for g, t in zip(geoms, ts)}
+
+
+def take_active(vol):
+    """-> the ActiveInput whose dense() produced exactly the tensor `vol` (same storage, shape and dtype), else None.  Empties the
+    side channel either way."""
+    act, _ACTIVE[0] = _ACTIVE[0], None
+    if act is None or not ACTIVE_FIRST_CONV or act.key != (vol.data_ptr(), tuple(vol.shape), vol.dtype):
+        return None
+    return act
 
 
 class ConvGeom:
@@ -323,6 +366,11 @@ class _SparseConv(torch.autograd.Function):
         ctx.geom, ctx.layout = geom, layout
         ctx.res_token = res_token
         ctx.fan_token = fan_token if (fan_token is not None and feats.requires_grad) else None
+        # the input is the dense() of a sparse level (FanoutToken.active): the backward runs over that level's rows with this table
+        act = ctx.fan_token.active if ctx.fan_token is not None else None
+        if act is not None and (id(geom) not in act.tables or r.split or r.halo is not None or feats.dtype != torch.bfloat16 or r.kvol == 1):
+            raise RuntimeError("a fan-out token over a sparse level's rows needs every branch on the bf16 table route")   # (the sum would mix row orders)
+        ctx.active = act
         # TrainStep: this parameter's slice of the flat gradient buffer - written in place by the backward ONLY if this is the
         # weight's single use in the step (a weight used twice gets two gradients that autograd must add: it may not alias them)
         _CONV_USES[id(weight)] = _CONV_USES.get(id(weight), 0) + 1
@@ -394,6 +442,13 @@ def _weight_grad(ctx, r, feats, dout):
     # autograd keeps that view as .grad and the step's packing copy has nothing to move for this parameter
     gv = ctx.grad_view if (v2 and ctx.grad_view is not None and ctx.grad_view.is_contiguous()
                            and ctx.grad_view.dtype == torch.float32 and _CONV_USES.get(ctx.weight_id, 0) == 1) else None
+    if ACTIVE_WGRAD and ctx.active is not None and not g.strided and ctx.layout == "oidhw" and v2:
+        # stride 1 over the dense() of a sparse level: an inactive input row is exactly zero and adds exactly zero - sum over the level's
+        # rows instead, dy gathered through the transposed table.  (Strided branches: counted over active input rows, their
+        # (row, offset) pairs are not fewer than over their output rows.)
+        act, ks = ctx.active, ctx.kio_shape
+        dw = nv.spconv_wgrad_active(dout, act.feats, act.tables[id(g)], act.lvl.n_dev, kvol, out=gv)
+        return dw.view(ks[4], ks[3], ks[0], ks[1], ks[2])
     if ctx.layout == "oidhw" and v2:
         # nn.Conv3d's own [Cout,Cin,kD,kH,kW] layout: autograd keeps the tensor as the gradient
         ks = ctx.kio_shape
@@ -411,20 +466,25 @@ def _input_grad(ctx, r, wc, dout):
     g, kvol, cin, cout = ctx.geom, r.kvol, r.cin, r.cout
     nbr = g.nbr_bwd if kvol > 1 else None
     add = _pending_addend(ctx)
-    fits = add is not None and add.dtype == dout.dtype and add.is_contiguous() and tuple(add.shape) == (g.n_in, cin)
+    # rows of the result: the lattice's - or, the input being the dense() of a sparse level (ctx.active), that level's `cap` rows,
+    # through the transposed table composed with the level's coordinates: the same launches over 27.7 % of the rows
+    n_in, n_in_dev = g.n_in, g.n_in_dev
+    if ctx.active is not None:
+        nbr, n_in, n_in_dev = ctx.active.tables[id(g)], ctx.active.lvl.n, ctx.active.lvl.n_dev
+    fits = add is not None and add.dtype == dout.dtype and add.is_contiguous() and tuple(add.shape) == (n_in, cin)
     if r.strided_split:
         prod = nv.linear_bf16(dout, wc.view(kvol * cin, cout), None, False)      # [n_out, K*Cin]
         fan = ctx.fan_token
         if not (fits and fan is not None and add is fan.acc):                    # only the other branches' sum rides the gather
             add = None
-        return nv.tap_gather_sum(prod, nbr, g.n_in_dev, g.n_in, cin, kvol, addend=add), add is not None
+        return nv.tap_gather_sum(prod, nbr, n_in_dev, n_in, cin, kvol, addend=add), add is not None
     if r.halo is not None:
         if not fits:
             add = None
         pk = ctx.pk_bwd if ctx.pk_bwd is not None else nv.subm_halo_wpack(wc)
         return nv.subm_halo_conv(dout, pk, r.halo, krev=True, addend=add, tag="spconv_dgrad"), add is not None
     # (an addend its epilogue cannot take - another shape or dtype, the first-generation kernel - nv.spconv_fwd adds after the launch)
-    return nv.spconv_fwd(dout, wc, nbr, g.n_in_dev, g.n_in, cin, transpose_w=True, addend=add), True
+    return nv.spconv_fwd(dout, wc, nbr, n_in_dev, n_in, cin, transpose_w=True, addend=add), True
 
 
 def _split_weight_grad(ctx, r, xs, dys):
@@ -632,18 +692,45 @@ class _ToDense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, lvl):
         ctx.lvl = lvl
-        return nv.to_dense(feats, lvl.coords, lvl.n_dev, lvl.batch, lvl.dims)
+        vol = nv.to_dense(feats, lvl.coords, lvl.n_dev, lvl.batch, lvl.dims)
+        ctx.active = _ACTIVE[0] = None
+        if ACTIVE_FIRST_CONV and ctx.needs_input_grad[0] and feats.dtype == torch.bfloat16 and feats.is_cuda:
+            ctx.set_materialize_grads(False)    # the readers may hand their gradient over in row order (ActiveInput.din): dvol = None
+            ctx.active = _ACTIVE[0] = ActiveInput(lvl, feats, vol)
+        return vol
 
     @staticmethod
     def backward(ctx, dvol):
-        lvl = ctx.lvl
-        cl = dvol.permute(0, 2, 3, 4, 1).contiguous()      # no copy when dvol is channels_last_3d
-        return nv.from_dense(cl, lvl.coords, lvl.n_dev, lvl.n), None
+        lvl, act = ctx.lvl, ctx.active
+        din = None
+        if act is not None:
+            din, act.din, act.feats = act.din, None, None
+        if dvol is not None:                               # (whatever read the volume besides the claimed convolutions - or all of it)
+            cl = dvol.permute(0, 2, 3, 4, 1).contiguous()      # no copy when dvol is channels_last_3d
+            rows = nv.from_dense(cl, lvl.coords, lvl.n_dev, lvl.n)
+            din = rows if din is None else din + rows
+        return din, None
 
 
 def to_dense(feats, lvl):
     """rows -> [B,C,D,H,W] (channels_last_3d memory) (ref: sparse_encoder_hd.py:133)."""
-    return _ToDense.apply(feats, lvl)
+    vol = _ToDense.apply(feats, lvl)
+    act = _ACTIVE[0]
+    if act is not None and act.key == (vol.data_ptr(), tuple(vol.shape), vol.dtype):
+        vol._u3d_active = act          # for dense_backward(): a backward cut at this volume
+    return vol
+
+
+def dense_backward(vol, gvol):
+    """vol.backward(gvol) for a backward that was cut at a to_dense() volume (TrainStep's phased backward: the readers saw a detached
+    leaf, gvol = its gradient).  gvol is None when the readers left their input gradient in the level's row order instead
+    (ActiveInput.din): the encoder's backward then starts from the level's rows - the dense() node has nothing left to do."""
+    act = getattr(vol, "_u3d_active", None)
+    if gvol is None and act is not None and act.din is not None:
+        feats, din, act.feats, act.din = act.feats, act.din, None, None
+        feats.backward(din)
+        return
+    vol.backward(gvol)
 
 
 class _PermuteRows(torch.autograd.Function):

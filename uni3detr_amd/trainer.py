@@ -548,7 +548,7 @@ class TrainStep:
     def _stage2b(self):
         """Phase B: the sparse encoder's backward from the gradient of its output."""
         x = self.model._encoder_out
-        x.backward(self._gx)
+        _sp.dense_backward(x, self._gx)      # (_gx None: SECOND3D's first convs left the gradient in the level's row order)
         self._pack(0, self.n_enc)
         self._gx = None
         self.model._encoder_out = self.model._encoder_cut = None
