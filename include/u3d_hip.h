@@ -242,6 +242,38 @@ int32_t u3d_bn_fold_batched(const void* jobs, int32_t njobs, int32_t total_block
 int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const int32_t* nbr, int32_t ld, const float* shift, int32_t relu,
                                   void* out, const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol,
                                   u3d_stream s);
+/* FP8 inference of the wide dense convolutions (fp8.hip, igemm_fp8.hip).  Format: OCP e4m3fn.  Every scale is a power of two.
+ * Quantiser q(x, e) = e4m3_rne(clamp(x * 2^-e, -448, 448)): saturating, ties to even, NaN -> a NaN code, +-0 -> 0x00 / 0x80.
+ *
+ * u3d_quant_rows_e4m3: q bytes [n_cap][c] = q(x bf16 [n_cap][c], *e_dev) for the first min(*n_dev, n_cap) rows; the other rows are not
+ * written.  c % 8 == 0 (else U3D_ERR_UNSUPPORTED), x 16-byte and q 8-byte aligned.
+ * u3d_absmax_rows: *slot = max(*slot, max |x|) over the first min(*n_dev, n_cap) rows of x bf16 [n_cap][c] - an unsigned integer
+ * atomicMax on the bit pattern: exact, order independent, no host sync.  A NaN or Inf input leaves +Inf.  The caller zeroes the slot.
+ * c % 8 == 0.
+ * u3d_bn_fold_fp8_batched: u3d_bn_fold_batched's job-table shape, ONE launch for all pairs, one workgroup per (pair, output channel).
+ * jobs: DEVICE array of njobs records of u3d_bn_fold_fp8_job_bytes() bytes, natural C layout
+ *   { const float* w; const float *gamma, *beta, *mean, *var; uint8_t* qw; int32_t* e_w; float* shift; int64_t sk, sa, sb; float eps;
+ *     int32_t kvol, cout, cin, first_block; }
+ * w / strides / gamma .. var as u3d_bn_fold_batched.  With wf = w * gamma / sqrt(var + eps) in f32 (the product that entry rounds to
+ * bf16): e_w int32 [cout] = the smallest e with max |wf[:, co, :]| <= 448 * 2^e (0 for an all-zero channel), qw e4m3 [kvol][cout][cin] =
+ * q(wf, e_w[co]) rounded ONCE from f32, shift f32 [cout] = beta - mean * scale.  first_block = the sum of cout over the jobs before
+ * this one, total_blocks = that sum over all jobs.
+ * u3d_igemm_fwd_affine_fp8: out bf16 = bf16_rne(act(conv(in; qw) * colscale[col] + shift[col])), e4m3 in [n_in][cin] and qw
+ * [kvol][cout][cin], f32 accumulation on the block-scaled MFMA with unit block scales, colscale / shift f32 [cout] (16-byte aligned),
+ * the other arguments as u3d_igemm_fwd_affine_bf16.  An absent neighbour (-1) contributes exact zeros.  Rows at or past *n_out_dev are
+ * left untouched.  Serves what u3d_igemm_fwd_fp8_plan serves, else U3D_ERR_UNSUPPORTED.
+ * u3d_igemm_fwd_fp8_plan (host only): the kernel (U3D_FWD_FP8_K_*) and its tile (*rows x *cols) for a shape - cin % 128 == 0,
+ * cout % 128 == 0, kvol > 1 with a table or kvol == 1 without one - or U3D_ERR_UNSUPPORTED.  u3d_igemm_fwd_plan and its epi values know nothing of it. */
+enum { U3D_FWD_FP8_K_256X256, U3D_FWD_FP8_K_192X256, U3D_FWD_FP8_K_256X256_ROWS, U3D_FWD_FP8_K_COUNT };
+int32_t u3d_quant_rows_e4m3(const void* x, void* q, const int32_t* n_dev, int32_t n_cap, int32_t c, const int32_t* e_dev, u3d_stream s);
+int32_t u3d_absmax_rows(const void* x, const int32_t* n_dev, int32_t n_cap, int32_t c, float* slot, u3d_stream s);
+int64_t u3d_bn_fold_fp8_job_bytes(void);
+int32_t u3d_bn_fold_fp8_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
+int32_t u3d_igemm_fwd_affine_fp8(const void* in, const void* qw, const int32_t* nbr, int32_t ld, const float* colscale,
+                                 const float* shift, int32_t relu, void* out, const int32_t* n_out_dev, int32_t n_out_cap, int32_t cin,
+                                 int32_t cout, int32_t kvol, u3d_stream s);
+int32_t u3d_igemm_fwd_fp8_plan(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol, int32_t has_nbr, int32_t* kernel, int32_t* rows,
+                               int32_t* cols);
 /* Split-bf16 convolution: f32-grade products on the bf16 matrix pipe, for the modules the reference keeps in fp32 (ref:
  * models/pts_encoder/sparse_encoder_hd.py:62-64 fp16_enabled=False, models/detectors/uni3detr.py:150-151; SECOND3D is never wrapped in
  * auto_fp16).  An f32 row matrix x travels as two bf16 planes (u3d_split_rows_f32: hi = bf16(x), lo = bf16(x - hi), stacked as rows

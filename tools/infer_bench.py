@@ -1,5 +1,6 @@
 """Eval forward, ms per batch: InferenceModel (eval-mode BatchNorm folded into the convolutions), InferenceModel(sparse_levels=True)
-(the sparse encoder's blocks and narrow strided convs folded too) and model.eval(), same process, the three paths alternating, medians
+(the sparse encoder's blocks and narrow strided convs folded too), InferenceModel(dense_fp8=True) (the wide dense convolutions on e4m3
+operands, calibrated on the workload's own scenes) and model.eval(), same process, the paths alternating, medians
 (and min .. max) of the replays after warm-up.  Needs the GPU.
 
     python tools/infer_bench.py [--reps 20] [--warmup 5]
@@ -55,16 +56,20 @@ def main():
     model = model.to(dev).set_precision("bf16").eval()
     inf = InferenceModel(model)
     inf_sp = InferenceModel(model, sparse_levels=True)
+    inf_f8 = InferenceModel(model, dense_fp8=True)
     for name, B, npts in (("sunrgbd_b8_20000", 8, 20000), ("sunrgbd_b2_12000", 2, 12000)):
         pts = [torch.from_numpy(room_scene(i, npts)[0]).to(dev) for i in range(B)]
+        inf_f8.calibrate([pts])
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):      # (the unfolded head needs the autocast; the folded scope brings its own)
             paths = {
                 "features_unfolded": lambda: model.extract_pts_feat(pts),
                 "features_folded": lambda: inf.extract_pts_feat(pts),
                 "features_folded_sparse": lambda: inf_sp.extract_pts_feat(pts),
+                "features_folded_fp8": lambda: inf_f8.extract_pts_feat(pts),
                 "detect_unfolded": lambda: model.simple_test_batched(None, pts, on_device=True),
                 "detect_folded": lambda: inf.simple_test_batched(None, pts, on_device=True),
                 "detect_folded_sparse": lambda: inf_sp.simple_test_batched(None, pts, on_device=True),
+                "detect_folded_fp8": lambda: inf_f8.simple_test_batched(None, pts, on_device=True),
             }
             calls = {}
             orig = nv.bn_apply
@@ -92,7 +97,7 @@ def main():
         res.update(workload=name, batch=B, points=npts, reps=a.reps, bn_apply_unfolded=calls["features_unfolded"],
                    bn_apply_folded=calls["features_folded"], bn_apply_folded_sparse=calls["features_folded_sparse"],
                    folded_layers=len(inf.folded), unfolded_layers=len(inf.unfolded), folded_layers_sparse=len(inf_sp.folded),
-                   unfolded_layers_sparse=len(inf_sp.unfolded))
+                   unfolded_layers_sparse=len(inf_sp.unfolded), fp8_layers=len(inf_f8.fp8_layers))
         print(json.dumps(res), flush=True)
 
 

@@ -36,11 +36,18 @@ the LDS-DMA affine kernel) and costs its u3d_bn_apply launch on the levels where
 The model itself is not changed: the folded route is taken only inside InferenceModel's own scope (sparse.fold_scope), and
 `model.simple_test*` called directly stays the unfolded yardstick.
 
+dense_fp8=True (off by default) runs the wide dense convolutions of SECOND3D and the FPN on OCP e4m3 operands (sparse.conv_affine_fp8:
+a quantise pass over the bf16 input rows, then u3d_igemm_fwd_affine_fp8 on the block-scaled MFMA).  Weights are folded and quantised per
+output channel from the f32 masters, activations per layer under a power-of-two scale that calibrate(batches) measures on a bf16 folded
+forward (fp8_state() / load_fp8_state() carry it).  `fp8_layers` names the pairs on that route - those the fp8 launch plan serves and that
+measured faster than bf16 -, `fp8_skipped` the rest with the reason.  A forward before calibration raises.  INTEGRATION.md N.
+
 Numerics: not bit-identical to conv + u3d_bn_apply.  Folded: bf16(w * scale) once, output rounded once.  Unfolded: bf16(w), conv
 output rounded to bf16, y rounded.  Both are a few bf16 roundings of the same real number (tests/test_bn_fold_gpu.py holds the folded
 error within 2 x the unfolded one against a float64 restatement).
 """
 import contextlib
+import math
 
 import torch
 from torch import nn
@@ -120,11 +127,67 @@ def classify(model, sparse_levels=False):
     return folded, unfolded
 
 
+_FP8_DENSE = ("pts_backbone.", "pts_neck.")
+_WHY_FP8_SCOPE = "not a dense-stack layer: SparseEncoderHD stays bf16"
+
+
+def fp8_exponent(x):
+    """The smallest integer e with x <= 448 * 2^e, i.e. ceil(log2(x / 448)), computed exactly (x = m * 2^k, 448 = 0.875 * 2^9); 0 for
+    x == 0.  The activation exponent of a layer is fp8_exponent(amax * headroom), a weight channel's fp8_exponent(max |w_folded|)."""
+    if not (x >= 0.0 and math.isfinite(x)):
+        raise ValueError(f"fp8_exponent: {x!r} is not a finite non-negative number")
+    if x == 0.0:
+        return 0
+    m, k = math.frexp(x)
+    return k - 9 if m <= 0.875 else k - 8
+
+
+def _fp8_slower(cin, cout, kvol, stride):
+    """The layer kinds the kernel serves but the quantise pass + fp8 convolution does not run faster than the bf16 launch, with the
+    measured pair of times (ms, medians, MI355X, 192 000 input rows: profiles/fp8_inference_layer_ab.txt); None: fp8 is faster."""
+    if stride > 1:
+        return (f"strided ({cin} -> {cout}, stride {stride}): the quantise pass walks every input row, {stride * stride} x the output rows - "
+                "measured quant + fp8 0.066 ms vs bf16 0.061 ms (stride 2, within the spread), 0.059 vs 0.046 ms (stride 4)")
+    if kvol == 1:
+        return (f"1 x 1 x 1 ({cin} -> {cout}): memory-bound, the fp8 kernel alone ties the bf16 one and the quantise pass comes on top - "
+                "measured quant + fp8 0.072 ms vs bf16 0.054 ms")
+    if cin == 128 and cout == 128:
+        return ("128 -> 128 channels: half of the 256-column tile is masked and a k-tile is the whole input row - measured quant + fp8 "
+                "0.078 ms vs bf16 0.077 ms (within the spread; at KITTI's 704 000 rows 0.282 vs 0.289 ms, 1.03 x, faster beyond the spread: skipped there too, this rule does not see the row count)")
+    return None
+
+
+def classify_fp8(model, pairs=None):
+    """-> (fp8, skipped): fp8 = names of the default-fold pairs of SECOND3D / SECOND3DFPN that the fp8 launch plan serves
+    (native.fwd_fp8_plan: Cin % 128 == 0, Cout % 128 == 0) and that measured faster than bf16 (_fp8_slower), skipped = [(name, reason)]
+    for every other folded pair.  Needs the built library but no device (the plan query is host only)."""
+    pairs = classify(model)[0] if pairs is None else pairs
+    mods = dict(model.named_modules())
+    fp8, skipped = [], []
+    for name, w, layout, _ in pairs:
+        kvol, cout, cin = nv.conv_weight_strides(tuple(w.shape), layout)[:3]
+        if not name.startswith(_FP8_DENSE):
+            skipped.append((name, _WHY_FP8_SCOPE))
+        elif nv.fwd_fp8_plan(1 << 16, cin, cout, kvol, kvol > 1) is None:
+            skipped.append((name, f"the fp8 launch plan does not serve {cin} -> {cout} channels, {kvol} offsets (channels % 128)"))
+        else:
+            why = _fp8_slower(cin, cout, kvol, max(getattr(mods[name], "stride", (1,))))
+            if why is None:
+                fp8.append(name)
+            else:
+                skipped.append((name, why))
+    return fp8, skipped
+
+
 class InferenceModel:
     """A Uni3DETR in eval mode and bf16 precision with its foldable BatchNorms folded away.  Owns the folded weights and shifts;
-    the wrapped model keeps its parameters, its state_dict and its own (unfolded) eval path."""
+    the wrapped model keeps its parameters, its state_dict and its own (unfolded) eval path.
 
-    def __init__(self, model, sparse_levels=False):
+    dense_fp8=True (off by default) runs the wide dense convolutions (SECOND3D, SECOND3DFPN: `fp8_layers`; the rest with the reason in
+    `fp8_skipped`) on e4m3 operands: weights folded and quantised per output channel, activations quantised per layer under a
+    power-of-two scale that calibrate() measures once (or load_fp8_state() restores).  Until then a forward raises RuntimeError."""
+
+    def __init__(self, model, sparse_levels=False, dense_fp8=False):
         if model.training:
             raise RuntimeError("InferenceModel folds eval-mode BatchNorm: call model.eval() first")
         prec = getattr(model, "precision", None)
@@ -142,9 +205,97 @@ class InferenceModel:
         self._map = {}
         self._buffers = []
         self._packs = None
+        self.dense_fp8 = bool(dense_fp8)
+        self.fp8_layers, self.fp8_skipped = classify_fp8(model) if self.dense_fp8 else ([], [])
+        self.fp8_headroom = None
+        self._fp8, self._fp8_table, self._fp8_sig = [], None, None      # sparse.Fp8Entry per fp8 layer, in fp8_layers order
         if self._pairs and self._pairs[0][1].is_cuda:
             self._allocate()
             self.refresh()
+
+    @property
+    def fp8_calibrated(self):
+        return self.fp8_headroom is not None
+
+    def _allocate_fp8(self):
+        """Per fp8 layer an Fp8Entry beside its bf16 buffers (which the calibration forward runs on): codes, channel exponents, column
+        scales; the activation exponents and the absmax slots of all layers are one tensor each (read once after calibration)."""
+        by_name = {p[0]: (p, b) for p, b in zip(self._pairs, self._buffers)}
+        dev = self._buffers[0][0].device
+        old = getattr(self, "_fp8_e_a", None)
+        self._fp8_e_a = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.int32, device=dev) if old is None else old.to(dev)
+        self._fp8_slots = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.float32, device=dev)
+        self._fp8 = []
+        for i, name in enumerate(self.fp8_layers):
+            # the entry SHARES the pair's bf16 buffers: wf stays resident for later calibrations, and both fold launches of a refresh() write
+            # the same values into `shift` (one formula, one f32 evaluation order in both kernels)
+            (_, w, layout, bn), (wf, shift, *_) = by_name[name]
+            ent = sp.Fp8Entry(name, torch.empty(tuple(wf.shape), dtype=torch.uint8, device=dev),
+                              torch.zeros((wf.shape[1],), dtype=torch.int32, device=dev), shift, wf,
+                              self._fp8_e_a[i:i + 1], torch.zeros((wf.shape[1],), dtype=torch.float32, device=dev), self._fp8_slots[i:i + 1])
+            self._fp8.append(ent)
+            self._map[id(bn)] = ent
+        self._fp8_table = None
+
+    def _fp8_scales(self):
+        """colscale[c] = 2^(e_a + e_w[c]) of every fp8 layer, on the device, into the buffers the entries already point at."""
+        for ent in self._fp8:
+            ent.colscale.copy_(torch.ldexp(torch.ones_like(ent.colscale), ent.e_w + ent.e_a))
+            ent.calibrated = True
+
+    def calibrate(self, batches, headroom=2.0):
+        """Measure the activation range of every fp8 layer: the bf16 folded forward runs over `batches` (an iterable of point lists,
+        what extract_pts_feat takes) and takes the running max |input| of each layer on the device (no host sync inside a forward);
+        then ONE read of the slots, e_a = ceil(log2(amax * headroom / 448)) per layer (headroom 2 = one binade: free in relative
+        precision, larger run-time values saturate), and the column scales.  -> {name: (amax, e_a)}.  A zero or non-finite amax
+        raises with the layer's name."""
+        if not self.dense_fp8:
+            raise RuntimeError("InferenceModel.calibrate: the model was not wrapped with dense_fp8=True")
+        if not self._map:
+            raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
+        if not (headroom >= 1.0 and math.isfinite(headroom)):
+            raise ValueError(f"calibrate: headroom must be a finite number >= 1, got {headroom!r}")
+        self._fp8_slots.zero_()
+        for ent in self._fp8:
+            ent.calibrating = True
+        try:
+            for points in batches:
+                self._extract(points)
+        finally:
+            for ent in self._fp8:
+                ent.calibrating = False
+        amax = self._fp8_slots.tolist()
+        out, e_a = {}, []
+        for ent, a in zip(self._fp8, amax):
+            if not (math.isfinite(a) and a > 0.0):
+                raise ValueError(f"calibrate: fp8 layer {ent.name} saw max |input| = {a!r} (no calibration data reached it, or a non-finite activation)")
+            e_a.append(fp8_exponent(a * headroom))
+            out[ent.name] = (a, e_a[-1])
+        if e_a:
+            self._fp8_e_a.copy_(torch.tensor(e_a, dtype=torch.int32))
+        self.fp8_headroom = float(headroom)
+        self._fp8_scales()
+        return out
+
+    def fp8_state(self):
+        """What calibration found, as plain Python: {"headroom": h, "e_a": {layer name: exponent}} (load_fp8_state restores it)."""
+        if not self.fp8_calibrated:
+            raise RuntimeError("InferenceModel.fp8_state: not calibrated")
+        return {"headroom": self.fp8_headroom, "e_a": dict(zip(self.fp8_layers, self._fp8_e_a[:len(self._fp8)].tolist()))}
+
+    def load_fp8_state(self, state):
+        """Restore activation exponents saved by fp8_state(): no calibration forward.  The layer names must be this model's."""
+        if not self.dense_fp8:
+            raise RuntimeError("InferenceModel.load_fp8_state: the model was not wrapped with dense_fp8=True")
+        if set(state["e_a"]) != set(self.fp8_layers):
+            raise ValueError("load_fp8_state: the saved layers are not this model's fp8 layers")
+        if not self._map:
+            raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
+        if self._fp8:
+            self._fp8_e_a.copy_(torch.tensor([int(state["e_a"][n]) for n in self.fp8_layers], dtype=torch.int32))
+        self.fp8_headroom = float(state["headroom"])
+        self._fp8_scales()
+        return self
 
     def _allocate(self):
         """Per pair (w_folded, shift); a pair that only sparse_levels folds gets a third item: w_packed, the folded weights in the
@@ -161,6 +312,8 @@ class InferenceModel:
             self._buffers.append(buf)
         self._map = {id(p[3]): b for p, b in zip(self._pairs, self._buffers)}
         self._packs = None
+        if self.dense_fp8:
+            self._allocate_fp8()
 
     def refresh(self):
         """Fold again: after an optimizer step, load_state_dict or a change of the running statistics.  One launch - with
@@ -181,6 +334,20 @@ class InferenceModel:
                 rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, wf, shift))
             self._table, self._sig = nv.BnFoldTable(rows), sig
         self._table.run()
+        if self._fp8:
+            # the fp8 layers again from the f32 masters (one rounding, not the bf16 copy rounded again): ONE more launch; the channel
+            # exponents may have moved, so the column scales follow
+            if self._fp8_table is None or sig != self._fp8_sig:
+                by_name = {p[0]: p for p in self._pairs}
+                rows = []
+                for ent in self._fp8:
+                    _, w, layout, bn = by_name[ent.name]
+                    rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
+                                 ent.qw, ent.e_w, ent.shift))
+                self._fp8_table, self._fp8_sig = nv.BnFoldFp8Table(rows), sig
+            self._fp8_table.run()
+            if self.fp8_calibrated:
+                self._fp8_scales()
         if self._packs is None:
             dev = self._buffers[0][0].device
             by_c = {}
@@ -193,18 +360,25 @@ class InferenceModel:
         return self
 
     @contextlib.contextmanager
-    def scope(self):
+    def scope(self, calibrating=False):
         """Inside: the wrapped model's forward takes the folded route, under bf16 autocast.  Refuses training mode and enabled
-        gradients."""
+        gradients - and, with fp8 layers, a forward before calibration (calibrating: calibrate()'s own forward)."""
         if self.model.training:
             raise RuntimeError("InferenceModel: the model went back to training mode")
         if torch.is_grad_enabled():
             raise RuntimeError("InferenceModel: gradients are enabled - the folded forward records no autograd graph (use torch.no_grad())")
+        if self.fp8_layers and not calibrating and not self.fp8_calibrated:
+            raise RuntimeError("InferenceModel(dense_fp8=True): no activation scales yet - run calibrate(batches) or load_fp8_state() first")
         if not self._map:
             raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
         # the head runs under bf16 autocast, as Uni3DETR.forward_pts_train runs it in this mode (the fused decoder takes bf16 rows)
         with sp.fold_scope(self._map), torch.autocast("cuda", dtype=torch.bfloat16):
             yield self
+
+    @torch.no_grad()
+    def _extract(self, points):
+        with self.scope(calibrating=True):
+            return self.model.extract_pts_feat(points)
 
     @torch.no_grad()
     def extract_pts_feat(self, points):

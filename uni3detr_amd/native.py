@@ -336,22 +336,25 @@ CALL_KIND = "sparse"
 USE_IGEMM_V2 = True
 
 
-def census_meta(n_in, n_out, cin, cout, kvol, nbr, act_bytes=2, w_bytes=None, v2=True, split=False):
+def census_meta(n_in, n_out, cin, cout, kvol, nbr, act_bytes=2, w_bytes=None, v2=True, split=False, in_bytes=None):
     """The census entry of one convolution launch: its valid rulebook pairs P (counted from `nbr`: a table, a RevNbr - reversing the
     offsets does not change the count - or None for a plain row product, P = n_out; one host sync) and its algorithmic bytes
     N_in*Cin*s + N_out*Cout*s + 8*P + K*Cin*Cout*w, s / w = bytes per activation / weight element (w_bytes=None: as the
-    activations; a weight gradient is written in f32: 4).
+    activations; a weight gradient is written in f32: 4).  in_bytes: bytes per INPUT element where they differ from the output's (an fp8
+    launch reads e4m3 rows and writes bf16 rows); None: act_bytes.
     split: a split-bf16 launch (kvol = the offsets of ONE of its three products) is priced as the f32 convolution it stands for: f32
     rows in and out, f32 weights, 2 * pairs * cin * cout flops (the kernel issues 3x)."""
     if split:
         act_bytes = w_bytes = 4
     elif w_bytes is None:
         w_bytes = act_bytes
+    if in_bytes is None or split:
+        in_bytes = act_bytes
     tab = nbr.t if isinstance(nbr, RevNbr) else nbr
     pairs = n_out if tab is None else int((tab[:kvol, :n_out] >= 0).sum().item())
     meta = dict(kind=CALL_KIND, v2=v2, split=True) if split else dict(kind=CALL_KIND, v2=v2)
     meta.update(n_in=n_in, n_out=n_out, cin=cin, cout=cout, kvol=kvol, pairs=pairs,
-                bytes=n_in * cin * act_bytes + n_out * cout * act_bytes + 8 * pairs + kvol * cin * cout * w_bytes, flops=2 * pairs * cin * cout)
+                bytes=n_in * cin * in_bytes + n_out * cout * act_bytes + 8 * pairs + kvol * cin * cout * w_bytes, flops=2 * pairs * cin * cout)
     return meta
 
 
@@ -879,6 +882,102 @@ def igemm_fwd_affine(inp, w_folded, nbr, shift, relu, n_out_dev, n_out, out=None
            "igemm_fwd_affine_bf16")
     if region is not None:
         timed_end(region, tag, inp.shape[0], n_out, cin, cout, kvol, nbr)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) inference of the wide dense convolutions (csrc/fp8.hip, csrc/igemm_fp8.hip).  Codes travel as uint8 tensors.
+# --------------------------------------------------------------------------------------------------
+FWD_FP8_KERNELS = tuple("fp8_glds8_" + n.lower() for n in _slot_names("U3D_FWD_FP8_K_"))      # 256x256, 192x256, 256x256_rows
+FwdFp8Plan = collections.namedtuple("FwdFp8Plan", "kernel rows cols")
+
+
+def fwd_fp8_plan(n_out, cin, cout, kvol, has_nbr):
+    """The kernel and tile u3d_igemm_fwd_affine_fp8 takes for the shape, None when it does not serve it (cin % 128, cout % 128, kvol > 1
+    with a table or kvol == 1 without one).  Host only: the library answers without a GPU."""
+    k, r, c = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib().u3d_igemm_fwd_fp8_plan(n_out, cin, cout, kvol, bool(has_nbr), C.byref(k), C.byref(r), C.byref(c))
+    if rc:
+        return None if rc == U3D_ERR_UNSUPPORTED else _check(rc, "igemm_fwd_fp8_plan")
+    return FwdFp8Plan(FWD_FP8_KERNELS[k.value], r.value, c.value)
+
+
+def quant_rows_e4m3(x, e_dev, n_dev, out=None):
+    """e4m3 codes (uint8 [n, C]) of the bf16 rows x under the power-of-two scale 2^e, e read from the device int32 e_dev: q(x, e) =
+    e4m3_rne(clamp(x * 2^-e, -448, 448)).  Only the first *n_dev rows of `out` are written."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] % 8 == 0 and x.data_ptr() % 16 == 0
+    assert e_dev.dtype == torch.int32 and e_dev.numel() == 1 and n_dev.dtype == torch.int32
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.uint8, device=x.device)
+    assert tuple(out.shape) == tuple(x.shape) and out.dtype == torch.uint8 and out.data_ptr() % 8 == 0
+    _check(lib().u3d_quant_rows_e4m3(_ptr(x), _ptr(out), _ptr(n_dev), x.shape[0], x.shape[1], _ptr(e_dev), _stream()), "quant_rows_e4m3")
+    return out
+
+
+def absmax_rows(x, n_dev, slot):
+    """slot = max(slot, max |x|) over the first *n_dev rows of the bf16 rows x; slot: one f32 device element (a view of a per-layer
+    table), zeroed by the caller.  Exact, order independent, no host sync; a NaN or Inf input leaves +Inf."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] % 8 == 0 and x.data_ptr() % 16 == 0
+    assert slot.dtype == torch.float32 and slot.numel() == 1 and n_dev.dtype == torch.int32
+    _check(lib().u3d_absmax_rows(_ptr(x), _ptr(n_dev), x.shape[0], x.shape[1], _ptr(slot), _stream()), "absmax_rows")
+    return slot
+
+
+class BnFoldFp8Job(C.Structure):
+    """One record of u3d_bn_fold_fp8_batched's device job table (include/u3d_hip.h)."""
+    _fields_ = [("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
+                ("qw", C.c_void_p), ("e_w", C.c_void_p), ("shift", C.c_void_p), ("sk", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64),
+                ("eps", C.c_float), ("kvol", C.c_int32), ("cout", C.c_int32), ("cin", C.c_int32), ("first_block", C.c_int32)]
+
+
+class BnFoldFp8Table:
+    """A job table on the device + what it points at (kept alive).  run(): ONE launch folds and quantises every pair
+    (u3d_bn_fold_fp8_batched)."""
+
+    def __init__(self, pairs):
+        """pairs: (weight f32 parameter, layout, gamma, beta, running_mean, running_var (f32 [Cout] each), eps, qw uint8
+        [kvol, Cout, Cin], e_w int32 [Cout], shift f32 [Cout])."""
+        assert int(lib().u3d_bn_fold_fp8_job_bytes()) == C.sizeof(BnFoldFp8Job)
+        jobs = (BnFoldFp8Job * len(pairs))()
+        fb = 0
+        for j, (w, layout, gamma, beta, mean, var, eps, qw, e_w, shift) in zip(jobs, pairs):
+            k, cout, cin, sk, sa, sb = conv_weight_strides(tuple(w.shape), layout)
+            for t in (w, gamma, beta, mean, var):
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "bn_fold_fp8 reads contiguous f32 device tensors"
+            assert all(tuple(t.shape) == (cout,) for t in (gamma, beta, mean, var))
+            assert qw.is_cuda and qw.dtype == torch.uint8 and qw.is_contiguous() and tuple(qw.shape) == (k, cout, cin)
+            assert e_w.is_cuda and e_w.dtype == torch.int32 and tuple(e_w.shape) == (cout,)
+            assert shift.is_cuda and shift.dtype == torch.float32 and tuple(shift.shape) == (cout,)
+            j.w, j.gamma, j.beta, j.mean, j.var = w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr()
+            j.qw, j.e_w, j.shift = qw.data_ptr(), e_w.data_ptr(), shift.data_ptr()
+            j.sk, j.sa, j.sb, j.eps = sk, sa, sb, float(eps)
+            j.kvol, j.cout, j.cin, j.first_block = k, cout, cin, fb
+            fb += cout
+        self.total_blocks, self.njobs, self.pairs = fb, len(pairs), list(pairs)
+        self.jobs_dev = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(pairs[0][7].device)
+
+    def run(self):
+        _check(lib().u3d_bn_fold_fp8_batched(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), "bn_fold_fp8_batched")
+
+
+def igemm_fwd_affine_fp8(qin, qw, nbr, colscale, shift, relu, n_out_dev, n_out, out=None, tag="spconv_fwd"):
+    """out = act(conv(qin; qw) * colscale + shift) on the block-scaled fp8 MFMA (u3d_igemm_fwd_affine_fp8): qin uint8 [n_in, cin] and qw
+    uint8 [kvol, cout, cin] e4m3 codes, nbr int32 [kvol, ld] or None for kvol == 1, colscale / shift f32 [cout], out bf16.  Rows at or
+    past *n_out_dev of `out` are left as they are.  A shape fwd_fp8_plan does not serve is an error: there is no other route."""
+    kvol, cout, cin = qw.shape
+    assert qin.dtype == torch.uint8 and qw.dtype == torch.uint8 and shift.dtype == torch.float32 and colscale.dtype == torch.float32
+    assert qin.shape[1] == cin and tuple(shift.shape) == (cout,) and tuple(colscale.shape) == (cout,) and (nbr is not None or kvol == 1)
+    assert shift.data_ptr() % 16 == 0 and colscale.data_ptr() % 16 == 0
+    assert nbr is None or (nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.shape[1] >= n_out)
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.bfloat16, device=qin.device)
+    assert tuple(out.shape) == (n_out, cout) and out.dtype == torch.bfloat16
+    region = timed_begin()
+    _check(lib().u3d_igemm_fwd_affine_fp8(_ptr(qin), _ptr(qw), _ptr(nbr), nbr.shape[1] if nbr is not None else 0, _ptr(colscale),
+                                          _ptr(shift), int(bool(relu)), _ptr(out), _ptr(n_out_dev), n_out, cin, cout, kvol, _stream()),
+           "igemm_fwd_affine_fp8")
+    if region is not None:
+        timed_end(region, tag, qin.shape[0], n_out, cin, cout, kvol, nbr, in_bytes=1, w_bytes=1)      # e4m3 rows and weights in, bf16 rows out
     return out
 
 

@@ -541,6 +541,7 @@ FUSED_CONV_STATS = True
 # Inside fold_scope(table) a conv_bn() call whose BatchNorm module is in `table` (id(bn) -> (w_folded, shift), the buffers an
 # InferenceModel owns) runs as ONE launch, conv_affine(); every other call, and every call outside a scope, is what it always was.
 # An entry of three, (w_folded, shift, w_packed or None), is a sparse-level pair of InferenceModel(sparse_levels=True): conv_folded().
+# An Fp8Entry is a pair of InferenceModel(dense_fp8=True): conv_affine_fp8(), or while calibrating the bf16 conv_affine() + absmax_rows.
 _FOLD = [None]
 
 
@@ -568,6 +569,38 @@ def conv_affine(feats, w_folded, shift, geom, relu=True):
     nv.CALL_KIND = geom.kind
     nbr = geom.nbr_fwd if kvol > 1 else None
     return nv.igemm_fwd_affine(feats.contiguous(), w_folded, nbr, shift, relu, geom.n_out_dev, geom.n_out)
+
+
+class Fp8Entry:
+    """A conv + BatchNorm pair on the fp8 route (InferenceModel(dense_fp8=True)).  Its own type: conv_bn tells the other entries
+    apart by their length.  qw uint8 [kvol, Cout, Cin] e4m3 codes, e_w int32 [Cout], shift f32 [Cout] (native.BnFoldFp8Table); e_a: the
+    activation exponent as a device int32 [1] (what the quantise pass reads) and colscale f32 [Cout] = 2^(e_a + e_w), both set by
+    calibration; w_folded: the bf16 folded weights the calibration forward runs on; slot: this layer's f32 absmax slot."""
+    __slots__ = ("name", "qw", "e_w", "shift", "w_folded", "e_a", "colscale", "slot", "calibrating", "calibrated")
+
+    def __init__(self, name, qw, e_w, shift, w_folded, e_a, colscale, slot):
+        self.name, self.qw, self.e_w, self.shift, self.w_folded = name, qw, e_w, shift, w_folded
+        self.e_a, self.colscale, self.slot = e_a, colscale, slot
+        self.calibrating = self.calibrated = False
+
+
+def conv_affine_fp8(feats, ent, geom, relu=True):
+    """relu(conv(q(feats); qw) * colscale + shift) in two launches: the bf16 input rows are quantised to e4m3 under the layer's
+    calibrated exponent (u3d_quant_rows_e4m3), then the fp8 convolution runs (u3d_igemm_fwd_affine_fp8).  Inference only; bf16 rows,
+    a shape native.fwd_fp8_plan serves - anything else is an error, not a detour."""
+    if torch.is_grad_enabled() and feats.requires_grad:
+        raise RuntimeError("conv_affine_fp8 is an inference path: it records no autograd node")
+    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
+        raise RuntimeError(f"conv_affine_fp8 needs bf16 device rows, got {feats.dtype} on {feats.device}")
+    if not ent.calibrated:
+        raise RuntimeError(f"fp8 layer {ent.name} has no activation scale yet: run InferenceModel.calibrate() or load_fp8_state() first")
+    kvol, cin = ent.qw.shape[0], ent.qw.shape[2]
+    if feats.shape[1] != cin:
+        raise ValueError(f"conv_affine_fp8: input has {feats.shape[1]} channels, folded weight expects {cin}")
+    nv.CALL_KIND = geom.kind
+    qin = nv.quant_rows_e4m3(feats.contiguous(), ent.e_a, geom.n_in_dev)
+    nbr = geom.nbr_fwd if kvol > 1 else None
+    return nv.igemm_fwd_affine_fp8(qin, ent.qw, nbr, ent.colscale, ent.shift, relu, geom.n_out_dev, geom.n_out)
 
 
 def conv_folded(feats, ent, geom, residual=None, relu=True):
@@ -603,6 +636,13 @@ def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dh
     if _FOLD[0] is not None:
         ent = _FOLD[0].get(id(bn))
         if ent is not None:
+            if isinstance(ent, Fp8Entry):
+                if bn.training or residual is not None or post_add is not None:
+                    raise RuntimeError("an fp8 conv + BatchNorm pair was called in training mode, or with a residual / level sum")
+                if not ent.calibrating:
+                    return conv_affine_fp8(feats, ent, geom, relu)
+                nv.absmax_rows(feats.contiguous(), geom.n_in_dev, ent.slot)     # calibration: the bf16 folded forward + this layer's input range
+                return conv_affine(feats, ent.w_folded, ent.shift, geom, relu)
             if len(ent) == 2:                   # (w_folded, shift): the default fold - the LDS-DMA affine kernel or an error
                 if bn.training or residual is not None or post_add is not None:
                     raise RuntimeError("a folded conv + BatchNorm pair was called in training mode, or with a residual / level sum")
