@@ -221,16 +221,24 @@ int32_t u3d_linear_bf16(const void* x, const void* w, const float* bias, int32_t
  * channel, scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale (ref: the conv -> BatchNorm -> ReLU chains of
  * sparse_encoder_hd.py:71-104, second_3d.py:52-76, second3d_fpn.py:60-90 under model.eval()).
  *
- * u3d_bn_fold_batched folds every pair of a model in ONE launch.  jobs: DEVICE array of njobs records of u3d_bn_fold_job_bytes()
- * bytes, natural C layout
- *   { const float* w; const float *gamma, *beta, *mean, *var; void* w_folded; float* shift; int64_t sk, sa, sb; float eps;
- *     int32_t kvol, cout, cin, scale_only, first_block; }
- * w: the f32 master weight, element (k, co, ci) at w[k * sk + co * sa + ci * sb] (element strides: the checkpoint layouts
- * [kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW] are read in place); gamma / beta / mean / var f32 [cout].  Written: w_folded bf16
- * [kvol][cout][cin] (the n-major layout of the LDS-DMA kernels) = bf16_rne(w * scale[co]) with scale computed in f32, and shift f32
- * [cout]; scale_only != 0: only w_folded is written and shift may be NULL (a second copy of a layer's weights whose shift another job
- * leaves).  cin % 4 == 0, w_folded 8-byte aligned.  first_block = the sum of u3d_bn_fold_job_blocks(kvol, cout, cin) over the jobs
- * before this one, total_blocks = that sum over all jobs. */
+ * u3d_bn_fold_batched folds every pair of a model in ONE launch.  jobs: DEVICE array of njobs u3d_bn_fold_job records
+ * (u3d_bn_fold_job_bytes() = its size), total_blocks = the sum of u3d_bn_fold_job_blocks(kvol, cout, cin) over all jobs. */
+typedef struct u3d_bn_fold_job {
+  const float* w;          /* the f32 master weight, element (k, co, ci) at w[k * sk + co * sa + ci * sb] (element strides: the
+                              checkpoint layouts [kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW] are read in place) */
+  const float* gamma;      /* gamma / beta / mean / var: f32 [cout] */
+  const float* beta;
+  const float* mean;
+  const float* var;
+  uint16_t* w_folded;      /* written: bf16 [kvol][cout][cin] (the n-major layout of the LDS-DMA kernels) = bf16_rne(w * scale[co]),
+                              scale computed in f32; 8-byte aligned */
+  float* shift;            /* written: f32 [cout]; may be NULL with scale_only */
+  int64_t sk, sa, sb;
+  float eps;
+  int32_t kvol, cout, cin; /* cin % 4 == 0 */
+  int32_t scale_only;      /* != 0: only w_folded is written (a second copy of a layer's weights whose shift another job leaves) */
+  int32_t first_block;     /* the sum of u3d_bn_fold_job_blocks(kvol, cout, cin) over the jobs before this one */
+} u3d_bn_fold_job;
 int64_t u3d_bn_fold_job_bytes(void);
 int32_t u3d_bn_fold_job_blocks(int32_t kvol, int32_t cout, int32_t cin);
 int32_t u3d_bn_fold_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
@@ -251,13 +259,8 @@ int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const in
  * atomicMax on the bit pattern: exact, order independent, no host sync.  A NaN or Inf input leaves +Inf.  The caller zeroes the slot.
  * c % 8 == 0.
  * u3d_bn_fold_fp8_batched: u3d_bn_fold_batched's job-table shape, ONE launch for all pairs, one workgroup per (pair, output channel).
- * jobs: DEVICE array of njobs records of u3d_bn_fold_fp8_job_bytes() bytes, natural C layout
- *   { const float* w; const float *gamma, *beta, *mean, *var; uint8_t* qw; int32_t* e_w; float* shift; int64_t sk, sa, sb; float eps;
- *     int32_t kvol, cout, cin, first_block; }
- * w / strides / gamma .. var as u3d_bn_fold_batched.  With wf = w * gamma / sqrt(var + eps) in f32 (the product that entry rounds to
- * bf16): e_w int32 [cout] = the smallest e with max |wf[:, co, :]| <= 448 * 2^e (0 for an all-zero channel), qw e4m3 [kvol][cout][cin] =
- * q(wf, e_w[co]) rounded ONCE from f32, shift f32 [cout] = beta - mean * scale.  first_block = the sum of cout over the jobs before
- * this one, total_blocks = that sum over all jobs.
+ * jobs: DEVICE array of njobs u3d_bn_fold_fp8_job records (below; u3d_bn_fold_fp8_job_bytes() = its size), total_blocks = the sum of
+ * cout over all jobs.  wf = w * gamma / sqrt(var + eps) in f32 is the product u3d_bn_fold_batched rounds to bf16.
  * u3d_igemm_fwd_affine_fp8: out bf16 = bf16_rne(act(conv(in; qw) * colscale[col] + shift[col])), e4m3 in [n_in][cin] and qw
  * [kvol][cout][cin], f32 accumulation on the block-scaled MFMA with unit block scales, colscale / shift f32 [cout] (16-byte aligned),
  * the other arguments as u3d_igemm_fwd_affine_bf16.  An absent neighbour (-1) contributes exact zeros.  Rows at or past *n_out_dev are
@@ -267,6 +270,20 @@ int32_t u3d_igemm_fwd_affine_bf16(const void* in, const void* w_folded, const in
 enum { U3D_FWD_FP8_K_256X256, U3D_FWD_FP8_K_192X256, U3D_FWD_FP8_K_256X256_ROWS, U3D_FWD_FP8_K_COUNT };
 int32_t u3d_quant_rows_e4m3(const void* x, void* q, const int32_t* n_dev, int32_t n_cap, int32_t c, const int32_t* e_dev, u3d_stream s);
 int32_t u3d_absmax_rows(const void* x, const int32_t* n_dev, int32_t n_cap, int32_t c, float* slot, u3d_stream s);
+typedef struct u3d_bn_fold_fp8_job {
+  const float* w;          /* w, sk / sa / sb, gamma .. var, eps: as in u3d_bn_fold_job */
+  const float* gamma;
+  const float* beta;
+  const float* mean;
+  const float* var;
+  uint8_t* qw;             /* written: e4m3 [kvol][cout][cin] = q(wf, e_w[co]), rounded ONCE from f32 */
+  int32_t* e_w;            /* written: int32 [cout], the smallest e with max |wf[:, co, :]| <= 448 * 2^e (0 for an all-zero channel) */
+  float* shift;            /* written: f32 [cout] = beta - mean * scale */
+  int64_t sk, sa, sb;
+  float eps;
+  int32_t kvol, cout, cin;
+  int32_t first_block;     /* the sum of cout over the jobs before this one */
+} u3d_bn_fold_fp8_job;
 int64_t u3d_bn_fold_fp8_job_bytes(void);
 int32_t u3d_bn_fold_fp8_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
 int32_t u3d_igemm_fwd_affine_fp8(const void* in, const void* qw, const int32_t* nbr, int32_t ld, const float* colscale,
@@ -304,9 +321,6 @@ int32_t u3d_igemm_direct_affine_bf16(const void* in, const void* w_folded, const
 /* The weight side of the same product: dst bf16 [3][k][a][b] = (hi, lo, hi) of the f32 element src[ik * sk + ia * sa + ib * sb]
  * (element strides: the checkpoint layouts [kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW] are read in place). */
 int32_t u3d_split3_weights(const float* src, int64_t sk, int64_t sa, int64_t sb, int32_t k, int32_t a, int32_t b, void* dst, u3d_stream s);
-/* The same for every convolution weight of a step in ONE launch.  jobs: device array of njobs records of u3d_split3_job_bytes() bytes,
- * natural C layout { const float* src; void* dst; int64_t sk, sa, sb; int32_t k, a, b, first_block; }, first_block = sum of
- * u3d_split3_job_blocks(k, a, b) over the jobs before this one; total_blocks = that sum over all jobs. */
 /* hi / lo bf16 planes (as u3d_split_rows_f32, all rows live) of up to 32 strided f32 row matrices in one launch; `jobs` is a HOST
  * structure (its contents travel in the kernel arguments; first_block is filled by the call). */
 typedef struct U3dSplitRowsJobs {
@@ -319,6 +333,15 @@ typedef struct U3dSplitRowsJobs {
 int32_t u3d_split_rows_batch(const U3dSplitRowsJobs* jobs, u3d_stream s);
 /* out = (a + b) + c over n f32 elements (n % 4 == 0, 16-byte aligned): the three partial weight gradients of a split-bf16 product. */
 int32_t u3d_sum3_f32(const float* a, const float* b, const float* c, float* out, int64_t n, u3d_stream s);
+/* u3d_split3_weights for every convolution weight of a step in ONE launch.  jobs: DEVICE array of njobs u3d_split3_job records
+ * (u3d_split3_job_bytes() = its size); total_blocks = the sum of u3d_split3_job_blocks(K, A, B) over all jobs. */
+typedef struct u3d_split3_job {
+  const float* src;        /* src, sk / sa / sb, K / A / B and dst: u3d_split3_weights' src, strides, k / a / b and dst */
+  uint16_t* dst;
+  int64_t sk, sa, sb;
+  int32_t K, A, B;
+  int32_t first_block;     /* the sum of u3d_split3_job_blocks(K, A, B) over the jobs before this one */
+} u3d_split3_job;
 int64_t u3d_split3_job_bytes(void);
 int32_t u3d_split3_job_blocks(int32_t k, int32_t a, int32_t b);
 int32_t u3d_split3_weights_batch(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);

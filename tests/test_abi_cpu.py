@@ -159,9 +159,12 @@ def test_struct_size_pins():
     """The sizes of the hand-written classes these layouts replaced: the derived layouts are the ones the kernels read."""
     s = abi.load().structs
     assert sorted(s) == sorted(["u3d_bitgrid", "u3d_declayer_params", "u3d_declayer_dims", "u3d_wpack_desc", "U3dSplitRowsJobs",
-                                "u3d_permute_desc", "u3d_fwd_plan_info"])
+                                "u3d_permute_desc", "u3d_fwd_plan_info", "u3d_bn_fold_job", "u3d_bn_fold_fp8_job", "u3d_split3_job"])
     for cls, size in ((nv.BitGridStruct, 40), (nv.DecLayerParams, 680), (nv.DecLayerDims, 68), (nv.WPackDesc, 48),
-                      (nv._SplitRowsJobs, 1032), (nv.FwdPlanInfo, 28)):
+                      (nv._SplitRowsJobs, 1032), (nv.FwdPlanInfo, 28), (nv.BnFoldJob, 104), (nv.BnFoldFp8Job, 112),
+                      (nv.Split3Set._Job, 56)):
         assert C.sizeof(cls) == size and issubclass(cls, C.Structure), cls
     assert np.dtype(nv.PERMUTE_DESC_DTYPE).itemsize == 56
     assert [n for n, _ in nv.BitGridStruct._fields_] == ["words", "prefix", "batch", "dz", "dy", "dx", "layout", "row_capacity"]
+    assert [n for n, _ in nv.BnFoldJob._fields_] == ["w", "gamma", "beta", "mean", "var", "w_folded", "shift", "sk", "sa", "sb", "eps",
+                                                     "kvol", "cout", "cin", "scale_only", "first_block"]

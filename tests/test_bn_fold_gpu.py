@@ -267,7 +267,7 @@ def test_model_structure_batched_tail_and_refresh(scene, monkeypatch):
     # dense stack is not bitwise reproducible from run to run (f32 sums in another order: ~1e-3 after the bf16 roundings), while half
     # a standard deviation on every channel of the last BatchNorm moves the O(1) feature volume by tens of percent
     bn = dict(model.named_modules())["pts_neck.extra_blocks.1"]
-    shift = inf._map[id(bn)][1]
+    shift = inf._by_bn[id(bn)].shift
     a, s0 = inf.extract_pts_feat(pts)[0].double(), shift.clone()
     bn.running_mean.add_(0.5)
     b, s1 = inf.extract_pts_feat(pts)[0].double(), shift.clone()

@@ -128,7 +128,7 @@ def test_default_is_unchanged_and_wrapper_follows_classify(named_model):
     f1, u1 = classify(m, sparse_levels=True)
     assert inf_s.sparse_levels is True and inf_s.folded == [p[0] for p in f1] and inf_s.unfolded == u1
     # no device: nothing allocated, the scope refuses
-    assert inf_s._map == {}
+    assert inf_s._by_bn == {} and all(r.w_folded is None and r.route is None for r in inf_s._records)
     with torch.no_grad(), pytest.raises(RuntimeError, match="device"):
         with inf_s.scope():
             pass

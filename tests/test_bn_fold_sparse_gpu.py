@@ -267,7 +267,7 @@ def test_model_batched_tail_and_refresh(scene):
     model.set_precision("bf16")
     inf = InferenceModel(model, sparse_levels=True)
     # refresh(): the fold and one pack launch per channel count; the plans stay while nothing moved
-    assert [p[4] for p in inf._packs] == [64, 128] and [p[2] for p in inf._packs] == [4, 4]
+    assert [p.c for p in inf._packs] == [64, 128] and [p.n for p in inf._packs] == [4, 4]
     table, packs = inf._table, inf._packs
     inf.refresh()
     assert inf._table is table and inf._packs is packs
@@ -286,9 +286,9 @@ def test_model_batched_tail_and_refresh(scene):
     # not asserted: the seeded running statistics are not the statistics of these activations, so the step has no known size in
     # units of the features.)
     bn = dict(model.named_modules())["pts_middle_encoder.encoder_layers.encoder_layer2.2.1"]
-    ent = inf._map[id(bn)]
-    assert ent[0].shape == (27, 64, 32) and len(ent) == 3 and ent[2] is None
-    shift = ent[1]
+    ent = inf._by_bn[id(bn)]
+    assert ent.w_folded.shape == (27, 64, 32) and ent.sparse_level and ent.route == "direct" and ent.w_packed is None
+    shift = ent.shift
     delta = 4 * bn.running_var.sqrt()
     a, s0 = inf.extract_pts_feat(pts)[0].double(), shift.clone()
     bn.running_mean.add_(delta)
@@ -304,13 +304,13 @@ def test_model_batched_tail_and_refresh(scene):
     assert _rel(b, a) <= 1e-2 and _rel(c, a) > 1e-2 and _rel(c, fresh) <= 1e-2
     # a halo-served block: its packed weights are rewritten by the same refresh()
     bn2 = dict(model.named_modules())["pts_middle_encoder.encoder_layers.encoder_layer3.0.bn1"]
-    e2 = inf._map[id(bn2)]
-    assert len(e2) == 3 and e2[2].shape == (27, 64, 64)
-    p0 = e2[2].clone()
+    e2 = inf._by_bn[id(bn2)]
+    assert e2.sparse_level and e2.route == "halo" and e2.w_packed.shape == (27, 64, 64)
+    p0 = e2.w_packed.clone()
     bn2.running_var.mul_(1.7)
-    assert torch.equal(e2[2].view(torch.int16), p0.view(torch.int16))
+    assert torch.equal(e2.w_packed.view(torch.int16), p0.view(torch.int16))
     inf.refresh()
-    assert not torch.equal(e2[2].view(torch.int16), p0.view(torch.int16))
-    assert torch.equal(e2[2].view(torch.int16), nv.subm_halo_wpack(e2[0]).view(torch.int16))
+    assert not torch.equal(e2.w_packed.view(torch.int16), p0.view(torch.int16))
+    assert torch.equal(e2.w_packed.view(torch.int16), nv.subm_halo_wpack(e2.w_folded).view(torch.int16))
     bn2.running_var.div_(1.7)
     inf.refresh()

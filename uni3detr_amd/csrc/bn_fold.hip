@@ -5,36 +5,24 @@
 // the LDS-DMA implicit-GEMM kernels already adds (glds_epilogue.inc, u3d_igemm_fwd_affine_bf16): conv -> BatchNorm -> ReLU becomes one
 // launch and one trip over the activation tensor.
 //
-// One launch folds every conv + BatchNorm pair of a model: the job table lives on the device (as U3dSplit3Job does for the split-bf16
+// One launch folds every conv + BatchNorm pair of a model: the job table lives on the device (as u3d_split3_job does for the split-bf16
 // weights, split_bf16.hip), blocks [first_block[j], first_block[j + 1]) of the grid work on job j.  The f32 master weight is read in
 // place through element strides, so both checkpoint layouts ([kD,kH,kW,Cin,Cout] and [Cout,Cin,kD,kH,kW]) need no re-laid-out copy.
 // Nothing here allocates or synchronises.
 #include "common.h"
 
-typedef unsigned short u16;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-// natural C layout (include/u3d_hip.h describes it field by field; u3d_bn_fold_job_bytes() is its size)
-struct U3dBnFoldJob {
-  const float* w;                              // f32 master weight: element (k, co, ci) at w[k * sk + co * sa + ci * sb]
-  const float *gamma, *beta, *mean, *var;      // f32 [cout]
-  u16* w_folded;                               // bf16 [kvol][cout][cin]: bf16_rne(w * scale[co])
-  float* shift;                                // f32 [cout]: beta - mean * scale (not written when scale_only)
-  long long sk, sa, sb;
-  float eps;
-  int kvol, cout, cin, scale_only, first_block;
-};
-
 #define BNFOLD_EPB 2048          /* elements per block: 256 threads x 4 consecutive input channels x 2 */
 
-__global__ __launch_bounds__(256) void k_bn_fold_batched(const U3dBnFoldJob* __restrict__ jobs, int njobs) {
+__global__ __launch_bounds__(256) void k_bn_fold_batched(const u3d_bn_fold_job* __restrict__ jobs, int njobs) {
   int lo = 0, hi = njobs;                               // the job of this block: last j with first_block[j] <= blockIdx.x
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
     if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid;
   }
-  const U3dBnFoldJob jb = jobs[lo];
+  const u3d_bn_fold_job jb = jobs[lo];
   const int blk = (int)blockIdx.x - jb.first_block;
   if (blk == 0 && !jb.scale_only)                       // the job's first block also leaves the shift
     for (int c = threadIdx.x; c < jb.cout; c += 256) {
@@ -57,17 +45,17 @@ __global__ __launch_bounds__(256) void k_bn_fold_batched(const U3dBnFoldJob* __r
   }
 }
 
-extern "C" int64_t u3d_bn_fold_job_bytes(void) { return (int64_t)sizeof(U3dBnFoldJob); }
+extern "C" int64_t u3d_bn_fold_job_bytes(void) { return (int64_t)sizeof(u3d_bn_fold_job); }
 extern "C" int32_t u3d_bn_fold_job_blocks(int32_t kvol, int32_t cout, int32_t cin) {
   const long long n = (long long)kvol * cout * cin;
   return (int32_t)((n + BNFOLD_EPB - 1) / BNFOLD_EPB);
 }
-// jobs: DEVICE array of njobs U3dBnFoldJob records, first_block ascending from 0 (the sum of u3d_bn_fold_job_blocks over the jobs
+// jobs: DEVICE array of njobs u3d_bn_fold_job records, first_block ascending from 0 (the sum of u3d_bn_fold_job_blocks over the jobs
 // before); total_blocks = that sum over all jobs.  Every job: cin % 4 == 0, w_folded 8-byte aligned (the caller's side of the contract:
 // the table is on the device and is not read here).
 extern "C" int32_t u3d_bn_fold_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s) {
   U3D_REQUIRE(jobs && njobs > 0 && total_blocks > 0, U3D_ERR_ARG);
-  hipLaunchKernelGGL(k_bn_fold_batched, dim3(total_blocks), dim3(256), 0, s, (const U3dBnFoldJob*)jobs, njobs);
+  hipLaunchKernelGGL(k_bn_fold_batched, dim3(total_blocks), dim3(256), 0, s, (const u3d_bn_fold_job*)jobs, njobs);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

@@ -96,26 +96,16 @@ extern "C" int32_t u3d_absmax_rows(const void* x, const int32_t* n_dev, int32_t 
 // channels first, so the workgroup walks its kvol * cin elements twice (the second time out of L2).  The f32 product is
 // u3d_bn_fold_batched's, and the code is rounded from it once - not from the bf16 copy.
 // ---------------------------------------------------------------------------------------------
-// natural C layout (include/u3d_hip.h describes it field by field; u3d_bn_fold_fp8_job_bytes() is its size)
-struct U3dBnFoldFp8Job {
-  const float* w;                              // f32 master weight: element (k, co, ci) at w[k * sk + co * sa + ci * sb]
-  const float *gamma, *beta, *mean, *var;      // f32 [cout]
-  unsigned char* qw;                           // e4m3 [kvol][cout][cin]: q(w * scale[co], e_w[co])
-  int* e_w;                                    // int32 [cout]: smallest e with max |w * scale[co]| <= 448 * 2^e (0 for an all-zero channel)
-  float* shift;                                // f32 [cout]: beta - mean * scale
-  long long sk, sa, sb;
-  float eps;
-  int kvol, cout, cin, first_block;            // first_block: the sum of cout over the jobs before this one
-};
+// (the job record: u3d_bn_fold_fp8_job, include/u3d_hip.h)
 
-__global__ __launch_bounds__(256) void k_bn_fold_fp8_batched(const U3dBnFoldFp8Job* __restrict__ jobs, int njobs) {
+__global__ __launch_bounds__(256) void k_bn_fold_fp8_batched(const u3d_bn_fold_fp8_job* __restrict__ jobs, int njobs) {
   __shared__ unsigned red[4];
   int lo = 0, hi = njobs;                               // the job of this block: last j with first_block[j] <= blockIdx.x
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
     if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid;
   }
-  const U3dBnFoldFp8Job jb = jobs[lo];
+  const u3d_bn_fold_fp8_job jb = jobs[lo];
   const int co = (int)blockIdx.x - jb.first_block;
   if (co >= jb.cout) return;
   const float scale = jb.gamma[co] / sqrtf(jb.var[co] + jb.eps);
@@ -149,11 +139,11 @@ __global__ __launch_bounds__(256) void k_bn_fold_fp8_batched(const U3dBnFoldFp8J
   }
 }
 
-extern "C" int64_t u3d_bn_fold_fp8_job_bytes(void) { return (int64_t)sizeof(U3dBnFoldFp8Job); }
-// jobs: DEVICE array of njobs U3dBnFoldFp8Job records, first_block ascending from 0; total_blocks = the sum of cout over all jobs.
+extern "C" int64_t u3d_bn_fold_fp8_job_bytes(void) { return (int64_t)sizeof(u3d_bn_fold_fp8_job); }
+// jobs: DEVICE array of njobs u3d_bn_fold_fp8_job records, first_block ascending from 0; total_blocks = the sum of cout over all jobs.
 extern "C" int32_t u3d_bn_fold_fp8_batched(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s) {
   U3D_REQUIRE(jobs && njobs > 0 && total_blocks > 0, U3D_ERR_ARG);
-  hipLaunchKernelGGL(k_bn_fold_fp8_batched, dim3(total_blocks), dim3(256), 0, (hipStream_t)s, (const U3dBnFoldFp8Job*)jobs, njobs);
+  hipLaunchKernelGGL(k_bn_fold_fp8_batched, dim3(total_blocks), dim3(256), 0, (hipStream_t)s, (const u3d_bn_fold_fp8_job*)jobs, njobs);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

@@ -26,9 +26,10 @@ sparse_levels=True (off by default) also folds the rest of SparseEncoderHD: ever
 convs.  The halo kernels and the direct-operand kernels have an affine instantiation for it (shift, then the block's identity as the
 addend, then ReLU, one rounding: u3d_subm_halo_conv64 / 128_affine_bf16, u3d_igemm_direct_affine_bf16), and refresh() packs the folded
 64- / 128-channel weights into the halo kernels' fragment order once (one batched launch per channel count) instead of once per conv
-and forward.  conv_input and the FPN entries above stay unfolded.  A folded conv is routed by shape when it runs (sparse.conv_folded):
-halo kernel, direct-operand kernel, the LDS-DMA affine kernel - and ONE case falls back to conv + u3d_bn_apply exactly as model.eval()
-runs it: the conv2 of a 64- / 128- / 256-channel block on a level the halo kernels do not serve (fewer than 4096 rows, more rows than
+and forward.  conv_input and the FPN entries above stay unfolded.  A folded pair is one record (sparse.FoldedPair) whose `route` - halo
+kernel, direct-operand kernel, the LDS-DMA affine kernel - is fixed by shape when its buffers are allocated; a call decides only
+whether the level's halo tables serve it (sparse._halo_of).  ONE case falls back to conv + u3d_bn_apply exactly as model.eval() runs
+it: the conv2 of a 64- / 128- / 256-channel block on a level the halo kernels do not serve (fewer than 4096 rows, more rows than
 the halo build's bitmap holds, or 256 channels as in ScanNet-large's last stage).  Its BatchNorm adds the identity, and the LDS-DMA
 kernels take a shift or an addend, not both.  Such a layer is listed in `folded` (its weights are folded; conv1 of the same block takes
 the LDS-DMA affine kernel) and costs its u3d_bn_apply launch on the levels where it falls back.
@@ -70,6 +71,12 @@ def classify(model, sparse_levels=False):
     """-> (folded, unfolded): folded = [(name, weight parameter, layout, BatchNorm module)], unfolded = [(name, reason)], in forward
     order.  `name` is the convolution's module path.  Needs no device.  sparse_levels: also fold SparseEncoderHD's block convs and
     narrow strided convs (input channels % 4 == 0: what the fold kernel writes)."""
+    folded, unfolded = _classify(model, sparse_levels)
+    return [p[:4] for p in folded], unfolded
+
+
+def _classify(model, sparse_levels):
+    """classify(), each folded pair with a fifth item: whether it is one that only sparse_levels folds (FoldedPair.sparse_level)."""
     from .plugin.dense import SECOND3D, SECOND3DFPN
     from .plugin.sparse_encoder import SparseBasicBlock, SparseEncoderHD
     names = {id(m): n for n, m in model.named_modules()}
@@ -77,14 +84,16 @@ def classify(model, sparse_levels=False):
 
     def pair(conv, bn, weight, layout, cin, cout, why=None, sparse_level=False):
         name = names[id(conv)]
-        if sparse_level and sparse_levels and cin % 4 == 0:
-            why = None                  # the halo / direct-operand affine kernels, else the LDS-DMA one (sparse.conv_folded)
-        elif why is None and not _wide(cin, cout):
+        if why is None and not _wide(cin, cout):
             why = _WHY_NARROW.format(cin=cin, cout=cout)
+        # what only sparse_levels folds: on the halo / direct-operand affine kernels, else the LDS-DMA one (sparse.conv_folded)
+        only_sparse = bool(why is not None and sparse_level and sparse_levels and cin % 4 == 0)
+        if only_sparse:
+            why = None
         if why is None and not (isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.affine and bn.track_running_stats):
             why = "BatchNorm without affine parameters or running statistics"
         if why is None:
-            folded.append((name, weight, layout, bn))
+            folded.append((name, weight, layout, bn, only_sparse))
         else:
             unfolded.append((name, why))
 
@@ -179,6 +188,16 @@ def classify_fp8(model, pairs=None):
     return fp8, skipped
 
 
+def _sources(r):
+    """The f32 tensors a record is folded from: the conv weight and the BatchNorm's parameters and running statistics."""
+    return r.weight, r.bn.weight, r.bn.bias, r.bn.running_mean, r.bn.running_var
+
+
+def _fold_job(r, *destinations):
+    """A record as a row of native.BnFoldTable / BnFoldFp8Table."""
+    return (r.weight.detach(), r.layout, r.bn.weight.detach(), r.bn.bias.detach(), r.bn.running_mean, r.bn.running_var, r.bn.eps) + destinations
+
+
 class InferenceModel:
     """A Uni3DETR in eval mode and bf16 precision with its foldable BatchNorms folded away.  Owns the folded weights and shifts;
     the wrapped model keeps its parameters, its state_dict and its own (unfolded) eval path.
@@ -196,46 +215,26 @@ class InferenceModel:
                              "which keeps the unfolded path)")
         self.model = model
         self.sparse_levels = bool(sparse_levels)
-        self._pairs, unfolded = classify(model, self.sparse_levels)
-        # the pairs only sparse_levels folds: their entries carry a third item and take sparse.conv_folded's routing
-        self._sparse = {p[0] for p in self._pairs} - {p[0] for p in classify(model)[0]} if self.sparse_levels else set()
-        self.folded = [p[0] for p in self._pairs]
+        folded, unfolded = _classify(model, self.sparse_levels)
+        self._records = [sp.FoldedPair(*p) for p in folded]      # in forward order; their buffers and routes: _allocate()
+        self.folded = [r.name for r in self._records]
         self.unfolded = list(unfolded)
         self._table, self._sig = None, None
-        self._map = {}
-        self._buffers = []
+        self._by_bn = {}          # id(BatchNorm module) -> record: what sparse.fold_scope takes; empty until the buffers exist
+        self._fp8 = []            # the records on the fp8 route, in fp8_layers order
         self._packs = None
         self.dense_fp8 = bool(dense_fp8)
-        self.fp8_layers, self.fp8_skipped = classify_fp8(model) if self.dense_fp8 else ([], [])
+        default_pairs = [(r.name, r.weight, r.layout, r.bn) for r in self._records if not r.sparse_level]
+        self.fp8_layers, self.fp8_skipped = classify_fp8(model, default_pairs) if self.dense_fp8 else ([], [])
         self.fp8_headroom = None
-        self._fp8, self._fp8_table, self._fp8_sig = [], None, None      # sparse.Fp8Entry per fp8 layer, in fp8_layers order
-        if self._pairs and self._pairs[0][1].is_cuda:
+        self._fp8_e_a, self._fp8_table, self._fp8_sig = None, None, None
+        if self._records and self._records[0].weight.is_cuda:
             self._allocate()
             self.refresh()
 
     @property
     def fp8_calibrated(self):
         return self.fp8_headroom is not None
-
-    def _allocate_fp8(self):
-        """Per fp8 layer an Fp8Entry beside its bf16 buffers (which the calibration forward runs on): codes, channel exponents, column
-        scales; the activation exponents and the absmax slots of all layers are one tensor each (read once after calibration)."""
-        by_name = {p[0]: (p, b) for p, b in zip(self._pairs, self._buffers)}
-        dev = self._buffers[0][0].device
-        old = getattr(self, "_fp8_e_a", None)
-        self._fp8_e_a = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.int32, device=dev) if old is None else old.to(dev)
-        self._fp8_slots = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.float32, device=dev)
-        self._fp8 = []
-        for i, name in enumerate(self.fp8_layers):
-            # the entry SHARES the pair's bf16 buffers: wf stays resident for later calibrations, and both fold launches of a refresh() write
-            # the same values into `shift` (one formula, one f32 evaluation order in both kernels)
-            (_, w, layout, bn), (wf, shift, *_) = by_name[name]
-            ent = sp.Fp8Entry(name, torch.empty(tuple(wf.shape), dtype=torch.uint8, device=dev),
-                              torch.zeros((wf.shape[1],), dtype=torch.int32, device=dev), shift, wf,
-                              self._fp8_e_a[i:i + 1], torch.zeros((wf.shape[1],), dtype=torch.float32, device=dev), self._fp8_slots[i:i + 1])
-            self._fp8.append(ent)
-            self._map[id(bn)] = ent
-        self._fp8_table = None
 
     def _fp8_scales(self):
         """colscale[c] = 2^(e_a + e_w[c]) of every fp8 layer, on the device, into the buffers the entries already point at."""
@@ -251,7 +250,7 @@ class InferenceModel:
         raises with the layer's name."""
         if not self.dense_fp8:
             raise RuntimeError("InferenceModel.calibrate: the model was not wrapped with dense_fp8=True")
-        if not self._map:
+        if not self._by_bn:
             raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
         if not (headroom >= 1.0 and math.isfinite(headroom)):
             raise ValueError(f"calibrate: headroom must be a finite number >= 1, got {headroom!r}")
@@ -289,7 +288,7 @@ class InferenceModel:
             raise RuntimeError("InferenceModel.load_fp8_state: the model was not wrapped with dense_fp8=True")
         if set(state["e_a"]) != set(self.fp8_layers):
             raise ValueError("load_fp8_state: the saved layers are not this model's fp8 layers")
-        if not self._map:
+        if not self._by_bn:
             raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
         if self._fp8:
             self._fp8_e_a.copy_(torch.tensor([int(state["e_a"][n]) for n in self.fp8_layers], dtype=torch.int32))
@@ -298,62 +297,53 @@ class InferenceModel:
         return self
 
     def _allocate(self):
-        """Per pair (w_folded, shift); a pair that only sparse_levels folds gets a third item: w_packed, the folded weights in the
-        halo kernels' fragment order, for the SubM block convs those kernels serve (27 offsets, 64 -> 64 / 128 -> 128), else None."""
+        """Every record's buffers and route (sparse.FoldedPair.allocate).  An fp8 layer keeps its bf16 buffers: w_folded stays resident for
+        later calibrations, and both fold launches of a refresh() write the same values into `shift` (one formula, one f32 evaluation
+        order in both kernels).  The activation exponents and absmax slots of all fp8 layers are one tensor each (read once)."""
         from .plugin.sparse_encoder import SparseConvWeight
         halo_convs = {id(m.weight) for m in self.model.modules() if isinstance(m, SparseConvWeight) and m.subm} if self.sparse_levels else ()
-        self._buffers = []
-        for name, w, layout, bn in self._pairs:
-            k, cout, cin = nv.conv_weight_strides(tuple(w.shape), layout)[:3]
-            buf = (torch.empty((k, cout, cin), dtype=torch.bfloat16, device=w.device),
-                   torch.empty((cout,), dtype=torch.float32, device=w.device))
-            if name in self._sparse:
-                buf += (torch.empty_like(buf[0]) if (id(w) in halo_convs and k == 27 and cin == cout and cin in (64, 128)) else None,)
-            self._buffers.append(buf)
-        self._map = {id(p[3]): b for p, b in zip(self._pairs, self._buffers)}
-        self._packs = None
+        dev = self._records[0].weight.device
         if self.dense_fp8:
-            self._allocate_fp8()
+            e_a = self._fp8_e_a        # (kept across a move to another device: calibration is not repeated)
+            self._fp8_e_a = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.int32, device=dev) if e_a is None else e_a.to(dev)
+            self._fp8_slots = torch.zeros((max(len(self.fp8_layers), 1),), dtype=torch.float32, device=dev)
+        for r in self._records:
+            i = self.fp8_layers.index(r.name) if r.name in self.fp8_layers else None
+            r.allocate(id(r.weight) in halo_convs, None if i is None else (self._fp8_e_a[i:i + 1], self._fp8_slots[i:i + 1]))
+        self._by_bn = {id(r.bn): r for r in self._records}
+        self._fp8 = [r for r in self._records if r.route == "fp8"]
+        assert [r.name for r in self._fp8] == self.fp8_layers
+        self._packs = self._fp8_table = None
 
     def refresh(self):
         """Fold again: after an optimizer step, load_state_dict or a change of the running statistics.  One launch - with
         sparse_levels, one more per channel count (64, 128) that packs the folded block weights for the halo kernels; the job table
         and the pack plans are rebuilt only when a parameter or buffer moved in memory."""
-        if not self._pairs:
+        if not self._records:
             return self
-        if not self._buffers or self._buffers[0][0].device != self._pairs[0][1].device:
+        dev = self._records[0].weight.device
+        if not self._by_bn or self._records[0].w_folded.device != dev:
             self._allocate()
             self._table = None
-        sig = tuple(t.data_ptr() for _, w, _, bn in self._pairs for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        sig = tuple(t.data_ptr() for r in self._records for t in _sources(r))
         if self._table is None or sig != self._sig:
-            rows = []
-            for (_, w, layout, bn), (wf, shift, *_) in zip(self._pairs, self._buffers):
-                for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var):
-                    if t.dtype != torch.float32:
-                        raise TypeError("InferenceModel folds from f32 master parameters and statistics")
-                rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, wf, shift))
-            self._table, self._sig = nv.BnFoldTable(rows), sig
+            if any(t.dtype != torch.float32 for r in self._records for t in _sources(r)):
+                raise TypeError("InferenceModel folds from f32 master parameters and statistics")
+            self._table, self._sig = nv.BnFoldTable([_fold_job(r, r.w_folded, r.shift) for r in self._records]), sig
         self._table.run()
         if self._fp8:
             # the fp8 layers again from the f32 masters (one rounding, not the bf16 copy rounded again): ONE more launch; the channel
             # exponents may have moved, so the column scales follow
             if self._fp8_table is None or sig != self._fp8_sig:
-                by_name = {p[0]: p for p in self._pairs}
-                rows = []
-                for ent in self._fp8:
-                    _, w, layout, bn = by_name[ent.name]
-                    rows.append((w.detach(), layout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                                 ent.qw, ent.e_w, ent.shift))
-                self._fp8_table, self._fp8_sig = nv.BnFoldFp8Table(rows), sig
+                self._fp8_table, self._fp8_sig = nv.BnFoldFp8Table([_fold_job(r, r.qw, r.e_w, r.shift) for r in self._fp8]), sig
             self._fp8_table.run()
             if self.fp8_calibrated:
                 self._fp8_scales()
         if self._packs is None:
-            dev = self._buffers[0][0].device
             by_c = {}
-            for b in self._buffers:
-                if len(b) > 2 and b[2] is not None:
-                    by_c.setdefault(b[0].shape[1], []).append((b[0], b[2]))
+            for r in self._records:
+                if r.w_packed is not None:
+                    by_c.setdefault(r.w_folded.shape[1], []).append((r.w_folded, r.w_packed))
             self._packs = [nv.subm_halo_wpack_plan(by_c[c], dev) for c in sorted(by_c)]
         for plan in self._packs:
             nv.subm_halo_wpack_batched(plan)
@@ -369,10 +359,10 @@ class InferenceModel:
             raise RuntimeError("InferenceModel: gradients are enabled - the folded forward records no autograd graph (use torch.no_grad())")
         if self.fp8_layers and not calibrating and not self.fp8_calibrated:
             raise RuntimeError("InferenceModel(dense_fp8=True): no activation scales yet - run calibrate(batches) or load_fp8_state() first")
-        if not self._map:
+        if not self._by_bn:
             raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
         # the head runs under bf16 autocast, as Uni3DETR.forward_pts_train runs it in this mode (the fused decoder takes bf16 rows)
-        with sp.fold_scope(self._map), torch.autocast("cuda", dtype=torch.bfloat16):
+        with sp.fold_scope(self._by_bn), torch.autocast("cuda", dtype=torch.bfloat16):
             yield self
 
     @torch.no_grad()

@@ -460,6 +460,9 @@ def subm_halo_wpack(w_nmajor, out=None):
     return out
 
 
+HaloWpackPlan = collections.namedtuple("HaloWpackPlan", "src dst n pairs c kvol")      # src / dst: device pointer arrays; pairs: kept alive
+
+
 def subm_halo_wpack_plan(pairs, device):
     """[(src, dst)] of [27, C, C] bf16 tensors, all with the same C in (64, 128) -> plan for subm_halo_wpack_batched (device pointer
     arrays; the tensors must stay alive)."""
@@ -467,14 +470,14 @@ def subm_halo_wpack_plan(pairs, device):
     assert all(tuple(a.shape) == (k, c, c) for a, _ in pairs) and ((k == 27 and c == 64) or c == 128)
     src = torch.tensor([a.data_ptr() for a, _ in pairs], dtype=torch.int64, device=device)
     dst = torch.tensor([b.data_ptr() for _, b in pairs], dtype=torch.int64, device=device)
-    return src, dst, len(pairs), pairs, c, k
+    return HaloWpackPlan(src, dst, len(pairs), pairs, c, k)
 
 
 def subm_halo_wpack_batched(plan):
-    if plan[4] == 64:
-        _check(lib().u3d_subm_halo_wpack_batched(_ptr(plan[0]), _ptr(plan[1]), plan[2], _stream()), "subm_halo_wpack_batched")
+    if plan.c == 64:
+        _check(lib().u3d_subm_halo_wpack_batched(_ptr(plan.src), _ptr(plan.dst), plan.n, _stream()), "subm_halo_wpack_batched")
     else:
-        _check(lib().u3d_subm_halo_wpack128_batched(_ptr(plan[0]), _ptr(plan[1]), plan[2], plan[5], _stream()), "subm_halo_wpack128_batched")
+        _check(lib().u3d_subm_halo_wpack128_batched(_ptr(plan.src), _ptr(plan.dst), plan.n, plan.kvol, _stream()), "subm_halo_wpack128_batched")
 
 
 def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=False, tag="spconv_fwd", max_slots=0):
@@ -677,14 +680,17 @@ def _split3_geometry(w, layout, nmajor):
     return k, a, b, sk, sa, sb
 
 
+def _upload_jobs(jobs, device):
+    """A ctypes array of job records as a device byte tensor (the caller keeps it alive for as long as a launch may read it)."""
+    return torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(device)
+
+
 class Split3Set:
     """Every (conv parameter, layout, n-major?) triple a step asks for, refreshed by ONE launch at the top of the step
     (u3d_split3_weights_batch).  A request the set has not seen yet is served by its own launch and joins the set; entries whose
     parameter died or moved (TrainStep re-homes parameters into its flat buffer) are dropped / re-described at the next refresh."""
 
-    class _Job(C.Structure):
-        _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("sk", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64),
-                    ("K", C.c_int32), ("A", C.c_int32), ("B", C.c_int32), ("first_block", C.c_int32)]
+    _Job = _struct("u3d_split3_job", "_Job")
 
     def __init__(self):
         self.entries = {}            # (data_ptr, nmajor) -> [weakref, layout, nmajor, dst, data_ptr, in the job table?, version, shape]
@@ -742,9 +748,7 @@ class Split3Set:
                 jobs[j].K, jobs[j].A, jobs[j].B, jobs[j].first_block = k, a, b, fb
                 fb += int(lib().u3d_split3_job_blocks(k, a, b))
                 e[5] = True
-            raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8)
-            dev = next(iter(self.entries.values()))[3].device
-            self.jobs_dev = raw.to(dev)
+            self.jobs_dev = _upload_jobs(jobs, next(iter(self.entries.values()))[3].device)
             self._keep.append(self.jobs_dev)
             self.total_blocks, self.njobs, self.dirty = fb, len(self.entries), False
         _check(lib().u3d_split3_weights_batch(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), "split3_weights_batch")
@@ -784,12 +788,7 @@ def split3_weights(weight, layout, nmajor, cache=None):
 # --------------------------------------------------------------------------------------------------
 # Inference: eval-mode BatchNorm folded into the convolution in front of it (csrc/bn_fold.hip, u3d_igemm_fwd_affine_bf16)
 # --------------------------------------------------------------------------------------------------
-class BnFoldJob(C.Structure):
-    """One record of u3d_bn_fold_batched's device job table (include/u3d_hip.h)."""
-    _fields_ = [("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
-                ("w_folded", C.c_void_p), ("shift", C.c_void_p), ("sk", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64),
-                ("eps", C.c_float), ("kvol", C.c_int32), ("cout", C.c_int32), ("cin", C.c_int32), ("scale_only", C.c_int32),
-                ("first_block", C.c_int32)]
+BnFoldJob = _struct("u3d_bn_fold_job", "BnFoldJob")       # one record of u3d_bn_fold_batched's device job table
 
 
 def conv_weight_strides(shape, layout):
@@ -827,29 +826,39 @@ def bn_fold_job_table(specs):
     return jobs, fb
 
 
-class BnFoldTable:
-    """A job table on the device + what it points at (kept alive).  run(): ONE launch folds every pair (u3d_bn_fold_batched)."""
+class _FoldTable:
+    """A fold job table on the device + what it points at (kept alive).  run(): ONE launch over every pair (ENTRY).  pairs: (weight
+    f32 parameter, layout, gamma, beta, running_mean, running_var (f32 [Cout] each), eps, destinations ...); a subclass checks the
+    destinations and fills the records in _jobs(pairs, geo) -> (ctypes array, total blocks), geo[i] = conv_weight_strides of pair i."""
 
     def __init__(self, pairs):
-        """pairs: (weight f32 parameter, layout, gamma, beta, running_mean, running_var (f32 [Cout] each), eps, w_folded bf16
-        [kvol, Cout, Cin], shift f32 [Cout] or None = scale_only)."""
-        specs = []
-        for w, layout, gamma, beta, mean, var, eps, wf, shift in pairs:
-            k, cout, cin = conv_weight_strides(tuple(w.shape), layout)[:3]
+        geo = []
+        for w, layout, gamma, beta, mean, var, *_ in pairs:
+            geo.append(conv_weight_strides(tuple(w.shape), layout))
             for t in (w, gamma, beta, mean, var):
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "bn_fold reads contiguous f32 device tensors"
-            assert all(tuple(t.shape) == (cout,) for t in (gamma, beta, mean, var))
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), self.ENTRY[4:] + " reads contiguous f32 device tensors"
+            assert all(tuple(t.shape) == (geo[-1][1],) for t in (gamma, beta, mean, var))
+        jobs, self.total_blocks = self._jobs(pairs, geo)
+        self.njobs, self.pairs = len(pairs), list(pairs)
+        self.jobs_dev = _upload_jobs(jobs, pairs[0][7].device)
+
+    def run(self):
+        _check(getattr(lib(), self.ENTRY)(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), self.ENTRY[4:])
+
+
+class BnFoldTable(_FoldTable):
+    """destinations: w_folded bf16 [kvol, Cout, Cin], shift f32 [Cout] or None = scale_only."""
+    ENTRY = "u3d_bn_fold_batched"
+
+    def _jobs(self, pairs, geo):
+        specs = []
+        for (w, layout, gamma, beta, mean, var, eps, wf, shift), (k, cout, cin, *_) in zip(pairs, geo):
             assert wf.is_cuda and wf.dtype == torch.bfloat16 and wf.is_contiguous() and tuple(wf.shape) == (k, cout, cin)
             assert shift is None or (shift.is_cuda and shift.dtype == torch.float32 and tuple(shift.shape) == (cout,))
             specs.append(dict(w=w.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), mean=mean.data_ptr(), var=var.data_ptr(),
                               w_folded=wf.data_ptr(), shift=None if shift is None else shift.data_ptr(), shape=w.shape, layout=layout,
                               eps=eps, scale_only=shift is None))
-        jobs, self.total_blocks = bn_fold_job_table(specs)
-        self.njobs, self.pairs = len(specs), list(pairs)
-        self.jobs_dev = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(pairs[0][7].device)
-
-    def run(self):
-        _check(lib().u3d_bn_fold_batched(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), "bn_fold_batched")
+        return bn_fold_job_table(specs)
 
 
 def bn_fold(pairs):
@@ -923,28 +932,18 @@ def absmax_rows(x, n_dev, slot):
     return slot
 
 
-class BnFoldFp8Job(C.Structure):
-    """One record of u3d_bn_fold_fp8_batched's device job table (include/u3d_hip.h)."""
-    _fields_ = [("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
-                ("qw", C.c_void_p), ("e_w", C.c_void_p), ("shift", C.c_void_p), ("sk", C.c_int64), ("sa", C.c_int64), ("sb", C.c_int64),
-                ("eps", C.c_float), ("kvol", C.c_int32), ("cout", C.c_int32), ("cin", C.c_int32), ("first_block", C.c_int32)]
+BnFoldFp8Job = _struct("u3d_bn_fold_fp8_job", "BnFoldFp8Job")       # one record of u3d_bn_fold_fp8_batched's device job table
 
 
-class BnFoldFp8Table:
-    """A job table on the device + what it points at (kept alive).  run(): ONE launch folds and quantises every pair
-    (u3d_bn_fold_fp8_batched)."""
+class BnFoldFp8Table(_FoldTable):
+    """Folds AND quantises every pair.  destinations: qw uint8 [kvol, Cout, Cin], e_w int32 [Cout], shift f32 [Cout]."""
+    ENTRY = "u3d_bn_fold_fp8_batched"
 
-    def __init__(self, pairs):
-        """pairs: (weight f32 parameter, layout, gamma, beta, running_mean, running_var (f32 [Cout] each), eps, qw uint8
-        [kvol, Cout, Cin], e_w int32 [Cout], shift f32 [Cout])."""
+    def _jobs(self, pairs, geo):
         assert int(lib().u3d_bn_fold_fp8_job_bytes()) == C.sizeof(BnFoldFp8Job)
         jobs = (BnFoldFp8Job * len(pairs))()
         fb = 0
-        for j, (w, layout, gamma, beta, mean, var, eps, qw, e_w, shift) in zip(jobs, pairs):
-            k, cout, cin, sk, sa, sb = conv_weight_strides(tuple(w.shape), layout)
-            for t in (w, gamma, beta, mean, var):
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "bn_fold_fp8 reads contiguous f32 device tensors"
-            assert all(tuple(t.shape) == (cout,) for t in (gamma, beta, mean, var))
+        for j, (w, layout, gamma, beta, mean, var, eps, qw, e_w, shift), (k, cout, cin, sk, sa, sb) in zip(jobs, pairs, geo):
             assert qw.is_cuda and qw.dtype == torch.uint8 and qw.is_contiguous() and tuple(qw.shape) == (k, cout, cin)
             assert e_w.is_cuda and e_w.dtype == torch.int32 and tuple(e_w.shape) == (cout,)
             assert shift.is_cuda and shift.dtype == torch.float32 and tuple(shift.shape) == (cout,)
@@ -953,11 +952,7 @@ class BnFoldFp8Table:
             j.sk, j.sa, j.sb, j.eps = sk, sa, sb, float(eps)
             j.kvol, j.cout, j.cin, j.first_block = k, cout, cin, fb
             fb += cout
-        self.total_blocks, self.njobs, self.pairs = fb, len(pairs), list(pairs)
-        self.jobs_dev = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(pairs[0][7].device)
-
-    def run(self):
-        _check(lib().u3d_bn_fold_fp8_batched(_ptr(self.jobs_dev), self.njobs, self.total_blocks, _stream()), "bn_fold_fp8_batched")
+        return jobs, fb
 
 
 def igemm_fwd_affine_fp8(qin, qw, nbr, colscale, shift, relu, n_out_dev, n_out, out=None, tag="spconv_fwd"):

@@ -538,10 +538,9 @@ FUSED_CONV_STATS = True
 
 
 # ---- inference: eval-mode BatchNorm folded into the convolution (uni3detr_amd/inference.py) ---------------------------------------------
-# Inside fold_scope(table) a conv_bn() call whose BatchNorm module is in `table` (id(bn) -> (w_folded, shift), the buffers an
-# InferenceModel owns) runs as ONE launch, conv_affine(); every other call, and every call outside a scope, is what it always was.
-# An entry of three, (w_folded, shift, w_packed or None), is a sparse-level pair of InferenceModel(sparse_levels=True): conv_folded().
-# An Fp8Entry is a pair of InferenceModel(dense_fp8=True): conv_affine_fp8(), or while calibrating the bf16 conv_affine() + absmax_rows.
+# Inside fold_scope(table) a conv_bn() call whose BatchNorm module is in `table` (id(bn) -> FoldedPair, the records an InferenceModel
+# owns) runs on the kernel the record's `route` names, conv_folded(); every other call, and every call outside a scope, is what it
+# always was.
 _FOLD = [None]
 
 
@@ -555,79 +554,103 @@ def fold_scope(table):
         _FOLD[0] = prev
 
 
+class FoldedPair:
+    """One folded conv + BatchNorm pair of an InferenceModel.  name / weight / layout / bn: the convolution's module path, its f32
+    parameter in its checkpoint layout and the BatchNorm module - what refresh() folds from; sparse_level: a pair only
+    InferenceModel(sparse_levels=True) folds.  allocate() adds the buffers and fixes the route: w_folded bf16 [kvol, Cout, Cin], shift
+    f32 [Cout] (native.BnFoldTable) and w_packed, w_folded in the halo kernels' fragment order or None.  A pair of
+    InferenceModel(dense_fp8=True) also has qw uint8 [kvol, Cout, Cin] e4m3 codes and e_w int32 [Cout] (native.BnFoldFp8Table, which
+    writes the same `shift`), e_a: the activation exponent as a device int32 [1] (what the quantise pass reads) and colscale f32 [Cout]
+    = 2^(e_a + e_w), both set by calibration, which runs on w_folded, and slot: this layer's f32 absmax slot.
+    route     the kernel, and what becomes of a residual (a block's conv2)
+    "affine"  LDS-DMA affine (nv.igemm_fwd_affine); a residual is an error
+    "direct"  direct-operand affine (nv.igemm_direct_affine), which takes the residual
+    "halo"    nv.subm_halo_conv_affine, which takes the residual, where the level's halo tables serve the call (_halo_of: the one
+              decision left to the call); else as "level"
+    "level"   LDS-DMA affine: every other sparse-level pair (ScanNet-large's 256-channel block convs).  With a residual conv_folded()
+              -> None and conv_bn runs conv + u3d_bn_apply: the LDS-DMA kernels take a shift OR an addend
+    "fp8"     conv_affine_fp8, or while calibrating absmax_rows + the LDS-DMA affine launch on w_folded; a residual is an error"""
+    __slots__ = ("name", "weight", "layout", "bn", "sparse_level", "route", "w_folded", "shift", "w_packed",
+                 "qw", "e_w", "e_a", "colscale", "slot", "calibrating", "calibrated")
+
+    def __init__(self, name, weight, layout, bn, sparse_level):
+        self.name, self.weight, self.layout, self.bn, self.sparse_level = name, weight, layout, bn, sparse_level
+        self.route = self.w_folded = self.shift = self.w_packed = None
+        self.qw = self.e_w = self.e_a = self.colscale = self.slot = None
+        self.calibrating = self.calibrated = False
+
+    def allocate(self, halo_conv, fp8=None):
+        """The buffers, on the parameter's device, and the route.  halo_conv: a SubM conv (the halo kernels serve 27 offsets, 64 -> 64 /
+        128 -> 128 of them); fp8: None or (e_a, slot), this layer's views of the model-wide tables."""
+        dev = self.weight.device
+        k, cout, cin = nv.conv_weight_strides(tuple(self.weight.shape), self.layout)[:3]
+        self.w_folded = torch.empty((k, cout, cin), dtype=torch.bfloat16, device=dev)
+        self.shift = torch.empty((cout,), dtype=torch.float32, device=dev)
+        packed = self.sparse_level and halo_conv and k == 27 and cin == cout and cin in (64, 128)
+        self.w_packed = torch.empty_like(self.w_folded) if packed else None
+        self.route = ("fp8" if fp8 else "affine" if not self.sparse_level else "halo" if packed
+                      else "direct" if nv.direct_serves(cin, cout, k) else "level")
+        if fp8:
+            self.qw = torch.empty((k, cout, cin), dtype=torch.uint8, device=dev)
+            self.e_w = torch.zeros((cout,), dtype=torch.int32, device=dev)
+            self.colscale = torch.zeros((cout,), dtype=torch.float32, device=dev)
+            self.e_a, self.slot = fp8
+
+
+def _inference_input(what, feats, w, geom, residual=None):
+    """The input checks of the inference path, for its three launch paths.  w: the pair's weights or codes, [kvol, Cout, Cin]."""
+    if torch.is_grad_enabled() and (feats.requires_grad or w.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError(f"{what} is an inference path: it records no autograd node")
+    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
+        raise RuntimeError(f"{what} needs bf16 device rows, got {feats.dtype} on {feats.device}")
+    if feats.shape[1] != w.shape[2]:
+        raise ValueError(f"{what}: input has {feats.shape[1]} channels, folded weight expects {w.shape[2]}")
+    if residual is not None and not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == (geom.n_out, w.shape[1])):
+        raise ValueError(f"{what}: the residual must be bf16 rows of the output's shape")
+
+
 def conv_affine(feats, w_folded, shift, geom, relu=True):
     """relu(conv(feats; w_folded) + shift) in one launch (u3d_igemm_fwd_affine_bf16): conv -> eval-mode BatchNorm -> ReLU with the
     BatchNorm's scale folded into the bf16 n-major weights [kvol, Cout, Cin] and its shift kept in f32 (native.bn_fold).  Inference
     only (no autograd node); bf16 rows, channels % 64 == 0 - anything else is an error, not a detour."""
-    if torch.is_grad_enabled() and (feats.requires_grad or w_folded.requires_grad):
-        raise RuntimeError("conv_affine is an inference path: it records no autograd node")
-    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
-        raise RuntimeError(f"conv_affine needs bf16 device rows, got {feats.dtype} on {feats.device}")
-    kvol, cin = w_folded.shape[0], w_folded.shape[2]
-    if feats.shape[1] != cin:
-        raise ValueError(f"conv_affine: input has {feats.shape[1]} channels, folded weight expects {cin}")
+    _inference_input("conv_affine", feats, w_folded, geom)
     nv.CALL_KIND = geom.kind
-    nbr = geom.nbr_fwd if kvol > 1 else None
+    nbr = geom.nbr_fwd if w_folded.shape[0] > 1 else None
     return nv.igemm_fwd_affine(feats.contiguous(), w_folded, nbr, shift, relu, geom.n_out_dev, geom.n_out)
-
-
-class Fp8Entry:
-    """A conv + BatchNorm pair on the fp8 route (InferenceModel(dense_fp8=True)).  Its own type: conv_bn tells the other entries
-    apart by their length.  qw uint8 [kvol, Cout, Cin] e4m3 codes, e_w int32 [Cout], shift f32 [Cout] (native.BnFoldFp8Table); e_a: the
-    activation exponent as a device int32 [1] (what the quantise pass reads) and colscale f32 [Cout] = 2^(e_a + e_w), both set by
-    calibration; w_folded: the bf16 folded weights the calibration forward runs on; slot: this layer's f32 absmax slot."""
-    __slots__ = ("name", "qw", "e_w", "shift", "w_folded", "e_a", "colscale", "slot", "calibrating", "calibrated")
-
-    def __init__(self, name, qw, e_w, shift, w_folded, e_a, colscale, slot):
-        self.name, self.qw, self.e_w, self.shift, self.w_folded = name, qw, e_w, shift, w_folded
-        self.e_a, self.colscale, self.slot = e_a, colscale, slot
-        self.calibrating = self.calibrated = False
 
 
 def conv_affine_fp8(feats, ent, geom, relu=True):
     """relu(conv(q(feats); qw) * colscale + shift) in two launches: the bf16 input rows are quantised to e4m3 under the layer's
     calibrated exponent (u3d_quant_rows_e4m3), then the fp8 convolution runs (u3d_igemm_fwd_affine_fp8).  Inference only; bf16 rows,
     a shape native.fwd_fp8_plan serves - anything else is an error, not a detour."""
-    if torch.is_grad_enabled() and feats.requires_grad:
-        raise RuntimeError("conv_affine_fp8 is an inference path: it records no autograd node")
-    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
-        raise RuntimeError(f"conv_affine_fp8 needs bf16 device rows, got {feats.dtype} on {feats.device}")
+    _inference_input("conv_affine_fp8", feats, ent.qw, geom)
     if not ent.calibrated:
         raise RuntimeError(f"fp8 layer {ent.name} has no activation scale yet: run InferenceModel.calibrate() or load_fp8_state() first")
-    kvol, cin = ent.qw.shape[0], ent.qw.shape[2]
-    if feats.shape[1] != cin:
-        raise ValueError(f"conv_affine_fp8: input has {feats.shape[1]} channels, folded weight expects {cin}")
     nv.CALL_KIND = geom.kind
     qin = nv.quant_rows_e4m3(feats.contiguous(), ent.e_a, geom.n_in_dev)
-    nbr = geom.nbr_fwd if kvol > 1 else None
+    nbr = geom.nbr_fwd if ent.qw.shape[0] > 1 else None
     return nv.igemm_fwd_affine_fp8(qin, ent.qw, nbr, ent.colscale, ent.shift, relu, geom.n_out_dev, geom.n_out)
 
 
 def conv_folded(feats, ent, geom, residual=None, relu=True):
-    """relu(conv(feats; w_folded) + shift + residual) of a folded pair in one launch, on the kernel that serves the shape; ent =
-    (w_folded, shift, w_packed or None).  -> None where no kernel has the epilogue: a residual (a block's conv2) on a level the halo and the
-    direct-operand kernels do not serve - the LDS-DMA kernels take a shift OR an addend; the caller then runs conv + u3d_bn_apply."""
-    w_folded, shift, w_packed = ent
-    kvol, cout, cin = w_folded.shape
-    if torch.is_grad_enabled() and (feats.requires_grad or (residual is not None and residual.requires_grad)):
-        raise RuntimeError("a folded conv + BatchNorm pair is an inference path: it records no autograd node")
-    if feats.dtype != torch.bfloat16 or not feats.is_cuda:
-        raise RuntimeError(f"a folded conv + BatchNorm pair needs bf16 device rows, got {feats.dtype} on {feats.device}")
-    if feats.shape[1] != cin:
-        raise ValueError(f"folded conv: input has {feats.shape[1]} channels, folded weight expects {cin}")
-    if residual is not None and not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == (geom.n_out, cout)):
-        raise ValueError("folded conv: the residual must be bf16 rows of the output's shape")
-    halo = _halo_of(geom, kvol, cin, cout) if w_packed is not None else None
+    """relu(conv(feats; w_folded) + shift + residual) of a FoldedPair on its route's kernel (the table in its docstring).  -> None
+    where no kernel has the epilogue: the caller then runs conv + u3d_bn_apply."""
+    if ent.route == "fp8" and not ent.calibrating:
+        return conv_affine_fp8(feats, ent, geom, relu)
+    _inference_input("a folded conv + BatchNorm pair", feats, ent.w_folded, geom, residual)
+    kvol, cout, cin = ent.w_folded.shape
+    halo = _halo_of(geom, kvol, cin, cout) if ent.route == "halo" else None
+    if residual is not None and halo is None and ent.route != "direct":
+        return None
+    feats, add = feats.contiguous(), None if residual is None else residual.contiguous()
+    nv.CALL_KIND = geom.kind
     if halo is not None:
-        nv.CALL_KIND = geom.kind
-        return nv.subm_halo_conv_affine(feats.contiguous(), w_packed, halo, shift, relu, None if residual is None else residual.contiguous())
-    if nv.direct_serves(cin, cout, kvol) and geom.nbr_fwd is not None:
-        nv.CALL_KIND = geom.kind
-        return nv.igemm_direct_affine(feats.contiguous(), w_folded, geom.nbr_fwd, shift, relu, geom.n_out_dev, geom.n_out,
-                                      None if residual is None else residual.contiguous())
-    if residual is None:
-        return conv_affine(feats, w_folded, shift, geom, relu)
-    return None
+        return nv.subm_halo_conv_affine(feats, ent.w_packed, halo, ent.shift, relu, add)
+    if ent.route == "direct":
+        return nv.igemm_direct_affine(feats, ent.w_folded, geom.nbr_fwd, ent.shift, relu, geom.n_out_dev, geom.n_out, add)
+    if ent.route == "fp8":
+        nv.absmax_rows(feats, geom.n_in_dev, ent.slot)      # calibration: the bf16 folded forward + this layer's input range
+    return nv.igemm_fwd_affine(feats, ent.w_folded, geom.nbr_fwd if kvol > 1 else None, ent.shift, relu, geom.n_out_dev, geom.n_out)
 
 
 def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dhwio", post_add=None, res_take=None, res_give=None, fan_token=None):
@@ -636,19 +659,10 @@ def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dh
     if _FOLD[0] is not None:
         ent = _FOLD[0].get(id(bn))
         if ent is not None:
-            if isinstance(ent, Fp8Entry):
-                if bn.training or residual is not None or post_add is not None:
-                    raise RuntimeError("an fp8 conv + BatchNorm pair was called in training mode, or with a residual / level sum")
-                if not ent.calibrating:
-                    return conv_affine_fp8(feats, ent, geom, relu)
-                nv.absmax_rows(feats.contiguous(), geom.n_in_dev, ent.slot)     # calibration: the bf16 folded forward + this layer's input range
-                return conv_affine(feats, ent.w_folded, ent.shift, geom, relu)
-            if len(ent) == 2:                   # (w_folded, shift): the default fold - the LDS-DMA affine kernel or an error
-                if bn.training or residual is not None or post_add is not None:
-                    raise RuntimeError("a folded conv + BatchNorm pair was called in training mode, or with a residual / level sum")
-                return conv_affine(feats, ent[0], ent[1], geom, relu)
-            if bn.training or post_add is not None:     # (w_folded, shift, w_packed or None): InferenceModel(sparse_levels=True)
-                raise RuntimeError("a folded conv + BatchNorm pair of a sparse level was called in training mode, or with a level sum")
+            if bn.training or post_add is not None or (residual is not None and not ent.sparse_level):
+                what = "an fp8 conv + BatchNorm pair" if ent.route == "fp8" else "a folded conv + BatchNorm pair"
+                raise RuntimeError(f"{what} of a sparse level was called in training mode, or with a level sum" if ent.sparse_level else
+                                   f"{what} was called in training mode, or with a residual / level sum")
             y = conv_folded(feats, ent, geom, residual, relu)
             if y is not None:
                 return y
