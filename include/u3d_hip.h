@@ -60,7 +60,7 @@ typedef struct u3d_bitgrid {
                            voxels instead of out-of-bounds gathers; 0: unlimited */
 } u3d_bitgrid;
 
-int64_t u3d_bitgrid_nwords(int32_t batch, int32_t dz, int32_t dy, int32_t dx);
+/* number of 64-bit words of a lattice: layout 0 batch * ceil(dz/4) * ceil(dy/4) * ceil(dx/4), layout 1 ceil(batch*dz*dy*dx / 64) */
 int64_t u3d_bitgrid_nwords_layout(int32_t batch, int32_t dz, int32_t dy, int32_t dx, int32_t layout);
 
 /* words must be zeroed by the caller (hipMemsetAsync) before marking. coors: int32 [n,4] (b,z,y,x);
@@ -347,57 +347,54 @@ int32_t u3d_split3_job_blocks(int32_t k, int32_t a, int32_t b);
 int32_t u3d_split3_weights_batch(const void* jobs, int32_t njobs, int32_t total_blocks, u3d_stream s);
 /* dst bf16 [2 * n_cap][c]: rows [0, n) = bf16(x), rows [n_cap, n_cap + n) = bf16(x - hi), n = min(*n_dev, n_cap); c % 4 == 0. */
 int32_t u3d_split_rows_f32(const float* x, const int32_t* n_dev, int32_t n_cap, int32_t c, void* dst, u3d_stream s);
-/* Output-stationary path of the 64 -> 64 channel, 27-offset submanifold convs (the stride-4 stage's SparseBasicBlocks, ref:
- * sparse_encoder_hd.py:106-138): rows are numbered in 4x4x4-block-major order, so the 27 x 128 table entries of a 128-row tile name
- * only a few hundred DISTINCT rows.  u3d_subm_halo_build (once per level and step) leaves, per tile, the sorted distinct rows
- * tile_rows int32 [tiles][3460] (slot 0 = the all-zero row), their number tile_cnt int32 [tiles] and the table rewritten as 16-bit
- * slots loc u16 [tiles][27][128] (within a (tile, offset): entry (r % 16) * 8 + r / 16 for row r).  u3d_subm_halo_sizes gives the
- * element counts for n_cap rows (the build returns U3D_ERR_UNSUPPORTED above 869 k rows: its per-tile row bitmap lives in LDS).
- * u3d_subm_halo_conv64_bf16 then computes what u3d_igemm_fwd_bf16 (transpose_w = 1; plain,
- * with an addend, with statistics) computes from the table: in/out/addend bf16 [n][64]; w_packed =
- * u3d_subm_halo_wpack of the n-major bf16 weights [27][64][64] (MFMA fragment order, same size); krev != 0 reads the offsets reversed (the transposed table of a SubM layer: input gradients, pass [K][Cin][Cout]);
- * addend nullable; stats nullable f64 [tiles][2][64] (128 rows per partial, as u3d_bn_finalize_partials takes them). */
+/* Output-stationary path of the 27-offset submanifold convs at 64 -> 64 channels (the stride-4 stage's SparseBasicBlocks, ref:
+ * sparse_encoder_hd.py:106-138) and of the <= 27-offset convs at 128 -> 128 (the stride-8 stage; with 9 offsets the stride-1 (1,3,3)
+ * convs of the dense stack, SECOND3D's 128-channel branch, ref: second_3d.py:52-76, whose tables are static).  Rows are numbered in
+ * 4x4x4-block-major order, so the 27 x 128 table entries of a 128-row tile name only a few hundred DISTINCT rows.
+ * Tables.  u3d_subm_halo_build (once per level and step) leaves, per tile, the sorted distinct rows tile_rows int32 [tiles][3460]
+ * (slot 0 = the all-zero row), their number tile_cnt int32 [tiles] and the table rewritten as 16-bit slots loc u16 [tiles][27][128]
+ * (within a (tile, offset): entry (r % 16) * 8 + r / 16 for row r; 27 slots per tile whatever kvol).  They do not depend on the
+ * channel count.  u3d_subm_halo_sizes gives the element counts for n_cap rows (the build returns U3D_ERR_UNSUPPORTED above 869 k
+ * rows: its per-tile row bitmap lives in LDS).  u3d_halo_tables names them for the entries that read them.
+ * Weights.  u3d_subm_halo_wpack: n-major bf16 [kvol][c][c] -> MFMA fragment order, same size; _batched packs n weights in one launch
+ * from device arrays of n source / destination pointers (the per-step shadow refresh packs every SubM weight of a width, forward and
+ * transposed, at once).
+ * Shapes (every entry with a c): c == 64 with kvol == 27, or c == 128 with 1 <= kvol <= 27; anything else U3D_ERR_UNSUPPORTED.
+ * u3d_subm_halo_conv_bf16: in / out / addend bf16 [n][c], addend nullable, stats nullable f64 [tiles][2][c] (128 rows per partial,
+ * as u3d_bn_finalize_partials takes them).
+ *   shift == NULL: what u3d_igemm_fwd_bf16 (transpose_w = 1; plain, with an addend, with statistics) computes from the table.
+ *     krev != 0 reads the offsets reversed (the transposed table of a SubM layer, or of a stride-1 "same" conv on a lattice: input
+ *     gradients, pass [K][Cin][Cout]).  relu must be 0.
+ *   shift != NULL (f32 [c], 16-byte aligned): the forward with an eval-mode BatchNorm folded in (the inference path).  w_packed = the
+ *     pack of the FOLDED weights (u3d_bn_fold_batched), out = bf16_rne(act(conv + shift[col] + addend[m][col])) - f32 until the one
+ *     rounding, in that order; the addend is the residual block's identity; relu != 0 applies max(., 0).  Rows at or past *n_dev are
+ *     left untouched.  Forward only and without statistics: krev != 0 or stats != NULL is U3D_ERR_ARG.  With a zero shift and relu == 0
+ *     the result equals the shift == NULL call on the same packed weights.  The epilogue is a compile-time variant of the kernels:
+ *     shift == NULL runs the code it ran without it.
+ * u3d_subm_halo_wgrad64_bf16: weight gradient of the 64 -> 64 layers from the same tables (kvol == 27): dw f32 [27][64][64]
+ * (spconv-1.x layout) = sum over rows m of x[nbr_k(m)]^T dy[m]; x / dy bf16 [n][64].  Persistent workgroups, both MFMA operands by
+ * transpose reads out of the staged distinct rows / the dy tile, offsets split over four workgroup groups, one f32 partial per
+ * workgroup summed in a fixed order (deterministic).  workspace: u3d_subm_halo_wgrad64_workspace() bytes.  Replaces
+ * u3d_igemm_wgrad_bf16 for this shape (ref: the weight half of spconv's indice_conv_backward for sparse_encoder_hd.py:106-138).
+ * max_slots (conv and wgrad): 0 = the stage buffer's capacity; a lower value only forces the fall-back paths for tiles with more
+ * distinct rows (test hook). */
+typedef struct u3d_halo_tables {      /* HOST structure, read during the call */
+  const int32_t* tile_rows;
+  const uint16_t* loc;
+  const int32_t* tile_cnt;
+  const int32_t* n_dev;
+  int32_t n_cap, kvol;
+} u3d_halo_tables;
 int32_t u3d_subm_halo_sizes(int32_t n_cap, int64_t* tile_rows_elems, int64_t* loc_elems, int32_t* tiles);
 int32_t u3d_subm_halo_build(const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t* tile_rows,
                             uint16_t* loc, int32_t* tile_cnt, int32_t kvol, u3d_stream s);
-int32_t u3d_subm_halo_wpack(const void* w_nmajor, void* w_packed, u3d_stream s);
-/* n weights in one launch: device arrays of n source / destination pointers (the per-step shadow refresh packs every 64 -> 64 SubM weight,
- * forward and transposed, at once). */
-int32_t u3d_subm_halo_wpack_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, u3d_stream s);
-int32_t u3d_subm_halo_conv64_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                  const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
-                                  const void* addend, void* out, double* stats, int32_t max_slots, u3d_stream s);
-/* The same for 128 -> 128 channels (the stride-8 stage): in/out/addend bf16 [n][128], w_packed = u3d_subm_halo_wpack128 of the n-major
- * bf16 weights [kvol][128][128]; stats f64 [tiles][2][128].  Tables from u3d_subm_halo_build (they do not depend on the channel count).
- * kvol <= 27 offsets (the build takes the same kvol; loc keeps 27 slots per tile): 27 for the sparse SubM levels, 9 for the stride-1
- * (1,3,3) convs of the dense stack (SECOND3D's 128-channel branch, ref: second_3d.py:52-76), whose tables are static - the transposed
- * table of a stride-1 "same" conv on a lattice is the forward one reversed, exactly as for SubM. */
-int32_t u3d_subm_halo_wpack128(const void* w_nmajor, void* w_packed, int32_t kvol, u3d_stream s);
-int32_t u3d_subm_halo_wpack128_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, int32_t kvol, u3d_stream s);
-int32_t u3d_subm_halo_conv128_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                   const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
-                                   const void* addend, void* out, double* stats, int32_t max_slots, int32_t kvol, u3d_stream s);
-/* The forward of both with an eval-mode BatchNorm folded in (the inference path): w_packed = u3d_subm_halo_wpack / _wpack128 of the
- * FOLDED n-major weights (u3d_bn_fold_batched), out = bf16_rne(act(conv + shift[col] + addend[m][col])) - f32 until the one
- * rounding, in that order; shift f32 [64] / [128] (required, 16-byte aligned), addend nullable (the residual block's identity),
- * relu != 0 applies max(., 0).  Rows at or past *n_dev are left untouched.  With shift == 0 and relu == 0 the result equals
- * u3d_subm_halo_conv64_bf16 / _conv128_bf16 (krev = 0) on the same packed weights.  The epilogue is a compile-time variant of the
- * kernels: the entries above run the code they ran without it. */
-int32_t u3d_subm_halo_conv64_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                         const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend, void* out,
-                                         const float* shift, int32_t relu, int32_t max_slots, u3d_stream s);
-int32_t u3d_subm_halo_conv128_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                          const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend, void* out,
-                                          const float* shift, int32_t relu, int32_t max_slots, int32_t kvol, u3d_stream s);
-/* Weight gradient of the same 64 -> 64 SubM layers from the same tables: dw f32 [27][64][64] (spconv-1.x layout) =
- * sum over rows m of x[nbr_k(m)]^T dy[m]; x / dy bf16 [n][64].  Persistent workgroups, both MFMA operands by transpose reads out of
- * the staged distinct rows / the dy tile, offsets split over four workgroup groups, one f32 partial per workgroup summed in a fixed
- * order (deterministic).  workspace: u3d_subm_halo_wgrad64_workspace() bytes.  max_slots (both functions): 0 = the stage buffer's
- * capacity; a lower value only forces the fall-back paths for tiles with more distinct rows (test hook).  Replaces u3d_igemm_wgrad_bf16 for this shape (ref: the
- * weight half of spconv's indice_conv_backward for sparse_encoder_hd.py:106-138). */
+int32_t u3d_subm_halo_wpack(const void* w_nmajor, void* w_packed, int32_t c, int32_t kvol, u3d_stream s);
+int32_t u3d_subm_halo_wpack_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, int32_t c, int32_t kvol, u3d_stream s);
+int32_t u3d_subm_halo_conv_bf16(const void* in, const void* w_packed, const u3d_halo_tables* t, int32_t c, int32_t krev,
+                                const void* addend, void* out, double* stats, const float* shift, int32_t relu,
+                                int32_t max_slots, u3d_stream s);
 int64_t u3d_subm_halo_wgrad64_workspace(void);
-int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, const int32_t* tile_rows, const uint16_t* loc,
-                                   const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, float* dw, void* workspace,
+int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, const u3d_halo_tables* t, float* dw, void* workspace,
                                    int64_t workspace_bytes, int32_t max_slots, u3d_stream s);
 int64_t u3d_igemm_wgrad_bf16_workspace(int32_t n_out_cap, int32_t cin, int32_t cout, int32_t kvol);
 /* out_layout 0: dw [K][Cin][Cout] (spconv-1.x / this library's layout); 1: dw [Cout][Cin][K] (nn.Conv3d's [Cout,Cin,kD,kH,kW]);
@@ -477,9 +474,16 @@ int32_t u3d_bn_finalize_partials(const double* partial, int32_t nblocks, int32_t
  * rows tap-major; their BatchNorm writes the lattice order directly instead of a separate row gather.  Requires no residual /
  * dres and C % 8 == 0 (bf16) or C % 4 == 0 (f32).
  * post_add (nullable, u3d_bn_apply): a tensor of y's shape and row order added AFTER the activation, y = act(..) + post_add - the
- * running sum of the FPN's upsampled levels (ref: second3d_fpn.py:131-134) without a separate add pass. */
+ * running sum of the FPN's upsampled levels (ref: second3d_fpn.py:131-134) without a separate add pass.
+ * planes (nullable; u3d_bn_apply and u3d_bn_bwd_apply, F32 rows): the pass ALSO leaves its output (y / dx) as the hi / lo bf16 planes
+ * of a split-bf16 product (planes: bf16 [2 * n_cap][C] in the output's row order, rows n .. n_cap of both planes zero - exactly what
+ * u3d_split_rows_f32 of the output would hold): the BatchNorm of the fp32 modules (ref: sparse_encoder_hd.py:62-64, second_3d.py:52-76
+ * - kept in fp32 by the reference) hands its consumer convolution the planes without a further pass over the tensor; the backward
+ * hands the producer convolution the planes of dy.  With planes, U3D_ERR_UNSUPPORTED and nothing launched when the dtype is not
+ * U3D_F32, C does not fit the vector kernels (C % 4, (C / 4) | 256), a column parameter is not 16-byte aligned, or row_map comes with
+ * a residual / dres: run the plain pass + the split. */
 int32_t u3d_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma,
-                     const float* beta, const void* residual, int32_t relu, void* y,
+                     const float* beta, const void* residual, int32_t relu, void* y, void* planes,
                      const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, const int32_t* row_map, const void* post_add,
                      u3d_stream s);
 /* backward: given dy (grad wrt y), y (for relu mask), x: sums f64 [2*C] = (sum g, sum g*xhat) where
@@ -492,19 +496,8 @@ int32_t u3d_bn_bwd_stats(const void* dy, const void* y, const void* x, const flo
                          const int32_t* row_map, float* sums_f32, u3d_stream s);
 /* dx = gamma*invstd*( g - sum_g/n - xhat*sum_gx/n ); dres = g (optional, may be NULL).  y NULL: as above (beta required). */
 int32_t u3d_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* invstd,
-                         const float* gamma, const float* beta, const double* sums, int32_t relu, void* dx, void* dres,
+                         const float* gamma, const float* beta, const double* sums, int32_t relu, void* dx, void* dres, void* planes,
                          const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, const int32_t* row_map, u3d_stream s);
-/* The same two passes over F32 rows that ALSO leave their output as the hi / lo bf16 planes of a split-bf16 product (planes: bf16
- * [2 * n_cap][C] in the output's row order, rows n .. n_cap of both planes zero - exactly what u3d_split_rows_f32 of the output would
- * hold): the BatchNorm of the fp32 modules (ref: sparse_encoder_hd.py:62-64, second_3d.py:52-76 - kept in fp32 by the reference)
- * hands its consumer convolution the planes without a further pass over the tensor; the backward hands the producer convolution the
- * planes of dy.  U3D_ERR_UNSUPPORTED when C does not fit the vector kernels (C % 4, (C / 4) | 256): run the plain pass + the split. */
-int32_t u3d_bn_apply_planes(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                            const float* residual, int32_t relu, float* y, void* planes, const int32_t* n_dev, int32_t n_cap,
-                            int32_t c, const int32_t* row_map, const float* post_add, u3d_stream s);
-int32_t u3d_bn_bwd_apply_planes(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
-                                const float* gamma, const float* beta, const double* sums, int32_t relu, float* dx, float* dres,
-                                void* planes, const int32_t* n_dev, int32_t n_cap, int32_t c, const int32_t* row_map, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
  * SparseConvTensor.dense() (ref: sparse_encoder_hd.py:133): rows -> channels-last dense volume
@@ -661,13 +654,11 @@ int32_t u3d_det_tail_pp(const float* prob, const float* fused, const float* boxe
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad
- * for stride > 1 (ref: models/backbones/second_3d.py:52-76 first conv of each block). */
-int32_t u3d_tap_gather_sum(const void* p, const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t c,
-                           int32_t kvol, int32_t dtype, void* out, u3d_stream s);
-/* ... + addend (nullable; out's shape and dtype): the input gradients the other branches of a shared input already summed
+ * for stride > 1 (ref: models/backbones/second_3d.py:52-76 first conv of each block).
+ * addend (nullable; out's shape and dtype) is added to the sum: the input gradients the other branches of a shared input already summed
  * (SECOND3D with is_cascade=False, ref: second_3d.py:89-114) - autograd's separate element-wise add over the full tensor disappears. */
-int32_t u3d_tap_gather_sum_add(const void* p, const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t c,
-                               int32_t kvol, int32_t dtype, const void* addend, void* out, u3d_stream s);
+int32_t u3d_tap_gather_sum(const void* p, const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t c,
+                           int32_t kvol, int32_t dtype, const void* addend, void* out, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm over the last dimension of a row matrix [n, C] (C <= 1024) with optional fused ReLU; input and output dtypes are
@@ -740,17 +731,15 @@ int32_t u3d_sine_embed_bwd(const float* logits, const float* dim_t, const void* 
  * bias-corrected moments).  state: 16 floats of device memory, zero-initialised by the caller: [0] step count (incremented here),
  * [1] clip coefficient, [2] 1-beta1^t, [3] 1-beta2^t, [4] ||g||, [5..10] lr, beta1, beta2, eps, weight_decay, max_norm (<= 0: no
  * clipping).  The kernels read the hyper-parameters from the state vector at run time: u3d_adamw_set_hyper (a one-thread launch,
- * issued between hipGraph replays) makes a captured u3d_adamw_step_state follow a learning-rate / momentum schedule (ref: the
+ * issued between hipGraph replays) makes a captured u3d_adamw_step_hold follow a learning-rate / momentum schedule (ref: the
  * `step` lr policy of uni3detr_sunrgbd.py:236-241 and the `cyclic` lr + momentum policies of the KITTI / nuScenes configs).
  * skip (optional): uint8 per 64-element chunk, 1 = parameter chunk received no gradient and is left untouched (torch.optim.AdamW
- * skips parameters whose .grad is None).  u3d_adamw_step = set_hyper + step_state with host scalars.  All pointers 16-byte aligned.
+ * skips parameters whose .grad is None).  u3d_adamw_step = set_hyper + step_hold (hold = NULL) with host scalars.  All pointers 16-byte aligned.
  * ---------------------------------------------------------------------------------------------- */
 int64_t u3d_adamw_workspace(int64_t n);
 int32_t u3d_adamw_set_hyper(float* state, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                             u3d_stream s);
-int32_t u3d_adamw_step_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
-                             const uint8_t* skip, void* workspace, int64_t workspace_bytes, u3d_stream s);
-/* u3d_adamw_step_state with a HOLD flag: hold (nullable) -> one device float; > 0 makes this step a no-op (parameters, moments and
+/* The step from the state vector.  HOLD flag: hold (nullable) -> one device float; > 0 makes this step a no-op (parameters, moments and
  * the step count untouched; state[11] = 1, state[12] += 1 = held steps so far).  Static-shape training (hipGraph replay over
  * capacity-sized sparse levels) uses it so that a batch that overflowed a level - on ANY rank: the flag rides in the job's
  * positive-count all-reduce - never trains on truncated levels; the host reads state[12] now and then and re-captures. */
@@ -905,7 +894,7 @@ int32_t u3d_kitti_reduce(const int32_t* st_tp, const int32_t* st_fp, const int32
  * u3d_nusc_rank_keys: key int64 [n] / idx int32 [n]: key[n-1-i] = descending-orderable score of row i, idx[n-1-i] = i.
  * u3d_nusc_match: one wave per segment (class * n_sample + sample): rank int32 [n] = prediction rows in rank order, mperm int32 [n] =
  *   rank positions grouped by segment, mseg [n_seg+1]; gord = GT rows grouped by segment, gseg [n_seg+1]; max_gt = the largest GT
- *   segment (U3D_ERR_UNSUPPORTED above 2048; dynamic LDS u3d_nusc_match_lds(max_gt)) -> tp int8 [4][n], match int32 [n] (GT row at
+ *   segment (U3D_ERR_UNSUPPORTED above 2048; dynamic LDS 16 * max_gt bytes: the segment's GT xy as f64) -> tp int8 [4][n], match int32 [n] (GT row at
  *   tp_th, -1 = none), by rank position.
  * u3d_nusc_accumulate: one workgroup per (class, threshold).  cseg [n_cls+1] = class segments of the rank order, npos [n_cls],
  *   gcoff [n_cls] = exclusive scan of npos, rec_interp f64 [101], period f64 [n_cls]; ws of u3d_nusc_accumulate_workspace(n, n_gt)
@@ -920,7 +909,6 @@ int32_t u3d_nusc_filter(const double* rec, const int32_t* off, int32_t n_sample,
                         u3d_stream s);
 int32_t u3d_nusc_compact(const double* rec, const int32_t* valid, const int32_t* pos, int32_t n, double* out, u3d_stream s);
 int32_t u3d_nusc_rank_keys(const double* rec, int32_t n, int64_t* key, int32_t* idx, u3d_stream s);
-int64_t u3d_nusc_match_lds(int32_t max_gt);
 int32_t u3d_nusc_match(const double* pred, const int32_t* rank, const int32_t* mperm, const int32_t* mseg, int32_t n_seg, int32_t n,
                        const double* gt, const int32_t* gord, const int32_t* gseg, int32_t max_gt, const double* ths, int32_t tp_th, int8_t* tp,
                        int32_t* match, u3d_stream s);
@@ -1008,18 +996,21 @@ enum {
   U3D_DG_QS2, U3D_DG_QS1, U3D_DG_RAW, U3D_DG_RPH2, U3D_DG_RPH1, U3D_DG_LNP, U3D_DG_DU1, U3D_DG_DPOSA, U3D_DG_SINE,
   U3D_DG_COUNT
 };
-int32_t u3d_decoder_layer_slots(int32_t m, int32_t ncls, int32_t code, int64_t* save_off, int64_t* grad_off);      /* = _dt(.., U3D_BF16, ..) */
-int32_t u3d_decoder_layer_slots_dt(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off);
-int32_t u3d_decoder_layer_blocks(int32_t m);   /* workgroups of the row-chain kernels = rows of every U3D_DG_LNP partial matrix (bf16) */
-int32_t u3d_decoder_layer_blocks_dt(int32_t m, int32_t dtype);   /* rows per workgroup: 32 (U3D_BF16) / 16 (U3D_F32) */
+int32_t u3d_decoder_layer_slots(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off);
+/* workgroups of the row-chain kernels = rows of every U3D_DG_LNP partial matrix; rows per workgroup: 32 (U3D_BF16) / 16 (U3D_F32) */
+int32_t u3d_decoder_layer_blocks(int32_t m, int32_t dtype);
 /* ROW PADDING: every row matrix this layer WRITES (x_out, xc_out, reg_out, cls_out, iou_out, dx, dref and all slots) must hold
- * u3d_decoder_layer_blocks_dt(m, dtype) * (32 | 16) rows; rows >= m receive values nobody reads.  Matrices it only READS (x, xc, ref, dx_out, dreg,
+ * u3d_decoder_layer_blocks(m, dtype) * (32 | 16) rows; rows >= m receive values nobody reads.  Matrices it only READS (x, xc, ref, dx_out, dreg,
  * dcls, diou) have m rows.  (The row kernels contain no branch on the row index: see csrc/decoder_common.h.) */
 /* x f32 [m,256] layer input, xc its bf16 copy, ref f32 [m,3] logits, value bf16 rows, rng: device uint64 seed.
- * Outputs: x_out f32 / xc_out bf16 [m,256], reg_out f32 [m,code], cls_out f32 [m,ncls], iou_out f32 [m]; save: the slot buffer. */
+ * Outputs: x_out f32 / xc_out bf16 [m,256], reg_out f32 [m,code], cls_out f32 [m,ncls], iou_out f32 [m]; save: the slot buffer.
+ * row_waves (both calls): the wave count of the row-chain launches = 8 (bf16 only: two waves per SIMD, the default of bf16), 4 (one
+ * wave per SIMD: the f32 kernels, and the bf16 comparison partner), 0 = the element type's default.  Results are bit-identical for
+ * either count; forward and backward of one layer may use different ones. */
 int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
                               const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
-                              float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, u3d_stream s);
+                              float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, int32_t row_waves,
+                              u3d_stream s);
 /* Gradients in: dx_out f32 [m,256] (NULL = zero), dreg f32 [m,code], dcls f32 [m,ncls], diou f32 [m].
  * Out: dx f32 [m,256] (w.r.t. the layer input x), vrec: the value-gradient records (u3d_value_records_bytes(m) bytes: d(sample) f32
  * [m][256], trilinear corner cells int32 [m][8] (-1 = outside the volume), corner weights f32 [m][8]) that u3d_value_scatter adds into
@@ -1027,18 +1018,7 @@ int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_d
 int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
                               const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
                               const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                              void* vrec, float* dref, void* grad, int64_t grad_bytes, u3d_stream s);
-/* The same two calls with the wave count of the row-chain launches as an argument: row_waves = 8 (bf16 only: two waves per SIMD, the
- * default of bf16), 4 (one wave per SIMD: the f32 kernels, and the bf16 comparison partner), 0 = the element type's default.  Results
- * are bit-identical for either count; forward and backward of one layer may use different ones. */
-int32_t u3d_decoder_layer_fwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                 const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
-                                 float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, int32_t row_waves,
-                                 u3d_stream s);
-int32_t u3d_decoder_layer_bwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                 const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
-                                 const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                                 void* vrec, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s);
+                              void* vrec, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s);
 int64_t u3d_value_records_bytes(int32_t m);
 /* Adds the records of one u3d_decoder_layer_bwd call into dvalue [n_cells][256] (f32, or bf16 when dvalue_bf16): per cell the sum over
  * its (row, corner) entries in ascending entry order, in f32, added once - bitwise reproducible.  work: u3d_value_scatter_workspace
@@ -1047,28 +1027,23 @@ int64_t u3d_value_scatter_workspace(int32_t n_cells);
 int32_t u3d_value_scatter(const void* records, int32_t m, int32_t n_cells, void* dvalue, int32_t dvalue_bf16, void* work,
                           int64_t work_bytes, u3d_stream s);
 /* Self-attention over groups on its own (the middle launch of the layer): q,k rows of qk [m,512] (q | k), v [m,256], 8 heads x 32;
- * o bf16 [m,256], lse f32 [m,8].  Backward: dqk [m,512], dv [m,256] bf16. */
+ * o bf16 [m,256], lse f32 [m,8].  Backward: dqk [m,512], dv [m,256] bf16.  dtype U3D_BF16 | U3D_F32 (the same kernels on either
+ * element type; U3D_F32: all matrices then f32, exact-f32 MFMA). */
 int32_t u3d_mha_fwd(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng, void* o,
-                    float* lse, u3d_stream s);
+                    float* lse, int32_t dtype, u3d_stream s);
 int32_t u3d_mha_bwd(const void* qk, const void* v, const void* o, const void* d_o, const float* lse, int32_t m, int32_t nq,
-                    float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, u3d_stream s);
-/* the same kernels on either element type (dtype U3D_BF16 | U3D_F32: all matrices then f32, exact-f32 MFMA) */
-int32_t u3d_mha_fwd_dt(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng, void* o,
-                       float* lse, int32_t dtype, u3d_stream s);
-int32_t u3d_mha_bwd_dt(const void* qk, const void* v, const void* o, const void* d_o, const float* lse, int32_t m, int32_t nq,
-                       float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, int32_t dtype, u3d_stream s);
+                    float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, int32_t dtype, u3d_stream s);
 /* Refresh of the weight copies the fused layer reads: for each descriptor dst = bf16(src [n][k]) (rows n >= N zero up to n_pad) and
  * dst_t = its transpose [k][n_pad_t], both stored in MFMA FRAGMENT ORDER: block (16-row tile, 32-element k-step) = 64 x 16 bytes in
  * lane order (lane = kq * 16 + row, 8 consecutive k each), blocks of a tile consecutive - one wave load of a weight fragment is
- * 1 KiB contiguous.  descs in device memory; one launch for all linears of all layers. */
+ * 1 KiB contiguous.  descs in device memory; one launch for all linears of all layers.  dtype U3D_F32: the same copies in f32
+ * (zero-padded rows / transposes of the f32 masters) for the parity-mode instantiation. */
 typedef struct u3d_wpack_desc {
   const float* src; void* dst; void* dst_t;
   int32_t n, k, n_pad, n_pad_t;   /* n_pad % 16 == 0, k % 32 == 0 (bf16) / % 16 (f32); packed transposes: k % 16 == 0, n_pad_t % 32 == 0 */
   int32_t t_plain;                /* 1: dst_t stays row-major [k][n_pad_t] (the <= 32-column final layers); 0: fragment order */
   int32_t reserved;
 } u3d_wpack_desc;
-int32_t u3d_wpack_bf16(const u3d_wpack_desc* descs_dev, int32_t count, int32_t max_elems, u3d_stream s);
-/* dtype U3D_F32: the same copies in f32 (zero-padded rows / transposes of the f32 masters) for the parity-mode instantiation */
 int32_t u3d_wpack(const u3d_wpack_desc* descs_dev, int32_t count, int32_t max_elems, int32_t dtype, u3d_stream s);
 /* keep-mask of the layer's dropout sites as bytes (testing aid): site 0..3 = out_proj, output_proj, FFN hidden, FFN out over
  * [m, 256 | 512], linear element index (cols = 0); site 4 = attention weights over [m*8, nq] (row = (group*8 + head)*nq + query):

@@ -1,5 +1,7 @@
 """uni3detr_amd/abi.py: the reader of include/u3d_hip.h on a small header with literal expected output, each of its refusals, the real
-header against the built library and the bindings native.lib() sets, and literal pins of signatures, constants and struct sizes."""
+header against the built library and the bindings native.lib() sets, literal pins of signatures, constants and struct sizes - and the
+one-entry-per-operation rule: every export is named by the package, the retired variant / wrapper names are gone, and the merged
+entries answer their argument and shape checks before any launch (no GPU involved)."""
 import ctypes as C
 import os
 import re
@@ -159,12 +161,130 @@ def test_struct_size_pins():
     """The sizes of the hand-written classes these layouts replaced: the derived layouts are the ones the kernels read."""
     s = abi.load().structs
     assert sorted(s) == sorted(["u3d_bitgrid", "u3d_declayer_params", "u3d_declayer_dims", "u3d_wpack_desc", "U3dSplitRowsJobs",
-                                "u3d_permute_desc", "u3d_fwd_plan_info", "u3d_bn_fold_job", "u3d_bn_fold_fp8_job", "u3d_split3_job"])
+                                "u3d_permute_desc", "u3d_fwd_plan_info", "u3d_bn_fold_job", "u3d_bn_fold_fp8_job", "u3d_split3_job",
+                                "u3d_halo_tables"])
     for cls, size in ((nv.BitGridStruct, 40), (nv.DecLayerParams, 680), (nv.DecLayerDims, 68), (nv.WPackDesc, 48),
                       (nv._SplitRowsJobs, 1032), (nv.FwdPlanInfo, 28), (nv.BnFoldJob, 104), (nv.BnFoldFp8Job, 112),
-                      (nv.Split3Set._Job, 56)):
+                      (nv.Split3Set._Job, 56), (nv.HaloTables, 40)):
         assert C.sizeof(cls) == size and issubclass(cls, C.Structure), cls
     assert np.dtype(nv.PERMUTE_DESC_DTYPE).itemsize == 56
     assert [n for n, _ in nv.BitGridStruct._fields_] == ["words", "prefix", "batch", "dz", "dy", "dx", "layout", "row_capacity"]
+    assert [n for n, _ in nv.HaloTables._fields_] == ["tile_rows", "loc", "tile_cnt", "n_dev", "n_cap", "kvol"]
     assert [n for n, _ in nv.BnFoldJob._fields_] == ["w", "gamma", "beta", "mean", "var", "w_folded", "shift", "sk", "sa", "sb", "eps",
                                                      "kvol", "cout", "cin", "scale_only", "first_block"]
+
+
+# The suffix variants, wrapper exports and orphans that one entry per operation replaced (HISTORY.md).  The plain names of the
+# renamed long forms (u3d_mha_fwd, u3d_decoder_layer_slots, ...) live on with the long forms' signatures: test_merged_signatures.
+RETIRED = ("u3d_subm_halo_conv64_bf16", "u3d_subm_halo_conv128_bf16", "u3d_subm_halo_conv64_affine_bf16",
+           "u3d_subm_halo_conv128_affine_bf16", "u3d_subm_halo_wpack128", "u3d_subm_halo_wpack128_batched",
+           "u3d_bn_apply_planes", "u3d_bn_bwd_apply_planes", "u3d_mha_fwd_dt", "u3d_mha_bwd_dt", "u3d_decoder_layer_fwd_nw",
+           "u3d_decoder_layer_bwd_nw", "u3d_decoder_layer_slots_dt", "u3d_decoder_layer_blocks_dt", "u3d_wpack_bf16",
+           "u3d_adamw_step_state", "u3d_tap_gather_sum_add", "u3d_bitgrid_nwords", "u3d_nusc_match_lds")
+OK, ARG, UNSUPPORTED = 0, -1, -2
+
+
+def test_every_export_is_named_by_the_package():
+    pkg = os.path.dirname(os.path.abspath(nv.__file__))
+    text = "\n".join(open(os.path.join(d, f)).read() for d, _, fs in os.walk(pkg) for f in fs if f.endswith(".py"))
+    words = set(re.findall(r"\bu3d_[a-z0-9_]+\b", text))
+    assert not [n for n in nv.exported_symbols() if n not in words]
+
+
+def test_retired_names_are_gone():
+    declared = set(re.findall(r"\bu3d_[a-z0-9_]+\b", open(abi.HEADER).read()))
+    raw = C.CDLL(nv.LIB_PATH)
+    for name in RETIRED:
+        assert name not in declared and name not in nv.exported_symbols() and not hasattr(raw, name), name
+
+
+def test_merged_signatures():
+    p = abi.load().prototypes
+    assert p["u3d_subm_halo_conv_bf16"] == (I, [P, P, P, I, I, P, P, P, P, I, I, P])
+    assert p["u3d_subm_halo_wpack"] == (I, [P, P, I, I, P]) and p["u3d_subm_halo_wpack_batched"] == (I, [P, P, I, I, I, P])
+    assert p["u3d_subm_halo_wgrad64_bf16"] == (I, [P, P, P, P, P, L, I, P])
+    assert p["u3d_bn_apply"] == (I, [P] * 6 + [I, P, P, P, I, I, I, P, P, P])                   # planes after y
+    assert p["u3d_bn_bwd_apply"] == (I, [P] * 8 + [I, P, P, P, P, I, I, I, P, P])               # planes after dres
+    assert p["u3d_mha_fwd"][1][-2:] == [I, P] and p["u3d_mha_bwd"][1][-2:] == [I, P]            # dtype, stream
+    assert p["u3d_decoder_layer_fwd"][1][-3:] == [L, I, P] and p["u3d_decoder_layer_bwd"][1][-3:] == [L, I, P]      # .., row_waves, stream
+    assert p["u3d_decoder_layer_slots"] == (I, [I, I, I, I, P, P]) and p["u3d_decoder_layer_blocks"] == (I, [I, I])
+    assert p["u3d_tap_gather_sum"] == (I, [P, P, I, P, I, I, I, I, P, P, P])                    # addend before out
+
+
+class _Host:
+    """64-byte-aligned addresses inside one host buffer, standing in for device pointers the calls never dereference."""
+
+    def __init__(self, n=16):
+        self.buf = (C.c_char * (64 * (n + 1)))()
+        self.base = (C.addressof(self.buf) + 63) & ~63
+
+    def __getitem__(self, i):
+        return C.c_void_p(self.base + 64 * i)
+
+
+def _halo_tables(h, n_cap=256, kvol=27):
+    return nv.HaloTables(h[0].value, h[1].value, h[2].value, h[3].value, n_cap, kvol)
+
+
+@pytest.mark.parametrize("c, kvol, krev, stats, shift, relu, want", [
+    (96, 27, 0, False, False, 0, UNSUPPORTED),
+    (64, 9, 0, False, False, 0, UNSUPPORTED),
+    (64, 27, 0, True, True, 0, ARG),            # the affine epilogue reduces no statistics
+    (64, 27, 1, False, True, 0, ARG),           # ... and is forward only
+    (128, 9, 1, False, True, 1, ARG),
+    (64, 27, 0, False, False, 1, ARG),          # a ReLU needs the affine epilogue
+    (128, 28, 0, False, False, 0, ARG),         # more offsets than loc holds
+    (96, 27, 1, False, True, 0, ARG),           # argument checks come before shape checks
+])
+def test_halo_conv_return_codes(c, kvol, krev, stats, shift, relu, want):
+    h = _Host()
+    t = _halo_tables(h, kvol=kvol)
+    rc = nv.lib().u3d_subm_halo_conv_bf16(h[4], h[5], C.byref(t), c, krev, None, h[6], h[7] if stats else None, h[8] if shift else None,
+                                          relu, 0, None)
+    assert rc == want
+
+
+def test_halo_null_and_wpack_return_codes():
+    h = _Host()
+    lib = nv.lib()
+    assert lib.u3d_subm_halo_conv_bf16(h[4], h[5], None, 64, 0, None, h[6], None, None, 0, 0, None) == ARG
+    t = _halo_tables(h)
+    t.loc = None
+    assert lib.u3d_subm_halo_conv_bf16(h[4], h[5], C.byref(t), 64, 0, None, h[6], None, None, 0, 0, None) == ARG
+    assert lib.u3d_subm_halo_wpack(h[0], h[1], 64, 9, None) == UNSUPPORTED
+    assert lib.u3d_subm_halo_wpack(h[0], h[1], 32, 27, None) == UNSUPPORTED
+    assert lib.u3d_subm_halo_wpack(h[0], None, 64, 27, None) == ARG
+    assert lib.u3d_subm_halo_wpack_batched(h[0], h[1], 2, 64, 9, None) == UNSUPPORTED
+    assert lib.u3d_subm_halo_wpack_batched(h[0], h[1], 0, 128, 9, None) == OK       # nothing to pack: no launch
+    assert lib.u3d_subm_halo_wpack_batched(h[0], h[1], -1, 128, 9, None) == ARG
+    t9 = _halo_tables(h, kvol=9)
+    assert lib.u3d_subm_halo_wgrad64_bf16(h[4], h[5], C.byref(t9), h[6], h[7], 1 << 40, 0, None) == UNSUPPORTED
+
+
+@pytest.mark.parametrize("planes", [False, True])
+def test_bn_planes_return_codes(planes):
+    h = _Host()
+    lib = nv.lib()
+    pl = h[9] if planes else None
+
+    def fwd(n_cap, c, dtype):       # x mean invstd gamma beta residual relu y planes n_dev n_cap c dtype row_map post_add stream
+        return lib.u3d_bn_apply(h[0], h[1], h[2], h[3], h[4], None, 1, h[5], pl, h[6], n_cap, c, dtype, None, None, None)
+
+    def bwd(n_cap, c, dtype):       # dy y x mean invstd gamma beta sums relu dx dres planes n_dev n_cap c dtype row_map stream
+        return lib.u3d_bn_bwd_apply(h[0], h[7], h[8], h[1], h[2], h[3], h[4], h[10], 1, h[5], None, pl, h[6], n_cap, c, dtype, None, None)
+
+    for call in (fwd, bwd):
+        assert call(0, 64, nv.F32) == OK                          # no rows: nothing launched
+        if planes:
+            assert call(0, 64, nv.BF16) == UNSUPPORTED            # the planes come from f32 rows only
+            assert call(0, 24, nv.F32) == UNSUPPORTED             # 24 % 4 == 0 but 256 % (24 / 4) != 0: not a vector-kernel shape
+        else:
+            assert call(0, 64, nv.BF16) == OK and call(0, 24, nv.F32) == OK
+    if planes:      # row_map together with a residual / dres; a misaligned column parameter
+        assert lib.u3d_bn_apply(h[0], h[1], h[2], h[3], h[4], h[7], 1, h[5], pl, h[6], 0, 64, nv.F32, h[8], None, None) == UNSUPPORTED
+        assert lib.u3d_bn_bwd_apply(h[0], h[7], h[8], h[1], h[2], h[3], h[4], h[10], 1, h[5], h[11], pl, h[6], 0, 64, nv.F32, h[12], None) \
+            == UNSUPPORTED
+        odd = C.c_void_p(h[1].value + 4)
+        assert lib.u3d_bn_apply(h[0], odd, h[2], h[3], h[4], None, 1, h[5], pl, h[6], 0, 64, nv.F32, None, None, None) == UNSUPPORTED
+        assert lib.u3d_bn_bwd_apply(h[0], h[7], h[8], odd, h[2], h[3], h[4], h[10], 1, h[5], None, pl, h[6], 0, 64, nv.F32, None, None) \
+            == UNSUPPORTED

@@ -14,7 +14,7 @@ from test_bn_fold_cpu import bf16_bits_from_f64, tiny_cfg
 from uni3detr_amd import native as nv
 from uni3detr_amd.inference import InferenceModel, classify
 
-NEW = ("u3d_subm_halo_conv64_affine_bf16", "u3d_subm_halo_conv128_affine_bf16", "u3d_igemm_direct_affine_bf16")
+NEW = ("u3d_subm_halo_conv_bf16", "u3d_igemm_direct_affine_bf16")
 
 
 def affine_epilogue64(acc, shift, addend=None, relu=False):

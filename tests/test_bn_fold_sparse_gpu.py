@@ -1,9 +1,11 @@
-"""InferenceModel(sparse_levels=True) on the GPU: the affine instantiations of the halo kernels (u3d_subm_halo_conv64 / 128_affine_bf16)
+"""InferenceModel(sparse_levels=True) on the GPU: the affine instantiations of the halo kernels (u3d_subm_halo_conv_bf16 with a shift)
 and of the direct-operand kernels (u3d_igemm_direct_affine_bf16) against the entries they are built from and against the float64
 restatement of tests/test_bn_fold_sparse_cpu.py, then the model: routing, launch counts, logits against the fp32 model, refresh.
 
 E(path) = max |path - f64| / max |f64| over live rows (the measure of tests/test_bn_fold_gpu.py); the folded path is held to
 E(folded) <= 2 * E(unfolded) with E(unfolded) < 2e-2, the unfolded path being conv + u3d_bn_apply as sparse._BNRows runs it."""
+import ctypes
+
 import pytest
 import torch
 
@@ -112,6 +114,30 @@ def test_halo_affine_identities_padding_and_error_bound(cuda, halo_case):
             print(f"halo{c} n={n} max_slots={ms} residual={add is not None}: E(folded) = {ef:.3e}  E(unfolded) = {eu:.3e}")
             assert eu < 2e-2
             assert ef <= 2 * eu, (ef, eu)
+
+
+@pytest.mark.parametrize("c", [64, 128])
+def test_halo_affine_refuses_krev_and_zero_shift_is_the_plain_conv(cuda, c):
+    """The merged entry on the smallest level of the halo tests (a few 128-row tiles): an affine call with krev = 1 is U3D_ERR_ARG
+    and writes nothing (the affine kernels used to zero krev silently); with a zero shift and no ReLU the affine instantiation gives
+    the plain one's bits."""
+    lvl, nbr = _level(seed=3, n_pts=300, dims=(8, 8, 8))
+    n, live = lvl.n, int(lvl.n_dev.item())
+    halo = nv.SubmHalo(nbr, lvl.n_dev, n)
+    assert halo.ok and halo.kvol == 27 and halo.tiles >= 2 and 0 < live <= n
+    torch.manual_seed(c)
+    x = torch.randn(n, c, device=cuda).bfloat16()
+    wp = nv.subm_halo_wpack((torch.randn(27, c, c, device=cuda) * 0.1).bfloat16())
+    zero = torch.zeros(c, device=cuda)
+    out = torch.full((n, c), SENT, dtype=torch.bfloat16, device=cuda)
+    rc = nv.lib().u3d_subm_halo_conv_bf16(nv._ptr(x), nv._ptr(wp), ctypes.byref(halo.tables), c, 1, None, nv._ptr(out), None, nv._ptr(zero),
+                                          0, 0, nv._stream())
+    torch.cuda.synchronize()
+    assert rc == -1 and bool((out.view(torch.int16) == torch.tensor(SENT).bfloat16().view(torch.int16).item()).all())
+    base = nv.subm_halo_conv(x, wp, halo)
+    got = nv.subm_halo_conv_affine(x, wp, halo, zero, False)
+    assert bool(torch.isfinite(base[:live]).all()) and float(base[:live].float().abs().max()) > 0
+    assert torch.equal(got[:live].view(torch.int16), base[:live].view(torch.int16))
 
 
 # ---- direct-operand kernels -------------------------------------------------------------------------------------------------------------

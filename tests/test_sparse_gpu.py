@@ -1130,7 +1130,7 @@ def test_split_bf16_conv_forward_backward_match_f32_oracle(cuda, cin, cout, kvol
 
 @pytest.mark.parametrize("c,res,rowmap", [(16, False, False), (64, True, False), (256, False, True), (512, False, False), (128, False, False)])
 def test_bn_passes_write_the_planes_a_split_product_reads(cuda, c, res, rowmap):
-    """u3d_bn_apply_planes / u3d_bn_bwd_apply_planes (round 6): the BatchNorm apply pass of the fp32 modules also leaves its output as the
+    """u3d_bn_apply / u3d_bn_bwd_apply with planes (round 6): the BatchNorm apply pass of the fp32 modules also leaves its output as the
     hi / lo bf16 planes of a split-bf16 product, the backward pass the planes of dx - bit for bit what u3d_split_rows_f32 of the same
     tensor holds (padding rows of a capacity-sized tensor: zeros), and y / dx themselves unchanged."""
     torch.manual_seed(c)
@@ -1164,6 +1164,38 @@ def test_bn_passes_write_the_planes_a_split_product_reads(cuda, c, res, rowmap):
     d = dx1.clone()
     d[n:] = 0
     assert torch.equal(dpl, nv.split_rows(d, nd))
+
+
+@pytest.mark.parametrize("c", [24, 64])
+def test_bn_planes_retry_where_the_fused_pass_does_not_take_the_shape(cuda, c):
+    """want_planes on f32 rows, one row past a 256-row block and with a device count below the capacity: c = 64 runs the fused pass,
+    c = 24 (a multiple of 4, but 256 % (24 / 4) != 0) is answered U3D_ERR_UNSUPPORTED and retried without planes -> (y, None) /
+    (dx, dres, None).  y / dx are the bits of the call without want_planes either way."""
+    torch.manual_seed(c)
+    n, live = 257, 200
+    x = (torch.randn(n, c, device=cuda) * 2 + 0.5).contiguous()
+    x[live:] = float("nan")
+    r = torch.randn(n, c, device=cuda)
+    gamma, beta = torch.rand(c, device=cuda) + 0.5, torch.randn(c, device=cuda) * 0.1
+    nd = torch.tensor([live], dtype=torch.int32, device=cuda)
+    mean, invstd = nv.bn_forward_stats(x, nd, 1e-3, 0.1)
+    bits = lambda t: t[:live].view(torch.int32)      # noqa: E731
+    y0 = nv.bn_apply(x, mean, invstd, gamma, beta, r, True, nd)
+    y1, pl = nv.bn_apply(x, mean, invstd, gamma, beta, r, True, nd, want_planes=True)
+    assert bool(torch.isfinite(y0[:live]).all()) and torch.equal(bits(y0), bits(y1))
+    dy = torch.randn(n, c, device=cuda)
+    sums = nv.bn_bwd_stats(dy, y0, x, mean, invstd, True, nd, gamma, beta)
+    dx0, dres0 = nv.bn_bwd_apply(dy, y0, x, mean, invstd, gamma, sums, True, nd, True, beta)
+    dx1, dres1, dpl = nv.bn_bwd_apply(dy, y0, x, mean, invstd, gamma, sums, True, nd, True, beta, want_planes=True)
+    assert bool(torch.isfinite(dx0[:live]).all()) and torch.equal(bits(dx0), bits(dx1)) and torch.equal(bits(dres0), bits(dres1))
+    if c == 24:
+        assert pl is None and dpl is None
+        return
+    for planes, t in ((pl, y1), (dpl, dx1)):
+        assert planes.shape == (2 * n, c) and planes.dtype == torch.bfloat16
+        ref = nv.split_rows(t, nd).view(2, n, c)
+        assert torch.equal(planes.view(2, n, c)[:, :live].view(torch.int16), ref[:, :live].view(torch.int16))
+        assert not bool(planes.view(2, n, c)[:, live:].view(torch.int16).any())      # rows past the count: zeros in both planes
 
 
 def test_split_convs_pick_up_the_planes_their_batchnorm_wrote(cuda):

@@ -329,7 +329,7 @@ def test_two_phase_backward_matches_single_backward(cuda, graph, buckets):
 
 
 def test_adamw_state_entry_follows_hyper_parameters_and_skip_mask(cuda):
-    """u3d_adamw_step_state reads lr / betas / weight decay from the device state (u3d_adamw_set_hyper) - what lets a captured graph
+    """u3d_adamw_step_hold reads lr / betas / weight decay from the device state (u3d_adamw_set_hyper) - what lets a captured graph
     follow the step / cyclic schedules - and leaves chunks flagged in the skip mask untouched (torch.optim.AdamW skips .grad is None)."""
     from uni3detr_amd import native as nv
     torch.manual_seed(3)

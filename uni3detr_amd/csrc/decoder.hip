@@ -44,15 +44,14 @@ static const int kSaveCols[U3D_DS_COUNT][2] = {   // (columns, bytes per element
     {256, 2}, {256, 2}, {256, 2},                                                                         // C1 UC2 C2
     {80, 4}};                                                                                             // AMASK (8 heads x 10 words per query row)
 
-extern "C" int32_t u3d_decoder_layer_blocks_dt(int32_t m, int32_t dtype) { return u3d_cdiv(m > 0 ? m : 1, dc_bm(dtype)); }
-extern "C" int32_t u3d_decoder_layer_blocks(int32_t m) { return u3d_decoder_layer_blocks_dt(m, U3D_BF16); }
+extern "C" int32_t u3d_decoder_layer_blocks(int32_t m, int32_t dtype) { return u3d_cdiv(m > 0 ? m : 1, dc_bm(dtype)); }
 
-extern "C" int32_t u3d_decoder_layer_slots_dt(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off) {
+extern "C" int32_t u3d_decoder_layer_slots(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off) {
   U3D_REQUIRE(m > 0 && ncls > 0 && ncls <= 32 && code > 0 && code <= 32, U3D_ERR_ARG);
   U3D_REQUIRE(dtype == U3D_BF16 || dtype == U3D_F32, U3D_ERR_ARG);
   auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
   const int es = dc_esize(dtype);
-  const int nb = u3d_decoder_layer_blocks_dt(m, dtype);
+  const int nb = u3d_decoder_layer_blocks(m, dtype);
   m = nb * dc_bm(dtype);          // every slot holds whole row blocks: the row kernels never branch on the row index
   if (save_off) {
     int64_t o = 0;
@@ -83,15 +82,12 @@ extern "C" int32_t u3d_decoder_layer_slots_dt(int32_t m, int32_t ncls, int32_t c
   }
   return U3D_OK;
 }
-extern "C" int32_t u3d_decoder_layer_slots(int32_t m, int32_t ncls, int32_t code, int64_t* save_off, int64_t* grad_off) {
-  return u3d_decoder_layer_slots_dt(m, ncls, code, U3D_BF16, save_off, grad_off);
-}
 
 template <typename E>
 static DcPtrs<E> dc_resolve(void* save, int m) {
   typedef typename E::T T;
   int64_t off[U3D_DS_COUNT + 1];
-  u3d_decoder_layer_slots_dt(m, 1, 1, E::DT, off, nullptr);
+  u3d_decoder_layer_slots(m, 1, 1, E::DT, off, nullptr);
   char* b = (char*)save;
   DcPtrs<E> p;
   p.sine = (T*)(b + off[U3D_DS_SINE]); p.rph1 = (T*)(b + off[U3D_DS_RPH1]); p.rph2 = (T*)(b + off[U3D_DS_RPH2]);
@@ -152,9 +148,6 @@ extern "C" int32_t u3d_wpack(const u3d_wpack_desc* descs_dev, int32_t count, int
   else hipLaunchKernelGGL(k_wpack<EF>, dim3(gx, count), dim3(256), 0, s, descs_dev);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
-}
-extern "C" int32_t u3d_wpack_bf16(const u3d_wpack_desc* descs_dev, int32_t count, int32_t max_elems, u3d_stream s) {
-  return u3d_wpack(descs_dev, count, max_elems, U3D_BF16, s);
 }
 
 __global__ void k_dropout_mask(const unsigned long long* rng, int layer, int site, long long n, unsigned thresh, int cols, unsigned char* keep) {
@@ -410,8 +403,8 @@ __global__ __launch_bounds__(256, 2) void k_mha_fwd(const typename E::T* __restr
   }
 }
 
-extern "C" int32_t u3d_mha_fwd_dt(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng,
-                                  void* o, float* lse, int32_t dtype, u3d_stream s) {
+extern "C" int32_t u3d_mha_fwd(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng,
+                               void* o, float* lse, int32_t dtype, u3d_stream s) {
   U3D_REQUIRE(qk && v && o && lse && m > 0 && nq > 0 && m % nq == 0 && p_attn >= 0.f && p_attn < 1.f, U3D_ERR_ARG);
   U3D_REQUIRE(p_attn == 0.f || rng, U3D_ERR_ARG);
   U3D_REQUIRE(dtype == U3D_BF16 || dtype == U3D_F32, U3D_ERR_ARG);
@@ -428,10 +421,6 @@ extern "C" int32_t u3d_mha_fwd_dt(const void* qk, const void* v, int32_t m, int3
   }
   U3D_CHECK_LAUNCH();
   return U3D_OK;
-}
-extern "C" int32_t u3d_mha_fwd(const void* qk, const void* v, int32_t m, int32_t nq, float p_attn, int32_t layer, const uint64_t* rng,
-                               void* o, float* lse, u3d_stream s) {
-  return u3d_mha_fwd_dt(qk, v, m, nq, p_attn, layer, rng, o, lse, U3D_BF16, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -896,7 +885,7 @@ static int32_t dc_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dim
                             float* iou_out, void* save, u3d_stream s) {
   typedef typename E::T T;
   const DcPtrs<E> S = dc_resolve<E>(save, d->m);
-  const int nb = u3d_decoder_layer_blocks_dt(d->m, E::DT);
+  const int nb = u3d_decoder_layer_blocks(d->m, E::DT);
   U3D_ALLOW_LDS(k_dec_pre<E>, DcLds<E>::BYTES);
   U3D_ALLOW_LDS(k_dec_post<E>, DcLds<E>::BYTES);
   // bf16, groups of at most one LDS chunk of queries: in-projection + attention in ONE launch per layer (k_mha_proj_fwd)
@@ -910,7 +899,7 @@ static int32_t dc_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dim
                        d->nq, scale_log2, dc_thresh(d->p_attn), dc_inv_keep(d->p_attn), d->layer, (const unsigned long long*)rng,
                        (u16*)S.qk, (u16*)S.v, (u16*)S.o, S.lse, S.amask);
   } else {
-    int32_t rc = u3d_mha_fwd_dt(S.qk, S.v, d->m, d->nq, d->p_attn, d->layer, rng, S.o, S.lse, E::DT, s);
+    int32_t rc = u3d_mha_fwd(S.qk, S.v, d->m, d->nq, d->p_attn, d->layer, rng, S.o, S.lse, E::DT, s);
     if (rc != U3D_OK) return rc;
   }
   hipLaunchKernelGGL(k_dec_post<E>, dim3(nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, x, ref, (const T*)value,
@@ -921,25 +910,20 @@ static int32_t dc_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dim
 
 // row_waves: waves per workgroup of the two row-chain launches - 8 (bf16 only: two waves per SIMD) | 4 | 0 = the element type's default
 // (bf16: 8, f32: 4).  The results do not depend on it, bit for bit.
-extern "C" int32_t u3d_decoder_layer_fwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                            const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
-                                            float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes,
-                                            int32_t row_waves, u3d_stream s) {
+extern "C" int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                         const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
+                                         float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes,
+                                         int32_t row_waves, u3d_stream s) {
   int32_t rc = dc_check(p, d);
   if (rc != U3D_OK) return rc;
   U3D_REQUIRE(x && xc && ref && value && x_out && xc_out && reg_out && cls_out && iou_out && save, U3D_ERR_ARG);
   U3D_REQUIRE((d->p_attn == 0.f && d->p_drop == 0.f) || rng, U3D_ERR_ARG);
   U3D_REQUIRE(row_waves == 0 || row_waves == 4 || (row_waves == 8 && d->dtype == U3D_BF16), U3D_ERR_ARG);
   int64_t off[U3D_DS_COUNT + 1];
-  u3d_decoder_layer_slots_dt(d->m, d->ncls, d->code, d->dtype, off, nullptr);
+  u3d_decoder_layer_slots(d->m, d->ncls, d->code, d->dtype, off, nullptr);
   U3D_REQUIRE(save_bytes >= off[U3D_DS_COUNT], U3D_ERR_WORKSPACE);
   if (d->dtype == U3D_BF16 && row_waves == 4)
     return dc_layer_fwd<EB4>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
   if (d->dtype == U3D_BF16) return dc_layer_fwd<EB>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
   return dc_layer_fwd<EF>(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, s);
-}
-extern "C" int32_t u3d_decoder_layer_fwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                         const float* ref, const void* value, const uint64_t* rng, float* x_out, void* xc_out,
-                                         float* reg_out, float* cls_out, float* iou_out, void* save, int64_t save_bytes, u3d_stream s) {
-  return u3d_decoder_layer_fwd_nw(p, d, x, xc, ref, value, rng, x_out, xc_out, reg_out, cls_out, iou_out, save, save_bytes, 0, s);
 }

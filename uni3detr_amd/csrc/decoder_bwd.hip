@@ -41,14 +41,14 @@ struct DcGrad {            // gradient-workspace slots
   int nb;                  // workgroups = rows of each LayerNorm partial matrix
 };
 
-extern "C" int32_t u3d_decoder_layer_slots_dt(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off);
-extern "C" int32_t u3d_decoder_layer_blocks_dt(int32_t m, int32_t dtype);
+extern "C" int32_t u3d_decoder_layer_slots(int32_t m, int32_t ncls, int32_t code, int32_t dtype, int64_t* save_off, int64_t* grad_off);
+extern "C" int32_t u3d_decoder_layer_blocks(int32_t m, int32_t dtype);
 
 template <typename E>
 static DcSave<E> dcb_resolve_save(const void* save, int m) {
   typedef typename E::T T;
   int64_t off[U3D_DS_COUNT + 1];
-  u3d_decoder_layer_slots_dt(m, 1, 1, E::DT, off, nullptr);
+  u3d_decoder_layer_slots(m, 1, 1, E::DT, off, nullptr);
   const char* b = (const char*)save;
   DcSave<E> p;
   p.sine = (const T*)(b + off[U3D_DS_SINE]); p.rph1 = (const T*)(b + off[U3D_DS_RPH1]); p.rph2 = (const T*)(b + off[U3D_DS_RPH2]);
@@ -69,7 +69,7 @@ template <typename E>
 static DcGrad<E> dcb_resolve_grad(void* grad, int m, int ncls, int code, int64_t* total) {
   typedef typename E::T T;
   int64_t off[U3D_DG_COUNT + 1];
-  u3d_decoder_layer_slots_dt(m, ncls, code, E::DT, nullptr, off);
+  u3d_decoder_layer_slots(m, ncls, code, E::DT, nullptr, off);
   char* b = (char*)grad;
   DcGrad<E> g;
   g.clso = (T*)(b + off[U3D_DG_CLSO]); g.c2u = (T*)(b + off[U3D_DG_C2U]); g.c1u = (T*)(b + off[U3D_DG_C1U]);
@@ -82,7 +82,7 @@ static DcGrad<E> dcb_resolve_grad(void* grad, int m, int ncls, int code, int64_t
   g.qs1 = (T*)(b + off[U3D_DG_QS1]); g.raw = (T*)(b + off[U3D_DG_RAW]); g.rph2 = (T*)(b + off[U3D_DG_RPH2]);
   g.rph1 = (T*)(b + off[U3D_DG_RPH1]); g.lnp = (float*)(b + off[U3D_DG_LNP]); g.du1 = (float*)(b + off[U3D_DG_DU1]);
   g.dposa = (T*)(b + off[U3D_DG_DPOSA]); g.sine = (T*)(b + off[U3D_DG_SINE]);
-  g.nb = u3d_decoder_layer_blocks_dt(m, E::DT);
+  g.nb = u3d_decoder_layer_blocks(m, E::DT);
   if (total) *total = off[U3D_DG_COUNT];
   return g;
 }
@@ -736,8 +736,8 @@ static void mha_bwd_launch(const void* qk, const void* v, const void* o, const v
   hipLaunchKernelGGL(k_mha_bwd_dkv<E>, grid, dim3(256), 0, s, (const T*)qk, (const T*)v, (const T*)o, (const T*)d_o, lse, nq, qt, scale_log2,
                      scale, dc_thresh(p_attn), dc_inv_keep(p_attn), layer, (const unsigned long long*)rng, (T*)dqk, (T*)dv, amask);
 }
-extern "C" int32_t u3d_mha_bwd_dt(const void* qk, const void* v, const void* o, const void* d_o, const float* lse, int32_t m, int32_t nq,
-                                  float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, int32_t dtype, u3d_stream s) {
+extern "C" int32_t u3d_mha_bwd(const void* qk, const void* v, const void* o, const void* d_o, const float* lse, int32_t m, int32_t nq,
+                               float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, int32_t dtype, u3d_stream s) {
   U3D_REQUIRE(qk && v && o && d_o && lse && dqk && dv && m > 0 && nq > 0 && m % nq == 0 && p_attn >= 0.f && p_attn < 1.f, U3D_ERR_ARG);
   U3D_REQUIRE(p_attn == 0.f || rng, U3D_ERR_ARG);
   U3D_REQUIRE(dtype == U3D_BF16 || dtype == U3D_F32, U3D_ERR_ARG);
@@ -746,10 +746,6 @@ extern "C" int32_t u3d_mha_bwd_dt(const void* qk, const void* v, const void* o, 
   else mha_bwd_launch<EF>(qk, v, o, d_o, lse, m, nq, p_attn, layer, rng, dqk, dv, s);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
-}
-extern "C" int32_t u3d_mha_bwd(const void* qk, const void* v, const void* o, const void* d_o, const float* lse, int32_t m, int32_t nq,
-                               float p_attn, int32_t layer, const uint64_t* rng, void* dqk, void* dv, u3d_stream s) {
-  return u3d_mha_bwd_dt(qk, v, o, d_o, lse, m, nq, p_attn, layer, rng, dqk, dv, U3D_BF16, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -880,7 +876,7 @@ static int32_t dcb_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_di
     U3D_REQUIRE((long long)(d->m / d->nq) * DC_NHEAD * d->nq * (d->nq + 1) < (1ll << 32), U3D_ERR_UNSUPPORTED);
     mha_bwd_launch<typename E::ME>(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, s, S.amask);
   } else {
-    int32_t rc = u3d_mha_bwd_dt(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, E::DT, s);
+    int32_t rc = u3d_mha_bwd(S.qk, S.v, S.o, G.d_o, S.lse, d->m, d->nq, d->p_attn, d->layer, rng, G.dqk, G.dv, E::DT, s);
     if (rc != U3D_OK) return rc;
   }
   hipLaunchKernelGGL(k_dec_pre_bwd<E>, dim3(G.nb), dim3(E::NW * 64), DcLds<E>::BYTES, s, *p, *d, S, G, dx);
@@ -888,11 +884,11 @@ static int32_t dcb_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_di
   return U3D_OK;
 }
 
-// row_waves: as in u3d_decoder_layer_fwd_nw (it need not be the forward call's: the slots do not depend on it)
-extern "C" int32_t u3d_decoder_layer_bwd_nw(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                            const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
-                                            const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                                            void* dvalue, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s) {
+// row_waves: as in u3d_decoder_layer_fwd (it need not be the forward call's: the slots do not depend on it)
+extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
+                                         const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
+                                         const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
+                                         void* dvalue, float* dref, void* grad, int64_t grad_bytes, int32_t row_waves, u3d_stream s) {
   (void)x; (void)xc; (void)xc_out;
   int32_t rc = dcb_check(p, d);
   if (rc != U3D_OK) return rc;
@@ -906,13 +902,6 @@ extern "C" int32_t u3d_decoder_layer_bwd_nw(const u3d_declayer_params* p, const 
   if (d->dtype == U3D_BF16)
     return dcb_layer_bwd<EB>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
   return dcb_layer_bwd<EF>(p, d, ref, value, rng, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes, s);
-}
-extern "C" int32_t u3d_decoder_layer_bwd(const u3d_declayer_params* p, const u3d_declayer_dims* d, const float* x, const void* xc,
-                                         const float* ref, const void* value, const uint64_t* rng, const void* xc_out, const void* save,
-                                         const float* dx_out, const float* dreg, const float* dcls, const float* diou, float* dx,
-                                         void* dvalue, float* dref, void* grad, int64_t grad_bytes, u3d_stream s) {
-  return u3d_decoder_layer_bwd_nw(p, d, x, xc, ref, value, rng, xc_out, save, dx_out, dreg, dcls, diou, dx, dvalue, dref, grad, grad_bytes,
-                                  0, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 // Every kernel is a template over an ELEMENT TRAIT E - the storage type of activations / weights / slots and the MFMA that consumes
 // them - and is instantiated on:
 //   EB  bf16 storage, v_mfma_f32_16x16x32_bf16, 32 rows per workgroup, 8 waves   (throughput mode, U3D_BF16)
-//   EB4 the same at 4 waves (row-chain kernels only; row_waves = 4 of u3d_decoder_layer_fwd_nw / _bwd_nw)
+//   EB4 the same at 4 waves (row-chain kernels only; row_waves = 4 of u3d_decoder_layer_fwd / _bwd)
 //   EF  f32 storage,  v_mfma_f32_16x16x4_f32 (bitwise an fma chain), 16 rows, 4 waves   (parity mode, U3D_F32: the 1e-3 reference goldens)
 // Same source, same launch structure, same slot layout (element size aside): what the parity tests exercise IS the benchmarked code.
 //
@@ -296,7 +296,7 @@ __device__ __forceinline__ f32x4 dc_relu4(f32x4 v) {
 
 // ---- control flow discipline -------------------------------------------------------------------------------------------------
 // Every loop below has a trip count the compiler can see is the same for all lanes (DC_FOR_TID), and no branch depends on the row
-// index: row matrices owned by this library (save / gradient slots, outputs) hold whole BM-row blocks (u3d_decoder_layer_blocks_dt(m)
+// index: row matrices owned by this library (save / gradient slots, outputs) hold whole BM-row blocks (u3d_decoder_layer_blocks(m)
 // * BM rows), caller-owned inputs of m rows are read through a clamped row index.  Reason: hipcc (ROCm 7.2) was seen to place
 // register-allocator copies (v_accvgpr_write) in the exit block of an exec-masked `for (i = tid; i < N; i += 256)` loop AHEAD of the
 // `s_or_b64 exec` that restores the lane mask - the copies ran with EXEC = 0 and the "saved" LDS addresses were garbage afterwards

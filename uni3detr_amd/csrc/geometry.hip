@@ -5,12 +5,9 @@
 // ============================================================================================
 // BitGrid
 // ============================================================================================
-extern "C" int64_t u3d_bitgrid_nwords(int32_t batch, int32_t dz, int32_t dy, int32_t dx) {
-  return (int64_t)batch * ((dz + 3) / 4) * ((dy + 3) / 4) * ((dx + 3) / 4);
-}
 extern "C" int64_t u3d_bitgrid_nwords_layout(int32_t batch, int32_t dz, int32_t dy, int32_t dx, int32_t layout) {
   if (layout == 1) return ((int64_t)batch * dz * dy * dx + 63) / 64;
-  return u3d_bitgrid_nwords(batch, dz, dy, dx);
+  return (int64_t)batch * ((dz + 3) / 4) * ((dy + 3) / 4) * ((dx + 3) / 4);
 }
 static inline long long grid_nwords(const u3d_bitgrid* g) { return u3d_bitgrid_nwords_layout(g->batch, g->dz, g->dy, g->dx, g->layout); }
 

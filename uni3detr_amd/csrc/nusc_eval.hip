@@ -212,7 +212,7 @@ extern "C" int32_t u3d_nusc_rank_keys(const double* rec, int32_t n, int64_t* key
 // order, then a wave argmin with the lowest index on ties); a TP iff that distance < ths[t].  Outputs by rank position r:
 // tp int8 [4][n], match int32 [n] = the GT row taken at threshold tp_th (-1: none).
 // ---------------------------------------------------------------------------------------------------------------------------
-extern "C" int64_t u3d_nusc_match_lds(int32_t max_gt) { return (int64_t)max_gt * 16; }
+static inline int64_t nusc_match_lds(int32_t max_gt) { return (int64_t)max_gt * 16; }
 
 __global__ __launch_bounds__(64) void k_nusc_match(const double* __restrict__ pred, const int* __restrict__ rank, const int* __restrict__ mperm,
                                                    const int* __restrict__ mseg, const double* __restrict__ gt, const int* __restrict__ gord,
@@ -275,7 +275,7 @@ extern "C" int32_t u3d_nusc_match(const double* pred, const int32_t* rank, const
   U3D_REQUIRE(max_gt <= NU_MAX_GT, U3D_ERR_UNSUPPORTED);
   if (n_seg == 0 || n == 0) return U3D_OK;
   U3D_REQUIRE(pred && rank && mperm && mseg && gseg && ths && tp && match && (max_gt == 0 || (gt && gord)), U3D_ERR_ARG);
-  hipLaunchKernelGGL(k_nusc_match, dim3(n_seg), dim3(64), (size_t)u3d_nusc_match_lds(max_gt), s, pred, rank, mperm, mseg, gt, gord, gseg,
+  hipLaunchKernelGGL(k_nusc_match, dim3(n_seg), dim3(64), (size_t)nusc_match_lds(max_gt), s, pred, rank, mperm, mseg, gt, gord, gseg,
                      ths, tp_th, n, (signed char*)tp, match);
   U3D_CHECK_LAUNCH();
   return U3D_OK;

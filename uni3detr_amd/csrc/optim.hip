@@ -147,10 +147,6 @@ extern "C" int32_t u3d_adamw_step_hold(float* param, const float* grad, float* e
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
-extern "C" int32_t u3d_adamw_step_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
-                                        const uint8_t* skip, void* workspace, int64_t workspace_bytes, u3d_stream s) {
-  return u3d_adamw_step_hold(param, grad, exp_avg, exp_avg_sq, n, state, skip, nullptr, workspace, workspace_bytes, s);
-}
 
 // ---------------------------------------------------------------------------------------------
 // The same step with gradient accumulation, a non-finite skip and EMA weights (u3d_adamw_step_accum): one captured batch is a
@@ -381,13 +377,13 @@ extern "C" int32_t u3d_capacity_flag(const int32_t* const* counts, const int32_t
 }
 
 // host-scalar form: writes the hyper-parameters into the state vector, then steps (a captured graph of THIS entry bakes them in;
-// schedules use u3d_adamw_set_hyper between replays + u3d_adamw_step_state inside the graph)
+// schedules use u3d_adamw_set_hyper between replays + u3d_adamw_step_hold inside the graph)
 extern "C" int32_t u3d_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, float max_norm, float* state, void* workspace,
                                   int64_t workspace_bytes, u3d_stream s) {
   int32_t rc = u3d_adamw_set_hyper(state, lr, beta1, beta2, eps, weight_decay, max_norm, s);
   if (rc != U3D_OK) return rc;
-  return u3d_adamw_step_state(param, grad, exp_avg, exp_avg_sq, n, state, nullptr, workspace, workspace_bytes, s);
+  return u3d_adamw_step_hold(param, grad, exp_avg, exp_avg_sq, n, state, nullptr, nullptr, workspace, workspace_bytes, s);
 }
 
 

@@ -629,7 +629,7 @@ __device__ __forceinline__ void store_planes4(u16* p, long long plane, const flo
   *(bf16x4_t*)p = h;
   *(bf16x4_t*)(p + plane) = l;
 }
-// PLANES (f32 rows only, u3d_bn_apply_planes / u3d_bn_bwd_apply_planes): the kernel ALSO leaves its output as the two bf16 planes a
+// PLANES (f32 rows only, u3d_bn_apply / u3d_bn_bwd_apply with planes): the kernel ALSO leaves its output as the two bf16 planes a
 // split-bf16 convolution reads ([2 * n_cap][c]: hi | lo, padding rows n .. n_cap zero) - the separate u3d_split_rows_f32 pass over the
 // tensor (one more read + write of every element, 186 launches per `parity` step) disappears for every tensor a BatchNorm produces
 template <typename T, bool PLANES = false>
@@ -735,13 +735,23 @@ static inline int ew_grid(long long total) {
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
+// planes (f32 rows only): y (dx) AND its hi / lo bf16 planes [2 * n_cap][c] in one pass (see k_bn_apply_vec<., PLANES>).
+// U3D_ERR_UNSUPPORTED for what that instantiation does not take (the caller then runs the plain pass + u3d_split_rows_f32).
 extern "C" int32_t u3d_bn_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                const void* residual, int32_t relu, void* y, const int32_t* n_dev, int32_t n_cap, int32_t c,
+                                const void* residual, int32_t relu, void* y, void* planes, const int32_t* n_dev, int32_t n_cap, int32_t c,
                                 int32_t dtype, const int32_t* row_map, const void* post_add, u3d_stream s) {
   U3D_REQUIRE(x && mean && invstd && gamma && beta && y && n_dev && c > 0, U3D_ERR_ARG);
+  const bool pal = al16(mean) && al16(invstd) && al16(gamma) && al16(beta);
+  if (planes) {
+    if (dtype != U3D_F32 || !bn_vec_ok(c, 4) || !pal || (row_map && residual)) return U3D_ERR_UNSUPPORTED;
+    if (n_cap <= 0) return U3D_OK;
+    hipLaunchKernelGGL((k_bn_apply_vec<float, true>), dim3(bn_vec_grid(n_cap, c, 4)), dim3(256), 0, s, (const float*)x, mean, invstd, gamma, beta,
+                       (const float*)residual, relu, (float*)y, n_dev, n_cap, c, row_map, (const float*)post_add, (u16*)planes);
+    U3D_CHECK_LAUNCH();
+    return U3D_OK;
+  }
   U3D_REQUIRE(!row_map || (!residual && bn_vec_ok(c, dtype == U3D_F32 ? 4 : 8)), U3D_ERR_UNSUPPORTED);
   U3D_REQUIRE(!post_add || bn_vec_ok(c, dtype == U3D_F32 ? 4 : 8), U3D_ERR_UNSUPPORTED);
-  const bool pal = al16(mean) && al16(invstd) && al16(gamma) && al16(beta);
   U3D_REQUIRE(!(row_map || post_add) || pal, U3D_ERR_ARG);
   if (n_cap <= 0) return U3D_OK;
   int g = ew_grid((long long)n_cap * c);
@@ -760,10 +770,19 @@ extern "C" int32_t u3d_bn_apply(const void* x, const float* mean, const float* i
 
 extern "C" int32_t u3d_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* invstd,
                                     const float* gamma, const float* beta, const double* sums, int32_t relu, void* dx, void* dres,
-                                    const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, const int32_t* row_map, u3d_stream s) {
+                                    void* planes, const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, const int32_t* row_map,
+                                    u3d_stream s) {
   U3D_REQUIRE(dy && x && mean && invstd && gamma && sums && dx && n_dev && c > 0 && (!relu || y || beta), U3D_ERR_ARG);
-  U3D_REQUIRE(!row_map || (!dres && bn_vec_ok(c, dtype == U3D_F32 ? 4 : 8)), U3D_ERR_UNSUPPORTED);
   const bool pal = al16(mean) && al16(invstd) && al16(gamma) && al16(beta) && al16(sums);
+  if (planes) {      // as u3d_bn_apply's
+    if (dtype != U3D_F32 || !bn_vec_ok(c, 4) || !pal || (row_map && dres)) return U3D_ERR_UNSUPPORTED;
+    if (n_cap <= 0) return U3D_OK;
+    hipLaunchKernelGGL((k_bn_bwd_apply_vec<float, true>), dim3(bn_vec_grid(n_cap, c, 4)), dim3(256), 0, s, (const float*)dy, (const float*)y,
+                       (const float*)x, mean, invstd, gamma, beta, sums, relu, (float*)dx, (float*)dres, n_dev, n_cap, c, row_map, (u16*)planes);
+    U3D_CHECK_LAUNCH();
+    return U3D_OK;
+  }
+  U3D_REQUIRE(!row_map || (!dres && bn_vec_ok(c, dtype == U3D_F32 ? 4 : 8)), U3D_ERR_UNSUPPORTED);
   U3D_REQUIRE(!row_map || pal, U3D_ERR_ARG);
   if (n_cap <= 0) return U3D_OK;
   int g = ew_grid((long long)n_cap * c);
@@ -776,31 +795,6 @@ extern "C" int32_t u3d_bn_bwd_apply(const void* dy, const void* y, const void* x
   else if (dtype == U3D_BF16)
     hipLaunchKernelGGL(k_bn_bwd_apply<u16>, dim3(g), dim3(256), 0, s, (const u16*)dy, (const u16*)y, (const u16*)x, mean, invstd, gamma, beta, sums, relu, (u16*)dx, (u16*)dres, n_dev, n_cap, c);
   else return U3D_ERR_UNSUPPORTED;
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-
-// f32 rows only: y (dx) AND its hi / lo bf16 planes [2 * n_cap][c] in one pass (see k_bn_apply_vec<., PLANES>).  U3D_ERR_UNSUPPORTED for
-// shapes the vector kernels do not take (the caller then runs u3d_bn_apply + u3d_split_rows_f32).
-extern "C" int32_t u3d_bn_apply_planes(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                       const float* residual, int32_t relu, float* y, void* planes, const int32_t* n_dev, int32_t n_cap,
-                                       int32_t c, const int32_t* row_map, const float* post_add, u3d_stream s) {
-  U3D_REQUIRE(x && mean && invstd && gamma && beta && y && planes && n_dev && c > 0, U3D_ERR_ARG);
-  if (!bn_vec_ok(c, 4) || !(al16(mean) && al16(invstd) && al16(gamma) && al16(beta)) || (row_map && residual)) return U3D_ERR_UNSUPPORTED;
-  if (n_cap <= 0) return U3D_OK;
-  hipLaunchKernelGGL((k_bn_apply_vec<float, true>), dim3(bn_vec_grid(n_cap, c, 4)), dim3(256), 0, s, x, mean, invstd, gamma, beta, residual, relu, y,
-                     n_dev, n_cap, c, row_map, post_add, (u16*)planes);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-extern "C" int32_t u3d_bn_bwd_apply_planes(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
-                                           const float* gamma, const float* beta, const double* sums, int32_t relu, float* dx, float* dres,
-                                           void* planes, const int32_t* n_dev, int32_t n_cap, int32_t c, const int32_t* row_map, u3d_stream s) {
-  U3D_REQUIRE(dy && x && mean && invstd && gamma && sums && dx && planes && n_dev && c > 0 && (!relu || y || beta), U3D_ERR_ARG);
-  if (!bn_vec_ok(c, 4) || !(al16(mean) && al16(invstd) && al16(gamma) && al16(beta) && al16(sums)) || (row_map && dres)) return U3D_ERR_UNSUPPORTED;
-  if (n_cap <= 0) return U3D_OK;
-  hipLaunchKernelGGL((k_bn_bwd_apply_vec<float, true>), dim3(bn_vec_grid(n_cap, c, 4)), dim3(256), 0, s, dy, y, x, mean, invstd, gamma, beta, sums, relu,
-                     dx, dres, n_dev, n_cap, c, row_map, (u16*)planes);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
@@ -878,11 +872,7 @@ __global__ __launch_bounds__(256) void k_tap_gather_sum(const T* __restrict__ p,
   }
 }
 extern "C" int32_t u3d_tap_gather_sum(const void* p, const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t c,
-                                      int32_t kvol, int32_t dtype, void* out, u3d_stream s) {
-  return u3d_tap_gather_sum_add(p, nbr, ld, n_dev, n_cap, c, kvol, dtype, nullptr, out, s);
-}
-extern "C" int32_t u3d_tap_gather_sum_add(const void* p, const int32_t* nbr, int32_t ld, const int32_t* n_dev, int32_t n_cap, int32_t c,
-                                          int32_t kvol, int32_t dtype, const void* addend, void* out, u3d_stream s) {
+                                      int32_t kvol, int32_t dtype, const void* addend, void* out, u3d_stream s) {
   U3D_REQUIRE(p && nbr && n_dev && out && c > 0 && kvol > 0, U3D_ERR_ARG);
   if (n_cap <= 0) return U3D_OK;
   if (dtype == U3D_BF16 && c % 8 == 0) {

@@ -195,7 +195,7 @@ __device__ __forceinline__ f32x4 hl_relu(f32x4 v) {
 }
 
 // in/out/addend bf16 [n][64]; wgt: k_halo_wpack of bf16 [27][64 (n)][64 (reduction)]; stats f64 [tiles][2][64] or null
-// AFFINE (inference, eval-mode BatchNorm folded into wgt; u3d_subm_halo_conv64_affine_bf16): out = bf16(relu(acc + shift[col] +
+// AFFINE (inference, eval-mode BatchNorm folded into wgt; u3d_subm_halo_conv_bf16 with a shift): out = bf16(relu(acc + shift[col] +
 // addend)), one rounding, forward only and without statistics.  A compile-time switch: the kernel sits at 128 accumulator registers
 // and two workgroups per CU, and the training / eval instantiation <false> (AF is the empty pack: it has no further argument) stays the code it was.
 struct HlAffine { const float* shift; int relu; };      // shift f32 [C]; the one element of AF when AFFINE
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void k_halo_wpack128(const u16* __restrict__ s
 }
 
 #define HL_C2 128
-// AFFINE: as k_subm_halo64 (u3d_subm_halo_conv128_affine_bf16)
+// AFFINE: as k_subm_halo64
 template <bool AFFINE, typename... AF>
 __global__ __launch_bounds__(256, 2) void k_subm_halo128(const u16* __restrict__ in, const u16* __restrict__ wgt,
                                                          const int32_t* __restrict__ tile_rows, const u16* __restrict__ loc,
@@ -819,55 +819,72 @@ extern "C" int32_t u3d_subm_halo_build(const int32_t* nbr, int32_t ld, const int
   return U3D_OK;
 }
 
-extern "C" int32_t u3d_subm_halo_wpack(const void* w_nmajor, void* w_packed, u3d_stream s) {
-  U3D_REQUIRE(w_nmajor && w_packed, U3D_ERR_ARG);
-  k_halo_wpack<<<u3d_cdiv(HL_K * 512, 256), 256, 0, (hipStream_t)s>>>((const u16*)w_nmajor, (u16*)w_packed, nullptr, nullptr);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
+// c == 64 needs all 27 offsets (k_subm_halo64 and k_halo_wpack hard-code them); c == 128 takes 1 .. 27
+static int32_t hl_shape(int32_t c, int32_t kvol) {
+  U3D_REQUIRE(kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
+  return (c == HL_C && kvol == HL_K) || c == HL_C2 ? U3D_OK : U3D_ERR_UNSUPPORTED;
 }
 
-extern "C" int32_t u3d_subm_halo_wpack_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, u3d_stream s) {
-  U3D_REQUIRE(srcs_dev && dsts_dev && n >= 0, U3D_ERR_ARG);
+// src / dst (one weight) or srcs / dsts (device arrays of n pointers), never both
+static int32_t hl_wpack(const void* src, void* dst, const void* const* srcs, void* const* dsts, int32_t n, int32_t c, int32_t kvol,
+                        u3d_stream s) {
+  if (const int32_t e = hl_shape(c, kvol)) return e;
   if (n == 0) return U3D_OK;
-  k_halo_wpack<<<dim3(u3d_cdiv(HL_K * 512, 256), n), 256, 0, (hipStream_t)s>>>(nullptr, nullptr, (const u16* const*)srcs_dev, (u16* const*)dsts_dev);
+  if (c == HL_C)
+    k_halo_wpack<<<dim3(u3d_cdiv(HL_K * 512, 256), n), 256, 0, (hipStream_t)s>>>((const u16*)src, (u16*)dst, (const u16* const*)srcs, (u16* const*)dsts);
+  else
+    k_halo_wpack128<<<dim3(u3d_cdiv(kvol * 2048, 256), n), 256, 0, (hipStream_t)s>>>((const u16*)src, (u16*)dst, (const u16* const*)srcs,
+                                                                                     (u16* const*)dsts, kvol);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
 
-extern "C" int32_t u3d_subm_halo_conv64_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                             const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
-                                             const void* addend, void* out, double* stats, int32_t max_slots, u3d_stream s) {
-  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && n_cap > 0, U3D_ERR_ARG);
+extern "C" int32_t u3d_subm_halo_wpack(const void* w_nmajor, void* w_packed, int32_t c, int32_t kvol, u3d_stream s) {
+  U3D_REQUIRE(w_nmajor && w_packed, U3D_ERR_ARG);
+  return hl_wpack(w_nmajor, w_packed, nullptr, nullptr, 1, c, kvol, s);
+}
+
+extern "C" int32_t u3d_subm_halo_wpack_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, int32_t c, int32_t kvol,
+                                               u3d_stream s) {
+  U3D_REQUIRE(srcs_dev && dsts_dev && n >= 0, U3D_ERR_ARG);
+  return hl_wpack(nullptr, nullptr, srcs_dev, dsts_dev, n, c, kvol, s);
+}
+
+// one launch of the instantiation KERNEL; tail: its arguments after maxs (kvol for 128 channels, then the HlAffine if AFFINE)
+template <auto KERNEL, typename... Tail>
+static int32_t hl_conv(const void* in, const void* w_packed, const u3d_halo_tables* t, int32_t krev, const void* addend, void* out,
+                       double* stats, int32_t max_slots, u3d_stream s, Tail... tail) {
   const int lds = HL_MAXS * HL_RS * 2;
   static_assert(HL_MAXS * HL_RS * 2 >= 4 * 16 * 64 * 16, "stage buffer holds the first reduce-scatter round");
-  U3D_ALLOW_LDS(k_subm_halo64<false>, lds);
-  k_subm_halo64<false><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
-                                                                    n_cap, krev, (const u16*)addend, (u16*)out, stats,
-                                                                    (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS);
+  U3D_ALLOW_LDS(KERNEL, lds);      // the mask is a static of this instantiation: one per kernel
+  KERNEL<<<u3d_cdiv(t->n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, t->tile_rows, t->loc, t->tile_cnt, t->n_dev,
+                                                                 t->n_cap, krev, (const u16*)addend, (u16*)out, stats,
+                                                                 (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS, tail...);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
 
-extern "C" int32_t u3d_subm_halo_conv64_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                                    const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend,
-                                                    void* out, const float* shift, int32_t relu, int32_t max_slots, u3d_stream s) {
-  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && shift && n_cap > 0, U3D_ERR_ARG);
-  const int lds = HL_MAXS * HL_RS * 2;
-  U3D_ALLOW_LDS((k_subm_halo64<true, HlAffine>), lds);
-  k_subm_halo64<true, HlAffine><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
-                                                                          n_cap, 0, (const u16*)addend, (u16*)out, nullptr,
-                                                                          (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS,
-                                                                          HlAffine{shift, relu != 0});
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
+extern "C" int32_t u3d_subm_halo_conv_bf16(const void* in, const void* w_packed, const u3d_halo_tables* t, int32_t c, int32_t krev,
+                                           const void* addend, void* out, double* stats, const float* shift, int32_t relu,
+                                           int32_t max_slots, u3d_stream s) {
+  U3D_REQUIRE(in && w_packed && t && t->tile_rows && t->loc && t->tile_cnt && t->n_dev && out && t->n_cap > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(shift ? !krev && !stats : !relu, U3D_ERR_ARG);      // the affine epilogue is forward-only and reduces no statistics
+  if (const int32_t e = hl_shape(c, t->kvol)) return e;
+  if (c == HL_C)
+    return shift ? hl_conv<k_subm_halo64<true, HlAffine>>(in, w_packed, t, 0, addend, out, nullptr, max_slots, s, HlAffine{shift, relu != 0})
+                 : hl_conv<k_subm_halo64<false>>(in, w_packed, t, krev, addend, out, stats, max_slots, s);
+  return shift ? hl_conv<k_subm_halo128<true, HlAffine>>(in, w_packed, t, 0, addend, out, nullptr, max_slots, s, (int)t->kvol,
+                                                         HlAffine{shift, relu != 0})
+               : hl_conv<k_subm_halo128<false>>(in, w_packed, t, krev, addend, out, stats, max_slots, s, (int)t->kvol);
 }
 
 extern "C" int64_t u3d_subm_halo_wgrad64_workspace(void) { return (int64_t)HW_WGS * HW_OPG * HL_C * HL_C * 4; }
 
-extern "C" int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, const int32_t* tile_rows, const uint16_t* loc,
-                                              const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, float* dw, void* workspace,
+extern "C" int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, const u3d_halo_tables* t, float* dw, void* workspace,
                                               int64_t workspace_bytes, int32_t max_slots, u3d_stream s) {
-  U3D_REQUIRE(x && dy && tile_rows && loc && tile_cnt && n_dev && dw && workspace && n_cap > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(x && dy && t && t->tile_rows && t->loc && t->tile_cnt && t->n_dev && dw && workspace && t->n_cap > 0, U3D_ERR_ARG);
+  if (t->kvol != HL_K) return U3D_ERR_UNSUPPORTED;      // the kernel walks all 27 offsets
+  const int32_t n_cap = t->n_cap;
   U3D_REQUIRE(workspace_bytes >= u3d_subm_halo_wgrad64_workspace(), U3D_ERR_WORKSPACE);
   if ((long long)n_cap * HL_C * 2 >= 0x7fffffffll) return U3D_ERR_UNSUPPORTED;      // 32-bit buffer offsets of the LDS-DMA
   constexpr int lds = 2 * HW_BUF * 2;
@@ -876,50 +893,9 @@ extern "C" int32_t u3d_subm_halo_wgrad64_bf16(const void* x, const void* dy, con
   U3D_ALLOW_LDS(k_subm_halo_wgrad64, lds);
   int nwg = HW_G * u3d_cdiv(n_cap, HL_T);
   if (nwg > HW_WGS) nwg = HW_WGS;
-  k_subm_halo_wgrad64<<<nwg, 512, lds, (hipStream_t)s>>>((const u16*)x, (const u16*)dy, tile_rows, loc, tile_cnt, n_dev, n_cap, (float*)workspace,
+  k_subm_halo_wgrad64<<<nwg, 512, lds, (hipStream_t)s>>>((const u16*)x, (const u16*)dy, t->tile_rows, t->loc, t->tile_cnt, t->n_dev, n_cap, (float*)workspace,
                                                           (max_slots > 0 && max_slots < HW_MAXS) ? max_slots : HW_MAXS);
   k_halo_wgrad_reduce<<<HL_K * HL_C * HL_C / 4 / 32, 256, 0, (hipStream_t)s>>>((const float*)workspace, nwg, dw);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-
-extern "C" int32_t u3d_subm_halo_wpack128(const void* w_nmajor, void* w_packed, int32_t kvol, u3d_stream s) {
-  U3D_REQUIRE(w_nmajor && w_packed && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
-  k_halo_wpack128<<<u3d_cdiv(kvol * 2048, 256), 256, 0, (hipStream_t)s>>>((const u16*)w_nmajor, (u16*)w_packed, nullptr, nullptr, kvol);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-extern "C" int32_t u3d_subm_halo_wpack128_batched(const void* const* srcs_dev, void* const* dsts_dev, int32_t n, int32_t kvol, u3d_stream s) {
-  U3D_REQUIRE(srcs_dev && dsts_dev && n >= 0 && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
-  if (n == 0) return U3D_OK;
-  k_halo_wpack128<<<dim3(u3d_cdiv(kvol * 2048, 256), n), 256, 0, (hipStream_t)s>>>(nullptr, nullptr, (const u16* const*)srcs_dev, (u16* const*)dsts_dev, kvol);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-extern "C" int32_t u3d_subm_halo_conv128_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                              const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, int32_t krev,
-                                              const void* addend, void* out, double* stats, int32_t max_slots, int32_t kvol,
-                                              u3d_stream s) {
-  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && n_cap > 0 && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
-  const int lds = HL_MAXS * HL_RS * 2;
-  U3D_ALLOW_LDS(k_subm_halo128<false>, lds);
-  k_subm_halo128<false><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev, n_cap,
-                                                                     krev, (const u16*)addend, (u16*)out, stats,
-                                                                     (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS, kvol);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-extern "C" int32_t u3d_subm_halo_conv128_affine_bf16(const void* in, const void* w_packed, const int32_t* tile_rows, const uint16_t* loc,
-                                                     const int32_t* tile_cnt, const int32_t* n_dev, int32_t n_cap, const void* addend,
-                                                     void* out, const float* shift, int32_t relu, int32_t max_slots, int32_t kvol,
-                                                     u3d_stream s) {
-  U3D_REQUIRE(in && w_packed && tile_rows && loc && tile_cnt && n_dev && out && shift && n_cap > 0 && kvol >= 1 && kvol <= HL_K, U3D_ERR_ARG);
-  const int lds = HL_MAXS * HL_RS * 2;
-  U3D_ALLOW_LDS((k_subm_halo128<true, HlAffine>), lds);
-  k_subm_halo128<true, HlAffine><<<u3d_cdiv(n_cap, HL_T), 256, lds, (hipStream_t)s>>>((const u16*)in, (const u16*)w_packed, tile_rows, loc, tile_cnt, n_dev,
-                                                                           n_cap, 0, (const u16*)addend, (u16*)out, nullptr,
-                                                                           (max_slots > 0 && max_slots < HL_MAXS) ? max_slots : HL_MAXS, kvol,
-                                                                           HlAffine{shift, relu != 0});
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

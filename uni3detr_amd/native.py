@@ -53,6 +53,7 @@ DG_NAMES = _slot_names("U3D_DG_")       # its backward-workspace slots: CLSO, C2
 DecLayerParams = _struct("u3d_declayer_params", "DecLayerParams")
 DecLayerDims = _struct("u3d_declayer_dims", "DecLayerDims")
 WPackDesc = _struct("u3d_wpack_desc", "WPackDesc")
+HaloTables = _struct("u3d_halo_tables", "HaloTables")
 
 _lib = None
 _I3 = C.c_int32 * 3     # the host arrays a few entry points take by pointer: constructors for the call sites
@@ -76,6 +77,8 @@ def lib():
             fn = getattr(l, name)   # AttributeError -> loud failure if a symbol is missing
             fn.restype = res
             fn.argtypes = args
+        if l.u3d_version() < 1:
+            raise U3DError(f"{LIB_PATH} reports ABI version {l.u3d_version()}: rebuild it (python -m uni3detr_amd.build)")
         _lib = l
     return _lib
 
@@ -424,6 +427,8 @@ class SubmHalo:
         self.tile_rows = torch.empty((a.value,), dtype=torch.int32, device=dev)
         self.loc = torch.empty((b.value,), dtype=torch.int16, device=dev)
         self.tile_cnt = torch.empty((t.value,), dtype=torch.int32, device=dev)
+        # what every entry that reads the tables takes (by reference); the tensors above keep the memory alive
+        self.tables = HaloTables(self.tile_rows.data_ptr(), self.loc.data_ptr(), self.tile_cnt.data_ptr(), n_dev.data_ptr(), n_cap, self.kvol)
         rc = lib().u3d_subm_halo_build(_ptr(nbr_fwd), nbr_fwd.shape[1], _ptr(n_dev), n_cap, _ptr(self.tile_rows), _ptr(self.loc),
                                        _ptr(self.tile_cnt), self.kvol, _stream())
         self.ok = rc != U3D_ERR_UNSUPPORTED     # more rows than the LDS row bitmap holds - the caller keeps the table kernels
@@ -440,23 +445,21 @@ def subm_halo_wgrad(x, dy, halo, out=None, max_slots=0):
     wsb = int(lib().u3d_subm_halo_wgrad64_workspace())
     ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
     region = timed_begin()
-    _check(lib().u3d_subm_halo_wgrad64_bf16(_ptr(x), _ptr(dy), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt), _ptr(halo.n_dev),
-                                            halo.n_cap, _ptr(dw), _ptr(ws), wsb, int(max_slots), _stream()), "subm_halo_wgrad64_bf16")
+    _check(lib().u3d_subm_halo_wgrad64_bf16(_ptr(x), _ptr(dy), C.byref(halo.tables), _ptr(dw), _ptr(ws), wsb, int(max_slots), _stream()),
+           "subm_halo_wgrad64_bf16")
     if region is not None:
         timed_end(region, "spconv_wgrad", halo.n_cap, halo.n_cap, 64, 64, 27, halo.nbr, w_bytes=4)
     return dw
 
 
 def subm_halo_wpack(w_nmajor, out=None):
-    """bf16 [27, 64 (out), 64 (reduction)] -> the MFMA fragment order u3d_subm_halo_conv64_bf16 reads (same shape and size)."""
+    """bf16 [27, 64 (out), 64 (reduction)] / [kvol, 128, 128] -> the MFMA fragment order u3d_subm_halo_conv_bf16 reads (same shape and
+    size)."""
     k, c = w_nmajor.shape[0], w_nmajor.shape[1]
     assert w_nmajor.dtype == torch.bfloat16 and w_nmajor.is_contiguous() and w_nmajor.shape[2] == c
     assert (k == 27 and c == 64) or (1 <= k <= 27 and c == 128)
     out = torch.empty_like(w_nmajor) if out is None else out
-    if c == 64:
-        _check(lib().u3d_subm_halo_wpack(_ptr(w_nmajor), _ptr(out), _stream()), "subm_halo_wpack")
-    else:
-        _check(lib().u3d_subm_halo_wpack128(_ptr(w_nmajor), _ptr(out), k, _stream()), "subm_halo_wpack128")
+    _check(lib().u3d_subm_halo_wpack(_ptr(w_nmajor), _ptr(out), c, k, _stream()), "subm_halo_wpack")
     return out
 
 
@@ -474,29 +477,20 @@ def subm_halo_wpack_plan(pairs, device):
 
 
 def subm_halo_wpack_batched(plan):
-    if plan.c == 64:
-        _check(lib().u3d_subm_halo_wpack_batched(_ptr(plan.src), _ptr(plan.dst), plan.n, _stream()), "subm_halo_wpack_batched")
-    else:
-        _check(lib().u3d_subm_halo_wpack128_batched(_ptr(plan.src), _ptr(plan.dst), plan.n, plan.kvol, _stream()), "subm_halo_wpack128_batched")
+    _check(lib().u3d_subm_halo_wpack_batched(_ptr(plan.src), _ptr(plan.dst), plan.n, plan.c, plan.kvol, _stream()), "subm_halo_wpack_batched")
 
 
 def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=False, tag="spconv_fwd", max_slots=0):
-    """64 -> 64 channel, 27-offset SubM conv out of the tile's staged distinct rows (u3d_subm_halo_conv64_bf16).
-    w_packed: subm_halo_wpack of bf16 [27, 64 (out), 64 (reduction)].  -> out, or (out, stats f64 [tiles, 2, 64], 128) with want_stats."""
+    """64 -> 64 channel, 27-offset (or 128 -> 128, <= 27-offset) SubM conv out of the tile's staged distinct rows
+    (u3d_subm_halo_conv_bf16 without a shift).  w_packed: subm_halo_wpack of bf16 [kvol, C (out), C (reduction)].  -> out, or (out, stats f64 [tiles, 2, 64], 128) with want_stats."""
     c = inp.shape[1]
     assert inp.dtype == torch.bfloat16 and c in (64, 128) and tuple(w_packed.shape) == (halo.kvol, c, c) and inp.shape[0] == halo.n_cap
     assert c == 128 or halo.kvol == 27
     out = torch.empty_like(inp)
     stats = torch.empty((halo.tiles, 2, c), dtype=torch.float64, device=inp.device) if want_stats else None
     region = timed_begin()
-    if c == 64:
-        _check(lib().u3d_subm_halo_conv64_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
-                                               _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
-                                               int(max_slots), _stream()), "subm_halo_conv64_bf16")
-    else:
-        _check(lib().u3d_subm_halo_conv128_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
-                                                _ptr(halo.n_dev), halo.n_cap, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
-                                                int(max_slots), halo.kvol, _stream()), "subm_halo_conv128_bf16")
+    _check(lib().u3d_subm_halo_conv_bf16(_ptr(inp), _ptr(w_packed), C.byref(halo.tables), c, int(krev), _ptr(addend), _ptr(out), _ptr(stats),
+                                         None, 0, int(max_slots), _stream()), "subm_halo_conv_bf16")
     if region is not None:
         timed_end(region, tag, halo.n_cap, halo.n_cap, c, c, halo.kvol, halo.nbr)
     return (out, stats, SubmHalo.TILE) if want_stats else out
@@ -504,7 +498,7 @@ def subm_halo_conv(inp, w_packed, halo, krev=False, addend=None, want_stats=Fals
 
 def subm_halo_conv_affine(inp, w_packed, halo, shift, relu, addend=None, max_slots=0, out=None, tag="spconv_fwd"):
     """act(conv(inp) + shift + addend) of a 64 -> 64 / 128 -> 128 SubM conv whose eval-mode BatchNorm is folded into the weights, out
-    of the level's halo tables in one launch (u3d_subm_halo_conv64_affine_bf16 / _conv128_affine_bf16).  w_packed: subm_halo_wpack of
+    of the level's halo tables in one launch (u3d_subm_halo_conv_bf16 with a shift).  w_packed: subm_halo_wpack of
     the FOLDED n-major weights (bn_fold), shift f32 [C], addend bf16 [n, C] or None (the residual block's identity).  Rows at or past
     *halo.n_dev of `out` are left as they are."""
     c = inp.shape[1]
@@ -516,14 +510,8 @@ def subm_halo_conv_affine(inp, w_packed, halo, shift, relu, addend=None, max_slo
         out = torch.empty_like(inp)
     assert out.shape == inp.shape and out.dtype == torch.bfloat16
     region = timed_begin()
-    if c == 64:
-        _check(lib().u3d_subm_halo_conv64_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
-                                                      _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
-                                                      int(max_slots), _stream()), "subm_halo_conv64_affine_bf16")
-    else:
-        _check(lib().u3d_subm_halo_conv128_affine_bf16(_ptr(inp), _ptr(w_packed), _ptr(halo.tile_rows), _ptr(halo.loc), _ptr(halo.tile_cnt),
-                                                       _ptr(halo.n_dev), halo.n_cap, _ptr(addend), _ptr(out), _ptr(shift), int(bool(relu)),
-                                                       int(max_slots), halo.kvol, _stream()), "subm_halo_conv128_affine_bf16")
+    _check(lib().u3d_subm_halo_conv_bf16(_ptr(inp), _ptr(w_packed), C.byref(halo.tables), c, 0, _ptr(addend), _ptr(out), None, _ptr(shift),
+                                         int(bool(relu)), int(max_slots), _stream()), "subm_halo_conv_bf16")
     if region is not None:
         timed_end(region, tag, halo.n_cap, halo.n_cap, c, c, halo.kvol, halo.nbr)
     return out
@@ -1022,7 +1010,8 @@ WGRAD_KERNELS = ("none", "conv_in", "narrow", "glds8_256", "glds_256", "glds_128
 
 def igemm_wgrad_plan(n_out, cin, cout, kvol, has_nbr, out_oik=False, out_layout=None):
     """(kernel family, tile, nsplit, workspace bytes) u3d_igemm_wgrad_bf16 takes for the shape; None when it does not serve it.
-    out_layout (0 / 1 / 2, see u3d_hip.h) overrides out_oik (= layout 1)."""
+    out_layout (0 / 1 / 2, see u3d_hip.h) overrides out_oik (= layout 1).  (u3d_igemm_wgrad_bf16_workspace answers only the bytes: the
+    query of a binder that does not want the plan; this package does not call it.)"""
     k, tile, ns, ws = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
     layout = (1 if out_oik else 0) if out_layout is None else int(out_layout)
     if lib().u3d_igemm_wgrad_plan(n_out, cin, cout, kvol, int(bool(has_nbr)), layout, C.byref(k), C.byref(tile), C.byref(ns),
@@ -1143,27 +1132,18 @@ def bn_forward_stats(x, n_dev, eps, momentum, running_mean=None, running_var=Non
 
 def bn_apply(x, mean, invstd, gamma, beta, residual, relu, n_dev, row_map=None, post_add=None, want_planes=False):
     """row_map (int32 [n], a bijection): row r of x lands in row row_map[r] of y (see include/u3d_hip.h).
-    want_planes (f32 rows): -> (y, planes) with planes bf16 [2 * n, c] = split_rows(y) written by the same pass (u3d_bn_apply_planes), or
-    (y, None) for a shape the fused pass does not take."""
+    want_planes (f32 rows): -> (y, planes) with planes bf16 [2 * n, c] = split_rows(y) written by the same pass, or (y, None) for a
+    shape the fused pass does not take."""
     n, c = x.shape
     y = torch.empty_like(x)
-    if want_planes:
-        planes = None
-        if x.dtype == torch.float32 and x.is_cuda:
-            planes = torch.empty((2 * n, c), dtype=torch.bfloat16, device=x.device)
-            rc = lib().u3d_bn_apply_planes(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), int(relu), _ptr(y),
-                                           _ptr(planes), _ptr(n_dev), n, c, _ptr(row_map), _ptr(post_add), _stream())
-            if rc == 0:
-                return y, planes
-            if rc != U3D_ERR_UNSUPPORTED:
-                _check(rc, "bn_apply_planes")
-            planes = None
-        _check(lib().u3d_bn_apply(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), int(relu),
-                                  _ptr(y), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _ptr(post_add), _stream()), "bn_apply")
-        return y, None
-    _check(lib().u3d_bn_apply(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), int(relu),
-                              _ptr(y), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _ptr(post_add), _stream()), "bn_apply")
-    return y
+    planes = torch.empty((2 * n, c), dtype=torch.bfloat16, device=x.device) if want_planes and x.dtype == torch.float32 else None
+    for planes in (planes, None):       # one retry without the planes when the fused pass does not take the shape
+        rc = lib().u3d_bn_apply(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), int(relu), _ptr(y), _ptr(planes),
+                                _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _ptr(post_add), _stream())
+        if planes is None or rc != U3D_ERR_UNSUPPORTED:
+            break
+    _check(rc, "bn_apply")
+    return (y, planes) if want_planes else y
 
 
 def bn_bwd_stats(dy, y, x, mean, invstd, relu, n_dev, gamma=None, beta=None, row_map=None, want_f32=False):
@@ -1179,25 +1159,18 @@ def bn_bwd_stats(dy, y, x, mean, invstd, relu, n_dev, gamma=None, beta=None, row
 
 
 def bn_bwd_apply(dy, y, x, mean, invstd, gamma, sums, relu, n_dev, want_dres, beta=None, row_map=None, want_planes=False):
-    """want_planes (f32 rows): -> (dx, dres, planes of dx or None) - u3d_bn_bwd_apply_planes."""
+    """want_planes (f32 rows): -> (dx, dres, planes of dx or None)."""
     n, c = x.shape
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    if want_planes:
-        if x.dtype == torch.float32 and x.is_cuda:
-            planes = torch.empty((2 * n, c), dtype=torch.bfloat16, device=x.device)
-            rc = lib().u3d_bn_bwd_apply_planes(_ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(sums), int(relu),
-                                               _ptr(dx), _ptr(dres), _ptr(planes), _ptr(n_dev), n, c, _ptr(row_map), _stream())
-            if rc == 0:
-                return dx, dres, planes
-            if rc != U3D_ERR_UNSUPPORTED:
-                _check(rc, "bn_bwd_apply_planes")
-        _check(lib().u3d_bn_bwd_apply(_ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(sums), int(relu),
-                                      _ptr(dx), _ptr(dres), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _stream()), "bn_bwd_apply")
-        return dx, dres, None
-    _check(lib().u3d_bn_bwd_apply(_ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(sums), int(relu),
-                                  _ptr(dx), _ptr(dres), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _stream()), "bn_bwd_apply")
-    return dx, dres
+    planes = torch.empty((2 * n, c), dtype=torch.bfloat16, device=x.device) if want_planes and x.dtype == torch.float32 else None
+    for planes in (planes, None):       # as bn_apply
+        rc = lib().u3d_bn_bwd_apply(_ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(sums), int(relu),
+                                    _ptr(dx), _ptr(dres), _ptr(planes), _ptr(n_dev), n, c, dtype_code(x), _ptr(row_map), _stream())
+        if planes is None or rc != U3D_ERR_UNSUPPORTED:
+            break
+    _check(rc, "bn_bwd_apply")
+    return (dx, dres, planes) if want_planes else (dx, dres)
 
 
 def to_dense(feat, coors, n_dev, batch, dims):
@@ -1688,8 +1661,8 @@ def tap_gather_sum(p, nbr, n_dev, n, c, kvol, addend=None):
     out = torch.empty((n, c), dtype=p.dtype, device=p.device)
     if addend is not None:
         assert addend.shape == out.shape and addend.dtype == out.dtype and addend.is_contiguous()
-    _check(lib().u3d_tap_gather_sum_add(_ptr(p), _ptr(nbr), nbr.shape[1], _ptr(n_dev), n, c, kvol, dtype_code(p), _ptr(addend), _ptr(out),
-                                        _stream()), "tap_gather_sum")
+    _check(lib().u3d_tap_gather_sum(_ptr(p), _ptr(nbr), nbr.shape[1], _ptr(n_dev), n, c, kvol, dtype_code(p), _ptr(addend), _ptr(out), _stream()),
+           "tap_gather_sum")
     return out
 
 
@@ -1941,7 +1914,7 @@ def decoder_layer_slots(m, ncls, code, dtype=torch.bfloat16):
     if r is None:
         so = (C.c_int64 * (len(DS_NAMES) + 1))()
         go = (C.c_int64 * (len(DG_NAMES) + 1))()
-        _check(lib().u3d_decoder_layer_slots_dt(m, ncls, code, dt_code(dtype), so, go), "decoder_layer_slots")
+        _check(lib().u3d_decoder_layer_slots(m, ncls, code, dt_code(dtype), so, go), "decoder_layer_slots")
         r = ({**{n: int(so[i]) for i, n in enumerate(DS_NAMES)}, "_total": int(so[len(DS_NAMES)])},
              {**{n: int(go[i]) for i, n in enumerate(DG_NAMES)}, "_total": int(go[len(DG_NAMES)])})
         _SLOT_CACHE[key] = r
@@ -1956,7 +1929,7 @@ def slot_view(buf, off, rows, cols, dtype):
 
 def decoder_blocks(m, dtype=torch.bfloat16):
     """workgroups of the row-chain kernels = rows of every LayerNorm partial matrix"""
-    return int(lib().u3d_decoder_layer_blocks_dt(m, dt_code(dtype)))
+    return int(lib().u3d_decoder_layer_blocks(m, dt_code(dtype)))
 
 
 def decoder_rows(m, dtype=torch.bfloat16):
@@ -1978,7 +1951,7 @@ def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save, row_waves
     reg = torch.empty((mp, code), dtype=torch.float32, device=dev)
     cls = torch.empty((mp, ncls), dtype=torch.float32, device=dev)
     iou = torch.empty((mp,), dtype=torch.float32, device=dev)
-    _check(lib().u3d_decoder_layer_fwd_nw(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
+    _check(lib().u3d_decoder_layer_fwd(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
                                           _ptr(x_out), _ptr(xc_out), _ptr(reg), _ptr(cls), _ptr(iou), _ptr(save), save.numel(),
                                           int(row_waves), _stream()), "decoder_layer_fwd")
     return x_out[:m], xc_out[:m], reg[:m], cls[:m], iou[:m]
@@ -1994,7 +1967,7 @@ def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, d
     mp = decoder_rows(m, torch.bfloat16 if dims.dtype == DT_BF16 else torch.float32)
     dx = torch.empty((mp, 256), dtype=torch.float32, device=ref.device)
     dref = torch.empty((mp, 3), dtype=torch.float32, device=ref.device) if dims.need_dref else None
-    _check(lib().u3d_decoder_layer_bwd_nw(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
+    _check(lib().u3d_decoder_layer_bwd(C.byref(params), C.byref(dims), _ptr(x), _ptr(xc), _ptr(ref), _ptr(value_rows), _ptr(rng),
                                           _ptr(xc_out), _ptr(save), _ptr(dx_out), _ptr(dreg), _ptr(dcls), _ptr(diou), _ptr(dx),
                                           _ptr(rec), _ptr(dref), _ptr(grad), grad.numel(), int(row_waves), _stream()),
            "decoder_layer_bwd")
@@ -2018,7 +1991,7 @@ def mha_fwd(qk, v, nq, p_attn=0.0, layer=0, rng=None):
     assert qk.dtype == v.dtype and qk.is_contiguous() and v.is_contiguous()
     o = torch.empty((m, 256), dtype=qk.dtype, device=qk.device)
     lse = torch.empty((m, 8), dtype=torch.float32, device=qk.device)
-    _check(lib().u3d_mha_fwd_dt(_ptr(qk), _ptr(v), m, nq, p_attn, layer, _ptr(rng), _ptr(o), _ptr(lse), dt_code(qk.dtype), _stream()),
+    _check(lib().u3d_mha_fwd(_ptr(qk), _ptr(v), m, nq, p_attn, layer, _ptr(rng), _ptr(o), _ptr(lse), dt_code(qk.dtype), _stream()),
            "mha_fwd")
     return o, lse
 
@@ -2027,17 +2000,13 @@ def mha_bwd(qk, v, o, d_o, lse, nq, p_attn=0.0, layer=0, rng=None):
     m = qk.shape[0]
     assert qk.dtype == v.dtype == o.dtype == d_o.dtype
     dqk, dv = torch.empty_like(qk), torch.empty_like(v)
-    _check(lib().u3d_mha_bwd_dt(_ptr(qk), _ptr(v), _ptr(o), _ptr(d_o), _ptr(lse), m, nq, p_attn, layer, _ptr(rng), _ptr(dqk), _ptr(dv),
+    _check(lib().u3d_mha_bwd(_ptr(qk), _ptr(v), _ptr(o), _ptr(d_o), _ptr(lse), m, nq, p_attn, layer, _ptr(rng), _ptr(dqk), _ptr(dv),
                                 dt_code(qk.dtype), _stream()), "mha_bwd")
     return dqk, dv
 
 
 def wpack(descs_dev, count, max_elems, dtype=torch.bfloat16):
     _check(lib().u3d_wpack(_ptr(descs_dev), count, max_elems, dt_code(dtype), _stream()), "wpack")
-
-
-def wpack_bf16(descs_dev, count, max_elems):
-    wpack(descs_dev, count, max_elems, torch.bfloat16)
 
 
 def dropout_mask(rng, layer, site, n, p, cols=0):
@@ -2419,7 +2388,9 @@ def det_tail(prob, fused, boxes, max_num, center_range, score_threshold=None, mo
     """The decode selection + post-processing of every scene in one call, no host sync (csrc/det_tail.hip; include/u3d_hip.h states
     the per-scene semantics).  prob / fused f32 [B,Q,C], boxes f32 [B,Q,7|9] gravity centre, center_range f32 [6] device tensor,
     score_thr f32 [C] device tensor or None, mode DET_TAIL_NONE / _NMS / _DECODE / _SOFT_NMS (soft_sigma, soft_prune; the scores are the
-    decayed ones) / _MERGE (nms_thr is the overlap threshold; scene-wide score order) -> DetBatch with K = min(max_num, Q*C)."""
+    decayed ones) / _MERGE (nms_thr is the overlap threshold; scene-wide score order) -> DetBatch with K = min(max_num, Q*C).
+    All five modes go through u3d_det_tail_pp; u3d_det_tail / u3d_det_tail_workspace, the library's earlier three-mode signature kept
+    for its other binders, are not called from here."""
     B, Q, Cn = prob.shape
     dim = boxes.shape[-1]
     dev = prob.device

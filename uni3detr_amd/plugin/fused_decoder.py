@@ -10,7 +10,7 @@ ref: projects/mmdet3d_plugin/models/utils/uni3detr_transformer.py:145-212 (decod
 models/dense_heads/uni3detr_head.py:367-387, 470-490 (branches; the box decode stays in Uni3DETRHead.forward).
 
 The module layout is the registry's (plugin/transformer.py, plugin/head.py): this file only gathers the parameters, keeps bf16
-copies of the weights (one refresh launch per step: u3d_wpack_bf16) and turns the kernels' gradient slots into parameter
+copies of the weights (one refresh launch per step: u3d_wpack) and turns the kernels' gradient slots into parameter
 gradients through the same deferred / batched mechanism the layer-by-layer path uses (plugin/param_grads.py).
 """
 import os

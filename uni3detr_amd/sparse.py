@@ -203,7 +203,7 @@ _SPLIT = [False]
 # outlives the forward that made it.  (Writing the planes from the BatchNorm apply that produces the rows - one pass less per layer -
 # was built and measured time-neutral, 216.0 vs 217.2 scenes/s: the extra 4 B / element of stores cost what the saved read gains.)
 _PLANES = {}
-_PLANES_BWD = {}          # planes of a gradient tensor produced together with it (u3d_bn_bwd_apply_planes); popped by their one consumer
+_PLANES_BWD = {}          # planes of a gradient tensor produced together with it (u3d_bn_bwd_apply with planes); popped by their one consumer
 BN_PLANES = True          # test-only module attribute: False = every tensor is split by its own u3d_split_rows_f32 pass (the A/B formulation)
 
 
@@ -701,7 +701,7 @@ class _BNRows(torch.autograd.Function):
             assert relu and residual is None and post_add.shape == x.shape and post_add.dtype == x.dtype
             post_add = post_add.contiguous()
         # split-bf16 scope, f32 rows: the pass also writes y's hi / lo bf16 planes for the convolution that reads y next, and the backward
-        # will write the planes of dx for the convolution that produced x (u3d_bn_apply_planes / u3d_bn_bwd_apply_planes)
+        # will write the planes of dx for the convolution that produced x (the planes argument of u3d_bn_apply / u3d_bn_bwd_apply)
         ctx.planes = bool(BN_PLANES and _SPLIT[0] and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 16 == 0)
         if ctx.planes:
             y, ypl = nv.bn_apply(x, mean, invstd, g32, b32, residual, relu, n_dev, row_map, post_add, want_planes=True)

@@ -481,7 +481,7 @@ class TrainStep:
     def _note_missing(self, lo, hi):
         """Parameters that received no gradient keep weights AND moments untouched, as torch.optim.AdamW skips `.grad is None`
         (the reference trains with find_unused_parameters=True).  The set is fixed by the model's structure: recorded once, from the
-        first eager backward, as a per-64-element skip mask for u3d_adamw_step_state."""
+        first eager backward, as a per-64-element skip mask for u3d_adamw_step_hold."""
         if not self.flat_update or self._skip_known:
             return
         seen, miss = self._seen_ranges, self._missing_idx
