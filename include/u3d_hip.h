@@ -651,6 +651,21 @@ int32_t u3d_det_tail_pp(const float* prob, const float* fused, const float* boxe
                         const float* score_thr, int32_t num_thr, float soft_sigma, float soft_prune, float* out_boxes, float* out_scores,
                         int32_t* out_labels, int32_t* out_count, int32_t* out_off, void* workspace, int64_t workspace_bytes, u3d_stream s);
 
+/* The validity gate of a captured inference step, applied in place to the outputs of u3d_det_tail_pp (boxes f32 [B,max_num,box_dim],
+ * scores f32 [B,max_num], labels int32 [B,max_num], count int32 [B], off int32 [B+1]; max_num is the padded row count K of those
+ * tensors).  flag: one device float, non-zero when the forward behind the detections must not be trusted (a sparse level over its
+ * capacity, an FPS time-out, a scene cut by u3d_batch_ingest: what u3d_capacity_flag and the ingest leave); n_live: one device int32,
+ * the number of leading scenes that carry real data (the rest are padding).
+ *   valid[0] = (flag[0] == 0), int32;
+ *   scene b is dead when flag[0] != 0 (a NaN counts as raised) or b >= n_live[0]: its rows [0, count[b]) are zeroed, count[b] = 0;
+ *   off = exclusive scan of the gated counts.
+ * Rows past count[b] are zero on input and stay so: the gated bytes are a function of the inputs alone.  A count outside
+ * [0, max_num] is read as clamped to it.  Two launches, no atomics on global memory, no allocation, no synchronisation.
+ * U3D_ERR_ARG: a null pointer, batch or max_num <= 0, box_dim not 7 or 9; U3D_ERR_UNSUPPORTED: batch > 65535 or
+ * max_num > U3D_DET_TAIL_MAX_K. */
+int32_t u3d_det_gate(const float* flag, const int32_t* n_live, float* boxes, float* scores, int32_t* labels, int32_t* count, int32_t* off,
+                     int32_t batch, int32_t max_num, int32_t box_dim, int32_t* valid, u3d_stream s);
+
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad

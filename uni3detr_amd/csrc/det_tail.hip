@@ -35,6 +35,8 @@
 //                pin -; boxes gathered (z -= dz * 0.5 in two rounded f32 steps unless the caller asks for the coder's gravity centres),
 //                rows past the count zeroed, count written.
 //   k_dt_offsets out_off = exclusive scan of out_count (the det_off layout of u3d_eval_* / u3d_tta_merge).
+//   k_dt_gate    u3d_det_gate, for a captured inference step: empties the scenes of a finished DetBatch that must not be read (a raised
+//                validity flag, or a padded scene at or past *n_live) and writes the flag as an int32; k_dt_offsets then rewrites off.
 // No atomics on global memory (LDS counters are integers: any order gives the same sum), so two runs give the same bytes.
 // Limits: K = min(max_num, nq * num_classes) <= 8192, box_dim 7 or 9, nq * num_classes < 2^31, num_classes <= 65536, in every mode.
 // Non-finite scores are outside the contract (torch orders NaN above everything; here a NaN orders by its bit pattern).
@@ -48,6 +50,7 @@
 #define DT_LDS_CAP U3D_DET_TAIL_LDS_CAP
 #define DT_NMS_THREADS 256
 #define DT_PP_THREADS 256                  /* k_dt_soft, k_dt_merge */
+#define DT_GATE_THREADS 256
 #define DT_ORDER_SCORE 1                /* k_dt_select: label, fused score descending, compacted position */
 #define DT_ORDER_POS 2                  /* label, compacted position */
 #define DT_POS_BITS 13                 /* a position < DT_MAX_K = 2^13 */
@@ -493,6 +496,38 @@ __global__ __launch_bounds__(64) void k_dt_offsets(const int* __restrict__ count
     carry += __shfl(incl, 63, 64);
   }
   if (lane == 0) off[batch] = carry;
+}
+
+// u3d_det_gate, one workgroup per scene: a scene is dead when the flag is raised (any non-zero value, a NaN too) or it lies at or past
+// *n_live.  A dead scene's rows [0, count[b]) are zeroed - the rows behind them are zero already (k_dt_emit) - and its count becomes 0,
+// so a gated DetBatch keeps "rows past count[b] are zero".  Every thread reads count[b] before thread 0 rewrites it (the barrier).
+__global__ __launch_bounds__(DT_GATE_THREADS) void k_dt_gate(const float* __restrict__ flag, const int* __restrict__ n_live, int K, int dim,
+                                                             float* __restrict__ boxes, float* __restrict__ scores,
+                                                             int* __restrict__ labels, int* __restrict__ count, int* __restrict__ valid) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const bool ok = flag[0] == 0.f;
+  if (b == 0 && tid == 0) valid[0] = ok ? 1 : 0;
+  if (ok && b < n_live[0]) return;                             // uniform over the workgroup
+  const int c = min(max(count[b], 0), K);
+  __syncthreads();
+  const long long bk = (long long)b * K;
+  for (int i = tid; i < c * dim; i += DT_GATE_THREADS) boxes[bk * dim + i] = 0.f;
+  for (int i = tid; i < c; i += DT_GATE_THREADS) {
+    scores[bk + i] = 0.f;
+    labels[bk + i] = 0;
+  }
+  if (tid == 0) count[b] = 0;
+}
+
+extern "C" int32_t u3d_det_gate(const float* flag, const int32_t* n_live, float* boxes, float* scores, int32_t* labels, int32_t* count,
+                                int32_t* off, int32_t batch, int32_t max_num, int32_t box_dim, int32_t* valid, u3d_stream s) {
+  U3D_REQUIRE(flag && n_live && boxes && scores && labels && count && off && valid && batch > 0 && max_num > 0 &&
+              (box_dim == 7 || box_dim == 9), U3D_ERR_ARG);
+  U3D_REQUIRE(batch <= 65535 && max_num <= DT_MAX_K, U3D_ERR_UNSUPPORTED);
+  hipLaunchKernelGGL(k_dt_gate, dim3(batch), dim3(DT_GATE_THREADS), 0, s, flag, n_live, max_num, box_dim, boxes, scores, labels, count, valid);
+  hipLaunchKernelGGL(k_dt_offsets, dim3(1), dim3(64), 0, s, count, batch, off);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
 }
 
 static inline size_t dt_align(size_t b) { return (b + 255) & ~(size_t)255; }

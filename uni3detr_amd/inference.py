@@ -43,6 +43,9 @@ output channel from the f32 masters, activations per layer under a power-of-two 
 forward (fp8_state() / load_fp8_state() carry it).  `fp8_layers` names the pairs on that route - those the fp8 launch plan serves and that
 measured faster than bf16 -, `fp8_skipped` the rest with the reason.  A forward before calibration raises.  INTEGRATION.md N.
 
+InferenceStep(inf, batch_size=B, point_capacity=P) replays the folded forward and the batched tail of an InferenceModel as one hipGraph
+over static, capacity-sized buffers, with a device-side validity gate (u3d_det_gate) and an eager fallback.  INTEGRATION.md O.
+
 Numerics: not bit-identical to conv + u3d_bn_apply.  Folded: bf16(w * scale) once, output rounded once.  Unfolded: bf16(w), conv
 output rounded to bf16, y rounded.  Both are a few bf16 roundings of the same real number (tests/test_bn_fold_gpu.py holds the folded
 error within 2 x the unfolded one against a float64 restatement).
@@ -396,3 +399,223 @@ class InferenceModel:
     def aug_test(self, points, img_metas, **kwargs):
         with self.scope():
             return self.model.aug_test(points, img_metas, **kwargs)
+
+
+class InferenceStep:
+    """The folded forward and the batched tail of an InferenceModel as ONE hipGraph over static buffers: a batch costs one replay
+    instead of a few hundred enqueued launches.
+
+        step = InferenceStep(inf, batch_size=B, point_capacity=P)
+        counts, caps = step.capture(batches=[pts_a, pts_b, ...], margin=1.25, warmup=3)
+        det = step.run(points)        # native.DetBatch in the graph's static buffers; step.valid (int32 [1]) says whether to read it
+        res = step.results(points)    # simple_test_batched's list of dicts on the host; the eager path when the replay was invalid
+        step.valid, step.fallbacks, step.overflows()
+
+    Inputs are TrainStep's capacity mode without GT: `cat` f32 [B * P, F] of which scene_off[B] rows are live, lens = [P] * B.  `points`
+    is a list of 1 .. B tensors [n <= P, F] (fewer than B: padded with copies of scene 0, which the gate empties again) or the dict a
+    DevicePipeline returns (exactly B scenes; loaded by u3d_batch_ingest, no host read).  The strided sparse levels are sized by
+    capture() from sample batches; static shapes are switched on only inside the step's own forward, so `inf.simple_test*` keep
+    running exact-size next to it.
+
+    Validity: one device flag = levels over their capacity (native.capacity_flag) + the several-workgroup FPS time-out + scenes the
+    ingest cut to P.  u3d_det_gate turns it into `valid` and empties every scene of an invalid replay, so nothing wrong can be read by
+    mistake.  Nothing is truncated silently and nothing is re-captured automatically: results() re-runs an invalid batch eagerly and
+    counts it in `fallbacks`; capture() may be called again with that batch among the samples.
+
+    Limits: an InferenceModel on one device, hard voxelization, B fixed, no aug_test.  An empty live scene gives NaN queries."""
+
+    def __init__(self, inf, batch_size, point_capacity):
+        if not isinstance(inf, InferenceModel):
+            raise TypeError(f"InferenceStep captures an InferenceModel, not {type(inf).__name__}: wrap the model first")
+        model = inf.model
+        if getattr(model, "dynamic_voxelization", False):
+            raise NotImplementedError("InferenceStep serves hard voxelization only: DynamicSimpleVFE sizes its voxel list by a host read "
+                                      "in eval mode, and this model has dynamic_voxelization=True")
+        B, P = int(batch_size), int(point_capacity)
+        if B < 1:
+            raise ValueError(f"InferenceStep(batch_size={batch_size}): at least one scene")
+        if P < 1:
+            raise ValueError(f"InferenceStep(point_capacity={point_capacity}): at least one point per scene")
+        self.inf, self.model = inf, model
+        self.batch_size, self.point_capacity = B, P
+        self.feat = int(model.pts_voxel_encoder.num_features)
+        self.fallbacks = 0
+        self.pts = self.valid = self.det = self.head_outs = None
+        self._graph = self._caps = None
+
+    # ---- static buffers ---------------------------------------------------------------------------------------------------
+    def _alloc(self):
+        """TrainStep._alloc_capacity_buffers without the GT: one spare row behind `cat` (an empty LAST scene makes the FPS gather read
+        the row at scene_off[B]).  Allocated once: a graph keeps these addresses."""
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("InferenceStep: the model is not on a GPU")
+        B, P = self.batch_size, self.point_capacity
+        self.dev = dev
+        self.pts = dict(cat=torch.zeros((B * P + 1, self.feat), dtype=torch.float32, device=dev)[:B * P],
+                        scene_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), lens=[P] * B)
+        self._ingest_flag = torch.zeros(1, dtype=torch.float32, device=dev)     # the bound batch had a scene cut to P
+        self._ingest_over = torch.zeros(2, dtype=torch.int32, device=dev)       # such batches so far (overflows())
+        self._n_live = torch.full((1,), B, dtype=torch.int32, device=dev)
+        self._flag = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._fps_err = nv.fps_err_buffer(dev)
+        self.valid = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _bind(self, points):
+        """Load a batch into the static buffers on the current stream -> the number of live scenes."""
+        if self.pts is None:
+            self._alloc()
+        B, P, cat = self.batch_size, self.point_capacity, self.pts["cat"]
+        if isinstance(points, dict):
+            if "sweeps" in points:
+                raise ValueError("InferenceStep: the batch still carries batch['sweeps'] - run the pipeline's LoadPointsFromMultiSweeps first")
+            pts, off, cnt = points["points"], points["scene_off"], points.get("count")
+            if not all(t is None or (torch.is_tensor(t) and t.device == cat.device) for t in (pts, off, cnt)):
+                raise ValueError(f"InferenceStep: every tensor of the batch must live on {cat.device}")
+            if pts.dim() != 2 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[1] != cat.shape[1]:
+                raise ValueError(f"InferenceStep: points must be contiguous float32 [n, {cat.shape[1]}], got {pts.dtype} {tuple(pts.shape)}")
+            if off.numel() != B + 1:
+                raise ValueError(f"InferenceStep: {off.numel() - 1} scenes, the step was built for {B}")
+            for t, n, what in ((off, B + 1, "scene_off"), (cnt, B, "count")):
+                if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
+                    raise ValueError(f"InferenceStep: {what} must be a contiguous int32 tensor of {n} elements")
+            self._ingest_flag.zero_()
+            nv.batch_ingest(pts, off, cnt, P, cat, self.pts["scene_off"], self._ingest_flag, overflow=self._ingest_over)
+            self._n_live.fill_(B)
+            return B
+        points = list(points)
+        n = len(points)
+        if not 1 <= n <= B:
+            raise ValueError(f"InferenceStep: {n} scenes, the step was built for 1 .. {B}")
+        if any(p.dim() != 2 or int(p.shape[1]) != cat.shape[1] for p in points):
+            raise ValueError(f"InferenceStep: points must have {cat.shape[1]} columns")
+        if any(p.device != cat.device for p in points):
+            raise ValueError(f"InferenceStep: every scene must live on {cat.device}")
+        if max(int(p.shape[0]) for p in points) > P:
+            raise ValueError(f"InferenceStep: a scene of {max(int(p.shape[0]) for p in points)} points exceeds point_capacity {P}")
+        packed = self.model.pack_points(points + [points[0]] * (B - n))        # the last batch of a dataset: padded, gated away again
+        cat[:packed["cat"].shape[0]].copy_(packed["cat"])
+        self.pts["scene_off"].copy_(packed["scene_off"])
+        self._ingest_flag.zero_()
+        self._n_live.fill_(n)
+        return n
+
+    # ---- the forward (same code eager or captured) ----------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _static(self):
+        """Capacity-sized levels, device-side counts and this step's FPS time-out record - for the step's own forward only."""
+        m, enc = self.model, self.model.pts_middle_encoder
+        prev = m.static_shapes, enc.level_capacities, m.fps_err
+        m.static_shapes, enc.level_capacities, m.fps_err = True, self._caps, self._fps_err
+        try:
+            yield
+        finally:
+            m.static_shapes, enc.level_capacities, m.fps_err = prev
+
+    def _fps_can_time_out(self):
+        """TrainStep._fps_can_time_out for eval: only sets above native.FPS_REG_MAX points run on workgroups that wait for each other."""
+        m = self.model
+        if getattr(m, "fps_max_wg", 0) == 1:
+            return False
+        return max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])) > nv.FPS_REG_MAX
+
+    @torch.no_grad()
+    def _forward(self):
+        """A straight line on one stream (extract_pts_feat would fork the FPS onto a side stream: parallel branches in a graph)."""
+        m = self.model
+        with self.inf.scope(), self._static():
+            v = m.stage_voxelize(self.pts)
+            fps = m.stage_fps(v)
+            feat = m.stage_features(v)
+            self.head_outs = m.pts_bbox_head(feat, None, fps)
+            self.det = m.pts_bbox_head.get_bboxes_batched(self.head_outs, None)
+            # the three sources of TrainStep._stage1_head's hold flag
+            enc = m.pts_middle_encoder
+            cnts, cps = list(enc.last_level_counts[1:1 + len(self._caps)]), list(self._caps)
+            if self._fps_can_time_out():
+                cnts, cps = cnts + [self._fps_err[:1]], cps + [0]
+            if cnts:
+                nv.capacity_flag(cnts, cps, self._flag)
+            else:
+                self._flag.zero_()
+            self._flag.add_(self._ingest_flag)
+            nv.det_gate(self.det, self._flag, self._n_live, self.valid)
+            self.det.valid = self.valid
+
+    def _drop_outputs(self):
+        """Drop every reference to an eager iteration's outputs BEFORE capturing (TrainStep._drop_step_state)."""
+        import gc
+        self.det = self.head_outs = None
+        self.model.pts_middle_encoder.last_level_counts = []
+        dec = getattr(getattr(self.model.pts_bbox_head, "transformer", None), "decoder", None)
+        if dec is not None:
+            dec._reg_outputs = dec._states_c = dec._cls_outputs = dec._iou_outputs = dec._coord_outputs = dec._refs_sig = None
+        gc.collect()
+        torch.cuda.synchronize()
+
+    def capture(self, batches, margin=1.25, warmup=3):
+        """Size the strided sparse levels from exact-size eager forwards over `batches` (each what run() takes; the largest count per
+        level x margin, rounded up to a multiple of 256 - TrainStep.measure_capacities), warm up, capture.  -> (counts, caps).  May be
+        called again, e.g. with a batch that overflowed added: the previous graph is dropped."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("InferenceStep.capture: at least one sample batch")
+        if int(warmup) < 1:
+            raise ValueError("InferenceStep.capture: at least one warm-up iteration (one-time initialisation must not fall into the capture)")
+        self._graph = None
+        if self.pts is not None:
+            self._drop_outputs()
+        enc = self.model.pts_middle_encoder
+        counts = None
+        for b in batches:
+            self._bind(b)
+            off = self.pts["scene_off"].tolist()
+            exact = dict(cat=self.pts["cat"][:off[-1]], scene_off=self.pts["scene_off"], lens=[off[i + 1] - off[i] for i in range(len(off) - 1)])
+            with torch.no_grad(), self.inf.scope():       # the counts come from the encoder: no FPS, no head
+                self.model.stage_features(self.model.stage_voxelize(exact))
+            c = [int(c.item()) for c in enc.last_level_counts]
+            counts = c if counts is None else [max(a, b_) for a, b_ in zip(counts, c)]
+        self._caps = [((int(c * margin) + 255) // 256) * 256 for c in counts[1:]]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):                      # static-shape eager warm-up on the capture stream
+                self._forward()
+        torch.cuda.current_stream().wait_stream(s)
+        self._drop_outputs()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+            self._forward()
+        torch.cuda.synchronize()
+        self._graph = g
+        return counts, list(self._caps)
+
+    # ---- use --------------------------------------------------------------------------------------------------------------
+    def run(self, points):
+        """Load `points` and replay: -> the native.DetBatch whose tensors are the graph's static outputs (`det.valid` is `step.valid`,
+        device int32 [1]: 1 = read it, 0 = every scene was emptied).  THE NEXT run() OVERWRITES THEM - copy what must outlive it.  No
+        host read, no allocation outside the graph's pool and no synchronisation for a packed dict; a list costs the host-sized copy of
+        pack_points.  `step.head_outs` are the head's raw outputs of the same replay."""
+        if self._graph is None:
+            raise RuntimeError("InferenceStep.run: capture() first")
+        self._bind(points)
+        self._graph.replay()
+        return self.det
+
+    def results(self, points, img_metas=None):
+        """run() and the one read of the tail (and of `valid` with it) -> simple_test_batched's list of dicts on the host, one per
+        live scene.  An invalid replay is re-run through inf.simple_test_batched (eager, exact-size) and counted in `fallbacks`."""
+        det = self.run(points)
+        n = self.batch_size if isinstance(points, dict) else len(points)
+        host, valid = det.cpu(), int(self.valid.cpu()[0])
+        if valid:
+            return [dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in host.to_list()[:n]]
+        self.fallbacks += 1
+        if isinstance(points, dict):
+            from .datapath import unpack_batch
+            points = unpack_batch({k: points[k] for k in ("points", "scene_off", "count") if k in points})[0]
+        return self.inf.simple_test_batched(img_metas, list(points))
+
+    def overflows(self):
+        """Packed batches the ingest had to cut to point_capacity so far (their replays were invalid).  One small device-to-host read."""
+        return 0 if self.pts is None else int(self._ingest_over.sum().item())

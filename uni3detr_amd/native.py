@@ -2421,3 +2421,21 @@ def det_tail(prob, fused, boxes, max_num, center_range, score_threshold=None, mo
                                  _ptr(out.boxes), _ptr(out.scores), _ptr(out.labels), _ptr(out.count), _ptr(out.off), _ptr(ws), wsb,
                                  _stream()), "det_tail")
     return out
+
+
+def det_gate(det, flag, n_live, valid=None):
+    """The validity gate of a captured inference step on a finished DetBatch, in place (u3d_det_gate; two launches, no host sync):
+    flag one device float (non-zero: the forward is not to be trusted), n_live one device int32 (scenes at or past it are padding)
+    -> valid int32 [1] = (flag == 0); a dead scene's rows are zeroed and its count is 0, det.off is the scan of the gated counts."""
+    B, K, dim = det.boxes.shape
+    dev = det.boxes.device
+    assert flag.dtype == torch.float32 and flag.numel() == 1 and n_live.dtype == torch.int32 and n_live.numel() == 1
+    assert det.boxes.dtype == torch.float32 and det.scores.dtype == torch.float32 and det.labels.dtype == torch.int32
+    assert det.scores.shape == (B, K) and det.labels.shape == (B, K)
+    assert det.count.dtype == torch.int32 and det.count.numel() == B and det.off.dtype == torch.int32 and det.off.numel() == B + 1
+    if valid is None:
+        valid = torch.empty((1,), dtype=torch.int32, device=dev)
+    assert valid.dtype == torch.int32 and valid.numel() == 1
+    _check(lib().u3d_det_gate(_ptr(flag), _ptr(n_live), _ptr(det.boxes), _ptr(det.scores), _ptr(det.labels), _ptr(det.count), _ptr(det.off),
+                              B, K, dim, _ptr(valid), _stream()), "det_gate")
+    return valid
