@@ -498,6 +498,23 @@ int32_t u3d_bn_bwd_stats(const void* dy, const void* y, const void* x, const flo
 int32_t u3d_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* invstd,
                          const float* gamma, const float* beta, const double* sums, int32_t relu, void* dx, void* dres, void* planes,
                          const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, const int32_t* row_map, u3d_stream s);
+/* The FPN's level sum (ref: second3d_fpn.py:131-134) in one pass over its output, U3D_BF16 rows: out[o] = sum over the levels i <
+ * levels (1 .. 4, in the order given) of relu(bn_i(x_i[idx_i[o]])), every partial sum rounded to bf16 - bit for bit what the chain of
+ * u3d_bn_apply launches with relu, row_map and post_add leaves, without writing and re-reading the partial sums.  The per-level
+ * arguments are HOST arrays of `levels` device pointers (they travel in the kernel arguments); idx[i] (int32 [n_cap], entries may be
+ * NULL = the identity) maps an OUTPUT row to the row of x_i - the inverse of u3d_bn_apply's row_map.
+ * u3d_bn_bwd_apply_sum: reads dout [n_cap][C] once and writes dx_i[idx_i[o]] of every level - u3d_bn_bwd_apply with relu, y NULL
+ * (mask recomputed from x_i) and that level's sums (u3d_bn_bwd_stats, still one call per level).
+ * U3D_ERR_UNSUPPORTED and nothing launched when dtype is not U3D_BF16, C does not fit the vector kernels (C % 8, (C / 8) | 256), the
+ * backward's staged parameters exceed 64 KiB of LDS (levels * C * 24 bytes; both entries) or a column parameter is not 16-byte
+ * aligned: the caller then runs the chain. */
+int32_t u3d_bn_apply_sum(const void* const* x, const float* const* mean, const float* const* invstd, const float* const* gamma,
+                         const float* const* beta, const int32_t* const* idx, int32_t levels, void* out, const int32_t* n_dev,
+                         int32_t n_cap, int32_t c, int32_t dtype, u3d_stream s);
+int32_t u3d_bn_bwd_apply_sum(const void* dout, const void* const* x, const float* const* mean, const float* const* invstd,
+                             const float* const* gamma, const float* const* beta, const double* const* sums,
+                             const int32_t* const* idx, void* const* dx, int32_t levels, const int32_t* n_dev, int32_t n_cap,
+                             int32_t c, int32_t dtype, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
  * SparseConvTensor.dense() (ref: sparse_encoder_hd.py:133): rows -> channels-last dense volume
@@ -1041,6 +1058,15 @@ int64_t u3d_value_records_bytes(int32_t m);
 int64_t u3d_value_scatter_workspace(int32_t n_cells);
 int32_t u3d_value_scatter(const void* records, int32_t m, int32_t n_cells, void* dvalue, int32_t dvalue_bf16, void* work,
                           int64_t work_bytes, u3d_stream s);
+/* The records of `layers` (1 .. 4) u3d_decoder_layer_bwd calls into ONE bf16 dvalue [n_cells][256] in three launches: records and m are
+ * HOST arrays (device pointers / row counts per layer), order (host, a permutation of 0 .. layers-1) names the layers in the order
+ * their per-cell sums are added.  A touched cell receives bf16(+0.0f + sum_order[0] + sum_order[1] + ...), each sum formed as
+ * u3d_value_scatter forms it and only the layers that touch the cell taking part - bit for bit what one u3d_value_scatter call per
+ * layer, in that order, into a zeroed f32 volume followed by a cast to bf16 leaves.  Cells no layer touches are not written: the
+ * caller zero-fills dvalue.  work: u3d_value_scatter_layers_workspace bytes of scratch, initialised by the call. */
+int64_t u3d_value_scatter_layers_workspace(int32_t layers, int32_t n_cells);
+int32_t u3d_value_scatter_layers(const void* const* records, const int32_t* m, const int32_t* order, int32_t layers, int32_t n_cells,
+                                 void* dvalue, void* work, int64_t work_bytes, u3d_stream s);
 /* Self-attention over groups on its own (the middle launch of the layer): q,k rows of qk [m,512] (q | k), v [m,256], 8 heads x 32;
  * o bf16 [m,256], lse f32 [m,8].  Backward: dqk [m,512], dv [m,256] bf16.  dtype U3D_BF16 | U3D_F32 (the same kernels on either
  * element type; U3D_F32: all matrices then f32, exact-f32 MFMA). */

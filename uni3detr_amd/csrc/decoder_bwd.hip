@@ -1009,3 +1009,137 @@ extern "C" int32_t u3d_value_scatter(const void* records, int32_t m, int32_t n_c
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// u3d_value_scatter_layers: the records of up to VSL_MAX u3d_decoder_layer_bwd calls into ONE bf16 volume gradient, in three launches
+// for all of them.  Per layer and cell the bookkeeping is u3d_value_scatter's (count, up to VS_K listed ids: the listed / scan decision
+// is taken per layer as there); one wave owns a cell across the layers (the smallest entry over all of them).  It forms each layer's
+// sum exactly as k_vs_reduce does, adds the sums of the layers that touch the cell to +0.0f in the caller's order - what adding them
+// one call at a time into a zeroed f32 accumulator leaves - and stores bf16(total) once: no f32 volume to zero, add into and cast.
+// ---------------------------------------------------------------------------------------------------------------------------
+#define VSL_MAX 4
+struct VsLayers {
+  const float* ds[VSL_MAX]; const int* cell[VSL_MAX]; const float* w[VSL_MAX];
+  int n_entries[VSL_MAX]; int first[VSL_MAX];         // first[l]: the layer's first entry in the numbering over all layers
+  int order[VSL_MAX];                                 // order[k]: the layer whose sum is added k-th
+  int layers, total;
+};
+template <typename T>
+__device__ __forceinline__ T vsl_pick(const T (&a)[VSL_MAX], int l) {      // a[l] of a kernel-argument array without indexing it by a register
+  T v = a[0];
+#pragma unroll
+  for (int i = 1; i < VSL_MAX; ++i)
+    if (l == i) v = a[i];
+  return v;
+}
+__device__ __forceinline__ int vsl_layer_of(const VsLayers& L, int g) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < VSL_MAX; ++i)
+    if (i < L.layers && g >= L.first[i]) l = i;
+  return l;
+}
+
+__global__ void k_vsl_init(int* __restrict__ owner, int* __restrict__ cnt, int n_cells, long long n_cnt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_cells) owner[i] = VS_NONE;
+  if (i < n_cnt) cnt[i] = 0;
+}
+
+__global__ void k_vsl_register(VsLayers L, int n_cells, int* __restrict__ owner, int* __restrict__ cnt, int* __restrict__ list) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= L.total) return;
+  const int l = vsl_layer_of(L, g), e = g - vsl_pick(L.first, l);
+  const int c = vsl_pick(L.cell, l)[e];
+  if (c < 0 || c >= n_cells) return;
+  atomicMin(&owner[c], g);
+  const size_t lc = (size_t)l * n_cells + c;
+  const int slot = atomicAdd(&cnt[lc], 1);
+  if (slot < VS_K) list[lc * VS_K + slot] = e;
+}
+
+// one wave per entry of any layer; lane l owns channels l, l + 64, l + 128, l + 192
+__global__ __launch_bounds__(256) void k_vsl_reduce(VsLayers L, int n_cells, const int* __restrict__ owner, const int* __restrict__ cnt,
+                                                    const int* __restrict__ list, unsigned short* __restrict__ dvalue) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x * 4 + wave;
+  if (g >= L.total) return;
+  const int l0 = vsl_layer_of(L, g);
+  const int c = vsl_pick(L.cell, l0)[g - vsl_pick(L.first, l0)];
+  if (c < 0 || c >= n_cells || owner[c] != g) return;            // wave-uniform
+  float tot[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < L.layers; ++k) {
+    const int l = vsl_pick(L.order, k);
+    const size_t lc = (size_t)l * n_cells + c;
+    const int n = cnt[lc];
+    if (n == 0) continue;                                          // a layer that does not touch the cell adds nothing
+    const float* __restrict__ ds = vsl_pick(L.ds, l);
+    const float* __restrict__ w = vsl_pick(L.w, l);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (n <= VS_K) {                                               // as k_vs_reduce: the listed ids in ascending order
+      const int mine = lane < n ? list[lc * VS_K + lane] : VS_NONE;
+      int rank = 0;
+      for (int q = 0; q < n; ++q) rank += __shfl(mine, q) < mine;
+      for (int q = 0; q < n; ++q)
+        vs_add_entry(ds, w, __shfl(mine, __builtin_ctzll(__ballot(lane < n && rank == q))), lane, acc);
+    } else {                                                       // ... or all of the layer's entries in order
+      const int* __restrict__ cell = vsl_pick(L.cell, l);
+      const int n_entries = vsl_pick(L.n_entries, l);
+      for (int base = 0; base < n_entries; base += 256) {
+        int cc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cc[q] = base + q * 64 + lane < n_entries ? cell[base + q * 64 + lane] : -1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          unsigned long long m = __ballot(cc[q] == c);
+          while (m) {
+            vs_add_entry(ds, w, base + q * 64 + __builtin_ctzll(m), lane, acc);
+            m &= m - 1;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[j] += acc[j];                  // the f32 accumulator's `+=`, one layer at a time
+  }
+  unsigned short* dst = dvalue + (size_t)c * 256 + lane;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) dst[j * 64] = vs_bf16_rne(tot[j]);
+}
+
+extern "C" int64_t u3d_value_scatter_layers_workspace(int32_t layers, int32_t n_cells) {
+  return (layers < 1 || layers > VSL_MAX || n_cells < 0) ? 0 : (int64_t)n_cells * (1 + (int64_t)layers * (1 + VS_K)) * 4;
+}
+
+extern "C" int32_t u3d_value_scatter_layers(const void* const* records, const int32_t* m, const int32_t* order, int32_t layers,
+                                            int32_t n_cells, void* dvalue, void* work, int64_t work_bytes, u3d_stream s) {
+  U3D_REQUIRE(records && m && order && dvalue && work && layers >= 1 && layers <= VSL_MAX && n_cells > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(work_bytes >= u3d_value_scatter_layers_workspace(layers, n_cells), U3D_ERR_WORKSPACE);
+  VsLayers L = {};
+  int64_t total = 0;
+  unsigned seen = 0;
+  for (int l = 0; l < layers; ++l) {
+    U3D_REQUIRE(records[l] && m[l] > 0 && order[l] >= 0 && order[l] < layers && !(seen >> order[l] & 1u), U3D_ERR_ARG);
+    seen |= 1u << order[l];
+    L.ds[l] = (const float*)records[l];
+    L.cell[l] = (const int*)(L.ds[l] + (size_t)m[l] * 256);
+    L.w[l] = (const float*)(L.cell[l] + (size_t)m[l] * 8);
+    L.n_entries[l] = m[l] * 8;
+    L.first[l] = (int)total;
+    L.order[l] = order[l];
+    total += (int64_t)m[l] * 8;
+    U3D_REQUIRE(total < (1ll << 31), U3D_ERR_UNSUPPORTED);
+  }
+  L.layers = layers;
+  L.total = (int)total;
+  int* owner = (int*)work;
+  int* cnt = owner + n_cells;
+  int* list = cnt + (size_t)layers * n_cells;
+  const long long n_cnt = (long long)layers * n_cells;
+  hipLaunchKernelGGL(k_vsl_init, dim3((unsigned)((n_cnt + 255) / 256)), dim3(256), 0, s, owner, cnt, n_cells, n_cnt);
+  hipLaunchKernelGGL(k_vsl_register, dim3((L.total + 255) / 256), dim3(256), 0, s, L, n_cells, owner, cnt, list);
+  hipLaunchKernelGGL(k_vsl_reduce, dim3((L.total + 3) / 4), dim3(256), 0, s, L, n_cells, (const int*)owner, (const int*)cnt,
+                     (const int*)list, (unsigned short*)dvalue);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}

@@ -800,6 +800,215 @@ extern "C" int32_t u3d_bn_bwd_apply(const void* dy, const void* y, const void* x
 }
 
 // ---------------------------------------------------------------------------------------------
+// The FPN's level sum in one pass (bf16): out = sum_i relu(bn_i(x_i)) over up to 4 levels that land on one lattice, and its
+// backward.  The chain of u3d_bn_apply launches (level i adds level i-1's output as post_add) streams every intermediate sum out and
+// in again, and its backward reads the one dout once per level; here a thread walks OUTPUT rows, reads x_i[idx_i[o]] of every level,
+// rounds the running sum to bf16 after every level exactly as the chain's stores do, and writes `out` once (backward: reads dout[o]
+// once and writes dx_i[idx_i[o]] of every level).  The per-element expressions are k_bn_apply_vec's / k_bn_bwd_apply_vec's with the
+// roundings those kernels compile to written out (fp contract off, the fused multiply-adds explicit), so the results are those
+// launches' bit for bit: tests/test_fpn_level_pass_gpu.py compares the two routes with torch.equal.
+// Per-column parameters of 4 levels do not fit a streaming kernel's registers (4 x 4 x 8 floats forward, 6 x 8 per level backward):
+// they are staged in LDS once per workgroup, and a thread takes them level by level for BNS_ROWS rows at a time, so that one set of
+// LDS reads serves BNS_ROWS rows (row by row, the LDS reads alone would cost a third of the HBM time).
+// ---------------------------------------------------------------------------------------------
+#define BNS_MAX_LEVELS 4
+#define BNS_ROWS 4          /* forward: 4 rows per thread and level (108 VGPRs, 4 waves per SIMD) */
+#define BNS_BWD_ROWS 2      /* backward: 6 parameter arrays per level - 4 rows cost 152 VGPRs (3 waves), 2 stay within 128 */
+#define BNS_MAX_LDS (64 * 1024)
+struct BnSumFwd {
+  const u16* x[BNS_MAX_LEVELS]; const float* mean[BNS_MAX_LEVELS]; const float* invstd[BNS_MAX_LEVELS];
+  const float* gamma[BNS_MAX_LEVELS]; const float* beta[BNS_MAX_LEVELS]; const int* idx[BNS_MAX_LEVELS];
+};
+struct BnSumBwd {
+  const u16* x[BNS_MAX_LEVELS]; u16* dx[BNS_MAX_LEVELS]; const float* mean[BNS_MAX_LEVELS]; const float* invstd[BNS_MAX_LEVELS];
+  const float* gamma[BNS_MAX_LEVELS]; const float* beta[BNS_MAX_LEVELS]; const double* sums[BNS_MAX_LEVELS];
+  const int* idx[BNS_MAX_LEVELS];
+};
+typedef float bns_f32x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bns_bf16x8 __attribute__((ext_vector_type(8)));
+
+__global__ __launch_bounds__(256) void k_bn_apply_sum(BnSumFwd lv, int levels, u16* __restrict__ out, const int* __restrict__ n_dev,
+                                                      int n_cap, int c) {
+  extern __shared__ float4 bns_lds4[];                                   // f32 [levels][4][c]: mean | invstd | gamma | beta
+  float* par = (float*)bns_lds4;
+  const int n = min(*n_dev, n_cap), cv = c / 8, rpb = 256 / cv;
+  if (n <= 0) return;
+#pragma unroll
+  for (int l = 0; l < BNS_MAX_LEVELS; ++l) {
+    if (l >= levels) break;
+    for (int i = threadIdx.x; i < c; i += 256) {
+      par[(l * 4 + 0) * c + i] = lv.mean[l][i]; par[(l * 4 + 1) * c + i] = lv.invstd[l][i];
+      par[(l * 4 + 2) * c + i] = lv.gamma[l][i]; par[(l * 4 + 3) * c + i] = lv.beta[l][i];
+    }
+  }
+  __syncthreads();
+  const int vc = threadIdx.x % cv, rl = threadIdx.x / cv;
+  const int tile = rpb * BNS_ROWS, ntiles = (n + tile - 1) / tile;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int r0 = t * tile + rl;                                        // this thread's rows: r0 + j * rpb
+    bns_bf16x8 acc[BNS_ROWS];                                            // the running sum as the chain stores it between levels
+#pragma unroll
+    for (int l = 0; l < BNS_MAX_LEVELS; ++l) {
+      if (l >= levels) break;
+      float mu[8], is[8], ga[8], be[8];
+      load_cols<8>(par + (l * 4 + 0) * c, vc * 8, mu); load_cols<8>(par + (l * 4 + 1) * c, vc * 8, is);
+      load_cols<8>(par + (l * 4 + 2) * c, vc * 8, ga); load_cols<8>(par + (l * 4 + 3) * c, vc * 8, be);
+      const u16* __restrict__ x = lv.x[l];
+      const int* __restrict__ idx = lv.idx[l];
+      float xv[BNS_ROWS][8];
+#pragma unroll
+      for (int j = 0; j < BNS_ROWS; ++j) {
+        const int r = min(r0 + j * rpb, n - 1);                          // rows past n: a valid row is read, nothing is stored
+        const long long src = idx ? (long long)idx[r] : (long long)r;
+        load_vec<u16>(x + src * c + (long long)vc * 8, xv[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < BNS_ROWS; ++j) {
+        bns_f32x8 f;
+        if (l > 0) f = __builtin_convertvector(acc[j], bns_f32x8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)                                           // the roundings of k_bn_apply_vec as compiled, spelled out:
+          float v = __builtin_fmaf((xv[j][e] - mu[e]) * is[e], ga[e], be[e]);      // sub, mul, one fused multiply-add
+          v = v > 0.f ? v : 0.f;
+          if (l > 0) v += f[e];                                          // y = act(bn(x)) + the sum so far, as k_bn_apply_vec's post_add
+          f[e] = v;
+        }
+        acc[j] = __builtin_convertvector(f, bns_bf16x8);                 // round to nearest even, as store_vec<u16>
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BNS_ROWS; ++j) {
+      const int r = r0 + j * rpb;
+      if (r < n) *(bns_bf16x8*)(out + (long long)r * c + (long long)vc * 8) = acc[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bn_bwd_apply_sum(BnSumBwd lv, int levels, const u16* __restrict__ dout,
+                                                          const int* __restrict__ n_dev, int n_cap, int c) {
+  extern __shared__ float4 bns_lds4[];                                   // f32 [levels][6][c]: mean | invstd | gamma | beta | mg | mgx
+  float* par = (float*)bns_lds4;
+  const int n = min(*n_dev, n_cap), cv = c / 8, rpb = 256 / cv;
+  if (n <= 0) return;
+  const float inv_n = 1.f / (float)n;
+#pragma unroll
+  for (int l = 0; l < BNS_MAX_LEVELS; ++l) {
+    if (l >= levels) break;
+    for (int i = threadIdx.x; i < c; i += 256) {
+      par[(l * 6 + 0) * c + i] = lv.mean[l][i]; par[(l * 6 + 1) * c + i] = lv.invstd[l][i];
+      par[(l * 6 + 2) * c + i] = lv.gamma[l][i]; par[(l * 6 + 3) * c + i] = lv.beta[l][i];
+      par[(l * 6 + 4) * c + i] = (float)lv.sums[l][i] * inv_n;           // load_cols_d's arithmetic
+      par[(l * 6 + 5) * c + i] = (float)lv.sums[l][c + i] * inv_n;
+    }
+  }
+  __syncthreads();
+  const int vc = threadIdx.x % cv, rl = threadIdx.x / cv;
+  const int tile = rpb * BNS_BWD_ROWS, ntiles = (n + tile - 1) / tile;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int r0 = t * tile + rl;
+    float gv[BNS_BWD_ROWS][8];
+#pragma unroll
+    for (int j = 0; j < BNS_BWD_ROWS; ++j)
+      load_vec<u16>(dout + (long long)min(r0 + j * rpb, n - 1) * c + (long long)vc * 8, gv[j]);
+#pragma unroll
+    for (int l = 0; l < BNS_MAX_LEVELS; ++l) {
+      if (l >= levels) break;
+      float mu[8], is[8], ga[8], be[8], mg[8], mgx[8];
+      load_cols<8>(par + (l * 6 + 0) * c, vc * 8, mu); load_cols<8>(par + (l * 6 + 1) * c, vc * 8, is);
+      load_cols<8>(par + (l * 6 + 2) * c, vc * 8, ga); load_cols<8>(par + (l * 6 + 3) * c, vc * 8, be);
+      load_cols<8>(par + (l * 6 + 4) * c, vc * 8, mg); load_cols<8>(par + (l * 6 + 5) * c, vc * 8, mgx);
+      const u16* __restrict__ x = lv.x[l];
+      u16* __restrict__ dx = lv.dx[l];
+      const int* __restrict__ idx = lv.idx[l];
+      float xv[BNS_BWD_ROWS][8];
+      long long src[BNS_BWD_ROWS];
+#pragma unroll
+      for (int j = 0; j < BNS_BWD_ROWS; ++j) {
+        const int r = min(r0 + j * rpb, n - 1);
+        src[j] = (idx ? (long long)idx[r] : (long long)r) * c + (long long)vc * 8;
+        load_vec<u16>(x + src[j], xv[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < BNS_BWD_ROWS; ++j) {
+        float dxv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {                                    // k_bn_bwd_apply_vec with relu and the mask recomputed from x
+          // its roundings as compiled, spelled out: there the mask's y is a multiply and an add (it may also come from memory, which
+          // keeps the two apart), and only xh * mgx is fused into its subtraction
+#pragma clang fp contract(off)
+          float g = gv[j][e];
+          const float xh = (xv[j][e] - mu[e]) * is[e];
+          const float yv = xh * ga[e] + be[e];
+          if (!(yv > 0.f)) g = 0.f;
+          dxv[e] = (ga[e] * is[e]) * __builtin_fmaf(-xh, mgx[e], g - mg[e]);
+        }
+        if (r0 + j * rpb < n) store_vec<u16>(dx + src[j], dxv);
+      }
+    }
+  }
+}
+
+static inline int bns_grid(int n_cap, int c, int rows) {
+  const int tile = 256 / (c / 8) * rows;
+  const long long b = ((long long)n_cap + tile - 1) / tile;
+  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+static inline bool bns_ptrs(const void* const* a, int levels, bool nullable = false) {      // all present (and 16-byte aligned)
+  for (int l = 0; l < levels; ++l)
+    if ((!a[l] && !nullable) || !al16(a[l])) return false;
+  return true;
+}
+
+extern "C" int32_t u3d_bn_apply_sum(const void* const* x, const float* const* mean, const float* const* invstd,
+                                    const float* const* gamma, const float* const* beta, const int32_t* const* idx, int32_t levels,
+                                    void* out, const int32_t* n_dev, int32_t n_cap, int32_t c, int32_t dtype, u3d_stream s) {
+  U3D_REQUIRE(x && mean && invstd && gamma && beta && idx && out && n_dev && c > 0 && levels >= 1 && levels <= BNS_MAX_LEVELS, U3D_ERR_ARG);
+  for (int l = 0; l < levels; ++l) U3D_REQUIRE(x[l] && mean[l] && invstd[l] && gamma[l] && beta[l], U3D_ERR_ARG);
+  const size_t lds = (size_t)levels * 4 * c * sizeof(float);
+  // (the bound is the backward's, 6 arrays per level: the forward takes no shape whose backward would be refused)
+  if (dtype != U3D_BF16 || !bn_vec_ok(c, 8) || lds / 4 * 6 > BNS_MAX_LDS) return U3D_ERR_UNSUPPORTED;
+  if (!bns_ptrs((const void* const*)mean, levels) || !bns_ptrs((const void* const*)invstd, levels) ||
+      !bns_ptrs((const void* const*)gamma, levels) || !bns_ptrs((const void* const*)beta, levels))
+    return U3D_ERR_UNSUPPORTED;
+  U3D_REQUIRE(bns_ptrs(x, levels) && al16(out), U3D_ERR_ARG);
+  if (n_cap <= 0) return U3D_OK;
+  BnSumFwd lv = {};
+  for (int l = 0; l < levels; ++l) {
+    lv.x[l] = (const u16*)x[l]; lv.mean[l] = mean[l]; lv.invstd[l] = invstd[l]; lv.gamma[l] = gamma[l]; lv.beta[l] = beta[l];
+    lv.idx[l] = idx[l];
+  }
+  hipLaunchKernelGGL(k_bn_apply_sum, dim3(bns_grid(n_cap, c, BNS_ROWS)), dim3(256), lds, s, lv, levels, (u16*)out, n_dev, n_cap, c);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+extern "C" int32_t u3d_bn_bwd_apply_sum(const void* dout, const void* const* x, const float* const* mean, const float* const* invstd,
+                                        const float* const* gamma, const float* const* beta, const double* const* sums,
+                                        const int32_t* const* idx, void* const* dx, int32_t levels, const int32_t* n_dev,
+                                        int32_t n_cap, int32_t c, int32_t dtype, u3d_stream s) {
+  U3D_REQUIRE(dout && x && mean && invstd && gamma && beta && sums && idx && dx && n_dev && c > 0 && levels >= 1 &&
+              levels <= BNS_MAX_LEVELS, U3D_ERR_ARG);
+  for (int l = 0; l < levels; ++l) U3D_REQUIRE(x[l] && mean[l] && invstd[l] && gamma[l] && beta[l] && sums[l] && dx[l], U3D_ERR_ARG);
+  const size_t lds = (size_t)levels * 6 * c * sizeof(float);
+  if (dtype != U3D_BF16 || !bn_vec_ok(c, 8) || lds > BNS_MAX_LDS) return U3D_ERR_UNSUPPORTED;
+  if (!bns_ptrs((const void* const*)mean, levels) || !bns_ptrs((const void* const*)invstd, levels) ||
+      !bns_ptrs((const void* const*)gamma, levels) || !bns_ptrs((const void* const*)beta, levels) ||
+      !bns_ptrs((const void* const*)sums, levels))
+    return U3D_ERR_UNSUPPORTED;
+  U3D_REQUIRE(bns_ptrs(x, levels) && bns_ptrs((const void* const*)dx, levels) && al16(dout), U3D_ERR_ARG);
+  if (n_cap <= 0) return U3D_OK;
+  BnSumBwd lv = {};
+  for (int l = 0; l < levels; ++l) {
+    lv.x[l] = (const u16*)x[l]; lv.dx[l] = (u16*)dx[l]; lv.mean[l] = mean[l]; lv.invstd[l] = invstd[l]; lv.gamma[l] = gamma[l];
+    lv.beta[l] = beta[l]; lv.sums[l] = sums[l]; lv.idx[l] = idx[l];
+  }
+  hipLaunchKernelGGL(k_bn_bwd_apply_sum, dim3(bns_grid(n_cap, c, BNS_BWD_ROWS)), dim3(256), lds, s, lv, levels, (const u16*)dout, n_dev, n_cap, c);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // dense() / its adjoint: rows <-> channels-last volume [B, Dz, Dy, Dx, C]
 // ---------------------------------------------------------------------------------------------
 template <bool TO_DENSE>

@@ -1173,6 +1173,40 @@ def bn_bwd_apply(dy, y, x, mean, invstd, gamma, sums, relu, n_dev, want_dres, be
     return (dx, dres, planes) if want_planes else (dx, dres)
 
 
+def _opt_ptr_array(tensors):
+    """_ptr_array with None entries (NULL)."""
+    arr = (C.c_void_p * len(tensors))()
+    for i, t in enumerate(tensors):
+        assert t is None or (t.is_cuda and t.is_contiguous()), "device-contiguous tensor required"
+        arr[i] = None if t is None else t.data_ptr()
+    return arr
+
+
+def bn_apply_sum(xs, means, invstds, gammas, betas, idxs, n_dev):
+    """out = sum_i relu(bn_i(xs[i][idxs[i]])) in one launch (u3d_bn_apply_sum; idxs[i] int32 [n] or None), every partial sum rounded to
+    bf16 as the chain of bn_apply(..., post_add) calls rounds it.  -> None for what the kernel does not take (the caller runs the chain)."""
+    n, c = xs[0].shape
+    assert all(x.shape == (n, c) and x.dtype == xs[0].dtype for x in xs)
+    out = torch.empty_like(xs[0])
+    rc = lib().u3d_bn_apply_sum(_opt_ptr_array(xs), _opt_ptr_array(means), _opt_ptr_array(invstds), _opt_ptr_array(gammas),
+                                _opt_ptr_array(betas), _opt_ptr_array(idxs), len(xs), _ptr(out), _ptr(n_dev), n, c, dtype_code(xs[0]),
+                                _stream())
+    if rc == U3D_ERR_UNSUPPORTED:
+        return None
+    _check(rc, "bn_apply_sum")
+    return out
+
+
+def bn_bwd_apply_sum(dout, xs, means, invstds, gammas, betas, sums, idxs, n_dev):
+    """The dx_i of bn_apply_sum's levels from one read of dout (u3d_bn_bwd_apply_sum); sums[i]: that level's bn_bwd_stats."""
+    n, c = dout.shape
+    dxs = [torch.empty_like(x) for x in xs]
+    _check(lib().u3d_bn_bwd_apply_sum(_ptr(dout), _opt_ptr_array(xs), _opt_ptr_array(means), _opt_ptr_array(invstds),
+                                      _opt_ptr_array(gammas), _opt_ptr_array(betas), _opt_ptr_array(sums), _opt_ptr_array(idxs),
+                                      _opt_ptr_array(dxs), len(xs), _ptr(n_dev), n, c, dtype_code(dout), _stream()), "bn_bwd_apply_sum")
+    return dxs
+
+
 def to_dense(feat, coors, n_dev, batch, dims):
     """-> logical [B, C, D, H, W] tensor in channels_last_3d memory format."""
     n, c = feat.shape
@@ -1959,10 +1993,11 @@ def decoder_layer_fwd(params, dims, x, xc, ref, value_rows, rng, save, row_waves
 
 def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad, row_waves=0):
     """dvalue: f32 [rows, 256] accumulator, or (bf16 kernels only) a bf16 one: the layer's value-volume gradient is ADDED to it, summed
-    per cell in a fixed order (value_scatter: bitwise reproducible)."""
+    per cell in a fixed order (value_scatter: bitwise reproducible).  dvalue None: nothing is scattered and the call returns
+    (dx, dref, records) - the caller scatters several layers' records at once (value_scatter_layers)."""
     m = dims.m
     dims.reserved = 0
-    assert dvalue.dtype == torch.float32 or dims.dtype == DT_BF16
+    assert dvalue is None or dvalue.dtype == torch.float32 or dims.dtype == DT_BF16
     rec = torch.empty(int(lib().u3d_value_records_bytes(m)), dtype=torch.uint8, device=ref.device)
     mp = decoder_rows(m, torch.bfloat16 if dims.dtype == DT_BF16 else torch.float32)
     dx = torch.empty((mp, 256), dtype=torch.float32, device=ref.device)
@@ -1971,6 +2006,8 @@ def decoder_layer_bwd(params, dims, x, xc, ref, value_rows, rng, xc_out, save, d
                                           _ptr(xc_out), _ptr(save), _ptr(dx_out), _ptr(dreg), _ptr(dcls), _ptr(diou), _ptr(dx),
                                           _ptr(rec), _ptr(dref), _ptr(grad), grad.numel(), int(row_waves), _stream()),
            "decoder_layer_bwd")
+    if dvalue is None:
+        return dx[:m], (None if dref is None else dref[:m]), rec
     value_scatter(rec, m, dvalue)
     return dx[:m], (None if dref is None else dref[:m])
 
@@ -1983,6 +2020,21 @@ def value_scatter(records, m, dvalue):
     work = torch.empty(int(lib().u3d_value_scatter_workspace(n)), dtype=torch.uint8, device=dvalue.device)
     _check(lib().u3d_value_scatter(_ptr(records), m, n, _ptr(dvalue), int(dvalue.dtype == torch.bfloat16), _ptr(work), work.numel(),
                                    _stream()), "value_scatter")
+
+
+VALUE_SCATTER_MAX_LAYERS = 4
+
+
+def value_scatter_layers(records, ms, dvalue, order=None):
+    """The records of up to VALUE_SCATTER_MAX_LAYERS decoder_layer_bwd calls into the zero-filled bf16 dvalue [cells, 256] in three
+    launches (u3d_value_scatter_layers): per cell the layers' sums are added in `order` (default: as listed) - the bits of one
+    value_scatter call per layer into a zeroed f32 volume, cast to bf16 afterwards."""
+    assert dvalue.is_contiguous() and dvalue.shape[1] == 256 and dvalue.dtype == torch.bfloat16
+    L, n = len(records), dvalue.shape[0]
+    order = list(range(L)) if order is None else list(order)
+    work = torch.empty(max(int(lib().u3d_value_scatter_layers_workspace(L, n)), 16), dtype=torch.uint8, device=dvalue.device)
+    _check(lib().u3d_value_scatter_layers(_ptr_array(records), (C.c_int32 * L)(*ms), (C.c_int32 * L)(*order), L, n, _ptr(dvalue),
+                                          _ptr(work), work.numel(), _stream()), "value_scatter_layers")
 
 
 def mha_fwd(qk, v, nq, p_attn=0.0, layer=0, rng=None):

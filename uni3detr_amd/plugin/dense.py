@@ -85,6 +85,9 @@ class Lattice:
 
 FUSED_LEVEL_SUM = True
 FUSED_UPSAMPLE_ORDER = True
+# with both of the above: the levels' BatchNorm apply passes run as ONE launch over the output rows, and one in the backward
+# (sp.bn_rows_sum) - the partial sums y0, y0 + y1 are neither written nor read, dout is read once.  Bit-identical to the chain.
+FUSED_LEVEL_PASS = True
 
 
 class _GatherBijection(torch.autograd.Function):
@@ -117,7 +120,8 @@ def conv_bn_relu(rows, B, dims, conv, bn, post_add=None, fan_token=None):
     return sp.conv_bn(rows, conv.weight, geom, bn, geom.n_out_dev, None, True, "oidhw", post_add, fan_token=fan_token), dims_out
 
 
-def deconv_bn_relu(rows, B, dims, deconv, bn, post_add=None):
+def _deconv_rows(rows, B, dims, deconv):
+    """The (1,s,s)/(1,s,s) transposed conv as one GEMM -> (y [n_in*s*s, Cout] in tap-major row order, idx, inv, dims_out, n_dev)."""
     s = deconv.stride[1]
     assert tuple(deconv.kernel_size) == (1, s, s) and tuple(deconv.stride) == (1, s, s), "non-overlapping (1,s,s) upsampling only"
     cin, cout = deconv.weight.shape[0], deconv.weight.shape[1]
@@ -127,6 +131,11 @@ def deconv_bn_relu(rows, B, dims, deconv, bn, post_add=None):
     y = sp.sparse_conv(rows, w, geom).view(n_in * s * s, cout)
     idx, inv, dims_out = Lattice.upsample_index(rows.device, B, dims, s)
     n_dev = Lattice.conv(rows.device, B, dims_out, (1, 1, 1), (1, 1, 1), (0, 0, 0))[0].n_out_dev
+    return y, idx, inv, dims_out, n_dev
+
+
+def deconv_bn_relu(rows, B, dims, deconv, bn, post_add=None):
+    y, idx, inv, dims_out, n_dev = _deconv_rows(rows, B, dims, deconv)
     if FUSED_UPSAMPLE_ORDER:
         # the GEMM leaves the rows tap-major; BatchNorm statistics do not care about row order, and its apply kernel writes
         # row r to its lattice position inv[r] (the backward reads dy there) - no separate gather pass over the upsampled volume
@@ -250,10 +259,40 @@ class SECOND3DFPN(nn.Module):
                            nn.ReLU(inplace=True)]
             self.extra_blocks = nn.Sequential(*layers)
 
+    def _level_pass(self, x):
+        """-> (out rows, B, dims) of the level sum as one BatchNorm apply pass, or None where the chain of per-level passes runs:
+        a flag off, rows that are not bf16 on the GPU, a BatchNorm in eval mode, a fold table or a split scope, a width
+        native.bn_apply_sum does not take."""
+        bns = [d[1] for d in self.deblocks]
+        if not (FUSED_LEVEL_PASS and FUSED_LEVEL_SUM and FUSED_UPSAMPLE_ORDER and sp._FOLD[0] is None and not sp._SPLIT[0]
+                and all(t.is_cuda and t.dtype == torch.bfloat16 for t in x) and all(bn.training for bn in bns)
+                and len({bn.num_features for bn in bns}) == 1
+                and sp.bn_rows_sum_serves(len(bns), bns[0].num_features, [p for bn in bns for p in (bn.weight, bn.bias)])):
+            return None
+        xs, stats, idxs, invs, odims, n_dev = [], [], [], [], None, None
+        for i, d in enumerate(self.deblocks):
+            rows, B, dims = to_rows(x[i])
+            if isinstance(d[0], nn.ConvTranspose3d):
+                y, idx, inv, dd, nd = _deconv_rows(rows, B, dims, d[0])
+                st = None
+            else:
+                conv = d[0]
+                geom, dd = Lattice.conv(rows.device, B, dims, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding))
+                if sp._conv_stats_serve(rows, d[1]):
+                    y, part, tr = sp.conv_with_stats(rows, conv.weight, geom, "oidhw")
+                    st = None if part is None else (part, tr)
+                else:
+                    y, st = sp.sparse_conv(rows, conv.weight, geom, "oidhw"), None
+                idx, inv, nd = None, None, geom.n_out_dev
+            assert odims is None or odims == dd, "FPN levels must land on one lattice"
+            odims, n_dev = dd, (nd if n_dev is None else n_dev)
+            xs.append(y); stats.append(st); idxs.append(idx); invs.append(inv)
+        return sp.bn_rows_sum(xs, bns, n_dev, stats, idxs, invs), B, odims
+
     def forward(self, x):
         assert len(x) == len(self.in_channels)
-        out, odims, B = None, None, None
-        for i, d in enumerate(self.deblocks):
+        out, B, odims = self._level_pass(x) or (None, None, None)
+        for i, d in enumerate(self.deblocks if out is None else ()):      # the chain of per-level passes
             rows, B, dims = to_rows(x[i])
             # the running sum of the levels rides in each level's BatchNorm apply kernel (y = relu(bn(x)) + sum so far)
             fuse = FUSED_LEVEL_SUM and out is not None and rows.is_cuda and out.dtype == rows.dtype

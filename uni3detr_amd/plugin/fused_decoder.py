@@ -27,6 +27,9 @@ ENABLED = True         # test-only module attribute: the GPU tests set it False 
 # (tests/test_decoder_gpu.py::test_packed_bf16_volume_gradient_scatter_vs_f32_accumulator).
 SHARED_DEFER = True     # test-only module attribute: shared linears' gradients summed by the deferred flush (False: autograd adds them)
 PK_SCATTER = os.environ.get("U3D_PK_SCATTER", "0") == "1"
+# the decoder layers' value-gradient records scattered by ONE call of the last layer's backward, straight into the bf16 volume gradient
+# (no f32 accumulator to zero-fill, add into per layer and cast): bit-identical to the f32 accumulator.  False: one scatter per layer.
+ONE_SCATTER = True
 POISON = os.environ.get("U3D_DEC_POISON", "0") == "1"      # debugging: NaN-fill the workspaces (read-before-write shows up as NaN)
 DEBUG_KEEP = None          # tests: a list that receives every backward call's gradient workspace
 # waves per workgroup of the bf16 row-chain kernels (k_dec_pre / k_dec_post and their backward), passed down every call: 8 = two waves
@@ -276,18 +279,33 @@ class FusedLayerFn(torch.autograd.Function):
         # each layer's volume gradient is summed per cell in a fixed order and added once (native.value_scatter); with PK_SCATTER and
         # bf16 kernels the accumulator over the layers is bf16 (no f32 volume to zero and cast), else f32
         acc_dt = torch.bfloat16 if (PK_SCATTER and rows.dtype == torch.bfloat16) else torch.float32
-        if accum is not None:
+        # ONE_SCATTER (bf16 rows, a shared accumulator): no accumulator at all - every layer leaves its records alive and the last
+        # backward scatters them together into a zero-filled bf16 volume (native.value_scatter_layers), the bits of the f32 route
+        if accum is not None and accum.buf is None and accum.records is None:       # the first backward of the stack decides
+            accum.records = [] if (ONE_SCATTER and acc_dt == torch.float32 and rows.dtype == torch.bfloat16 and want_dv
+                                   and accum.uses <= nv.VALUE_SCATTER_MAX_LAYERS) else False
+        one = accum is not None and isinstance(accum.records, list)
+        if one:
+            dvalue = None
+        elif accum is not None:
             if accum.buf is None:
                 accum.buf = torch.zeros(rows.shape, dtype=acc_dt, device=dev)
             dvalue = accum.buf
         else:
             dvalue = torch.zeros(rows.shape, dtype=acc_dt, device=dev)
-        dx, dref = nv.decoder_layer_bwd(ctx.params, d, x, xc, ref, rows, fd.rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue, grad,
-                                        ctx.row_waves)
+        dx, dref, *rec = nv.decoder_layer_bwd(ctx.params, d, x, xc, ref, rows, fd.rng, xc_out, save, dx_out, dreg, dcls, diou, dvalue,
+                                              grad, ctx.row_waves)
         if DEBUG_KEEP is not None:
             DEBUG_KEEP.append(grad)
         drows = None
-        if accum is not None:
+        if one:
+            accum.records.append((rec[0], M))
+            accum.remaining -= 1
+            if accum.remaining == 0:       # the f32 route's order of the sums: as the backwards ran, last decoder layer first
+                drows = torch.zeros(rows.shape, dtype=torch.bfloat16, device=dev)
+                nv.value_scatter_layers([r for r, _ in accum.records], [m for _, m in accum.records], drows)
+                accum.records = None
+        elif accum is not None:
             accum.remaining -= 1
             if accum.remaining == 0:
                 drows = accum.buf.to(rows.dtype) if want_dv else None

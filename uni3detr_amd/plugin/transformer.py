@@ -418,7 +418,9 @@ class ValueGradAccum:
     gradient-accumulation add of the whole [B*D*H*W, C] volume per layer."""
 
     def __init__(self, uses):
-        self.remaining, self.buf = uses, None
+        self.uses = self.remaining = uses
+        self.buf = None
+        self.records = None       # fused decoder, bf16: the layers' value-gradient records, scattered together by the last backward
 
 
 class _TrilinearSample(torch.autograd.Function):

@@ -666,19 +666,34 @@ def conv_bn(feats, weight, geom, bn, n_dev, residual=None, relu=True, layout="dh
             y = conv_folded(feats, ent, geom, residual, relu)
             if y is not None:
                 return y
-    if FUSED_CONV_STATS and bn.training and feats.is_cuda and (feats.dtype == torch.bfloat16 or _split_serves(feats, feats.shape[1], bn.num_features) == "wide"):
+    if _conv_stats_serve(feats, bn):
         # res_take: this conv's input is the identity of a residual block - its backward sums the token's gradient into the input
         # gradient; res_give: this BatchNorm adds that identity - its backward leaves the identity's gradient in the token
         # fan_token: this conv is one of several that take the same input (FanoutToken)
-        y, stats = _SparseConv.apply(feats, weight, geom, layout, True, res_take, fan_token)
-        if stats.numel():
-            tr = getattr(stats, "_u3d_tile_rows", None)
-            if tr is None:                      # attribute lost on the way through autograd: recover it from the shape
-                nb = stats.shape[0]
-                tr = next((t for t in (128, 256, 192) if (y.shape[0] + t - 1) // t == nb), 0)
+        y, stats, tr = conv_with_stats(feats, weight, geom, layout, res_take, fan_token)
+        if stats is not None:
             return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, True, stats, tr, None, post_add, res_give)
         return _BNRows.apply(y, bn.weight, bn.bias, residual, n_dev, bn, relu, bn.training, None, 0, None, post_add, res_give)
     return bn_rows(sparse_conv(feats, weight, geom, layout, fan_token), bn, n_dev, residual, relu, None, post_add)
+
+
+def _conv_stats_serve(feats, bn):
+    """The convolution in front of a training-mode BatchNorm is asked for the statistics of its output."""
+    return bool(FUSED_CONV_STATS and bn.training and feats.is_cuda
+                and (feats.dtype == torch.bfloat16 or _split_serves(feats, feats.shape[1], bn.num_features) == "wide"))
+
+
+def conv_with_stats(feats, weight, geom, layout, res_take=None, fan_token=None):
+    """-> (y, stats, rows per tile): the conv with the BatchNorm statistics of y reduced per row tile in its epilogue (what
+    native.bn_finalize_partials takes), or (y, None, 0) where the kernel serving the shape does not produce them."""
+    y, stats = _SparseConv.apply(feats, weight, geom, layout, True, res_take, fan_token)
+    if not stats.numel():
+        return y, None, 0
+    tr = getattr(stats, "_u3d_tile_rows", None)
+    if tr is None:                      # attribute lost on the way through autograd: recover it from the shape
+        nb = stats.shape[0]
+        tr = next((t for t in (128, 256, 192) if (y.shape[0] + t - 1) // t == nb), 0)
+    return y, stats, tr
 
 
 class _BNRows(torch.autograd.Function):
@@ -740,6 +755,69 @@ class _BNRows(torch.autograd.Function):
 def bn_rows(x, bn, n_dev, residual=None, relu=True, row_map=None, post_add=None):
     """row_map: the output (and its gradient) use a permuted row order, y[row_map[r]] = bn(x[r]) - see u3d_bn_apply."""
     return _BNRows.apply(x, bn.weight, bn.bias, residual, n_dev, bn, relu, bn.training, None, 0, row_map, post_add, None)
+
+
+def bn_rows_sum_serves(levels, c, params):
+    """native.bn_apply_sum / bn_bwd_apply_sum take this level count, width and these column parameters (u3d_bn_apply_sum's
+    preconditions, asked before the statistics run: a refusal afterwards could not be undone)."""
+    return (2 <= levels <= 4 and c % 8 == 0 and 256 % (c // 8) == 0 and levels * 6 * c * 4 <= 64 * 1024
+            and all(p.dtype != torch.float32 or p.data_ptr() % 16 == 0 for p in params))
+
+
+class _BNRowsSum(torch.autograd.Function):
+    """sum_i relu(BatchNorm_i(x_i)) over levels that land on one lattice, training statistics, bf16 rows: the chain of _BNRows nodes
+    with post_add (plugin.dense.SECOND3DFPN) as ONE node.  Statistics as in _BNRows, level by level (the conv's partials or a pass over
+    x_i; the backward's three passes with row_map); one apply launch forward and one backward instead of one per level - the partial
+    sums are neither written nor read again, and dout is read once.  Bit-identical to the chain.
+    specs[i] = (bn, stats or None, tile_rows, idx or None, inv or None): idx maps a lattice row to the row of x_i, inv is its inverse
+    (Lattice.upsample_index); tensors = x_0, gamma_0, beta_0, x_1, ..."""
+
+    @staticmethod
+    def forward(ctx, n_dev, specs, *tensors):
+        xs, gammas, betas = tensors[0::3], tensors[1::3], tensors[2::3]
+        n = xs[0].shape[0]
+        means, invstds = [], []
+        for x, (bn, stats, tile_rows, _, _) in zip(xs, specs):
+            mom = bn.momentum if bn.momentum is not None else 0.1
+            if stats is not None:
+                mean, invstd = nv.bn_finalize_partials(stats, tile_rows, n_dev, n, bn.eps, mom, bn.running_mean, bn.running_var,
+                                                       bn.num_batches_tracked)
+            else:
+                mean, invstd = nv.bn_forward_stats(x, n_dev, bn.eps, mom, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            means.append(mean)
+            invstds.append(invstd)
+        g32, b32 = [g.float() for g in gammas], [b.float() for b in betas]
+        idxs = [s[3] for s in specs]
+        out = nv.bn_apply_sum(xs, means, invstds, g32, b32, idxs, n_dev)
+        if out is None:
+            raise nv.U3DError("bn_apply_sum refused a shape bn_rows_sum_serves() let through")
+        ctx.save_for_backward(*xs, *means, *invstds, *g32, *b32)
+        ctx.n_dev, ctx.idxs, ctx.invs = n_dev, idxs, [s[4] for s in specs]
+        ctx.pdtypes = [g.dtype for g in gammas]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = len(ctx.idxs)
+        t = ctx.saved_tensors
+        xs, means, invstds, gammas, betas = (t[i * L:(i + 1) * L] for i in range(5))
+        dout = dout.contiguous()
+        # the sum's gradient w.r.t. every level is dout itself; the mask of each level's ReLU is recomputed from x_i (_BNRows' remask)
+        stats = [nv.bn_bwd_stats(dout, None, xs[i], means[i], invstds[i], True, ctx.n_dev, gammas[i], betas[i], ctx.invs[i], want_f32=True)
+                 for i in range(L)]
+        dxs = nv.bn_bwd_apply_sum(dout, xs, means, invstds, gammas, betas, [s[0] for s in stats], ctx.idxs, ctx.n_dev)
+        grads = []
+        for i in range(L):
+            s32 = stats[i][1] if ctx.pdtypes[i] == torch.float32 else stats[i][1].to(ctx.pdtypes[i])
+            grads += [dxs[i], s32[1], s32[0]]
+        return (None, None, *grads)
+
+
+def bn_rows_sum(xs, bns, n_dev, stats, idxs, invs):
+    """stats[i]: (partials, rows per tile) of the conv that produced xs[i] (conv_with_stats), or None."""
+    specs = [(bn, None if st is None else st[0], 0 if st is None else st[1], idx, inv) for bn, st, idx, inv in zip(bns, stats, idxs, invs)]
+    flat = [t for x, bn in zip(xs, bns) for t in (x, bn.weight, bn.bias)]
+    return _BNRowsSum.apply(n_dev, specs, *flat)
 
 
 class _ToDense(torch.autograd.Function):
