@@ -1255,6 +1255,23 @@ int32_t u3d_gtdb_crop(const float* points, int64_t n_rows, const int32_t* scene_
                       int32_t tiles, const float* boxes, int32_t n_boxes, const int32_t* box_off, const int32_t* box_valid, int32_t box_dim,
                       int32_t max_boxes, const int32_t* tile_ws, const int32_t* obj_off, int64_t total, float* out, u3d_stream s);
 
+/* LoadPointsFromFile / NormalizePointsColor (mmdet3d, recalled): uni3detr_amd/csrc/points_load.hip.
+ * raw [n_rows, load_dim] f32, 3 <= load_dim <= 8, n_rows < 2^31: the file rows of all scenes, scene b = rows scene_off[b] ..
+ * scene_off[b+1] (exactly packed, device).  out [n_rows, n_use + (shift_height != 0)]: out[:, k] = raw[:, use_dim[k]] (use_dim a HOST
+ * array, at most 8 output columns); with shift_height the column z - floor32 goes in after the third selected column, z = the third
+ * selected column, and floor_height f32 [batch] gets floor32 per scene: load_table f64 [batch][2] = (i, g) of NumPy's `linear`
+ * percentile (pos = (n - 1) * 0.0099, i = floor(pos), g = pos - i, computed by the host in float64); a = z_(i), b = z_(min(i + 1,
+ * n - 1)) are the exact order statistics of the scene's float32 z; in float64 without contraction d = b - a, floor = a + d * g when
+ * g < 0.5, b - d * (1 - g) otherwise; floor32 = f32(floor), height = z - floor32 in float32.  A NaN z makes the scene's floor and
+ * heights NaN; an empty scene's floor is NaN.  workspace: u3d_points_load_workspace(n_rows, shift_height) bytes.  No host read. */
+int64_t u3d_points_load_workspace(int64_t n_rows, int32_t shift_height);
+int32_t u3d_points_load(const float* raw, int64_t n_rows, int32_t load_dim, const int32_t* scene_off, int32_t batch,
+                        const double* load_table, const int32_t* use_dim, int32_t n_use, int32_t shift_height, void* workspace,
+                        int64_t workspace_bytes, float* out, float* floor_height, u3d_stream s);
+/* points [n_rows, feat] f32 in place: columns col0 .. col0 + 2 become (c - mean) / 255 in float32 (mean 0: only the division) */
+int32_t u3d_points_color_norm(float* points, int64_t n_rows, int32_t feat, int32_t col0, float mean0, float mean1, float mean2,
+                              u3d_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@ arithmetic runs in libu3d_hip.so (uni3detr_amd/csrc/datapath.hip) - there is no 
 A batch is a dict: points [N,F] f32 (all scenes packed), scene_off int32 [B+1] (device), optional count int32 [B] (live rows at
 the front of every scene's segment, set by PointsRangeFilter), gt_bboxes_3d [G,7|9] f32 packed + gt_off int32 [B+1] (device).
 """
+import os
+
 import numpy as np
 import torch
 
@@ -580,6 +582,160 @@ def _upload_sweeps(records, key_lens, feat, dev):
                 out_rows=int(out_rows), n_key=int(key_off[-1]), load_dim=ld)
 
 
+def _disk_backend_only(name, file_client_args):
+    backend = (file_client_args or {}).get("backend", "disk")
+    if backend != "disk" or any(k != "backend" for k in (file_client_args or {})):
+        raise NotImplementedError(f"{name}: file_client_args {dict(file_client_args)} (only the disk backend)")
+
+
+@OBJECT_AUG.register_module()
+class LoadPointsFromFile:
+    """ref: mmdet3d LoadPointsFromFile (v1.0.0rc5, RECALLED from its published behaviour - that version is not in the reference tree,
+    parity is unpinned; the contract is INTEGRATION.md section P), the first entry of every shipped pipeline.  The host part is
+    read_points (the file read, one record per scene) and pack_batch(None, ..., raw=records) (one upload); this transform runs on the
+    device (csrc/points_load.hip): batch["raw_points"] [R, load_dim] -> batch["points"] [R, len(use_dim) + shift_height], the use_dim
+    gather and, with shift_height, the column z - floor after the third selected one, floor = float32(np.percentile(z, 0.99)) per
+    scene under the declared rule (linear interpolation in float64 between the exact order statistics of the float32 column).
+    Publishes batch["floor_height"] (f32 [B], device) with shift_height and batch["color_dims"] (the last three columns) with
+    use_color; drops raw_points and load_table.  It drops no row: scene_off stays as packed."""
+
+    def __init__(self, coord_type, load_dim=6, use_dim=(0, 1, 2), shift_height=False, use_color=False, file_client_args=None):
+        _disk_backend_only("LoadPointsFromFile", file_client_args)
+        if str(coord_type).upper() not in ("CAMERA", "LIDAR", "DEPTH"):
+            raise ValueError(f"LoadPointsFromFile: coord_type {coord_type!r}")
+        self.coord_type, self.load_dim = str(coord_type).upper(), int(load_dim)
+        self.use_dim = list(range(use_dim)) if isinstance(use_dim, int) else [int(d) for d in use_dim]
+        self.shift_height, self.use_color = bool(shift_height), bool(use_color)
+        feat = len(self.use_dim) + int(self.shift_height)
+        if not 3 <= self.load_dim <= 8 or not 1 <= len(self.use_dim) or feat > 8:
+            raise NotImplementedError(f"LoadPointsFromFile: load_dim {load_dim} / use_dim {use_dim} (3 <= load_dim <= 8, at most 8 output "
+                                      "columns)")
+        if max(self.use_dim) >= self.load_dim or min(self.use_dim) < 0:
+            raise ValueError(f"LoadPointsFromFile: expect all used dimensions < {self.load_dim}, got {self.use_dim}")
+        if self.shift_height and len(self.use_dim) < 3:
+            raise ValueError("LoadPointsFromFile: shift_height needs x, y, z as the first three used dimensions")
+        if self.use_color and len(self.use_dim) < 6:
+            raise ValueError("LoadPointsFromFile: use_color needs at least six used dimensions (upstream asserts it)")
+        self.feat = feat
+
+    def __call__(self, batch):
+        if "raw_points" not in batch:
+            raise KeyError("LoadPointsFromFile needs batch['raw_points'] (pack_batch(None, ..., raw=records))")
+        raw = batch["raw_points"]
+        if raw.shape[1] != self.load_dim:
+            raise ValueError(f"LoadPointsFromFile: the batch holds raw rows of {raw.shape[1]} columns, the entry load_dim {self.load_dim}")
+        if raw.shape[0] >= 2 ** 31:
+            raise NotImplementedError("LoadPointsFromFile: 2^31 rows or more in the batch")
+        batch["points"], floor = nv.points_load(raw, batch["scene_off"], batch.get("load_table"), self.use_dim, self.shift_height)
+        del batch["raw_points"]             # spent (stream-ordered free)
+        batch.pop("load_table", None)
+        if self.shift_height:
+            batch["floor_height"], batch["height_dim"] = floor, 3
+        if self.use_color:
+            batch["color_dims"] = [self.feat - 3, self.feat - 2, self.feat - 1]
+        return batch
+
+
+@OBJECT_AUG.register_module()
+class NormalizePointsColor:
+    """ref: mmdet3d NormalizePointsColor (recalled): colour = (colour - color_mean) / 255.0 in float32, one launch in place over the
+    three colour columns LoadPointsFromFile(use_color=True) published; color_mean None only divides."""
+
+    def __init__(self, color_mean=None):
+        if color_mean is not None and len(color_mean) != 3:
+            raise ValueError(f"NormalizePointsColor: color_mean {color_mean!r} (three values)")
+        self.color_mean = None if color_mean is None else [float(v) for v in color_mean]
+
+    def __call__(self, batch):
+        dims = batch["color_dims"]          # KeyError without it: upstream asserts the colour attribute
+        if list(dims) != list(range(dims[0], dims[0] + 3)):
+            raise NotImplementedError(f"NormalizePointsColor: colour columns {list(dims)} (three neighbouring columns)")
+        nv.points_color_norm(batch["points"], dims[0], self.color_mean)
+        return batch
+
+
+# The LoadPointsFromFile entries of the shipped configs (configs/pipelines.py lists the loading entries by type only).
+SHIPPED_LOAD_ENTRIES = {
+    "sunrgbd": dict(type="LoadPointsFromFile", coord_type="DEPTH", shift_height=True, load_dim=6, use_dim=[0, 1, 2]),
+    "scannet": dict(type="LoadPointsFromFile", coord_type="DEPTH", shift_height=False, load_dim=3, use_dim=[0, 1, 2]),
+    "scannet_large": dict(type="LoadPointsFromFile", coord_type="DEPTH", shift_height=False, load_dim=3, use_dim=[0, 1, 2]),
+    "kitti_3classes": dict(type="LoadPointsFromFile", coord_type="LIDAR", load_dim=4, use_dim=4),
+    "kitti_car": dict(type="LoadPointsFromFile", coord_type="LIDAR", load_dim=4, use_dim=4),
+    "nuscenes": dict(type="LoadPointsFromFile", coord_type="LIDAR", load_dim=5, use_dim=5),
+}
+
+
+def load_table(n_rows):
+    """(i, g) per scene of NumPy's `linear` percentile at q = 0.99: pos = (n - 1) * (0.99 / 100), i = floor(pos), g = pos - i, in
+    float64 -> f64 [B, 2] (an empty scene gets (0, 0); read_points refuses it when the height is asked for)."""
+    n = np.asarray(n_rows, np.int64)
+    pos = (np.maximum(n, 1) - 1).astype(np.float64) * np.true_divide(0.99, 100)
+    i = np.floor(pos)
+    return np.stack([i, pos - i], 1)
+
+
+def read_points(path_or_info, entry_cfg):
+    """The host part of LoadPointsFromFile for one scene: a path, or a dict with `pts_filename`; entry_cfg: the pipeline entry.
+    Upstream's read (np.load for .npy, else np.fromfile(float32), then reshape(-1, load_dim)) and nothing else ->
+    dict(raw=float32 [n, load_dim], load_dim=...)."""
+    entry = LoadPointsFromFile(**{k: v for k, v in entry_cfg.items() if k != "type"})
+    path = os.fspath(path_or_info["pts_filename"] if isinstance(path_or_info, dict) else path_or_info)
+    a = np.load(path) if path.endswith(".npy") else np.fromfile(path, dtype=np.float32)
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, entry.load_dim)
+    if entry.shift_height and a.shape[0] == 0:
+        raise ValueError(f"LoadPointsFromFile: {path} holds no point, shift_height needs the percentile of its heights")
+    return dict(raw=a, load_dim=entry.load_dim)
+
+
+def _upload_raw(records, gt, labels, dev, pinned=None):
+    """The raw file rows of every scene, the percentile table, scene_off and - where they come as NumPy arrays - the GT boxes and
+    labels, in one pinned buffer and one host-to-device copy -> the batch entries.  pinned: a callable nbytes -> pinned uint8 tensor
+    (a caller that owns its staging buffers, feeder.BatchFeeder); by default the caching host allocator keeps the buffer until the
+    copy is done."""
+    B = len(records)
+    if B == 0:
+        raise ValueError("pack_batch: no scene")
+    ld = int(records[0]["load_dim"])
+    if any(int(r["load_dim"]) != ld for r in records):
+        raise ValueError(f"raw records of differing load_dim {[r['load_dim'] for r in records]}")
+    lens = [int(r["raw"].shape[0]) for r in records]
+    R = sum(lens)
+    if R >= 2 ** 31:
+        raise NotImplementedError("pack_batch: 2^31 raw rows or more in the batch (the device offsets are int32)")
+    ints = [np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)]
+    G, dim = 0, 7
+    if gt is not None:
+        if len(gt) != B:
+            raise ValueError(f"{len(gt)} GT box arrays for {B} scenes")
+        gl = [int(g.shape[0]) for g in gt]
+        G, dim = sum(gl), int(gt[0].shape[1])
+        ints.append(np.concatenate([[0], np.cumsum(gl)]).astype(np.int32))
+        if labels is not None:
+            ints.append(np.concatenate([np.asarray(l).reshape(-1) for l in labels]).astype(np.int32) if G else np.zeros(0, np.int32))
+    ints = np.concatenate(ints)
+    pad = lambda n: (n + 15) // 16 * 16            # noqa: E731
+    nb_t, nb_i, nb_g = B * 16, pad(ints.size * 4), pad(G * dim * 4)
+    total = nb_t + nb_i + nb_g + R * ld * 4
+    buf = pinned(total) if pinned is not None else torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+    host = buf.numpy()
+    host[:nb_t].view(np.float64)[:] = load_table(lens).reshape(-1)
+    host[nb_t:nb_t + ints.size * 4].view(np.int32)[:] = ints
+    if G:
+        np.concatenate([np.asarray(g, np.float32) for g in gt], 0, out=host[nb_t + nb_i:nb_t + nb_i + G * dim * 4].view(np.float32).reshape(G, dim))
+    if R:
+        np.concatenate([r["raw"] for r in records], 0, out=host[nb_t + nb_i + nb_g:total].view(np.float32).reshape(R, ld))
+    d = buf[:total].to(dev, non_blocking=True)            # the one upload
+    di = d[nb_t:nb_t + ints.size * 4].view(torch.int32)
+    out = dict(raw_points=d[nb_t + nb_i + nb_g:].view(torch.float32).reshape(R, ld), scene_off=di[:B + 1],
+               load_table=d[:nb_t].view(torch.float64).reshape(B, 2))
+    if gt is not None:
+        out["gt_off"] = di[B + 1:2 * B + 2]
+        out["gt_bboxes_3d"] = d[nb_t + nb_i:nb_t + nb_i + G * dim * 4].view(torch.float32).reshape(G, dim)
+        if labels is not None:
+            out["gt_labels_3d"] = di[2 * B + 2:2 * B + 2 + G]
+    return out, lens
+
+
 @OBJECT_AUG.register_module()
 class PointShuffle:
     """ref: mmdet3d PointShuffle (recalled: BasePoints.shuffle, one torch.randperm per sample).  The torch stream cannot be replayed
@@ -632,16 +788,25 @@ _PASSTHROUGH = {"LoadPointsFromFile", "LoadAnnotations3D", "DefaultFormatBundle3
 
 class DevicePipeline:
     """The device-side part of a config's `train_pipeline` / `test_pipeline` list: loading / formatting entries (and the
-    ground-truth database sampler, which needs the dataset's files) stay with the host loader and are skipped here."""
+    ground-truth database sampler, which needs the dataset's files) stay with the host loader and are skipped here unless the
+    constructor opts them in."""
 
-    def __init__(self, pipeline_cfg, gt_database=None, object_noise=False, sweeps=False, point_shuffle=False, name_filter=False):
+    def __init__(self, pipeline_cfg, gt_database=None, object_noise=False, sweeps=False, point_shuffle=False, name_filter=False, load=False,
+                 normalize_color=False):
         """gt_database (uni3detr_amd.gtdb.GTDatabase): run ObjectSample / UnifiedObjectSample on the device; object_noise=True: run
         ObjectNoise on the device; sweeps=True: LoadPointsFromMultiSweeps (the batch then needs pack_batch(..., sweeps=...));
-        point_shuffle=True: PointShuffle; name_filter=True: ObjectNameFilter.  Without them these entries stay in `skipped`."""
+        point_shuffle=True: PointShuffle; name_filter=True: ObjectNameFilter; load=True: LoadPointsFromFile (the batch then comes from
+        pack_batch(None, ..., raw=...)); normalize_color=True: NormalizePointsColor.  Without them these entries stay in `skipped`.
+        load_cfg / sweeps_cfg: the opted-in loading entries as the config gives them (what read_points / read_sweeps take)."""
         self.transforms, self.skipped = [], []
+        self.load_cfg = self.sweeps_cfg = None
         opt_in = {"ObjectNoise": object_noise, "LoadPointsFromMultiSweeps": sweeps, "PointShuffle": point_shuffle,
-                  "ObjectNameFilter": name_filter}
+                  "ObjectNameFilter": name_filter, "LoadPointsFromFile": load, "NormalizePointsColor": normalize_color}
         for c in pipeline_cfg:
+            if c["type"] == "LoadPointsFromFile" and load:
+                self.load_cfg = dict(c)
+            if c["type"] == "LoadPointsFromMultiSweeps" and sweeps:
+                self.sweeps_cfg = dict(c)
             if c["type"] in ("ObjectSample", "UnifiedObjectSample") and gt_database is not None:
                 if "db_sampler" not in c:
                     raise KeyError(f"pipeline entry {c['type']!r}: a device GT-paste needs the entry's db_sampler (sample_groups, rate)")
@@ -661,15 +826,36 @@ class DevicePipeline:
         return batch
 
 
-def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_labels_3d=None, *, sweeps=None):
+def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_labels_3d=None, *, sweeps=None, raw=None, device=None,
+               pinned=None):
     """list of per-scene [n_i,F] tensors (+ list of [g_i,7|9] box tensors, + list of label tensors) on one device -> the batch dict
     the transforms take.  sweeps: one read_sweeps record per scene (the points are then the key frames): every raw sweep row goes up
     in one copy from pinned memory, batch["sweeps"] holds the records and the device tables until the merge drops them,
-    batch["sweep_choices"] the choices."""
-    dev = points[0].device
-    lens = [int(p.shape[0]) for p in points]
-    off = torch.tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=dev)
-    batch = dict(points=torch.cat([p.float() for p in points]).contiguous(), scene_off=off, box_type_3d=box_type_3d, height_dim=height_dim)
+    batch["sweep_choices"] the choices.
+    raw: one read_points record per scene, `points` must then be None (LoadPointsFromFile makes them on the device): all raw rows go
+    up in one pinned buffer and one copy, batch["raw_points"] [R, load_dim], batch["scene_off"] from the row counts (the loader drops
+    no row), batch["load_table"] f64 [B, 2] = (i, g) per scene (datapath.load_table).  The GT boxes / labels may then be NumPy arrays:
+    they travel in the same copy.  device: where to (default: the GT tensors' device, else "cuda"); pinned: see _upload_raw.  With
+    sweeps= as well the key frames are the loader's output, so the loader has to keep all load_dim columns of the sweep records."""
+    if raw is not None:
+        if points is not None:
+            raise ValueError("pack_batch: raw= takes the place of points (pass points=None)")
+        raw = list(raw)
+        host_gt = gt_bboxes_3d is not None and all(isinstance(g, np.ndarray) for g in gt_bboxes_3d)
+        if device is None:
+            device = gt_bboxes_3d[0].device if gt_bboxes_3d is not None and len(gt_bboxes_3d) and not host_gt else "cuda"
+        dev = torch.device(device)
+        up, lens = _upload_raw(raw, gt_bboxes_3d if host_gt else None, gt_labels_3d if host_gt else None, dev, pinned)
+        batch = dict(up, box_type_3d=box_type_3d, height_dim=height_dim)
+        if host_gt:
+            gt_bboxes_3d = None
+        feat = int(raw[0]["load_dim"])
+    else:
+        dev = points[0].device
+        lens = [int(p.shape[0]) for p in points]
+        off = torch.tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=dev)
+        batch = dict(points=torch.cat([p.float() for p in points]).contiguous(), scene_off=off, box_type_3d=box_type_3d, height_dim=height_dim)
+        feat = int(batch["points"].shape[1])
     if gt_bboxes_3d is not None:
         gl = [int(g.shape[0]) for g in gt_bboxes_3d]
         batch["gt_off"] = torch.tensor(np.concatenate([[0], np.cumsum(gl)]).astype(np.int32), device=dev)
@@ -680,7 +866,7 @@ def pack_batch(points, gt_bboxes_3d=None, box_type_3d="Depth", height_dim=3, gt_
             batch["gt_labels_3d"] = (torch.cat([l.to(torch.int32) for l in gt_labels_3d]).contiguous() if sum(gl)
                                      else torch.zeros((0,), dtype=torch.int32, device=dev))
     if sweeps is not None:
-        batch["sweeps"] = _upload_sweeps(list(sweeps), lens, int(batch["points"].shape[1]), dev)
+        batch["sweeps"] = _upload_sweeps(list(sweeps), lens, feat, dev)
         batch["sweep_choices"] = [r["choices"] for r in sweeps]
     return batch
 

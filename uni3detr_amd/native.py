@@ -2212,6 +2212,40 @@ def sweeps_merge(key_points, raw, seg_tab, seg_param, seg_chunk0, scene_chunk0, 
 
 
 # --------------------------------------------------------------------------------------------------
+# LoadPointsFromFile / NormalizePointsColor (csrc/points_load.hip)
+# --------------------------------------------------------------------------------------------------
+def points_load(raw, scene_off, load_table, use_dim, shift_height):
+    """-> (points [R, len(use_dim) + shift_height] f32, floor_height f32 [B] or None): the use_dim gather of the raw file rows and,
+    with shift_height, the height column after the third selected one (include/u3d_hip.h u3d_points_load; no host sync)."""
+    assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.is_contiguous() and scene_off.dtype == torch.int32
+    dev, rows, load_dim = raw.device, int(raw.shape[0]), int(raw.shape[1])
+    batch = scene_off.numel() - 1
+    use = [int(d) for d in use_dim]
+    sh = int(bool(shift_height))
+    if sh:
+        assert load_table is not None and load_table.dtype == torch.float64 and load_table.numel() == 2 * batch and load_table.is_contiguous()
+    out = torch.empty((rows, len(use) + sh), dtype=torch.float32, device=dev)
+    floor = torch.empty((batch,), dtype=torch.float32, device=dev) if sh else None
+    wsb = int(lib().u3d_points_load_workspace(rows, sh))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb > 0 else None
+    _check(lib().u3d_points_load(_ptr(raw) if rows else None, rows, load_dim, _ptr(scene_off), batch, _ptr(load_table) if sh else None,
+                                 (C.c_int32 * len(use))(*use), len(use), sh, _ptr(ws), wsb, _ptr(out) if rows else None, _ptr(floor),
+                                 _stream()), "points_load")
+    return out, floor
+
+
+def points_color_norm(points, col0, mean=None):
+    """columns col0 .. col0 + 2 of points [R, F] f32 become (c - mean) / 255.0 in place; mean None: only the division."""
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous()
+    m = [0.0, 0.0, 0.0] if mean is None else [float(v) for v in mean]
+    assert len(m) == 3
+    rows = int(points.shape[0])
+    _check(lib().u3d_points_color_norm(_ptr(points) if rows else None, rows, int(points.shape[1]), int(col0), m[0], m[1], m[2], _stream()),
+           "points_color_norm")
+    return points
+
+
+# --------------------------------------------------------------------------------------------------
 # GT-paste / ObjectNoise (csrc/objaug.hip)
 # --------------------------------------------------------------------------------------------------
 OA_CAP = 1024          # boxes per scene the collision / noise kernels stage in LDS
