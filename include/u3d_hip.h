@@ -683,6 +683,47 @@ int32_t u3d_det_tail_pp(const float* prob, const float* fused, const float* boxe
 int32_t u3d_det_gate(const float* flag, const int32_t* n_live, float* boxes, float* scores, int32_t* labels, int32_t* count, int32_t* off,
                      int32_t batch, int32_t max_num, int32_t box_dim, int32_t* valid, u3d_stream s);
 
+/* A device-resident store for the detections of a whole dataset (csrc/det_store.hip): finished DetBatches are appended stream-ordered,
+ * with no host read, and packed once into the flat layout of u3d_eval_* (the counterpart of the result list the reference's
+ * extra_tools/test.py collects on the host).  The store is caller-owned memory, zeroed cursor to start with:
+ *   st_boxes f32 [R, box_dim], st_scores f32 [R], st_labels int32 [R]     R = row_capacity
+ *   table int32 [S, 2] = (first row, count) per scene                     S = scene_capacity
+ *   cursor int32 [4] = (scenes recorded, rows used, invalid calls, refused calls)
+ *   invalid int32 [M, 2] = (first scene, scenes) per invalid call         M = invalid_capacity (0: invalid may be NULL)
+ * u3d_det_store_append takes the tensors of a DetBatch (boxes [batch, max_num, box_dim], scores / labels [batch, max_num] with the rows
+ * past count[b] zero, count int32 [batch]; a count outside [0, max_num] is read as clamped, as in u3d_det_gate), n_live (one device
+ * int32, NULL = batch; clamped to [0, batch]), valid (one device int32, NULL = 1) and scene_ids (int32 [batch] or NULL).
+ *   scene_ids NULL: the leading n_live scenes become scenes cursor[0] .. cursor[0] + n_live - 1, their live rows go to rows cursor[1] ..
+ *     in scene order, table and cursor advance; scenes at or past n_live are padding and are not recorded.  With valid[0] == 0 the
+ *     scenes are recorded with count 0 (numbering stays aligned with the dataset), (first scene, n_live) is written to
+ *     invalid[cursor[2]] if cursor[2] < M, and cursor[2] is incremented in any case (n_live == 0: nothing to record, nothing counted).
+ *     The call is REFUSED AS A WHOLE when the scenes would pass S or the rows would pass R: it writes nothing and increments cursor[3].
+ *   scene_ids given (the repair of scenes recorded empty): the rows are appended at cursor[1] and table[scene_ids[b]] is overwritten for
+ *     b < n_live; cursor[0] does not move.  A scene id outside [0, cursor[0]), rows that would pass R, or valid[0] == 0 refuse the call
+ *     as above.  An id named twice: the last one wins.  The rows an overwritten entry pointed to stay where they are, unreferenced.
+ * A cursor outside the store refuses the call too.  Two launches, no atomics on global memory, no allocation, no synchronisation; it can
+ * be captured in a graph, and then every replay appends.  The bytes written are a function of the inputs alone: nothing at or past the
+ * used rows of the store is ever read.  Every workgroup re-derives the call's plan from count: O(batch) reads each.
+ * U3D_ERR_ARG: a null pointer (other than n_live / valid / scene_ids, and invalid with M == 0), batch, max_num, R or S <= 0, M < 0,
+ * box_dim not 7 or 9; U3D_ERR_UNSUPPORTED: batch > 65535, max_num > U3D_DET_TAIL_MAX_K, R * box_dim >= 2^31.  Checked before any launch. */
+int32_t u3d_det_store_append(const float* boxes, const float* scores, const int32_t* labels, const int32_t* count, int32_t batch,
+                             int32_t max_num, int32_t box_dim, const int32_t* n_live, const int32_t* valid, const int32_t* scene_ids,
+                             float* st_boxes, float* st_scores, int32_t* st_labels, int32_t* table, int32_t* cursor, int32_t* invalid,
+                             int32_t row_capacity, int32_t scene_capacity, int32_t invalid_capacity, u3d_stream s);
+
+/* The first n_scenes scenes of a store (n_scenes <= cursor[0], which the host has read) in the evaluators' layout, in scene index order:
+ * out_boxes f32 [out_rows, box_dim], out_scores f32 [out_rows], out_labels int32 [out_rows], out_off int32 [n_scenes + 1] = exclusive
+ * scan of the table's counts (the det_off of u3d_eval_*).  Rows a repair left unreferenced do not appear.  out_off is always the full
+ * scan; a row whose place lies at or past out_rows is not written, so out_off[n_scenes] > out_rows tells a too small output.  A table
+ * entry is read as clamped to a run inside [0, R).  bad int32 [2]: bad[0] = 1 when a packed score is not finite, bad[1] = 1 when a
+ * packed label lies outside [0, num_classes) (num_classes <= 0: not checked), else 0.  At most two launches (one for n_scenes == 0), no
+ * atomics on global memory, no allocation, no synchronisation; equal inputs give equal bytes.
+ * U3D_ERR_ARG: a null pointer, n_scenes or out_rows < 0, R <= 0, box_dim not 7 or 9; U3D_ERR_UNSUPPORTED: R * box_dim or
+ * out_rows * box_dim >= 2^31. */
+int32_t u3d_det_store_pack(const float* st_boxes, const float* st_scores, const int32_t* st_labels, const int32_t* table, int32_t n_scenes,
+                           int32_t row_capacity, int32_t box_dim, int32_t num_classes, float* out_boxes, float* out_scores,
+                           int32_t* out_labels, int32_t out_rows, int32_t* out_off, int32_t* bad, u3d_stream s);
+
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad

@@ -442,8 +442,8 @@ class IndoorEvaluator:
         if not bbox_list:
             return
         dev = self.device
-        db, ds, dl, gb, gl = [], [], [], [], []
-        for det, g, lab in zip(bbox_list, gt_boxes, gt_labels):
+        db, ds, dl = [], [], []
+        for det in bbox_list:
             if isinstance(det, dict):
                 det = det.get("pts_bbox", det)
                 det = (det["boxes_3d"], det["scores_3d"], det["labels_3d"])
@@ -453,6 +453,15 @@ class IndoorEvaluator:
             ds.append(torch.as_tensor(s).to(dev, torch.float32).reshape(-1))
             dl.append(torch.as_tensor(l).to(dev, torch.int32).reshape(-1))
             self._det_counts.append(int(b.shape[0]))
+        self._det["boxes"].append(torch.cat(db))
+        self._det["scores"].append(torch.cat(ds))
+        self._det["labels"].append(torch.cat(dl))
+        self._add_gt(gt_boxes, gt_labels)
+
+    def _add_gt(self, gt_boxes, gt_labels):
+        dev = self.device
+        gb, gl = [], []
+        for g, lab in zip(gt_boxes, gt_labels):
             if hasattr(g, "tensor"):
                 gbox = _rows7(g.tensor, dev)
             else:
@@ -461,11 +470,28 @@ class IndoorEvaluator:
             gb.append(gbox)
             gl.append(torch.as_tensor(lab).to(dev, torch.int32).reshape(-1))
             self._gt_counts.append(int(gbox.shape[0]))
-        self._det["boxes"].append(torch.cat(db))
-        self._det["scores"].append(torch.cat(ds))
-        self._det["labels"].append(torch.cat(dl))
         self._gt["boxes"].append(torch.cat(gb))
         self._gt["labels"].append(torch.cat(gl))
+
+    def add_store(self, store, gt_boxes, gt_labels):
+        """add() for every scene of a det_store.DetStore at once, in the store's scene order: the detections are store.packed() (they
+        never leave the device), the per-scene counts come from one read of its det_off.  gt_boxes / gt_labels: one entry per scene of
+        the store, as for add().  Bit-identical to add() over the same scenes in the same order.  Labels are checked by compute()."""
+        errors = ("indoor evaluation: detection scores must be finite", "")
+        if self.device.type == "cpu":
+            return self.add(store.results(errors=errors), gt_boxes, gt_labels)
+        boxes, scores, labels, off = store.packed(errors=errors)
+        counts = torch.diff(off).tolist()
+        if not len(counts) == len(gt_boxes) == len(gt_labels):
+            raise ValueError(f"IndoorEvaluator.add_store: the store holds {len(counts)} scenes, GT was given for {len(gt_boxes)}")
+        if not counts:
+            return
+        assert sum(counts) == boxes.shape[0]
+        self._det["boxes"].append(_rows7(boxes, self.device))
+        self._det["scores"].append(scores.to(self.device))
+        self._det["labels"].append(labels.to(self.device))
+        self._det_counts.extend(counts)
+        self._add_gt(gt_boxes, gt_labels)
 
     def compute(self, label2cat=None, logger="silent"):
         """-> the dict of `indoor_eval` (label2cat defaults to {c: str(c)}).  Labels outside [0, num_classes) raise ValueError."""

@@ -443,6 +443,12 @@ class InferenceStep:
         self.pts = self.valid = self.det = self.head_outs = None
         self._graph = self._caps = None
 
+    @property
+    def n_live(self):
+        """Device int32 [1]: the leading scenes of the bound batch that carry real data (the rest is padding the gate empties); None
+        before the first batch is bound.  What det_store.DetStore.append takes next to `det` and `valid`."""
+        return None if self.pts is None else self._n_live
+
     # ---- static buffers ---------------------------------------------------------------------------------------------------
     def _alloc(self):
         """TrainStep._alloc_capacity_buffers without the GT: one spare row behind `cat` (an empty LAST scene makes the FPS gather read

@@ -562,15 +562,41 @@ class KittiEvaluator:
                 self._scores.append(torch.as_tensor(r["scores_3d"]).to(self.device, torch.float32).reshape(-1))
                 self._labels.append(torch.as_tensor(r["labels_3d"]).to(self.device, torch.int32).reshape(-1))
                 self._counts.append(int(b.shape[0]))
-                T, P2, hw = _calib(info)
-                self._calib.append(np.concatenate([T.reshape(-1), P2.reshape(-1)]))
-                self._img.append(hw)
-            g = _encode(info["annos"], True)
-            self._gt.append(g)
-            self._gt_counts.append(g.shape[0])
-            self._gt_alpha0.append(g[0, 11] if g.shape[0] else None)
-            if self.device.type == "cpu":
-                self._counts.append(0)
+            self._add_info(info)
+
+    def _add_info(self, info):
+        """one scene's calibration rows (device path) and encoded GT"""
+        if self.device.type != "cpu":
+            T, P2, hw = _calib(info)
+            self._calib.append(np.concatenate([T.reshape(-1), P2.reshape(-1)]))
+            self._img.append(hw)
+        g = _encode(info["annos"], True)
+        self._gt.append(g)
+        self._gt_counts.append(g.shape[0])
+        self._gt_alpha0.append(g[0, 11] if g.shape[0] else None)
+        if self.device.type == "cpu":
+            self._counts.append(0)
+
+    def add_store(self, store, infos):
+        """add() for every scene of a det_store.DetStore at once, in the store's scene order: the detections are store.packed() (they
+        never leave the device), the per-scene counts come from one read of its det_off; infos: one per scene of the store.
+        Bit-identical to add() over the same scenes in the same order."""
+        errors = ("kitti_eval: detection scores must be finite", "KittiEvaluator: labels must index class_names")
+        if self.device.type == "cpu":
+            return self.add(store.results(len(self.class_names), errors), infos)
+        boxes, scores, labels, off = store.packed(len(self.class_names), errors)
+        counts = torch.diff(off).tolist()
+        if len(counts) != len(infos):
+            raise ValueError(f"KittiEvaluator.add_store: the store holds {len(counts)} scenes, {len(infos)} infos were given")
+        if not counts:
+            return
+        assert sum(counts) == boxes.shape[0]
+        self._boxes.append(boxes.to(self.device)[:, :7])
+        self._scores.append(scores.to(self.device))
+        self._labels.append(labels.to(self.device))
+        self._counts.extend(counts)
+        for info in infos:
+            self._add_info(info)
 
     def compute(self, logger="silent"):
         """-> ret_dict of `kitti_eval` over everything added (the result string goes to `logger`)."""

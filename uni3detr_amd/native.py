@@ -2525,3 +2525,43 @@ def det_gate(det, flag, n_live, valid=None):
     _check(lib().u3d_det_gate(_ptr(flag), _ptr(n_live), _ptr(det.boxes), _ptr(det.scores), _ptr(det.labels), _ptr(det.count), _ptr(det.off),
                               B, K, dim, _ptr(valid), _stream()), "det_gate")
     return valid
+
+
+# --------------------------------------------------------------------------------------------------
+# The device-resident detection store (csrc/det_store.hip; uni3detr_amd/det_store.py owns the buffers)
+# --------------------------------------------------------------------------------------------------
+def det_store_append(det, n_live, valid, scene_ids, boxes, scores, labels, table, cursor, invalid):
+    """Append a DetBatch to a store's buffers (u3d_det_store_append; two launches, no host sync, capturable).  n_live / valid: one
+    device int32 each or None; scene_ids int32 [B] or None (given: the repair path).  boxes [R,D], scores [R], labels int32 [R], table
+    int32 [S,2], cursor int32 [4], invalid int32 [M,2] are the store.  A call that does not fit is refused on the device (cursor[3])."""
+    B, K, dim = det.boxes.shape
+    assert det.boxes.dtype == torch.float32 and det.scores.dtype == torch.float32 and det.labels.dtype == torch.int32
+    assert det.scores.shape == (B, K) and det.labels.shape == (B, K) and det.count.dtype == torch.int32 and det.count.numel() == B
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == dim
+    R, S, M = int(boxes.shape[0]), int(table.shape[0]), int(invalid.shape[0])
+    assert scores.numel() == R and labels.numel() == R and labels.dtype == torch.int32
+    assert table.dtype == torch.int32 and table.shape == (S, 2) and cursor.dtype == torch.int32 and cursor.numel() == 4
+    assert invalid.dtype == torch.int32 and invalid.shape == (M, 2)
+    for t, n in ((n_live, 1), (valid, 1), (scene_ids, B)):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == n)
+    _check(lib().u3d_det_store_append(_ptr(det.boxes), _ptr(det.scores), _ptr(det.labels), _ptr(det.count), B, K, dim, _ptr(n_live),
+                                      _ptr(valid), _ptr(scene_ids), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(table), _ptr(cursor),
+                                      _ptr(invalid) if M else None, R, S, M, _stream()), "det_store_append")
+
+
+def det_store_pack(boxes, scores, labels, table, n_scenes, out_rows, num_classes=0):
+    """The first n_scenes scenes of a store in the evaluators' layout (u3d_det_store_pack; two launches, no host sync) ->
+    (boxes [out_rows,D], scores [out_rows], labels int32 [out_rows], det_off int32 [n_scenes+1], bad int32 [2]) on the device."""
+    R, dim = boxes.shape
+    dev = boxes.device
+    n_scenes, out_rows = int(n_scenes), int(out_rows)
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and labels.dtype == torch.int32 and table.dtype == torch.int32
+    assert scores.numel() == R and labels.numel() == R and table.dim() == 2 and table.shape[1] == 2 and 0 <= n_scenes <= table.shape[0]
+    ob = torch.empty((max(out_rows, 1), dim), dtype=torch.float32, device=dev)
+    osc = torch.empty((max(out_rows, 1),), dtype=torch.float32, device=dev)
+    ol = torch.empty((max(out_rows, 1),), dtype=torch.int32, device=dev)
+    off = torch.empty((n_scenes + 1,), dtype=torch.int32, device=dev)
+    bad = torch.empty((2,), dtype=torch.int32, device=dev)
+    _check(lib().u3d_det_store_pack(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(table), n_scenes, R, dim, int(num_classes), _ptr(ob),
+                                    _ptr(osc), _ptr(ol), out_rows, _ptr(off), _ptr(bad), _stream()), "det_store_pack")
+    return ob[:out_rows], osc[:out_rows], ol[:out_rows], off, bad

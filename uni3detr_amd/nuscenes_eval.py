@@ -678,6 +678,13 @@ class NuScenesEvaluator:
                 self._gt.append(tuple(torch.as_tensor(x, device=self.device) for x in
                                       (e.g_rows[-1], e.g_cls[-1].astype(np.int32), e.g_pts[-1], e.g_attr[-1].astype(np.int32))))
 
+    def add_store(self, store, infos):
+        """add() for every sample of a det_store.DetStore (box_dim 9) at once, in the store's scene order.  The predictions are encoded
+        on the host, so they come through store.results(): one copy per tensor for the whole dataset instead of one per batch.
+        Bit-identical to add() over the same samples in the same order."""
+        self.add(store.results(self.tab.C, ("nuscenes_eval: detection scores must be finite", "nuscenes_eval: labels must index class_names")),
+                 infos)
+
     def compute(self, logger="silent"):
         """-> ret_dict of `nuscenes_eval` over everything added (the summary goes to `logger`)."""
         if not len(self):
