@@ -724,6 +724,37 @@ int32_t u3d_det_store_pack(const float* st_boxes, const float* st_scores, const 
                            int32_t row_capacity, int32_t box_dim, int32_t num_classes, float* out_boxes, float* out_scores,
                            int32_t* out_labels, int32_t out_rows, int32_t* out_off, int32_t* bad, u3d_stream s);
 
+/* The stores of several ranks merged into one, in dataset order (csrc/det_store.hip; det_store.gather_stores: the counterpart of the
+ * reference's collect_results behind multi_gpu_test).  The W shards come in wire form - every rank's u3d_det_store_pack output padded
+ * to common sizes and stacked, as an all-gather leaves them:
+ *   sh_boxes f32 [W, Nmax, box_dim], sh_scores f32 [W, Nmax], sh_labels int32 [W, Nmax]
+ *   sh_off int32 [W, Smax + 1]       shard w's det_off: its local scene l holds the shard's rows sh_off[w][l] .. sh_off[w][l + 1] - 1
+ *   sh_head int32 [W, 2] = (scenes, rows) of every shard, on the device
+ *   scene_map int32 [n_scenes, 2] = (shard, local scene) of every scene to merge, in the order they are to appear
+ * and the destination is a store as u3d_det_store_append describes it (st_boxes .. invalid, R, S, M; invalid is not touched).
+ *   The n_scenes mapped scenes become scenes cursor[0] .. cursor[0] + n_scenes - 1 of the destination; their rows are written
+ *   compactly, in map order, from row cursor[1] on; table gets (first row, count) per scene, cursor[0] += n_scenes, cursor[1] += the
+ *   rows written.  A shard's offsets are read clamped into [0, rows of that shard] (a = clamp(sh_off[w][l]), b = clamp(sh_off[w][l + 1]):
+ *   the scene is the run of max(b - a, 0) rows from a), so no row outside the shard's own is read whatever sh_off holds.  A map entry
+ *   named twice is copied twice.
+ *   The call is REFUSED AS A WHOLE - it writes nothing to the store and increments cursor[3] - when the scenes would pass S or the
+ *   rows would pass R, when a cursor lies outside the store (cursor[0] outside [0, S], cursor[1] < 0), when a map entry names a shard
+ *   outside [0, W) or a local scene outside [0, scenes of that shard), or when a shard head lies outside [0, Smax] x [0, Nmax].
+ * Two launches: one workgroup validates, decides the refusal and scans the mapped counts into the workspace (u3d_det_store_merge_workspace
+ * (n_scenes) bytes, no contents required), O(n_scenes + W) reads in all; then one workgroup per scene copies its run and writes its
+ * table entry, and the first of them the cursor - the only writer of table / cursor, stream-ordered behind the only reader of the
+ * cursor.  No atomics on global memory, no allocation, no synchronisation, no host read; the bytes written are a function of the inputs
+ * alone: nothing at or past the used rows of the destination is read.  n_scenes == 0 validates the heads and the cursor and moves nothing.
+ * U3D_ERR_ARG: a null pointer (other than invalid with M == 0), W, Nmax, R or S <= 0, n_scenes, Smax or M < 0, box_dim not 7 or 9;
+ * U3D_ERR_UNSUPPORTED: R * box_dim or W * Nmax * box_dim >= 2^31; U3D_ERR_WORKSPACE: a workspace below
+ * u3d_det_store_merge_workspace(n_scenes).  Checked before any launch, in that order. */
+int64_t u3d_det_store_merge_workspace(int32_t n_scenes);
+int32_t u3d_det_store_merge(const float* sh_boxes, const float* sh_scores, const int32_t* sh_labels, const int32_t* sh_off,
+                            const int32_t* sh_head, int32_t n_shards, int32_t shard_rows, int32_t shard_scenes, int32_t box_dim,
+                            const int32_t* scene_map, int32_t n_scenes, float* st_boxes, float* st_scores, int32_t* st_labels,
+                            int32_t* table, int32_t* cursor, int32_t* invalid, int32_t row_capacity, int32_t scene_capacity,
+                            int32_t invalid_capacity, void* workspace, int64_t workspace_bytes, u3d_stream s);
+
 /* Second half of the strided-convolution input gradient (first half: P = dout @ [W_0^T | ... | W_{K-1}^T] with u3d_linear_bf16 on
  * the weight viewed as [K*Cin, Cout]): din[i][c] = sum_kappa P[nbr[kappa][i]][kappa*C + c], nbr = transposed table (mode 1 of
  * u3d_nbr_table / u3d_dense_nbr_table), f32 accumulation.  Replaces the dgrad half of spconv's indice_conv_backward / cuDNN dgrad

@@ -1,4 +1,4 @@
-// A device-resident store for the detections of a whole dataset (u3d_det_store_append / u3d_det_store_pack; include/u3d_hip.h states the
+// A device-resident store for the detections of a whole dataset (u3d_det_store_append / _pack / _merge; include/u3d_hip.h states the
 // semantics).  A finished DetBatch - the padded outputs of u3d_det_tail_pp behind u3d_det_gate - is appended stream-ordered, with no
 // host read; the store keeps the scenes in dataset order and is packed once into the flat layout the evaluators consume.
 //
@@ -16,6 +16,11 @@
 //   k_ds_offsets pack, launch 1.  One wave: out_off = exclusive scan of the table's counts, bad[] zeroed.
 //   k_ds_gather  pack, launch 2.  One workgroup per scene: its run of rows to out_off[scene], flat dword copies as above; a non-finite
 //                score or a label outside [0, num_classes) stores 1 to bad[0] / bad[1] (every writer stores the same value).
+//   k_dm_plan    merge, launch 1.  ONE workgroup: n_scenes is a dataset size, so the plan is made once and kept in the workspace - the
+//                refusal (heads, map entries, cursor, capacities) and, 256 scenes per step, the exclusive scan of the mapped counts
+//                (64-lane scans, the four wave totals through LDS).  It is the only reader of the cursor's first two entries.
+//   k_dm_copy    merge, launch 2.  One workgroup per scene: its run of shard rows to the planned place, flat dword copies as above, and
+//                its table entry; workgroup 0 writes the cursor (or counts the refusal).  The only writer of table / cursor.
 // Nothing here reads a store row at or past the used rows, so the bytes written depend on the inputs alone.
 #include "common.h"
 
@@ -237,6 +242,130 @@ extern "C" int32_t u3d_det_store_pack(const float* st_boxes, const float* st_sco
   if (n_scenes > 0)
     hipLaunchKernelGGL(k_ds_gather, dim3(n_scenes), dim3(DS_THREADS), 0, s, st_boxes, st_scores, st_labels, table, row_capacity, box_dim,
                        num_classes, out_off, out_rows, out_boxes, out_scores, out_labels, bad);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+// ---- merge: the shards of several ranks into one store ----------------------------------------------------------------------------
+// workspace, int32: [0] refuse, [1] cursor[0] as read, [2] cursor[1] as read, [3] rows used after the call; then per mapped scene
+// (first row in the store, count, first row in the flattened shards [W * Nmax])
+#define DM_HEAD 4
+#define DM_REC 3
+
+__global__ __launch_bounds__(DS_THREADS) void k_dm_plan(const int* __restrict__ sh_off, const int* __restrict__ sh_head, int W, int Nmax,
+                                                        int Smax, const int* __restrict__ map, int n, const int* __restrict__ cursor, int R,
+                                                        int S, int* __restrict__ ws) {
+  __shared__ long long wave_sum[DS_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cur_s = cursor[0], cur_r = cursor[1];
+  int bad = 0;
+  for (int w = tid; w < W; w += DS_THREADS) {
+    const int hs = sh_head[2 * w], hr = sh_head[2 * w + 1];
+    bad |= (hs < 0 || hs > Smax || hr < 0 || hr > Nmax) ? 1 : 0;
+  }
+  long long carry = cur_r;
+  for (int base = 0; base < n; base += DS_THREADS) {                   // (uniform trip count: the barriers below are reached by all)
+    const int i = base + tid;
+    int cnt = 0, src = 0;
+    if (i < n) {
+      const int w = map[2 * (long long)i], l = map[2 * (long long)i + 1];
+      bool ok = false;
+      if (w >= 0 && w < W) {
+        const int hs = sh_head[2 * w], hr = sh_head[2 * w + 1];
+        if (hs >= 0 && hs <= Smax && hr >= 0 && hr <= Nmax && l >= 0 && l < hs) {      // no index below is taken on trust
+          const int* off = sh_off + (long long)w * (Smax + 1) + l;
+          const int a = min(max(off[0], 0), hr), b = min(max(off[1], 0), hr);
+          cnt = max(b - a, 0);
+          src = w * Nmax + a;                                          // + cnt <= (w + 1) * Nmax: inside shard w
+          ok = true;
+        }
+      }
+      bad |= ok ? 0 : 1;
+    }
+    long long incl = cnt;
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long u = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += u;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    long long pre = 0, tot = 0;
+    for (int k = 0; k < DS_WAVES; ++k) {
+      const long long v = wave_sum[k];
+      if (k < wave) pre += v;
+      tot += v;
+    }
+    if (i < n) {
+      int* rec = ws + DM_HEAD + DM_REC * (long long)i;
+      rec[0] = (int)(carry + pre + incl - cnt);                        // meaningful when the call is not refused: then <= R
+      rec[1] = cnt;
+      rec[2] = src;
+    }
+    carry += tot;
+    __syncthreads();
+  }
+  const int any_bad = __syncthreads_or(bad);
+  if (tid == 0) {
+    const bool outside = cur_s < 0 || cur_s > S || cur_r < 0;
+    ws[0] = (any_bad || outside || (long long)cur_s + n > (long long)S || carry > (long long)R) ? 1 : 0;
+    ws[1] = cur_s;
+    ws[2] = cur_r;
+    ws[3] = (int)carry;
+  }
+}
+
+__global__ __launch_bounds__(DS_THREADS) void k_dm_copy(const float* __restrict__ sh_boxes, const float* __restrict__ sh_scores,
+                                                        const int* __restrict__ sh_labels, int D, int n, const int* __restrict__ ws,
+                                                        float* __restrict__ st_boxes, float* __restrict__ st_scores,
+                                                        int* __restrict__ st_labels, int* __restrict__ table, int* __restrict__ cursor) {
+  const int scene = blockIdx.x, tid = threadIdx.x;
+  if (ws[0]) {                                                         // uniform over the grid
+    if (scene == 0 && tid == 0) cursor[3] = cursor[3] + 1;
+    return;
+  }
+  const int cur_s = ws[1];
+  if (scene < n) {                                                     // (n == 0 still launches workgroup 0, for the cursor)
+    const int* rec = ws + DM_HEAD + DM_REC * (long long)scene;
+    const int dst = rec[0], c = rec[1], src = rec[2];                  // dst + c <= R, src + c inside its shard: checked by the plan
+    const float* sb = sh_boxes + (long long)src * D;
+    float* db = st_boxes + (long long)dst * D;
+    for (int i = tid; i < c * D; i += DS_THREADS) db[i] = sb[i];
+    for (int i = tid; i < c; i += DS_THREADS) {
+      st_scores[dst + i] = sh_scores[src + i];
+      st_labels[dst + i] = sh_labels[src + i];
+    }
+    if (tid == 0) {
+      table[2 * ((long long)cur_s + scene)] = dst;                     // cur_s + n <= S: checked by the plan
+      table[2 * ((long long)cur_s + scene) + 1] = c;
+    }
+  }
+  if (scene == 0 && tid == 0) {
+    cursor[0] = cur_s + n;
+    cursor[1] = ws[3];
+  }
+}
+
+extern "C" int64_t u3d_det_store_merge_workspace(int32_t n_scenes) {
+  return 4ll * (DM_HEAD + DM_REC * (long long)max(n_scenes, 0));
+}
+
+extern "C" int32_t u3d_det_store_merge(const float* sh_boxes, const float* sh_scores, const int32_t* sh_labels, const int32_t* sh_off,
+                                       const int32_t* sh_head, int32_t n_shards, int32_t shard_rows, int32_t shard_scenes, int32_t box_dim,
+                                       const int32_t* scene_map, int32_t n_scenes, float* st_boxes, float* st_scores, int32_t* st_labels,
+                                       int32_t* table, int32_t* cursor, int32_t* invalid, int32_t row_capacity, int32_t scene_capacity,
+                                       int32_t invalid_capacity, void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  U3D_REQUIRE(sh_boxes && sh_scores && sh_labels && sh_off && sh_head && scene_map && st_boxes && st_scores && st_labels && table &&
+              cursor && workspace && n_shards > 0 && shard_rows > 0 && shard_scenes >= 0 && n_scenes >= 0 && row_capacity > 0 &&
+              scene_capacity > 0 && invalid_capacity >= 0 && (invalid || invalid_capacity == 0) && (box_dim == 7 || box_dim == 9),
+              U3D_ERR_ARG);
+  U3D_REQUIRE((long long)row_capacity * box_dim < (1ll << 31) && (long long)n_shards * shard_rows * box_dim < (1ll << 31),
+              U3D_ERR_UNSUPPORTED);
+  U3D_REQUIRE(workspace_bytes >= u3d_det_store_merge_workspace(n_scenes), U3D_ERR_WORKSPACE);
+  int* ws = (int*)workspace;
+  hipLaunchKernelGGL(k_dm_plan, dim3(1), dim3(DS_THREADS), 0, s, sh_off, sh_head, n_shards, shard_rows, shard_scenes, scene_map, n_scenes,
+                     cursor, row_capacity, scene_capacity, ws);
+  hipLaunchKernelGGL(k_dm_copy, dim3(max(n_scenes, 1)), dim3(DS_THREADS), 0, s, sh_boxes, sh_scores, sh_labels, box_dim, n_scenes, ws,
+                     st_boxes, st_scores, st_labels, table, cursor);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

@@ -2565,3 +2565,34 @@ def det_store_pack(boxes, scores, labels, table, n_scenes, out_rows, num_classes
     _check(lib().u3d_det_store_pack(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(table), n_scenes, R, dim, int(num_classes), _ptr(ob),
                                     _ptr(osc), _ptr(ol), out_rows, _ptr(off), _ptr(bad), _stream()), "det_store_pack")
     return ob[:out_rows], osc[:out_rows], ol[:out_rows], off, bad
+
+
+def det_store_merge_workspace(n_scenes):
+    """bytes of scratch u3d_det_store_merge wants for n_scenes mapped scenes"""
+    return int(lib().u3d_det_store_merge_workspace(int(n_scenes)))
+
+
+def det_store_merge(sh_boxes, sh_scores, sh_labels, sh_off, sh_head, scene_map, boxes, scores, labels, table, cursor, invalid,
+                    workspace=None):
+    """The shards of several ranks into a store's buffers, in the order of scene_map (u3d_det_store_merge; two launches, no host sync).
+    sh_boxes [W,Nmax,D], sh_scores [W,Nmax], sh_labels int32 [W,Nmax], sh_off int32 [W,Smax+1], sh_head int32 [W,2] = (scenes, rows),
+    scene_map int32 [n,2] = (shard, local scene); boxes .. invalid are the store as det_store_append takes it.  A call that does not fit
+    or names what no shard holds is refused on the device (cursor[3]).  workspace: a device buffer of det_store_merge_workspace(n) bytes
+    (None: allocated here)."""
+    W, Nmax, dim = sh_boxes.shape
+    n, Smax = int(scene_map.shape[0]), int(sh_off.shape[1]) - 1
+    assert sh_boxes.dtype == torch.float32 and sh_scores.dtype == torch.float32 and sh_labels.dtype == torch.int32
+    assert sh_scores.shape == (W, Nmax) and sh_labels.shape == (W, Nmax) and sh_off.dtype == torch.int32 and sh_off.shape == (W, Smax + 1)
+    assert sh_head.dtype == torch.int32 and sh_head.shape == (W, 2) and scene_map.dtype == torch.int32 and scene_map.shape == (n, 2)
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == dim
+    R, S, M = int(boxes.shape[0]), int(table.shape[0]), int(invalid.shape[0])
+    assert scores.numel() == R and labels.numel() == R and labels.dtype == torch.int32
+    assert table.dtype == torch.int32 and table.shape == (S, 2) and cursor.dtype == torch.int32 and cursor.numel() == 4
+    assert invalid.dtype == torch.int32 and invalid.shape == (M, 2)
+    need = det_store_merge_workspace(n)                    # (below: an empty map has no address; with n == 0 the pointer is not read)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=boxes.device)
+    _check(lib().u3d_det_store_merge(_ptr(sh_boxes), _ptr(sh_scores), _ptr(sh_labels), _ptr(sh_off), _ptr(sh_head), W, Nmax, Smax, dim,
+                                     _ptr(scene_map if n else sh_head), n, _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(table),
+                                     _ptr(cursor), _ptr(invalid) if M else None, R, S, M, _ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), _stream()), "det_store_merge")

@@ -8,8 +8,65 @@ loop of the reference's extra_tools/test.py -> single_gpu_test, without its per-
 
 Per batch: on_batch(i), step.run(batch), store.append(step.det, n_live=step.n_live, valid=step.valid) - for a packed dict no host read
 follows, the replays queue up behind each other.  After the loop the batches whose replay was invalid (store.invalid_batches(), one
-host read) are run again eagerly and exact-size and put into their places.  One device, no aug_test.
+host read) are run again eagerly and exact-size and put into their places.  No aug_test.
+
+Several ranks: ShardPlan deals the one-device loop's batches out round robin, every rank runs test_dataset
+on its share into its own store, and det_store.gather_stores merges the stores on the device, in dataset order, on every rank:
+
+    plan = ShardPlan(len(samples), B, world)
+    store = DetStore(max(plan.scenes(rank), 1), K, 7, "cuda")
+    with BatchFeeder(samples, plan.order(rank), pipe, batch_size=B, drop_last=False) as feeder:
+        test_dataset(step, feeder, store, reload=..., on_batch=seed_by_global_batch, batch_ids=plan.batch_ids(rank))
+    whole = gather_stores(store, plan, num_classes=C); evaluator.add_store(whole, gt_boxes, gt_labels)
 """
+import numpy as np
+
+
+class ShardPlan:
+    """Which rank runs which batch of a dataset of n_scenes in batches of batch_size.  Global batch j - dataset positions j * B ..
+    min((j + 1) * B, n) - 1, exactly the one-device loop's batch j - goes to rank j % world as that rank's local batch j // world.  Only
+    the globally last batch can be partial, and it is the last local batch of its rank, so a rank's scenes number contiguously in
+    its own store.  A rank without batches (world > number of batches) is legal: zero scenes.  Pure host code."""
+
+    def __init__(self, n_scenes, batch_size, world):
+        n, B, W = int(n_scenes), int(batch_size), int(world)
+        if n < 0 or B < 1 or W < 1:
+            raise ValueError(f"ShardPlan(n_scenes={n}, batch_size={B}, world={W}): n_scenes >= 0, batch_size and world >= 1")
+        self.n_scenes, self.batch_size, self.world = n, B, W
+        self.n_batches = -(-n // B)
+
+    def _rank(self, rank):
+        r = int(rank)
+        if not 0 <= r < self.world:
+            raise ValueError(f"ShardPlan: rank {r} of a world of {self.world}")
+        return r
+
+    def batch_ids(self, rank):
+        """-> the global index of each local batch of `rank`, in local order"""
+        return list(range(self._rank(rank), self.n_batches, self.world))
+
+    def order(self, rank, order=None):
+        """-> the rank's sample order for BatchFeeder(..., drop_last=False): the entries of `order` (default: 0 .. n_scenes - 1, the
+        dataset positions themselves) at the positions of its batches"""
+        B, n = self.batch_size, self.n_scenes
+        if order is not None:
+            order = list(order)
+            if len(order) != n:
+                raise ValueError(f"ShardPlan.order: an order of {len(order)} entries for {n} scenes")
+        pos = [p for j in self.batch_ids(rank) for p in range(j * B, min((j + 1) * B, n))]
+        return pos if order is None else [order[p] for p in pos]
+
+    def scenes(self, rank):
+        """-> how many scenes `rank` runs"""
+        B, n = self.batch_size, self.n_scenes
+        return sum(min((j + 1) * B, n) - j * B for j in self.batch_ids(rank))
+
+    def scene_map(self):
+        """-> int32 [n_scenes, 2]: (shard, local scene) of every dataset position - u3d_det_store_merge's scene_map"""
+        B, W = self.batch_size, self.world
+        pos = np.arange(self.n_scenes, dtype=np.int64)
+        j = pos // B
+        return np.stack([j % W, (j // W) * B + pos % B], 1).astype(np.int32)
 
 
 def _scenes(batch):
@@ -20,7 +77,7 @@ def _scenes(batch):
     return list(batch)
 
 
-def test_dataset(step, batches, store, reload=None, on_batch=None):
+def test_dataset(step, batches, store, reload=None, on_batch=None, batch_ids=None):
     """step: a captured inference.InferenceStep; batches: any iterable of what step.run takes (a feeder.BatchFeeder yields packed dicts;
     a last dict with fewer scenes than the step's batch goes through run's list form, which pads and gates - that one batch costs a
     host read; a list holds 1 .. B scenes, as run() demands); store: a det_store.DetStore with room for the dataset - its
@@ -29,7 +86,11 @@ def test_dataset(step, batches, store, reload=None, on_batch=None):
     so a caller who wants reproducible results seeds there.
     reload(i): returns the scenes of batch i again (a list of point tensors or a packed dict) for the repair of an invalid replay - the
     loop keeps no batch, a feeder's slots are reused.  Each repaired batch is counted in step.fallbacks; an invalid batch without
-    `reload` raises RuntimeError.  -> store."""
+    `reload` raises RuntimeError.
+    batch_ids: the global index of every batch of this loop (ShardPlan.batch_ids(rank)) - on_batch and reload then receive batch_ids[i]
+    in place of i, and the messages name that batch, so that a rank seeds and reloads by the batch's place in the dataset as the
+    one-device loop does.  None: the loop's own count.  -> store."""
+    gid = (lambda i: i) if batch_ids is None else (lambda i: batch_ids[i])
     base = first = len(store)            # (a host read before anything is in flight) a store may already hold an earlier part
     starts = {}
     for i, batch in enumerate(batches):
@@ -41,7 +102,7 @@ def test_dataset(step, batches, store, reload=None, on_batch=None):
             batch = list(batch)
             n = len(batch)
         if on_batch is not None:
-            on_batch(i)
+            on_batch(gid(i))
         step.run(batch)
         store.append(step.det, n_live=step.n_live, valid=step.valid)
         starts[first] = (i, n)
@@ -52,7 +113,7 @@ def test_dataset(step, batches, store, reload=None, on_batch=None):
         if starts.get(scene, (None, None))[1] != n:
             raise RuntimeError(f"test_dataset: the store reports an invalid batch of scenes {scene} .. {scene + n - 1} that this loop did "
                                "not append")
-        i = starts[scene][0]
+        i = gid(starts[scene][0])
         if reload is None:
             raise RuntimeError(f"test_dataset: the replay of batch {i} (scenes {scene} .. {scene + n - 1}) was invalid (a sparse level "
                                "over its capacity, an FPS time-out or a scene cut to point_capacity) and no reload= was given to run it again")
