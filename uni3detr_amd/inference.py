@@ -58,6 +58,7 @@ from torch import nn
 
 from . import native as nv
 from . import sparse as sp
+from . import static_batch as sb
 
 _WHY_NARROW = "narrow level ({cin} -> {cout} channels): direct-operand kernels read `bias` as an addend"
 _WHY_INPUT = "conv_input: {cin} -> {cout} channels on its own kernel"
@@ -411,7 +412,7 @@ class InferenceStep:
         res = step.results(points)    # simple_test_batched's list of dicts on the host; the eager path when the replay was invalid
         step.valid, step.fallbacks, step.overflows()
 
-    Inputs are TrainStep's capacity mode without GT: `cat` f32 [B * P, F] of which scene_off[B] rows are live, lens = [P] * B.  `points`
+    Inputs are a static_batch.StaticBatch without GT: `cat` f32 [B * P, F] of which scene_off[B] rows are live, lens = [P] * B.  `points`
     is a list of 1 .. B tensors [n <= P, F] (fewer than B: padded with copies of scene 0, which the gate empties again) or the dict a
     DevicePipeline returns (exactly B scenes; loaded by u3d_batch_ingest, no host read).  The strided sparse levels are sized by
     capture() from sample batches; static shapes are switched on only inside the step's own forward, so `inf.simple_test*` keep
@@ -451,18 +452,14 @@ class InferenceStep:
 
     # ---- static buffers ---------------------------------------------------------------------------------------------------
     def _alloc(self):
-        """TrainStep._alloc_capacity_buffers without the GT: one spare row behind `cat` (an empty LAST scene makes the FPS gather read
-        the row at scene_off[B]).  Allocated once: a graph keeps these addresses."""
+        """The point buffers without GT, this step's flag, FPS time-out record and `valid`.  Allocated once: a graph keeps these addresses."""
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("InferenceStep: the model is not on a GPU")
-        B, P = self.batch_size, self.point_capacity
         self.dev = dev
-        self.pts = dict(cat=torch.zeros((B * P + 1, self.feat), dtype=torch.float32, device=dev)[:B * P],
-                        scene_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), lens=[P] * B)
-        self._ingest_flag = torch.zeros(1, dtype=torch.float32, device=dev)     # the bound batch had a scene cut to P
-        self._ingest_over = torch.zeros(2, dtype=torch.int32, device=dev)       # such batches so far (overflows())
-        self._n_live = torch.full((1,), B, dtype=torch.int32, device=dev)
+        self._buf = sb.StaticBatch(self.batch_size, self.point_capacity, self.feat, dev)
+        self.pts = self._buf.pts
+        self._n_live = torch.full((1,), self.batch_size, dtype=torch.int32, device=dev)
         self._flag = torch.zeros(1, dtype=torch.float32, device=dev)
         self._fps_err = nv.fps_err_buffer(dev)
         self.valid = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -471,38 +468,16 @@ class InferenceStep:
         """Load a batch into the static buffers on the current stream -> the number of live scenes."""
         if self.pts is None:
             self._alloc()
-        B, P, cat = self.batch_size, self.point_capacity, self.pts["cat"]
+        B = self.batch_size
         if isinstance(points, dict):
-            if "sweeps" in points:
-                raise ValueError("InferenceStep: the batch still carries batch['sweeps'] - run the pipeline's LoadPointsFromMultiSweeps first")
-            pts, off, cnt = points["points"], points["scene_off"], points.get("count")
-            if not all(t is None or (torch.is_tensor(t) and t.device == cat.device) for t in (pts, off, cnt)):
-                raise ValueError(f"InferenceStep: every tensor of the batch must live on {cat.device}")
-            if pts.dim() != 2 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[1] != cat.shape[1]:
-                raise ValueError(f"InferenceStep: points must be contiguous float32 [n, {cat.shape[1]}], got {pts.dtype} {tuple(pts.shape)}")
-            if off.numel() != B + 1:
-                raise ValueError(f"InferenceStep: {off.numel() - 1} scenes, the step was built for {B}")
-            for t, n, what in ((off, B + 1, "scene_off"), (cnt, B, "count")):
-                if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
-                    raise ValueError(f"InferenceStep: {what} must be a contiguous int32 tensor of {n} elements")
-            self._ingest_flag.zero_()
-            nv.batch_ingest(pts, off, cnt, P, cat, self.pts["scene_off"], self._ingest_flag, overflow=self._ingest_over)
-            self._n_live.fill_(B)
-            return B
-        points = list(points)
-        n = len(points)
-        if not 1 <= n <= B:
-            raise ValueError(f"InferenceStep: {n} scenes, the step was built for 1 .. {B}")
-        if any(p.dim() != 2 or int(p.shape[1]) != cat.shape[1] for p in points):
-            raise ValueError(f"InferenceStep: points must have {cat.shape[1]} columns")
-        if any(p.device != cat.device for p in points):
-            raise ValueError(f"InferenceStep: every scene must live on {cat.device}")
-        if max(int(p.shape[0]) for p in points) > P:
-            raise ValueError(f"InferenceStep: a scene of {max(int(p.shape[0]) for p in points)} points exceeds point_capacity {P}")
-        packed = self.model.pack_points(points + [points[0]] * (B - n))        # the last batch of a dataset: padded, gated away again
-        cat[:packed["cat"].shape[0]].copy_(packed["cat"])
-        self.pts["scene_off"].copy_(packed["scene_off"])
-        self._ingest_flag.zero_()
+            self._buf.bind_packed(points, "InferenceStep:")
+            n = B
+        else:
+            points = list(points)
+            n = len(points)
+            if not 1 <= n <= B:
+                raise ValueError(f"InferenceStep: {n} scenes, the step was built for 1 .. {B}")
+            self._buf.bind_scenes(self.model, points + [points[0]] * (B - n), "InferenceStep:")      # the last batch of a dataset: padded, gated away again
         self._n_live.fill_(n)
         return n
 
@@ -518,13 +493,6 @@ class InferenceStep:
         finally:
             m.static_shapes, enc.level_capacities, m.fps_err = prev
 
-    def _fps_can_time_out(self):
-        """TrainStep._fps_can_time_out for eval: only sets above native.FPS_REG_MAX points run on workgroups that wait for each other."""
-        m = self.model
-        if getattr(m, "fps_max_wg", 0) == 1:
-            return False
-        return max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])) > nv.FPS_REG_MAX
-
     @torch.no_grad()
     def _forward(self):
         """A straight line on one stream (extract_pts_feat would fork the FPS onto a side stream: parallel branches in a graph)."""
@@ -535,33 +503,20 @@ class InferenceStep:
             feat = m.stage_features(v)
             self.head_outs = m.pts_bbox_head(feat, None, fps)
             self.det = m.pts_bbox_head.get_bboxes_batched(self.head_outs, None)
-            # the three sources of TrainStep._stage1_head's hold flag
-            enc = m.pts_middle_encoder
-            cnts, cps = list(enc.last_level_counts[1:1 + len(self._caps)]), list(self._caps)
-            if self._fps_can_time_out():
-                cnts, cps = cnts + [self._fps_err[:1]], cps + [0]
-            if cnts:
-                nv.capacity_flag(cnts, cps, self._flag)
-            else:
-                self._flag.zero_()
-            self._flag.add_(self._ingest_flag)
+            times_out = sb.fps_can_time_out(m, max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])))
+            sb.validity_flag(m, self._caps, self._fps_err if times_out else None, self._buf.ingest_flag, self._flag)
             nv.det_gate(self.det, self._flag, self._n_live, self.valid)
             self.det.valid = self.valid
 
     def _drop_outputs(self):
-        """Drop every reference to an eager iteration's outputs BEFORE capturing (TrainStep._drop_step_state)."""
-        import gc
+        """Drop every reference to an eager iteration's outputs BEFORE capturing (static_batch.drop_decoder_outputs says why)."""
         self.det = self.head_outs = None
         self.model.pts_middle_encoder.last_level_counts = []
-        dec = getattr(getattr(self.model.pts_bbox_head, "transformer", None), "decoder", None)
-        if dec is not None:
-            dec._reg_outputs = dec._states_c = dec._cls_outputs = dec._iou_outputs = dec._coord_outputs = dec._refs_sig = None
-        gc.collect()
-        torch.cuda.synchronize()
+        sb.drop_decoder_outputs(self.model)
 
     def capture(self, batches, margin=1.25, warmup=3):
         """Size the strided sparse levels from exact-size eager forwards over `batches` (each what run() takes; the largest count per
-        level x margin, rounded up to a multiple of 256 - TrainStep.measure_capacities), warm up, capture.  -> (counts, caps).  May be
+        level x margin, rounded up to a multiple of 256 - static_batch.level_capacity), warm up, capture.  -> (counts, caps).  May be
         called again, e.g. with a batch that overflowed added: the previous graph is dropped."""
         batches = list(batches)
         if not batches:
@@ -572,26 +527,19 @@ class InferenceStep:
         if self.pts is not None:
             self._drop_outputs()
         enc = self.model.pts_middle_encoder
-        counts = None
+        seen = []
         for b in batches:
             self._bind(b)
             off = self.pts["scene_off"].tolist()
             exact = dict(cat=self.pts["cat"][:off[-1]], scene_off=self.pts["scene_off"], lens=[off[i + 1] - off[i] for i in range(len(off) - 1)])
             with torch.no_grad(), self.inf.scope():       # the counts come from the encoder: no FPS, no head
                 self.model.stage_features(self.model.stage_voxelize(exact))
-            c = [int(c.item()) for c in enc.last_level_counts]
-            counts = c if counts is None else [max(a, b_) for a, b_ in zip(counts, c)]
-        self._caps = [((int(c * margin) + 255) // 256) * 256 for c in counts[1:]]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):                      # static-shape eager warm-up on the capture stream
-                self._forward()
-        torch.cuda.current_stream().wait_stream(s)
+            seen.append([int(c.item()) for c in enc.last_level_counts])
+        counts = sb.max_level_counts(seen)
+        self._caps = [sb.level_capacity(c, margin) for c in counts[1:]]
+        s = sb.warm_up(self._forward, warmup)            # static-shape eager warm-up on the capture stream
         self._drop_outputs()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-            self._forward()
+        g = sb.capture_graph(self._forward, s)
         torch.cuda.synchronize()
         self._graph = g
         return counts, list(self._caps)
@@ -624,4 +572,4 @@ class InferenceStep:
 
     def overflows(self):
         """Packed batches the ingest had to cut to point_capacity so far (their replays were invalid).  One small device-to-host read."""
-        return 0 if self.pts is None else int(self._ingest_over.sum().item())
+        return 0 if self.pts is None else int(self._buf.ingest_over.sum().item())

@@ -24,7 +24,6 @@ PointSample): set_packed_batch() fills the static buffers from a DevicePipeline 
 the capacity is cut and raises the same HOLD flag.
 """
 import contextlib
-import gc
 import math
 import os
 import sys
@@ -36,6 +35,7 @@ import torch.distributed as dist
 
 from . import native as nv
 from . import sparse as _sp
+from . import static_batch as _sb
 from .plugin import transformer as _T
 
 
@@ -230,7 +230,9 @@ class TrainStep:
             self.pts = model.pack_points(points) if not isinstance(points, dict) else points
             self.gts = self._pack_gts_static(gt_bboxes_3d, gt_labels_3d) if not isinstance(gt_bboxes_3d, dict) else gt_bboxes_3d
         else:
-            self._alloc_capacity_buffers(points, gt_bboxes_3d)
+            G = max(int(gt_capacity), max((int(g.tensor.shape[0] if hasattr(g, "tensor") else g.shape[0]) for g in gt_bboxes_3d), default=0), 1)
+            self._buf = _sb.StaticBatch(len(points), point_capacity, points[0].shape[1], self.dev, G, model.pts_bbox_head.gt_dim)
+            self.pts, self.gts = self._buf.pts, self._buf.gts
             self.set_batch(points, gt_bboxes_3d, gt_labels_3d)
         self.labels = gt_labels_3d
         self.capacity_margin = capacity_margin
@@ -238,93 +240,18 @@ class TrainStep:
         self.loss = None
 
     # ---- batches --------------------------------------------------------------------------------------------------------
-    def _alloc_capacity_buffers(self, points, gt_bboxes_3d):
-        """Capacity mode: `cat` holds B * P rows of which scene_off[B] are live (the detector and its kernels take `lens` = [P] * B as
-        upper bounds and read the real extents from scene_off on the device), the GT buffers B * G rows as in _pack_gts_static.  One
-        spare row behind `cat`: an empty LAST scene makes the FPS gather read the row at scene_off[B] (its value cannot matter: all
-        samples of an empty set are that one row, the unit-cube map of a single point is 0 / 0)."""
-        B, P, F_ = len(points), self.point_capacity, int(points[0].shape[1])
-        G = max(int(self.gt_capacity), max((int(g.tensor.shape[0] if hasattr(g, "tensor") else g.shape[0]) for g in gt_bboxes_3d), default=0), 1)
-        gd = int(self.model.pts_bbox_head.gt_dim)
-        dev = self.dev
-        self.pts = dict(cat=torch.zeros((B * P + 1, F_), dtype=torch.float32, device=dev)[:B * P],
-                        scene_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), lens=[P] * B)
-        self.gts = dict(gt=torch.zeros((B * G, gd), dtype=torch.float32, device=dev), labels=torch.zeros(B * G, dtype=torch.int32, device=dev),
-                        gt_off=torch.zeros(B + 1, dtype=torch.int32, device=dev), gmax=G)
-        # [0]: the bound batch had a scene cut to P or G (ORed into the step's HOLD flag, _stage1_head); counters: calls of
-        # set_packed_batch that cut (points, boxes), read with the held-step counter
-        self._ingest_flag = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._ingest_over = torch.zeros(2, dtype=torch.int32, device=dev)
-
     def set_packed_batch(self, batch):
-        """Capacity mode: load the batch dict a DevicePipeline returns (points, scene_off[, count], gt_bboxes_3d, gt_off[, gt_count],
-        gt_labels_3d) INTO the static buffers with u3d_batch_ingest on the current stream - no device-to-host copy, no host
-        synchronisation.  The host checks what it knows without a read (scene count, columns, dtypes, devices); what only the device
-        knows is handled there: a scene above the point capacity or above `gmax` boxes is cut to it and the step's update is held
-        (ingest_overflows() counts such batches; step() raises at its periodic check)."""
+        """Capacity mode: static_batch.bind_packed of the batch dict a DevicePipeline returns (with gt_bboxes_3d, gt_labels_3d, gt_off).  A
+        scene it had to cut holds the step's update (ingest_overflows() counts such batches; step() raises at its periodic check)."""
         if self.point_capacity is None:
             raise RuntimeError("set_packed_batch needs a TrainStep built with point_capacity=P (capacity mode)")
-        if "sweeps" in batch:
-            raise ValueError("set_packed_batch: the batch still carries batch['sweeps'] - run the pipeline's LoadPointsFromMultiSweeps first")
-        pts, off = batch["points"], batch["scene_off"]
-        cat, B = self.pts["cat"], len(self.pts["lens"])
-
-        def dev_ok(t):
-            return t is None or (torch.is_tensor(t) and t.device == cat.device)
-
-        def i32(t, n, what):
-            if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
-                raise ValueError(f"set_packed_batch: {what} must be a contiguous int32 tensor of {n} elements")
-
-        g, lab, go = batch.get("gt_bboxes_3d"), batch.get("gt_labels_3d"), batch.get("gt_off")
-        cnt, gcnt = batch.get("count"), batch.get("gt_count")
-        if not all(dev_ok(t) for t in (pts, off, cnt, g, lab, go, gcnt)):
-            raise ValueError(f"set_packed_batch: every tensor of the batch must live on {cat.device}")
-        if pts.dim() != 2 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[1] != cat.shape[1]:
-            raise ValueError(f"set_packed_batch: points must be contiguous float32 [n, {cat.shape[1]}], got {pts.dtype} {tuple(pts.shape)}")
-        if off.numel() != B + 1:
-            raise ValueError(f"set_packed_batch: {off.numel() - 1} scenes, the step was built for {B}")
-        i32(off, B + 1, "scene_off"); i32(cnt, B, "count")
-        if g is not None:
-            if g.dim() != 2 or g.dtype != torch.float32 or not g.is_contiguous() or g.shape[1] not in (7, 9):
-                raise ValueError(f"set_packed_batch: gt_bboxes_3d must be contiguous float32 [g, 7 | 9], got {g.dtype} {tuple(g.shape)}")
-            if lab is None or go is None:
-                raise ValueError("set_packed_batch: gt_bboxes_3d needs gt_labels_3d and gt_off")
-            i32(lab, g.shape[0], "gt_labels_3d"); i32(go, B + 1, "gt_off"); i32(gcnt, B, "gt_count")
-        self._ingest_flag.zero_()
-        nv.batch_ingest(pts, off, cnt, self.point_capacity, cat, self.pts["scene_off"], self._ingest_flag, gt=g, gt_labels=lab, gt_off=go,
-                        gt_count=gcnt, gt_cap=int(self.gts["gmax"]), gt_out=self.gts["gt"], labels_out=self.gts["labels"],
-                        gt_off_out=self.gts["gt_off"], overflow=self._ingest_over)
-
-    def _set_batch_capacity(self, points, gt_bboxes_3d, gt_labels_3d):
-        """set_batch in capacity mode for lists of tensors: the sizes are known on the host, so nothing is cut - a scene above the
-        point capacity or above gmax raises before anything is written."""
-        P, B = self.point_capacity, len(self.pts["lens"])
-        if len(points) != B or len(gt_bboxes_3d) != B:
-            raise ValueError(f"set_batch: {len(points)} scenes, the step was built for {B}")
-        lens = [int(p.shape[0]) for p in points]
-        if max(lens) > P:
-            raise ValueError(f"set_batch: a scene of {max(lens)} points exceeds point_capacity {P}")
-        if any(int(p.shape[1]) != self.pts["cat"].shape[1] for p in points):
-            raise ValueError(f"set_batch: points must have {self.pts['cat'].shape[1]} columns")
-        d = self.model.pts_bbox_head.pack_gts(gt_bboxes_3d, gt_labels_3d, self.dev)
-        if int(d["gmax"]) > int(self.gts["gmax"]):
-            raise ValueError(f"set_batch: {int(d['gmax'])} boxes in one scene exceed the capacity {int(self.gts['gmax'])}")
-        pts = self.model.pack_points(points)
-        n, g = sum(lens), d["gt"].shape[0]
-        self.pts["cat"][:n].copy_(pts["cat"])
-        self.pts["scene_off"].copy_(pts["scene_off"])
-        self.gts["gt"][:g].copy_(d["gt"])
-        self.gts["labels"][:g].copy_(d["labels"])
-        self.gts["gt_off"].copy_(d["gt_off"])
-        self._ingest_flag.zero_()
+        _sb.refuse_sweeps(batch, "set_packed_batch:")       # (bind_packed's first refusal, made before self's buffers are looked up)
+        self._buf.bind_packed(batch, "set_packed_batch:")
 
     def ingest_overflows(self):
         """Batches set_packed_batch had to cut (a scene above point_capacity, or above gmax boxes) since the last check; their steps
         were held.  One small device-to-host read, made where held_steps() is read."""
-        if self.point_capacity is None:
-            return 0
-        return int(self._ingest_over.sum().item())
+        return 0 if self.point_capacity is None else int(self._buf.ingest_over.sum().item())
 
     def _pack_gts_static(self, gt_bboxes_3d, gt_labels_3d):
         """GT buffers with a fixed per-scene capacity (`gt_capacity` boxes): the captured graphs size the cost matrix by the capacity
@@ -345,19 +272,22 @@ class TrainStep:
         with must hold: same number of scenes, the same number of points per scene, at most `gmax` boxes per scene - anything else
         raises (build a new TrainStep / call capture() again for a different shape).  Capacity mode (point_capacity=P): lists of
         tensors of any per-scene size up to P; beyond P or gmax raises ValueError before anything is written."""
-        if self.point_capacity is not None and not isinstance(points, dict):
-            return self._set_batch_capacity(points, gt_bboxes_3d, gt_labels_3d)
-        pts = self.model.pack_points(points) if not isinstance(points, dict) else points
-        if list(pts["lens"]) != list(self.pts["lens"]) or pts["cat"].shape != self.pts["cat"].shape:
-            raise ValueError(f"set_batch: points per scene {list(pts['lens'])} differ from the captured layout {list(self.pts['lens'])}")
+        capacity = self.point_capacity is not None and not isinstance(points, dict)
+        if not capacity:              # (capacity: the sizes are known on the host, bind_scenes below refuses what does not fit)
+            pts = self.model.pack_points(points) if not isinstance(points, dict) else points
+            if list(pts["lens"]) != list(self.pts["lens"]) or pts["cat"].shape != self.pts["cat"].shape:
+                raise ValueError(f"set_batch: points per scene {list(pts['lens'])} differ from the captured layout {list(self.pts['lens'])}")
         d = self.model.pts_bbox_head.pack_gts(gt_bboxes_3d, gt_labels_3d, self.dev) if not isinstance(gt_bboxes_3d, dict) else gt_bboxes_3d
         if d["gt_off"].numel() != self.gts["gt_off"].numel():
             raise ValueError("set_batch: number of scenes differs from the captured batch")
         n = d["gt"].shape[0]
         if int(d["gmax"]) > int(self.gts["gmax"]) or n > self.gts["gt"].shape[0]:
             raise ValueError(f"set_batch: {int(d['gmax'])} boxes in one scene exceed the captured capacity {int(self.gts['gmax'])}")
-        self.pts["cat"].copy_(pts["cat"])
-        self.pts["scene_off"].copy_(pts["scene_off"])
+        if capacity:
+            self._buf.bind_scenes(self.model, points, "set_batch:")
+        else:
+            self.pts["cat"].copy_(pts["cat"])
+            self.pts["scene_off"].copy_(pts["scene_off"])
         self.gts["gt"][:n].copy_(d["gt"])
         self.gts["labels"][:n].copy_(d["labels"])
         self.gts["gt_off"].copy_(d["gt_off"])
@@ -422,32 +352,17 @@ class TrainStep:
         L = npos.numel()
         self._msg = torch.empty(L + 1, dtype=torch.float32, device=npos.device)
         self._msg[:L].copy_(npos)
-        enc = getattr(m, "pts_middle_encoder", None)
-        caps = getattr(enc, "level_capacities", None) if enc is not None else None
-        cnts, cps = [], []
-        if caps is not None and m.static_shapes:
-            cnts, cps = list(enc.last_level_counts[1:1 + len(caps)]), list(caps)
-            vfe = getattr(m, "pts_voxel_encoder", None)
-            if getattr(vfe, "capacity", None) is not None and vfe.last_count_dev is not None:      # dynamic voxelization: the voxel list too
-                cnts, cps = [vfe.last_count_dev] + cnts, [int(vfe.capacity)] + cps
-        if self._fps_can_time_out():
-            cnts, cps = cnts + [m.fps_err[:1]], cps + [0]        # the FPS time-out flag of this step's launch as a "count" with capacity 0
-        if cnts:
-            nv.capacity_flag(cnts, cps, self._msg[L:])
-        else:
-            self._msg[L:].zero_()
-        if self.point_capacity is not None:
-            self._msg[L:].add_(self._ingest_flag)                # the bound batch was cut to the point / GT capacity: hold, as above
+        caps = getattr(getattr(m, "pts_middle_encoder", None), "level_capacities", None) if m.static_shapes else None
+        _sb.validity_flag(m, caps, m.fps_err if self._fps_can_time_out() else None,
+                          None if self.point_capacity is None else self._buf.ingest_flag, self._msg[L:])
         self._num_pos = self._msg[:L]
 
     def _fps_can_time_out(self):
-        """Only FPS over sets above native.FPS_REG_MAX points runs on several workgroups that wait for each other."""
+        """static_batch.fps_can_time_out for what this step hands to the FPS: its largest scene, or the hard voxelization's voxel limit."""
         m = self.model
-        if getattr(m, "fps_err", None) is None or getattr(m, "fps_max_wg", 0) == 1:
-            return False
         vl = getattr(m, "pts_voxel_layer", None)
         mv = 0 if (vl is None or m.dynamic_voxelization) else int(vl.max_voxels[0 if m.training else 1])
-        return max(max(self.pts["lens"]), mv) > nv.FPS_REG_MAX
+        return getattr(m, "fps_err", None) is not None and _sb.fps_can_time_out(m, max(max(self.pts["lens"]), mv))
 
     def _reduce_num_pos(self):
         """ONE small all-reduce per step: the mean positive counts (ref: reduce_mean in uni3detr_head.py:658-664, 680-681) and, in the
@@ -777,20 +692,20 @@ class TrainStep:
         vfe = getattr(m, "pts_voxel_encoder", None) if getattr(m, "dynamic_voxelization", False) else None
         if vfe is not None:
             vfe.capacity = None
-        counts = None
+        seen = []
         for b in (batches if batches else [None]):
             if isinstance(b, dict):
                 self.set_packed_batch(b)
             elif b is not None:
                 self.set_batch(*b)
             self.eager_step()
-            c = [int(c.item()) for c in m.pts_middle_encoder.last_level_counts]
-            counts = c if counts is None else [max(a, b_) for a, b_ in zip(counts, c)]
-        caps = [((int(c * self.capacity_margin) + 255) // 256) * 256 for c in counts[1:]]
+            seen.append([int(c.item()) for c in m.pts_middle_encoder.last_level_counts])
+        counts = _sb.max_level_counts(seen)
+        caps = [_sb.level_capacity(c, self.capacity_margin) for c in counts[1:]]
         m.pts_middle_encoder.level_capacities = caps
         if vfe is not None:
             # dynamic voxelization: the voxel list itself (level 0) is capacity-sized too, with the count kept on the device
-            vfe.capacity = ((int(counts[0] * self.capacity_margin) + 255) // 256) * 256
+            vfe.capacity = _sb.level_capacity(counts[0], self.capacity_margin)
         m.static_shapes = True
         return counts, caps
 
@@ -813,17 +728,12 @@ class TrainStep:
         return counts
 
     def _drop_step_state(self):
-        """Drop the eager iteration's activations / autograd graph BEFORE capturing: releasing them from inside a capture (when the
-        attributes are re-assigned) tears down autograd nodes mid-capture and crashes hipStreamEndCapture."""
+        """Drop the eager iteration's activations / autograd graph BEFORE capturing (static_batch.drop_decoder_outputs says why)."""
         self._outs = self._T = self._num_pos = self._msg = self._losses = self.loss = None
         self._gx = self._v = self._fps = self._feat = None
         self.model._encoder_out = self.model._encoder_cut = None
         self.model.pts_bbox_head._loss_total = None
-        dec = getattr(getattr(self.model.pts_bbox_head, "transformer", None), "decoder", None)
-        if dec is not None:
-            dec._reg_outputs = dec._states_c = dec._cls_outputs = dec._iou_outputs = dec._coord_outputs = dec._refs_sig = None
-        gc.collect()
-        torch.cuda.synchronize()
+        _sb.drop_decoder_outputs(self.model)
 
     def capture(self, warmup=3, keep_state=True, batches=None, remember_batches=True):
         """Measure the sparse-level capacities (over `batches`, a list of (points, gts, labels) or packed batch dicts, when given), warm up, capture.
@@ -837,21 +747,13 @@ class TrainStep:
             self._capture_batches = batches
         snap = self.snapshot_full() if keep_state else None
         counts, caps = self.measure_capacities(batches)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):                      # static-shape eager warm-up on the capture stream
-                self.eager_step()
-        torch.cuda.current_stream().wait_stream(s)
+        s = _sb.warm_up(self.eager_step, warmup)         # static-shape eager warm-up on the capture stream
         torch.cuda.synchronize()
         self._drop_step_state()
         pool = torch.cuda.graph_pool_handle()
 
         def captured(name, pool=pool):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode="thread_local"):
-                getattr(self, name)()
-            return g
+            return _sb.capture_graph(getattr(self, name), s, pool)
 
         # the plan, one graph per captured stage; stage 1 (the plan's first record) is ONE graph or, with fps_graph, FOUR:
         # voxelize | FPS || encoder + dense stack | head + matching.  Every node of one hipGraph runs on a single hardware queue on this
@@ -1070,11 +972,11 @@ class TrainStep:
         drops such batches) can go on stepping."""
         if self.point_capacity is None:
             return
-        n_pts, n_gt = (int(v) for v in self._ingest_over.tolist())
+        n_pts, n_gt = (int(v) for v in self._buf.ingest_over.tolist())
         if n_pts == 0 and n_gt == 0:
             return
         held = self.held_steps()
-        self._ingest_over.zero_()
+        self._buf.ingest_over.zero_()
         self.opt_state[11:13].zero_()
         what = []
         if n_pts:
