@@ -117,6 +117,75 @@ def test_route(cuda, inputs, name, mode, in_epilogue):
     assert torch.allclose(run[0][0], run[1][0], rtol=1e-4, atol=1e-6) and torch.allclose(run[0][1], run[1][1], rtol=1e-4, atol=1e-6)
 
 
+@pytest.fixture(scope="module")
+def exact_inputs():
+    """exact_inputs(name, device): integer inputs of one shape and their float64 result, built once and shared like `inputs`."""
+    cache = {}
+
+    def get(name, dev):
+        if name not in cache:
+            cache[name] = _build_exact(name, dev)
+        return cache[name]
+    yield get
+    cache.clear()
+
+
+def _build_exact(name, dev):
+    """x and the addend integers in [-3, 3], w in [-2, 2]: exact in bf16, and every sum an integer of at most 27 * 256 * 6 < 2^24, so
+    the f32 accumulator holds the float64 result whatever the order of its additions."""
+    n, cin, cout, kvol, table, nmajor = SHAPES[name][0]
+    gen = torch.Generator().manual_seed(2000 * cin + cout + kvol)
+    x = torch.randint(-3, 4, (n, cin), generator=gen).to(dev).bfloat16()
+    w = torch.randint(-2, 3, (kvol, cin, cout), generator=gen).to(dev).bfloat16()                      # [K][Cin][Cout]
+    add = torch.randint(-3, 4, (n, cout), generator=gen).to(dev).bfloat16()
+    nbr = None
+    if table:
+        t = torch.randint(0, n, (kvol, n), generator=gen, dtype=torch.int32)
+        t[torch.rand(kvol, n, generator=gen) < 0.3] = -1
+        nbr = t.to(dev).contiguous()
+    ref = torch.zeros(n, cout, dtype=torch.float64, device=dev)
+    for k in range(kvol):
+        idx = nbr[k].long() if table else torch.arange(n, device=dev)
+        ref += (x.double()[idx.clamp(min=0)] * (idx >= 0).unsqueeze(1)) @ w[k].double()
+    assert float(ref.abs().max()) < 2 ** 24
+    return dict(x=x, w=w.transpose(1, 2).contiguous() if nmajor else w, add=add, nbr=nbr, ref=ref,
+                n_dev=torch.tensor([n - 13], dtype=torch.int32, device=dev))
+
+
+@pytest.mark.parametrize("name,mode,in_epilogue", [c for c in CASES if c[1] in ("plain", "add")])
+def test_route_exact(cuda, exact_inputs, name, mode, in_epilogue):
+    """Integer operands through every plain / addend route: the accumulator is exact and the kernels round once to bf16, to nearest
+    even, so the live rows ARE the float64 reference rounded to bf16 - of conv + addend where the addend goes through the epilogue,
+    plus the addend in bf16 where spconv_fwd adds it afterwards.  torch.equal, no tolerance."""
+    shape, kernel = SHAPES[name]
+    n, cin, cout, kvol, table, nmajor = shape
+    c = exact_inputs(name, cuda)
+    live = n - 13
+    plan = nv.fwd_plan(*shape, mode)
+    assert (plan and (plan.family, plan.kernel)) == kernel and (mode != "add" or bool(plan and plan.takes_addend) == in_epilogue)
+    addend = c["add"] if mode == "add" else None
+    if mode == "plain":
+        want = c["ref"].to(torch.bfloat16)
+    elif in_epilogue:
+        want = (c["ref"] + c["add"].double()).to(torch.bfloat16)
+    else:
+        want = c["ref"].to(torch.bfloat16) + c["add"]
+    y = nv.spconv_fwd(c["x"], c["w"], c["nbr"], c["n_dev"], n, cout, transpose_w=nmajor, tag="spconv_fwd", addend=addend)
+    assert torch.equal(y[:live], want[:live])
+    # the launch itself, into a buffer the test owns: rows past the count keep the sentinel
+    out = torch.full((n, cout), SENT, dtype=torch.bfloat16, device=cuda)
+    nbr_p, ld = nv._nbr_ptr_ld(c["nbr"])
+    ptrs = (nv._ptr(c["x"]), nv._ptr(c["w"]), nbr_p, ld, nv._ptr(out), nv._ptr(c["n_dev"]), n, cin, cout, kvol, int(nmajor))
+    if kernel is None:
+        nv._check(nv.lib().u3d_spconv_fwd(*ptrs, nv.BF16, nv._stream()), "spconv_fwd")
+    else:
+        nv._check(nv.lib().u3d_igemm_fwd_bf16(*ptrs, nv._ptr(addend) if in_epilogue else None, None, nv._stream()), "igemm_fwd_bf16")
+    assert bool((out[live:] == SENT).all())
+    if addend is not None and not in_epilogue:
+        out[:live] += addend[:live]                                     # added afterwards, as spconv_fwd does
+    assert torch.equal(out[:live], want[:live])
+
+
 def test_an_epilogue_the_plan_lacks_is_refused(cuda, inputs):
     """An addend for the register-staged kernels, statistics for 32 -> 64: the entry says so instead of dropping them."""
     for name, addend, stats in (("reg_16_n", True, False), ("direct_32_64", False, True), ("first_generation", False, False)):
