@@ -938,6 +938,10 @@ int32_t u3d_eval_tp(const int64_t* perm, int32_t n_det, const float* iou_max, co
 int32_t u3d_eval_ap(const uint8_t* tp, int32_t n_det, const int32_t* seg, const int32_t* npos, int32_t num_classes, int32_t n_thr,
                     int32_t n_gt, double* prec_ws, float* ap, double* rec, u3d_stream s);
 
+/* u3d_compact_rows: out[pos[d]] = rec[d] where valid[d], for n rows of row_bytes bytes each (a positive multiple of 4, else
+ * U3D_ERR_ARG; rows move as 32-bit words); pos int32 [n] = exclusive scan of valid int32 [n].  One launch, none for n == 0. */
+int32_t u3d_compact_rows(const void* rec, const int32_t* valid, const int32_t* pos, int32_t n, int32_t row_bytes, void* out, u3d_stream s);
+
 /* ------------------------------------------------------------------------------------------------
  * KITTI 3-D detection evaluation (mmdet3d's kitti_eval: clean_data, compute_statistics, get_thresholds, eval_class; semantics in
  * uni3detr_amd/kitti_eval.py).  Records are f32 [., 16]: camera box (x, y, z bottom centre, l, h, w, ry), 2-D box (x1, y1, x2, y2),
@@ -946,7 +950,7 @@ int32_t u3d_eval_ap(const uint8_t* tp, int32_t n_det, const int32_t* seg, const 
  * exclusive scan of nd * ng, ov f32 [3][n_pairs] = bbox / bev / 3d overlap matrices [dt][gt] per scene.
  * u3d_kitti_convert: LiDAR bottom-centre boxes [n,7] + scores + labels -> rec [n,16] and valid int32 [n] (inside the image and strictly
  *   inside lim = pcd_limit_range); calib f32 [n_scene][32] = R0_rect @ Tr_velo_to_cam then P2 (row-major 4x4), img f32 [n_scene][2] = (H, W).
- * u3d_kitti_compact: out[pos[d]] = rec[d] where valid[d] (pos = exclusive scan of valid).
+ *   The valid rows are then kept with u3d_compact_rows.
  * u3d_kitti_flags: for the K <= 3 class codes cls, flag index f = class slot * 3 + difficulty: gt_flag / dt_flag int8 [3K][n] in
  *   {-1, 0, 1}, nvalid int32 [3K] = GT with flag 0, dc_iof f32 [n_dt] = max DontCare intersection over the detection's area.
  * Groups g (n_group): flag index gfid, metric gmet (0 bbox, 1 bev, 2 3d), min overlap gmin.
@@ -961,7 +965,6 @@ int32_t u3d_eval_ap(const uint8_t* tp, int32_t n_det, const int32_t* seg, const 
 int32_t u3d_kitti_convert(const float* boxes, const float* scores, const int32_t* labels, const int32_t* off, int32_t n_scene, int32_t n,
                           const float* calib, const float* img, const int32_t* label_code, int32_t n_label, const float* lim, float* rec,
                           int32_t* valid, u3d_stream s);
-int32_t u3d_kitti_compact(const float* rec, const int32_t* valid, const int32_t* pos, int32_t n, float* out, u3d_stream s);
 int32_t u3d_kitti_overlaps(const float* dt, const int32_t* dt_off, const float* gt, const int32_t* gt_off, const int64_t* ov_off,
                            int32_t n_scene, int64_t n_pairs, float* ov, u3d_stream s);
 int32_t u3d_kitti_flags(const float* dt, const int32_t* dt_off, int32_t n_scene, int32_t n_dt, const float* gt, const int32_t* gt_off,
@@ -994,7 +997,7 @@ int32_t u3d_kitti_reduce(const int32_t* st_tp, const int32_t* st_fp, const int32
  *   and ego-frame xy radius <= cls_range; GT: an evaluated class or a rack).  attr_moving / attr_still int32 [n_cls]: the prediction
  *   attribute codes by |global v_xy| > 0.2.
  * u3d_nusc_filter: valid &= ego_dist < cls_range, GT points != 0, not (bike[class] and centre inside a rack row of gt / gt_off).
- * u3d_nusc_compact: out[pos[d]] = rec[d] where valid[d] (pos = exclusive scan of valid).
+ *   The valid rows are then kept with u3d_compact_rows.
  * u3d_nusc_rank_keys: key int64 [n] / idx int32 [n]: key[n-1-i] = descending-orderable score of row i, idx[n-1-i] = i.
  * u3d_nusc_match: one wave per segment (class * n_sample + sample): rank int32 [n] = prediction rows in rank order, mperm int32 [n] =
  *   rank positions grouped by segment, mseg [n_seg+1]; gord = GT rows grouped by segment, gseg [n_seg+1]; max_gt = the largest GT
@@ -1011,7 +1014,6 @@ int32_t u3d_nusc_convert(const double* rows, const int32_t* cls, const int32_t* 
 int32_t u3d_nusc_filter(const double* rec, const int32_t* off, int32_t n_sample, int32_t n, int32_t is_pred, const double* calib,
                         const double* gt, const int32_t* gt_off, const double* cls_range, const int32_t* bike, int32_t n_cls, int32_t* valid,
                         u3d_stream s);
-int32_t u3d_nusc_compact(const double* rec, const int32_t* valid, const int32_t* pos, int32_t n, double* out, u3d_stream s);
 int32_t u3d_nusc_rank_keys(const double* rec, int32_t n, int64_t* key, int32_t* idx, u3d_stream s);
 int32_t u3d_nusc_match(const double* pred, const int32_t* rank, const int32_t* mperm, const int32_t* mseg, int32_t n_seg, int32_t n,
                        const double* gt, const int32_t* gord, const int32_t* gseg, int32_t max_gt, const double* ths, int32_t tp_th, int8_t* tp,

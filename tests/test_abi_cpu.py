@@ -180,7 +180,8 @@ RETIRED = ("u3d_subm_halo_conv64_bf16", "u3d_subm_halo_conv128_bf16", "u3d_subm_
            "u3d_subm_halo_conv128_affine_bf16", "u3d_subm_halo_wpack128", "u3d_subm_halo_wpack128_batched",
            "u3d_bn_apply_planes", "u3d_bn_bwd_apply_planes", "u3d_mha_fwd_dt", "u3d_mha_bwd_dt", "u3d_decoder_layer_fwd_nw",
            "u3d_decoder_layer_bwd_nw", "u3d_decoder_layer_slots_dt", "u3d_decoder_layer_blocks_dt", "u3d_wpack_bf16",
-           "u3d_adamw_step_state", "u3d_tap_gather_sum_add", "u3d_bitgrid_nwords", "u3d_nusc_match_lds")
+           "u3d_adamw_step_state", "u3d_tap_gather_sum_add", "u3d_bitgrid_nwords", "u3d_nusc_match_lds", "u3d_kitti_compact",
+           "u3d_nusc_compact")
 OK, ARG, UNSUPPORTED = 0, -1, -2
 
 

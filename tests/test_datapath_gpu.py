@@ -59,6 +59,28 @@ def test_augment_points_and_boxes_match_oracle(cuda, coord, dim):
     np.testing.assert_allclose(got_b, exp_b, rtol=0, atol=2e-6)
 
 
+def test_augment_with_an_empty_first_middle_and_last_scene(cuda):
+    """every row takes its scene's parameters from the offsets: scenes without points / boxes in front, between and behind the others"""
+    from uni3detr_amd import datapath as dp
+    from uni3detr_amd import native as nv
+    rng = np.random.default_rng(21)
+    pts, boxes = _scenes(rng, [0, 170, 0, 130, 0]), _boxes(rng, [0, 3, 0, 2, 0])
+    B, coord = 5, od.LIDAR
+    fh, fv = np.array([1, 0, 1, 1, 0], bool), np.array([0, 1, 0, 0, 1], bool)
+    ang = rng.uniform(-0.5236, 0.5236, B).astype(np.float32)
+    sc = rng.uniform(0.85, 1.15, B).astype(np.float32)
+    tr = rng.normal(0, 0.1, (B, 3)).astype(np.float32)
+    batch = dp.pack_batch([torch.from_numpy(p).cuda() for p in pts], [torch.from_numpy(b).cuda() for b in boxes], box_type_3d="LiDAR")
+    tab = torch.from_numpy(np.concatenate([np.stack([fh, fv, np.sin(ang), np.cos(ang), ang, sc], 1), tr], 1).astype(np.float32)).cuda()
+    nv.points_augment(batch["points"], batch["scene_off"], tab, coord, 3)
+    nv.boxes_augment(batch["gt_bboxes_3d"], batch["gt_off"], tab, coord)
+    assert batch["scene_off"].tolist() == [0, 0, 170, 170, 300, 300] and batch["gt_off"].tolist() == [0, 0, 3, 3, 5, 5]
+    exp_p = np.concatenate([od.augment_points(p, fh[i], fv[i], ang[i], sc[i], coord, 3, tr[i]) for i, p in enumerate(pts)])
+    exp_b = np.concatenate([od.augment_boxes(b, fh[i], fv[i], ang[i], sc[i], coord, tr[i]) for i, b in enumerate(boxes)])
+    np.testing.assert_allclose(batch["points"].cpu().numpy()[:300], exp_p, rtol=0, atol=2e-6)          # the bound of the test above
+    np.testing.assert_allclose(batch["gt_bboxes_3d"].cpu().numpy()[:5], exp_b, rtol=0, atol=2e-6)
+
+
 def test_range_filter_is_order_preserving_and_strict(cuda):
     from uni3detr_amd import datapath as dp
     from uni3detr_amd import native as nv

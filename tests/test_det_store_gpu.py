@@ -441,6 +441,65 @@ def test_nuscenes_add_store_equals_add(cuda):
         assert np.float64(got[k]).tobytes() == np.float64(want[k]).tobytes(), (k, got[k], want[k])
 
 
+S3 = 3
+
+
+def _indoor3(cuda):
+    data = eval_scenes(S3, K6, C6, seed=31)
+    dets = [(np.asarray(d[2], np.float32), np.asarray(d[3], np.float32), np.asarray(d[4]).astype(np.int32)) for d in data]
+    rest = ([torch.from_numpy(d[0]).to(cuda) for d in data], [torch.from_numpy(d[1]).to(cuda) for d in data])
+    return dets, rest, lambda: ev.IndoorEvaluator(C6, device=cuda), (ev.ERRORS[0], ev.ERRORS[2].format(C6)), 7
+
+
+def _kitti3(cuda):
+    infos, results = kitti_scenes(S3, det_per_scene=K6, seed=32)
+    dets = [(np.asarray(r["boxes_3d"], np.float32).reshape(-1, 7)[:K6], np.asarray(r["scores_3d"], np.float32)[:K6],
+             np.asarray(r["labels_3d"]).astype(np.int32)[:K6]) for r in results]
+    return dets, (infos,), lambda: ke.KittiEvaluator(["Pedestrian", "Cyclist", "Car"], device=cuda), ke.ERRORS, 7
+
+
+def _nusc3(cuda):
+    infos, results = nusc_samples(S3, preds_per_sample=K6, seed=33, class_names=ne.CLASSES[:C6])
+    dets = [(np.asarray(r["boxes_3d"], np.float32).reshape(-1, 9)[:K6], np.asarray(r["scores_3d"], np.float32)[:K6],
+             np.asarray(r["labels_3d"]).astype(np.int32)[:K6]) for r in results]
+    return dets, (infos,), lambda: ne.NuScenesEvaluator(ne.CLASSES[:C6], device=cuda), ne.ERRORS, 9
+
+
+@pytest.mark.parametrize("family", [_indoor3, _kitti3, _nusc3], ids=["indoor", "kitti", "nuscenes"])
+@pytest.mark.parametrize("what", ["score", "label"])
+def test_the_evaluators_messages_on_the_device(cuda, family, what):
+    """a NaN score and a label one past the classes give the evaluator's one message, the module constant, from the device compute()
+    after add() and from add_store() (the store's own check, or compute() where the store is not given the classes)"""
+    dets, rest, make, errors, D = family(cuda)
+    want = errors[0] if what == "score" else errors[1]
+    bad = [tuple(np.copy(x) for x in d) for d in dets]
+    assert len(bad[1][1]) >= 2
+    if what == "score":
+        bad[1][1][1] = np.nan
+    else:
+        bad[1][2][0] = C6
+    with pytest.raises(ValueError) as e:
+        a = make()
+        a.add([dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in bad], *rest)
+        a.compute()
+    assert str(e.value) == want
+    with pytest.raises(ValueError) as e:
+        b = make()
+        b.add_store(_store_of(cuda, bad, D, batch=2), *rest)
+        b.compute()
+    assert str(e.value) == want
+
+
+def test_nuscenes_add_store_scene_count_mismatch(cuda):
+    dets, (infos,), make, _, D = _nusc3(cuda)
+    e = make()
+    with pytest.raises(ValueError) as err:
+        e.add_store(_store_of(cuda, dets, D, batch=2), infos[:2])
+    assert str(err.value) == "nuscenes_eval: one result per info" and len(e) == 0
+    e.add_store(_store_of(cuda, dets, D, batch=2), infos)
+    assert len(e) == S3 and e.compute()
+
+
 # ---- 7: end to end --------------------------------------------------------------------------------------------------------------------
 B7, P7 = 2, 10240
 

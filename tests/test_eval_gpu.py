@@ -207,3 +207,19 @@ def test_simple_test_results_evaluate_on_device_as_on_host(cuda):
     label2cat = {c: str(c) for c in range(10)}
     _same(ev.indoor_eval(ga, res, THRS, label2cat, logger="silent", device=cuda),
           ev.indoor_eval(ga, res, THRS, label2cat, logger="silent", device="cpu"))
+
+
+def test_empty_first_middle_and_last_scene_change_nothing(cuda):
+    """scenes with neither detections nor GT, in front of, between and behind two others: every detection still meets the GT of its own
+    scene, so the result is that of the two scenes alone, bit for bit"""
+    data = eval_scenes(2, 140, 5, seed=19)
+    none = tuple(x[:0] for x in data[0])
+    outs = []
+    for scenes in (data, [none, data[0], none, data[1], none]):
+        e = ev.IndoorEvaluator(5, THRS, device=cuda)
+        e.add([[torch.from_numpy(d[2]).to(cuda), torch.from_numpy(d[3]).to(cuda), torch.from_numpy(d[4]).to(cuda)] for d in scenes],
+              [torch.from_numpy(d[0]).to(cuda) for d in scenes], [torch.from_numpy(d[1]).to(cuda) for d in scenes])
+        outs.append(e.compute())
+    assert set(outs[0]) == set(outs[1]) and 0.0 < outs[0]["mAP_0.25"] <= 1.0
+    for k in outs[0]:
+        assert np.float64(outs[0][k]).tobytes() == np.float64(outs[1][k]).tobytes(), k

@@ -176,3 +176,19 @@ def test_simple_test_results_evaluate_on_device_as_on_host(cuda):
     dev.add(res, infos)
     host.add(res, infos)
     _same(dev.compute(), host.compute(), tol=1e-6)
+
+
+def test_empty_first_middle_and_last_scene_change_nothing(cuda):
+    """scenes with neither detections nor GT, in front of, between and behind two others: every detection keeps its own scene's
+    calibration and GT, so the result is that of the two scenes alone, bit for bit"""
+    infos, results = kitti_scenes(2, det_per_scene=40, seed=15)
+    none = dict(infos[0], annos={k: v[:0] for k, v in infos[0]["annos"].items()})
+    outs = []
+    for r, i in ((results, infos), ([_empty_result(), results[0], _empty_result(), results[1], _empty_result()],
+                                    [none, infos[0], none, infos[1], none])):
+        e = ke.KittiEvaluator(CLASSES, device=cuda)
+        e.add(r, i)
+        outs.append(e.compute())
+    assert set(outs[0]) == set(outs[1]) and any(v > 0 for v in outs[0].values())
+    for k in outs[0]:
+        assert np.float64(outs[0][k]).tobytes() == np.float64(outs[1][k]).tobytes(), k

@@ -137,6 +137,23 @@ def test_use_color_and_normalize(cuda, tmp_path, shift, mean):
         dp.NormalizePointsColor(mean)(_load(tmp_path, raws, SUN, tag="k"))
 
 
+def test_empty_first_middle_and_last_scene(cuda):
+    """the height column takes every row's scene from scene_off: scenes without rows in front, between and behind the others (the
+    file reader refuses such a scene when the height is asked for, so this goes to the entry itself) - their floor is NaN"""
+    from uni3detr_amd import datapath as dp
+    from uni3detr_amd import native as nv
+    from uni3detr_amd.eval_common import offsets
+    rng = np.random.default_rng(12)
+    raws = [_raw(rng, n) for n in (0, 170, 0, 130, 0)]                      # 300 rows: two workgroups of the gather
+    tab = torch.from_numpy(dp.load_table([len(a) for a in raws])).to(cuda)
+    pts, fl = nv.points_load(torch.from_numpy(np.concatenate(raws)).to(cuda), offsets([len(a) for a in raws], cuda), tab, [0, 1, 2], True)
+    pts, fl = pts.cpu().numpy(), fl.cpu().numpy()
+    assert pts.shape == (300, 4) and np.isnan(fl[[0, 2, 4]]).all()
+    for b, lo in ((1, 0), (3, 170)):
+        want, wfl = R.load_points(raws[b], [0, 1, 2], True)
+        assert R.same(pts[lo:lo + len(want)], want) and R.same(fl[b:b + 1], np.array([wfl], np.float32))
+
+
 def test_error_codes(cuda):
     from uni3detr_amd import native as nv
     import ctypes as C

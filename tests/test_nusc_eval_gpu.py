@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from uni3detr_amd import nuscenes_eval as ne
+from uni3detr_amd.eval_common import offsets
 from uni3detr_amd.synth import nusc_samples
 
 pytestmark = pytest.mark.gpu
@@ -60,7 +61,7 @@ def test_same_global_boxes_give_identical_matches_and_metrics(cuda):
     hp, hpc, hg, hgc = ne.host_global(a, tab)
     h = ne.host_core(hp, hpc, hg, hgc, tab)
     t = lambda x: torch.as_tensor(x, dtype=torch.float64, device=cuda).contiguous()   # noqa: E731
-    d = ne.device_core(t(hp), ne._off(hpc, cuda), t(hg), ne._off(hgc, cuda), tab, ne._dev_tables(tab, cuda))
+    d = ne.device_core(t(hp), offsets(hpc, cuda), t(hg), offsets(hgc, cuda), tab, ne._dev_tables(tab, cuda))
     assert np.array_equal(d["rank"], h["rank"]) and np.array_equal(d["cseg"], h["cseg"]) and np.array_equal(d["npos"], h["npos"])
     assert np.array_equal(d["tp"], h["tp"]) and np.array_equal(d["match"], h["match"])
     assert np.array_equal(d["mri"], h["mri"])
@@ -162,3 +163,18 @@ def test_simple_test_results_evaluate_on_device_as_on_host(cuda):
     dev.add(res, infos)
     host.add(res, infos)
     _same(dev.compute(), host.compute())
+
+
+def test_empty_first_middle_and_last_sample_change_nothing(cuda):
+    """samples with neither predictions nor GT, in front of, between and behind two others: every box keeps its own sample's
+    calibration and GT, so the result is that of the two samples alone, bit for bit"""
+    infos, results = nusc_samples(2, seed=37)
+    none = dict(infos[0], **{k: infos[0][k][:0] for k in ("gt_names", "gt_boxes", "gt_velocity", "num_lidar_pts", "num_radar_pts", "gt_attr_names")})
+    outs = []
+    for r, i in ((results, infos), ([_empty(), results[0], _empty(), results[1], _empty()], [none, infos[0], none, infos[1], none])):
+        e = ne.NuScenesEvaluator(device=cuda)
+        e.add(r, i)
+        outs.append(e.compute())
+    assert set(outs[0]) == set(outs[1]) and outs[0]["pts_bbox_NuScenes/mAP"] > 0
+    for k in outs[0]:
+        assert np.float64(outs[0][k]).tobytes() == np.float64(outs[1][k]).tobytes(), k

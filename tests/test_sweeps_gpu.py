@@ -76,6 +76,7 @@ CASES = {
     "four_scenes_padding": ([(700, []), (300, [10, 20]), (0, []), (257, [300] * 10)], {}),
     "four_scenes_no_padding": ([(700, []), (300, [10, 20]), (0, []), (257, [300] * 10)], dict(pad_empty_sweeps=False)),
     "no_remove_close_test_mode": ([(640, [70] * 12), (90, [])], dict(remove_close=False, test_mode=True, use_dim=[4, 0, 1])),
+    "empty_first_middle_last_segment": ([(0, [0, 40]), (120, [0, 60, 0]), (50, [30, 0])], {}),
     "load_dim_6": ([(400, [200, 0, 300])], dict(load_dim=6, use_dim=[0, 1, 2, 5, 4], sweeps_num=2)),
 }
 

@@ -158,6 +158,10 @@ def test_merge_edge_cases(cuda):
     for g, sc in zip(got, [single, gaps]):
         _assert_same(g, R.merge(sc, P, R.LIDAR, max_num=5))
         assert len(g[2]) == 5
+    # scenes without a detection in front of, between and behind the others
+    scenes = [empty, single, empty, gaps, empty]
+    for g, sc in zip(_merge_scenes(cuda, scenes, P, R.LIDAR, 7), scenes):
+        _assert_same(g, R.merge(sc, P, R.LIDAR))
 
 
 def test_merge_large_segment_takes_the_global_path(cuda):

@@ -142,6 +142,8 @@ def test_batch_ingest_matches_restatement(cuda, F, dim, gd):
     many = [int(v) for v in np.random.default_rng(9).integers(0, 40, 600)]
     _ingest_case(cuda, F, dim, gd, many, None, [1] * 600, None, 32, 1, 6)
     _ingest_case(cuda, F, dim, gd, sizes, None, [0] * 5, None, 1300, 3, 7)
+    # an empty first, middle and last scene, on both sides
+    _ingest_case(cuda, F, dim, gd, [0, 170, 0, 130, 0], None, [0, 3, 0, 2, 0], None, 170, 3, 8)
 
 
 # ---- 4: spare rows are inert -----------------------------------------------------------------------------------------------------

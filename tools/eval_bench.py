@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from uni3detr_amd import evaluation as ev  # noqa: E402
+from uni3detr_amd.eval_common import offsets  # noqa: E402
 from uni3detr_amd.synth import eval_scenes  # noqa: E402
 
 SETS = {"sunrgbd": (5050, 1000, 10, 12), "scannet": (312, 5000, 18, 40)}
@@ -44,7 +45,7 @@ def main():
         db, ds, dl, dc, gb, gl, gc = flat(data)
         f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)                          # noqa: E731
         i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32)).to(dev)                            # noqa: E731
-        args = (f32(db), f32(ds), i32(dl), i32(ev._offsets(dc)), f32(gb), i32(gl), i32(ev._offsets(gc)), ncls, (0.25, 0.5), dev)
+        args = (f32(db), f32(ds), i32(dl), i32(offsets(dc)), f32(gb), i32(gl), i32(offsets(gc)), ncls, (0.25, 0.5), dev)
         times = []
         for r in range(2 + a.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -20,6 +20,18 @@
 
 static inline int u3d_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The segment of element v in CSR offsets: the last s in [0, n) with off[s * stride] <= v (off ascending, off[0] <= v; v at or past
+// off[n * stride] goes with the last segment).  An empty segment never wins: its successor starts at the same element.
+template <typename I>
+__device__ __forceinline__ int u3d_segment_of(const int* __restrict__ off, int n, I v, int stride = 1) {
+  int lo = 0, hi = n;                   // off[lo * stride] <= v < off[hi * stride]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid * stride] <= v) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // Raise a kernel's dynamic-LDS limit once per DEVICE (the attribute is per device; a process-wide flag would leave a second GPU
 // of the process at the 64 KiB default).  `mask`: one word per call site (bit = device id; setting the attribute twice is harmless,
 // so the relaxed read-modify-write needs no lock).  Devices >= 64 simply set it every time.

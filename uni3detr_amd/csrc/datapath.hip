@@ -15,20 +15,11 @@
 
 #define AUG_NP U3D_AUG_NPARAM
 
-__device__ __forceinline__ int dp_scene_of(const int* __restrict__ off, int batch, int i) {
-  int lo = 0, hi = batch;               // off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ void k_points_augment(float* __restrict__ pts, const int* __restrict__ scene_off, int batch, int n_total, int feat,
                                  const float* __restrict__ params, int coord, int height_dim) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_total) return;
-  const int b = dp_scene_of(scene_off, batch, i);
+  const int b = u3d_segment_of(scene_off, batch, i);
   if (i >= scene_off[batch]) return;
   const float* p = params + b * AUG_NP;
   float* r = pts + (long long)i * feat;
@@ -45,7 +36,7 @@ __global__ void k_boxes_augment(float* __restrict__ boxes, const int* __restrict
                                 const float* __restrict__ params, int coord) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int b = dp_scene_of(gt_off, batch, i);
+  const int b = u3d_segment_of(gt_off, batch, i);
   if (i >= gt_off[batch]) return;
   float* r = boxes + (long long)i * dim;
   dp_box_augment(r, r, dim, params + b * AUG_NP, coord);
@@ -183,7 +174,7 @@ __global__ void k_point_shuffle(const float* __restrict__ pts, const int* __rest
   if (i >= n_total) return;
   int src = i;
   if (i >= scene_off[0] && i < scene_off[batch]) {
-    const int b = dp_scene_of(scene_off, batch, i);
+    const int b = u3d_segment_of(scene_off, batch, i);
     const int r0 = scene_off[b], seg = scene_off[b + 1] - r0;
     int n = count ? count[b] : seg;
     n = n > seg ? seg : (n < 0 ? 0 : n);

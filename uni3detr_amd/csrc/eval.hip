@@ -16,16 +16,6 @@
 #define EVAL_GT_LDS 1024            // GT boxes staged per workgroup (32 B each); the rest of a very large scene is read from global
 #define EVAL_AP_THREADS 1024
 
-// last s with off[s] <= v (off ascending, off[0] = 0 <= v)
-__device__ static int eval_find_scene(const int* __restrict__ off, int n_scene, int v) {
-  int lo = 0, hi = n_scene;          // answer in [lo, hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // descending-orderable score bits: a larger score gives a smaller key; -0.0 is +0.0
 __device__ static unsigned int eval_desc_bits(float s) {
   if (s == 0.f) s = 0.f;
@@ -45,8 +35,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_iou_argmax(const float* _
   const int d0 = blockIdx.x * EVAL_THREADS;
   const int d = d0 + threadIdx.x;
   if (threadIdx.x == 0) {
-    const int s0 = eval_find_scene(det_off, n_scene, d0);
-    const int s1 = eval_find_scene(det_off, n_scene, min(d0 + EVAL_THREADS, n_det) - 1);
+    const int s0 = u3d_segment_of(det_off, n_scene, d0);
+    const int s1 = u3d_segment_of(det_off, n_scene, min(d0 + EVAL_THREADS, n_det) - 1);
     range_sh[0] = gt_off[s0];
     range_sh[1] = gt_off[s1 + 1];
   }
@@ -59,7 +49,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_iou_argmax(const float* _
   }
   __syncthreads();
   if (d >= n_det) return;
-  const int s = eval_find_scene(det_off, n_scene, d);
+  const int s = u3d_segment_of(det_off, n_scene, d);
   const int cls = det_labels[d];
   float p[7];
 #pragma unroll

@@ -79,15 +79,6 @@ __global__ __launch_bounds__(INGEST_THREADS) void k_ingest_scan(const int* __res
   }
 }
 
-__device__ __forceinline__ int ingest_scene_of(const int* s_off, int B, int i) {
-  int lo = 0, hi = B;                   // s_off[lo] <= i < s_off[hi]; an empty scene never wins (its successor starts at the same row)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (s_off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 template <int W>
 __global__ __launch_bounds__(INGEST_THREADS) void k_ingest_rows(const float* __restrict__ points, int n_src, int F,
                                                                 const int* __restrict__ scene_off, const int* __restrict__ dst_off, int B,
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void k_ingest_rows(const float* __r
     const long long u = (long long)blockIdx.x * INGEST_THREADS + threadIdx.x;
     const long long row = u / upr;
     if (row >= s_off[B]) return;
-    const int q = (int)(u - row * upr), b = ingest_scene_of(s_off, B, (int)row);
+    const int q = (int)(u - row * upr), b = u3d_segment_of(s_off, B, (int)row);
     const long long src = (long long)scene_off[b] + (row - s_off[b]);
     if (src >= n_src) return;           // (offsets that point past the source: nothing is read there)
     if (W == 4) ((float4*)cat)[row * upr + q] = ((const float4*)points)[src * upr + q];
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void k_ingest_rows(const float* __r
   }
   const long long j = (long long)(blockIdx.x - point_blocks) * INGEST_THREADS + threadIdx.x;
   if (j >= s_off[B]) return;
-  const int b = ingest_scene_of(s_off, B, (int)j);
+  const int b = u3d_segment_of(s_off, B, (int)j);
   const long long src = (long long)gt_off[b] + (j - s_off[b]);
   if (src >= g_src) return;
   const float* r = gt + src * sd;

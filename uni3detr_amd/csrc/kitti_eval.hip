@@ -5,7 +5,7 @@
 // Records (float32, KE_REC per row): 0-6 camera box (x, y, z = bottom centre, l, h, w, ry), 7-10 2-D box (x1, y1, x2, y2), 11 alpha,
 // 12 score (detections) / ignore bits of the three difficulties (GT, computed on the host in float64), 13 class code (KE_*).
 //   u3d_kitti_convert     per LiDAR detection: camera box, projected and clipped 2-D box, alpha, validity (image and point-cloud range)
-//   u3d_kitti_compact     stable scatter of the valid rows to their exclusive-scan positions (the caller scans the validity flags)
+//   (the caller scans the validity flags and keeps the valid rows with u3d_compact_rows, csrc/compact.hip)
 //   u3d_kitti_overlaps    one workgroup per scene, the scene's GT in LDS: bbox / bev / 3d overlap matrices [dt][gt], flat, scene-offset
 //   u3d_kitti_flags       GT and detection flags per (class, difficulty), num_valid_gt, DontCare IoF per detection
 //   u3d_kitti_pass1       one wave per (group, scene): compute_statistics(compute_fp = False); the detection argmax is a wave reduction
@@ -32,16 +32,6 @@
 
 __constant__ float ke_min_height[3] = {40.f, 25.f, 25.f};
 
-// last s with off[s] <= v (off ascending, off[0] = 0 <= v)
-__device__ static int ke_find_scene(const int* __restrict__ off, int n_scene, int v) {
-  int lo = 0, hi = n_scene;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // LiDAR -> KITTI camera-frame detections.  calib [n_scene][32] = T = R0_rect @ Tr_velo_to_cam (4x4, row-major), then P2 (4x4);
 // img [n_scene][2] = (H, W); lim [6] = pcd_limit_range; label_code [n_label] = class code of class_names[label].
@@ -53,7 +43,7 @@ __global__ __launch_bounds__(KE_THREADS) void k_kitti_convert(const float* __res
                                                               float* __restrict__ rec, int* __restrict__ valid) {
   const int d = blockIdx.x * KE_THREADS + threadIdx.x;
   if (d >= n) return;
-  const int s = ke_find_scene(off, n_scene, d);
+  const int s = u3d_segment_of(off, n_scene, d);
   const float* T = calib + (long long)s * 32;
   const float* P = T + 16;
   const float* b = boxes + (long long)d * 7;
@@ -100,23 +90,6 @@ extern "C" int32_t u3d_kitti_convert(const float* boxes, const float* scores, co
               U3D_ERR_ARG);
   hipLaunchKernelGGL(k_kitti_convert, dim3(u3d_cdiv(n, KE_THREADS)), dim3(KE_THREADS), 0, s, boxes, scores, labels, off, n_scene, n, calib,
                      img, label_code, n_label, lim, rec, valid);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-
-__global__ __launch_bounds__(KE_THREADS) void k_kitti_compact(const float* __restrict__ rec, const int* __restrict__ valid,
-                                                              const int* __restrict__ pos, int n, float* __restrict__ out) {
-  const long long k = (long long)blockIdx.x * KE_THREADS + threadIdx.x;
-  if (k >= (long long)n * KE_REC) return;
-  const int d = (int)(k / KE_REC), c = (int)(k % KE_REC);
-  if (valid[d]) out[(long long)pos[d] * KE_REC + c] = rec[k];
-}
-
-extern "C" int32_t u3d_kitti_compact(const float* rec, const int32_t* valid, const int32_t* pos, int32_t n, float* out, u3d_stream s) {
-  U3D_REQUIRE(n >= 0, U3D_ERR_ARG);
-  if (n == 0) return U3D_OK;
-  U3D_REQUIRE(rec && valid && pos && out, U3D_ERR_ARG);
-  hipLaunchKernelGGL(k_kitti_compact, dim3(u3d_cdiv((long long)n * KE_REC, KE_THREADS)), dim3(KE_THREADS), 0, s, rec, valid, pos, n, out);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }
@@ -233,7 +206,7 @@ __global__ __launch_bounds__(KE_THREADS) void k_kitti_dt_flags(const float* __re
   for (int ci = 0; ci < K; ++ci)
     for (int df = 0; df < 3; ++df)
       dt_flag[(long long)(ci * 3 + df) * n_dt + j] = (signed char)(height < (double)ke_min_height[df] ? 1 : code == cls[ci] ? 0 : -1);
-  const int s = ke_find_scene(dt_off, n_scene, j);
+  const int s = u3d_segment_of(dt_off, n_scene, j);
   const float area = (a[9] - a[7]) * (a[10] - a[8]);
   float best = 0.f;
   for (int i = gt_off[s]; i < gt_off[s + 1]; ++i) {

@@ -7,7 +7,7 @@
 // the LiDAR-frame yaw for a bicycle-rack row).
 //   u3d_nusc_convert      one thread per box: LiDAR -> ego -> global (float64), the prediction attribute, the upstream ego-radius drop
 //   u3d_nusc_filter       one thread per box: the devkit filters (ego_dist < class_range, GT points, bicycle / motorcycle in a rack)
-//   u3d_nusc_compact      stable scatter of the valid rows to their exclusive-scan positions (the caller scans the flags)
+//   (the caller scans the flags and keeps the valid rows with u3d_compact_rows, csrc/compact.hip)
 //   u3d_nusc_rank_keys    descending-orderable 64-bit score keys in reversed row order (the caller stable-sorts by score, then class)
 //   u3d_nusc_match        one wave per (class, sample): the four greedy matchings, the sample's GT of the class in LDS
 //   u3d_nusc_accumulate   one workgroup per (class, threshold): tp cumsum, the 101-point interpolation, cummeans, calc_ap / calc_tp
@@ -28,16 +28,6 @@
 #define NU_RACK -2
 #define NU_PI 3.141592653589793
 
-// last s with off[s] <= v (off ascending, off[0] = 0 <= v)
-__device__ static int nu_find_sample(const int* __restrict__ off, int n_sample, int v) {
-  int lo = 0, hi = n_sample;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // conversion.  rows f64 [n][9] = x, y, z, l, w, h, yaw, vx, vy in the LiDAR frame (z: bottom for predictions, gravity centre for GT);
 // calib f64 [n_sample][24] = lidar2ego rotation (3x3 row-major), translation, ego2global rotation, translation.  valid int32 [n]:
@@ -52,7 +42,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_nusc_convert(const double* __res
                                                              int* __restrict__ valid) {
   const int d = blockIdx.x * NU_THREADS + threadIdx.x;
   if (d >= n) return;
-  const int s = nu_find_sample(off, n_sample, d);
+  const int s = u3d_segment_of(off, n_sample, d);
   const double* R1 = calib + (long long)s * 24;
   const double* t1 = R1 + 9;
   const double* R2 = R1 + 12;
@@ -137,7 +127,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_nusc_filter(const double* __rest
   const double* r = rec + (long long)d * NU_REC;
   const int k = (int)r[10];
   if (k < 0 || k >= n_cls) { valid[d] = 0; return; }
-  const int s = nu_find_sample(off, n_sample, d);
+  const int s = u3d_segment_of(off, n_sample, d);
   const double* R1 = calib + (long long)s * 24;
   const double* t2 = R1 + 21;
   const double dx = r[0] - t2[0], dy = r[1] - t2[1];
@@ -160,23 +150,6 @@ extern "C" int32_t u3d_nusc_filter(const double* rec, const int32_t* off, int32_
   U3D_REQUIRE(rec && off && n_sample > 0 && calib && gt_off && cls_range && bike && valid, U3D_ERR_ARG);
   hipLaunchKernelGGL(k_nusc_filter, dim3(u3d_cdiv(n, NU_THREADS)), dim3(NU_THREADS), 0, s, rec, off, n_sample, n, is_pred, calib, gt, gt_off,
                      cls_range, bike, n_cls, valid);
-  U3D_CHECK_LAUNCH();
-  return U3D_OK;
-}
-
-__global__ __launch_bounds__(NU_THREADS) void k_nusc_compact(const double* __restrict__ rec, const int* __restrict__ valid,
-                                                             const int* __restrict__ pos, int n, double* __restrict__ out) {
-  const long long k = (long long)blockIdx.x * NU_THREADS + threadIdx.x;
-  if (k >= (long long)n * NU_REC) return;
-  const int d = (int)(k / NU_REC), c = (int)(k % NU_REC);
-  if (valid[d]) out[(long long)pos[d] * NU_REC + c] = rec[k];
-}
-
-extern "C" int32_t u3d_nusc_compact(const double* rec, const int32_t* valid, const int32_t* pos, int32_t n, double* out, u3d_stream s) {
-  U3D_REQUIRE(n >= 0, U3D_ERR_ARG);
-  if (n == 0) return U3D_OK;
-  U3D_REQUIRE(rec && valid && pos && out, U3D_ERR_ARG);
-  hipLaunchKernelGGL(k_nusc_compact, dim3(u3d_cdiv((long long)n * NU_REC, NU_THREADS)), dim3(NU_THREADS), 0, s, rec, valid, pos, n, out);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

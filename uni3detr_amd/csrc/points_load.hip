@@ -165,16 +165,6 @@ __global__ __launch_bounds__(PL_THREADS) void k_points_floor(const float* __rest
   }
 }
 
-// The scene of row r: scene_off[s] <= r < scene_off[s + 1] (empty scenes skipped over); rows past scene_off[batch] go with the last.
-__device__ __forceinline__ int pl_scene_of(const int* __restrict__ scene_off, int batch, long long r) {
-  int lo = 0, hi = batch;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (scene_off[mid] <= r) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(PL_ROWS) void k_points_gather(const float* __restrict__ raw, long long n_rows, int load_dim,
                                                           const int* __restrict__ scene_off, int batch, PlUseDim use, int n_use,
                                                           const float* __restrict__ floor_h, float* __restrict__ out) {
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(PL_ROWS) void k_points_gather(const float* __restri
       dst[floor_h && k >= 3 ? k + 1 : k] = x;
     }
   }
-  if (floor_h) dst[3] = z - floor_h[pl_scene_of(scene_off, batch, r)];
+  if (floor_h) dst[3] = z - floor_h[u3d_segment_of(scene_off, batch, r)];
 }
 
 __global__ __launch_bounds__(PL_ROWS) void k_points_color(float* __restrict__ points, long long n_rows, int feat, int col0, float m0, float m1,

@@ -28,15 +28,6 @@ struct SwUseDim {
   int d[SW_MAXF];
 };
 
-__device__ __forceinline__ int sw_seg_of(const int* __restrict__ chunk0, int n_seg, int c) {
-  int lo = 0, hi = n_seg;               // chunk0[lo] <= c < chunk0[hi]; empty segments (chunk0[s] == chunk0[s+1]) are skipped over
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (chunk0[mid] <= c) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // The row this thread handles in chunk c, its segment and whether it is kept.  Rows are read only when valid.
 struct SwRow {
   int seg, kind, row;
@@ -48,7 +39,7 @@ __device__ __forceinline__ SwRow sw_row(const float* __restrict__ key, long long
                                         int load_dim, const int* __restrict__ seg_tab, const int* __restrict__ seg_chunk0, int n_seg, int c,
                                         int t) {
   SwRow r;
-  r.seg = sw_seg_of(seg_chunk0, n_seg, c);
+  r.seg = u3d_segment_of(seg_chunk0, n_seg, c);
   const int* e = seg_tab + r.seg * U3D_SWEEPS_SEG_FIELDS;
   r.kind = e[0];
   const long long src0 = e[1];

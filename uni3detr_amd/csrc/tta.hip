@@ -23,15 +23,6 @@
 #define TTA_LDS_CAP U3D_TTA_LDS_CAP
 #define TTA_LDS_THREADS 256
 
-__device__ __forceinline__ int tta_find(const int* __restrict__ off, int stride, int count, int i) {
-  int lo = 0, hi = count;               // off[lo * stride] <= i < off[hi * stride]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid * stride] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ bool tta_valid(float score, int label, int ncls) {
   return isfinite(score) && label >= 0 && label < ncls;
 }
@@ -50,7 +41,7 @@ __global__ void k_tta_prep(const float* __restrict__ boxes, const int* __restric
                            int n, int dim, int coord, float* __restrict__ mapped, float* __restrict__ bev) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || i >= det_off[nviews]) return;
-  const int v = tta_find(det_off, 1, nviews, i);
+  const int v = u3d_segment_of(det_off, nviews, i);
   float* o = mapped + (long long)i * dim;
   for (int k = 0; k < dim; ++k) o[k] = boxes[(long long)i * dim + k];
   dp_box_augment(o, o, dim, inv + (long long)v * TTA_NP, coord);      // in place, as k_boxes_augment
@@ -69,7 +60,7 @@ __global__ void k_tta_rank(const float* __restrict__ scores, const int* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int V = nviews_per_scene;
   if (i >= n || i >= det_off[batch * V]) return;
-  const int s = tta_find(det_off, V, batch, i);
+  const int s = u3d_segment_of(det_off, batch, i, V);
   const int base = det_off[s * V], end = det_off[(s + 1) * V];
   const float sc = scores[i];
   const int lab = labels[i];
@@ -175,7 +166,7 @@ __global__ void k_tta_select(const float* __restrict__ mapped, const float* __re
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   const int V = nviews_per_scene;
   if (g >= n || g >= det_off[batch * V]) return;
-  const int s = tta_find(det_off, V, batch, g);
+  const int s = u3d_segment_of(det_off, batch, g, V);
   const int base = det_off[s * V], r = g - base, nv = nvalid[s];
   if (r >= nv || !keep[g]) return;
   const int i = ord[g];

@@ -18,25 +18,20 @@ Two implementations of the same result: the device path (csrc/eval.hip, through 
 the stable sort of the 64-bit (class, score) keys) and a float64 NumPy restatement for `device="cpu"` (saved results on a machine
 without a GPU).
 """
-import logging
-
 import numpy as np
 import torch
 
+from .eval_common import DetBuffer, as_tensor, default_device, fit_columns, invalid_device, invalid_host, offsets, print_log, to_numpy
+
 _EPS = np.finfo(np.float64).eps
+# the messages of the input checks: a non-finite score, a negative label, a label that num_classes does not cover
+ERRORS = ("indoor evaluation: detection scores must be finite", "indoor evaluation: labels must be non-negative",
+          "indoor evaluation: labels must be below num_classes = {}")
 
 
 # --------------------------------------------------------------------------------------------------
 # input preparation
 # --------------------------------------------------------------------------------------------------
-def _to_numpy(x):
-    if hasattr(x, "tensor"):
-        x = x.tensor
-    if isinstance(x, torch.Tensor):
-        return x.detach().cpu().numpy()
-    return np.asarray(x)
-
-
 def _gt_bottom_boxes(gt_boxes_upright_depth, axis_aligned_lw=False):
     """gravity-centre GT [n,6|7] -> float32 [n,7] bottom-centre (DepthInstance3DBoxes(..., origin=(0.5, 0.5, 0.5)).tensor)."""
     g = np.asarray(gt_boxes_upright_depth)
@@ -57,18 +52,11 @@ def _gt_bottom_boxes(gt_boxes_upright_depth, axis_aligned_lw=False):
 
 
 def _flatten_dt(dt_annos):
-    boxes, scores, labels, counts = [], [], [], []
+    buf = DetBuffer(7, torch.float32, "cpu")
     for d in dt_annos:
-        if "pts_bbox" in d:
-            d = d["pts_bbox"]
-        b = _to_numpy(d["boxes_3d"]).astype(np.float32)
-        b = b.reshape(b.shape[0], -1)[:, :7] if b.size else np.zeros((0, 7), np.float32)
-        boxes.append(b)
-        scores.append(_to_numpy(d["scores_3d"]).astype(np.float32).reshape(-1))
-        labels.append(_to_numpy(d["labels_3d"]).astype(np.int64).reshape(-1))
-        counts.append(b.shape[0])
-    return (np.concatenate(boxes) if boxes else np.zeros((0, 7), np.float32), np.concatenate(scores) if scores else np.zeros(0, np.float32),
-            np.concatenate(labels) if labels else np.zeros(0, np.int64), np.asarray(counts, np.int64))
+        buf.add(d)
+    boxes, scores, labels, _ = buf.cat()
+    return boxes.numpy(), scores.numpy(), labels.numpy(), np.asarray(buf.counts, np.int64)
 
 
 def _flatten_gt(gt_annos, axis_aligned_lw):
@@ -86,34 +74,17 @@ def _flatten_gt(gt_annos, axis_aligned_lw):
             np.asarray(counts, np.int64))
 
 
-def _rows7(t, dev):
-    """Boxes [n, >=6] (any n, including 0) -> float32 [n, 7] on `dev`; a missing yaw column is 0."""
-    t = torch.as_tensor(t).to(dev, torch.float32)
-    n = t.shape[0] if t.dim() else 0
-    out = torch.zeros((n, 7), dtype=torch.float32, device=dev)
-    if t.numel():
-        t = t.reshape(n, -1)
-        out[:, : min(7, t.shape[1])] = t[:, :7]
-    return out
-
-
-def _offsets(counts):
-    off = np.zeros(len(counts) + 1, np.int64)
-    off[1:] = np.cumsum(counts)
-    return off
-
-
-def _check_inputs(scores, det_labels, gt_labels):
-    if not np.all(np.isfinite(scores)):
-        raise ValueError("indoor evaluation: detection scores must be finite")
-    if (det_labels.size and det_labels.min() < 0) or (gt_labels.size and gt_labels.min() < 0):
-        raise ValueError("indoor evaluation: labels must be non-negative")
+def _raise_invalid(flags, num_classes):
+    """flags: eval_common.invalid_host / invalid_device over the detection and GT labels"""
+    for bad, msg in zip(flags, ERRORS):
+        if bad:
+            raise ValueError(msg.format(num_classes))
 
 
 # --------------------------------------------------------------------------------------------------
 # host path (float64 NumPy)
 # --------------------------------------------------------------------------------------------------
-def _rect(cx, cy, w, h, a):
+def rect_corners(cx, cy, w, h, a):
     """[P,4,2] counter-clockwise corners (pp_rect)."""
     c, s = np.cos(a), np.sin(a)
     sx = np.array([-0.5, 0.5, 0.5, -0.5])
@@ -122,7 +93,7 @@ def _rect(cx, cy, w, h, a):
     return np.stack([cx[:, None] + x * c[:, None] - y * s[:, None], cy[:, None] + x * s[:, None] + y * c[:, None]], -1)
 
 
-def _inter_area(a, b):
+def rect_inter_area(a, b):
     """Area of rectangle a clipped by rectangle b (Sutherland-Hodgman over b's 4 edges, the clip order of pp_inter_area), [P]."""
     P = a.shape[0]
     poly = np.zeros((P, 8, 2))
@@ -165,9 +136,9 @@ def box_iou3d_pairs(p, q, chunk=1 << 16):
         w2, h2 = np.maximum(b[:, 3], 1e-4), np.maximum(b[:, 4], 1e-4)
         a1, a2 = w1 * h1, w2 * h2
         z = np.zeros(a.shape[0])
-        ra = _rect(z, z, w1, h1, a[:, 6])
-        rb = _rect(b[:, 0] - a[:, 0], b[:, 1] - a[:, 1], w2, h2, b[:, 6])
-        inter = _inter_area(ra, rb)
+        ra = rect_corners(z, z, w1, h1, a[:, 6])
+        rb = rect_corners(b[:, 0] - a[:, 0], b[:, 1] - a[:, 1], w2, h2, b[:, 6])
+        inter = rect_inter_area(ra, rb)
         with np.errstate(divide="ignore", invalid="ignore"):
             iou2d = np.where((a1 >= 1e-14) & (a2 >= 1e-14), inter / (a1 + a2 - inter), 0.0)
             ov_bev = iou2d * (a1 + a2) / (1.0 + iou2d)
@@ -284,15 +255,7 @@ def _host_eval(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, 
 def _device_eval(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, num_classes, iou_thrs, device):
     """All inputs are torch tensors on `device` (boxes f32 [.,7], scores f32, labels int32, offsets int32)."""
     from . import native as nv
-    bad = torch.stack([(~torch.isfinite(det_scores)).any(), (det_labels < 0).any(), (gt_labels < 0).any(),
-                       (det_labels >= num_classes).any(), (gt_labels >= num_classes).any()])
-    bad = bad.cpu()                                                     # the one validation sync
-    if bool(bad[0]):
-        raise ValueError("indoor evaluation: detection scores must be finite")
-    if bool(bad[1]) or bool(bad[2]):
-        raise ValueError("indoor evaluation: labels must be non-negative")
-    if bool(bad[3]) or bool(bad[4]):
-        raise ValueError(f"indoor evaluation: labels must be below num_classes = {num_classes}")
+    _raise_invalid(invalid_device(det_scores, (det_labels, gt_labels), num_classes), num_classes)
     thr = torch.tensor([float(t) for t in iou_thrs], dtype=torch.float32, device=device)
     r = nv.eval_indoor(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, num_classes, thr)
     seg = r["seg"].cpu().numpy()
@@ -305,13 +268,13 @@ def evaluate_flat(det_boxes, det_scores, det_labels, det_counts, gt_boxes, gt_la
                   device="cpu"):
     """Array-level entry: detections / GT concatenated over scenes (bottom-centre boxes [.,7], per-scene counts).
     -> dict with ap float32 [T, C], rec float64 [T, C], npos / ndet [C] (numpy) and the intermediate per-detection results."""
-    det_boxes = np.asarray(_to_numpy(det_boxes), np.float32).reshape(-1, 7)
-    det_scores = np.asarray(_to_numpy(det_scores), np.float32).reshape(-1)
-    det_labels = np.asarray(_to_numpy(det_labels), np.int64).reshape(-1)
-    gt_boxes = np.asarray(_to_numpy(gt_boxes), np.float32).reshape(-1, 7)
-    gt_labels = np.asarray(_to_numpy(gt_labels), np.int64).reshape(-1)
-    det_off, gt_off = _offsets(np.asarray(det_counts)), _offsets(np.asarray(gt_counts))
-    _check_inputs(det_scores, det_labels, gt_labels)
+    det_boxes = np.asarray(to_numpy(det_boxes), np.float32).reshape(-1, 7)
+    det_scores = np.asarray(to_numpy(det_scores), np.float32).reshape(-1)
+    det_labels = np.asarray(to_numpy(det_labels), np.int64).reshape(-1)
+    gt_boxes = np.asarray(to_numpy(gt_boxes), np.float32).reshape(-1, 7)
+    gt_labels = np.asarray(to_numpy(gt_labels), np.int64).reshape(-1)
+    det_off, gt_off = offsets(det_counts), offsets(gt_counts)
+    _raise_invalid(invalid_host(det_scores, (det_labels, gt_labels)), None)
     num_classes = int(max(num_classes, det_labels.max(initial=-1) + 1, gt_labels.max(initial=-1) + 1))
     if torch.device(device).type == "cpu":
         return _host_eval(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, num_classes, iou_thrs)
@@ -325,19 +288,6 @@ def evaluate_flat(det_boxes, det_scores, det_labels, det_counts, gt_boxes, gt_la
 # --------------------------------------------------------------------------------------------------
 # result dict and summary table
 # --------------------------------------------------------------------------------------------------
-def _print_log(msg, logger=None):
-    if logger is None:
-        print(msg)
-    elif isinstance(logger, logging.Logger):
-        logger.info(msg)
-    elif logger == "silent":
-        pass
-    elif isinstance(logger, str):
-        logging.getLogger(logger).info(msg)
-    else:
-        raise TypeError(f"logger should be a logging.Logger, a str or None, got {type(logger)}")
-
-
 def _nanmean(vals, dtype):
     v = np.asarray([x for x in vals if not np.isnan(x)], dtype)
     if v.size == 0:
@@ -362,7 +312,7 @@ def _results(res, label2cat, iou_thrs, logger):
         ret[f"mAR_{thr:.2f}"] = _nanmean(recs, np.float64)
         cols.append([f"{float(a):.4f}" for a in aps] + [f"{ret[f'mAP_{thr:.2f}']:.4f}"])
         cols.append([f"{r:.4f}" for r in recs] + [f"{ret[f'mAR_{thr:.2f}']:.4f}"])
-    _print_log("\n" + format_table([header] + [list(r) for r in zip(*cols)]), logger)
+    print_log("\n" + format_table([header] + [list(r) for r in zip(*cols)]), logger)
     return ret
 
 
@@ -378,12 +328,6 @@ def format_table(rows):
 # --------------------------------------------------------------------------------------------------
 # public interface
 # --------------------------------------------------------------------------------------------------
-def _default_device(device):
-    if device is None:
-        return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-    return torch.device(device)
-
-
 def indoor_eval(gt_annos, dt_annos, metric, label2cat, logger=None, box_type_3d=None, box_mode_3d=None, axis_aligned_lw=False, device=None):
     """mmdet3d's indoor_eval (the reference's indoor_eval_ov with every class seen): per-class AP / recall at each IoU threshold of
     `metric`, their means over the non-NaN classes, and a printed summary table.
@@ -396,7 +340,7 @@ def indoor_eval(gt_annos, dt_annos, metric, label2cat, logger=None, box_type_3d=
     db, ds, dl, dc = _flatten_dt(dt_annos)
     gb, gl, gc = _flatten_gt(gt_annos, axis_aligned_lw)
     num_classes = int(max([int(k) for k in label2cat.keys()] + [-1])) + 1
-    res = evaluate_flat(db, ds, dl, dc, gb, gl, gc, num_classes, tuple(metric), _default_device(device))
+    res = evaluate_flat(db, ds, dl, dc, gb, gl, gc, num_classes, tuple(metric), default_device(device))
     return _results(res, label2cat, tuple(metric), logger)
 
 
@@ -409,7 +353,7 @@ def indoor_eval_ov(seen_classes, gt_annos, dt_annos, metric, label2cat, logger=N
     for name, keep in (("seen", True), ("unseen", False)):
         v = [ret[f"{cat}_AP_{t}"] for cat in label2cat.values() if (cat in seen_classes) == keep and f"{cat}_AP_{t}" in ret]
         if v:
-            _print_log(f"{name} AP{int(round(float(metric[0]) * 100))}: {_nanmean(v, np.float64)}", logger)
+            print_log(f"{name} AP{int(round(float(metric[0]) * 100))}: {_nanmean(v, np.float64)}", logger)
     return ret
 
 
@@ -427,87 +371,54 @@ class IndoorEvaluator:
         self.reset()
 
     def reset(self):
-        self._det = {"boxes": [], "scores": [], "labels": []}
+        self._det = DetBuffer(7, torch.float32, self.device)
         self._gt = {"boxes": [], "labels": []}
-        self._det_counts, self._gt_counts = [], []
+        self._gt_counts = []
 
     def __len__(self):
-        return len(self._det_counts)
+        return len(self._det)
 
     def add(self, bbox_list, gt_boxes, gt_labels):
         """bbox_list: per scene [boxes [n,>=7] bottom-centre, scores [n], labels [n]] (or a dict with boxes_3d / scores_3d / labels_3d);
         gt_boxes: per scene a gravity-centre tensor [m,6|7] (gt_boxes_upright_depth layout), or a box structure with `.tensor`
         (bottom-centre, the mmdet3d convention of gt_bboxes_3d); gt_labels: per scene [m]."""
         assert len(bbox_list) == len(gt_boxes) == len(gt_labels)
-        if not bbox_list:
-            return
-        dev = self.device
-        db, ds, dl = [], [], []
         for det in bbox_list:
-            if isinstance(det, dict):
-                det = det.get("pts_bbox", det)
-                det = (det["boxes_3d"], det["scores_3d"], det["labels_3d"])
-            b, s, l = det
-            b = _rows7(b.tensor if hasattr(b, "tensor") else b, dev)      # a scene may have no detections
-            db.append(b)
-            ds.append(torch.as_tensor(s).to(dev, torch.float32).reshape(-1))
-            dl.append(torch.as_tensor(l).to(dev, torch.int32).reshape(-1))
-            self._det_counts.append(int(b.shape[0]))
-        self._det["boxes"].append(torch.cat(db))
-        self._det["scores"].append(torch.cat(ds))
-        self._det["labels"].append(torch.cat(dl))
+            self._det.add(det)                                              # a scene may have no detections
         self._add_gt(gt_boxes, gt_labels)
 
     def _add_gt(self, gt_boxes, gt_labels):
         dev = self.device
-        gb, gl = [], []
         for g, lab in zip(gt_boxes, gt_labels):
-            if hasattr(g, "tensor"):
-                gbox = _rows7(g.tensor, dev)
-            else:
-                gbox = _rows7(g, dev)
-                gbox[:, 2] = gbox[:, 2] + gbox[:, 5] * -0.5            # gravity -> bottom centre, as _gt_bottom_boxes
-            gb.append(gbox)
-            gl.append(torch.as_tensor(lab).to(dev, torch.int32).reshape(-1))
+            gbox = fit_columns(as_tensor(g, torch.float32, dev), 7)
+            if not hasattr(g, "tensor"):
+                gbox = gbox.clone()
+                gbox[:, 2] = gbox[:, 2] + gbox[:, 5] * -0.5                # gravity -> bottom centre, as _gt_bottom_boxes
+            self._gt["boxes"].append(gbox)
+            self._gt["labels"].append(as_tensor(lab, torch.int32, dev).reshape(-1))
             self._gt_counts.append(int(gbox.shape[0]))
-        self._gt["boxes"].append(torch.cat(gb))
-        self._gt["labels"].append(torch.cat(gl))
 
     def add_store(self, store, gt_boxes, gt_labels):
         """add() for every scene of a det_store.DetStore at once, in the store's scene order: the detections are store.packed() (they
         never leave the device), the per-scene counts come from one read of its det_off.  gt_boxes / gt_labels: one entry per scene of
         the store, as for add().  Bit-identical to add() over the same scenes in the same order.  Labels are checked by compute()."""
-        errors = ("indoor evaluation: detection scores must be finite", "")
-        if self.device.type == "cpu":
-            return self.add(store.results(errors=errors), gt_boxes, gt_labels)
-        boxes, scores, labels, off = store.packed(errors=errors)
-        counts = torch.diff(off).tolist()
-        if not len(counts) == len(gt_boxes) == len(gt_labels):
-            raise ValueError(f"IndoorEvaluator.add_store: the store holds {len(counts)} scenes, GT was given for {len(gt_boxes)}")
-        if not counts:
-            return
-        assert sum(counts) == boxes.shape[0]
-        self._det["boxes"].append(_rows7(boxes, self.device))
-        self._det["scores"].append(scores.to(self.device))
-        self._det["labels"].append(labels.to(self.device))
-        self._det_counts.extend(counts)
+        assert len(gt_boxes) == len(gt_labels)
+        self._det.add_store(store, len(gt_boxes), f"IndoorEvaluator.add_store: the store holds {{n}} scenes, GT was given for {len(gt_boxes)}",
+                            0, (ERRORS[0], ""))
         self._add_gt(gt_boxes, gt_labels)
 
     def compute(self, label2cat=None, logger="silent"):
         """-> the dict of `indoor_eval` (label2cat defaults to {c: str(c)}).  Labels outside [0, num_classes) raise ValueError."""
         if label2cat is None:
             label2cat = {c: str(c) for c in range(self.num_classes)}
-        if not self._det_counts:
+        if not len(self):
             raise ValueError("IndoorEvaluator.compute: nothing was added")
-        cat = lambda xs, shape, dt: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.device)     # noqa: E731
-        db, ds, dl = cat(self._det["boxes"], (0, 7), torch.float32), cat(self._det["scores"], (0,), torch.float32), cat(self._det["labels"], (0,), torch.int32)
-        gb, gl = cat(self._gt["boxes"], (0, 7), torch.float32), cat(self._gt["labels"], (0,), torch.int32)
+        db, ds, dl, det_off = self._det.cat()
+        gb = torch.cat(self._gt["boxes"]) if self._gt["boxes"] else torch.zeros((0, 7), dtype=torch.float32, device=self.device)
+        gl = torch.cat(self._gt["labels"]) if self._gt["labels"] else torch.zeros((0,), dtype=torch.int32, device=self.device)
         if self.device.type == "cpu":
-            if (dl.numel() and int(dl.max()) >= self.num_classes) or (gl.numel() and int(gl.max()) >= self.num_classes):
-                raise ValueError(f"indoor evaluation: labels must be below num_classes = {self.num_classes}")
-            res = evaluate_flat(db, ds, dl, self._det_counts, gb, gl, self._gt_counts, self.num_classes, self.iou_thrs, "cpu")
+            _raise_invalid(invalid_host(ds.numpy(), (dl.numpy(), gl.numpy()), self.num_classes), self.num_classes)
+            res = evaluate_flat(db, ds, dl, self._det.counts, gb, gl, self._gt_counts, self.num_classes, self.iou_thrs, "cpu")
         else:
-            i32 = lambda a: torch.tensor(_offsets(a), dtype=torch.int32, device=self.device)      # noqa: E731
-            res = _device_eval(db.contiguous(), ds.contiguous(), dl.contiguous(), i32(self._det_counts), gb.contiguous(), gl.contiguous(),
-                               i32(self._gt_counts), self.num_classes, self.iou_thrs, self.device)
+            res = _device_eval(db, ds, dl, det_off, gb, gl, offsets(self._gt_counts, self.device), self.num_classes, self.iou_thrs, self.device)
         return _results(res, label2cat, self.iou_thrs, logger)

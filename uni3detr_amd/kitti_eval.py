@@ -26,8 +26,12 @@ yardstick.  Everything is deterministic: any batching of the same scenes gives b
 import numpy as np
 import torch
 
-from .evaluation import _inter_area, _print_log, _rect, _to_numpy
+from .eval_common import DetBuffer, default_device, invalid_device, invalid_host, offsets, print_log, raise_invalid
+from .evaluation import rect_corners, rect_inter_area
 
+# the messages of the detection checks: a non-finite score, a label that does not index class_names
+ERRORS = ("kitti_eval: detection scores must be finite", "KittiEvaluator: labels must index class_names")
+_SHORT = "kitti_eval: boxes_3d must have 7 columns (x, y, z, dx, dy, dz, yaw)"
 CLASS_TO_NAME = {0: "Car", 1: "Pedestrian", 2: "Cyclist"}
 _NAME_TO_ID = {v.lower(): k for k, v in CLASS_TO_NAME.items()}
 # class codes of the device records: Car, Pedestrian, Cyclist, Van, Person_sitting, DontCare, anything else
@@ -99,8 +103,7 @@ def _encode(anno, is_gt):
         r[:, 12] = bits
     else:
         sc = np.asarray(anno["score"], np.float64).reshape(n)
-        if not np.all(np.isfinite(sc)):
-            raise ValueError("kitti_eval: detection scores must be finite")
+        raise_invalid(invalid_host(sc, np.zeros(0)), ERRORS)
         r[:, 12] = sc
     r[:, 13] = _codes(anno["name"])
     return r
@@ -155,7 +158,8 @@ def box_overlaps(dt, gt):
         return np.zeros((n, k)), np.zeros((n, k))
     p, q = np.repeat(a, k, 0), np.tile(b, (n, 1))
     z = np.zeros(p.shape[0])
-    inter = _inter_area(_rect(z, z, p[:, 3], p[:, 5], -p[:, 6]), _rect(q[:, 0] - p[:, 0], q[:, 2] - p[:, 2], q[:, 3], q[:, 5], -q[:, 6]))
+    inter = rect_inter_area(rect_corners(z, z, p[:, 3], p[:, 5], -p[:, 6]),
+                            rect_corners(q[:, 0] - p[:, 0], q[:, 2] - p[:, 2], q[:, 3], q[:, 5], -q[:, 6]))
     ok = (p[:, 3:6] > 0).all(1) & (q[:, 3:6] > 0).all(1)
     inter = np.where(ok, inter, 0.0)
     dy = np.minimum(p[:, 1], q[:, 1]) - np.maximum(p[:, 1] - p[:, 4], q[:, 1] - q[:, 4])
@@ -293,7 +297,7 @@ def host_core(dt, dt_counts, gt, gt_counts, class_ids, metrics, aos, ov=None, dc
     """float64 restatement of the device path over records (see _encode).  ov / dcf: optional per-scene overlaps [3, nd, ng] and DontCare
     IoF [nd] to use instead of computing them.  -> dict with the same fields as the device path (numpy)."""
     S = len(dt_counts)
-    doff, goff = np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int64), np.concatenate([[0], np.cumsum(gt_counts)]).astype(np.int64)
+    doff, goff = offsets(dt_counts), offsets(gt_counts)
     dts = [dt[doff[s]:doff[s + 1]] for s in range(S)]
     gts = [gt[goff[s]:goff[s + 1]] for s in range(S)]
     if ov is None:
@@ -361,8 +365,7 @@ def _device_core(dt, dt_off, gt, gt_off, dt_counts, gt_counts, class_ids, metric
 
 
 def _upload(rec, counts, dev):
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-    return torch.as_tensor(rec.astype(np.float32), device=dev).reshape(-1, 16), torch.as_tensor(off, device=dev)
+    return torch.as_tensor(rec.astype(np.float32), device=dev).reshape(-1, 16), offsets(counts, dev)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -404,14 +407,8 @@ def _results(ap, class_ids, metrics, aos, logger=None):
                 for d in range(3):
                     ret[_KEYS["overall"].format(metric=_KEYS["metric"][x], ap=kind, difficulty=DIFFICULTY[d])] = float(mean[d])
     if logger is not None:
-        _print_log(result, logger)
+        print_log(result, logger)
     return result, ret
-
-
-def _default_device(device):
-    if device is None:
-        return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-    return torch.device(device)
 
 
 def _metric_ids(eval_types):
@@ -440,7 +437,7 @@ def kitti_eval(gt_annos, dt_annos, current_classes, eval_types=("bbox", "bev", "
     gt, gc = _encode_all(gt_annos, True)
     dt, dc = _encode_all(dt_annos, False)
     aos = _compute_aos(gt_annos, dt_annos) and 0 in metrics
-    r = evaluate_records(dt, dc, gt, gc, class_ids, metrics, aos, _default_device(device))
+    r = evaluate_records(dt, dc, gt, gc, class_ids, metrics, aos, default_device(device))
     return _results(r["ap"], class_ids, metrics, aos)
 
 
@@ -478,28 +475,34 @@ def _empty_anno(sample_idx):
                 sample_idx=np.array([], np.int64) if sample_idx is None else np.full(0, sample_idx, np.int64))
 
 
-def _result_arrays(res):
-    if "pts_bbox" in res:
-        res = res["pts_bbox"]
-    b = _to_numpy(res["boxes_3d"]).astype(np.float64)
-    b = b.reshape(b.shape[0], -1)[:, :7] if b.size else np.zeros((0, 7))
-    return b, _to_numpy(res["scores_3d"]).astype(np.float64).reshape(-1), _to_numpy(res["labels_3d"]).astype(np.int64).reshape(-1)
+def _scene(info):
+    """what the conversion needs of one info: (T, P2, image (H, W), image_idx or None, the device path's calibration row T | P2)"""
+    T, P2, hw = _calib(info)
+    return T, P2, hw, info.get("image", {}).get("image_idx"), np.concatenate([T.reshape(-1), P2.reshape(-1)])
+
+
+def _host_buffer():
+    return DetBuffer(7, torch.float64, "cpu", short=_SHORT)
 
 
 def lidar_results_to_kitti(results, infos, class_names, pcd_limit_range=(0, -40, -3, 70.4, 40, 0.0)):
     """`Uni3DETR.simple_test` results (LiDAR bottom-centre boxes, counter-clockwise yaw) -> KITTI dt annos, the float64 counterpart of
     KittiDataset.bbox2result_kitti + convert_valid_bboxes (infos: mmdet3d KITTI info dicts with calib / image)."""
     assert len(results) == len(infos)
+    buf = _host_buffer()
+    for res in results:
+        buf.add(res)
+    return _buffer_to_kitti(buf, [_scene(i) for i in infos], class_names, pcd_limit_range)
+
+
+def _buffer_to_kitti(buf, scenes, class_names, pcd_limit_range):
+    """lidar_results_to_kitti over a host DetBuffer (float64) and the scenes' _scene() tuples"""
+    boxes, scores, labels, off = (t.numpy() for t in buf.cat())
+    raise_invalid(invalid_host(scores, labels, len(class_names)), ERRORS)
     lim = np.asarray(pcd_limit_range, np.float64)
     out = []
-    for res, info in zip(results, infos):
-        sample_idx = info.get("image", {}).get("image_idx")
-        b, sc, lab = _result_arrays(res)
-        if lab.size and (lab.min() < 0 or lab.max() >= len(class_names)):
-            raise ValueError("lidar_results_to_kitti: labels must index class_names")
-        if not np.all(np.isfinite(sc)):
-            raise ValueError("kitti_eval: detection scores must be finite")
-        T, P2, hw = _calib(info)
+    for s, (T, P2, hw, sample_idx, _) in enumerate(scenes):
+        b, sc, lab = boxes[off[s]:off[s + 1]], scores[off[s]:off[s + 1]], labels[off[s]:off[s + 1]]
         loc = np.concatenate([b[:, :3], np.ones((b.shape[0], 1))], 1) @ T.T
         loc = loc[:, :3]
         dims = b[:, [3, 5, 4]]
@@ -540,90 +543,57 @@ class KittiEvaluator:
         self.reset()
 
     def reset(self):
-        self._boxes, self._scores, self._labels, self._counts = [], [], [], []
-        self._gt, self._gt_counts, self._gt_alpha0 = [], [], []
-        self._calib, self._img, self._results, self._infos = [], [], [], []
+        on_host = self.device.type == "cpu"                                # the host path is the float64 restatement
+        self._det = DetBuffer(7, torch.float64 if on_host else torch.float32, self.device, short=_SHORT)
+        self._gt, self._gt_counts, self._gt_alpha0, self._scenes = [], [], [], []
 
     def __len__(self):
-        return len(self._counts)
+        return len(self._gt_counts)
 
     def add(self, results, infos):
         assert len(results) == len(infos)
-        for res, info in zip(results, infos):
-            if self.device.type == "cpu":
-                self._results.append(res)
-                self._infos.append(info)
-            else:
-                r = res.get("pts_bbox", res)
-                b = r["boxes_3d"]
-                b = torch.as_tensor(b.tensor if hasattr(b, "tensor") else b).to(self.device, torch.float32)
-                b = b.reshape(b.shape[0], -1)[:, :7] if b.numel() else torch.zeros((0, 7), dtype=torch.float32, device=self.device)
-                self._boxes.append(b)
-                self._scores.append(torch.as_tensor(r["scores_3d"]).to(self.device, torch.float32).reshape(-1))
-                self._labels.append(torch.as_tensor(r["labels_3d"]).to(self.device, torch.int32).reshape(-1))
-                self._counts.append(int(b.shape[0]))
-            self._add_info(info)
+        for res in results:
+            self._det.add(res)
+        self._add_infos(infos)
 
-    def _add_info(self, info):
-        """one scene's calibration rows (device path) and encoded GT"""
-        if self.device.type != "cpu":
-            T, P2, hw = _calib(info)
-            self._calib.append(np.concatenate([T.reshape(-1), P2.reshape(-1)]))
-            self._img.append(hw)
-        g = _encode(info["annos"], True)
-        self._gt.append(g)
-        self._gt_counts.append(g.shape[0])
-        self._gt_alpha0.append(g[0, 11] if g.shape[0] else None)
-        if self.device.type == "cpu":
-            self._counts.append(0)
+    def _add_infos(self, infos):
+        """per scene: what the conversion needs of its calibration, and the encoded GT"""
+        for info in infos:
+            self._scenes.append(_scene(info))
+            g = _encode(info["annos"], True)
+            self._gt.append(g)
+            self._gt_counts.append(g.shape[0])
+            self._gt_alpha0.append(g[0, 11] if g.shape[0] else None)
 
     def add_store(self, store, infos):
         """add() for every scene of a det_store.DetStore at once, in the store's scene order: the detections are store.packed() (they
         never leave the device), the per-scene counts come from one read of its det_off; infos: one per scene of the store.
         Bit-identical to add() over the same scenes in the same order."""
-        errors = ("kitti_eval: detection scores must be finite", "KittiEvaluator: labels must index class_names")
-        if self.device.type == "cpu":
-            return self.add(store.results(len(self.class_names), errors), infos)
-        boxes, scores, labels, off = store.packed(len(self.class_names), errors)
-        counts = torch.diff(off).tolist()
-        if len(counts) != len(infos):
-            raise ValueError(f"KittiEvaluator.add_store: the store holds {len(counts)} scenes, {len(infos)} infos were given")
-        if not counts:
-            return
-        assert sum(counts) == boxes.shape[0]
-        self._boxes.append(boxes.to(self.device)[:, :7])
-        self._scores.append(scores.to(self.device))
-        self._labels.append(labels.to(self.device))
-        self._counts.extend(counts)
-        for info in infos:
-            self._add_info(info)
+        self._det.add_store(store, len(infos), f"KittiEvaluator.add_store: the store holds {{n}} scenes, {len(infos)} infos were given",
+                            len(self.class_names), ERRORS)
+        self._add_infos(infos)
 
     def compute(self, logger="silent"):
         """-> ret_dict of `kitti_eval` over everything added (the result string goes to `logger`)."""
-        if not self._gt_counts:
+        if not len(self):
             raise ValueError("KittiEvaluator.compute: nothing was added")
         gt = np.concatenate(self._gt)
         valid_alpha_gt = any(a is not None and a != -10 for a in self._gt_alpha0)
         if self.device.type == "cpu":
-            dt_annos = lidar_results_to_kitti(self._results, self._infos, self.class_names, self.pcd_limit_range)
+            dt_annos = _buffer_to_kitti(self._det, self._scenes, self.class_names, self.pcd_limit_range)
             dt, dc = _encode_all(dt_annos, False)
             aos = valid_alpha_gt and any(np.any(a["alpha"] != -10) for a in dt_annos) and 0 in self.metrics
             r = host_core(dt, dc, gt, self._gt_counts, self.class_ids, self.metrics, aos)
             return _results(r["ap"], self.class_ids, self.metrics, aos, logger)[1]
         from . import native as nv
         dev = self.device
-        boxes, scores, labels = torch.cat(self._boxes), torch.cat(self._scores), torch.cat(self._labels)
-        bad = torch.stack([(~torch.isfinite(scores)).any(), ((labels < 0) | (labels >= len(self.class_names))).any()]).cpu()
-        if bool(bad[0]):
-            raise ValueError("kitti_eval: detection scores must be finite")
-        if bool(bad[1]):
-            raise ValueError("KittiEvaluator: labels must index class_names")
-        off = torch.as_tensor(np.concatenate([[0], np.cumsum(self._counts)]).astype(np.int32), device=dev)
-        calib = torch.as_tensor(np.asarray(self._calib, np.float32).reshape(-1, 32), device=dev)
-        img = torch.as_tensor(np.asarray(self._img, np.float32).reshape(-1, 2), device=dev)
+        boxes, scores, labels, off = self._det.cat()
+        raise_invalid(invalid_device(scores, labels, len(self.class_names)), ERRORS)
+        calib = torch.as_tensor(np.asarray([s[4] for s in self._scenes], np.float32).reshape(-1, 32), device=dev)
+        img = torch.as_tensor(np.asarray([s[2] for s in self._scenes], np.float32).reshape(-1, 2), device=dev)
         codes = torch.as_tensor(_codes(self.class_names).astype(np.int32), device=dev)
         lim = torch.as_tensor(np.asarray(self.pcd_limit_range, np.float32), device=dev)
-        dt, dt_off = nv.kitti_convert(boxes.contiguous(), scores.contiguous(), labels.contiguous(), off, calib, img, codes, lim)
+        dt, dt_off = nv.kitti_convert(boxes, scores, labels, off, calib, img, codes, lim)
         dt_counts = np.diff(dt_off.cpu().numpy()).tolist()
         aos = valid_alpha_gt and bool((dt[:, 11] != -10).any()) and 0 in self.metrics
         g, goff = _upload(gt, self._gt_counts, dev)

@@ -1474,6 +1474,21 @@ def eval_indoor(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels,
 KITTI_NT = 41
 
 
+def compact_rows(rec, valid, off):
+    """The rows of rec [n, k] with valid int32 [n] set, in input order (u3d_compact_rows after an ATen scan of the flags), and the
+    offsets int32 [S+1] of the kept rows for the CSR offsets `off` of the input.  -> (out [m, k], new_off).  One host synchronisation (m)."""
+    dev = off.device
+    incl = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), torch.cumsum(valid, 0, dtype=torch.int32)])
+    new_off = incl[off.long()].to(torch.int32).contiguous()
+    pos = incl[:-1].contiguous()
+    m = int(incl[-1])
+    out = torch.empty((m, rec.shape[1]), dtype=rec.dtype, device=dev)
+    if m:                                                                    # nothing kept: nothing to launch (and `out` has no storage)
+        _check(lib().u3d_compact_rows(_ptr(rec), _ptr(valid), _ptr(pos), rec.shape[0], rec.shape[1] * rec.element_size(), _ptr(out),
+                                      _stream()), "compact_rows")
+    return out, new_off
+
+
 def kitti_convert(boxes, scores, labels, off, calib, img, label_code, lim):
     """LiDAR detections -> KITTI records (u3d_kitti_convert + a stable compaction).  boxes f32 [n,7] bottom-centre, scores f32 [n],
     labels int32 [n], off int32 [S+1], calib f32 [S,32], img f32 [S,2] (H, W), label_code int32 [L], lim f32 [6] (all on the device).
@@ -1484,13 +1499,7 @@ def kitti_convert(boxes, scores, labels, off, calib, img, label_code, lim):
     valid = torch.empty((n,), dtype=torch.int32, device=dev)
     _check(lib().u3d_kitti_convert(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(off), S, n, _ptr(calib), _ptr(img), _ptr(label_code),
                                    label_code.numel(), _ptr(lim), _ptr(rec), _ptr(valid), _stream()), "kitti_convert")
-    incl = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), torch.cumsum(valid, 0, dtype=torch.int32)])
-    new_off = incl[off.long()].to(torch.int32).contiguous()
-    pos = incl[:-1].contiguous()
-    m = int(incl[-1])
-    out = torch.empty((m, 16), dtype=torch.float32, device=dev)
-    _check(lib().u3d_kitti_compact(_ptr(rec), _ptr(valid), _ptr(pos), n, _ptr(out), _stream()), "kitti_compact")
-    return out, new_off
+    return compact_rows(rec, valid, off)
 
 
 def kitti_eval_core(dt, dt_off, gt, gt_off, cls, gfid, gmet, gmin, aos, dt_counts, gt_counts):
@@ -1557,12 +1566,7 @@ def nusc_to_global(rows, cls, attr, aux, off, calib, is_pred, cls_range, attr_mo
         gt_rec, gt_off = rec, off
     _check(lib().u3d_nusc_filter(_ptr(rec), _ptr(off), S, n, int(is_pred), _ptr(calib), _ptr(gt_rec) if gt_rec.numel() else None,
                                  _ptr(gt_off), _ptr(cls_range), _ptr(bike), C, _ptr(valid), _stream()), "nusc_filter")
-    incl = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), torch.cumsum(valid, 0, dtype=torch.int32)])
-    new_off = incl[off.long()].to(torch.int32).contiguous()
-    pos = incl[:-1].contiguous()
-    m = int(incl[-1])
-    out = torch.empty((m, NUSC_REC), dtype=torch.float64, device=dev)
-    _check(lib().u3d_nusc_compact(_ptr(rec), _ptr(valid), _ptr(pos), n, _ptr(out), _stream()), "nusc_compact")
+    out, new_off = compact_rows(rec, valid, off)
     return rec, valid, out, new_off
 
 

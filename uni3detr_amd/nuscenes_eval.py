@@ -48,8 +48,12 @@ import warnings
 import numpy as np
 import torch
 
-from .evaluation import _print_log, _to_numpy
+from .eval_common import DetBuffer, default_device, invalid_device, invalid_host, offsets, print_log, raise_invalid
 
+# the messages of the prediction checks: a non-finite score, a label that does not index class_names; too few columns; too many boxes
+ERRORS = ("nuscenes_eval: detection scores must be finite", "nuscenes_eval: labels must index class_names")
+_SHORT = "nuscenes_eval: boxes_3d must have 9 columns (x, y, z, l, w, h, yaw, vx, vy)"
+_TOO_MANY = "nuscenes_eval: a sample has {n} predictions, more than {cap}"
 CLASSES = ("car", "truck", "trailer", "bus", "construction_vehicle", "bicycle", "motorcycle", "pedestrian", "traffic_cone", "barrier")
 CLASS_RANGE = dict(car=50, truck=50, bus=50, trailer=50, construction_vehicle=50, pedestrian=40, motorcycle=40, bicycle=40,
                    traffic_cone=30, barrier=30)
@@ -141,23 +145,16 @@ def _calib(info):
                            quaternion_matrix(info["ego2global_rotation"]).reshape(-1), np.asarray(info["ego2global_translation"], np.float64).reshape(3)])
 
 
-def _result_arrays(res, n_cls):
-    """-> boxes f64 [m, 9], scores f64 [m], labels int64 [m], validated"""
-    if "pts_bbox" in res:
-        res = res["pts_bbox"]
-    b = _to_numpy(res["boxes_3d"]).astype(np.float64)
-    b = b.reshape(b.shape[0], -1) if b.size else np.zeros((0, 9))
-    if b.shape[1] < 9:
-        raise ValueError("nuscenes_eval: boxes_3d must have 9 columns (x, y, z, l, w, h, yaw, vx, vy)")
-    sc = _to_numpy(res["scores_3d"]).astype(np.float64).reshape(-1)
-    lab = _to_numpy(res["labels_3d"]).astype(np.int64).reshape(-1)
-    if b.shape[0] > MAX_BOXES_PER_SAMPLE:
-        raise ValueError(f"nuscenes_eval: a sample has {b.shape[0]} predictions, more than {MAX_BOXES_PER_SAMPLE}")
-    if not np.all(np.isfinite(sc)):
-        raise ValueError("nuscenes_eval: detection scores must be finite")
-    if lab.size and (lab.min() < 0 or lab.max() >= n_cls):
-        raise ValueError("nuscenes_eval: labels must index class_names")
-    return b[:, :9], sc, lab
+def _pred_buffer(device, result_name="pts_bbox"):
+    """predictions f64 [m, 9] with scores and labels; a sample with more than MAX_BOXES_PER_SAMPLE of them raises when it is added"""
+    return DetBuffer(9, torch.float64, device, short=_SHORT, result_name=result_name, cap=MAX_BOXES_PER_SAMPLE, cap_message=_TOO_MANY)
+
+
+def _host_arrays(buf, n_cls):
+    """a host prediction buffer -> boxes f64 [m, 9], scores f64 [m], labels int64 [m], validated"""
+    b, sc, lab, _ = (t.numpy() for t in buf.cat())
+    raise_invalid(invalid_host(sc, lab, n_cls), ERRORS)
+    return b, sc, lab
 
 
 def _gt_arrays(info, tab):
@@ -231,7 +228,7 @@ def _in_rack(p, rk, R1, R2):
 def devkit_filter(rec, valid, counts, calib, gt_rec, gt_counts, is_pred, tab):
     """float64 restatement of u3d_nusc_filter -> valid bool [n]"""
     valid = valid.copy()
-    off, goff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), np.concatenate([[0], np.cumsum(gt_counts)]).astype(np.int64)
+    off, goff = offsets(counts), offsets(gt_counts)
     for s in range(len(counts)):
         r = rec[off[s]:off[s + 1]]
         v = valid[off[s]:off[s + 1]]
@@ -253,7 +250,7 @@ def devkit_filter(rec, valid, counts, calib, gt_rec, gt_counts, is_pred, tab):
 
 
 def _compact(rec, valid, counts):
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    off = offsets(counts)
     return rec[valid], [int(valid[off[s]:off[s + 1]].sum()) for s in range(len(counts))]
 
 
@@ -378,13 +375,14 @@ def host_metrics(pred, gt, rank, cseg, tp, match, npos, tab):
 
 
 class _Encoded:
-    """host encoding of (results, infos): LiDAR rows, classes, aux, attributes and counts of both sides, calibration"""
+    """(results, infos) as the evaluation takes them: the predictions in a DetBuffer on `device`, and the host encoding of the infos -
+    LiDAR rows, classes, points, attributes and counts of the GT, calibration"""
 
-    def __init__(self, tab):
+    def __init__(self, tab, device="cpu", result_name="pts_bbox"):
         self.tab = tab
-        self.p_rows, self.p_score, self.p_lab, self.p_counts = [], [], [], []
+        self.pred = _pred_buffer(device, result_name)
         self.g_rows, self.g_cls, self.g_pts, self.g_attr, self.g_counts = [], [], [], [], []
-        self.calib, self.tokens, self.has_attr = [], [], []
+        self.g_dev, self.calib, self.tokens, self.has_attr = [], [], [], []
 
     def add_gt(self, info):
         rows, cls, pts, attr, has = _gt_arrays(info, self.tab)
@@ -393,27 +391,32 @@ class _Encoded:
         self.g_pts.append(pts)
         self.g_attr.append(attr)
         self.g_counts.append(rows.shape[0])
+        self.g_dev.append(tuple(torch.as_tensor(x, device=self.pred.device) for x in (rows, cls, pts, attr)))
         self.calib.append(_calib(info))
         self.tokens.append(info.get("token", str(len(self.tokens))))
         self.has_attr.append(has)
 
     def add_pred(self, res):
-        b, sc, lab = _result_arrays(res, self.tab.C)
-        self.p_rows.append(b)
-        self.p_score.append(sc)
-        self.p_lab.append(lab)
-        self.p_counts.append(b.shape[0])
+        self.pred.add(res)
 
     @staticmethod
     def _cat(xs, shape, dtype):
         return np.concatenate(xs).astype(dtype) if xs else np.zeros(shape, dtype)
 
     def arrays(self):
-        return dict(p_rows=self._cat(self.p_rows, (0, 9), np.float64), p_score=self._cat(self.p_score, (0,), np.float64),
-                    p_lab=self._cat(self.p_lab, (0,), np.int32), p_counts=list(self.p_counts),
+        """everything on the host (a host buffer), the predictions validated"""
+        b, sc, lab = _host_arrays(self.pred, self.tab.C)
+        return dict(p_rows=b, p_score=sc, p_lab=lab.astype(np.int32), p_counts=list(self.pred.counts),
                     g_rows=self._cat(self.g_rows, (0, 9), np.float64), g_cls=self._cat(self.g_cls, (0,), np.int32),
                     g_pts=self._cat(self.g_pts, (0,), np.float64), g_attr=self._cat(self.g_attr, (0,), np.int32),
                     g_counts=list(self.g_counts), calib=np.asarray(self.calib, np.float64).reshape(-1, 24))
+
+    def gt_device(self):
+        """the GT as device_global takes it: what add_gt left on the buffer's device, concatenated"""
+        dev = self.pred.device
+        g_rows, g_cls, g_pts, g_attr = (torch.cat([g[k] for g in self.g_dev]).contiguous() for k in range(4))
+        return dict(g_rows=g_rows.reshape(-1, 9), g_cls=g_cls, g_pts=g_pts, g_attr=g_attr, g_off=offsets(self.g_counts, dev),
+                    calib=torch.as_tensor(np.asarray(self.calib, np.float64).reshape(-1, 24), device=dev))
 
 
 def host_global(a, tab):
@@ -445,10 +448,6 @@ def _dev_tables(tab, dev):
                 ths=f64(DIST_THS), ri=f64(_REC_INTERP))
 
 
-def _off(counts, dev):
-    return torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), device=dev)
-
-
 def device_global(p_rows, p_score, p_lab, p_off, g_rows, g_cls, g_pts, g_attr, g_off, calib, dt):
     """device tensors (rows f64, labels / classes / attributes int32, offsets int32 [S+1], calib f64 [S, 24]) -> (pred records,
     offsets, GT records, offsets) after conversion, filters and compaction"""
@@ -470,8 +469,8 @@ def device_core(pred, pred_off, gt, gt_off, tab, dt):
 def _upload_encoded(a, dev):
     f64 = lambda x: torch.as_tensor(x, dtype=torch.float64, device=dev).contiguous()   # noqa: E731
     i32 = lambda x: torch.as_tensor(x, dtype=torch.int32, device=dev).contiguous()     # noqa: E731
-    return dict(p_rows=f64(a["p_rows"]), p_score=f64(a["p_score"]), p_lab=i32(a["p_lab"]), p_off=_off(a["p_counts"], dev),
-                g_rows=f64(a["g_rows"]), g_cls=i32(a["g_cls"]), g_pts=f64(a["g_pts"]), g_attr=i32(a["g_attr"]), g_off=_off(a["g_counts"], dev),
+    return dict(p_rows=f64(a["p_rows"]), p_score=f64(a["p_score"]), p_lab=i32(a["p_lab"]), p_off=offsets(a["p_counts"], dev),
+                g_rows=f64(a["g_rows"]), g_cls=i32(a["g_cls"]), g_pts=f64(a["g_pts"]), g_attr=i32(a["g_attr"]), g_off=offsets(a["g_counts"], dev),
                 calib=f64(a["calib"]))
 
 
@@ -532,14 +531,8 @@ def _results(ap, tp_err, class_names, result_name="pts_bbox", attr_known=True, l
         for c in class_names:
             e = label_tp[c]
             lines.append(f"{c:<22}{np.mean(list(label_aps[c].values())):8.3f}" + "".join(f"{e[m]:8.3f}" for m in TP_METRICS))
-        _print_log("\n" + "\n".join(lines), logger)
+        print_log("\n" + "\n".join(lines), logger)
     return ret
-
-
-def _default_device(device):
-    if device is None:
-        return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-    return torch.device(device)
 
 
 def _attr_warning(attr_known, logger):
@@ -564,10 +557,6 @@ def evaluate_encoded(a, tab, device="cpu"):
     return device_core(pred, pred_off, gt, gt_off, tab, dt)
 
 
-def _unwrap(results, result_name):
-    return [r[result_name] if result_name in r else r for r in results]
-
-
 def nuscenes_eval(results, infos, class_names=CLASSES, eval_version="detection_cvpr_2019", result_name="pts_bbox", logger=None, device=None):
     """The devkit's detection evaluation of `simple_test` results -> upstream `_evaluate_single`'s ret_dict.
     device: None = the GPU when there is one, "cpu" = the float64 host path."""
@@ -575,13 +564,13 @@ def nuscenes_eval(results, infos, class_names=CLASSES, eval_version="detection_c
     if len(results) != len(infos):
         raise ValueError("nuscenes_eval: one result per info")
     tab = _Tables(class_names)
-    enc = _Encoded(tab)
-    for res, info in zip(_unwrap(results, result_name), infos):
+    enc = _Encoded(tab, result_name=result_name)
+    for res, info in zip(results, infos):
         enc.add_gt(info)
         enc.add_pred(res)
     attr_known = any(enc.has_attr)
     _attr_warning(attr_known, logger)
-    r = evaluate_encoded(enc.arrays(), tab, _default_device(device))
+    r = evaluate_encoded(enc.arrays(), tab, default_device(device))
     return _results(r["ap"], r["tp_err"], tab.names, result_name, attr_known, logger)
 
 
@@ -602,8 +591,10 @@ def lidar_results_to_nusc(results, infos, class_names=CLASSES, modality=None):
         raise ValueError("nuscenes_eval: one result per info")
     tab = _Tables(class_names)
     out = {}
-    for res, info in zip(_unwrap(results, "pts_bbox"), infos):
-        b, sc, lab = _result_arrays(res, tab.C)
+    for res, info in zip(results, infos):
+        buf = _pred_buffer("cpu")
+        buf.add(res)
+        b, sc, lab = _host_arrays(buf, tab.C)
         cal = _calib(info)[None]
         rec, valid = to_global(b, lab.astype(np.int32), sc, None, [b.shape[0]], cal, True, tab)
         q = _qmul(np.asarray(info["ego2global_rotation"], np.float64) / np.linalg.norm(info["ego2global_rotation"]),
@@ -647,9 +638,7 @@ class NuScenesEvaluator:
         self.reset()
 
     def reset(self):
-        self._enc = _Encoded(self.tab)
-        self._boxes, self._scores, self._labels = [], [], []
-        self._gt = []
+        self._enc = _Encoded(self.tab, self.device, self.result_name)
 
     def __len__(self):
         return len(self._enc.g_counts)
@@ -657,33 +646,17 @@ class NuScenesEvaluator:
     def add(self, results, infos):
         if len(results) != len(infos):
             raise ValueError("nuscenes_eval: one result per info")
-        for res, info in zip(_unwrap(results, self.result_name), infos):
-            if self.device.type == "cpu":
-                self._enc.add_pred(res)
-            else:
-                b = res["boxes_3d"]
-                b = torch.as_tensor(b.tensor if hasattr(b, "tensor") else b).to(self.device, torch.float64)
-                b = b.reshape(b.shape[0], -1) if b.numel() else torch.zeros((0, 9), dtype=torch.float64, device=self.device)
-                if b.shape[0] > MAX_BOXES_PER_SAMPLE:
-                    raise ValueError(f"nuscenes_eval: a sample has {b.shape[0]} predictions, more than {MAX_BOXES_PER_SAMPLE}")
-                if b.shape[1] < 9:
-                    raise ValueError("nuscenes_eval: boxes_3d must have 9 columns (x, y, z, l, w, h, yaw, vx, vy)")
-                self._boxes.append(b[:, :9])
-                self._scores.append(torch.as_tensor(res["scores_3d"]).to(self.device, torch.float64).reshape(-1))
-                self._labels.append(torch.as_tensor(res["labels_3d"]).to(self.device, torch.int32).reshape(-1))
-                self._enc.p_counts.append(int(b.shape[0]))
+        for res, info in zip(results, infos):
+            self._enc.add_pred(res)
             self._enc.add_gt(info)
-            if self.device.type != "cpu":
-                e = self._enc
-                self._gt.append(tuple(torch.as_tensor(x, device=self.device) for x in
-                                      (e.g_rows[-1], e.g_cls[-1].astype(np.int32), e.g_pts[-1], e.g_attr[-1].astype(np.int32))))
 
     def add_store(self, store, infos):
-        """add() for every sample of a det_store.DetStore (box_dim 9) at once, in the store's scene order.  The predictions are encoded
-        on the host, so they come through store.results(): one copy per tensor for the whole dataset instead of one per batch.
-        Bit-identical to add() over the same samples in the same order."""
-        self.add(store.results(self.tab.C, ("nuscenes_eval: detection scores must be finite", "nuscenes_eval: labels must index class_names")),
-                 infos)
+        """add() for every sample of a det_store.DetStore (box_dim 9) at once, in the store's scene order: the predictions are
+        store.packed() (they never leave the device, float32 -> float64 there is exact), the per-sample counts come from one read of
+        its det_off.  Bit-identical to add() over the same samples in the same order."""
+        self._enc.pred.add_store(store, len(infos), "nuscenes_eval: one result per info", self.tab.C, ERRORS)
+        for info in infos:
+            self._enc.add_gt(info)
 
     def compute(self, logger="silent"):
         """-> ret_dict of `nuscenes_eval` over everything added (the summary goes to `logger`)."""
@@ -694,17 +667,11 @@ class NuScenesEvaluator:
         if self.device.type == "cpu":
             r = evaluate_encoded(self._enc.arrays(), self.tab, "cpu")
             return _results(r["ap"], r["tp_err"], self.class_names, self.result_name, attr_known, logger)
-        dev = self.device
-        boxes, scores, labels = torch.cat(self._boxes), torch.cat(self._scores), torch.cat(self._labels)
-        bad = torch.stack([(~torch.isfinite(scores)).any(), ((labels < 0) | (labels >= self.tab.C)).any()]).cpu()
-        if bool(bad[0]):
-            raise ValueError("nuscenes_eval: detection scores must be finite")
-        if bool(bad[1]):
-            raise ValueError("nuscenes_eval: labels must index class_names")
-        g_rows, g_cls, g_pts, g_attr = (torch.cat([g[k] for g in self._gt]).contiguous() for k in range(4))
-        calib = torch.as_tensor(np.asarray(self._enc.calib, np.float64).reshape(-1, 24), device=dev)
-        dt = _dev_tables(self.tab, dev)
-        pred, pred_off, gt, gt_off = device_global(boxes.contiguous(), scores.contiguous(), labels.contiguous(), _off(self._enc.p_counts, dev),
-                                                   g_rows.reshape(-1, 9), g_cls, g_pts, g_attr, _off(self._enc.g_counts, dev), calib, dt)
+        boxes, scores, labels, p_off = self._enc.pred.cat()
+        raise_invalid(invalid_device(scores, labels, self.tab.C), ERRORS)
+        u = self._enc.gt_device()
+        dt = _dev_tables(self.tab, self.device)
+        pred, pred_off, gt, gt_off = device_global(boxes, scores, labels, p_off, u["g_rows"], u["g_cls"], u["g_pts"], u["g_attr"], u["g_off"],
+                                                   u["calib"], dt)
         r = device_core(pred, pred_off, gt, gt_off, self.tab, dt)
         return _results(r["ap"], r["tp_err"], self.class_names, self.result_name, attr_known, logger)
