@@ -1283,6 +1283,25 @@ int32_t u3d_tta_merge(const float* boxes, const float* scores, const int32_t* la
                       const float* params, int32_t batch, int32_t views, int32_t coord, int32_t num_classes, float nms_thr, int32_t max_num,
                       int32_t max_per_scene, void* workspace, int64_t workspace_bytes, float* out_boxes, float* out_scores,
                       int32_t* out_labels, int32_t* out_count, u3d_stream s);
+/* u3d_tta_merge behind the batched detection tail, whose counts exist only on the device: the same merge over the PADDED layout that
+ * u3d_det_tail_pp writes for batch*views scenes (views scene-major, view-minor).  boxes f32 [batch*views][max_det][box_dim], scores f32
+ * / labels int32 [batch*views][max_det], count int32 [batch*views] on the DEVICE, clamped to [0, max_det]; rows of a view at or past
+ * its count are never read and may hold anything; params, coord, num_classes, nms_thr, max_num as u3d_tta_merge takes them.  Scene by
+ * scene the result is bit-identical to u3d_tta_merge on rows [v][0 .. count[v]) of every view concatenated in view order: the same
+ * kernels, with the candidate's memory row computed from the device scan of the counts.  The outputs form a complete DetBatch:
+ * out_boxes [batch][max_num][box_dim], out_scores / out_labels [batch][max_num] with the rows at or past out_count[b] WRITTEN AS ZERO,
+ * out_count int32 [batch], out_off int32 [batch+1] = exclusive scan of out_count.  No host-known row count: every grid, the workspace
+ * and the choice of the global-memory NMS path (views*max_det > U3D_TTA_LDS_CAP) depend on batch, views, max_det, num_classes only;
+ * no allocation, no synchronisation, no blocking copy - the call may be captured into a graph.  No atomics: equal inputs give equal
+ * bytes.  Checked before any launch: U3D_ERR_ARG for a null pointer or a bad shape (batch, views, max_det, num_classes, max_num <= 0,
+ * box_dim not 7 / 9, coord not 0 / 1); U3D_ERR_UNSUPPORTED for batch > 65535, max_det or max_num > U3D_DET_TAIL_MAX_K, batch*views*max_det
+ * >= 2^31, or views*max_det > 524288 (the suppression words of one mask row must fit the sweep's 64 KiB of LDS); U3D_ERR_WORKSPACE
+ * for a workspace below u3d_tta_merge_padded_workspace (which returns -1 for a shape the call refuses). */
+int64_t u3d_tta_merge_padded_workspace(int32_t batch, int32_t views, int32_t max_det, int32_t box_dim, int32_t num_classes);
+int32_t u3d_tta_merge_padded(const float* boxes, const float* scores, const int32_t* labels, const int32_t* count, int32_t batch,
+                             int32_t views, int32_t max_det, int32_t box_dim, const float* params, int32_t coord, int32_t num_classes,
+                             float nms_thr, int32_t max_num, void* workspace, int64_t workspace_bytes, float* out_boxes, float* out_scores,
+                             int32_t* out_labels, int32_t* out_count, int32_t* out_off, u3d_stream s);
 
 /* LoadPointsFromMultiSweeps (mmdet3d, recalled): uni3detr_amd/csrc/sweeps.hip.  Output, scene after scene:
  * the key frame (time column 4 set to 0), then every chosen sweep's rows that survive remove_close (|x| < 1 and |y| < 1 dropped, on

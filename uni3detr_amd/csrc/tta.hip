@@ -15,6 +15,12 @@
 // Layout: boxes [n, box_dim] f32 bottom-centre, box_dim 7 or 9, scores [n] f32, labels [n] int32; det_off int32 [batch*views + 1]:
 // view v = rows det_off[v] .. det_off[v+1]), scene s = views s*views .. s*views + views - 1 (scene-major, view-minor); params f32
 // [batch*views][U3D_AUG_NPARAM], the FORWARD parameters of every view (rotation / scale, then flip: the inner test pipeline's order).
+// u3d_tta_merge_padded runs the same kernels on the padded layout of the batched detection tail (boxes [batch*views][K][box_dim], a
+// device count per view): candidate i of the concatenated order lives at memory row v*K + (i - det_off[v]), det_off being the scan of
+// the clamped counts that k_tta_scan leaves in the workspace.  Only k_tta_prep touches the caller's rows - it is the one kernel
+// templated on the layout, and for the padded one it also leaves the candidate's score and label at index i - so everything behind
+// it is literally the ragged entry's code on the ragged entry's indices.  Every grid is sized by batch*views*K; threads past
+// det_off[batch*views] leave at once.  k_tta_zero_tail / k_tta_scan finish the DetBatch (zero rows past the count, out_off).
 #include "common.h"
 #include "box_aug.h"
 #include "box_iou.h"
@@ -37,13 +43,22 @@ __global__ void k_tta_inverse(const float* __restrict__ params, int nviews, floa
   q[0] = p[0]; q[1] = p[1]; q[2] = -p[2]; q[3] = p[3]; q[4] = -p[4]; q[5] = 1.f / p[5]; q[6] = 0.f; q[7] = 0.f; q[8] = 0.f;
 }
 
-__global__ void k_tta_prep(const float* __restrict__ boxes, const int* __restrict__ det_off, const float* __restrict__ inv, int nviews,
-                           int n, int dim, int coord, float* __restrict__ mapped, float* __restrict__ bev) {
+template <bool PADDED>
+__global__ void k_tta_prep(const float* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ labels,
+                           const int* __restrict__ det_off, const float* __restrict__ inv, int nviews, int n, int dim, int coord, int K,
+                           float* __restrict__ mapped, float* __restrict__ bev, float* __restrict__ cscores, int* __restrict__ clabels) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || i >= det_off[nviews]) return;
   const int v = u3d_segment_of(det_off, nviews, i);
+  // the candidate's memory row: the concatenated index itself, or its place in view v's block of K rows (rows at or past the view's
+  // count are never addressed: i - det_off[v] < det_off[v + 1] - det_off[v])
+  const long long row = PADDED ? (long long)v * K + (i - det_off[v]) : (long long)i;
+  if (PADDED) {
+    cscores[i] = scores[row];
+    clabels[i] = labels[row];
+  }
   float* o = mapped + (long long)i * dim;
-  for (int k = 0; k < dim; ++k) o[k] = boxes[(long long)i * dim + k];
+  for (int k = 0; k < dim; ++k) o[k] = boxes[row * dim + k];
   dp_box_augment(o, o, dim, inv + (long long)v * TTA_NP, coord);      // in place, as k_boxes_augment
   // mmdet3d xywhr2xyxyr on .bev = (x, y, dx, dy, yaw), then nms_bev's way back to (cx, cy, w, h, yaw), in f32
   const float hw = o[3] / 2.f, hh = o[4] / 2.f;
@@ -187,6 +202,52 @@ __global__ void k_tta_select(const float* __restrict__ mapped, const float* __re
   if (rank == 0) out_count[s] = min(total, max_num);
 }
 
+// out[0 .. n] = exclusive scan of in[i] clamped to [0, hi]: ONE workgroup, every thread a contiguous chunk
+__global__ __launch_bounds__(256) void k_tta_scan(const int* __restrict__ in, int n, int hi, int* __restrict__ out) {
+  __shared__ int part[256];
+  const int t = threadIdx.x, per = (n + 255) / 256;
+  const int lo = min(t * per, n), end = min(lo + per, n);
+  int sum = 0;
+  for (int i = lo; i < end; ++i) sum += min(max(in[i], 0), hi);
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int run = part[t] - sum;
+  for (int i = lo; i < end; ++i) {
+    out[i] = run;
+    run += min(max(in[i], 0), hi);
+  }
+  if (t == 255) out[n] = part[255];
+}
+
+// seg, nvalid and out_count <- 0 for the entry that may be captured.  A kernel, not hipMemsetAsync: the memset NODE of a captured graph
+// does not leave zeros on replay on this stack (geometry.hip, query.hip fps_launch), and a (scene, class) without candidates keeps
+// what the clear left in seg.
+__global__ void k_tta_clear(int* __restrict__ seg, int nseg, int* __restrict__ nvalid, int* __restrict__ out_count, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nseg) seg[i] = 0;
+  if (i < batch) {
+    nvalid[i] = 0;
+    out_count[i] = 0;
+  }
+}
+
+// DetBatch's contract: rows at or past out_count[b] are zero (a replay's static outputs still hold the previous replay's rows)
+__global__ void k_tta_zero_tail(const int* __restrict__ out_count, int batch, int max_num, int dim, float* __restrict__ out_boxes,
+                                float* __restrict__ out_scores, int* __restrict__ out_labels) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long long)batch * max_num) return;
+  if ((int)(g % max_num) < out_count[g / max_num]) return;
+  for (int k = 0; k < dim; ++k) out_boxes[g * dim + k] = 0.f;
+  out_scores[g] = 0.f;
+  out_labels[g] = 0;
+}
+
 static inline size_t tta_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" int64_t u3d_tta_merge_workspace(int32_t n, int32_t box_dim, int32_t batch, int32_t views, int32_t num_classes,
@@ -201,6 +262,61 @@ extern "C" int64_t u3d_tta_merge_workspace(int32_t n, int32_t box_dim, int32_t b
   return (int64_t)b;
 }
 
+// the suppression words of one mask row must fit the sweep's LDS and the mask grid's y dimension
+static inline bool tta_global_ok(int max_per_scene) {
+  const int nw = (max_per_scene + 63) / 64;
+  return max_per_scene <= TTA_LDS_CAP || ((size_t)nw * 8 <= 64 * 1024 && nw <= 65535);
+}
+
+// The merge behind both entries.  n bounds the candidates (the grids); the real total is det_off[batch * views], read on the device.
+// PADDED: boxes / scores / labels are [batch*views][K] blocks and cscores / clabels receive the candidates' scores and labels in
+// concatenated order; otherwise the caller's arrays already are in that order and K, cscores, clabels are unused.
+template <bool PADDED>
+static int32_t tta_run(const float* boxes, const float* scores, const int32_t* labels, int32_t n, int32_t box_dim, const int32_t* det_off,
+                       const float* params, int32_t batch, int32_t views, int32_t coord, int32_t num_classes, float nms_thr,
+                       int32_t max_num, int32_t max_per_scene, int32_t K, float* cscores, int32_t* clabels, void* workspace,
+                       float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_count, u3d_stream s) {
+  const bool global_path = max_per_scene > TTA_LDS_CAP;
+  const int nw = (max_per_scene + 63) / 64;
+  char* w = (char*)workspace;
+  float* inv = (float*)w; w += tta_align((size_t)batch * views * TTA_NP * 4);
+  float* mapped = (float*)w; w += tta_align((size_t)n * box_dim * 4);
+  float* bev = (float*)w; w += tta_align((size_t)n * 5 * 4);
+  int* ord = (int*)w; w += tta_align((size_t)n * 4);
+  unsigned char* keep = (unsigned char*)w; w += tta_align((size_t)n);
+  int* seg = (int*)w; w += tta_align((size_t)batch * num_classes * 2 * 4);
+  int* nvalid = (int*)w; w += tta_align((size_t)batch * 4);
+  unsigned long long* mask = global_path ? (unsigned long long*)w : nullptr;
+  const float* sc = PADDED ? cscores : scores;              // what every kernel behind k_tta_prep reads, by concatenated index
+  const int32_t* lb = PADDED ? clabels : labels;
+  if (PADDED) {
+    const int nseg = batch * num_classes * 2;
+    hipLaunchKernelGGL(k_tta_clear, dim3(u3d_cdiv(nseg, 256)), dim3(256), 0, s, seg, nseg, nvalid, out_count, batch);
+  } else {                                                  // (the ragged entry: its out_count is cleared by the caller)
+    U3D_REQUIRE(hipMemsetAsync(seg, 0, (size_t)batch * num_classes * 2 * 4, s) == hipSuccess, U3D_ERR_LAUNCH);
+    U3D_REQUIRE(hipMemsetAsync(nvalid, 0, (size_t)batch * 4, s) == hipSuccess, U3D_ERR_LAUNCH);
+  }
+  const int nviews = batch * views;
+  hipLaunchKernelGGL(k_tta_inverse, dim3(u3d_cdiv(nviews, 64)), dim3(64), 0, s, params, nviews, inv);
+  hipLaunchKernelGGL(k_tta_prep<PADDED>, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, boxes, scores, labels, det_off, inv, nviews, n, box_dim,
+                     coord, K, mapped, bev, cscores, clabels);
+  hipLaunchKernelGGL(k_tta_rank, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, sc, lb, det_off, batch, views, n, num_classes, ord, seg, nvalid);
+  hipLaunchKernelGGL(k_tta_nms_lds, dim3(num_classes, batch), dim3(TTA_LDS_THREADS), 0, s, bev, det_off, views, ord, seg, num_classes,
+                     nms_thr, keep);
+  if (global_path) {
+    // (the padded entry: a grid of views * K rows whatever the counts are; blocks past nvalid[s] or of a small segment leave at once.
+    //  Measured at 4 x 900 rows, 500 live: 0.10 ms per call for the grid that does nothing - profiles/tta_step_ab.txt)
+    hipLaunchKernelGGL(k_tta_mask, dim3(max_per_scene, nw, batch), dim3(64), 0, s, bev, lb, det_off, views, ord, seg, nvalid,
+                       num_classes, nms_thr, max_per_scene, nw, mask);
+    hipLaunchKernelGGL(k_tta_sweep, dim3(num_classes, batch), dim3(64), (size_t)nw * 8, s, mask, det_off, views, seg, num_classes,
+                       max_per_scene, nw, keep);
+  }
+  hipLaunchKernelGGL(k_tta_select, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, mapped, sc, lb, det_off, batch, views, n, box_dim, ord,
+                     nvalid, keep, max_num, out_boxes, out_scores, out_labels, out_count);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
 extern "C" int32_t u3d_tta_merge(const float* boxes, const float* scores, const int32_t* labels, int32_t n, int32_t box_dim,
                                  const int32_t* det_off, const float* params, int32_t batch, int32_t views, int32_t coord,
                                  int32_t num_classes, float nms_thr, int32_t max_num, int32_t max_per_scene, void* workspace,
@@ -212,35 +328,51 @@ extern "C" int32_t u3d_tta_merge(const float* boxes, const float* scores, const 
   if (n == 0) return U3D_OK;
   U3D_REQUIRE(boxes && scores && labels && workspace && out_boxes && out_scores && out_labels, U3D_ERR_ARG);
   U3D_REQUIRE(workspace_bytes >= u3d_tta_merge_workspace(n, box_dim, batch, views, num_classes, max_per_scene), U3D_ERR_WORKSPACE);
-  const bool global_path = max_per_scene > TTA_LDS_CAP;
-  const int nw = (max_per_scene + 63) / 64;
-  U3D_REQUIRE(!global_path || ((size_t)nw * 8 <= 64 * 1024 && nw <= 65535), U3D_ERR_UNSUPPORTED);
+  U3D_REQUIRE(tta_global_ok(max_per_scene), U3D_ERR_UNSUPPORTED);
+  return tta_run<false>(boxes, scores, labels, n, box_dim, det_off, params, batch, views, coord, num_classes, nms_thr, max_num,
+                        max_per_scene, 0, nullptr, nullptr, workspace, out_boxes, out_scores, out_labels, out_count, s);
+}
+
+// ---- the padded layout of the batched detection tail ------------------------------------------------------------------------------
+static inline bool tta_padded_shape_ok(int batch, int views, int K, int box_dim, int num_classes) {
+  return batch > 0 && views > 0 && K > 0 && (box_dim == 7 || box_dim == 9) && num_classes > 0;
+}
+
+// batch*views*K candidates at most, a scene views*K: what the grids, the workspace and the choice of the NMS path depend on
+static inline bool tta_padded_supported(int batch, int views, int K, int num_classes) {
+  return batch <= 65535 && K <= U3D_DET_TAIL_MAX_K && (long long)views * K < (1ll << 31) && (long long)batch * views * K < (1ll << 31) &&
+         (long long)batch * num_classes * 2 < (1ll << 31) && tta_global_ok(views * K);
+}
+
+extern "C" int64_t u3d_tta_merge_padded_workspace(int32_t batch, int32_t views, int32_t max_det, int32_t box_dim, int32_t num_classes) {
+  if (!tta_padded_shape_ok(batch, views, max_det, box_dim, num_classes) || !tta_padded_supported(batch, views, max_det, num_classes)) return -1;
+  const int n = batch * views * max_det;
+  return (int64_t)(tta_align(((size_t)batch * views + 1) * 4) + 2 * tta_align((size_t)n * 4)) +
+         u3d_tta_merge_workspace(n, box_dim, batch, views, num_classes, views * max_det);
+}
+
+extern "C" int32_t u3d_tta_merge_padded(const float* boxes, const float* scores, const int32_t* labels, const int32_t* count, int32_t batch,
+                                        int32_t views, int32_t max_det, int32_t box_dim, const float* params, int32_t coord,
+                                        int32_t num_classes, float nms_thr, int32_t max_num, void* workspace, int64_t workspace_bytes,
+                                        float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_count, int32_t* out_off,
+                                        u3d_stream s) {
+  U3D_REQUIRE(boxes && scores && labels && count && params && workspace && out_boxes && out_scores && out_labels && out_count && out_off,
+              U3D_ERR_ARG);
+  U3D_REQUIRE(tta_padded_shape_ok(batch, views, max_det, box_dim, num_classes) && (coord == 0 || coord == 1) && max_num > 0, U3D_ERR_ARG);
+  U3D_REQUIRE(tta_padded_supported(batch, views, max_det, num_classes) && max_num <= U3D_DET_TAIL_MAX_K, U3D_ERR_UNSUPPORTED);
+  U3D_REQUIRE(workspace_bytes >= u3d_tta_merge_padded_workspace(batch, views, max_det, box_dim, num_classes), U3D_ERR_WORKSPACE);
+  const int nviews = batch * views, n = nviews * max_det;
   char* w = (char*)workspace;
-  float* inv = (float*)w; w += tta_align((size_t)batch * views * TTA_NP * 4);
-  float* mapped = (float*)w; w += tta_align((size_t)n * box_dim * 4);
-  float* bev = (float*)w; w += tta_align((size_t)n * 5 * 4);
-  int* ord = (int*)w; w += tta_align((size_t)n * 4);
-  unsigned char* keep = (unsigned char*)w; w += tta_align((size_t)n);
-  int* seg = (int*)w; w += tta_align((size_t)batch * num_classes * 2 * 4);
-  int* nvalid = (int*)w; w += tta_align((size_t)batch * 4);
-  unsigned long long* mask = global_path ? (unsigned long long*)w : nullptr;
-  U3D_REQUIRE(hipMemsetAsync(seg, 0, (size_t)batch * num_classes * 2 * 4, s) == hipSuccess, U3D_ERR_LAUNCH);
-  U3D_REQUIRE(hipMemsetAsync(nvalid, 0, (size_t)batch * 4, s) == hipSuccess, U3D_ERR_LAUNCH);
-  const int nviews = batch * views;
-  hipLaunchKernelGGL(k_tta_inverse, dim3(u3d_cdiv(nviews, 64)), dim3(64), 0, s, params, nviews, inv);
-  hipLaunchKernelGGL(k_tta_prep, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, boxes, det_off, inv, nviews, n, box_dim, coord, mapped, bev);
-  hipLaunchKernelGGL(k_tta_rank, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, scores, labels, det_off, batch, views, n, num_classes, ord, seg,
-                     nvalid);
-  hipLaunchKernelGGL(k_tta_nms_lds, dim3(num_classes, batch), dim3(TTA_LDS_THREADS), 0, s, bev, det_off, views, ord, seg, num_classes,
-                     nms_thr, keep);
-  if (global_path) {
-    hipLaunchKernelGGL(k_tta_mask, dim3(max_per_scene, nw, batch), dim3(64), 0, s, bev, labels, det_off, views, ord, seg, nvalid,
-                       num_classes, nms_thr, max_per_scene, nw, mask);
-    hipLaunchKernelGGL(k_tta_sweep, dim3(num_classes, batch), dim3(64), (size_t)nw * 8, s, mask, det_off, views, seg, num_classes,
-                       max_per_scene, nw, keep);
-  }
-  hipLaunchKernelGGL(k_tta_select, dim3(u3d_cdiv(n, 256)), dim3(256), 0, s, mapped, scores, labels, det_off, batch, views, n, box_dim, ord,
-                     nvalid, keep, max_num, out_boxes, out_scores, out_labels, out_count);
+  int* det_off = (int*)w; w += tta_align(((size_t)nviews + 1) * 4);
+  float* cscores = (float*)w; w += tta_align((size_t)n * 4);
+  int* clabels = (int*)w; w += tta_align((size_t)n * 4);
+  hipLaunchKernelGGL(k_tta_scan, dim3(1), dim3(256), 0, s, count, nviews, max_det, det_off);      // (out_count: cleared in tta_run)
+  const int32_t rc = tta_run<true>(boxes, scores, labels, n, box_dim, det_off, params, batch, views, coord, num_classes, nms_thr, max_num,
+                                   views * max_det, max_det, cscores, clabels, w, out_boxes, out_scores, out_labels, out_count, s);
+  if (rc != U3D_OK) return rc;
+  hipLaunchKernelGGL(k_tta_zero_tail, dim3(u3d_cdiv((long long)batch * max_num, 256)), dim3(256), 0, s, out_count, batch, max_num, box_dim,
+                     out_boxes, out_scores, out_labels);
+  hipLaunchKernelGGL(k_tta_scan, dim3(1), dim3(256), 0, s, out_count, batch, max_num, out_off);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

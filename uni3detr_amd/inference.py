@@ -44,7 +44,8 @@ forward (fp8_state() / load_fp8_state() carry it).  `fp8_layers` names the pairs
 measured faster than bf16 -, `fp8_skipped` the rest with the reason.  A forward before calibration raises.  INTEGRATION.md N.
 
 InferenceStep(inf, batch_size=B, point_capacity=P) replays the folded forward and the batched tail of an InferenceModel as one hipGraph
-over static, capacity-sized buffers, with a device-side validity gate (u3d_det_gate) and an eager fallback.  INTEGRATION.md O.
+over static, capacity-sized buffers, with a device-side validity gate (u3d_det_gate) and an eager fallback.  INTEGRATION.md O.  With
+views=A it captures test-time augmentation as well: B * A views forward, the multi-view merge on the padded tail.  INTEGRATION.md S.
 
 Numerics: not bit-identical to conv + u3d_bn_apply.  Folded: bf16(w * scale) once, output rounded once.  Unfolded: bf16(w), conv
 output rounded to bf16, y rounded.  Both are a few bf16 roundings of the same real number (tests/test_bn_fold_gpu.py holds the folded
@@ -59,6 +60,7 @@ from torch import nn
 from . import native as nv
 from . import sparse as sp
 from . import static_batch as sb
+from .tta import coord_of as _coord_of
 
 _WHY_NARROW = "narrow level ({cin} -> {cout} channels): direct-operand kernels read `bias` as an addend"
 _WHY_INPUT = "conv_input: {cin} -> {cout} channels on its own kernel"
@@ -401,6 +403,12 @@ class InferenceModel:
         with self.scope():
             return self.model.aug_test(points, img_metas, **kwargs)
 
+    @torch.no_grad()
+    def aug_test_batched(self, batch_or_points, img_metas=None, **kwargs):
+        """Uni3DETR.aug_test_batched on the folded route: one forward over all views, the batched tail and the padded merge on the device."""
+        with self.scope():
+            return self.model.aug_test_batched(batch_or_points, img_metas, **kwargs)
+
 
 class InferenceStep:
     """The folded forward and the batched tail of an InferenceModel as ONE hipGraph over static buffers: a batch costs one replay
@@ -423,9 +431,23 @@ class InferenceStep:
     mistake.  Nothing is truncated silently and nothing is re-captured automatically: results() re-runs an invalid batch eagerly and
     counts it in `fallbacks`; capture() may be called again with that batch among the samples.
 
-    Limits: an InferenceModel on one device, hard voxelization, B fixed, no aug_test.  An empty live scene gives NaN queries."""
+    Test-time augmentation: InferenceStep(inf, batch_size=B, point_capacity=P, views=A, tta_nms_thr=0.1,
+    tta_max_num=500) captures the forward over B * A scenes (scene-major, view-minor), the batched tail into `view_det` [B * A, K, D] and
+    the multi-view merge over that padded layout (native.tta_merge_padded) into `det` [B, tta_max_num, D]; the gate, `n_live`,
+    `fallbacks` and results() count SAMPLES.  `points` is then the expanded dict a DevicePipeline with MultiScaleFlipAug3D returns (B * A
+    scenes, tta_views == A; its tta_params go into the step's static view table with a device-to-device copy) or a list of n * A
+    tensors, 1 <= n <= B, with tta_params= f32 [n * A, 9] (missing samples: copies of sample 0's views and table rows, gated away).
+    The coordinate code of the merge (Depth / LiDAR) comes from box_type_3d= or from the first dict bound before capture and is fixed
+    from then on: a later dict that disagrees is refused.  An invalid replay is re-run through inf.aug_test_batched.  views=1 is the
+    step described above, with no view buffers and no further launches.
 
-    def __init__(self, inf, batch_size, point_capacity):
+    Limits: an InferenceModel on one device, hard voxelization, B and `views` fixed per step, all views of a sample in one batch.  An
+    empty live scene gives NaN queries."""
+
+    def __init__(self, inf, batch_size, point_capacity, views=1, tta_nms_thr=0.1, tta_max_num=500, box_type_3d=None):
+        A = int(views)
+        if A < 1:
+            raise ValueError(f"InferenceStep(views={views}): at least one view per sample")
         if not isinstance(inf, InferenceModel):
             raise TypeError(f"InferenceStep captures an InferenceModel, not {type(inf).__name__}: wrap the model first")
         model = inf.model
@@ -439,9 +461,15 @@ class InferenceStep:
             raise ValueError(f"InferenceStep(point_capacity={point_capacity}): at least one point per scene")
         self.inf, self.model = inf, model
         self.batch_size, self.point_capacity = B, P
+        self.views, self.tta_nms_thr, self.tta_max_num = A, float(tta_nms_thr), int(tta_max_num)
+        if A > 1 and not 1 <= self.tta_max_num <= nv.DET_TAIL_MAX_K:
+            raise ValueError(f"InferenceStep(tta_max_num={tta_max_num}): 1 .. {nv.DET_TAIL_MAX_K}")
+        self.box_type_3d = box_type_3d
+        self.coord = None if box_type_3d is None else _coord_of(box_type_3d)        # views > 1: the merge's coordinate code
         self.feat = int(model.pts_voxel_encoder.num_features)
         self.fallbacks = 0
         self.pts = self.valid = self.det = self.head_outs = None
+        self.view_det = self.tta_params = None                    # views > 1 only: the per-view tail of a replay, the static view table
         self._graph = self._caps = None
 
     @property
@@ -457,27 +485,60 @@ class InferenceStep:
         if dev.type != "cuda":
             raise RuntimeError("InferenceStep: the model is not on a GPU")
         self.dev = dev
-        self._buf = sb.StaticBatch(self.batch_size, self.point_capacity, self.feat, dev)
+        self._buf = sb.StaticBatch(self.batch_size * self.views, self.point_capacity, self.feat, dev)
         self.pts = self._buf.pts
         self._n_live = torch.full((1,), self.batch_size, dtype=torch.int32, device=dev)
         self._flag = torch.zeros(1, dtype=torch.float32, device=dev)
         self._fps_err = nv.fps_err_buffer(dev)
         self.valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.views > 1:
+            self.tta_params = torch.zeros((self.batch_size * self.views, nv.AUG_NPARAM), dtype=torch.float32, device=dev)
 
-    def _bind(self, points):
-        """Load a batch into the static buffers on the current stream -> the number of live scenes."""
+    def _view_table(self, tab, rows):
+        """The host's checks of a view table of `rows` views: nothing is read."""
+        if not torch.is_tensor(tab) or tab.dtype != torch.float32 or tuple(tab.shape) != (rows, nv.AUG_NPARAM):
+            raise ValueError(f"InferenceStep: tta_params must be a float32 tensor [{rows}, {nv.AUG_NPARAM}] (one row per view)")
+        if tab.device != self.dev:
+            raise ValueError(f"InferenceStep: tta_params must live on {self.dev}")
+        return tab
+
+    def _bind(self, points, tta_params=None):
+        """Load a batch into the static buffers on the current stream -> the number of live samples."""
         if self.pts is None:
             self._alloc()
-        B = self.batch_size
+        B, A = self.batch_size, self.views
         if isinstance(points, dict):
+            if A > 1:
+                if int(points.get("tta_views", 1)) != A:
+                    raise ValueError(f"InferenceStep: the batch has tta_views = {points.get('tta_views', 1)}, the step was built for {A} views")
+                off = points.get("scene_off")
+                if torch.is_tensor(off) and off.numel() != B * A + 1:
+                    raise ValueError(f"InferenceStep: {off.numel() - 1} scenes, the step was built for {B} samples of {A} views")
+                tab = self._view_table(points.get("tta_params") if tta_params is None else tta_params, B * A)
+                coord = _coord_of(points.get("box_type_3d", "Depth"))
+                if self.coord is None and self._graph is None:
+                    self.coord, self.box_type_3d = coord, points.get("box_type_3d", "Depth")
+                if coord != self.coord:
+                    raise ValueError(f"InferenceStep: the batch is in {points.get('box_type_3d', 'Depth')!r} coordinates, the step merges "
+                                     f"its views in {self.box_type_3d!r} coordinates")
             self._buf.bind_packed(points, "InferenceStep:")
+            if A > 1:
+                self.tta_params.copy_(tab)
             n = B
         else:
             points = list(points)
-            n = len(points)
-            if not 1 <= n <= B:
-                raise ValueError(f"InferenceStep: {n} scenes, the step was built for 1 .. {B}")
-            self._buf.bind_scenes(self.model, points + [points[0]] * (B - n), "InferenceStep:")      # the last batch of a dataset: padded, gated away again
+            n, rest = divmod(len(points), A)
+            if rest or not 1 <= n <= B:
+                raise ValueError(f"InferenceStep: {len(points)} scenes, the step was built for 1 .. {B} samples" + (f" of {A} views" if A > 1 else ""))
+            if A > 1:
+                if tta_params is None:
+                    raise ValueError("InferenceStep: a list of views needs tta_params= (one row per view)")
+                tab = self._view_table(tta_params, n * A)
+            self._buf.bind_scenes(self.model, points + points[:A] * (B - n), "InferenceStep:")      # the last batch of a dataset: padded, gated away again
+            if A > 1:
+                self.tta_params[:n * A].copy_(tab)
+                if n < B:
+                    self.tta_params[n * A:].copy_(tab[:A].repeat(B - n, 1))
         self._n_live.fill_(n)
         return n
 
@@ -503,6 +564,13 @@ class InferenceStep:
             feat = m.stage_features(v)
             self.head_outs = m.pts_bbox_head(feat, None, fps)
             self.det = m.pts_bbox_head.get_bboxes_batched(self.head_outs, None)
+            if self.views > 1:
+                # the views of every sample merged where the tail left them: padded rows, device counts (u3d_tta_merge_padded)
+                if self.coord is None:
+                    raise RuntimeError("InferenceStep(views > 1): no coordinate code yet - pass box_type_3d= or capture from a packed dict")
+                self.view_det = self.det
+                self.det = nv.tta_merge_padded(self.view_det, self.tta_params, self.views, self.coord, m.pts_bbox_head.num_classes,
+                                               self.tta_nms_thr, self.tta_max_num)
             times_out = sb.fps_can_time_out(m, max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])))
             sb.validity_flag(m, self._caps, self._fps_err if times_out else None, self._buf.ingest_flag, self._flag)
             nv.det_gate(self.det, self._flag, self._n_live, self.valid)
@@ -510,14 +578,15 @@ class InferenceStep:
 
     def _drop_outputs(self):
         """Drop every reference to an eager iteration's outputs BEFORE capturing (static_batch.drop_decoder_outputs says why)."""
-        self.det = self.head_outs = None
+        self.det = self.view_det = self.head_outs = None
         self.model.pts_middle_encoder.last_level_counts = []
         sb.drop_decoder_outputs(self.model)
 
     def capture(self, batches, margin=1.25, warmup=3):
-        """Size the strided sparse levels from exact-size eager forwards over `batches` (each what run() takes; the largest count per
-        level x margin, rounded up to a multiple of 256 - static_batch.level_capacity), warm up, capture.  -> (counts, caps).  May be
-        called again, e.g. with a batch that overflowed added: the previous graph is dropped."""
+        """Size the strided sparse levels from exact-size eager forwards over `batches` (each what run() takes - with views > 1 the
+        expanded dict or a pair (list of n * A views, tta_params); the largest count per level x margin, rounded up to a multiple of
+        256 - static_batch.level_capacity), warm up, capture.  -> (counts, caps).  May be called again, e.g. with a batch that overflowed
+        added: the previous graph is dropped."""
         batches = list(batches)
         if not batches:
             raise ValueError("InferenceStep.capture: at least one sample batch")
@@ -529,7 +598,7 @@ class InferenceStep:
         enc = self.model.pts_middle_encoder
         seen = []
         for b in batches:
-            self._bind(b)
+            self._bind(*self._sample(b))
             off = self.pts["scene_off"].tolist()
             exact = dict(cat=self.pts["cat"][:off[-1]], scene_off=self.pts["scene_off"], lens=[off[i + 1] - off[i] for i in range(len(off) - 1)])
             with torch.no_grad(), self.inf.scope():       # the counts come from the encoder: no FPS, no head
@@ -545,26 +614,38 @@ class InferenceStep:
         return counts, list(self._caps)
 
     # ---- use --------------------------------------------------------------------------------------------------------------
-    def run(self, points):
+    @staticmethod
+    def _sample(batch):
+        """A sample batch of capture(): what run() takes, or the pair (list of views, tta_params) -> run()'s arguments."""
+        if isinstance(batch, tuple) and len(batch) == 2 and torch.is_tensor(batch[1]) and not torch.is_tensor(batch[0]):
+            return batch
+        return batch, None
+
+    def run(self, points, tta_params=None):
         """Load `points` and replay: -> the native.DetBatch whose tensors are the graph's static outputs (`det.valid` is `step.valid`,
         device int32 [1]: 1 = read it, 0 = every scene was emptied).  THE NEXT run() OVERWRITES THEM - copy what must outlive it.  No
         host read, no allocation outside the graph's pool and no synchronisation for a packed dict; a list costs the host-sized copy of
-        pack_points.  `step.head_outs` are the head's raw outputs of the same replay."""
+        pack_points.  `step.head_outs` are the head's raw outputs of the same replay.  views > 1: `det` holds one merged scene per
+        sample, `step.view_det` the per-view tail of the same replay; a list of views comes with tta_params= (one row per view)."""
         if self._graph is None:
             raise RuntimeError("InferenceStep.run: capture() first")
-        self._bind(points)
+        self._bind(points, tta_params)
         self._graph.replay()
         return self.det
 
-    def results(self, points, img_metas=None):
+    def results(self, points, img_metas=None, tta_params=None):
         """run() and the one read of the tail (and of `valid` with it) -> simple_test_batched's list of dicts on the host, one per
-        live scene.  An invalid replay is re-run through inf.simple_test_batched (eager, exact-size) and counted in `fallbacks`."""
-        det = self.run(points)
-        n = self.batch_size if isinstance(points, dict) else len(points)
+        live sample.  An invalid replay is re-run through inf.simple_test_batched - with views > 1 through inf.aug_test_batched -
+        (eager, exact-size) and counted in `fallbacks`."""
+        det = self.run(points, tta_params)
+        n = self.batch_size if isinstance(points, dict) else len(points) // self.views
         host, valid = det.cpu(), int(self.valid.cpu()[0])
         if valid:
             return [dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in host.to_list()[:n]]
         self.fallbacks += 1
+        if self.views > 1:
+            return self.inf.aug_test_batched(points if isinstance(points, dict) else list(points), tta_params=tta_params, views=self.views,
+                                             box_type_3d=self.box_type_3d, nms_thr=self.tta_nms_thr, max_num=self.tta_max_num)
         if isinstance(points, dict):
             from .datapath import unpack_batch
             points = unpack_batch({k: points[k] for k in ("points", "scene_off", "count") if k in points})[0]

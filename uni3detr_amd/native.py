@@ -2423,6 +2423,44 @@ def tta_merge(boxes, scores, labels, det_off, params, views, coord, num_classes,
     return out_b, out_s, out_l, out_c
 
 
+def tta_merge_padded(det, params, views, coord, num_classes, nms_thr=0.1, max_num=500, out=None):
+    """tta_merge behind the batched tail: det is the DetBatch of B*views scenes (scene-major, view-minor) as get_bboxes_batched leaves
+    it - padded [B*views, K, D] with DEVICE counts; params f32 [B*views, 9] the forward view table -> the merged DetBatch ([B, max_num,
+    D], rows past count[b] zero, off written).  Scene by scene bit-identical to tta_merge on the compacted rows.  No host read, no
+    synchronisation; with `out` (what an earlier call returned for the same shapes) no allocation either, so the call can be captured:
+    the workspace rides on the returned batch as `out.workspace`."""
+    V, K, dim = det.boxes.shape
+    dev = det.boxes.device
+    views, max_num = int(views), int(max_num)
+    if views < 1 or V % views:
+        raise U3DError(f"tta_merge_padded: {V} scenes are not a whole number of samples of {views} views")
+    if det.boxes.dtype != torch.float32 or det.scores.dtype != torch.float32 or det.labels.dtype != torch.int32 or det.count.dtype != torch.int32:
+        raise U3DError("tta_merge_padded takes float32 boxes / scores and int32 labels / counts")
+    if det.scores.shape != (V, K) or det.labels.shape != (V, K) or det.count.numel() != V:
+        raise U3DError("tta_merge_padded: boxes [V,K,D], scores / labels [V,K] and count [V] do not fit together")
+    if params.dtype != torch.float32 or tuple(params.shape) != (V, AUG_NPARAM) or params.device != dev:
+        raise U3DError(f"tta_merge_padded: params must be float32 [{V}, {AUG_NPARAM}] on {dev}")
+    B = V // views
+    wsb = int(lib().u3d_tta_merge_padded_workspace(B, views, K, dim, int(num_classes)))
+    if wsb <= 0 or max_num < 1 or max_num > DET_TAIL_MAX_K:
+        raise U3DError(f"tta_merge_padded: unsupported shape (B={B}, views={views}, K={K}, box_dim={dim}, num_classes={num_classes}, "
+                       f"max_num={max_num} of at most {DET_TAIL_MAX_K})")
+    if out is None:
+        out = DetBatch(torch.empty((B, max_num, dim), dtype=torch.float32, device=dev), torch.empty((B, max_num), dtype=torch.float32, device=dev),
+                       torch.empty((B, max_num), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                       torch.empty((B + 1,), dtype=torch.int32, device=dev))
+        out.workspace = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    ws = getattr(out, "workspace", None)
+    if tuple(out.boxes.shape) != (B, max_num, dim) or ws is None or ws.numel() < wsb or out.boxes.device != dev:
+        raise U3DError("tta_merge_padded: `out` was not made by a call of the same shapes")
+    # named locals: a copy that .contiguous() makes must stay alive until the launch
+    bx, sc, lb, ct, pr = det.boxes.contiguous(), det.scores.contiguous(), det.labels.contiguous(), det.count.contiguous(), params.contiguous()
+    _check(lib().u3d_tta_merge_padded(_ptr(bx), _ptr(sc), _ptr(lb), _ptr(ct), B, views, K, dim, _ptr(pr), int(coord), int(num_classes),
+                                      float(nms_thr), max_num, _ptr(ws), ws.numel(), _ptr(out.boxes), _ptr(out.scores), _ptr(out.labels),
+                                      _ptr(out.count), _ptr(out.off), _stream()), "tta_merge_padded")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # The batched inference tail (csrc/det_tail.hip)
 # --------------------------------------------------------------------------------------------------

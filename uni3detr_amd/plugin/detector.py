@@ -389,6 +389,59 @@ class Uni3DETR(nn.Module):
                                  self.pts_bbox_head.num_classes, nms_thr, max_num)
         return [{k: v.cpu() for k, v in r.items()} for r in merged]
 
+    @torch.no_grad()
+    def aug_test_batched(self, batch_or_points, img_metas=None, *, tta_params=None, views=None, box_type_3d=None, on_device=False,
+                         nms_thr=0.1, max_num=500):
+        """aug_test with the whole tail on the device: ONE batched extract_pts_feat + head forward over all B*A views,
+        get_bboxes_batched, then native.tta_merge_padded on the padded DetBatch as it is - the per-view counts never come to the host.
+        Input, one of
+          * the expanded packed dict a DevicePipeline with MultiScaleFlipAug3D returns (tta_views, tta_params, box_type_3d are its own;
+            splitting it into scenes reads its offsets once);
+          * points[a][b] / img_metas[a][b], aug_test's arguments (the view table is tta.view_params of the metas unless tta_params is given);
+          * a flat list of B*A scenes, scene-major and view-minor, with views=A and tta_params f32 [B*A, 9] (box_type_3d: 'Depth' /
+            'LiDAR', default 'Depth').
+        on_device=True returns the merged native.DetBatch ([B, max_num, D], rows past count[b] zero) with no host read of a result;
+        otherwise B dicts in simple_test's format from one copy per tensor.  The same detections as aug_test(batched_tail=True)."""
+        from ..tta import coord_of, view_params
+        from .. import native as nv
+        flat_m = None
+        if isinstance(batch_or_points, dict):
+            from ..datapath import unpack_batch
+            batch = batch_or_points
+            if "tta_views" not in batch or "tta_params" not in batch:
+                raise ValueError("aug_test_batched: the batch carries no tta_views / tta_params - run MultiScaleFlipAug3D in its pipeline")
+            A = int(batch["tta_views"]) if views is None else int(views)
+            tta_params = batch["tta_params"] if tta_params is None else tta_params
+            box_type_3d = batch.get("box_type_3d", "Depth") if box_type_3d is None else box_type_3d
+            flat_p = list(unpack_batch({k: batch[k] for k in ("points", "scene_off", "count") if k in batch})[0])
+        elif len(batch_or_points) and isinstance(batch_or_points[0], (list, tuple)):
+            points = batch_or_points
+            A, B = len(points), len(points[0])
+            assert img_metas is not None and len(img_metas) == A and all(len(p) == B and len(m) == B for p, m in zip(points, img_metas))
+            flat_p = [points[a][b] for b in range(B) for a in range(A)]           # scene-major, view-minor
+            flat_m = [img_metas[a][b] for b in range(B) for a in range(A)]
+            if box_type_3d is None:
+                box_type_3d = flat_m[0].get("box_type_3d", "Depth")
+        else:
+            flat_p = list(batch_or_points)
+            if views is None or tta_params is None:
+                raise ValueError("aug_test_batched: a flat list of scenes needs views= and tta_params=")
+            A = int(views)
+        if A < 1 or not flat_p or len(flat_p) % A:
+            raise ValueError(f"aug_test_batched: {len(flat_p)} scenes are not a whole number of samples of {A} views")
+        if tta_params is None:
+            tta_params = view_params(flat_m, flat_p[0].device)
+        if tuple(tta_params.shape) != (len(flat_p), nv.AUG_NPARAM):
+            raise ValueError(f"aug_test_batched: tta_params must be [{len(flat_p)}, {nv.AUG_NPARAM}], got {tuple(tta_params.shape)}")
+        pts_feat, fpsbpts = self.extract_pts_feat(flat_p)
+        outs = self.pts_bbox_head(pts_feat, flat_m, fpsbpts)
+        view_det = self.pts_bbox_head.get_bboxes_batched(outs, flat_m)
+        det = nv.tta_merge_padded(view_det, tta_params.float().contiguous(), A, coord_of(box_type_3d or "Depth"), self.pts_bbox_head.num_classes,
+                                  nms_thr, max_num)
+        if on_device:
+            return det
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in det.cpu().to_list()]
+
     # ------------------------------------------------------------------------------------------
     def pack_points(self, pts):
         return self._pack_points(pts)

@@ -8,7 +8,11 @@ loop of the reference's extra_tools/test.py -> single_gpu_test, without its per-
 
 Per batch: on_batch(i), step.run(batch), store.append(step.det, n_live=step.n_live, valid=step.valid) - for a packed dict no host read
 follows, the replays queue up behind each other.  After the loop the batches whose replay was invalid (store.invalid_batches(), one
-host read) are run again eagerly and exact-size and put into their places.  No aug_test.
+host read) are run again eagerly and exact-size and put into their places.
+
+Test-time augmentation: a step built with views=A > 1 takes the expanded dicts a BatchFeeder yields when its pipeline carries
+MultiScaleFlipAug3D (B * A scenes, tta_views, tta_params); the loop and the store count SAMPLES, the merged DetBatch of a replay is
+what goes into the store - build it with max_num = the step's tta_max_num - and the repair runs inf.aug_test_batched.
 
 Several ranks: ShardPlan deals the one-device loop's batches out round robin, every rank runs test_dataset
 on its share into its own store, and det_store.gather_stores merges the stores on the device, in dataset order, on every rank:
@@ -77,11 +81,25 @@ def _scenes(batch):
     return list(batch)
 
 
+def _views_of(batch, views):
+    """a batch of a step with views > 1 -> (the list of its views, their tta_params rows): run()'s list form"""
+    if isinstance(batch, dict):
+        return _scenes(batch), batch["tta_params"]
+    if isinstance(batch, tuple) and len(batch) == 2 and not hasattr(batch[0], "shape"):
+        return list(batch[0]), batch[1]
+    raise ValueError(f"test_dataset: with views = {views} a batch is the expanded packed dict or the pair (list of views, tta_params)")
+
+
 def test_dataset(step, batches, store, reload=None, on_batch=None, batch_ids=None):
     """step: a captured inference.InferenceStep; batches: any iterable of what step.run takes (a feeder.BatchFeeder yields packed dicts;
     a last dict with fewer scenes than the step's batch goes through run's list form, which pads and gates - that one batch costs a
     host read; a list holds 1 .. B scenes, as run() demands); store: a det_store.DetStore with room for the dataset - its
     scene count is read once before the loop, so that a store which already holds an earlier part works.
+    A step with views = A > 1 (test-time augmentation): a dict holds B * A scenes, view-minor, and counts (scenes // A) samples; a partial
+    last dict goes through the list form together with its tta_params rows; a list batch is the pair (list of n * A views, tta_params
+    [n * A, 9]).  The store receives one merged scene per sample, so it is built with max_num = the step's tta_max_num: a step whose
+    `det` is wider than store.max_num raises ValueError.  reload(i) returns the expanded dict or that pair; the repair runs
+    step.inf.aug_test_batched.
     on_batch(i): called before batch i runs, and again before its repair - the head draws random query points in every eval forward,
     so a caller who wants reproducible results seeds there.
     reload(i): returns the scenes of batch i again (a list of point tensors or a packed dict) for the repair of an invalid replay - the
@@ -91,19 +109,31 @@ def test_dataset(step, batches, store, reload=None, on_batch=None, batch_ids=Non
     in place of i, and the messages name that batch, so that a rank seeds and reloads by the batch's place in the dataset as the
     one-device loop does.  None: the loop's own count.  -> store."""
     gid = (lambda i: i) if batch_ids is None else (lambda i: batch_ids[i])
+    A = int(getattr(step, "views", 1))
     base = first = len(store)            # (a host read before anything is in flight) a store may already hold an earlier part
     starts = {}
     for i, batch in enumerate(batches):
+        tab = None
         if isinstance(batch, dict):
-            n = int(batch["scene_off"].numel()) - 1
+            n = (int(batch["scene_off"].numel()) - 1) // A
             if n < step.batch_size:
-                batch = _scenes(batch)
+                batch, tab = _views_of(batch, A) if A > 1 else (_scenes(batch), None)
+        elif A > 1:
+            batch, tab = _views_of(batch, A)
+            n = len(batch) // A
         else:
             batch = list(batch)
             n = len(batch)
         if on_batch is not None:
             on_batch(gid(i))
-        step.run(batch)
+        if tab is None:
+            step.run(batch)
+        else:
+            step.run(batch, tta_params=tab)
+        width, room = getattr(getattr(step.det, "boxes", None), "shape", None), getattr(store, "max_num", None)
+        if width is not None and room is not None and int(width[1]) > int(room):
+            raise ValueError(f"test_dataset: the step's detections are {int(width[1])} rows wide, the store was built for max_num = {room}"
+                             + (" - build it with max_num = the step's tta_max_num" if A > 1 else ""))
         store.append(step.det, n_live=step.n_live, valid=step.valid)
         starts[first] = (i, n)
         first += n
@@ -117,12 +147,24 @@ def test_dataset(step, batches, store, reload=None, on_batch=None, batch_ids=Non
         if reload is None:
             raise RuntimeError(f"test_dataset: the replay of batch {i} (scenes {scene} .. {scene + n - 1}) was invalid (a sparse level "
                                "over its capacity, an FPS time-out or a scene cut to point_capacity) and no reload= was given to run it again")
-        scenes = _scenes(reload(i))
-        if len(scenes) != n:
-            raise RuntimeError(f"test_dataset: reload({i}) returned {len(scenes)} scenes, batch {i} had {n}")
+        again = reload(i)
+        if A > 1:
+            scenes, tab = _views_of(again, A)
+            if len(scenes) != n * A:
+                raise RuntimeError(f"test_dataset: reload({i}) returned {len(scenes)} views = {len(scenes) / A:g} samples of {A} views, "
+                                   f"batch {i} had {n} samples")
+        else:
+            scenes = _scenes(again)
+            if len(scenes) != n:
+                raise RuntimeError(f"test_dataset: reload({i}) returned {len(scenes)} scenes, batch {i} had {n}")
         if on_batch is not None:
             on_batch(i)
-        store.put(scene, step.inf.simple_test_batched(None, scenes, on_device=True))
+        if A > 1:
+            det = step.inf.aug_test_batched(scenes, tta_params=tab, views=A, box_type_3d=step.box_type_3d, on_device=True,
+                                            nms_thr=step.tta_nms_thr, max_num=step.tta_max_num)
+        else:
+            det = step.inf.simple_test_batched(None, scenes, on_device=True)
+        store.put(scene, det)
         step.fallbacks += 1
     return store
 
