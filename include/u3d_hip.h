@@ -157,13 +157,30 @@ int32_t u3d_voxelize_hard_chunked(const float* points, const int32_t* scene_off,
  * Dynamic voxelization + DynamicSimpleVFE (ref: models/detectors/uni3detr.py:155-171; upstream mmcv Voxelization with
  * max_num_points=-1 and DynamicScatter(average_points=True)).
  *   u3d_voxelize_dynamic: per point (b, z, y, x) int32, or (b,-1,-1,-1) when out of range (same floor formula as hard mode).
+ *   n_total is an upper bound, as for u3d_voxelize_hard: rows at or past scene_off[B] (read on the device) are spare capacity, never
+ *   become points and get (-1,-1,-1,-1), which u3d_bitgrid_mark / u3d_bitgrid_rank skip; with scene_off[B] == n_total no such row exists.
  *   u3d_scatter_mean: feats[rank[i], :] = mean of points with that rank (rank < 0 skipped); sums f32 [V,nfeat] and
- *   counts int32 [V] must be zeroed by the caller; f32 atomics (as the upstream kernel), then an in-place divide.
+ *   counts int32 [V] must be zeroed by the caller; f32 atomics (as the upstream kernel), then an in-place divide: the bits of a
+ *   mean follow the order in which its points arrive.
+ *   u3d_scatter_mean_exact: the same mean and counts with bits that do NOT depend on that order - any permutation of the rows (with
+ *   their ranks) and any two calls give identical bytes.  Per (voxel, feature): e = exponent of the largest |v| (integer atomicMax on
+ *   the bit patterns), every v rounded once to the integer rint(v * 2^(shift - e)) and summed with 64-bit integer atomics (exact), the
+ *   sum scaled back and divided by the count in f64, rounded once to f32.  shift = min(40, 61 - ceil(log2(n_total))), from the host's
+ *   n_total (40 below 2^21 rows): n_total values below 2^(e+1) cannot overflow 63 bits.  Against the exact mean m of values v_i:
+ *   |mean - m| <= 2^-23 |m| + 2^-shift max|v_i|.  A voxel with one point returns that point's bits (-0 as +0), a row without points 0
+ *   and count 0; ranks < 0 or >= n_voxels are skipped.  mean f32 [V,nfeat] and counts int32 [V] are written in full, and neither
+ *   they nor the workspace (u3d_scatter_mean_exact_workspace(V, nfeat) bytes, 8-byte aligned) need zeroing.  Four launches, one thread
+ *   per (row, feature), no host read.  Non-finite values are out of contract: they are dropped or give any value, never a fault.
+ *   U3D_ERR_ARG: a null pointer (points / rank may be null when n_total == 0), n_total < 0, nfeat <= 0, n_voxels <= 0;
+ *   U3D_ERR_WORKSPACE: workspace_bytes below the query.  Both before any launch.
  * ---------------------------------------------------------------------------------------------- */
 int32_t u3d_voxelize_dynamic(const float* points, const int32_t* scene_off, int32_t batch, int32_t n_total, int32_t nfeat,
                              const float voxel_size[3], const float pc_range[6], int32_t* coors, u3d_stream s);
 int32_t u3d_scatter_mean(const float* points, const int32_t* rank, int32_t n_total, int32_t nfeat, float* sums,
                          int32_t* counts, int32_t n_voxels, u3d_stream s);
+int64_t u3d_scatter_mean_exact_workspace(int32_t n_voxels, int32_t nfeat);
+int32_t u3d_scatter_mean_exact(const float* points, const int32_t* rank, int32_t n_total, int32_t nfeat, float* mean,
+                               int32_t* counts, int32_t n_voxels, void* workspace, int64_t workspace_bytes, u3d_stream s);
 
 /* ------------------------------------------------------------------------------------------------
  * Sparse convolution as output-stationary implicit GEMM over the neighbour table

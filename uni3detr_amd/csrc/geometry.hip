@@ -1024,6 +1024,10 @@ __global__ void k_vox_dynamic(const float* __restrict__ pts, const int* __restri
                               int4* __restrict__ coors) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_total) return;
+  if (i >= scene_off[B]) {  // spare capacity behind the last scene: never a point, whatever the row holds
+    coors[i] = make_int4(-1, -1, -1, -1);
+    return;
+  }
   int b = 0;
   while (b + 1 < B && i >= scene_off[b + 1]) ++b;
   const float* p = pts + (long long)i * cfg.nfeat;
@@ -1076,6 +1080,102 @@ extern "C" int32_t u3d_scatter_mean(const float* points, const int32_t* rank, in
   U3D_REQUIRE(points && rank && sums && counts && nfeat > 0, U3D_ERR_ARG);
   if (n_total > 0) hipLaunchKernelGGL(k_scatter_accum, dim3(u3d_cdiv(n_total, 256)), dim3(256), 0, s, points, rank, n_total, nfeat, sums, counts);
   if (n_voxels > 0) hipLaunchKernelGGL(k_scatter_divide, dim3(u3d_cdiv((long long)n_voxels * nfeat, 256)), dim3(256), 0, s, sums, counts, n_voxels, nfeat);
+  U3D_CHECK_LAUNCH();
+  return U3D_OK;
+}
+
+// --------------------------------------------------------------------------------------------
+// The same mean, order-free: per (voxel, feature) a fixed-point sum under the exponent of the cell's largest |value|.
+//   pass 1  cell_max[r, f] <- max |v| as a bit pattern (integer atomicMax: order-free), counts[r] += 1
+//   pass 2  acc[r, f] += rint(v * 2^(shift - e)), e = exponent of cell_max[r, f]  (64-bit integer atomic add: exact, order-free)
+//   pass 3  mean[r, f] = f32(acc * 2^(e - shift) / count)                           (in f64: ONE rounding)
+// |v| < 2^(e+1) gives |rint(..)| <= 2^(shift+1); n_total of them stay below 2^62 with shift <= 61 - ceil(log2(n_total)).
+// One thread per (row, feature) in every pass: coalesced, no loop whose length follows a segment.
+// --------------------------------------------------------------------------------------------
+struct ScatterExactWs {
+  unsigned* cell_max;         // [V * nfeat] bits of the largest |v|
+  unsigned long long* acc;    // [V * nfeat] two's-complement fixed-point sums
+};
+static inline long long scatter_exact_cells(int n_voxels, int nfeat) { return (long long)n_voxels * nfeat; }
+static inline int64_t scatter_exact_bytes(int n_voxels, int nfeat) {
+  return scatter_exact_cells(n_voxels, nfeat) * (int64_t)(sizeof(unsigned long long) + sizeof(unsigned));
+}
+static inline int scatter_exact_shift(int n_total) {
+  int lg = 0;
+  while ((1ll << lg) < (long long)n_total) ++lg;  // ceil(log2(n_total)), 0 for n_total <= 1
+  return 61 - lg < 40 ? 61 - lg : 40;
+}
+// unbiased exponent of a cell's largest |v|; a subnormal maximum counts as 2^-126 (its values are then exact integers of 2^-149)
+__device__ __forceinline__ int scatter_exact_exp(unsigned max_bits) {
+  int e = (int)(max_bits >> 23);
+  return (e > 0 ? e : 1) - 127;
+}
+
+__global__ void k_scatter_exact_init(ScatterExactWs w, long long cells, int* __restrict__ counts, int n_voxels) {
+  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < cells) {
+    w.cell_max[t] = 0u;
+    w.acc[t] = 0ull;
+  }
+  if (t < n_voxels) counts[t] = 0;
+}
+__global__ void k_scatter_exact_max(const float* __restrict__ pts, const int* __restrict__ rank, long long n_elem, int nfeat,
+                                    int n_voxels, ScatterExactWs w, int* __restrict__ counts) {
+  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_elem) return;
+  long long i = t / nfeat;
+  int f = (int)(t - i * nfeat);
+  int r = rank[i];
+  if (r < 0 || r >= n_voxels) return;
+  atomicMax(&w.cell_max[(long long)r * nfeat + f], __float_as_uint(pts[t]) & 0x7fffffffu);
+  if (f == 0) atomicAdd(&counts[r], 1);
+}
+__global__ void k_scatter_exact_add(const float* __restrict__ pts, const int* __restrict__ rank, long long n_elem, int nfeat,
+                                    int n_voxels, int shift, ScatterExactWs w) {
+  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_elem) return;
+  long long i = t / nfeat;
+  int f = (int)(t - i * nfeat);
+  int r = rank[i];
+  if (r < 0 || r >= n_voxels) return;
+  long long cell = (long long)r * nfeat + f;
+  double q = ldexp((double)pts[t], shift - scatter_exact_exp(w.cell_max[cell]));  // exact: a power-of-two scale in f64
+  if (!(fabs(q) < 4611686018427387904.0)) return;                                 // non-finite input (out of contract): dropped
+  long long qi = __double2ll_rn(q);
+  if (qi != 0) atomicAdd(&w.acc[cell], (unsigned long long)qi);
+}
+__global__ void k_scatter_exact_mean(ScatterExactWs w, const int* __restrict__ counts, long long cells, int nfeat, int shift,
+                                     float* __restrict__ mean) {
+  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  int c = counts[t / nfeat];
+  double sum = ldexp((double)(long long)w.acc[t], scatter_exact_exp(w.cell_max[t]) - shift);
+  mean[t] = c > 0 ? (float)(sum / (double)c) : 0.f;
+}
+
+extern "C" int64_t u3d_scatter_mean_exact_workspace(int32_t n_voxels, int32_t nfeat) {
+  if (n_voxels <= 0 || nfeat <= 0) return 0;
+  return scatter_exact_bytes(n_voxels, nfeat);
+}
+
+extern "C" int32_t u3d_scatter_mean_exact(const float* points, const int32_t* rank, int32_t n_total, int32_t nfeat, float* mean,
+                                          int32_t* counts, int32_t n_voxels, void* workspace, int64_t workspace_bytes, u3d_stream s) {
+  U3D_REQUIRE(mean && counts && workspace && nfeat > 0 && n_voxels > 0 && n_total >= 0, U3D_ERR_ARG);
+  U3D_REQUIRE(n_total == 0 || (points && rank), U3D_ERR_ARG);
+  U3D_REQUIRE(((uintptr_t)workspace & 7) == 0, U3D_ERR_ARG);
+  U3D_REQUIRE(workspace_bytes >= scatter_exact_bytes(n_voxels, nfeat), U3D_ERR_WORKSPACE);
+  const long long cells = scatter_exact_cells(n_voxels, nfeat), n_elem = (long long)n_total * nfeat;
+  const int shift = scatter_exact_shift(n_total);
+  ScatterExactWs w;
+  w.acc = (unsigned long long*)workspace;  // the 8-byte array first: both stay aligned
+  w.cell_max = (unsigned*)(w.acc + cells);
+  const long long init = cells > n_voxels ? cells : n_voxels;
+  hipLaunchKernelGGL(k_scatter_exact_init, dim3(u3d_cdiv(init, 256)), dim3(256), 0, s, w, cells, counts, n_voxels);
+  if (n_total > 0) {
+    hipLaunchKernelGGL(k_scatter_exact_max, dim3(u3d_cdiv(n_elem, 256)), dim3(256), 0, s, points, rank, n_elem, nfeat, n_voxels, w, counts);
+    hipLaunchKernelGGL(k_scatter_exact_add, dim3(u3d_cdiv(n_elem, 256)), dim3(256), 0, s, points, rank, n_elem, nfeat, n_voxels, shift, w);
+  }
+  hipLaunchKernelGGL(k_scatter_exact_mean, dim3(u3d_cdiv(cells, 256)), dim3(256), 0, s, w, (const int*)counts, cells, nfeat, shift, mean);
   U3D_CHECK_LAUNCH();
   return U3D_OK;
 }

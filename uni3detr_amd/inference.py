@@ -46,6 +46,8 @@ measured faster than bf16 -, `fp8_skipped` the rest with the reason.  A forward 
 InferenceStep(inf, batch_size=B, point_capacity=P) replays the folded forward and the batched tail of an InferenceModel as one hipGraph
 over static, capacity-sized buffers, with a device-side validity gate (u3d_det_gate) and an eager fallback.  INTEGRATION.md O.  With
 views=A it captures test-time augmentation as well: B * A views forward, the multi-view merge on the padded tail.  INTEGRATION.md S.
+It serves dynamic voxelization (ScanNet-large, DynamicSimpleVFE) too: a capacity-sized voxel list and, inside scope(), order-free voxel
+means, so that a replay and its eager fallback compute the same bits.  INTEGRATION.md T.
 
 Numerics: not bit-identical to conv + u3d_bn_apply.  Folded: bf16(w * scale) once, output rounded once.  Unfolded: bf16(w), conv
 output rounded to bf16, y rounded.  Both are a few bf16 roundings of the same real number (tests/test_bn_fold_gpu.py holds the folded
@@ -367,9 +369,20 @@ class InferenceModel:
             raise RuntimeError("InferenceModel(dense_fp8=True): no activation scales yet - run calibrate(batches) or load_fp8_state() first")
         if not self._by_bn:
             raise RuntimeError("InferenceModel: the model was not on the device when it was wrapped; move it there and call refresh()")
-        # the head runs under bf16 autocast, as Uni3DETR.forward_pts_train runs it in this mode (the fused decoder takes bf16 rows)
-        with sp.fold_scope(self._by_bn), torch.autocast("cuda", dtype=torch.bfloat16):
-            yield self
+        # dynamic voxelization: order-free voxel means inside the scope, so that a captured replay, its eager fallback and a second
+        # replay of the same points compute the same bits (outside it the encoder keeps its f32 atomics)
+        vfe = getattr(self.model, "pts_voxel_encoder", None)
+        order_free = hasattr(vfe, "exact_mean")
+        prev = vfe.exact_mean if order_free else None
+        if order_free:
+            vfe.exact_mean = True
+        try:
+            # the head runs under bf16 autocast, as Uni3DETR.forward_pts_train runs it in this mode (the fused decoder takes bf16 rows)
+            with sp.fold_scope(self._by_bn), torch.autocast("cuda", dtype=torch.bfloat16):
+                yield self
+        finally:
+            if order_free:
+                vfe.exact_mean = prev
 
     @torch.no_grad()
     def _extract(self, points):
@@ -441,8 +454,13 @@ class InferenceStep:
     from then on: a later dict that disagrees is refused.  An invalid replay is re-run through inf.aug_test_batched.  views=1 is the
     step described above, with no view buffers and no further launches.
 
-    Limits: an InferenceModel on one device, hard voxelization, B and `views` fixed per step, all views of a sample in one batch.  An
-    empty live scene gives NaN queries."""
+    Dynamic voxelization (ScanNet-large: dynamic_voxelization=True with a DynamicSimpleVFE): the voxel list is a
+    level like the others - capture() sizes it from the same sample forwards (never above B * views * P rows) and returns its size in
+    front of `caps`, a list that overflows raises the same flag -, the spare rows of `cat` never become points (u3d_voxelize_dynamic)
+    and the voxel means are order-free inside inf.scope() (u3d_scatter_mean_exact), so a replay and its eager fallback agree.
+
+    Limits: an InferenceModel on one device, B and `views` fixed per step, all views of a sample in one batch.  An empty live scene
+    gives NaN queries."""
 
     def __init__(self, inf, batch_size, point_capacity, views=1, tta_nms_thr=0.1, tta_max_num=500, box_type_3d=None):
         A = int(views)
@@ -451,9 +469,11 @@ class InferenceStep:
         if not isinstance(inf, InferenceModel):
             raise TypeError(f"InferenceStep captures an InferenceModel, not {type(inf).__name__}: wrap the model first")
         model = inf.model
-        if getattr(model, "dynamic_voxelization", False):
-            raise NotImplementedError("InferenceStep serves hard voxelization only: DynamicSimpleVFE sizes its voxel list by a host read "
-                                      "in eval mode, and this model has dynamic_voxelization=True")
+        from .plugin.detector import DynamicSimpleVFE
+        self.dynamic = bool(getattr(model, "dynamic_voxelization", False))
+        if self.dynamic and not isinstance(getattr(model, "pts_voxel_encoder", None), DynamicSimpleVFE):
+            raise NotImplementedError("InferenceStep: this model has dynamic_voxelization=True and no DynamicSimpleVFE as its voxel encoder - "
+                                      "the capacity-sized voxel list of the dynamic route is that encoder's")
         B, P = int(batch_size), int(point_capacity)
         if B < 1:
             raise ValueError(f"InferenceStep(batch_size={batch_size}): at least one scene")
@@ -466,7 +486,9 @@ class InferenceStep:
             raise ValueError(f"InferenceStep(tta_max_num={tta_max_num}): 1 .. {nv.DET_TAIL_MAX_K}")
         self.box_type_3d = box_type_3d
         self.coord = None if box_type_3d is None else _coord_of(box_type_3d)        # views > 1: the merge's coordinate code
-        self.feat = int(model.pts_voxel_encoder.num_features)
+        # columns of a point row: the hard VFE names them; DynamicSimpleVFE averages whatever the middle encoder takes
+        self.feat = int(model.pts_middle_encoder.in_channels if self.dynamic else model.pts_voxel_encoder.num_features)
+        self._vox_cap = None                                      # dynamic voxelization: rows of the voxel list, sized by capture()
         self.fallbacks = 0
         self.pts = self.valid = self.det = self.head_outs = None
         self.view_det = self.tta_params = None                    # views > 1 only: the per-view tail of a replay, the static view table
@@ -549,10 +571,16 @@ class InferenceStep:
         m, enc = self.model, self.model.pts_middle_encoder
         prev = m.static_shapes, enc.level_capacities, m.fps_err
         m.static_shapes, enc.level_capacities, m.fps_err = True, self._caps, self._fps_err
+        vfe = m.pts_voxel_encoder if self.dynamic else None
+        if vfe is not None:             # dynamic voxelization: the voxel list capacity-sized too, its count left on the device
+            prev_vfe = vfe.capacity, vfe.static_eval
+            vfe.capacity, vfe.static_eval = self._vox_cap, True
         try:
             yield
         finally:
             m.static_shapes, enc.level_capacities, m.fps_err = prev
+            if vfe is not None:
+                vfe.capacity, vfe.static_eval = prev_vfe
 
     @torch.no_grad()
     def _forward(self):
@@ -571,7 +599,10 @@ class InferenceStep:
                 self.view_det = self.det
                 self.det = nv.tta_merge_padded(self.view_det, self.tta_params, self.views, self.coord, m.pts_bbox_head.num_classes,
                                                self.tta_nms_thr, self.tta_max_num)
-            times_out = sb.fps_can_time_out(m, max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])))
+            # the largest set the FPS can see: P points, or the hard voxelizer's limit (dynamic: its voxel-coordinate FPS runs over the
+            # per-point rows, and max_voxels is -1)
+            times_out = sb.fps_can_time_out(m, self.point_capacity if self.dynamic
+                                            else max(self.point_capacity, int(m.pts_voxel_layer.max_voxels[1])))
             sb.validity_flag(m, self._caps, self._fps_err if times_out else None, self._buf.ingest_flag, self._flag)
             nv.det_gate(self.det, self._flag, self._n_live, self.valid)
             self.det.valid = self.valid
@@ -580,6 +611,8 @@ class InferenceStep:
         """Drop every reference to an eager iteration's outputs BEFORE capturing (static_batch.drop_decoder_outputs says why)."""
         self.det = self.view_det = self.head_outs = None
         self.model.pts_middle_encoder.last_level_counts = []
+        if self.dynamic:
+            self.model.pts_voxel_encoder.last_count_dev = None
         sb.drop_decoder_outputs(self.model)
 
     def capture(self, batches, margin=1.25, warmup=3):
@@ -606,12 +639,15 @@ class InferenceStep:
             seen.append([int(c.item()) for c in enc.last_level_counts])
         counts = sb.max_level_counts(seen)
         self._caps = [sb.level_capacity(c, margin) for c in counts[1:]]
+        if self.dynamic:
+            # the voxel list (level 0) the same way; every voxel holds a point, so B * views * P rows always suffice
+            self._vox_cap = min(sb.level_capacity(counts[0], margin), self.batch_size * self.views * self.point_capacity)
         s = sb.warm_up(self._forward, warmup)            # static-shape eager warm-up on the capture stream
         self._drop_outputs()
         g = sb.capture_graph(self._forward, s)
         torch.cuda.synchronize()
         self._graph = g
-        return counts, list(self._caps)
+        return counts, ([self._vox_cap] if self.dynamic else []) + list(self._caps)
 
     # ---- use --------------------------------------------------------------------------------------------------------------
     @staticmethod

@@ -248,6 +248,22 @@ def scatter_mean(points, rank, n_voxels):
     return sums, counts
 
 
+def scatter_mean_exact(points, rank, n_voxels):
+    """scatter_mean with bits that do not depend on the order the points arrive in (u3d_scatter_mean_exact: fixed-point integer
+    sums): -> (mean f32 [n_voxels, F], counts int32 [n_voxels]).  Nothing is zeroed here, nothing is read back."""
+    n_total, nfeat = points.shape
+    dev = points.device
+    mean = torch.empty((n_voxels, nfeat), dtype=torch.float32, device=dev)
+    counts = torch.empty((n_voxels,), dtype=torch.int32, device=dev)
+    if n_voxels == 0:
+        return mean, counts
+    wsb = int(lib().u3d_scatter_mean_exact_workspace(n_voxels, nfeat))
+    ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=dev)           # 8-byte aligned
+    _check(lib().u3d_scatter_mean_exact(_ptr(points), _ptr(rank), n_total, nfeat, _ptr(mean), _ptr(counts), n_voxels, _ptr(ws), ws.numel() * 8,
+                                        _stream()), "scatter_mean_exact")
+    return mean, counts
+
+
 # --------------------------------------------------------------------------------------------------
 # sparse conv / BN / dense
 # --------------------------------------------------------------------------------------------------

@@ -36,7 +36,8 @@ class HardSimpleVFE(nn.Module):
 @VOXEL_ENCODERS.register_module()
 class DynamicSimpleVFE(nn.Module):
     """mean of the points of every occupied voxel; voxels come out in lexicographic (b,z,y,x) order like upstream's
-    DynamicScatter -> torch.unique(dim=0).  Linear BitGrid rank + f32 atomics on the device."""
+    DynamicScatter -> torch.unique(dim=0).  Linear BitGrid rank + f32 atomics on the device (exact_mean: fixed-point
+    integer sums instead, bits independent of the arrival order)."""
 
     def __init__(self, voxel_size=(0.2, 0.2, 4), point_cloud_range=(0, -40, -3, 70.4, 40, 1)):
         super().__init__()
@@ -46,6 +47,9 @@ class DynamicSimpleVFE(nn.Module):
         # stays on the device (last_count_dev); None: exact size, one host read (as upstream's torch.unique)
         self.capacity = None
         self.last_count_dev = None
+        # both off unless a caller turns them on for its own forward (InferenceStep._static, InferenceModel.scope):
+        self.static_eval = False        # the capacity-sized route in eval mode too (a plain model.eval() forward stays exact-size)
+        self.exact_mean = False         # order-free means (u3d_scatter_mean_exact) instead of f32 atomics: equal points, equal bits
 
     def grid_dims(self):
         vs, pr = self.voxel_size, self.point_cloud_range
@@ -62,15 +66,17 @@ class DynamicSimpleVFE(nn.Module):
         g.mark(coors)
         g.scan()
         self.last_count_dev = g.count_dev
-        if self.capacity is None or not self.training:
+        if self.capacity is None or not (self.training or self.static_eval):
             n_vox = int(g.count_dev.item())
         else:
             # no host read: capacity-sized list, ranks past it come back as -1 (their points are dropped; the step's capacity flag
-            # reports it and the update is held - TrainStep), rows past the count stay (-1, ...) and zero
+            # reports it and the update is held - TrainStep - or the replay gated away - InferenceStep), rows past the count stay
+            # (-1, ...) and zero
             n_vox = int(self.capacity)
             g.set_row_capacity(n_vox)
         rank = g.rank(coors)
-        feats, _ = nv.scatter_mean(features.float().contiguous(), rank, n_vox)
+        mean = nv.scatter_mean_exact if self.exact_mean else nv.scatter_mean
+        feats, _ = mean(features.float().contiguous(), rank, n_vox)
         return feats, g.coords(n_vox)
 
 
