@@ -892,6 +892,35 @@ int32_t u3d_adamw_step(float* param, const float* grad, float* exp_avg, float* e
                        float beta2, float eps, float weight_decay, float max_norm, float* state, void* workspace,
                        int64_t workspace_bytes, u3d_stream s);
 
+/* ------------------------------------------------------------------------------------------------
+ * Device-resident step log (csrc/step_log.hip; upstream reads every loss on the host per iteration: mmcv's TextLoggerHook behind
+ * extra_tools/train.py).  A ring of `capacity` rows of U3D_STEP_LOG_FIXED + n_terms 32-bit columns plus one int64 cursor, both in
+ * device memory and zero-initialised by the caller.  The cursor counts the rows appended so far; row k lives in slot k % capacity.
+ * Columns: [0] step number = the cursor before the append (int32 bits), [1] outcome (int32 bits) in the coding of acc_state[5] - 0
+ * accumulated, 1 applied, 2 dropped, 3 held; without acc_state: 3 if opt_state[11] > 0, else 1 -, [2] total loss, [3] gradient norm
+ * (acc_state[6], without acc_state opt_state[4]), [4] clip coefficient opt_state[1], [5] lr opt_state[5], [6] beta1 opt_state[6],
+ * [7] 0 (reserved), [8 + i] *terms[i].  Floats are stored as their bits.
+ * u3d_step_log_bytes: bytes of the row ring (0 for capacity <= 0 or n_terms outside [0, U3D_STEP_LOG_MAX_TERMS]).
+ * u3d_step_log_append: terms is a HOST array of n_terms device pointers to one f32 each (they travel as kernel arguments: a captured
+ *   launch keeps them); total one device f32; opt_state / acc_state (nullable) the vectors of u3d_adamw_step_hold / _accum, read
+ *   AFTER that call on the same stream.  One launch of one workgroup: reads the cursor, writes the row, advances the cursor.  No host
+ *   read, no allocation, no atomics, capturable; the only writer of rows and cursor.
+ * u3d_step_log_window: statistics of the latest n = min(last, cursor, capacity) rows taken in ascending step order.  out f32
+ *   [U3D_STEP_LOG_FIXED + n_terms][4] = (mean, min, max, rows used) per column, zeros for columns 0 and 1 and wherever no row is used.
+ *   A held row (outcome 3) is used by no column, columns 3 and 4 use applied rows (outcome 1) only, a NaN / Inf value is skipped.  The
+ *   mean is a float64 sum in that order, divided and rounded once to f32.  counts int32 [4] = (n, held rows, dropped rows, non-finite
+ *   totals among the rows not held).  One workgroup per column, no atomics: two calls give the same bytes.
+ * U3D_ERR_ARG: a null pointer (acc_state excepted), capacity <= 0, n_terms outside [0, U3D_STEP_LOG_MAX_TERMS], last < 0; nothing is
+ * launched or written then.
+ * ---------------------------------------------------------------------------------------------- */
+#define U3D_STEP_LOG_FIXED 8
+#define U3D_STEP_LOG_MAX_TERMS 64
+int64_t u3d_step_log_bytes(int64_t capacity, int32_t n_terms);
+int32_t u3d_step_log_append(const float* const* terms, int32_t n_terms, const float* total, const float* opt_state,
+                            const float* acc_state, void* rows, int64_t* cursor, int64_t capacity, u3d_stream s);
+int32_t u3d_step_log_window(const void* rows, const int64_t* cursor, int64_t capacity, int32_t n_terms, int64_t last, float* out,
+                            int32_t* counts, u3d_stream s);
+
 /* bf16 shadows of the flat f32 parameter buffer, refreshed once per training step (bf16 mode; upstream has no counterpart: its
  * fp32 run reads the parameters directly).  u3d_cast_bf16: dst[i] = bf16(src[i]) (round to nearest even), 16-byte aligned pointers.
  * u3d_permute_bf16_batched: for every descriptor, dst[dst_off + (k*rows + r)*cols + c] = src[src_off + k*stride_k + r*stride_r +

@@ -83,10 +83,11 @@ def load_checkpoint(model, checkpoint, map_location="cpu", strict=False, trusted
     return ck
 
 
-def save_checkpoint(model, path, meta=None, optimizer_state=None, to_spconv2=False):
+def save_checkpoint(model, path, meta=None, optimizer_state=None, to_spconv2=False, extra=None):
     """{'meta', 'state_dict' [, 'optimizer']} as the reference's runner writes it; to_spconv2 permutes the sparse conv weights to the
     spconv 2.x layout.  optimizer_state: TrainStep.optimizer_state_dict() (flat AdamW moments + step count) for `resume_from`;
-    TrainStep.load_optimizer_state_dict(ck['optimizer']) puts it back."""
+    TrainStep.load_optimizer_state_dict(ck['optimizer']) puts it back.  extra: further top-level entries (training.fit: step_log) -
+    tensors and plain containers only, or the tensors-only unpickler refuses the file."""
     sd = collections.OrderedDict()
     for k, v in model.state_dict().items():
         v = v.detach().cpu()
@@ -96,5 +97,9 @@ def save_checkpoint(model, path, meta=None, optimizer_state=None, to_spconv2=Fal
     ck = {"meta": dict(meta or {}), "state_dict": sd}
     if optimizer_state is not None:
         ck["optimizer"] = optimizer_state
+    for k, v in (extra or {}).items():
+        if k in ck:
+            raise ValueError(f"save_checkpoint: extra entry {k!r} would replace the checkpoint's own")
+        ck[k] = v
     torch.save(ck, path)
     return ck

@@ -1710,6 +1710,31 @@ def capacity_flag(counts, caps, flag):
            "capacity_flag")
 
 
+def step_log_bytes(capacity, n_terms):
+    """Bytes of a step log's row ring (u3d_step_log_bytes; 0 = refused)."""
+    return int(lib().u3d_step_log_bytes(int(capacity), int(n_terms)))
+
+
+def step_log_append(terms, total, opt_state, acc_state, rows, cursor):
+    """One row into the step-log ring `rows` (int32 [capacity, U3D_STEP_LOG_FIXED + len(terms)]) at `cursor` (int64 [1]), on the current
+    stream, capturable (u3d_step_log_append).  terms: list of device f32 scalars, total: a device f32 scalar, opt_state / acc_state
+    (or None): the vectors of adamw_step_state / adamw_step_accum."""
+    assert rows.dtype == torch.int32 and cursor.dtype == torch.int64 and rows.shape[1] == _K["U3D_STEP_LOG_FIXED"] + len(terms)
+    assert total.dtype == torch.float32 and all(t.dtype == torch.float32 for t in terms)
+    _check(lib().u3d_step_log_append(_ptr_array(terms) if terms else None, len(terms), _ptr(total), _ptr(opt_state), _ptr(acc_state),
+                                     _ptr(rows), _ptr(cursor), rows.shape[0], _stream()), "step_log_append")
+
+
+def step_log_window(rows, cursor, last, out, counts):
+    """out f32 [columns, 4] = (mean, min, max, rows used) and counts int32 [4] = (rows seen, held, dropped, non-finite totals) of the
+    latest `last` rows of a step log (u3d_step_log_window); stream-ordered, no host read."""
+    n_terms = rows.shape[1] - _K["U3D_STEP_LOG_FIXED"]
+    assert rows.dtype == torch.int32 and out.dtype == torch.float32 and counts.dtype == torch.int32
+    assert out.numel() >= 4 * rows.shape[1] and counts.numel() >= 4
+    _check(lib().u3d_step_log_window(_ptr(rows), _ptr(cursor), rows.shape[0], n_terms, int(last), _ptr(out), _ptr(counts), _stream()),
+           "step_log_window")
+
+
 def tap_gather_sum(p, nbr, n_dev, n, c, kvol, addend=None):
     """din[i] = sum_k p[nbr[k][i], k*c:(k+1)*c] (+ addend[i]) (f32 accumulate); p: [n_out, kvol*c]."""
     out = torch.empty((n, c), dtype=p.dtype, device=p.device)

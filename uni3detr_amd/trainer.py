@@ -84,7 +84,7 @@ class TrainStep:
     def __init__(self, model, points, gt_bboxes_3d, gt_labels_3d, lr=1e-4, weight_decay=0.01, max_norm=10.0, graph=True,
                  capacity_margin=1.25, flat_update=True, overlap_reduce=False, betas=(0.9, 0.999), eps=1e-8, gt_capacity=64,
                  check_every=50, pg_hooks=None, fps_graph=None, grad_comm_dtype=torch.float32, reduce_buckets=None, point_capacity=None,
-                 accum_steps=1, skip_nonfinite=False, ema_decay=None):
+                 accum_steps=1, skip_nonfinite=False, ema_decay=None, log=None):
         """pg_hooks: (teardown, setup) callables that destroy / re-create the default process group; needed only for a collective
         re-capture after a capacity overflow on a multi-rank run (bench.py passes them).
         point_capacity: None - the static point buffer has exactly the initial batch's layout (set_batch takes that layout only).  An
@@ -94,7 +94,11 @@ class TrainStep:
         INTEGRATION.md M): step() is then a MICRO-step, an update is applied every `accum_steps`-th one that was not held, with the
         window's mean gradient; a window whose mean gradient has a NaN / Inf norm is dropped on the device (that entry always does so:
         skip_nonfinite=True asks for it alone); ema_decay=d in (0, 1) keeps EMA weights (ema_state_dict / ema_scope).  Counters:
-        applied_updates(), nonfinite_skips(), window_fill().  With the defaults nothing of this is allocated or launched."""
+        applied_updates(), nonfinite_skips(), window_fill().  With the defaults nothing of this is allocated or launched.
+        log: a step_log.StepLog (flat_update=True) - the update stage then ends with one u3d_step_log_append (eager or captured, no host
+        read): outcome, total loss, gradient norm, clip coefficient, lr, beta1 and every loss term of this step, in the order of the
+        head's loss dict, which the first step fixes as the log's columns.  capture() / recapture() take their
+        measuring and warm-up steps back out of the log (keep_state), so the ring and the cursor survive them."""
         accum_steps = int(accum_steps)
         if accum_steps < 1:
             raise ValueError(f"TrainStep(accum_steps={accum_steps}): at least 1 micro-step per update")
@@ -107,6 +111,9 @@ class TrainStep:
             raise NotImplementedError("TrainStep(accum_steps=... / skip_nonfinite=... / ema_decay=...) needs flat_update=True: the window, "
                                       "the non-finite skip and the EMA weights are kept by the device-side flat AdamW step")
         self.acc = self.ema = self.acc_state = None
+        if log is not None and not flat_update:
+            raise NotImplementedError("TrainStep(log=...) needs flat_update=True: the log reads the device-side state of the flat AdamW step")
+        self.log = log
         if point_capacity is not None:
             point_capacity = int(point_capacity)
             if getattr(model, "dynamic_voxelization", False):
@@ -552,13 +559,24 @@ class TrainStep:
         if self.accum:
             nv.adamw_step_accum(self.flat_param, self.flat_grad, self.acc, self.exp_avg, self.exp_avg_sq, self.opt_state, self.acc_state,
                                 ema=self.ema, skip=self._skip, workspace=self._opt_ws, hold=None if self._msg is None else self._msg[-1:])
+            self._log_append()
             return
         if self.flat_update:
             nv.adamw_step_state(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.opt_state, self._skip, self._opt_ws,
                                  hold=None if self._msg is None else self._msg[-1:])
+            self._log_append()
             return
         torch.nn.utils.clip_grad_norm_(self.params, self.max_norm, foreach=True)
         self.opt.step()
+
+    def _log_append(self):
+        """The step's row into the device-side log: the loss terms and the total the backward stage left on the device, the state the
+        update just wrote.  One launch; inside a capture the pointers travel with it."""
+        if self.log is None:
+            return
+        terms = {k: (v if v.dtype == torch.float32 else v.float()) for k, v in self._losses.items()}
+        total = self.loss if self.loss.dtype == torch.float32 else self.loss.float()
+        self.log.append(terms, total, self.opt_state, self.acc_state)
 
     def _reset_opt_state(self):
         if self.flat_update:
@@ -647,6 +665,8 @@ class TrainStep:
     def snapshot_full(self):
         """Model state + optimizer state (moments, step count); restore_full() puts all of it back in place."""
         snap = dict(model=self.snapshot())
+        if self.log is not None:
+            snap["log"] = self.log.snapshot()
         if self.flat_update:
             snap["flat"] = {k: t.clone() for k, t in self._flat_state()}
         else:       # torch.optim.AdamW: moments and step counters of every parameter that has state already
@@ -658,6 +678,8 @@ class TrainStep:
         with torch.no_grad():
             for t, s_ in zip(list(self.model.parameters()) + list(self.model.buffers()), snap["model"]):
                 t.copy_(s_)
+            if self.log is not None and "log" in snap:
+                self.log.restore(snap["log"])
             if self.flat_update:
                 for k, t in self._flat_state():
                     t.copy_(snap["flat"][k])
